@@ -17,11 +17,17 @@ frame*: with N > 1 ranks every rank runs the workload on its own frame (frame-le
 frame cannot be split without halo exchange over the ~348-px receptive radius) -- weak scaling, no data-path
 collective.  chop* / chain*: ONE shared frame, its tile list sharded over the ranks, raw HR tiles sent to rank 0
 over RCCL and blended there (innfer_amd/parallel.py) -- strong scaling.
-Whatever the headline workload, the line also carries `tile_sharded`: BASELINE config 4 (chain4k) timed the same
+With --full, whatever the headline workload, the line also carries `tile_sharded`: BASELINE config 4 (chain4k) timed the same
 way (barrier + synchronise on both sides, max over ranks) on the SAME ranks, with the exchange bytes / ms of one
 profiled pass -- the north_star's "tiles partition across the GPUs, reassembled with an RCCL gather".
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0: metric, value (MPix/s), unit, higher_is_better, dtype, steps, warmup and ms_per_step (wall ms of
+one timed step).  A plain run does only that: set up, warm up, time exactly --steps steps, write the outputs (--dump-outputs DIR), print.
+--dump-outputs DIR: after the timed steps, rank 0 writes what its last step returned to DIR as .npy files -- `output_sample` (float32): a
+fixed, seeded sample of the output's elements (torch.randint, seed 0, sorted; the whole flattened output when it is small enough), and
+`output_stats`: float64 [channels, 4] of sum, sum of squares, min, max per output channel over the whole output.  Inputs and weights are
+seeded, so two builds given the same arguments can be compared file for file.
+--full adds everything else the line carries (each part can still be switched off by its --no-* / --sharded-steps option):
   roofline     : dominant kernel (by summed time) -- algorithmic FLOPs and bytes per launch / its average launch
                  duration, from HIP events around every launch of one forward; BOTH roofs per kernel, `bound` = the larger floor
   cpu_baseline : the oracle (torch fp32 restatement of the reference) timed on the host cores on a
@@ -30,6 +36,7 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
   unet64       : BASELINE config 5 (pix2pix UNet_256 on 64x3x256x256), N == 1 only
   pan540       : PAN 4x on a 1x3x540x960 frame (north_star's third conv stack), N == 1 only (+ pan_chop1080: the CLI's tiled shape; pan540_fp32: the -no_fp16 mode)
   srresnet1080 : SRResNet-16 4x on the 1080p frame (north_star's second conv stack), N == 1 only
+  tile_sharded : BASELINE config 4 on the same ranks (above)
 """
 import argparse
 import ctypes as C
@@ -643,6 +650,33 @@ def timed_steps(step, steps, warmup, world, sync, barrier, max_over_ranks):
     return max_over_ranks(wall)
 
 
+DUMP_SAMPLE = 8 << 20                               # float32 elements of output_sample.npy: 32 MB
+
+
+def dump_outputs(y, outdir, seed=0):
+    """--dump-outputs: the output of the last timed step as DIR/output_sample.npy (float32: DUMP_SAMPLE elements at sorted indices drawn by
+    torch.randint from a CPU generator seeded with `seed`; the whole flattened output when it has no more) and DIR/output_stats.npy (float64
+    [C, 4]: sum, sum of squares, min, max of each output channel over the whole output)."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    flat = y.detach().reshape(-1)
+    n = flat.numel()
+    if n <= DUMP_SAMPLE:
+        sample = flat.float().cpu()
+    else:
+        idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(seed)).sort().values
+        sample = flat[idx.to(flat.device)].float().cpu()
+    np.save(os.path.join(outdir, "output_sample.npy"), sample.numpy())
+    stats = []
+    for c in range(y.shape[1]):
+        yc = y[:, c].double()
+        stats.append([yc.sum().item(), (yc * yc).sum().item(), yc.min().item(), yc.max().item()])
+        del yc
+    np.save(os.path.join(outdir, "output_stats.npy"), np.asarray(stats, dtype=np.float64))
+    log(f"outputs of the last step ({tuple(y.shape)} {y.dtype}) -> {outdir}: {min(n, DUMP_SAMPLE)} sampled elements + per-channel stats")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -651,24 +685,30 @@ def main():
     ap.add_argument("--workload", default="frame1080", choices=WORKLOADS)
     ap.add_argument("--band-rows", type=int, default=0)
     ap.add_argument("--tile-batch", type=int, default=0, help="chop workloads: tiles per network launch (0 = innfer_amd.parallel.tile_batches: evenly sized launches of <= 272 tiles)")
-    ap.add_argument("--sharded-steps", type=int, default=-1, help="timed passes of the tile_sharded (chain4k) measurement; 0 = skip; default 2 on one GPU, 5 on N > 1 "
-                    "(the strong-scaling table of the first multi-GPU run comes from these objects: VERDICT r4 item 6a)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: roofline + power probe, tile_sharded, chop8k, unet64, pan540, srresnet1080 and "
+                    "cpu_baseline (off by default: a plain run sets up, warms up, times --steps steps, dumps its outputs and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0) to DIR/<name>.npy: a seeded sample "
+                    "and per-channel statistics of the output, float32 / float64, well under 64 MB")
+    ap.add_argument("--sharded-steps", type=int, default=-1, help="with --full: timed passes of the tile_sharded (chain4k) measurement; 0 = skip; default 2 on one GPU, "
+                    "5 on N > 1 (the strong-scaling table of the first multi-GPU run comes from these objects: VERDICT r4 item 6a)")
     ap.add_argument("--fp32", action="store_true", help="frame workloads: a float32 frame = the fp32-accurate engine (the reference's -no_fp16 mode); no roofline object")
     ap.add_argument("--no-hr-chain", action="store_true", help="A/B: the last up-conv and HR_conv0 + conv_last as two launches (innfer_net_set_hr_chain 0)")
     ap.add_argument("--no-fused-tail", action="store_true", help="A/B: HR_conv0 and conv_last as two launches (innfer_net_set_fused_tail 0)")
     ap.add_argument("--no-upconv-phases", action="store_true", help="A/B: the up-convs as nine taps on the HR grid (innfer_net_set_upconv_phases 0)")
     ap.add_argument("--upconv-phase-visits", action="store_true", help="A/B: the phase up-convs with one phase per visit of a tile (innfer_net_set_upconv_phases 2; default: all four phases in one visit)")
     ap.add_argument("--residual-lds", type=int, default=1, choices=[0, 1, 2], help="A/B: innfer_net_set_residual_lds -- the dense block's residual from the conv's own LDS stages: 0 never, 1 the RRDB-end blocks (default), 2 every block")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the chop8k (BASELINE config 3) and unet64 (config 5) objects of the line")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-power-probe", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline object")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the chop8k (BASELINE config 3), unet64 (config 5), pan540 and srresnet1080 objects of the line")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline object (and the power probe)")
+    ap.add_argument("--no-power-probe", action="store_true", help="with --full: skip the power probe of the roofline object")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_child:
         return cpu_baseline_child()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return spawn_ranks(args, sys.argv[1:])
 
@@ -679,6 +719,9 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     if args.sharded_steps < 0:
         args.sharded_steps = 5 if world > 1 else 2
+    if not args.full:                               # a plain run: the headline and nothing else
+        args.no_roofline = args.no_power_probe = args.no_extras = args.no_cpu_baseline = True
+        args.sharded_steps = 0
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if world != args.gpus:
         log(f"--gpus {args.gpus} but the launcher started {world} rank(s): reporting n_gpus = {world}")
@@ -786,18 +829,24 @@ def main():
 
     log('warmup + timed region')
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    n_done = [0]
+    n_done, last = [0], [None]
 
     def step_ev():                                  # HIP events around the K timed steps only (torch's current stream = the launch stream)
         if n_done[0] == args.warmup:
             e0.record()
         n_done[0] += 1
-        return step()
+        y = step()
+        if n_done[0] > args.warmup:                 # a timed step's output: the same reference timed_steps holds, no extra memory
+            last[0] = y
+        return y
     wall = timed_steps(step_ev, args.steps, args.warmup, world, sync, barrier, max_over_ranks)
     e1.record()
     sync()
     log(f'timed {args.steps} steps in {wall:.3f} s')
     ev_ms = e0.elapsed_time(e1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last[0], args.dump_outputs)
+    last[0] = None
 
     line = None
     if rank == 0:

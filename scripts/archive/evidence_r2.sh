@@ -7,7 +7,7 @@ OUT=$ROOT/gpurun_out/r2/evidence
 mkdir -p $OUT
 cd $ROOT
 # 1. headline bench (BASELINE config 2) with roofline, power probe, tile_sharded (config 4) and cpu baseline
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_frame1080.json 2> $OUT/bench_frame1080.err
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_frame1080.json 2> $OUT/bench_frame1080.err
 # 2. rocprofv3 kernel stats + FETCH / WRITE passes of the same workload
 bash scripts/profile.sh r2_frame > $OUT/profile_frame.txt 2>&1
 cp gpurun_out/prof_r2_frame/traffic.json $OUT/traffic.json 2>/dev/null

@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/r4/evidence
 mkdir -p $OUT
 cd $ROOT
 # 1. the driver's command
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_frame1080.json 2> $OUT/bench_frame1080_per_layer.txt
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_frame1080.json 2> $OUT/bench_frame1080_per_layer.txt
 # 2. rocprofv3 kernel stats + FETCH / WRITE passes of the headline workload
 bash scripts/profile.sh r4_frame --no-extras > $OUT/profile_frame.txt 2>&1
 cp gpurun_out/prof_r4_frame/traffic.json $OUT/traffic.json 2>/dev/null

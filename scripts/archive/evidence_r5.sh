@@ -6,14 +6,14 @@ OUT=$ROOT/gpurun_out/r5/evidence
 mkdir -p $OUT
 cd $ROOT
 # 1. the driver's command
-python3 bench.py --steps 20 --warmup 5 > $OUT/bench_frame1080.json 2> $OUT/bench_frame1080_per_layer.txt
+python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_frame1080.json 2> $OUT/bench_frame1080_per_layer.txt
 # 2. cumulative same-box A/B: the round-4 library (build/libinnfer_amd_r4.so, kept from the round's first minute) against this round's, interleaved, driver-form frame
 #    (VERDICT r4 weak 8).  The round-4 Python shells do not exist any more: both libraries run under this round's host code (the RRDB path's host code is unchanged).
 if [ -f build/libinnfer_amd_r4.so ]; then
   cp build/libinnfer_amd_r4.so innfer_amd/lib/libinnfer_amd_r4.so
   for rep in 1 2 3; do
     for LIB in libinnfer_amd_r4.so libinnfer_amd.so; do
-      INNFER_LIB=$PWD/innfer_amd/lib/$LIB INNFER_ABI_ANY=1 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-power-probe --no-extras --sharded-steps 0 2>/dev/null | tail -1 | \
+      INNFER_LIB=$PWD/innfer_amd/lib/$LIB INNFER_ABI_ANY=1 python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-power-probe --no-extras --sharded-steps 0 2>/dev/null | tail -1 | \
         python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print('$LIB', d['ms_per_step'], d['value'], {k.replace('conv3x3_pc',''):round(v['avg_ms'],4) for k,v in d['roofline']['per_kernel'].items()})"
     done
   done > $OUT/ab_r4_vs_r5.txt 2>&1

@@ -4,8 +4,8 @@
 TAG=$1; FLAG=$2; REPS=${3:-2}
 OUT=gpurun_out/r4_$TAG; mkdir -p $OUT
 for i in $(seq 1 $REPS); do
-  python3 bench.py --steps 20 --warmup 5 --no-extras --sharded-steps 0 --no-cpu-baseline --no-power-probe > $OUT/a$i.json 2> $OUT/a$i.err
-  python3 bench.py --steps 20 --warmup 5 --no-extras --sharded-steps 0 --no-cpu-baseline --no-power-probe $FLAG > $OUT/b$i.json 2> $OUT/b$i.err
+  python3 bench.py --full --steps 20 --warmup 5 --no-extras --sharded-steps 0 --no-cpu-baseline --no-power-probe > $OUT/a$i.json 2> $OUT/a$i.err
+  python3 bench.py --full --steps 20 --warmup 5 --no-extras --sharded-steps 0 --no-cpu-baseline --no-power-probe $FLAG > $OUT/b$i.json 2> $OUT/b$i.err
 done
 python3 - "$OUT" "$FLAG" $REPS <<'PY'
 import json, sys

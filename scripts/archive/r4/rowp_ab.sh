@@ -2,7 +2,7 @@
 # A/B of the plane row order of the 64-output layers (shipped) against the lane-contiguous order (make ab_rowp0), interleaved on one box
 for i in 1 2 3; do
   for lib in "" innfer_amd/lib/libinnfer_amd_rowp0.so; do
-    INNFER_LIB=$lib python3 bench.py --steps 10 --warmup 4 --no-extras --no-cpu-baseline --sharded-steps 0 --no-power-probe 2>/dev/null | python3 -c "
+    INNFER_LIB=$lib python3 bench.py --full --steps 10 --warmup 4 --no-extras --no-cpu-baseline --sharded-steps 0 --no-power-probe 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1])
 pk=d.get('per_kernel') or d['roofline'].get('per_kernel')

@@ -2,7 +2,7 @@
 # A/B of the frame with the phase up-convs as one visit per tile (default) and as one phase per visit (round 3's form), interleaved, shipped library
 for i in 1 2 3; do
   for f in "" "--upconv-phase-visits"; do
-    python3 bench.py --steps 10 --warmup 4 --no-extras --no-cpu-baseline --sharded-steps 0 --no-power-probe $f 2>/dev/null | python3 -c "
+    python3 bench.py --full --steps 10 --warmup 4 --no-extras --no-cpu-baseline --sharded-steps 0 --no-power-probe $f 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1])
 pk=d.get('per_kernel') or d['roofline'].get('per_kernel')

@@ -16,11 +16,11 @@ step() {          # step <name> <command...>: stdout -> $OUT/<name>.txt, stderr 
 }
 cd "$ROOT"
 # 1. the driver-form line (headline + every side object)
-step bench_frame1080 python3 bench.py
+step bench_frame1080 python3 bench.py --full
 # 2. same-box A/B of the chained HR tail: on / off / on / off, headline only
 for i in 1 2; do
-    step ab_chain_on_$i python3 bench.py --no-extras --sharded-steps 0 --steps 10 --no-cpu-baseline
-    step ab_chain_off_$i python3 bench.py --no-extras --sharded-steps 0 --steps 10 --no-cpu-baseline --no-hr-chain
+    step ab_chain_on_$i python3 bench.py --full --no-extras --sharded-steps 0 --steps 10 --no-cpu-baseline
+    step ab_chain_off_$i python3 bench.py --full --no-extras --sharded-steps 0 --steps 10 --no-cpu-baseline --no-hr-chain
 done
 # 3. rocprofv3 kernel statistics + FETCH_SIZE / WRITE_SIZE passes of the frame (scripts/profile.sh -> gpurun_out/prof_r6/summary.txt, traffic.json)
 step profile_frame bash scripts/profile.sh r6 --no-extras --no-power-probe

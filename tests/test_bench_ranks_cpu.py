@@ -50,6 +50,11 @@ def test_launcher_env_wins_over_the_flag():
     assert not [l for l in outs[1][0].splitlines() if l.startswith("{")]      # only rank 0 prints the line (gloo itself chats on stdout)
 
 
+def test_steps_must_be_positive():
+    r = _run(["--gpus", "1", "--steps", "0", "--warmup", "1"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 def test_a_failing_rank_fails_the_run():
     r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "nonsense"])
     assert r.returncode != 0

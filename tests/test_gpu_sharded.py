@@ -7,7 +7,8 @@
     == the unsharded result, bit for bit;
   * two real rank processes (gloo rendezvous, both on cuda:0 -- the box has one GPU) through ChopRunner / run_chain with the
     HIP kernels == the single-process result, bit for bit;
-  * `python bench.py --gpus 2` (INNFER_BENCH_DRYRUN=1) starts two ranks and prints ONE line with n_gpus == 2 and the tile_sharded object.
+  * `python bench.py --gpus 2 --full` (INNFER_BENCH_DRYRUN=1) starts two ranks and prints ONE line with n_gpus == 2 and the tile_sharded object;
+    a plain `python bench.py --dump-outputs DIR` prints the headline only and dumps what its last step computed.
 """
 import json
 import os
@@ -201,7 +202,7 @@ def test_bench_two_ranks_dry_run(dev):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "INNFER_BENCH_SELFTEST"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--workload", "frame540",
-                        "--sharded-steps", "1", "--no-power-probe", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--sharded-steps", "1", "--no-power-probe", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -219,6 +220,40 @@ def test_bench_two_ranks_dry_run(dev):
     rf = line["roofline"]
     assert rf["bound"] in ("hbm", "mfma") and rf["unit"] == ("GB/s" if rf["bound"] == "hbm" else "TFLOP/s")
     assert 0 < rf["frac"] <= 1 and 0 < rf["frac_mfma"] <= 1 and 0 < rf["frac_hbm"] <= 1
+
+
+def test_bench_plain_run_dumps_its_last_step(dev, tmp_path):
+    """A plain `bench.py` run (no --full) carries the headline only, and --dump-outputs writes what its last timed step returned: a seeded
+    sample of the output + per-channel statistics, float32 / float64, at most 64 MB -- equal to the same forward run here."""
+    import bench
+    from innfer_amd import synth
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "INNFER_BENCH_SELFTEST", "INNFER_BENCH_DRYRUN"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "frame540",
+                        "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "MPix/s" and line["higher_is_better"] is True and line["dtype"] == "f16"
+    assert not {"roofline", "tile_sharded", "chop8k", "unet64", "pan540", "srresnet1080", "cpu_baseline"} & set(line)
+    files = sorted(p.name for p in out.iterdir())
+    assert files == ["output_sample.npy", "output_stats.npy"]
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 << 20
+    sample, stats = np.load(out / "output_sample.npy"), np.load(out / "output_stats.npy")
+    assert sample.dtype == np.float32 and sample.shape == (bench.DUMP_SAMPLE,)
+    assert stats.dtype == np.float64 and stats.shape == (3, 4)
+    net, _ = bench.build_net(dev)
+    y = net(torch.from_numpy(synth.uniform((1, 3, 540, 960), 2)).to(dev).half())
+    idx = torch.randint(0, y.numel(), (bench.DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(sample, y.reshape(-1)[idx.to(dev)].float().cpu().numpy())
+    yd = y.double()
+    assert np.allclose(stats[:, 2], yd.amin(dim=(0, 2, 3)).cpu().numpy()) and np.allclose(stats[:, 3], yd.amax(dim=(0, 2, 3)).cpu().numpy())
+    assert np.allclose(stats[:, 0], yd.sum(dim=(0, 2, 3)).cpu().numpy(), rtol=1e-9)
+    net.release_workspace()
 
 
 def test_cabi_comm_single_rank(dev):
