@@ -45,8 +45,8 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  innfer_version() returns the library's; a binding should compare. */
-#define INNFER_ABI_VERSION 113
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  innfer_version() returns the library's; a binding should compare. */
+#define INNFER_ABI_VERSION 114
 int innfer_version(void);
 const char* innfer_last_error(void);
 
@@ -417,6 +417,43 @@ int innfer_pack_convt2x(const float* h_weight_iohw, int K, int C, int k, void* h
 int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream);
 /* Panels of the split form: 3 * innfer_conv3x3_packed_bytes(K, C) bytes ((w - wh) * 2^11 | wh | wh, in the order the kernel's virtual chunks meet them).  (106) */
 int innfer_pack_conv3x3_split(const float* h_weight_oihw, int K, int C, void* h_packed);
+
+/* (114) The generic fp32 convolution and normalisation of the fp32 mode (csrc/f32ops.hip: the -no_fp16 forwards of pix2pix UNet, CycleGAN ResNet, WBC UNet, PPON
+ * and PAN's fp32 convs) as single launches, for tests.  The fields are csrc/common.h F32Conv's (see there), device pointers, NCHW fp32 views:
+ *   out[n][k][Y][X] = epilogue(bias[k] + sum_{tap, c} w[k][c][tap] * in_act(in[n][c][oy * isy + dy[tap]][ox * isx + dx[tap]])),  (Y, X) = (oy * osy + ooy, ox * osx + oox)
+ * form: 0 the kernel the networks get for this view (the planner's choice), 1 the direct (large-view) kernel whatever the plan.
+ * d_packed from innfer_pack_f32conv (h_w [K][C][ntap]; innfer_f32conv_packed_floats(K, C, ntap) floats). */
+typedef struct {
+    const float* d_in; int64_t in_nstride, in_cstride; int C, Hin, Win;
+    const float* d_packed; const float* d_bias; int K;
+    float* d_out; int64_t out_nstride, out_cstride, out_pstride; int Wout;
+    int Ho, Wo;
+    int osy, osx, ooy, oox;
+    int isy, isx;
+    int ntap, dy[49], dx[49];
+    int pad_mode;                       /* 0 zero, 1 reflect, 2 replicate */
+    int up;                             /* taps walk the nearest-2x upsampled input */
+    int in_act;                         /* 0 / 1 LeakyReLU(0.2) / 2 ReLU on the input */
+    int act;                            /* 0 none, 1 LeakyReLU(0.2), 2 ReLU, 3 tanh, 4 sigmoid */
+    float oscale;
+    const float* d_res; int64_t res_nstride, res_cstride;
+    const float* d_mul; int64_t mul_nstride, mul_cstride;
+    int N;
+    int phase_k;
+    int form;
+} innfer_f32conv_args;
+
+size_t innfer_f32conv_packed_floats(int K, int C, int ntap);
+int innfer_pack_f32conv(const float* h_w, int K, int C, int ntap, float* h_packed);
+int innfer_f32conv(const innfer_f32conv_args* a, void* stream);
+/* Host only (no device call): what innfer_f32conv would launch.  plan[8] = {direct, NKT, NPT, IMG, CC, vec4, workgroups, LDS bytes}; the direct kernel reports
+ * NKT = NPT = IMG = CC = vec4 = 0 and LDS 0. */
+int innfer_f32conv_plan(const innfer_f32conv_args* a, int* plan);
+/* Per-(image, channel) plane normalisation (f32_norm_launch): mode 0 batch statistics + affine, 1 running statistics + affine, 2 instance norm, 3 y = x * weight + bias;
+ * then act (as above), then + res.  form: 0 the kernel the networks get for this plane size, 1 the three-pass kernel. */
+int innfer_f32_norm(const float* d_in, int64_t in_ns, int64_t in_cs, float* d_out, int64_t out_ns, int64_t out_cs, int N, int C, int64_t HW, int mode, float eps,
+                    const float* d_weight, const float* d_bias, const float* d_rmean, const float* d_rvar, int act,
+                    const float* d_res, int64_t res_ns, int64_t res_cs, int form, void* stream);
 
 /* NCHW (f16/f32) <-> blocked-NHWC f16 slab helpers used by tests of the single conv. */
 int innfer_nchw_to_slab(const void* d_src, int src_dtype, void* d_slab, int64_t group_stride, int ch_off,

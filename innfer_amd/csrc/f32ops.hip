@@ -748,23 +748,39 @@ void f32conv_pack(int K, int C, int ntap, const std::function<float(int, int, in
                 }
 }
 
-int f32conv_launch(const F32Conv& L, hipStream_t s) {
+namespace {
+
+// What f32conv_launch runs for a given F32Conv: the tiled kernel with its tile / chunk geometry, or the direct (large-view) kernel.  Host code only (no device
+// call): innfer_f32conv_plan reports it without a GPU.
+struct F32Plan {
+    F32Conv k;                   // the launch's view (out_pstride 0 -> 1)
+    int direct;                  // 1: f32conv_kernel
+    F32Tile t;                   // tiled: geometry
+    int NKT, NPT, tiles, zgroups;
+    size_t lds;
+    int ktb, C4, Kp;             // direct: channel tiles per block, panel geometry
+    long grid_x, grid_y, grid_z;
+};
+
+int f32conv_plan(const F32Conv& L, int force_direct, F32Plan& P) {
     if (L.ntap < 1 || L.ntap > 49 || L.C < 1 || L.K < 1 || L.N < 1 || L.Ho < 1 || L.Wo < 1) return set_error(INNFER_ERR_INVALID, "f32conv: bad arguments");
     if (L.phase_k && (L.phase_k < 0 || L.K != 4 * L.phase_k || L.osy != 1 || L.osx != 1 || L.ooy || L.oox || (L.out_pstride > 1)))
         return set_error(INNFER_ERR_INVALID, "f32conv: fused phases take K = 4 * phase_k channels on the input grid (osy = osx = 1, no offset)");
     const int C4 = (L.C + 3) / 4, Kp = (L.K + 31) / 32 * 32, nkt = Kp / 32;
     const long npx = (long)L.Ho * L.Wo;
-    F32Conv k = L;
+    P = F32Plan{};
+    P.k = L;
+    F32Conv& k = P.k;
     if (k.out_pstride == 0) k.out_pstride = 1;
-    GtScope gt(s, "f32conv (fp32 MFMA, -no_fp16 mode)", 2.0 * L.N * (double)npx * L.K * L.C * L.ntap, (double)L.N * npx * (L.C * L.ntap / (double)(L.isy * L.isx) + L.K) * 4.0);
+    P.C4 = C4; P.Kp = Kp;
 #ifdef INNFER_ABLATE
     static const int f32_direct = getenv("INNFER_F32_DIRECT") ? atoi(getenv("INNFER_F32_DIRECT")) : 0;      // A/B: the direct (round-4) kernel for every shape
 #else
     constexpr int f32_direct = 0;
 #endif
     // ---- the LDS-tiled kernel: 256-pixel tiles of 8 x 32 / 16 x 16 pixels of one image, or of the whole (<= 8 x 8) grids of several images ----
-    if (!f32_direct) {
-        F32Tile t{};
+    if (!f32_direct && !force_direct) {
+        F32Tile& t = P.t;
         t.C4 = C4; t.Kp = Kp;
         int dymin = L.dy[0], dymax = L.dy[0], dxmin = L.dx[0], dxmax = L.dx[0];
         for (int i = 1; i < L.ntap; ++i) {
@@ -864,31 +880,53 @@ int f32conv_launch(const F32Conv& L, hipStream_t s) {
 #ifdef INNFER_ABLATE
             t.abl = getenv("INNFER_F32_ABL") ? atoi(getenv("INNFER_F32_ABL")) : 0;
 #endif
-            const size_t lds = std::max(lds_total(cc), (size_t)16 * NKT * ((npt1 ? 64 : 256) + 4) * 4);      // (>= the epilogue's [channel][pixel] tile)
-            switch (NKT * 2 + (npt1 ? 1 : 0)) {
-                case 2: return f32conv_tiled_launch<1, 4>(k, t, tiles, zgroups, lds, s);
-                case 3: return f32conv_tiled_launch<1, 1>(k, t, tiles, zgroups, lds, s);
-                case 4: return f32conv_tiled_launch<2, 4>(k, t, tiles, zgroups, lds, s);
-                case 5: return f32conv_tiled_launch<2, 1>(k, t, tiles, zgroups, lds, s);
-                case 6: return f32conv_tiled_launch<3, 4>(k, t, tiles, zgroups, lds, s);
-                case 7: return f32conv_tiled_launch<3, 1>(k, t, tiles, zgroups, lds, s);
-                case 8: return f32conv_tiled_launch<4, 4>(k, t, tiles, zgroups, lds, s);
-                default: return f32conv_tiled_launch<4, 1>(k, t, tiles, zgroups, lds, s);
-            }
+            P.lds = std::max(lds_total(cc), (size_t)16 * NKT * ((npt1 ? 64 : 256) + 4) * 4);      // (>= the epilogue's [channel][pixel] tile)
+            P.NKT = NKT; P.NPT = npt1 ? 1 : 4; P.tiles = tiles; P.zgroups = zgroups;
+            P.grid_x = (long)tiles * t.nkg; P.grid_y = 1; P.grid_z = zgroups;
+            return INNFER_OK;
+        }
+        P.t = F32Tile{};
+    }
+    P.direct = 1;
+    P.ktb = nkt >= 4 ? 4 : (nkt >= 2 ? 2 : 1);
+    const long ptiles = (npx + 63) / 64;
+    const int ptb = 4 / P.ktb;
+    P.grid_x = (ptiles + ptb - 1) / ptb; P.grid_y = (nkt + P.ktb - 1) / P.ktb; P.grid_z = L.N;
+    return INNFER_OK;
+}
+
+// force_direct: the direct kernel whatever the plan (innfer_f32conv form 1: the large-view fallback under test on ordinary shapes)
+int f32conv_launch_form(const F32Conv& L, int force_direct, hipStream_t s) {
+    F32Plan P;
+    if (int rc = f32conv_plan(L, force_direct, P)) return rc;
+    const F32Conv& k = P.k;
+    const long npx = (long)L.Ho * L.Wo;
+    GtScope gt(s, "f32conv (fp32 MFMA, -no_fp16 mode)", 2.0 * L.N * (double)npx * L.K * L.C * L.ntap, (double)L.N * npx * (L.C * L.ntap / (double)(L.isy * L.isx) + L.K) * 4.0);
+    if (!P.direct) {
+        const F32Tile& t = P.t;
+        switch (P.NKT * 2 + (P.NPT == 1 ? 1 : 0)) {
+            case 2: return f32conv_tiled_launch<1, 4>(k, t, P.tiles, P.zgroups, P.lds, s);
+            case 3: return f32conv_tiled_launch<1, 1>(k, t, P.tiles, P.zgroups, P.lds, s);
+            case 4: return f32conv_tiled_launch<2, 4>(k, t, P.tiles, P.zgroups, P.lds, s);
+            case 5: return f32conv_tiled_launch<2, 1>(k, t, P.tiles, P.zgroups, P.lds, s);
+            case 6: return f32conv_tiled_launch<3, 4>(k, t, P.tiles, P.zgroups, P.lds, s);
+            case 7: return f32conv_tiled_launch<3, 1>(k, t, P.tiles, P.zgroups, P.lds, s);
+            case 8: return f32conv_tiled_launch<4, 4>(k, t, P.tiles, P.zgroups, P.lds, s);
+            default: return f32conv_tiled_launch<4, 1>(k, t, P.tiles, P.zgroups, P.lds, s);
         }
     }
-    const int ktb = nkt >= 4 ? 4 : (nkt >= 2 ? 2 : 1);
-    const long ptiles = (npx + 63) / 64;
-    const int ptb = 4 / ktb;
-    hipLaunchKernelGGL(f32conv_kernel, dim3((unsigned)((ptiles + ptb - 1) / ptb), (unsigned)((nkt + ktb - 1) / ktb), (unsigned)L.N), dim3(256), 0, s, k, ktb, C4, Kp);
+    hipLaunchKernelGGL(f32conv_kernel, dim3((unsigned)P.grid_x, (unsigned)P.grid_y, (unsigned)P.grid_z), dim3(256), 0, s, k, P.ktb, P.C4, P.Kp);
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
 }
 
-int f32_norm_launch(const float* in, long in_ns, long in_cs, float* out, long out_ns, long out_cs, int N, int C, long HW, int mode, float eps,
-                    const float* weight, const float* bias, const float* rmean, const float* rvar, int act, hipStream_t s,
-                    const float* res, long res_ns, long res_cs) {
-    if ((mode == 0 || mode == 2) && HW <= 64) {                       // statistics of tiny planes: a wave per plane
+// three_pass: f32_norm_kernel whatever the plane size (innfer_f32_norm form 1: the reference the register forms must equal bit for bit)
+int f32_norm_launch_form(const float* in, long in_ns, long in_cs, float* out, long out_ns, long out_cs, int N, int C, long HW, int mode, float eps,
+                         const float* weight, const float* bias, const float* rmean, const float* rvar, int act, hipStream_t s,
+                         const float* res, long res_ns, long res_cs, int three_pass) {
+    if (three_pass) {
+        hipLaunchKernelGGL(f32_norm_kernel, dim3(C, N), dim3(256), 0, s, in, in_ns, in_cs, out, out_ns, out_cs, C, HW, mode, eps, weight, bias, rmean, rvar, act, res, res_ns, res_cs);
+    } else if ((mode == 0 || mode == 2) && HW <= 64) {                       // statistics of tiny planes: a wave per plane
         hipLaunchKernelGGL(f32_norm_small_kernel, dim3((unsigned)(((long)C * N + 3) / 4)), dim3(256), 0, s, in, in_ns, in_cs, out, out_ns, out_cs, C, (int)HW, N, mode, eps, weight, bias, act, res, res_ns, res_cs);
     } else if ((mode == 0 || mode == 2) && HW <= 256 * 16) {          // the plane in registers: one read instead of three (same bits as the three-pass kernel)
         hipLaunchKernelGGL(f32_norm_reg_kernel<16>, dim3(C, N), dim3(256), 0, s, in, in_ns, in_cs, out, out_ns, out_cs, C, (int)HW, mode, eps, weight, bias, act, res, res_ns, res_cs);
@@ -899,6 +937,16 @@ int f32_norm_launch(const float* in, long in_ns, long in_cs, float* out, long ou
     }
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
+}
+
+}  // namespace
+
+int f32conv_launch(const F32Conv& L, hipStream_t s) { return f32conv_launch_form(L, 0, s); }
+
+int f32_norm_launch(const float* in, long in_ns, long in_cs, float* out, long out_ns, long out_cs, int N, int C, long HW, int mode, float eps,
+                    const float* weight, const float* bias, const float* rmean, const float* rvar, int act, hipStream_t s,
+                    const float* res, long res_ns, long res_cs) {
+    return f32_norm_launch_form(in, in_ns, in_cs, out, out_ns, out_cs, N, C, HW, mode, eps, weight, bias, rmean, rvar, act, s, res, res_ns, res_cs, 0);
 }
 
 int f32_act_copy_launch(const float* in, long in_ns, float* out, long out_ns, long per_image, int N, int act, hipStream_t s) {
@@ -956,3 +1004,68 @@ int f32_prefix_lrelu_launch(float* t, int N, int groups, int gc, long hw, hipStr
 }
 
 }  // namespace innfer
+
+// ---- C ABI (114): single launches of the two building blocks, for tests ----
+using namespace innfer;
+
+namespace {
+int f32conv_from_args(const innfer_f32conv_args* a, F32Conv& c) {
+    if (!a) return set_error(INNFER_ERR_INVALID, "f32conv: null argument");
+    if (!a->d_in || !a->d_packed || !a->d_out || (a->form != 0 && a->form != 1) || a->pad_mode < 0 || a->pad_mode > 2 || a->in_act < 0 || a->in_act > 2 ||
+        a->act < 0 || a->act > 4 || a->isy < 1 || a->isx < 1 || a->osy < 1 || a->osx < 1 || a->out_pstride < 0)
+        return set_error(INNFER_ERR_INVALID, "f32conv: bad arguments");
+    c = F32Conv{};
+    c.in = a->d_in; c.in_nstride = a->in_nstride; c.in_cstride = a->in_cstride; c.C = a->C; c.Hin = a->Hin; c.Win = a->Win;
+    c.wp = a->d_packed; c.bias = a->d_bias; c.K = a->K;
+    c.out = a->d_out; c.out_nstride = a->out_nstride; c.out_cstride = a->out_cstride; c.out_pstride = a->out_pstride; c.Wout = a->Wout;
+    c.Ho = a->Ho; c.Wo = a->Wo; c.osy = a->osy; c.osx = a->osx; c.ooy = a->ooy; c.oox = a->oox; c.isy = a->isy; c.isx = a->isx;
+    c.ntap = a->ntap;
+    for (int i = 0; i < 49; ++i) { c.dy[i] = a->dy[i]; c.dx[i] = a->dx[i]; }
+    c.pad_mode = a->pad_mode; c.up = a->up; c.in_act = a->in_act; c.act = a->act; c.oscale = a->oscale;
+    c.res = a->d_res; c.res_nstride = a->res_nstride; c.res_cstride = a->res_cstride;
+    c.mul = a->d_mul; c.mul_nstride = a->mul_nstride; c.mul_cstride = a->mul_cstride;
+    c.N = a->N; c.phase_k = a->phase_k;
+    return INNFER_OK;
+}
+}  // namespace
+
+extern "C" size_t innfer_f32conv_packed_floats(int K, int C, int ntap) { return (K > 0 && C > 0 && ntap > 0 && ntap <= 49) ? f32conv_packed_floats(K, C, ntap) : 0; }
+
+extern "C" int innfer_pack_f32conv(const float* h_w, int K, int C, int ntap, float* h_packed) {
+    if (!h_w || !h_packed || K <= 0 || C <= 0 || ntap <= 0 || ntap > 49) return set_error(INNFER_ERR_INVALID, "pack_f32conv: K=%d C=%d ntap=%d", K, C, ntap);
+    f32conv_pack(K, C, ntap, [&](int k, int c, int t) { return h_w[((size_t)k * C + c) * ntap + t]; }, h_packed);
+    return INNFER_OK;
+}
+
+extern "C" int innfer_f32conv(const innfer_f32conv_args* a, void* stream) {
+    F32Conv c;
+    if (int rc = f32conv_from_args(a, c)) return rc;
+    return f32conv_launch_form(c, a->form, (hipStream_t)stream);
+}
+
+extern "C" int innfer_f32conv_plan(const innfer_f32conv_args* a, int* plan) {
+    F32Conv c;
+    if (!plan) return set_error(INNFER_ERR_INVALID, "f32conv_plan: null plan");
+    if (int rc = f32conv_from_args(a, c)) return rc;
+    F32Plan P;
+    if (int rc = f32conv_plan(c, a->form, P)) return rc;
+    plan[0] = P.direct;
+    plan[1] = P.direct ? 0 : P.NKT;
+    plan[2] = P.direct ? 0 : P.NPT;
+    plan[3] = P.direct ? 0 : 1 << P.t.imgs;
+    plan[4] = P.direct ? 0 : P.t.CC;
+    plan[5] = P.direct ? 0 : P.t.vec4;
+    plan[6] = (int)std::min<long>(P.grid_x * P.grid_y * P.grid_z, 0x7fffffffL);
+    plan[7] = P.direct ? 0 : (int)P.lds;
+    return INNFER_OK;
+}
+
+extern "C" int innfer_f32_norm(const float* d_in, int64_t in_ns, int64_t in_cs, float* d_out, int64_t out_ns, int64_t out_cs, int N, int C, int64_t HW, int mode, float eps,
+                               const float* d_weight, const float* d_bias, const float* d_rmean, const float* d_rvar, int act,
+                               const float* d_res, int64_t res_ns, int64_t res_cs, int form, void* stream) {
+    if (!d_in || !d_out || N < 1 || N > 65535 || C < 1 || HW < 1 || mode < 0 || mode > 3 || act < 0 || act > 4 || (form != 0 && form != 1) ||
+        (mode != 2 && (!d_weight || !d_bias)) || (mode == 1 && (!d_rmean || !d_rvar)))
+        return set_error(INNFER_ERR_INVALID, "f32_norm: bad arguments (mode %d)", mode);
+    return f32_norm_launch_form(d_in, in_ns, in_cs, d_out, out_ns, out_cs, N, C, HW, mode, eps, d_weight, d_bias, d_rmean, d_rvar, act, (hipStream_t)stream,
+                                d_res, res_ns, res_cs, form);
+}

@@ -52,6 +52,25 @@ class ConvArgs(C.Structure):
     ]
 
 
+class F32ConvArgs(C.Structure):
+    _fields_ = [
+        ("d_in", C.c_void_p), ("in_nstride", C.c_int64), ("in_cstride", C.c_int64), ("C", C.c_int), ("Hin", C.c_int), ("Win", C.c_int),
+        ("d_packed", C.c_void_p), ("d_bias", C.c_void_p), ("K", C.c_int),
+        ("d_out", C.c_void_p), ("out_nstride", C.c_int64), ("out_cstride", C.c_int64), ("out_pstride", C.c_int64), ("Wout", C.c_int),
+        ("Ho", C.c_int), ("Wo", C.c_int),
+        ("osy", C.c_int), ("osx", C.c_int), ("ooy", C.c_int), ("oox", C.c_int),
+        ("isy", C.c_int), ("isx", C.c_int),
+        ("ntap", C.c_int), ("dy", C.c_int * 49), ("dx", C.c_int * 49),
+        ("pad_mode", C.c_int), ("up", C.c_int), ("in_act", C.c_int), ("act", C.c_int),
+        ("oscale", C.c_float),
+        ("d_res", C.c_void_p), ("res_nstride", C.c_int64), ("res_cstride", C.c_int64),
+        ("d_mul", C.c_void_p), ("mul_nstride", C.c_int64), ("mul_cstride", C.c_int64),
+        ("N", C.c_int),
+        ("phase_k", C.c_int),
+        ("form", C.c_int),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/innfer_amd.h
 SIGNATURES = {
     "innfer_version": (C.c_int, []),
@@ -191,6 +210,12 @@ SIGNATURES = {
                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "innfer_inthwc_to_nchw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_nchw_to_inthwc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "innfer_f32conv_packed_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "innfer_pack_f32conv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "innfer_f32conv": (C.c_int, [C.POINTER(F32ConvArgs), C.c_void_p]),
+    "innfer_f32conv_plan": (C.c_int, [C.POINTER(F32ConvArgs), C.POINTER(C.c_int)]),
+    "innfer_f32_norm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_float,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
 }
 
 # INNFER_ABI_ANY=1 (measurement only: scripts/evidence_r5.sh A/Bs an OLDER build of the library against the current one on one box): bind the entry points that
@@ -210,7 +235,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 lib = _lib
 
-ABI_VERSION = 113          # the header revision this binding was written against (INNFER_ABI_VERSION)
+ABI_VERSION = 114          # the header revision this binding was written against (INNFER_ABI_VERSION)
 if _lib.innfer_version() != ABI_VERSION and not _ABI_ANY:
     raise ImportError(f"{LIB_PATH} speaks ABI {_lib.innfer_version()}, this binding {ABI_VERSION}: rebuild with `make`")
 
@@ -250,6 +275,25 @@ def chop_plan(H, W, patch=200, step=0.5):
     ys, xs = (C.c_int * nh.value)(), (C.c_int * nw.value)()
     check(_lib.innfer_chop_plan(H, W, patch, step, C.byref(ps), C.byref(nh), C.byref(nw), ys, xs))
     return ps.value, list(ys), list(xs)
+
+
+F32_PLAN_KEYS = ("direct", "NKT", "NPT", "IMG", "CC", "vec4", "workgroups", "lds")
+
+
+def f32conv_args(taps, **fields):
+    """F32ConvArgs from keyword fields (names of the struct) and the tap list [(dy, dx)]; pointers as integers."""
+    a = F32ConvArgs(**fields)
+    a.ntap = len(taps)
+    for i, (dy, dx) in enumerate(taps):
+        a.dy[i], a.dx[i] = dy, dx
+    return a
+
+
+def f32conv_plan(a):
+    """innfer_f32conv_plan (host only): what innfer_f32conv would launch for the F32ConvArgs `a`, as a dict of F32_PLAN_KEYS."""
+    plan = (C.c_int * 8)()
+    check(_lib.innfer_f32conv_plan(C.byref(a), plan))
+    return dict(zip(F32_PLAN_KEYS, plan))
 
 
 def blend_profile(P, step=0.5, scale=1):
