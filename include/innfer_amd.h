@@ -45,8 +45,8 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  innfer_version() returns the library's; a binding should compare. */
-#define INNFER_ABI_VERSION 114
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  innfer_version() returns the library's; a binding should compare. */
+#define INNFER_ABI_VERSION 115
 int innfer_version(void);
 const char* innfer_last_error(void);
 
@@ -554,6 +554,34 @@ int innfer_inthwc_to_nchw(const void* d_img, int bits, int H, int W, int C, int 
                           void* d_out, int out_dtype, void* stream);
 int innfer_nchw_to_inthwc(const void* d_in, int in_dtype, int H, int W, int C, int rgb2bgr, int denormalize, int bits,
                           void* d_img, void* stream);
+
+/* fit_channels (115): gray, gray + alpha and BGRA images through an RGB network (in_nc == out_nc == 3).  Extends np2tensor / tensor2np
+ * (utils/utils.py:164-248) and the image loop (run.py:404-442), which hand such images to the network as they are.  Layouts, HWC in OpenCV
+ * order, C = 1 gray, 2 gray + alpha, 4 BGRA; the last channel of C 2 / 4 is the alpha plane.
+ *   colour input [3, H, W]: (g, g, g), or R, G, B from BGRA -- np2tensor of a 3-channel image (same /maxval, normalisation, cast);
+ *   alpha input  [3, H, W]: (a, a, a);
+ *   output: B, G, R of the colour result exactly as tensor2np (C 4), or gray = mean3(colour result) (C 1 / 2); alpha = mean3(alpha result), or
+ *   alpha_const when the network did not run on a constant alpha plane (it is copied as is).
+ * mean3(y) = ((y0 + y1) + y2) / 3 in fp32, round to nearest, of the result's three channels already rounded to the result dtype (via_dtype on the
+ * chop path); rounded to that dtype again, then quantised as tensor2np (denormalise, clip, * 255 or 65535, round half to even).
+ *
+ * innfer_channel_minmax: d_minmax[0] = min, d_minmax[1] = max of channel `ch` of a uint8 / uint16 (bits 8 / 16) HWC image; two device ints.
+ * innfer_extract_tiles_u8_fit: innfer_extract_tiles_u8 of the colour input into tiles [0, tile_count) of a [*, 3, P, P] buffer and, alpha != 0,
+ *   of the alpha input into tiles [tile_count, 2 tile_count): one pixel's C bytes in one load, four pixels per thread where the geometry allows.
+ * innfer_recompose_u8_fit: innfer_recompose_u8 of the n colour tiles [0, n) and, alpha != 0, of the alpha tiles [n, 2 n) in one pass: each
+ *   pixel's weights once, every channel summed in innfer_recompose_u8's order (so B, G, R are its bytes), then the output above; alpha == 0 with
+ *   C 2 / 4 needs alpha_const in [0, 255].  Stores C bytes per pixel into d_img [scale H, scale W, C].
+ * innfer_inthwc_to_nchw_fit / innfer_nchw_to_inthwc_fit: the same split and merge on whole images (uint8 / uint16), for the tensor path: d_alpha
+ *   may be null (no alpha plane, or a constant one: then alpha_const in [0, 2^bits - 1] is stored).  Channel order is always flipped (bgr2rgb). */
+int innfer_channel_minmax(const void* d_img, int bits, int H, int W, int C, int ch, int* d_minmax, void* stream);
+int innfer_extract_tiles_u8_fit(const uint8_t* d_img, int C, int H, int W, int normalize, int patch, double step,
+                                int tile_begin, int tile_count, int alpha, void* d_tiles, int tile_dtype, void* stream);
+int innfer_recompose_u8_fit(const void* d_tiles, int dtype, int n_tiles, int P, int height, int width, double step, int scale,
+                            int via_dtype, int denormalize, int C, int alpha, int alpha_const, uint8_t* d_img, void* stream);
+int innfer_inthwc_to_nchw_fit(const void* d_img, int bits, int H, int W, int C, int normalize, float maxval,
+                              void* d_colour, void* d_alpha, int out_dtype, void* stream);
+int innfer_nchw_to_inthwc_fit(const void* d_colour, const void* d_alpha, int in_dtype, int H, int W, int C, int denormalize, int bits,
+                              int alpha_const, void* d_img, void* stream);
 
 /* srgb2linear / linear2srgb (utils/colors.py:29-46, 49-60), the pointwise halves of the `-cf` colour
  * fix: uint8 sRGB -> float32 linear, and float32 linear -> uint8 sRGB (clip, gamma, *255, TRUNCATING

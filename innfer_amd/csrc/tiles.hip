@@ -309,6 +309,176 @@ __global__ void k_linear2srgb(const float* in, uint8_t* out, long n) {
     out[i] = (uint8_t)(int)s;                                   // astype(np.uint8): truncation
 }
 
+// ---- fit_channels: 1-, 2- and 4-channel integer images through an RGB (3 -> 3) network (ABI 115) ------------------------------------------------
+// Image layouts (HWC, OpenCV order): C 1 = gray, 2 = gray + alpha, 4 = BGRA.  The colour input of the network is (g, g, g) or RGB, the alpha input
+// (a, a, a); a gray or alpha result is mean3 of the network's three channels: ((y0 + y1) + y2) / 3 in fp32, rounded to the result type, then
+// quantised as tensor2np.  The C - 1 channel of a 2- / 4-channel image is its alpha.
+
+// C bytes (or shorts) of one pixel in one load / store: 1, 2, 4 or 8 bytes, naturally aligned
+template <typename T, int C> struct alignas(sizeof(T) * C) Px { T v[C]; };
+
+// one np2tensor element: float32(x) / maxval [-> ((x - 0.5) * 2).clamp(-1, 1)] -- the ops of k_u8_to_nchw / k_extract_u8
+__device__ __forceinline__ float to_unit(float x, float maxval, int normalize) {
+    float v = __fdiv_rn(x, maxval);
+    if (normalize) v = fminf(fmaxf(__fmul_rn(__fsub_rn(v, 0.5f), 2.0f), -1.0f), 1.0f);
+    return v;
+}
+
+// one tensor2np element (k_nchw_to_u8 / k_recompose U8OUT): [denormalise,] clip(range * v, 0, range), round half to even
+__device__ __forceinline__ int quantise(float v, int denormalize, float range) {
+    if (denormalize) v = fminf(fmaxf(__fdiv_rn(__fsub_rn(v, -1.0f), 2.0f), 0.0f), 1.0f);
+    return __float2int_rn(fminf(fmaxf(__fmul_rn(range, v), 0.0f), range));
+}
+
+template <typename TO>
+__device__ __forceinline__ TO mean3(TO y0, TO y1, TO y2) {
+    return (TO)__fdiv_rn(__fadd_rn(__fadd_rn((float)y0, (float)y1), (float)y2), 3.0f);
+}
+
+// min / max of channel `ch` of an HWC integer image: per thread, per wave, per 256-thread block (LDS), then one atomic pair per block into mm[0..1]
+// (set by k_minmax_init).  At most 256 blocks: atomics on one address serialise, one pair per wave of a 1080p grid cost ~0.1 ms.
+__global__ void k_minmax_init(int* mm) { mm[0] = 0x7fffffff; mm[1] = -1; }
+
+template <typename T>
+__global__ void __launch_bounds__(256) k_channel_minmax(const T* img, long hw, int C, int ch, int* mm) {
+    __shared__ int slo[4], shi[4];
+    int lo = 0x7fffffff, hi = -1;
+    for (long px = (long)blockIdx.x * blockDim.x + threadIdx.x; px < hw; px += (long)gridDim.x * blockDim.x) {
+        const int v = img[px * C + ch];
+        lo = min(lo, v);
+        hi = max(hi, v);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, __shfl_xor(lo, o, 64));
+        hi = max(hi, __shfl_xor(hi, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) { slo[threadIdx.x >> 6] = lo; shi[threadIdx.x >> 6] = hi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) { lo = min(lo, slo[w]); hi = max(hi, shi[w]); }
+        if (hi >= 0) {
+            atomicMin(mm, lo);
+            atomicMax(mm + 1, hi);
+        }
+    }
+}
+
+// extract_patches_2d of the colour and alpha planes: V consecutive pixels of one tile row per thread, all C channels of them in one load; colour
+// tile k goes to slot k - tile_begin, its alpha tile (alpha != 0) to slot count + k - tile_begin, both [3, ps, ps].  V = 4 needs ps, the tile step and
+// W multiples of 4 (every tile origin is then, and the V * C bytes are aligned).
+template <typename TO, int C, int V>
+__global__ void k_extract_u8_fit(const uint8_t* img, TO* tiles, int H, int W, int ps, int step_int, int nw, int tile_begin, int count, long total,
+                                 int normalize, int alpha) {
+    typedef TO vo __attribute__((ext_vector_type(V)));
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // over count * ps * (ps / V)
+    if (i >= total) return;
+    const int q = ps / V;
+    const int x = (int)(i % q) * V;
+    const int y = (int)((i / q) % ps);
+    const int kk = (int)(i / ((long)q * ps));
+    const int k = kk + tile_begin;
+    const int th = k / nw, tw = k % nw;
+    int oy = th * step_int; if (oy > H - ps) oy = H - ps;
+    int ox = tw * step_int; if (ox > W - ps) ox = W - ps;
+    const Px<uint8_t, C * V> p = *(const Px<uint8_t, C * V>*)(img + ((long)(oy + y) * W + ox + x) * C);
+    vo col[3], a;
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)                                 // RGB from BGR(A); (g, g, g) from gray
+            col[c][j] = (TO)to_unit((float)p.v[j * C + (C == 4 ? 2 - c : 0)], 255.0f, normalize);
+        if (C > 1) a[j] = (TO)to_unit((float)p.v[j * C + C - 1], 255.0f, normalize);
+    }
+    const long pp = (long)ps * ps, o = (long)y * ps + x;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *(vo*)(tiles + ((long)kk * 3 + c) * pp + o) = col[c];
+    if (C > 1 && alpha) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) *(vo*)(tiles + ((long)(count + kk) * 3 + c) * pp + o) = a;
+    }
+}
+
+// The blend of innfer_recompose_u8 for the colour tiles [0, n) and, with alpha, the alpha tiles [n, 2n): one thread per output pixel, each tile's
+// weight computed once and applied to all six numerators in k_recompose's order (so each channel is what innfer_recompose_u8 stores), then tensor2np
+// of B, G, R (C 4) or of mean3 (gray), and of mean3 of the alpha result or the constant alpha `aconst` (>= 0); the pixel's C bytes in one store.
+template <typename TI, typename TO, int C>
+__global__ void k_recompose_u8_fit(const TI* tiles, int n, int P, int FH, int FW, int eff, int nh, int nw, int ov, int alpha, int aconst,
+                                   int denormalize, uint8_t* img) {
+    const int X = blockIdx.x * blockDim.x + threadIdx.x;
+    const int Y = blockIdx.y;
+    if (X >= FW) return;
+    constexpr int NC = C > 1 ? 6 : 3;
+    float num[NC], den = 0.f;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) num[c] = 0.f;
+    const long pp = (long)P * P, aoff = (long)n * 3 * pp;
+    const int h0 = max(0, (Y - P + eff) / eff), w0 = max(0, (X - P + eff) / eff);
+    for (int h = h0; h < nh; ++h) {
+        const int oy = min(h * eff, FH - P);
+        if (oy > Y) break;
+        if (Y - oy >= P) continue;
+        const float wy = profile(Y - oy, P, ov);
+        for (int w = w0; w < nw; ++w) {
+            const int ox = min(w * eff, FW - P);
+            if (ox > X) break;
+            if (X - ox >= P) continue;
+            const float wgt = __fmul_rn(profile(X - ox, P, ov), wy);
+            den = __fadd_rn(den, wgt);
+            const long k = (long)h * nw + w;
+            const TI* tp = tiles + (k * 3 * P + (Y - oy)) * (long)P + (X - ox);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) num[c] = __fadd_rn(num[c], __fmul_rn((float)tp[c * pp], wgt));
+            if (C > 1 && alpha) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) num[3 + c] = __fadd_rn(num[3 + c], __fmul_rn((float)tp[aoff + c * pp], wgt));
+            }
+        }
+    }
+    TO r[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) r[c] = (TO)__fdiv_rn(num[c], den);
+    Px<uint8_t, C> o;
+    if (C == 4) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o.v[2 - c] = (uint8_t)quantise((float)r[c], denormalize, 255.0f);
+    } else {
+        o.v[0] = (uint8_t)quantise((float)mean3(r[0], r[1], r[2]), denormalize, 255.0f);
+    }
+    if (C > 1) o.v[C - 1] = alpha ? (uint8_t)quantise((float)mean3(r[NC - 3], r[NC - 2], r[NC - 1]), denormalize, 255.0f) : (uint8_t)aconst;
+    *(Px<uint8_t, C>*)(img + ((long)Y * FW + X) * C) = o;
+}
+
+// np2tensor of the two planes on whole images: colour [3, hw] (RGB from BGRA, (g, g, g) from gray), alpha [3, hw] (a, a, a) when `alpha` is non-null
+template <typename TI, typename TO, int C>
+__global__ void k_inthwc_to_nchw_fit(const TI* img, TO* col, TO* alpha, long hw, int normalize, float maxval) {
+    const long px = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (px >= hw) return;
+    const Px<TI, C> p = *(const Px<TI, C>*)(img + px * C);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) col[c * hw + px] = (TO)to_unit((float)p.v[C == 4 ? 2 - c : 0], maxval, normalize);
+    if (C > 1 && alpha) {
+        const TO a = (TO)to_unit((float)p.v[C - 1], maxval, normalize);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) alpha[c * hw + px] = a;
+    }
+}
+
+// tensor2np of the two results into the image's layout: B, G, R (C 4) or mean3 gray, and mean3 of the alpha result or the constant `aconst`
+template <typename TI, typename TU, int C>
+__global__ void k_nchw_to_inthwc_fit(const TI* col, const TI* alpha, long hw, int denormalize, float range, int aconst, TU* img) {
+    const long px = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (px >= hw) return;
+    Px<TU, C> o;
+    if (C == 4) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o.v[2 - c] = (TU)quantise((float)col[c * hw + px], denormalize, range);
+    } else {
+        o.v[0] = (TU)quantise((float)mean3(col[px], col[hw + px], col[2 * hw + px]), denormalize, range);
+    }
+    if (C > 1) o.v[C - 1] = alpha ? (TU)quantise((float)mean3(alpha[px], alpha[hw + px], alpha[2 * hw + px]), denormalize, range) : (TU)aconst;
+    *(Px<TU, C>*)(img + px * C) = o;
+}
+
 inline unsigned blocks(long total, int bs) { return (unsigned)((total + bs - 1) / bs); }
 
 }  // namespace
@@ -575,6 +745,128 @@ extern "C" int innfer_linear_to_srgb(const float* d_in, uint8_t* d_out, size_t n
     if (!d_in || !d_out) return set_error(INNFER_ERR_INVALID, "linear_to_srgb: null argument");
     if (n == 0) return INNFER_OK;
     hipLaunchKernelGGL(k_linear2srgb, dim3(blocks((long)n, 256)), dim3(256), 0, (hipStream_t)stream, d_in, d_out, (long)n);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+// ------------------------------------------------------------------ fit_channels entry points (ABI 115)
+extern "C" int innfer_channel_minmax(const void* d_img, int bits, int H, int W, int C, int ch, int* d_minmax, void* stream) {
+    const long hw = (long)H * W;
+    if (!d_img || !d_minmax || hw <= 0 || C <= 0 || ch < 0 || ch >= C || (bits != 8 && bits != 16))
+        return set_error(INNFER_ERR_INVALID, "channel_minmax: bad arguments (bits %d, C %d, ch %d)", bits, C, ch);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_minmax_init, dim3(1), dim3(1), 0, s, d_minmax);
+    const unsigned g = blocks(hw, 256) < 256 ? blocks(hw, 256) : 256;
+    if (bits == 8) hipLaunchKernelGGL(k_channel_minmax<uint8_t>, dim3(g), dim3(256), 0, s, (const uint8_t*)d_img, hw, C, ch, d_minmax);
+    else hipLaunchKernelGGL(k_channel_minmax<uint16_t>, dim3(g), dim3(256), 0, s, (const uint16_t*)d_img, hw, C, ch, d_minmax);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+extern "C" int innfer_extract_tiles_u8_fit(const uint8_t* d_img, int C, int H, int W, int normalize, int patch, double step,
+                                           int tile_begin, int tile_count, int alpha, void* d_tiles, int tile_dtype, void* stream) {
+    if (!d_img || !d_tiles) return set_error(INNFER_ERR_INVALID, "extract_tiles_u8_fit: null argument");
+    if (C != 1 && C != 2 && C != 4) return set_error(INNFER_ERR_INVALID, "extract_tiles_u8_fit: %d channels (1, 2 or 4)", C);
+    if (alpha && C == 1) return set_error(INNFER_ERR_INVALID, "extract_tiles_u8_fit: a 1-channel image has no alpha");
+    int ps, nh, nw;
+    if (int rc = innfer_chop_plan(H, W, patch, step, &ps, &nh, &nw, nullptr, nullptr)) return rc;
+    const int step_int = (int)(ps * step);
+    if (tile_begin < 0 || tile_count < 0 || tile_begin + tile_count > nh * nw)
+        return set_error(INNFER_ERR_INVALID, "extract_tiles_u8_fit: tile range [%d,+%d) outside %d tiles", tile_begin, tile_count, nh * nw);
+    if (tile_count == 0) return INNFER_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const bool x4 = ps % 4 == 0 && step_int % 4 == 0 && W % 4 == 0;
+    const long total = (long)tile_count * ps * (x4 ? ps / 4 : ps);
+    const int a = alpha ? 1 : 0;
+#define EXF(TO, CC, V) hipLaunchKernelGGL((k_extract_u8_fit<TO, CC, V>), dim3(blocks(total, 256)), dim3(256), 0, s, d_img, (TO*)d_tiles, H, W, ps, step_int, nw, \
+                                          tile_begin, tile_count, total, normalize, a)
+#define EXF_C(TO) do { if (x4) { if (C == 1) EXF(TO, 1, 4); else if (C == 2) EXF(TO, 2, 4); else EXF(TO, 4, 4); } \
+                       else { if (C == 1) EXF(TO, 1, 1); else if (C == 2) EXF(TO, 2, 1); else EXF(TO, 4, 1); } } while (0)
+    if (tile_dtype == INNFER_F16) EXF_C(f16);
+    else if (tile_dtype == INNFER_F32) EXF_C(float);
+    else return set_error(INNFER_ERR_INVALID, "extract_tiles_u8_fit: bad dtype %d", tile_dtype);
+#undef EXF_C
+#undef EXF
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+extern "C" int innfer_recompose_u8_fit(const void* d_tiles, int dtype, int n, int P, int height, int width, double step, int scale,
+                                       int via_dtype, int denormalize, int C, int alpha, int alpha_const, uint8_t* d_img, void* stream) {
+    if (!d_tiles || !d_img) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: null argument");
+    if (C != 1 && C != 2 && C != 4) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: %d channels (1, 2 or 4)", C);
+    if (C == 1 ? alpha != 0 : (!alpha && (alpha_const < 0 || alpha_const > 255)))
+        return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: a %d-channel image needs %s", C, C == 1 ? "no alpha tiles" : "alpha tiles or a constant alpha in [0, 255]");
+    if (step < 0.5 || step > 1.0) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: step must be in [0.5,1]");
+    if (n <= 0 || P <= 0 || scale <= 0) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: bad sizes");
+    const int FH = scale * height, FW = scale * width;
+    if (FH < P || FW < P) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: patch %d larger than output %dx%d", P, FH, FW);
+    const int ov = blend_overlap(P, step, scale);
+    if (P - 2 * ov < 0) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: overlap %d exceeds half of patch %d (reference raises too)", ov, P);
+    const int eff = (int)(step * P), step_int = (int)(P * step);
+    const int nh = 1 + (FH - P) / step_int + ((FH - P) % step_int != 0);
+    const int nw = 1 + (FW - P) / step_int + ((FW - P) % step_int != 0);
+    if (n != nh * nw) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: one image of %dx%d tiles expected, got %d colour tiles", nh, nw, n);
+    hipStream_t s = (hipStream_t)stream;
+    dim3 grid((FW + 255) / 256, FH, 1), block(256);
+    const int a = alpha ? 1 : 0;
+#define RCF(TI, TO, CC) hipLaunchKernelGGL((k_recompose_u8_fit<TI, TO, CC>), grid, block, 0, s, (const TI*)d_tiles, n, P, FH, FW, eff, nh, nw, ov, a, alpha_const, \
+                                           denormalize, d_img)
+#define RCF_C(TI, TO) do { if (C == 1) RCF(TI, TO, 1); else if (C == 2) RCF(TI, TO, 2); else RCF(TI, TO, 4); } while (0)
+    if (dtype == INNFER_F16 && via_dtype == INNFER_F16) RCF_C(f16, f16);
+    else if (dtype == INNFER_F16 && via_dtype == INNFER_F32) RCF_C(f16, float);
+    else if (dtype == INNFER_F32 && via_dtype == INNFER_F32) RCF_C(float, float);
+    else if (dtype == INNFER_F32 && via_dtype == INNFER_F16) RCF_C(float, f16);
+    else return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: bad dtype");
+#undef RCF_C
+#undef RCF
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+extern "C" int innfer_inthwc_to_nchw_fit(const void* d_img, int bits, int H, int W, int C, int normalize, float maxval,
+                                         void* d_colour, void* d_alpha, int out_dtype, void* stream) {
+    const long hw = (long)H * W;
+    if (!d_img || !d_colour || hw <= 0 || !(maxval > 0.f)) return set_error(INNFER_ERR_INVALID, "inthwc_to_nchw_fit: bad arguments");
+    if (C != 1 && C != 2 && C != 4) return set_error(INNFER_ERR_INVALID, "inthwc_to_nchw_fit: %d channels (1, 2 or 4)", C);
+    if (d_alpha && C == 1) return set_error(INNFER_ERR_INVALID, "inthwc_to_nchw_fit: a 1-channel image has no alpha");
+    if ((bits != 8 && bits != 16) || (out_dtype != INNFER_F16 && out_dtype != INNFER_F32))
+        return set_error(INNFER_ERR_INVALID, "inthwc_to_nchw_fit: bits %d (8, 16), dtype %d", bits, out_dtype);
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 g(blocks(hw, 256)), b(256);
+#define TNF(TI, TO, CC) hipLaunchKernelGGL((k_inthwc_to_nchw_fit<TI, TO, CC>), g, b, 0, s, (const TI*)d_img, (TO*)d_colour, (TO*)d_alpha, hw, normalize, maxval)
+#define TNF_C(TI, TO) do { if (C == 1) TNF(TI, TO, 1); else if (C == 2) TNF(TI, TO, 2); else TNF(TI, TO, 4); } while (0)
+    if (bits == 8 && out_dtype == INNFER_F16) TNF_C(uint8_t, f16);
+    else if (bits == 8) TNF_C(uint8_t, float);
+    else if (out_dtype == INNFER_F16) TNF_C(uint16_t, f16);
+    else TNF_C(uint16_t, float);
+#undef TNF_C
+#undef TNF
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+extern "C" int innfer_nchw_to_inthwc_fit(const void* d_colour, const void* d_alpha, int in_dtype, int H, int W, int C, int denormalize, int bits,
+                                         int alpha_const, void* d_img, void* stream) {
+    const long hw = (long)H * W;
+    if (!d_colour || !d_img || hw <= 0) return set_error(INNFER_ERR_INVALID, "nchw_to_inthwc_fit: bad arguments");
+    if (C != 1 && C != 2 && C != 4) return set_error(INNFER_ERR_INVALID, "nchw_to_inthwc_fit: %d channels (1, 2 or 4)", C);
+    if ((bits != 8 && bits != 16) || (in_dtype != INNFER_F16 && in_dtype != INNFER_F32))
+        return set_error(INNFER_ERR_INVALID, "nchw_to_inthwc_fit: bits %d (8, 16), dtype %d", bits, in_dtype);
+    const int amax = bits == 8 ? 255 : 65535;
+    if (C == 1 ? d_alpha != nullptr : (!d_alpha && (alpha_const < 0 || alpha_const > amax)))
+        return set_error(INNFER_ERR_INVALID, "nchw_to_inthwc_fit: a %d-channel image needs %s", C, C == 1 ? "no alpha result" : "an alpha result or a constant alpha in range");
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 g(blocks(hw, 256)), b(256);
+#define NTF(TI, TU, CC) hipLaunchKernelGGL((k_nchw_to_inthwc_fit<TI, TU, CC>), g, b, 0, s, (const TI*)d_colour, (const TI*)d_alpha, hw, denormalize, (float)amax, \
+                                           alpha_const, (TU*)d_img)
+#define NTF_C(TI, TU) do { if (C == 1) NTF(TI, TU, 1); else if (C == 2) NTF(TI, TU, 2); else NTF(TI, TU, 4); } while (0)
+    if (bits == 8 && in_dtype == INNFER_F16) NTF_C(f16, uint8_t);
+    else if (bits == 8) NTF_C(float, uint8_t);
+    else if (in_dtype == INNFER_F16) NTF_C(f16, uint16_t);
+    else NTF_C(float, uint16_t);
+#undef NTF_C
+#undef NTF
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
 }

@@ -210,6 +210,11 @@ SIGNATURES = {
                                           C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "innfer_inthwc_to_nchw": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_nchw_to_inthwc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "innfer_channel_minmax": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "innfer_extract_tiles_u8_fit": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_recompose_u8_fit": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]),
+    "innfer_inthwc_to_nchw_fit": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_nchw_to_inthwc_fit": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
     "innfer_f32conv_packed_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "innfer_pack_f32conv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "innfer_f32conv": (C.c_int, [C.POINTER(F32ConvArgs), C.c_void_p]),
@@ -235,7 +240,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 lib = _lib
 
-ABI_VERSION = 114          # the header revision this binding was written against (INNFER_ABI_VERSION)
+ABI_VERSION = 115          # the header revision this binding was written against (INNFER_ABI_VERSION)
 if _lib.innfer_version() != ABI_VERSION and not _ABI_ANY:
     raise ImportError(f"{LIB_PATH} speaks ABI {_lib.innfer_version()}, this binding {ABI_VERSION}: rebuild with `make`")
 

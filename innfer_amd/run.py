@@ -193,17 +193,27 @@ class Model:
         with torch.no_grad():
             return self._predict(data)
 
-    def run_u8(self, img, normalize=False, fp16=True, out=None):
+    def run_u8(self, img, normalize=False, fp16=True, out=None, fit_channels=False):
         """Image in, image out: tensor2np(self(np2tensor(img, normalize)[.half()]), denormalize=normalize) (run.py:421-431) with the two
         conversions fused into the neighbouring kernels -- the tile gather / the blend on the chop path (innfer_extract_tiles_u8,
         innfer_recompose_u8), the first / last conv otherwise (EngineModule.forward_u8).  Bit-identical to the separate passes.
-        img: uint8 HWC BGR(A), a numpy array (uploaded / downloaded as uint8) or a cuda tensor (stays on the GPU)."""
+        img: uint8 HWC BGR(A), a numpy array (uploaded / downloaded as uint8) or a cuda tensor (stays on the GPU).
+        fit_channels: gray (HW, HW1), gray + alpha (HW2) and BGRA images through a 3 -> 3 network (utils.fit_channels_plan): the colour plane
+        as (g, g, g) / RGB, a non-constant alpha plane as (a, a, a); returns the input's layout at the network's scale."""
         import numpy as np
         from . import lib as L
         from .architectures.engine_module import EngineModule
         from .parallel import run_tile_batches
         from .utils import utils as U
         host = isinstance(img, np.ndarray)
+        if fit_channels:
+            dtype = img.dtype if host else (np.uint8 if img.dtype == torch.uint8 else np.float32)
+            plan = U.fit_channels_plan(tuple(img.shape), dtype, getattr(self.model, 'in_nc', self.in_nc), getattr(self.model, 'out_nc', self.out_nc))
+            if plan == 0:                                       # a 2-D image for a 1-channel network: run as H x W x 1, return H x W
+                r = self.run_u8(img[:, :, None], normalize=normalize, fp16=fp16, out=None if out is None else out[:, :, None])
+                return r[:, :, 0]
+            if plan is not None:
+                return self._run_u8_fit(img, plan, normalize, fp16, out)
         d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img.contiguous()
         if d.dtype != torch.uint8 or d.dim() != 3:
             raise TypeError('run_u8: expected a uint8 HWC image')
@@ -235,6 +245,55 @@ class Model:
                 if out is None:
                     out = torch.empty((y.shape[2], y.shape[3], y.shape[1]), dtype=torch.uint8, device=d.device)
                 L.check(L.lib.innfer_nchw_to_u8hwc(y.data_ptr(), U._dt(y), y.shape[2], y.shape[3], y.shape[1], int(bool(normalize)), out.data_ptr(), stream))
+        return out.cpu().numpy() if host else out
+
+    def _run_u8_fit(self, img, C, normalize, fp16, out):
+        """run_u8(fit_channels=True) of an HW / HWC (C 1, 2, 4) uint8 image with a 3 -> 3 network.  Chop: the colour tiles and the alpha tiles
+        (none when the alpha plane is constant) are gathered into one buffer, run as one tile stream and blended in one pass
+        (innfer_extract_tiles_u8_fit / innfer_recompose_u8_fit).  Otherwise the two planes are split, run as separate forwards (never one batch:
+        train-mode BatchNorm depends on the batch) and merged (innfer_inthwc_to_nchw_fit / innfer_nchw_to_inthwc_fit)."""
+        import numpy as np
+        from . import lib as L
+        from .parallel import run_tile_batches
+        from .utils import utils as U
+        host = isinstance(img, np.ndarray)
+        d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img.contiguous()
+        if d.dtype != torch.uint8:
+            raise TypeError('run_u8: expected a uint8 image')
+        H, W = d.shape[:2]
+        s = int(self.scale or 1)
+        dt = torch.float16 if fp16 else torch.float32
+        code = L.F16 if fp16 else L.F32
+        shape = U.fit_channels_out_shape(tuple(d.shape), s)
+        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous()):
+            raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {shape}')
+        with torch.no_grad(), torch.cuda.device(d.device):
+            stream = torch.cuda.current_stream(d.device).cuda_stream
+            if self.chop:
+                const = U.alpha_constant(d, C) if C in (2, 4) else None
+                alpha = C in (2, 4) and const is None
+                ps = min(H, W, 200)
+                _, ys, xs = L.chop_plan(H, W, ps, 0.5)
+                n = len(ys) * len(xs)
+                tiles = torch.empty(((2 if alpha else 1) * n, 3, ps, ps), dtype=dt, device=d.device)
+                L.check(L.lib.innfer_extract_tiles_u8_fit(d.data_ptr(), C, H, W, int(bool(normalize)), ps, 0.5, 0, n, int(alpha), tiles.data_ptr(), code, stream))
+                hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=self._tile_buffer(tiles))
+                if hr.shape[1] != 3:
+                    raise ValueError(f'run_u8: fit_channels needs a 3-channel result, the network returned {hr.shape[1]}')
+                hr = hr.contiguous()
+                if out is None:
+                    out = torch.empty(shape, dtype=torch.uint8, device=d.device)
+                L.check(L.lib.innfer_recompose_u8_fit(hr.data_ptr(), U._dt(hr), n, hr.shape[2], H, W, 0.5, s, U._dt(hr), int(bool(normalize)), C,
+                                                      int(alpha), -1 if const is None else const, out.data_ptr(), stream))
+            else:
+                colour, alpha, const = U.fit_split(d, normalize=normalize, dtype=dt)
+                y = self._predict(colour)
+                ya = self._predict(alpha) if alpha is not None else None
+                r = U.fit_merge(y, ya, const, C, denormalize=normalize, bits=8)
+                if out is None:
+                    out = r.view(shape)
+                else:
+                    out.copy_(r.view(shape))
         return out.cpu().numpy() if host else out
 
 
@@ -307,6 +366,9 @@ def build_parser():
     parser.add_argument('-no_gpu', '-cpu', required=False, action='store_false', help='Run in CPU if enabled.')
     parser.add_argument('-no_fp16', required=False, action='store_false', help='Disable fp16 mode if needed.')
     parser.add_argument('-norm', required=False, action='store_true', help='Normalizes images in range [-1,1] if set, else [0,1].')
+    # not a reference flag: absent from the parsed namespace unless given, so the reference's flags parse to exactly what they did
+    parser.add_argument('-fit_channels', required=False, action='store_true', default=argparse.SUPPRESS,
+                        help='Run gray, gray + alpha and RGBA images through RGB models (alpha as a gray image through the model).')
     return parser
 
 
@@ -350,6 +412,23 @@ def main(argv=None):
         for m in models:
             if not isinstance(m.model, EngineModule) and not getattr(m.model, '_has_fp32', False):
                 raise NotImplementedError(f"-no_fp16: no fp32-accurate engine is built for '{m.arch}' ({type(m.model).__name__}); drop the flag to run its fp16 engine")
+    fit_channels = getattr(args, 'fit_channels', False)
+    if fit_channels:
+        ins = [getattr(m.model, 'in_nc', m.in_nc) for m in models]
+        outs = [getattr(m.model, 'out_nc', m.out_nc) for m in models]
+
+        def fit_plan(im):
+            # utils.fit_channels_plan for the chain: 0 (H x W for a 1-channel first network) as it says; 1, 2, 4 only when every network is 3 -> 3
+            plan = U.fit_channels_plan(im.shape, im.dtype, ins[0], outs[-1])
+            return plan if plan == 0 or all(i == o == 3 for i, o in zip(ins, outs)) else None
+
+        def fit_chain(t_in):                # the tensor path of one plane: the chain [with the guided filter, the plane's own input as the guide]
+            t = t_in
+            for mod in models:
+                t = mod(t)
+                if use_guided_filter:
+                    t = U.guided_filter(t_in, t, r=1, eps=5e-3)
+            return t
     images = U.get_images_paths(args.input)
     os.makedirs(args.output, exist_ok=True)
     # The loop is pipelined over the images: one thread decodes the next image file while the GPU works on this one, up to sixteen threads
@@ -386,7 +465,15 @@ def main(argv=None):
                 img = U.linear_resize(img, resize)
             if use_modcrop:
                 img = U.modcrop(img, 4)
-            if len(models) == 1 and not use_guided_filter and img.dtype == np.uint8 and img.ndim == 3:
+            plan = fit_plan(img) if fit_channels else None
+            flat = plan is not None and img.ndim == 2                                   # a 2-D image runs as H x W x 1 and is saved 2-D
+            if flat:
+                img = img[:, :, None]
+            if plan and len(models) == 1 and not use_guided_filter and img.dtype == np.uint8:          # plan 1, 2, 4: colour (+ alpha) planes
+                img_out = models[0].run_u8(img, normalize=normalize, fp16=fp16, fit_channels=True)
+            elif plan:
+                img_out = U.fit_channels_forward(fit_chain, img, normalize=normalize, device=device, dtype=torch.float16 if fp16 else torch.float32)
+            elif len(models) == 1 and not use_guided_filter and img.dtype == np.uint8 and img.ndim == 3:
                 img_out = models[0].run_u8(img, normalize=normalize, fp16=fp16)          # conversions fused into the tile gather / blend / first and last conv
             else:
                 t_img = U.np2tensor(img, normalize=normalize, device=device, dtype=torch.float16 if fp16 else torch.float32)
@@ -398,6 +485,8 @@ def main(argv=None):
                 img_out = U.tensor2np(t_out.detach(), denormalize=normalize)
             if args.cf:
                 img_out = U.color_fix(img, img_out)
+            if flat:
+                img, img_out = img[:, :, 0], img_out[:, :, 0]
             out_path = osp.join(args.output, f'{img_name:s}.png')
             fut = writer.submit(save_after, last_write.get(out_path), img, img_out, out_path)
             last_write[out_path] = fut

@@ -155,6 +155,104 @@ def tensor2np(img, rgb2bgr=True, remove_batch=True, data_range=255, denormalize=
     return arr[:, :, 0] if n_dim == 2 else arr
 
 
+# ---------------------------------------------------------------- fit_channels: gray, gray + alpha and BGRA images through an RGB network
+# The colour plane goes through the network as (g, g, g) or RGB, the alpha plane as (a, a, a); a gray or alpha result is mean3 of the network's
+# three channels, ((y0 + y1) + y2) / 3 in fp32 rounded to the result dtype, quantised as tensor2np.  A constant alpha plane is not run: its value is
+# copied.  Kernels: csrc/tiles.hip (include/innfer_amd.h, ABI 115).  The reference runs such images as they are and fails (utils.py:164-248).
+
+def fit_channels_plan(shape, dtype, in_nc, out_nc):
+    """How Model.run_u8(fit_channels=True) / `-fit_channels` run an image of `shape` (HWC or HW) with an in_nc -> out_nc network:
+    1, 2 or 4 -- the image's channel count (2-D = 1): colour (+ alpha) through a 3 -> 3 network; 0 -- a 2-D image for an in_nc == 1 network,
+    run as H x W x 1; None -- the image does not qualify and goes the way it goes without the switch (an image that already has in_nc channels,
+    a network that is not 3 -> 3, any other channel count)."""
+    nd = len(shape)
+    if nd == 2 and in_nc == 1:
+        plan = 0
+    elif in_nc == 3 and out_nc == 3 and (nd == 2 or (nd == 3 and shape[2] in (1, 2, 4))):
+        plan = 1 if nd == 2 else int(shape[2])
+    else:
+        return None
+    if np.dtype(dtype) not in (np.dtype(np.uint8), np.dtype(np.uint16)):
+        raise NotImplementedError(f'fit_channels: uint8 / uint16 images are built, got {np.dtype(dtype)}')
+    return plan
+
+
+def fit_channels_out_shape(shape, scale):
+    """Shape of the image fit_channels returns for an input of `shape` (HW or HWC) and a network of `scale`: the input's layout at scale x the size."""
+    return (shape[0] * scale, shape[1] * scale) + tuple(shape[2:])
+
+
+def _bits(t):
+    return 8 if t.dtype == torch.uint8 else 16
+
+
+def alpha_constant(d_img, C):
+    """The value of the alpha plane (the last channel) of the [H, W, C] uint8 / int16-viewed uint16 GPU image when it is one value everywhere,
+    else None: min and max on the GPU, one 8-byte readback."""
+    H, W = d_img.shape[:2]
+    mm = torch.empty(2, dtype=torch.int32, device=d_img.device)
+    with _on(d_img):
+        L.check(L.lib.innfer_channel_minmax(d_img.data_ptr(), _bits(d_img), H, W, C, C - 1, mm.data_ptr(), _stream(d_img)))
+    lo, hi = mm.tolist()
+    return lo if lo == hi else None
+
+
+def fit_split(d_img, normalize=False, dtype=torch.float32):
+    """np2tensor of the two planes of an [H, W] / [H, W, C] (C 1, 2, 4) uint8 / int16-viewed uint16 GPU image:
+    (colour [1, 3, H, W], alpha [1, 3, H, W] or None, alpha_const or None).  alpha is None when the image has no alpha plane or a constant one."""
+    x = d_img.contiguous()
+    H, W = x.shape[:2]
+    C = x.shape[2] if x.dim() == 3 else 1
+    const = alpha_constant(x, C) if C in (2, 4) else None
+    colour = torch.empty((1, 3, H, W), dtype=dtype, device=x.device)
+    alpha = torch.empty_like(colour) if C in (2, 4) and const is None else None
+    maxval = 255.0 if _bits(x) == 8 else 65535.0
+    with _on(x):
+        L.check(L.lib.innfer_inthwc_to_nchw_fit(x.data_ptr(), _bits(x), H, W, C, int(bool(normalize)), maxval, colour.data_ptr(),
+                                                alpha.data_ptr() if alpha is not None else None, _dt(colour), _stream(x)))
+    return colour, alpha, const
+
+
+def fit_merge(colour, alpha, alpha_const, C, denormalize=False, bits=8, out=None):
+    """tensor2np of the two results into the image's layout, on the GPU: colour / alpha [1, 3, H', W'] results of one dtype (alpha None when
+    alpha_const holds the constant alpha, or C == 1) -> [H', W', C] uint8 (bits 8) or int16-viewed uint16 (bits 16) tensor (`out` if given)."""
+    colour = colour.contiguous()
+    if colour.dim() != 4 or colour.shape[:2] != (1, 3):
+        raise ValueError(f'fit_merge: expected a [1, 3, H, W] result, got {tuple(colour.shape)}')
+    if alpha is not None:
+        alpha = alpha.contiguous()
+        if alpha.shape != colour.shape or alpha.dtype != colour.dtype:
+            raise ValueError('fit_merge: the alpha result must match the colour result in shape and dtype')
+    H, W = colour.shape[2:]
+    if out is None:
+        out = torch.empty((H, W, C), dtype=torch.uint8 if bits == 8 else torch.int16, device=colour.device)
+    with _on(colour):
+        L.check(L.lib.innfer_nchw_to_inthwc_fit(colour.data_ptr(), alpha.data_ptr() if alpha is not None else None, _dt(colour), H, W, C,
+                                                int(bool(denormalize)), bits, -1 if alpha_const is None else int(alpha_const), out.data_ptr(), _stream(colour)))
+    return out
+
+
+def fit_channels_forward(fn, img, normalize=False, device='cuda', dtype=torch.float32):
+    """The tensor path of fit_channels (model chains, the guided filter, uint16 images): img, an HW / HWC (C 1, 2, 4) uint8 or uint16 numpy image,
+    -> the same layout and dtype at the network's scale.  fn maps a [1, 3, H, W] tensor of `dtype` to the network's [1, 3, H', W'] result; it runs on
+    the colour plane and, as its own call, on a non-constant alpha plane."""
+    if not isinstance(img, np.ndarray) or img.ndim not in (2, 3):
+        raise TypeError('fit_channels_forward: expected an HW / HWC numpy image')
+    if fit_channels_plan(img.shape, img.dtype, 3, 3) is None:
+        raise ValueError(f'fit_channels_forward: a {img.shape[2]}-channel image has no fit_channels layout (1, 2 or 4 channels)')
+    host = np.ascontiguousarray(img)
+    bits = 8 if host.dtype == np.uint8 else 16
+    d_img = torch.from_numpy(host if bits == 8 else host.view(np.int16)).to(device)
+    C = img.shape[2] if img.ndim == 3 else 1
+    colour, alpha, const = fit_split(d_img, normalize=normalize, dtype=dtype)
+    y = fn(colour)
+    ya = fn(alpha) if alpha is not None else None
+    arr = fit_merge(y, ya, const, C, denormalize=normalize, bits=bits).cpu().numpy()
+    if bits == 16:
+        arr = arr.view(np.uint16)
+    return arr[:, :, 0] if img.ndim == 2 else arr
+
+
 # ---------------------------------------------------------------- files (utils.py:36-133): the image loop's codec hand-off
 def _suffixes(extensions):
     return tuple(extensions) if not isinstance(extensions, str) else (extensions,)
