@@ -45,8 +45,8 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  innfer_version() returns the library's; a binding should compare. */
-#define INNFER_ABI_VERSION 115
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  innfer_version() returns the library's; a binding should compare. */
+#define INNFER_ABI_VERSION 116
 int innfer_version(void);
 const char* innfer_last_error(void);
 
@@ -67,6 +67,21 @@ int innfer_rrdbnet_create(innfer_net_t* out, int in_nc, int out_nc, int nf, int 
  * PixelShuffle(3), nf 64 only) instead of 'upconv'.  innfer_rrdbnet_create(...) = innfer_rrdbnet_create_ex(..., 3, 1, 0).  (104) */
 int innfer_rrdbnet_create_ex(innfer_net_t* out, int in_nc, int out_nc, int nf, int nb,
                              int gc, int scale, int plus, int nr, int act, int pixelshuffle_up);
+
+/* The same with BasicSR's RRDBNet input stage (Real-ESRGAN x2plus and every BasicSR model of scale 2 or 1): unshuffle = r in {1, 2, 4} puts pixel_unshuffle(x, r) in
+ * front of the first conv, which then has in_nc r^2 input channels (torch order c r^2 + i r + j; `model.0` reports C = in_nc r^2 and takes [nf, in_nc r^2, 3, 3]).  The
+ * unshuffled tensor is never written: the conv reads a 3r x 3r window of the image at stride r.  With r > 1 (built for in_nc 3) H x W of innfer_net_workspace_bytes /
+ * innfer_net_flops / innfer_net_forward[_timed] is the IMAGE: every layer runs on the LR grid h x w = ceil(H / r) x ceil(W / r), an image whose size is not a multiple
+ * of r is reflect-padded bottom / right (pad <= 3, needs H, W >= 4) and the result is [N, out_nc, scale h, scale w] -- the caller crops it to (scale / r) H x (scale / r) W.
+ * innfer_net_scale still answers `scale`.  r = 1 is innfer_rrdbnet_create_ex.  (116) */
+int innfer_rrdbnet_create_ex2(innfer_net_t* out, int in_nc, int out_nc, int nf, int nb,
+                              int gc, int scale, int plus, int nr, int act, int pixelshuffle_up, int unshuffle);
+/* The first conv of such a network alone (for tests): conv3x3(pixel_unshuffle(x, unshuffle)) + bias + act (0 none, 1 LeakyReLU(0.2), 2 ReLU) of N images [in_nc 3, H, W]
+ * (planar fp16 / fp32, or uint8 HWC BGR with np2tensor's `normalize` and fp16 rounding as in innfer_net_set_u8_io) into a blocked slab of K (32 | 64) channels on the
+ * LR grid (group stride in elements; lo != 0: the (hi, lo) pair of the fp32-accurate mode, lo elements apart).  Host fp32 weights [K, 3 r^2, 3, 3]; packs, uploads,
+ * launches and waits.  (116) */
+int innfer_first_conv_unshuffle(const void* d_in, int in_dtype, int normalize, int fp16_mode, int N, int in_nc, int H, int W, int unshuffle,
+                                const float* h_weight_oihw, const float* h_bias, int K, int act, void* d_slab, int64_t group_stride, int64_t lo, void* stream);
 
 /* SRResNet / SRGAN with the reference defaults (norm none, ReLU, CNA,
  * pixelshuffle, res_scale 1: utils/defaults.py:53-67). */

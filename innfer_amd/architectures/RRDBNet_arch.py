@@ -5,7 +5,7 @@ import ctypes as C
 
 from .. import lib as L
 from .engine_module import EngineModule
-from .keys import mrrdb_key_of, mrrdbnet_shapes, rrdbnet_shapes
+from .keys import REALESRGAN_UNSHUFFLE, mrrdb_key_of, mrrdbnet_shapes, realesrgan_key_map, realesrgan_shapes, rrdbnet_shapes
 
 
 # `finalact` (block.py:81-101 act()) -> activation code of the last conv's epilogue
@@ -122,3 +122,29 @@ class MRRDBNet(EngineModule):
 
     def _param_key(self, engine_key):
         return mrrdb_key_of(engine_key, self.nb)
+
+
+class RealESRGANNet(EngineModule):
+    """BasicSR's RRDBNet (the Real-ESRGAN x4plus / x4plus_anime_6B / x2plus releases and every model trained with BasicSR): the old-arch 4x graph under
+    BasicSR's parameter names; scale 2 / 1 put pixel_unshuffle(x, 2 / 4) in front of conv_first, which the engine folds into that conv's addressing
+    (csrc/conv_first_unshuffle.hip).  Constructor surface and state-dict keys are BasicSR's.  An image whose size is not a multiple of the unshuffle
+    factor is reflect-padded bottom / right inside the first conv and the result cropped, as BasicSR's inference tools do."""
+
+    def __init__(self, num_in_ch=3, num_out_ch=3, scale=4, num_feat=64, num_block=23, num_grow_ch=32):
+        if scale not in REALESRGAN_UNSHUFFLE:
+            raise NotImplementedError(f'RealESRGANNet: scale={scale} (BasicSR RRDBNet: 4, 2 or 1)')
+        if num_grow_ch != 32:
+            raise NotImplementedError(f'RealESRGANNet: num_grow_ch={num_grow_ch} is not built on the HIP path (32 only)')
+        super().__init__(realesrgan_shapes(num_in_ch, num_out_ch, scale, num_feat, num_block, 32))
+        self.in_nc, self.out_nc, self.nf, self.nb, self.gc = num_in_ch, num_out_ch, num_feat, num_block, 32
+        self.upscale = scale                              # the true scale: 4 // unshuffle
+        self.unshuffle = REALESRGAN_UNSHUFFLE[scale]
+        self._old2new = {old: new for new, old in realesrgan_key_map(num_block).items()}
+
+    def _create_handle(self):
+        h = C.c_void_p()
+        L.check(L.lib.innfer_rrdbnet_create_ex2(C.byref(h), self.in_nc, self.out_nc, self.nf, self.nb, self.gc, 4, 0, 3, 1, 0, self.unshuffle))
+        return h
+
+    def _param_key(self, engine_key):
+        return self._old2new[engine_key]

@@ -25,6 +25,8 @@ def get_network(opt_net):
         from .WBCNet_arch import UnetGeneratorWBC as net
     elif kind == 'mrrdb_net':
         from .RRDBNet_arch import MRRDBNet as net
+    elif kind == 'realesrgan_net':
+        from .RRDBNet_arch import RealESRGANNet as net
     else:
         raise NotImplementedError('Model [{:s}] not recognized'.format(kind))
     return net(**opt_net)

@@ -55,6 +55,14 @@ class EngineModule(nn.Module):
         self.fused_tail = True       # innfer_net_set_fused_tail: HR_conv0 -> conv_last as one kernel where the shapes allow it (results agree to the last fp16 rounding with the two-launch form)
         self.residual_lds = 1        # innfer_net_set_residual_lds: the dense block's `x5 * 0.2 + x` takes x from the conv's own staged LDS tiles -- 1 the RRDB-end blocks (measured gain), 2 every block, 0 never (all agree to the last fp16 rounding)
 
+    unshuffle = 1                    # pixel_unshuffle factor the engine folds into its first conv (RealESRGANNet: 2 / 4): the result has (engine scale // unshuffle) x the input's size
+
+    def _io_sizes(self, H, W, s):
+        """(rows, columns) the engine writes for an H x W input and those of the result: the engine runs on ceil(H / r) x ceil(W / r) (reflect pad to a
+        multiple of r inside the first conv) and the padded rows / columns are cropped."""
+        r = self.unshuffle
+        return (-(-H // r) * s, -(-W // r) * s), (H * s // r, W * s // r)
+
     # ---- subclasses provide the C handle ------------------------------------
     def _create_handle(self):
         raise NotImplementedError
@@ -197,15 +205,19 @@ class EngineModule(nn.Module):
         x = x.contiguous()
         N, _, H, W = x.shape
         s = L.lib.innfer_net_scale(self._handle)
-        out = _result_tensor(out, (N, self.out_nc, H * s, W * s), x)
+        full, want = self._io_sizes(H, W, s)
+        out = _result_tensor(out, (N, self.out_nc) + want, x)
+        res = out if full == want else torch.empty((N, self.out_nc) + full, dtype=x.dtype, device=x.device)
         need = L.lib.innfer_net_workspace_bytes(self._handle, N, H, W)
         if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
         dt = L.F16 if x.dtype == torch.float16 else L.F32
         stream = torch.cuda.current_stream(x.device).cuda_stream
-        L.check(L.lib.innfer_net_forward(self._handle, x.data_ptr(), dt, out.data_ptr(), dt, N, H, W,
+        L.check(L.lib.innfer_net_forward(self._handle, x.data_ptr(), dt, res.data_ptr(), dt, N, H, W,
                                          self._ws.data_ptr(), self._ws.numel(), stream))
+        if res is not out:               # the rows / columns of the reflect pad
+            out.copy_(res[:, :, :want[0], :want[1]])
         return out
 
     def forward_u8(self, img, normalize=False, fp16=True, out=None):
@@ -232,7 +244,8 @@ class EngineModule(nn.Module):
             if Cc != self.in_nc:
                 raise ValueError(f'forward_u8: the image has {Cc} channels, the network takes {self.in_nc}')
             s = L.lib.innfer_net_scale(self._handle)
-            shape = (N, H * s, W * s, self.out_nc) if batched else (H * s, W * s, self.out_nc)
+            full, want = self._io_sizes(H, W, s)
+            shape = (N,) + want + (self.out_nc,) if batched else want + (self.out_nc,)
             if out is None:
                 out = torch.empty(shape, dtype=torch.uint8, device=x.device)
             elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
@@ -241,8 +254,11 @@ class EngineModule(nn.Module):
             if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
                 self._ws = None
                 self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
-            L.check(L.lib.innfer_net_forward(self._handle, x.data_ptr(), L.U8, out.data_ptr(), L.U8, N, H, W,
+            res = out if full == want else torch.empty((N,) + full + (self.out_nc,), dtype=torch.uint8, device=x.device)
+            L.check(L.lib.innfer_net_forward(self._handle, x.data_ptr(), L.U8, res.data_ptr(), L.U8, N, H, W,
                                              self._ws.data_ptr(), self._ws.numel(), torch.cuda.current_stream(x.device).cuda_stream))
+            if res is not out:
+                out.copy_(res[:, :want[0], :want[1]] if batched else res[0, :want[0], :want[1]])
         return out
 
     def release_workspace(self):
@@ -259,7 +275,8 @@ class EngineModule(nn.Module):
             L.check(L.lib.innfer_net_set_precision(self._handle, int(dtype == torch.float32)))
             elt = 4 if dtype == torch.float32 else 2
             s = L.lib.innfer_net_scale(self._handle)
-            return L.lib.innfer_net_workspace_bytes(self._handle, b, ps, ps) + b * (self.in_nc * ps * ps + 2 * self.out_nc * (ps * s) ** 2) * elt
+            (hh, ww), _ = self._io_sizes(ps, ps, s)
+            return L.lib.innfer_net_workspace_bytes(self._handle, b, ps, ps) + b * (self.in_nc * ps * ps + 2 * self.out_nc * hh * ww) * elt
 
     def _out_shape(self, N, H, W, device=None):
         """Shape of forward's result for an [N, in_nc, H, W] input (the scale is the engine's)."""
@@ -267,7 +284,7 @@ class EngineModule(nn.Module):
         with torch.cuda.device(device):
             self._engine_on(device)
             s = L.lib.innfer_net_scale(self._handle)
-        return (N, self.out_nc, H * s, W * s)
+        return (N, self.out_nc) + self._io_sizes(H, W, s)[1]
 
     def flops(self, N, H, W, device=None):
         device = self._home_device(device)

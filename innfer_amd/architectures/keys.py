@@ -85,6 +85,49 @@ def mrrdb_key_of(old_key, nb):
     return "RRDB_trunk." + old_key[len("model.1.sub."):-2]
 
 
+# BasicSR's RRDBNet (rrdbnet_arch.py; the Real-ESRGAN releases): its fixed conv names -> the engine's old-arch names for the same convs.  THE table: the
+# names are BasicSR's as published; a correction goes here and nowhere else.  '{nb}' is the number of blocks.
+REALESRGAN_FIXED = (
+    ("conv_first", "model.0"),
+    ("conv_body", "model.1.sub.{nb}"),
+    ("conv_up1", "model.3"),
+    ("conv_up2", "model.6"),
+    ("conv_hr", "model.8"),
+    ("conv_last", "model.10"),
+)
+# a dense-block conv: BasicSR 'body.<b>.rdb<m>.conv<k>' <-> old-arch 'model.1.sub.<b>.RDB<m>.conv<k>.0'
+REALESRGAN_BLOCK = ("body.{b}.rdb{m}.conv{k}", "model.1.sub.{b}.RDB{m}.conv{k}.0")
+REALESRGAN_UNSHUFFLE = {4: 1, 2: 2, 1: 4}          # BasicSR `scale` -> pixel_unshuffle factor in front of conv_first (the graph behind it is always the 4x one)
+
+
+def realesrgan_key_map(nb):
+    """{BasicSR conv prefix: old-arch conv prefix} of an nb-block BasicSR RRDBNet ('.weight' / '.bias' follow both)."""
+    m = {new: old.format(nb=nb) for new, old in REALESRGAN_FIXED}
+    for b in range(nb):
+        for r in (1, 2, 3):
+            for k in range(1, 6):
+                m[REALESRGAN_BLOCK[0].format(b=b, m=r, k=k)] = REALESRGAN_BLOCK[1].format(b=b, m=r, k=k)
+    return m
+
+
+def realesrgan_key_of(old_key, nb):
+    """Old-arch conv key of the engine -> BasicSR's name for the same conv."""
+    inv = {old: new for new, old in realesrgan_key_map(nb).items()}
+    return inv[old_key]
+
+
+def realesrgan_shapes(num_in_ch=3, num_out_ch=3, scale=4, num_feat=64, num_block=23, num_grow_ch=32):
+    """State-dict key -> shape of BasicSR's RRDBNet: the old-arch 4x graph under BasicSR's names, conv_first taking num_in_ch * r^2 channels
+    (r = 1, 2, 4 for scale 4, 2, 1: pixel_unshuffle in front of it)."""
+    r = REALESRGAN_UNSHUFFLE[scale]
+    old = rrdbnet_shapes(num_in_ch * r * r, num_out_ch, num_feat, num_block, num_grow_ch, 4)
+    s = {}
+    for new, o in realesrgan_key_map(num_block).items():
+        s[new + ".weight"] = old[o + ".weight"]
+        s[new + ".bias"] = old[o + ".bias"]
+    return s
+
+
 def srresnet_layout(nb, norm=False, mode='CNA'):
     """Positions of a ResNetBlock's / LR_conv's layers inside the flattened Sequentials (SRResNet_arch.py:23-27,68-86; block.py:242-254,
     B.sequential flattens nested Sequentials): {engine key -> (conv key, BatchNorm in front of the conv or None, BatchNorm behind it or None)}.

@@ -156,6 +156,21 @@ struct FirstConvLaunch {
 };
 int first_conv_launch(const FirstConvLaunch& L, hipStream_t s);
 
+// ---- first conv behind a folded pixel_unshuffle(r), r = 2 | 4 (conv_first_unshuffle.hip): BasicSR RRDBNet scale 2 / 1 -------------
+struct FirstUnshuffleLaunch {
+    const void* in; int in_f32; int Cin;          // the full-resolution image, NCHW planar; Cin = 3 (the conv itself has Cin r^2 input channels)
+    int in_u8, in_norm, in_round16;               // as FirstConvLaunch
+    int r;                                        // unshuffle factor
+    const void* wpk;                              // first_unshuffle_pack image (device)
+    const float* bias;
+    f16* out; long out_gstride; f16* out2; long out2_gstride;   // slabs on the LR grid ceil(H / r) x ceil(W / r)
+    int K; int N, H, W; int act;                  // H x W: the image (reflect-padded bottom / right to a multiple of r inside the kernel)
+    long out_lo, out2_lo;
+};
+size_t first_unshuffle_packed_bytes(int K, int r);
+void first_unshuffle_pack(const float* w_oihw, int K, int r, void* packed);   // host; w [K][3 r^2][3][3]
+int first_unshuffle_launch(const FirstUnshuffleLaunch& L, hipStream_t s);
+
 // ---- layout / tiles / blend / pre-post (tiles.hip) ---------------------------
 int nchw_to_slab(const void* src, int src_f32, f16* slab, long gstride, int ch_off, int N, int C, int H, int W, hipStream_t s);
 int slab_to_nchw(const f16* slab, long gstride, int ch_off, void* dst, int dst_f32, int N, int C, int H, int W, hipStream_t s);

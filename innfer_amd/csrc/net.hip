@@ -137,6 +137,8 @@ struct innfer_net {
     int ps_pc = INNFER_PS_PC_DEFAULT;   // PixelShuffle(2) stages on the producer / consumer kernel (phase-major panels); 0 (A/B builds): the two-workgroup kernel of rounds 1-4
     int res_lds = 1;             // the dense block's x5 * 0.2 + x with x taken from the conv's own staged LDS tiles (innfer_net_set_residual_lds; conv3x3_pc RLDS): 1 = where the RRDB's residual follows, 2 = every block
     bool plus = false;           // ESRGAN+ residual paths (RRDBNet_arch.py:155-160)
+    int unshuffle = 1;           // innfer_rrdbnet_create_ex2: pixel_unshuffle(r) in front of the first conv (BasicSR RRDBNet scale 2 / 1), folded into that conv (conv_first_unshuffle.hip);
+                                 // the forward's H x W is the image, every layer runs on the LR grid ceil(H / r) x ceil(W / r)
     int fp32 = 0;                // innfer_net_set_precision: 1 = fp32-accurate forward on split operands (conv3x3.hip SPLIT), the reference's -no_fp16 mode (run.py:345,421-422)
     std::vector<ConvSlot> convs;
 };
@@ -164,6 +166,11 @@ extern "C" int innfer_rrdbnet_create(innfer_net_t* out, int in_nc, int out_nc, i
 
 extern "C" int innfer_rrdbnet_create_ex(innfer_net_t* out, int in_nc, int out_nc, int nf, int nb,
                                         int gc, int scale, int plus, int nr, int act, int pixelshuffle_up) {
+    return innfer_rrdbnet_create_ex2(out, in_nc, out_nc, nf, nb, gc, scale, plus, nr, act, pixelshuffle_up, 1);
+}
+
+extern "C" int innfer_rrdbnet_create_ex2(innfer_net_t* out, int in_nc, int out_nc, int nf, int nb,
+                                         int gc, int scale, int plus, int nr, int act, int pixelshuffle_up, int unshuffle) {
     if (!out) return set_error(INNFER_ERR_INVALID, "rrdbnet_create: null out");
     if (nr < 1 || nr > 64 || (act != 1 && act != 2))
         return set_error(INNFER_ERR_UNSUPPORTED, "rrdbnet_create: nr=%d act=%d (built: nr >= 1; act 1 LeakyReLU(0.2), 2 ReLU)", nr, act);
@@ -175,11 +182,16 @@ extern "C" int innfer_rrdbnet_create_ex(innfer_net_t* out, int in_nc, int out_nc
         return set_error(INNFER_ERR_UNSUPPORTED, "rrdbnet_create: nf=%d gc=%d (need nf in {32,64}, gc %% 32 == 0)", nf, gc);
     if (in_nc < 1 || in_nc > 8 || out_nc < 1 || out_nc > 16 || nb < 1)
         return set_error(INNFER_ERR_INVALID, "rrdbnet_create: in_nc=%d out_nc=%d nb=%d", in_nc, out_nc, nb);
+    if (unshuffle != 1 && unshuffle != 2 && unshuffle != 4)
+        return set_error(INNFER_ERR_UNSUPPORTED, "rrdbnet_create: unshuffle %d (built: 1, 2, 4)", unshuffle);
+    if (unshuffle > 1 && in_nc != 3)
+        return set_error(INNFER_ERR_UNSUPPORTED, "rrdbnet_create: unshuffle %d with in_nc=%d (the folded pixel_unshuffle is built for in_nc 3: 12 or 48 channels into the first conv)", unshuffle, in_nc);
     innfer_net* net = new innfer_net();
+    net->unshuffle = unshuffle;
     net->kind = 0; net->in_nc = in_nc; net->out_nc = out_nc; net->nf = nf; net->nb = nb;
     net->gc = gc; net->scale = scale; net->n_up = n_upscale(scale); net->plus = plus != 0;
     net->nr = nr; net->trunk_act = act; net->ps_up = pixelshuffle_up != 0;
-    add_conv(net, "model.0", nf, in_nc, true);
+    add_conv(net, "model.0", nf, in_nc * unshuffle * unshuffle, true);
     for (int b = 0; b < nb; ++b)
         for (int r = 1; r <= nr; ++r) {
             char rdb[96];        // nr == 3: attributes RDB1..RDB3, else nn.Sequential `RDBs` (RRDBNet_arch.py:73-88)
@@ -297,7 +309,11 @@ extern "C" int innfer_net_set_conv(innfer_net_t net, int idx, const float* w, co
     ConvSlot& c = net->convs[idx];
     std::vector<char> host;
     size_t bias_n;
-    if (c.first) {
+    if (c.first && net->unshuffle > 1) {          // the LDS image of conv_first_unshuffle.hip: hi | lo fragments, k in window order
+        host.resize(first_unshuffle_packed_bytes(c.K, net->unshuffle));
+        first_unshuffle_pack(w, c.K, net->unshuffle, host.data());
+        bias_n = c.K;
+    } else if (c.first) {
         host.resize((size_t)c.C * 9 * c.K * sizeof(float));
         float* d = (float*)host.data();
         for (int ci = 0; ci < c.C; ++ci)
@@ -452,6 +468,7 @@ extern "C" int innfer_net_set_final_act(innfer_net_t net, int act) {
 
 extern "C" double innfer_net_flops(innfer_net_t net, int N, int H, int W) {
     if (!net) return 0.0;
+    H = (H + net->unshuffle - 1) / net->unshuffle; W = (W + net->unshuffle - 1) / net->unshuffle;      // the LR grid
     double px = (double)N * H * W, f = 0.0;
     const int nconv = (int)net->convs.size();
     // resolution multiplier per conv: trunk at 1x, up-conv u at 4^(u+1) (RRDB: conv runs AFTER the
@@ -503,7 +520,7 @@ static Carve carve(const innfer_net* net, int N, int H, int W) {
 
 extern "C" size_t innfer_net_workspace_bytes(innfer_net_t net, int N, int H, int W) {
     if (!net || N <= 0 || H <= 0 || W <= 0) return 0;
-    return carve(net, N, H, W).total;
+    return carve(net, N, (H + net->unshuffle - 1) / net->unshuffle, (W + net->unshuffle - 1) / net->unshuffle).total;
 }
 
 namespace {
@@ -692,6 +709,19 @@ int do_first(const FirstConvLaunch& F, hipStream_t s) {
     return timed_end(s, 2.0 * 9.0 * F.K * F.Cin * px, px * (F.Cin * (F.in_f32 ? 4.0 : 2.0) + F.K * 2.0 * (F.out2 ? 2 : 1)), 0);
 }
 
+// the first conv behind the folded pixel_unshuffle: FLOPs and bytes per LR pixel (3 r^2 input values, K outputs per slab), kind 0 like every first conv
+int do_first_unshuffle(const FirstUnshuffleLaunch& F, hipStream_t s) {
+    int rc = timed_begin(s);
+    if (rc) return rc;
+    rc = first_unshuffle_launch(F, s);
+    if (rc) return rc;
+    rc = debug_after("first_conv_unshuffle", s);
+    if (rc) return rc;
+    const int cin = F.Cin * F.r * F.r;
+    const double px = (double)F.N * ((F.H + F.r - 1) / F.r) * ((F.W + F.r - 1) / F.r);
+    return timed_end(s, 2.0 * 9.0 * F.K * cin * px, px * (cin * (F.in_u8 ? 1.0 : F.in_f32 ? 4.0 : 2.0) + F.K * 2.0 * (F.out2 ? 2 : 1)), 0);
+}
+
 struct Plan {                    // one MFMA conv in the launch list
     ConvLaunch L;
 };
@@ -754,6 +784,8 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     if (out_dtype == INNFER_U8 && net->out_nc > 4) return set_error(INNFER_ERR_UNSUPPORTED, "forward: a uint8 image has at most 4 channels (out_nc %d)", net->out_nc);
     for (auto& c : net->convs)
         if (!c.loaded) return set_error(INNFER_ERR_INVALID, "forward: weights of '%s' were never set", c.key.c_str());
+    const int img_h = H, img_w = W;               // (unshuffle > 1: the image; H x W below is the LR grid every layer runs on)
+    H = (H + net->unshuffle - 1) / net->unshuffle; W = (W + net->unshuffle - 1) / net->unshuffle;
     const Carve cv = carve(net, N, H, W);
     if (ws_bytes < cv.total) return set_error(INNFER_ERR_WORKSPACE, "forward: workspace %zu < %zu bytes", ws_bytes, cv.total);
     hipStream_t s = (hipStream_t)stream;
@@ -774,7 +806,17 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     f16* trunk = (f16*)(ws + cv.trunk);
     int ci = 0;
 
-    {   // conv_first: NCHW input -> fea (+ slab[0][0:nf))
+    if (net->unshuffle > 1) {   // conv_first(pixel_unshuffle(x, r)): the image -> fea + slab[0][0:nf) on the LR grid
+        const ConvSlot& c0 = net->convs[ci++];
+        FirstUnshuffleLaunch F{};
+        F.in = d_in; F.in_f32 = in_dtype == INNFER_F32; F.Cin = net->in_nc; F.r = net->unshuffle; F.wpk = c0.d_w; F.bias = c0.d_b;
+        F.in_u8 = in_dtype == INNFER_U8; F.in_norm = net->u8_normalize; F.in_round16 = net->u8_round16;
+        F.out = fea; F.out_gstride = G; F.out2 = slab[0]; F.out2_gstride = G;
+        F.K = nf; F.N = N; F.H = img_h; F.W = img_w; F.act = 0;
+        F.out_lo = LO; F.out2_lo = LO;
+        int rc = do_first_unshuffle(F, s);
+        if (rc) return rc;
+    } else {   // conv_first: NCHW input -> fea (+ slab[0][0:nf))
         const ConvSlot& c0 = net->convs[ci++];
         FirstConvLaunch F{};
         F.in = d_in; F.in_f32 = in_dtype == INNFER_F32; F.Cin = c0.C; F.w = (const float*)c0.d_w; F.bias = c0.d_b;
@@ -1138,4 +1180,34 @@ extern "C" int innfer_nchw_to_slab(const void* d_src, int src_dtype, void* d_sla
 extern "C" int innfer_slab_to_nchw(const void* d_slab, int64_t group_stride, int ch_off, void* d_dst, int dst_dtype,
                                    int N, int C, int H, int W, void* stream) {
     return slab_to_nchw((const f16*)d_slab, group_stride, ch_off, d_dst, dst_dtype == INNFER_F32, N, C, H, W, (hipStream_t)stream);
+}
+
+// conv3x3(pixel_unshuffle(x, r)) alone, for tests: packs and uploads the weights, launches conv_first_unshuffle.hip's kernel into a slab on the LR grid, waits.
+extern "C" int innfer_first_conv_unshuffle(const void* d_in, int in_dtype, int normalize, int fp16_mode, int N, int in_nc, int H, int W, int unshuffle,
+                                           const float* h_weight_oihw, const float* h_bias, int K, int act, void* d_slab, int64_t group_stride, int64_t lo, void* stream) {
+    if (!d_in || !h_weight_oihw || !d_slab) return set_error(INNFER_ERR_INVALID, "first_conv_unshuffle: null argument");
+    if (in_dtype != INNFER_F16 && in_dtype != INNFER_F32 && in_dtype != INNFER_U8) return set_error(INNFER_ERR_INVALID, "first_conv_unshuffle: bad dtype");
+    if ((unshuffle != 2 && unshuffle != 4) || in_nc != 3 || (K != 32 && K != 64) || act < 0 || act > 2 || N <= 0 || H <= 0 || W <= 0)
+        return set_error(INNFER_ERR_UNSUPPORTED, "first_conv_unshuffle: unshuffle %d (2 | 4), in_nc %d (3), K %d (32 | 64), act %d (0..2)", unshuffle, in_nc, K, act);
+    const long px = (long)N * ((H + unshuffle - 1) / unshuffle) * ((W + unshuffle - 1) / unshuffle);
+    if (group_stride < px * 32 || lo < 0) return set_error(INNFER_ERR_INVALID, "first_conv_unshuffle: group_stride %ld < %ld", (long)group_stride, px * 32);
+    std::vector<char> host(first_unshuffle_packed_bytes(K, unshuffle));
+    first_unshuffle_pack(h_weight_oihw, K, unshuffle, host.data());
+    std::vector<float> bias(K, 0.f);
+    if (h_bias) for (int k = 0; k < K; ++k) bias[k] = h_bias[k];
+    void* d_w = nullptr; float* d_b = nullptr;
+    INNFER_HIP(hipMalloc(&d_w, host.size()));
+    if (hipMalloc((void**)&d_b, K * sizeof(float)) != hipSuccess) { (void)hipFree(d_w); return set_error(INNFER_ERR_NOMEM, "first_conv_unshuffle: out of device memory"); }
+    int rc = INNFER_OK;
+    if (hipMemcpy(d_w, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_b, bias.data(), K * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        rc = set_error(INNFER_ERR_HIP, "first_conv_unshuffle: copying the weights failed");
+    if (rc == INNFER_OK) {
+        FirstUnshuffleLaunch F{};
+        F.in = d_in; F.in_f32 = in_dtype == INNFER_F32; F.Cin = in_nc; F.in_u8 = in_dtype == INNFER_U8; F.in_norm = normalize != 0; F.in_round16 = fp16_mode != 0;
+        F.r = unshuffle; F.wpk = d_w; F.bias = d_b; F.out = (f16*)d_slab; F.out_gstride = group_stride; F.K = K; F.N = N; F.H = H; F.W = W; F.act = act; F.out_lo = lo;
+        rc = first_unshuffle_launch(F, (hipStream_t)stream);
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "first_conv_unshuffle: the launch failed");
+    }
+    (void)hipFree(d_w); (void)hipFree(d_b);
+    return rc;
 }

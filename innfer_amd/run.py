@@ -16,13 +16,14 @@ import torch
 
 from .architectures import get_network
 from .utils.defaults import get_network_G_config
-from .utils.utils import extract_patches_2d, mod2normal, recompose_tensor, swa2normal
+from .utils.utils import extract_patches_2d, mod2normal, recompose_tensor, swa2normal, unwrap_params
 
 # families the HIP engine implements; the other branches of the reference's key
 # sniffing are recognised and refused explicitly
 _SNIFF = (
     ('SCPA_trunk.0.conv1_a.weight', 'pan'),
     ('model.1.sub.0.res.0.weight', 'srgan'),
+    ('body.0.rdb1.conv1.weight', 'realesrgan'),      # BasicSR's RRDBNet (with conv_first.weight): ahead of the new-arch probe, which shares conv_first
     ('conv_first.weight', 'mesrgan'),
     ('model.0.weight', 'esrgan'),
     ('CFEM.0.weight', 'ppon'),
@@ -35,16 +36,19 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
     shapes -- host logic of Model.load_model / infer_params (run.py:44-72,103-165).
     Returns dict(arch, scale, in_nc, out_nc, nf, nb, plus, net_params, state_dict)
     where state_dict has been SWA-unwrapped / converted to old-arch keys."""
+    state_dict = unwrap_params(state_dict)
     if 'n_averaged' in state_dict:
         state_dict = swa2normal(state_dict)
     for probe, arch in _SNIFF:
-        if probe in state_dict:
+        if probe in state_dict and (arch != 'realesrgan' or 'conv_first.weight' in state_dict):
             break
     else:
         raise Exception("Could not infer model parameters.")
     if arch == 'mesrgan':                    # new-arch checkpoints run as old-arch (run.py:57-61)
         state_dict = mod2normal(state_dict)
         arch = 'esrgan'
+    if arch == 'realesrgan':
+        return _infer_realesrgan(state_dict, in_nc)
     if arch == 'pan':
         return _infer_pan(state_dict, scale, in_nc, out_nc)
     if arch == 'ppon':
@@ -76,6 +80,29 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
         cfg['plus'] = info['plus']
     info['net_params'] = get_network_G_config(cfg, info['scale'])
     return info
+
+
+def _infer_realesrgan(state_dict, in_nc=3):
+    """BasicSR RRDBNet checkpoints (Real-ESRGAN x4plus, x4plus_anime_6B, x2plus, ...): everything is read off the keys and shapes.  The state dict keeps
+    BasicSR's keys -- the RealESRGANNet shell registers its parameters under them."""
+    blocks = {int(k.split('.')[1]) for k in state_dict if k.startswith('body.')}
+    nb = max(blocks) + 1
+    if blocks != set(range(nb)):
+        raise Exception("Could not infer model parameters.")
+    w0 = state_dict['conv_first.weight']
+    nf, cin = int(w0.shape[0]), int(w0.shape[1])
+    gc = int(state_dict['body.0.rdb1.conv1.weight'].shape[0])
+    if gc != 32:
+        raise NotImplementedError(f'BasicSR RRDBNet checkpoint with num_grow_ch={gc}: only 32 is built on the HIP path')
+    out_nc = int(state_dict['conv_last.weight'].shape[0])
+    # conv_first takes in_nc * r^2 channels behind pixel_unshuffle(r): 3, 12 or 48 for RGB.  A count that is not in_nc times 1, 4 or 16 is a plain 4x model of that many channels.
+    r = {1: 1, 4: 2, 16: 4}.get(cin // in_nc if in_nc and cin % in_nc == 0 else 0)
+    if r is None:
+        r, in_nc = 1, cin
+    scale = 4 // r
+    cfg = {'type': 'realesrgan', 'in_nc': in_nc, 'out_nc': out_nc, 'nf': nf, 'nb': nb, 'gc': gc, 'scale': scale}
+    return dict(arch='realesrgan', scale=scale, in_nc=in_nc, out_nc=out_nc, nf=nf, nb=nb, plus=False, state_dict=state_dict,
+                net_params=get_network_G_config(cfg, scale))
 
 
 def _infer_pan(state_dict, scale, in_nc, out_nc):
@@ -126,6 +153,7 @@ class Model:
             raise NotImplementedError('TorchScript models are opaque graphs and cannot run on the HIP engine')
         if state_dict is None:
             state_dict = torch.load(self.model_path, map_location='cpu')
+        state_dict = unwrap_params(state_dict)
         if self.arch == 'infer':
             info = infer_from_state_dict(state_dict, self.scale, self.in_nc, self.out_nc)
             state_dict = info['state_dict']

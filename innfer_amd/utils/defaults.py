@@ -105,6 +105,14 @@ def get_network_G_config(network_G, scale):
         cfg['nf'] = _pick(opts, 'nf', 64)
         cfg['nb'] = _pick(opts, 'nb', 24)
         cfg['gc'] = _pick(opts, 'gc', 32)
+    elif kind in ('realesrgan_net', 'realesrgan'):         # BasicSR's RRDBNet (the Real-ESRGAN releases): its own constructor surface
+        cfg['type'] = 'realesrgan_net'
+        cfg['num_in_ch'] = _pick(opts, 'in_nc', 3)
+        cfg['num_out_ch'] = _pick(opts, 'out_nc', 3)
+        cfg['scale'] = _pick(opts, 'scale', scale)
+        cfg['num_feat'] = _pick(opts, 'nf', 64)
+        cfg['num_block'] = _pick(opts, 'nb', 23)
+        cfg['num_grow_ch'] = _pick(opts, 'gc', 32)
     else:
         raise NotImplementedError(f'Generator model [{kind:s}] not recognized')
 

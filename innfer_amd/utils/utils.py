@@ -594,6 +594,28 @@ def normal2mod(state_dict):
     return out
 
 
+def unwrap_params(state_dict):
+    """The state dict inside a BasicSR / Real-ESRGAN checkpoint: those files hold {'params_ema': {...}} and / or {'params': {...}}; the EMA weights are
+    the ones BasicSR's own loaders prefer.  Anything else is returned as it is."""
+    if isinstance(state_dict, dict):
+        for name in ('params_ema', 'params'):
+            if isinstance(state_dict.get(name), dict):
+                return state_dict[name]
+    return state_dict
+
+
+def realesrgan2normal(state_dict):
+    """BasicSR RRDBNet keys (conv_first / body.N.rdbM.convK / conv_body / conv_up1,2 / conv_hr / conv_last) -> old-arch keys, for any number of blocks
+    (architectures.keys.realesrgan_key_map).  conv_first keeps its in_nc * r^2 input channels: the old-arch graph then takes pixel_unshuffle(x, r)."""
+    from ..architectures.keys import realesrgan_key_map
+    nb = 1 + max(int(k.split('.')[1]) for k in state_dict if k.startswith('body.'))
+    out = {}
+    for new, old in realesrgan_key_map(nb).items():
+        for p in ('weight', 'bias'):
+            out[f'{old}.{p}'] = state_dict[f'{new}.{p}']
+    return out
+
+
 def swa2normal(state_dict):
     """Unwrap a torch.optim.swa_utils.AveragedModel checkpoint: keep only
     'module.module.*' entries, stripped of that prefix (utils.py:701-720)."""
