@@ -45,8 +45,8 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  innfer_version() returns the library's; a binding should compare. */
-#define INNFER_ABI_VERSION 116
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  innfer_version() returns the library's; a binding should compare. */
+#define INNFER_ABI_VERSION 117
 int innfer_version(void);
 const char* innfer_last_error(void);
 
@@ -597,6 +597,44 @@ int innfer_inthwc_to_nchw_fit(const void* d_img, int bits, int H, int W, int C, 
                               void* d_colour, void* d_alpha, int out_dtype, void* stream);
 int innfer_nchw_to_inthwc_fit(const void* d_colour, const void* d_alpha, int in_dtype, int H, int W, int C, int denormalize, int bits,
                               int alpha_const, void* d_img, void* stream);
+
+/* Seamless modes (117): upscale a tileable texture without a seam at its border.  The image is treated as if it had been padded by `pad` pixels on
+ * every side and the padding (scale * pad pixels) cut off the result; not in the reference, whose users pad and crop on the host.  The virtual padded
+ * image is P[y, x, c] = img[m(y - pad, H), m(x - pad, W), c], all channels (alpha included), size (H + 2 pad) x (W + 2 pad), with the index map
+ *   INNFER_BORDER_TILE       m(i, n) = i mod n, a true modulo, any n >= 1                                     (np.pad mode 'wrap')
+ *   INNFER_BORDER_MIRROR     j = i mod 2 (n - 1); m = j < n ? j : 2 (n - 1) - j; n >= 2, else INNFER_ERR_INVALID  (np.pad 'reflect', OpenCV REFLECT_101)
+ *   INNFER_BORDER_REPLICATE  m = clamp(i, 0, n - 1)                                                            (np.pad 'edge')
+ *   INNFER_BORDER_ALPHA_PAD  every channel is 0 outside the image (transparent black)
+ *
+ * innfer_border_index (host only): m(i, n) as the kernels compute it -- the source index, INNFER_BORDER_OUTSIDE for alpha_pad outside [0, n),
+ *   INNFER_BORDER_ERROR (and innfer_last_error) for mirror with n < 2, n < 1 or an unknown mode.
+ * innfer_pad_inthwc: the padded image itself, uint8 / uint16 (bits 8 / 16) HWC, any C, into d_out [H + 2 pad, W + 2 pad, C]: the front end of every
+ *   path that is not fused (whole-image forwards, model chains, 16-bit images, the guided filter); the result is then cropped by the caller.
+ * innfer_extract_tiles_u8_seamless / innfer_extract_tiles_u8_fit_seamless: innfer_extract_tiles_u8 / innfer_extract_tiles_u8_fit of the padded image
+ *   without the padded image: the tile lattice is innfer_chop_plan(H + 2 pad, W + 2 pad, patch, step), every tile element is read from d_img [H, W, C]
+ *   through the index map (alpha_pad outside: the value of a 0 byte, i.e. 0, or -1 under `normalize`).  Arithmetic, channel flip, tile range, tile
+ *   dtype and tile order (fit: colour tiles, then alpha tiles) are those of the entry points they extend; C 1 .. 4 (fit: 1, 2, 4); at most 65535 tiles
+ *   per call.  Four pixels per thread where patch % 4 == 0, as one load where the run does not cross a fold of the map.
+ * innfer_recompose_u8_seamless / innfer_recompose_u8_fit_seamless: innfer_recompose_u8 / innfer_recompose_u8_fit restricted to a crop window.  height
+ *   and width are those of the PADDED low-resolution image, crop (low-resolution pixels, 2 crop < height, width) is what is cut off each side: d_img
+ *   is [scale (height - 2 crop), scale (width - 2 crop), C] and its pixel (Y, X) is pixel (Y + scale crop, X + scale crop) of the full blend -- the
+ *   same tiles in the same order with the same weights, so the same bytes.  Pixels outside the window are neither computed nor stored. */
+#define INNFER_BORDER_TILE 0
+#define INNFER_BORDER_MIRROR 1
+#define INNFER_BORDER_REPLICATE 2
+#define INNFER_BORDER_ALPHA_PAD 3
+#define INNFER_BORDER_OUTSIDE (-1)
+#define INNFER_BORDER_ERROR (-2)
+int innfer_border_index(int i, int n, int mode);
+int innfer_pad_inthwc(const void* d_img, int bits, int H, int W, int C, int pad, int mode, void* d_out, void* stream);
+int innfer_extract_tiles_u8_seamless(const uint8_t* d_img, int C, int H, int W, int normalize, int patch, double step,
+                                     int tile_begin, int tile_count, int pad, int mode, void* d_tiles, int tile_dtype, void* stream);
+int innfer_extract_tiles_u8_fit_seamless(const uint8_t* d_img, int C, int H, int W, int normalize, int patch, double step,
+                                         int tile_begin, int tile_count, int alpha, int pad, int mode, void* d_tiles, int tile_dtype, void* stream);
+int innfer_recompose_u8_seamless(const void* d_tiles, int dtype, int n_tiles, int C, int P, int height, int width, double step, int scale,
+                                 int via_dtype, int denormalize, int crop, uint8_t* d_img, void* stream);
+int innfer_recompose_u8_fit_seamless(const void* d_tiles, int dtype, int n_tiles, int P, int height, int width, double step, int scale,
+                                     int via_dtype, int denormalize, int C, int alpha, int alpha_const, int crop, uint8_t* d_img, void* stream);
 
 /* srgb2linear / linear2srgb (utils/colors.py:29-46, 49-60), the pointwise halves of the `-cf` colour
  * fix: uint8 sRGB -> float32 linear, and float32 linear -> uint8 sRGB (clip, gamma, *255, TRUNCATING

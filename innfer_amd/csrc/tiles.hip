@@ -9,6 +9,7 @@
 // 3.2 GB output and the fp32 result is bit-identical to the reference's
 // scatter loop.
 #include "common.h"
+#include "tiles_common.h"
 
 // Bit-exact parity with the reference's separate torch ops (mul, then +=, then /) needs every
 // rounding kept: hipcc defaults to -ffp-contract=fast, which would fuse a*w + num into one FMA.
@@ -123,21 +124,6 @@ __global__ void k_extract_u8(const uint8_t* img, TO* tiles, int C, int H, int W,
     float v = __fdiv_rn((float)img[((long)(oy + y) * W + ox + x) * C + sc], 255.0f);
     if (normalize) v = fminf(fmaxf(__fmul_rn(__fsub_rn(v, 0.5f), 2.0f), -1.0f), 1.0f);
     tiles[i] = (TO)v;
-}
-
-// torch.linspace(start, end, steps)[i] in fp32 = one fused multiply-add per element,
-// counted from the nearer end (ATen RangeFactories; verified against golden G2).
-__device__ __forceinline__ float lin(float start, float end, int steps, int i) {
-    if (steps == 1) return start;
-    const float step = __fdiv_rn(__fsub_rn(end, start), (float)(steps - 1));
-    return i < steps / 2 ? __fmaf_rn(step, (float)i, start)
-                         : __fmaf_rn(-step, (float)(steps - i - 1), end);
-}
-
-__device__ __forceinline__ float profile(int i, int P, int ov) {
-    if (i < ov) return lin(0.1f, 1.0f, ov, i);
-    if (i < P - ov) return 1.0f;
-    return lin(1.0f, 0.1f, ov, i - (P - ov));
 }
 
 // U8OUT: tensor2np of the blended image as the store -- the blended value is rounded to TO (the tensor recompose_tensor would have returned),
@@ -314,27 +300,6 @@ __global__ void k_linear2srgb(const float* in, uint8_t* out, long n) {
 // (a, a, a); a gray or alpha result is mean3 of the network's three channels: ((y0 + y1) + y2) / 3 in fp32, rounded to the result type, then
 // quantised as tensor2np.  The C - 1 channel of a 2- / 4-channel image is its alpha.
 
-// C bytes (or shorts) of one pixel in one load / store: 1, 2, 4 or 8 bytes, naturally aligned
-template <typename T, int C> struct alignas(sizeof(T) * C) Px { T v[C]; };
-
-// one np2tensor element: float32(x) / maxval [-> ((x - 0.5) * 2).clamp(-1, 1)] -- the ops of k_u8_to_nchw / k_extract_u8
-__device__ __forceinline__ float to_unit(float x, float maxval, int normalize) {
-    float v = __fdiv_rn(x, maxval);
-    if (normalize) v = fminf(fmaxf(__fmul_rn(__fsub_rn(v, 0.5f), 2.0f), -1.0f), 1.0f);
-    return v;
-}
-
-// one tensor2np element (k_nchw_to_u8 / k_recompose U8OUT): [denormalise,] clip(range * v, 0, range), round half to even
-__device__ __forceinline__ int quantise(float v, int denormalize, float range) {
-    if (denormalize) v = fminf(fmaxf(__fdiv_rn(__fsub_rn(v, -1.0f), 2.0f), 0.0f), 1.0f);
-    return __float2int_rn(fminf(fmaxf(__fmul_rn(range, v), 0.0f), range));
-}
-
-template <typename TO>
-__device__ __forceinline__ TO mean3(TO y0, TO y1, TO y2) {
-    return (TO)__fdiv_rn(__fadd_rn(__fadd_rn((float)y0, (float)y1), (float)y2), 3.0f);
-}
-
 // min / max of channel `ch` of an HWC integer image: per thread, per wave, per 256-thread block (LDS), then one atomic pair per block into mm[0..1]
 // (set by k_minmax_init).  At most 256 blocks: atomics on one address serialise, one pair per wave of a 1080p grid cost ~0.1 ms.
 __global__ void k_minmax_init(int* mm) { mm[0] = 0x7fffffff; mm[1] = -1; }
@@ -479,8 +444,6 @@ __global__ void k_nchw_to_inthwc_fit(const TI* col, const TI* alpha, long hw, in
     *(Px<TU, C>*)(img + px * C) = o;
 }
 
-inline unsigned blocks(long total, int bs) { return (unsigned)((total + bs - 1) / bs); }
-
 }  // namespace
 
 int nchw_to_slab(const void* src, int f32, f16* slab, long gstride, int ch_off, int N, int C, int H, int W, hipStream_t s) {
@@ -570,13 +533,6 @@ extern "C" int innfer_extract_tiles(const void* d_img, int dtype, int C, int H, 
     else return set_error(INNFER_ERR_INVALID, "extract_tiles: bad dtype %d", dtype);
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
-}
-
-// overlap = scale * int(round((1-step) * (P/scale)))  with Python's round-half-to-even (utils.py:396)
-static int blend_overlap(int P, double step, int scale) {
-    const double v = (1.0 - step) * ((double)P / scale);
-    double r = __builtin_rint(v);                                     // FE_TONEAREST = half to even
-    return scale * (int)r;
 }
 
 static float lin_host(float start, float end, int steps, int i) {

@@ -217,6 +217,12 @@ SIGNATURES = {
     "innfer_recompose_u8_fit": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]),
     "innfer_inthwc_to_nchw_fit": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_nchw_to_inthwc_fit": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
+    "innfer_border_index": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "innfer_pad_inthwc": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]),
+    "innfer_extract_tiles_u8_seamless": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_extract_tiles_u8_fit_seamless": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_recompose_u8_seamless": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_double] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
+    "innfer_recompose_u8_fit_seamless": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
     "innfer_f32conv_packed_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "innfer_pack_f32conv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "innfer_f32conv": (C.c_int, [C.POINTER(F32ConvArgs), C.c_void_p]),
@@ -242,7 +248,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 lib = _lib
 
-ABI_VERSION = 116          # the header revision this binding was written against (INNFER_ABI_VERSION)
+ABI_VERSION = 117          # the header revision this binding was written against (INNFER_ABI_VERSION)
 if _lib.innfer_version() != ABI_VERSION and not _ABI_ANY:
     raise ImportError(f"{LIB_PATH} speaks ABI {_lib.innfer_version()}, this binding {ABI_VERSION}: rebuild with `make`")
 
@@ -282,6 +288,19 @@ def chop_plan(H, W, patch=200, step=0.5):
     ys, xs = (C.c_int * nh.value)(), (C.c_int * nw.value)()
     check(_lib.innfer_chop_plan(H, W, patch, step, C.byref(ps), C.byref(nh), C.byref(nw), ys, xs))
     return ps.value, list(ys), list(xs)
+
+
+BORDER_MODES = {"tile": 0, "mirror": 1, "replicate": 2, "alpha_pad": 3}       # INNFER_BORDER_*: the seamless modes
+BORDER_OUTSIDE = -1
+
+
+def border_index(i, n, mode):
+    """innfer_border_index (host only): the source index the seamless kernels read for position i (relative to the image) on an axis of n pixels;
+    BORDER_OUTSIDE for alpha_pad outside the image.  mode: a name of BORDER_MODES or its code."""
+    r = _lib.innfer_border_index(int(i), int(n), BORDER_MODES.get(mode, mode) if isinstance(mode, str) else int(mode))
+    if r < BORDER_OUTSIDE:
+        raise ValueError(last_error())
+    return r
 
 
 F32_PLAN_KEYS = ("direct", "NKT", "NPT", "IMG", "CC", "vec4", "workgroups", "lds")

@@ -212,11 +212,15 @@ class ChopRunner:
     (all ranks get it with broadcast_result=True, used between chained models).
     With profile=True every phase is bracketed by a device synchronise and `self.last` holds
     {tiles, compute_ms, exchange_ms, exchange_bytes, blend_ms, bcast_ms} of the call (never in a timed region).
+    seamless   : must be None -- the seamless modes (Model.run_u8) are not built for the sharded chop: NotImplementedError.
     """
 
     def __init__(self, model_fn, scale, tile_batch=None, patch=200, step=0.5, group=None,
                  extract_fn=None, recompose_fn=None, plan_fn=None, out_channels=None, out_dtype=None,
-                 shard='tiles', profile=False, transport='torch'):
+                 shard='tiles', profile=False, transport='torch', seamless=None):
+        if seamless is not None:
+            raise NotImplementedError("ChopRunner: the seamless modes are built for Model.run_u8 on one GPU (the sharded chop works on tensors, whose "
+                                      "tiles are cut from the image as it is); pad with utils.seamless_pad and crop with utils.seamless_crop around it")
         if shard not in ('tiles', 'rows'):
             raise ValueError("shard must be 'tiles' or 'rows'")
         if transport not in ('torch', 'cabi') or (transport == 'cabi' and shard != 'tiles'):
@@ -343,9 +347,11 @@ class ChopRunner:
         return result
 
 
-def run_chain(runners, data):
+def run_chain(runners, data, seamless=None):
     """Model chain `a+b` (run.py:424-426): every stage is tile-sharded; the blended
-    intermediate is broadcast so each rank can cut its own next-stage tiles."""
+    intermediate is broadcast so each rank can cut its own next-stage tiles.  seamless must be None (see ChopRunner)."""
+    if seamless is not None:
+        raise NotImplementedError("run_chain: the seamless modes are not built for the sharded chop; pad and crop around it (utils.seamless_pad / seamless_crop)")
     x = data
     for i, r in enumerate(runners):
         x = r(x, broadcast_result=(i + 1 < len(runners)))

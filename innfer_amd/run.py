@@ -221,27 +221,36 @@ class Model:
         with torch.no_grad():
             return self._predict(data)
 
-    def run_u8(self, img, normalize=False, fp16=True, out=None, fit_channels=False):
+    def run_u8(self, img, normalize=False, fp16=True, out=None, fit_channels=False, seamless=None):
         """Image in, image out: tensor2np(self(np2tensor(img, normalize)[.half()]), denormalize=normalize) (run.py:421-431) with the two
         conversions fused into the neighbouring kernels -- the tile gather / the blend on the chop path (innfer_extract_tiles_u8,
         innfer_recompose_u8), the first / last conv otherwise (EngineModule.forward_u8).  Bit-identical to the separate passes.
         img: uint8 HWC BGR(A), a numpy array (uploaded / downloaded as uint8) or a cuda tensor (stays on the GPU).
         fit_channels: gray (HW, HW1), gray + alpha (HW2) and BGRA images through a 3 -> 3 network (utils.fit_channels_plan): the colour plane
-        as (g, g, g) / RGB, a non-constant alpha plane as (a, a, a); returns the input's layout at the network's scale."""
+        as (g, g, g) / RGB, a non-constant alpha plane as (a, a, a); returns the input's layout at the network's scale.
+        seamless: 'tile', 'mirror', 'replicate' or 'alpha_pad' -- the result of the image padded by SEAMLESS_PAD pixels that way (utils.seamless_pad_np),
+        without the padding: bit for bit run_u8(seamless_pad_np(img, mode))[PAD s:-PAD s, PAD s:-PAD s].  On the chop path the tile gather reads the
+        image through the border map and the blend stores the crop window only (innfer_extract_tiles_u8_seamless, innfer_recompose_u8_seamless and
+        their _fit forms): neither the padded image nor the padded result exists.  Otherwise the image is padded on the GPU, run and cropped."""
         import numpy as np
         from . import lib as L
         from .architectures.engine_module import EngineModule
         from .parallel import run_tile_batches
         from .utils import utils as U
         host = isinstance(img, np.ndarray)
+        mode = None
+        if seamless is not None:
+            mode = U.seamless_mode(seamless, *img.shape[:2])
+            if not self.chop:
+                return self._run_u8_padded(img, seamless, normalize, fp16, out, fit_channels)
         if fit_channels:
             dtype = img.dtype if host else (np.uint8 if img.dtype == torch.uint8 else np.float32)
             plan = U.fit_channels_plan(tuple(img.shape), dtype, getattr(self.model, 'in_nc', self.in_nc), getattr(self.model, 'out_nc', self.out_nc))
             if plan == 0:                                       # a 2-D image for a 1-channel network: run as H x W x 1, return H x W
-                r = self.run_u8(img[:, :, None], normalize=normalize, fp16=fp16, out=None if out is None else out[:, :, None])
+                r = self.run_u8(img[:, :, None], normalize=normalize, fp16=fp16, out=None if out is None else out[:, :, None], seamless=seamless)
                 return r[:, :, 0]
             if plan is not None:
-                return self._run_u8_fit(img, plan, normalize, fp16, out)
+                return self._run_u8_fit(img, plan, normalize, fp16, out, mode)
         d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img.contiguous()
         if d.dtype != torch.uint8 or d.dim() != 3:
             raise TypeError('run_u8: expected a uint8 HWC image')
@@ -253,17 +262,27 @@ class Model:
         fused_net = isinstance(self.model, EngineModule) and self.arch != 'ppon'
         with torch.no_grad(), torch.cuda.device(d.device):
             if self.chop:
-                ps = min(H, W, 200)
-                _, ys, xs = L.chop_plan(H, W, ps, 0.5)
+                pad = 0 if mode is None else U.SEAMLESS_PAD                  # the lattice is the padded image's
+                ps = min(H + 2 * pad, W + 2 * pad, 200)
+                _, ys, xs = L.chop_plan(H + 2 * pad, W + 2 * pad, ps, 0.5)
                 n = len(ys) * len(xs)
                 tiles = torch.empty((n, Cc, ps, ps), dtype=dt, device=d.device)
-                L.check(L.lib.innfer_extract_tiles_u8(d.data_ptr(), Cc, H, W, int(bool(normalize)), ps, 0.5, 0, n, tiles.data_ptr(), code, stream))
+                if mode is None:
+                    L.check(L.lib.innfer_extract_tiles_u8(d.data_ptr(), Cc, H, W, int(bool(normalize)), ps, 0.5, 0, n, tiles.data_ptr(), code, stream))
+                else:
+                    L.check(L.lib.innfer_extract_tiles_u8_seamless(d.data_ptr(), Cc, H, W, int(bool(normalize)), ps, 0.5, 0, n, pad, mode, tiles.data_ptr(), code, stream))
                 hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=self._tile_buffer(tiles))
                 Co, P = hr.shape[1], hr.shape[2]
                 if out is None:
                     out = torch.empty((H * s, W * s, Co), dtype=torch.uint8, device=d.device)
-                L.check(L.lib.innfer_recompose_u8(hr.data_ptr(), U._dt(hr), n, Co, P, H, W, 0.5, s, U._dt(hr), int(bool(normalize)),
-                                                  out.data_ptr(), stream))
+                if mode is None:
+                    L.check(L.lib.innfer_recompose_u8(hr.data_ptr(), U._dt(hr), n, Co, P, H, W, 0.5, s, U._dt(hr), int(bool(normalize)),
+                                                      out.data_ptr(), stream))
+                else:
+                    if tuple(out.shape) != (H * s, W * s, Co) or out.dtype != torch.uint8 or not out.is_contiguous():
+                        raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {(H * s, W * s, Co)}')
+                    L.check(L.lib.innfer_recompose_u8_seamless(hr.data_ptr(), U._dt(hr), n, Co, P, H + 2 * pad, W + 2 * pad, 0.5, s, U._dt(hr),
+                                                               int(bool(normalize)), pad, out.data_ptr(), stream))
             elif fused_net:
                 out = self.model.forward_u8(d, normalize=normalize, fp16=fp16, out=out)
             else:
@@ -275,11 +294,30 @@ class Model:
                 L.check(L.lib.innfer_nchw_to_u8hwc(y.data_ptr(), U._dt(y), y.shape[2], y.shape[3], y.shape[1], int(bool(normalize)), out.data_ptr(), stream))
         return out.cpu().numpy() if host else out
 
-    def _run_u8_fit(self, img, C, normalize, fp16, out):
+    def _run_u8_padded(self, img, seamless, normalize, fp16, out, fit_channels):
+        """run_u8(seamless=) where the chop kernels do not apply (whole-image forwards): pad on the GPU (innfer_pad_inthwc), run as without the switch,
+        crop on the GPU."""
+        import numpy as np
+        from .utils import utils as U
+        host = isinstance(img, np.ndarray)
+        d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img
+        if d.dtype != torch.uint8:
+            raise TypeError('run_u8: expected a uint8 image')
+        r = self.run_u8(U.seamless_pad(d, seamless), normalize=normalize, fp16=fp16, fit_channels=fit_channels)
+        r = U.seamless_crop(r, int(self.scale or 1))
+        if out is not None:
+            if tuple(out.shape) != tuple(r.shape) or out.dtype != torch.uint8:
+                raise ValueError(f'run_u8: out must be a uint8 tensor of shape {tuple(r.shape)}')
+            out.copy_(r)
+            r = out
+        return r.cpu().numpy() if host else r
+
+    def _run_u8_fit(self, img, C, normalize, fp16, out, mode=None):
         """run_u8(fit_channels=True) of an HW / HWC (C 1, 2, 4) uint8 image with a 3 -> 3 network.  Chop: the colour tiles and the alpha tiles
         (none when the alpha plane is constant) are gathered into one buffer, run as one tile stream and blended in one pass
         (innfer_extract_tiles_u8_fit / innfer_recompose_u8_fit).  Otherwise the two planes are split, run as separate forwards (never one batch:
-        train-mode BatchNorm depends on the batch) and merged (innfer_inthwc_to_nchw_fit / innfer_nchw_to_inthwc_fit)."""
+        train-mode BatchNorm depends on the batch) and merged (innfer_inthwc_to_nchw_fit / innfer_nchw_to_inthwc_fit).
+        mode: the border code of run_u8(seamless=) on the chop path (the _seamless forms of the two kernels)."""
         import numpy as np
         from . import lib as L
         from .parallel import run_tile_batches
@@ -299,20 +337,31 @@ class Model:
             stream = torch.cuda.current_stream(d.device).cuda_stream
             if self.chop:
                 const = U.alpha_constant(d, C) if C in (2, 4) else None
+                if mode == L.BORDER_MODES['alpha_pad'] and const:           # the padding's alpha is 0: only an all-0 plane stays constant
+                    const = None
                 alpha = C in (2, 4) and const is None
-                ps = min(H, W, 200)
-                _, ys, xs = L.chop_plan(H, W, ps, 0.5)
+                pad = 0 if mode is None else U.SEAMLESS_PAD
+                ps = min(H + 2 * pad, W + 2 * pad, 200)
+                _, ys, xs = L.chop_plan(H + 2 * pad, W + 2 * pad, ps, 0.5)
                 n = len(ys) * len(xs)
                 tiles = torch.empty(((2 if alpha else 1) * n, 3, ps, ps), dtype=dt, device=d.device)
-                L.check(L.lib.innfer_extract_tiles_u8_fit(d.data_ptr(), C, H, W, int(bool(normalize)), ps, 0.5, 0, n, int(alpha), tiles.data_ptr(), code, stream))
+                if mode is None:
+                    L.check(L.lib.innfer_extract_tiles_u8_fit(d.data_ptr(), C, H, W, int(bool(normalize)), ps, 0.5, 0, n, int(alpha), tiles.data_ptr(), code, stream))
+                else:
+                    L.check(L.lib.innfer_extract_tiles_u8_fit_seamless(d.data_ptr(), C, H, W, int(bool(normalize)), ps, 0.5, 0, n, int(alpha), pad, mode,
+                                                                       tiles.data_ptr(), code, stream))
                 hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=self._tile_buffer(tiles))
                 if hr.shape[1] != 3:
                     raise ValueError(f'run_u8: fit_channels needs a 3-channel result, the network returned {hr.shape[1]}')
                 hr = hr.contiguous()
                 if out is None:
                     out = torch.empty(shape, dtype=torch.uint8, device=d.device)
-                L.check(L.lib.innfer_recompose_u8_fit(hr.data_ptr(), U._dt(hr), n, hr.shape[2], H, W, 0.5, s, U._dt(hr), int(bool(normalize)), C,
-                                                      int(alpha), -1 if const is None else const, out.data_ptr(), stream))
+                if mode is None:
+                    L.check(L.lib.innfer_recompose_u8_fit(hr.data_ptr(), U._dt(hr), n, hr.shape[2], H, W, 0.5, s, U._dt(hr), int(bool(normalize)), C,
+                                                          int(alpha), -1 if const is None else const, out.data_ptr(), stream))
+                else:
+                    L.check(L.lib.innfer_recompose_u8_fit_seamless(hr.data_ptr(), U._dt(hr), n, hr.shape[2], H + 2 * pad, W + 2 * pad, 0.5, s, U._dt(hr),
+                                                                   int(bool(normalize)), C, int(alpha), -1 if const is None else const, pad, out.data_ptr(), stream))
             else:
                 colour, alpha, const = U.fit_split(d, normalize=normalize, dtype=dt)
                 y = self._predict(colour)
@@ -375,6 +424,8 @@ def get_scale_name(model_path, scale=None):
     return scale
 
 
+SEAMLESS_CHOICES = ('tile', 'mirror', 'replicate', 'alpha_pad')           # utils.SEAMLESS_MODES
+
 pix2pix_extras = {'meval': False, 'strict': True, 'normalize': True}       # run.py:299-303
 cyglegan_extras = {'meval': True, 'strict': False, 'normalize': True}      # run.py:305-309
 default_extras = {'meval': True, 'strict': True, 'normalize': False}       # run.py:311-315
@@ -397,6 +448,9 @@ def build_parser():
     # not a reference flag: absent from the parsed namespace unless given, so the reference's flags parse to exactly what they did
     parser.add_argument('-fit_channels', required=False, action='store_true', default=argparse.SUPPRESS,
                         help='Run gray, gray + alpha and RGBA images through RGB models (alpha as a gray image through the model).')
+    parser.add_argument('-seamless', required=False, choices=SEAMLESS_CHOICES, default=argparse.SUPPRESS,
+                        help='Upscale tileable textures without a seam: the image is padded by 16 px (tile: wrap around, mirror, replicate: edge pixels, '
+                             'alpha_pad: transparent black) and the padding is cut off the result.')
     return parser
 
 
@@ -426,6 +480,10 @@ def main(argv=None):
         use_guided_filter = use_modcrop = True
     else:
         defaults, resize, chop = default_extras, False, True
+    seamless = getattr(args, 'seamless', None)
+    if seamless and resize:
+        raise ValueError(f"-seamless {seamless} with '{args.arch}': the preset enlarges every image to a multiple of {resize} px first, which no tileable "
+                         "texture survives; resize the texture yourself and run it without the preset")
     meval, strict = defaults['meval'], defaults['strict']
     normalize = defaults['normalize'] or args.norm
     device = torch.device('cuda')
@@ -497,12 +555,17 @@ def main(argv=None):
             flat = plan is not None and img.ndim == 2                                   # a 2-D image runs as H x W x 1 and is saved 2-D
             if flat:
                 img = img[:, :, None]
-            if plan and len(models) == 1 and not use_guided_filter and img.dtype == np.uint8:          # plan 1, 2, 4: colour (+ alpha) planes
-                img_out = models[0].run_u8(img, normalize=normalize, fp16=fp16, fit_channels=True)
+            single = len(models) == 1 and not use_guided_filter and img.dtype == np.uint8
+            sm = {'seamless': seamless} if seamless else {}                             # run_u8 pads and crops inside its kernels
+            src = img
+            if seamless and not (single and (plan or img.ndim == 3)):                   # chains, 16-bit images, the guided filter: pad once in front, crop behind
+                img = U.seamless_pad(img, seamless)
+            if plan and single:                                                         # plan 1, 2, 4: colour (+ alpha) planes
+                img_out = models[0].run_u8(img, normalize=normalize, fp16=fp16, fit_channels=True, **sm)
             elif plan:
                 img_out = U.fit_channels_forward(fit_chain, img, normalize=normalize, device=device, dtype=torch.float16 if fp16 else torch.float32)
-            elif len(models) == 1 and not use_guided_filter and img.dtype == np.uint8 and img.ndim == 3:
-                img_out = models[0].run_u8(img, normalize=normalize, fp16=fp16)          # conversions fused into the tile gather / blend / first and last conv
+            elif single and img.ndim == 3:
+                img_out = models[0].run_u8(img, normalize=normalize, fp16=fp16, **sm)    # conversions fused into the tile gather / blend / first and last conv
             else:
                 t_img = U.np2tensor(img, normalize=normalize, device=device, dtype=torch.float16 if fp16 else torch.float32)
                 t_out = t_img
@@ -511,6 +574,11 @@ def main(argv=None):
                     if use_guided_filter:
                         t_out = U.guided_filter(t_img, t_out, r=1, eps=5e-3)
                 img_out = U.tensor2np(t_out.detach(), denormalize=normalize)
+            if img is not src:                                                          # padded in front of the chain: PAD x the chain's scale off every side
+                total = 1
+                for mod in models:
+                    total *= int(mod.scale or 1)
+                img, img_out = src, U.seamless_crop(img_out, total)
             if args.cf:
                 img_out = U.color_fix(img, img_out)
             if flat:

@@ -3,6 +3,8 @@ utils/defaults.py:3-147 for the families on the HIP hot path.  Same input
 contract (a kind string or a dict with 'type' / 'which_model_G'), same output keys,
 so configs written for the reference resolve identically."""
 
+SEAMLESS_PAD = 16          # low-resolution pixels the seamless modes pad on every side (utils.seamless_pad, Model.run_u8(seamless=), `run.py -seamless`)
+
 _RRDB = ('rrdb_net', 'esrgan', 'evsrgan', 'esrgan-lite')
 _SRRES = ('sr_resnet', 'srresnet', 'srgan')
 

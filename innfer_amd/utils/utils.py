@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .. import lib as L
+from .defaults import SEAMLESS_PAD
 
 try:                                    # the reference reads / writes through OpenCV (utils.py:3-4,68-95); PIL is the stand-in where it is absent
     import cv2
@@ -251,6 +252,68 @@ def fit_channels_forward(fn, img, normalize=False, device='cuda', dtype=torch.fl
     if bits == 16:
         arr = arr.view(np.uint16)
     return arr[:, :, 0] if img.ndim == 2 else arr
+
+
+# ---------------------------------------------------------------- seamless modes: tileable textures without a seam at the border
+# The image is run as if it had been padded by SEAMLESS_PAD pixels with its own continuation ('tile', 'mirror', 'replicate') or with transparent black
+# ('alpha_pad') and the padding cut off the result.  Kernels: csrc/tiles_seamless.hip (include/innfer_amd.h, ABI 117).  Not in the reference.
+SEAMLESS_MODES = tuple(L.BORDER_MODES)
+_NP_PAD_MODE = {'tile': 'wrap', 'mirror': 'reflect', 'replicate': 'edge', 'alpha_pad': 'constant'}
+
+
+def seamless_mode(mode, H=None, W=None):
+    """The INNFER_BORDER_* code of a seamless mode name; ValueError for an unknown name and for 'mirror' on an image with a side of one pixel."""
+    if mode not in L.BORDER_MODES:
+        raise ValueError(f"seamless: mode must be one of {', '.join(SEAMLESS_MODES)}, got {mode!r}")
+    if mode == 'mirror' and H is not None and (H < 2 or W < 2):
+        raise ValueError(f"seamless: 'mirror' needs at least 2 rows and 2 columns, the image is {H}x{W}")
+    return L.BORDER_MODES[mode]
+
+
+def seamless_pad_np(img, mode, pad=SEAMLESS_PAD):
+    """The contract of the seamless modes in numpy: the HW / HWC image padded by `pad` pixels on every side of its two image axes, all channels alike --
+    np.pad modes 'wrap' (tile), 'reflect' (mirror), 'edge' (replicate), zeros (alpha_pad)."""
+    seamless_mode(mode, img.shape[0], img.shape[1])
+    width = ((pad, pad), (pad, pad)) + ((0, 0),) * (img.ndim - 2)
+    return np.pad(img, width, mode=_NP_PAD_MODE[mode])
+
+
+def seamless_pad(img, mode, pad=SEAMLESS_PAD):
+    """seamless_pad_np on the GPU (innfer_pad_inthwc): img is an HW / HWC uint8 or uint16 numpy image (a numpy image comes back) or a uint8 / int16-viewed
+    uint16 GPU tensor (a GPU tensor comes back)."""
+    host = isinstance(img, np.ndarray)
+    if img.ndim not in (2, 3):
+        raise TypeError('seamless_pad: expected an HW / HWC image')
+    H, W = img.shape[:2]
+    code = seamless_mode(mode, H, W)
+    if host:
+        if img.dtype not in (np.uint8, np.uint16):
+            raise TypeError(f'seamless_pad: uint8 / uint16 images, got {img.dtype}')
+        a = np.ascontiguousarray(img)
+        d = torch.from_numpy(a if a.dtype == np.uint8 else a.view(np.int16)).cuda()
+    else:
+        if img.dtype not in (torch.uint8, torch.int16):
+            raise TypeError(f'seamless_pad: uint8 / int16-viewed uint16 tensors, got {img.dtype}')
+        _need_cuda(img, 'seamless_pad')
+        d = img.contiguous()
+    Cc = d.shape[2] if d.dim() == 3 else 1
+    out = torch.empty((H + 2 * pad, W + 2 * pad) + tuple(d.shape[2:]), dtype=d.dtype, device=d.device)
+    with _on(d):
+        L.check(L.lib.innfer_pad_inthwc(d.data_ptr(), _bits(d), H, W, Cc, pad, code, out.data_ptr(), _stream(d)))
+    if not host:
+        return out
+    arr = out.cpu().numpy()
+    return arr.view(np.uint16) if img.dtype == np.uint16 else arr
+
+
+def seamless_crop(img_out, scale, pad=SEAMLESS_PAD):
+    """The result of a padded image without its padding: scale * pad pixels off every side of an HW / HWC numpy image or GPU tensor (a contiguous copy)."""
+    c = int(scale) * pad
+    H, W = img_out.shape[:2]
+    if H <= 2 * c or W <= 2 * c:
+        raise ValueError(f'seamless_crop: nothing is left of {H}x{W} after {c} pixels off every side')
+    r = img_out[c:H - c, c:W - c]
+    return np.ascontiguousarray(r) if isinstance(img_out, np.ndarray) else r.contiguous()
 
 
 # ---------------------------------------------------------------- files (utils.py:36-133): the image loop's codec hand-off
