@@ -560,7 +560,9 @@ int innfer_nchw_to_u8hwc(const void* d_in, int in_dtype, int H, int W, int C, in
 /* The chop path with uint8 images at both ends (104): extract_patches_2d(np2tensor(img)) and tensor2np(recompose_tensor(tiles)) without the
  * float image in between -- the tile gather converts (same /255, flip, normalisation, cast to the tile dtype), the blend stores uint8 HWC
  * BGR(A) (the blended value is first rounded to via_dtype, the dtype recompose_tensor would have returned).  One image; same geometry and
- * arithmetic as innfer_extract_tiles / innfer_recompose, bit-identical to the separate passes. */
+ * arithmetic as innfer_extract_tiles / innfer_recompose, bit-identical to the separate passes.  They are innfer_extract_tiles_u8_seamless at
+ * pad = 0 and innfer_recompose_u8_seamless at crop = 0 (117, below): one gather and one blend kernel serve every uint8 chop entry point.  The
+ * gather takes any C >= 1 (3 n channels are fully flipped, 4 is [2, 1, 0, 3]), the blend C 1 .. 4. */
 int innfer_extract_tiles_u8(const uint8_t* d_img, int C, int H, int W, int normalize, int patch, double step,
                             int tile_begin, int tile_count, void* d_tiles, int tile_dtype, void* stream);
 int innfer_recompose_u8(const void* d_tiles, int dtype, int n_tiles, int C, int P, int height, int width, double step, int scale,
@@ -583,6 +585,7 @@ int innfer_nchw_to_inthwc(const void* d_in, int in_dtype, int H, int W, int C, i
  * innfer_channel_minmax: d_minmax[0] = min, d_minmax[1] = max of channel `ch` of a uint8 / uint16 (bits 8 / 16) HWC image; two device ints.
  * innfer_extract_tiles_u8_fit: innfer_extract_tiles_u8 of the colour input into tiles [0, tile_count) of a [*, 3, P, P] buffer and, alpha != 0,
  *   of the alpha input into tiles [tile_count, 2 tile_count): one pixel's C bytes in one load, four pixels per thread where the geometry allows.
+ *   It is innfer_extract_tiles_u8_fit_seamless at pad = 0, as innfer_recompose_u8_fit is innfer_recompose_u8_fit_seamless at crop = 0.
  * innfer_recompose_u8_fit: innfer_recompose_u8 of the n colour tiles [0, n) and, alpha != 0, of the alpha tiles [n, 2 n) in one pass: each
  *   pixel's weights once, every channel summed in innfer_recompose_u8's order (so B, G, R are its bytes), then the output above; alpha == 0 with
  *   C 2 / 4 needs alpha_const in [0, 255].  Stores C bytes per pixel into d_img [scale H, scale W, C].
@@ -613,12 +616,14 @@ int innfer_nchw_to_inthwc_fit(const void* d_colour, const void* d_alpha, int in_
  * innfer_extract_tiles_u8_seamless / innfer_extract_tiles_u8_fit_seamless: innfer_extract_tiles_u8 / innfer_extract_tiles_u8_fit of the padded image
  *   without the padded image: the tile lattice is innfer_chop_plan(H + 2 pad, W + 2 pad, patch, step), every tile element is read from d_img [H, W, C]
  *   through the index map (alpha_pad outside: the value of a 0 byte, i.e. 0, or -1 under `normalize`).  Arithmetic, channel flip, tile range, tile
- *   dtype and tile order (fit: colour tiles, then alpha tiles) are those of the entry points they extend; C 1 .. 4 (fit: 1, 2, 4); at most 65535 tiles
- *   per call.  Four pixels per thread where patch % 4 == 0, as one load where the run does not cross a fold of the map.
+ *   dtype and tile order (fit: colour tiles, then alpha tiles) are those of the entry points they extend; C 1 .. 4 (fit: 1, 2, 4; C > 4 only at
+ *   pad = 0, INNFER_ERR_UNSUPPORTED otherwise).  Four pixels per thread where patch % 4 == 0, as one load where the run does not cross a fold of the
+ *   map and its bytes are aligned.  pad = 0 is the plain gather, whatever the mode: the map is the identity.
  * innfer_recompose_u8_seamless / innfer_recompose_u8_fit_seamless: innfer_recompose_u8 / innfer_recompose_u8_fit restricted to a crop window.  height
  *   and width are those of the PADDED low-resolution image, crop (low-resolution pixels, 2 crop < height, width) is what is cut off each side: d_img
  *   is [scale (height - 2 crop), scale (width - 2 crop), C] and its pixel (Y, X) is pixel (Y + scale crop, X + scale crop) of the full blend -- the
- *   same tiles in the same order with the same weights, so the same bytes.  Pixels outside the window are neither computed nor stored. */
+ *   same tiles in the same order with the same weights, so the same bytes.  Pixels outside the window are neither computed nor stored.  crop = 0 is
+ *   the plain blend. */
 #define INNFER_BORDER_TILE 0
 #define INNFER_BORDER_MIRROR 1
 #define INNFER_BORDER_REPLICATE 2

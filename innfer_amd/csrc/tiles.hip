@@ -3,6 +3,7 @@
 //   - chop_forward tile extraction  (utils/utils.py:318-369 as used by run.py:178-181)
 //   - overlap blend / recompose     (utils/utils.py:372-445)
 //   - uint8 HWC BGR <-> float NCHW RGB pre/post (utils/utils.py:164-194,197-248)
+// (the uint8 chop path -- gather and blend with the conversions fused in -- is tiles_u8.hip)
 // All of them are one read + one write per element; the blend is written as a
 // GATHER (one thread per output pixel walks the <=3x3 tiles covering it in the
 // reference's (h,w) order) so there are no atomics, no read-modify-write of the
@@ -105,32 +106,8 @@ __global__ void k_extract_x4(const T* img, T* tiles, int C, int H, int W, int ps
     *(v4*)(tiles + i * 4) = *(const v4*)(img + ((long)c * H + oy + y) * W + ox + x);
 }
 
-// extract_patches_2d of np2tensor(img) without the float image in between: tile element = float32(u8) / 255 [-> (x - 0.5) * 2 clamped]
-// [-> fp16], channels flipped BGR -> RGB (3n channels: full flip; 4: [2,1,0,3]) -- the values k_u8_to_nchw + k_extract produce
-template <typename TO>
-__global__ void k_extract_u8(const uint8_t* img, TO* tiles, int C, int H, int W, int ps, int step_int, int nw, int tile_begin, long total,
-                             int normalize) {
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // over count*C*ps*ps
-    if (i >= total) return;
-    const int x = (int)(i % ps);
-    const int y = (int)((i / ps) % ps);
-    const int c = (int)((i / ((long)ps * ps)) % C);
-    const int k = (int)(i / ((long)ps * ps * C)) + tile_begin;
-    const int th = k / nw, tw = k % nw;
-    int oy = th * step_int; if (oy > H - ps) oy = H - ps;
-    int ox = tw * step_int; if (ox > W - ps) ox = W - ps;
-    int sc = c;
-    if (C % 3 == 0) sc = C - 1 - c; else if (C == 4 && c < 3) sc = 2 - c;
-    float v = __fdiv_rn((float)img[((long)(oy + y) * W + ox + x) * C + sc], 255.0f);
-    if (normalize) v = fminf(fmaxf(__fmul_rn(__fsub_rn(v, 0.5f), 2.0f), -1.0f), 1.0f);
-    tiles[i] = (TO)v;
-}
-
-// U8OUT: tensor2np of the blended image as the store -- the blended value is rounded to TO (the tensor recompose_tensor would have returned),
-// optionally denormalised, scaled, clipped, rounded half to even and written as a uint8 HWC BGR(A) pixel (`img`, batch 1).
-template <typename TI, typename TO, bool U8OUT = false>
-__global__ void k_recompose(const TI* tiles, TO* out, int C, int P, int FH, int FW, int eff,
-                            int nh, int nw, int ov, uint8_t* img = nullptr, int denormalize = 0) {
+template <typename TI, typename TO>
+__global__ void k_recompose(const TI* tiles, TO* out, int C, int P, int FH, int FW, int eff, int nh, int nw, int ov) {
     const int X = blockIdx.x * blockDim.x + threadIdx.x;
     const int Y = blockIdx.y;
     const int b = blockIdx.z;
@@ -163,18 +140,7 @@ __global__ void k_recompose(const TI* tiles, TO* out, int C, int P, int FH, int 
         }
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-            if (cb + c < C) {
-                const TO r = (TO)__fdiv_rn(num[c], den);
-                if constexpr (U8OUT) {
-                    float v = (float)r;
-                    if (denormalize) v = fminf(fmaxf(__fdiv_rn(__fsub_rn(v, -1.0f), 2.0f), 0.0f), 1.0f);
-                    v = fminf(fmaxf(__fmul_rn(255.0f, v), 0.0f), 255.0f);
-                    const int ch = cb + c, sc = (C == 3 || (C == 4 && ch < 3)) ? 2 - ch : ch;
-                    img[((long)Y * FW + X) * C + sc] = (uint8_t)__float2int_rn(v);
-                } else {
-                    out[(((long)b * C + cb + c) * FH + Y) * FW + X] = r;
-                }
-            }
+            if (cb + c < C) out[(((long)b * C + cb + c) * FH + Y) * FW + X] = (TO)__fdiv_rn(num[c], den);
     }
 }
 
@@ -298,7 +264,8 @@ __global__ void k_linear2srgb(const float* in, uint8_t* out, long n) {
 // ---- fit_channels: 1-, 2- and 4-channel integer images through an RGB (3 -> 3) network (ABI 115) ------------------------------------------------
 // Image layouts (HWC, OpenCV order): C 1 = gray, 2 = gray + alpha, 4 = BGRA.  The colour input of the network is (g, g, g) or RGB, the alpha input
 // (a, a, a); a gray or alpha result is mean3 of the network's three channels: ((y0 + y1) + y2) / 3 in fp32, rounded to the result type, then
-// quantised as tensor2np.  The C - 1 channel of a 2- / 4-channel image is its alpha.
+// quantised as tensor2np.  The C - 1 channel of a 2- / 4-channel image is its alpha.  Here: the whole-image converters and the alpha scan; the chop
+// path's gather and blend are the FIT forms of tiles_u8.hip.
 
 // min / max of channel `ch` of an HWC integer image: per thread, per wave, per 256-thread block (LDS), then one atomic pair per block into mm[0..1]
 // (set by k_minmax_init).  At most 256 blocks: atomics on one address serialise, one pair per wave of a 1080p grid cost ~0.1 ms.
@@ -326,91 +293,6 @@ __global__ void __launch_bounds__(256) k_channel_minmax(const T* img, long hw, i
             atomicMax(mm + 1, hi);
         }
     }
-}
-
-// extract_patches_2d of the colour and alpha planes: V consecutive pixels of one tile row per thread, all C channels of them in one load; colour
-// tile k goes to slot k - tile_begin, its alpha tile (alpha != 0) to slot count + k - tile_begin, both [3, ps, ps].  V = 4 needs ps, the tile step and
-// W multiples of 4 (every tile origin is then, and the V * C bytes are aligned).
-template <typename TO, int C, int V>
-__global__ void k_extract_u8_fit(const uint8_t* img, TO* tiles, int H, int W, int ps, int step_int, int nw, int tile_begin, int count, long total,
-                                 int normalize, int alpha) {
-    typedef TO vo __attribute__((ext_vector_type(V)));
-    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // over count * ps * (ps / V)
-    if (i >= total) return;
-    const int q = ps / V;
-    const int x = (int)(i % q) * V;
-    const int y = (int)((i / q) % ps);
-    const int kk = (int)(i / ((long)q * ps));
-    const int k = kk + tile_begin;
-    const int th = k / nw, tw = k % nw;
-    int oy = th * step_int; if (oy > H - ps) oy = H - ps;
-    int ox = tw * step_int; if (ox > W - ps) ox = W - ps;
-    const Px<uint8_t, C * V> p = *(const Px<uint8_t, C * V>*)(img + ((long)(oy + y) * W + ox + x) * C);
-    vo col[3], a;
-#pragma unroll
-    for (int j = 0; j < V; ++j) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c)                                 // RGB from BGR(A); (g, g, g) from gray
-            col[c][j] = (TO)to_unit((float)p.v[j * C + (C == 4 ? 2 - c : 0)], 255.0f, normalize);
-        if (C > 1) a[j] = (TO)to_unit((float)p.v[j * C + C - 1], 255.0f, normalize);
-    }
-    const long pp = (long)ps * ps, o = (long)y * ps + x;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) *(vo*)(tiles + ((long)kk * 3 + c) * pp + o) = col[c];
-    if (C > 1 && alpha) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *(vo*)(tiles + ((long)(count + kk) * 3 + c) * pp + o) = a;
-    }
-}
-
-// The blend of innfer_recompose_u8 for the colour tiles [0, n) and, with alpha, the alpha tiles [n, 2n): one thread per output pixel, each tile's
-// weight computed once and applied to all six numerators in k_recompose's order (so each channel is what innfer_recompose_u8 stores), then tensor2np
-// of B, G, R (C 4) or of mean3 (gray), and of mean3 of the alpha result or the constant alpha `aconst` (>= 0); the pixel's C bytes in one store.
-template <typename TI, typename TO, int C>
-__global__ void k_recompose_u8_fit(const TI* tiles, int n, int P, int FH, int FW, int eff, int nh, int nw, int ov, int alpha, int aconst,
-                                   int denormalize, uint8_t* img) {
-    const int X = blockIdx.x * blockDim.x + threadIdx.x;
-    const int Y = blockIdx.y;
-    if (X >= FW) return;
-    constexpr int NC = C > 1 ? 6 : 3;
-    float num[NC], den = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) num[c] = 0.f;
-    const long pp = (long)P * P, aoff = (long)n * 3 * pp;
-    const int h0 = max(0, (Y - P + eff) / eff), w0 = max(0, (X - P + eff) / eff);
-    for (int h = h0; h < nh; ++h) {
-        const int oy = min(h * eff, FH - P);
-        if (oy > Y) break;
-        if (Y - oy >= P) continue;
-        const float wy = profile(Y - oy, P, ov);
-        for (int w = w0; w < nw; ++w) {
-            const int ox = min(w * eff, FW - P);
-            if (ox > X) break;
-            if (X - ox >= P) continue;
-            const float wgt = __fmul_rn(profile(X - ox, P, ov), wy);
-            den = __fadd_rn(den, wgt);
-            const long k = (long)h * nw + w;
-            const TI* tp = tiles + (k * 3 * P + (Y - oy)) * (long)P + (X - ox);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) num[c] = __fadd_rn(num[c], __fmul_rn((float)tp[c * pp], wgt));
-            if (C > 1 && alpha) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) num[3 + c] = __fadd_rn(num[3 + c], __fmul_rn((float)tp[aoff + c * pp], wgt));
-            }
-        }
-    }
-    TO r[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) r[c] = (TO)__fdiv_rn(num[c], den);
-    Px<uint8_t, C> o;
-    if (C == 4) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) o.v[2 - c] = (uint8_t)quantise((float)r[c], denormalize, 255.0f);
-    } else {
-        o.v[0] = (uint8_t)quantise((float)mean3(r[0], r[1], r[2]), denormalize, 255.0f);
-    }
-    if (C > 1) o.v[C - 1] = alpha ? (uint8_t)quantise((float)mean3(r[NC - 3], r[NC - 2], r[NC - 1]), denormalize, 255.0f) : (uint8_t)aconst;
-    *(Px<uint8_t, C>*)(img + ((long)Y * FW + X) * C) = o;
 }
 
 // np2tensor of the two planes on whole images: colour [3, hw] (RGB from BGRA, (g, g, g) from gray), alpha [3, hw] (a, a, a) when `alpha` is non-null
@@ -557,18 +439,10 @@ extern "C" int innfer_blend_profile(int P, double step, int scale, float* h_prof
 
 extern "C" int innfer_recompose(const void* d_tiles, int dtype, int n, int C, int P, int height, int width,
                                 double step, int scale, void* d_out, int out_dtype, void* stream) {
-    if (step < 0.5 || step > 1.0) return set_error(INNFER_ERR_INVALID, "recompose: step must be in [0.5,1]");
-    if (n <= 0 || C <= 0 || P <= 0 || scale <= 0) return set_error(INNFER_ERR_INVALID, "recompose: bad sizes");
-    const int FH = scale * height, FW = scale * width;
-    if (FH < P || FW < P) return set_error(INNFER_ERR_INVALID, "recompose: patch %d larger than output %dx%d", P, FH, FW);
-    const int ov = blend_overlap(P, step, scale);
-    if (P - 2 * ov < 0)
-        return set_error(INNFER_ERR_INVALID, "recompose: overlap %d exceeds half of patch %d (reference raises too)", ov, P);
-    const int eff = (int)(step * P), step_int = (int)(P * step);
-    const int nh = 1 + (FH - P) / step_int + ((FH - P) % step_int != 0);
-    const int nw = 1 + (FW - P) / step_int + ((FW - P) % step_int != 0);
-    if (n % (nh * nw)) return set_error(INNFER_ERR_INVALID, "recompose: %d tiles is not a multiple of %dx%d", n, nh, nw);
-    const int nb = n / (nh * nw);
+    if (C <= 0) return set_error(INNFER_ERR_INVALID, "recompose: bad sizes");
+    BlendGeo g;
+    if (int rc = blend_geo("recompose", n, P, height, width, step, scale, 0, true, &g)) return rc;
+    const int FH = g.FH, FW = g.FW, ov = g.ov, eff = g.eff, nh = g.nh, nw = g.nw, nb = n / (nh * nw);
     hipStream_t s = (hipStream_t)stream;
     // four pixels per thread when every tile origin (multiples of eff, or FW - P for the ragged last column) and the row pitch are multiples of 4
     const bool x4 = P % 4 == 0 && eff % 4 == 0 && FW % 4 == 0;
@@ -581,52 +455,6 @@ extern "C" int innfer_recompose(const void* d_tiles, int dtype, int n, int C, in
     else if (dtype == INNFER_F32 && out_dtype == INNFER_F16) RC(float, f16);
     else return set_error(INNFER_ERR_INVALID, "recompose: bad dtype");
 #undef RC
-    INNFER_HIP(hipGetLastError());
-    return INNFER_OK;
-}
-
-extern "C" int innfer_extract_tiles_u8(const uint8_t* d_img, int C, int H, int W, int normalize, int patch, double step,
-                                       int tile_begin, int tile_count, void* d_tiles, int tile_dtype, void* stream) {
-    if (!d_img || !d_tiles || C <= 0) return set_error(INNFER_ERR_INVALID, "extract_tiles_u8: null argument / no channels");
-    int ps, nh, nw;
-    if (int rc = innfer_chop_plan(H, W, patch, step, &ps, &nh, &nw, nullptr, nullptr)) return rc;
-    const int step_int = (int)(ps * step);
-    if (tile_begin < 0 || tile_count < 0 || tile_begin + tile_count > nh * nw)
-        return set_error(INNFER_ERR_INVALID, "extract_tiles_u8: tile range [%d,+%d) outside %d tiles", tile_begin, tile_count, nh * nw);
-    const long total = (long)tile_count * C * ps * ps;
-    if (total == 0) return INNFER_OK;
-    hipStream_t s = (hipStream_t)stream;
-    if (tile_dtype == INNFER_F16)
-        hipLaunchKernelGGL(k_extract_u8<f16>, dim3(blocks(total, 256)), dim3(256), 0, s, d_img, (f16*)d_tiles, C, H, W, ps, step_int, nw, tile_begin, total, normalize);
-    else if (tile_dtype == INNFER_F32)
-        hipLaunchKernelGGL(k_extract_u8<float>, dim3(blocks(total, 256)), dim3(256), 0, s, d_img, (float*)d_tiles, C, H, W, ps, step_int, nw, tile_begin, total, normalize);
-    else return set_error(INNFER_ERR_INVALID, "extract_tiles_u8: bad dtype %d", tile_dtype);
-    INNFER_HIP(hipGetLastError());
-    return INNFER_OK;
-}
-
-extern "C" int innfer_recompose_u8(const void* d_tiles, int dtype, int n, int C, int P, int height, int width, double step, int scale,
-                                   int via_dtype, int denormalize, uint8_t* d_img, void* stream) {
-    if (!d_tiles || !d_img) return set_error(INNFER_ERR_INVALID, "recompose_u8: null argument");
-    if (step < 0.5 || step > 1.0) return set_error(INNFER_ERR_INVALID, "recompose_u8: step must be in [0.5,1]");
-    if (n <= 0 || C <= 0 || C > 4 || P <= 0 || scale <= 0) return set_error(INNFER_ERR_INVALID, "recompose_u8: bad sizes");
-    const int FH = scale * height, FW = scale * width;
-    if (FH < P || FW < P) return set_error(INNFER_ERR_INVALID, "recompose_u8: patch %d larger than output %dx%d", P, FH, FW);
-    const int ov = blend_overlap(P, step, scale);
-    if (P - 2 * ov < 0) return set_error(INNFER_ERR_INVALID, "recompose_u8: overlap %d exceeds half of patch %d (reference raises too)", ov, P);
-    const int eff = (int)(step * P), step_int = (int)(P * step);
-    const int nh = 1 + (FH - P) / step_int + ((FH - P) % step_int != 0);
-    const int nw = 1 + (FW - P) / step_int + ((FW - P) % step_int != 0);
-    if (n != nh * nw) return set_error(INNFER_ERR_INVALID, "recompose_u8: one image of %dx%d tiles expected, got %d tiles", nh, nw, n);
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((FW + 255) / 256, FH, 1), block(256);
-#define RCU(TI, TO) hipLaunchKernelGGL((k_recompose<TI, TO, true>), grid, block, 0, s, (const TI*)d_tiles, (TO*)nullptr, C, P, FH, FW, eff, nh, nw, ov, d_img, denormalize)
-    if (dtype == INNFER_F16 && via_dtype == INNFER_F16) RCU(f16, f16);
-    else if (dtype == INNFER_F16 && via_dtype == INNFER_F32) RCU(f16, float);
-    else if (dtype == INNFER_F32 && via_dtype == INNFER_F32) RCU(float, float);
-    else if (dtype == INNFER_F32 && via_dtype == INNFER_F16) RCU(float, f16);
-    else return set_error(INNFER_ERR_INVALID, "recompose_u8: bad dtype");
-#undef RCU
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
 }
@@ -715,67 +543,6 @@ extern "C" int innfer_channel_minmax(const void* d_img, int bits, int H, int W, 
     const unsigned g = blocks(hw, 256) < 256 ? blocks(hw, 256) : 256;
     if (bits == 8) hipLaunchKernelGGL(k_channel_minmax<uint8_t>, dim3(g), dim3(256), 0, s, (const uint8_t*)d_img, hw, C, ch, d_minmax);
     else hipLaunchKernelGGL(k_channel_minmax<uint16_t>, dim3(g), dim3(256), 0, s, (const uint16_t*)d_img, hw, C, ch, d_minmax);
-    INNFER_HIP(hipGetLastError());
-    return INNFER_OK;
-}
-
-extern "C" int innfer_extract_tiles_u8_fit(const uint8_t* d_img, int C, int H, int W, int normalize, int patch, double step,
-                                           int tile_begin, int tile_count, int alpha, void* d_tiles, int tile_dtype, void* stream) {
-    if (!d_img || !d_tiles) return set_error(INNFER_ERR_INVALID, "extract_tiles_u8_fit: null argument");
-    if (C != 1 && C != 2 && C != 4) return set_error(INNFER_ERR_INVALID, "extract_tiles_u8_fit: %d channels (1, 2 or 4)", C);
-    if (alpha && C == 1) return set_error(INNFER_ERR_INVALID, "extract_tiles_u8_fit: a 1-channel image has no alpha");
-    int ps, nh, nw;
-    if (int rc = innfer_chop_plan(H, W, patch, step, &ps, &nh, &nw, nullptr, nullptr)) return rc;
-    const int step_int = (int)(ps * step);
-    if (tile_begin < 0 || tile_count < 0 || tile_begin + tile_count > nh * nw)
-        return set_error(INNFER_ERR_INVALID, "extract_tiles_u8_fit: tile range [%d,+%d) outside %d tiles", tile_begin, tile_count, nh * nw);
-    if (tile_count == 0) return INNFER_OK;
-    hipStream_t s = (hipStream_t)stream;
-    const bool x4 = ps % 4 == 0 && step_int % 4 == 0 && W % 4 == 0;
-    const long total = (long)tile_count * ps * (x4 ? ps / 4 : ps);
-    const int a = alpha ? 1 : 0;
-#define EXF(TO, CC, V) hipLaunchKernelGGL((k_extract_u8_fit<TO, CC, V>), dim3(blocks(total, 256)), dim3(256), 0, s, d_img, (TO*)d_tiles, H, W, ps, step_int, nw, \
-                                          tile_begin, tile_count, total, normalize, a)
-#define EXF_C(TO) do { if (x4) { if (C == 1) EXF(TO, 1, 4); else if (C == 2) EXF(TO, 2, 4); else EXF(TO, 4, 4); } \
-                       else { if (C == 1) EXF(TO, 1, 1); else if (C == 2) EXF(TO, 2, 1); else EXF(TO, 4, 1); } } while (0)
-    if (tile_dtype == INNFER_F16) EXF_C(f16);
-    else if (tile_dtype == INNFER_F32) EXF_C(float);
-    else return set_error(INNFER_ERR_INVALID, "extract_tiles_u8_fit: bad dtype %d", tile_dtype);
-#undef EXF_C
-#undef EXF
-    INNFER_HIP(hipGetLastError());
-    return INNFER_OK;
-}
-
-extern "C" int innfer_recompose_u8_fit(const void* d_tiles, int dtype, int n, int P, int height, int width, double step, int scale,
-                                       int via_dtype, int denormalize, int C, int alpha, int alpha_const, uint8_t* d_img, void* stream) {
-    if (!d_tiles || !d_img) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: null argument");
-    if (C != 1 && C != 2 && C != 4) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: %d channels (1, 2 or 4)", C);
-    if (C == 1 ? alpha != 0 : (!alpha && (alpha_const < 0 || alpha_const > 255)))
-        return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: a %d-channel image needs %s", C, C == 1 ? "no alpha tiles" : "alpha tiles or a constant alpha in [0, 255]");
-    if (step < 0.5 || step > 1.0) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: step must be in [0.5,1]");
-    if (n <= 0 || P <= 0 || scale <= 0) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: bad sizes");
-    const int FH = scale * height, FW = scale * width;
-    if (FH < P || FW < P) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: patch %d larger than output %dx%d", P, FH, FW);
-    const int ov = blend_overlap(P, step, scale);
-    if (P - 2 * ov < 0) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: overlap %d exceeds half of patch %d (reference raises too)", ov, P);
-    const int eff = (int)(step * P), step_int = (int)(P * step);
-    const int nh = 1 + (FH - P) / step_int + ((FH - P) % step_int != 0);
-    const int nw = 1 + (FW - P) / step_int + ((FW - P) % step_int != 0);
-    if (n != nh * nw) return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: one image of %dx%d tiles expected, got %d colour tiles", nh, nw, n);
-    hipStream_t s = (hipStream_t)stream;
-    dim3 grid((FW + 255) / 256, FH, 1), block(256);
-    const int a = alpha ? 1 : 0;
-#define RCF(TI, TO, CC) hipLaunchKernelGGL((k_recompose_u8_fit<TI, TO, CC>), grid, block, 0, s, (const TI*)d_tiles, n, P, FH, FW, eff, nh, nw, ov, a, alpha_const, \
-                                           denormalize, d_img)
-#define RCF_C(TI, TO) do { if (C == 1) RCF(TI, TO, 1); else if (C == 2) RCF(TI, TO, 2); else RCF(TI, TO, 4); } while (0)
-    if (dtype == INNFER_F16 && via_dtype == INNFER_F16) RCF_C(f16, f16);
-    else if (dtype == INNFER_F16 && via_dtype == INNFER_F32) RCF_C(f16, float);
-    else if (dtype == INNFER_F32 && via_dtype == INNFER_F32) RCF_C(float, float);
-    else if (dtype == INNFER_F32 && via_dtype == INNFER_F16) RCF_C(float, f16);
-    else return set_error(INNFER_ERR_INVALID, "recompose_u8_fit: bad dtype");
-#undef RCF_C
-#undef RCF
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
 }

@@ -223,19 +223,17 @@ class Model:
 
     def run_u8(self, img, normalize=False, fp16=True, out=None, fit_channels=False, seamless=None):
         """Image in, image out: tensor2np(self(np2tensor(img, normalize)[.half()]), denormalize=normalize) (run.py:421-431) with the two
-        conversions fused into the neighbouring kernels -- the tile gather / the blend on the chop path (innfer_extract_tiles_u8,
-        innfer_recompose_u8), the first / last conv otherwise (EngineModule.forward_u8).  Bit-identical to the separate passes.
+        conversions fused into the neighbouring kernels -- the tile gather / the blend on the chop path (_chop_u8: innfer_extract_tiles_u8_seamless,
+        innfer_recompose_u8_seamless and their _fit forms, at pad = 0 / crop = 0 without a seamless mode), the first / last conv otherwise (EngineModule.forward_u8).  Bit-identical to the separate passes.
         img: uint8 HWC BGR(A), a numpy array (uploaded / downloaded as uint8) or a cuda tensor (stays on the GPU).
         fit_channels: gray (HW, HW1), gray + alpha (HW2) and BGRA images through a 3 -> 3 network (utils.fit_channels_plan): the colour plane
         as (g, g, g) / RGB, a non-constant alpha plane as (a, a, a); returns the input's layout at the network's scale.
         seamless: 'tile', 'mirror', 'replicate' or 'alpha_pad' -- the result of the image padded by SEAMLESS_PAD pixels that way (utils.seamless_pad_np),
         without the padding: bit for bit run_u8(seamless_pad_np(img, mode))[PAD s:-PAD s, PAD s:-PAD s].  On the chop path the tile gather reads the
-        image through the border map and the blend stores the crop window only (innfer_extract_tiles_u8_seamless, innfer_recompose_u8_seamless and
-        their _fit forms): neither the padded image nor the padded result exists.  Otherwise the image is padded on the GPU, run and cropped."""
+        image through the border map and the blend stores the crop window only: neither the padded image nor the padded result exists.  Otherwise the image is padded on the GPU, run and cropped."""
         import numpy as np
         from . import lib as L
         from .architectures.engine_module import EngineModule
-        from .parallel import run_tile_batches
         from .utils import utils as U
         host = isinstance(img, np.ndarray)
         mode = None
@@ -262,27 +260,7 @@ class Model:
         fused_net = isinstance(self.model, EngineModule) and self.arch != 'ppon'
         with torch.no_grad(), torch.cuda.device(d.device):
             if self.chop:
-                pad = 0 if mode is None else U.SEAMLESS_PAD                  # the lattice is the padded image's
-                ps = min(H + 2 * pad, W + 2 * pad, 200)
-                _, ys, xs = L.chop_plan(H + 2 * pad, W + 2 * pad, ps, 0.5)
-                n = len(ys) * len(xs)
-                tiles = torch.empty((n, Cc, ps, ps), dtype=dt, device=d.device)
-                if mode is None:
-                    L.check(L.lib.innfer_extract_tiles_u8(d.data_ptr(), Cc, H, W, int(bool(normalize)), ps, 0.5, 0, n, tiles.data_ptr(), code, stream))
-                else:
-                    L.check(L.lib.innfer_extract_tiles_u8_seamless(d.data_ptr(), Cc, H, W, int(bool(normalize)), ps, 0.5, 0, n, pad, mode, tiles.data_ptr(), code, stream))
-                hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=self._tile_buffer(tiles))
-                Co, P = hr.shape[1], hr.shape[2]
-                if out is None:
-                    out = torch.empty((H * s, W * s, Co), dtype=torch.uint8, device=d.device)
-                if mode is None:
-                    L.check(L.lib.innfer_recompose_u8(hr.data_ptr(), U._dt(hr), n, Co, P, H, W, 0.5, s, U._dt(hr), int(bool(normalize)),
-                                                      out.data_ptr(), stream))
-                else:
-                    if tuple(out.shape) != (H * s, W * s, Co) or out.dtype != torch.uint8 or not out.is_contiguous():
-                        raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {(H * s, W * s, Co)}')
-                    L.check(L.lib.innfer_recompose_u8_seamless(hr.data_ptr(), U._dt(hr), n, Co, P, H + 2 * pad, W + 2 * pad, 0.5, s, U._dt(hr),
-                                                               int(bool(normalize)), pad, out.data_ptr(), stream))
+                out = self._chop_u8(d, normalize, fp16, out, mode=mode)
             elif fused_net:
                 out = self.model.forward_u8(d, normalize=normalize, fp16=fp16, out=out)
             else:
@@ -293,6 +271,43 @@ class Model:
                     out = torch.empty((y.shape[2], y.shape[3], y.shape[1]), dtype=torch.uint8, device=d.device)
                 L.check(L.lib.innfer_nchw_to_u8hwc(y.data_ptr(), U._dt(y), y.shape[2], y.shape[3], y.shape[1], int(bool(normalize)), out.data_ptr(), stream))
         return out.cpu().numpy() if host else out
+
+    def _chop_u8(self, d, normalize, fp16, out, fit_C=None, mode=None):
+        """The chop path of run_u8 for the uint8 device image d: plan, gather, run the tiles, blend -- one gather and one blend call for all four forms.
+        fit_C: the fit_channels plan (1, 2, 4) or None; mode: the border code of run_u8(seamless=) or None, which is the same two kernels at pad = 0 /
+        crop = 0.  out is checked here under a seamless mode (_run_u8_fit has checked its own); the plain form takes it as given, as it always has."""
+        from . import lib as L
+        from .parallel import run_tile_batches
+        from .utils import utils as U
+        H, W = d.shape[:2]
+        s = int(self.scale or 1)
+        dt, code = (torch.float16, L.F16) if fp16 else (torch.float32, L.F32)
+        stream = torch.cuda.current_stream(d.device).cuda_stream
+        pad, border = (0, L.BORDER_MODES['replicate']) if mode is None else (U.SEAMLESS_PAD, mode)      # the lattice is the padded image's
+        const = U.alpha_constant(d, fit_C) if fit_C in (2, 4) else None
+        if mode == L.BORDER_MODES['alpha_pad'] and const:                   # the padding's alpha is 0: only an all-0 plane stays constant
+            const = None
+        alpha = fit_C in (2, 4) and const is None
+        ps = min(H + 2 * pad, W + 2 * pad, 200)
+        _, ys, xs = L.chop_plan(H + 2 * pad, W + 2 * pad, ps, 0.5)
+        n = len(ys) * len(xs)
+        tiles = torch.empty(((2 if alpha else 1) * n, 3 if fit_C else d.shape[2], ps, ps), dtype=dt, device=d.device)
+        gather = (d.data_ptr(), fit_C or d.shape[2], H, W, int(bool(normalize)), ps, 0.5, 0, n) + ((int(alpha),) if fit_C else ())
+        L.check((L.lib.innfer_extract_tiles_u8_fit_seamless if fit_C else L.lib.innfer_extract_tiles_u8_seamless)(*gather, pad, border, tiles.data_ptr(), code, stream))
+        hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=self._tile_buffer(tiles))
+        if fit_C and hr.shape[1] != 3:
+            raise ValueError(f'run_u8: fit_channels needs a 3-channel result, the network returned {hr.shape[1]}')
+        hr = hr.contiguous()
+        Co, P = hr.shape[1], hr.shape[2]
+        shape = U.fit_channels_out_shape(tuple(d.shape), s) if fit_C else (H * s, W * s, Co)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=d.device)
+        elif mode is not None and (tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous()):
+            raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {shape}')
+        blend = (hr.data_ptr(), U._dt(hr), n) + (() if fit_C else (Co,)) + (P, H + 2 * pad, W + 2 * pad, 0.5, s, U._dt(hr), int(bool(normalize)))
+        blend += (fit_C, int(alpha), -1 if const is None else const) if fit_C else ()
+        L.check((L.lib.innfer_recompose_u8_fit_seamless if fit_C else L.lib.innfer_recompose_u8_seamless)(*blend, pad, out.data_ptr(), stream))
+        return out
 
     def _run_u8_padded(self, img, seamless, normalize, fp16, out, fit_channels):
         """run_u8(seamless=) where the chop kernels do not apply (whole-image forwards): pad on the GPU (innfer_pad_inthwc), run as without the switch,
@@ -315,53 +330,22 @@ class Model:
     def _run_u8_fit(self, img, C, normalize, fp16, out, mode=None):
         """run_u8(fit_channels=True) of an HW / HWC (C 1, 2, 4) uint8 image with a 3 -> 3 network.  Chop: the colour tiles and the alpha tiles
         (none when the alpha plane is constant) are gathered into one buffer, run as one tile stream and blended in one pass
-        (innfer_extract_tiles_u8_fit / innfer_recompose_u8_fit).  Otherwise the two planes are split, run as separate forwards (never one batch:
+        (_chop_u8: the FIT forms of the gather and the blend).  Otherwise the two planes are split, run as separate forwards (never one batch:
         train-mode BatchNorm depends on the batch) and merged (innfer_inthwc_to_nchw_fit / innfer_nchw_to_inthwc_fit).
-        mode: the border code of run_u8(seamless=) on the chop path (the _seamless forms of the two kernels)."""
+        mode: the border code of run_u8(seamless=) on the chop path."""
         import numpy as np
-        from . import lib as L
-        from .parallel import run_tile_batches
         from .utils import utils as U
         host = isinstance(img, np.ndarray)
         d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img.contiguous()
         if d.dtype != torch.uint8:
             raise TypeError('run_u8: expected a uint8 image')
-        H, W = d.shape[:2]
-        s = int(self.scale or 1)
         dt = torch.float16 if fp16 else torch.float32
-        code = L.F16 if fp16 else L.F32
-        shape = U.fit_channels_out_shape(tuple(d.shape), s)
+        shape = U.fit_channels_out_shape(tuple(d.shape), int(self.scale or 1))
         if out is not None and (tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous()):
             raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {shape}')
         with torch.no_grad(), torch.cuda.device(d.device):
-            stream = torch.cuda.current_stream(d.device).cuda_stream
             if self.chop:
-                const = U.alpha_constant(d, C) if C in (2, 4) else None
-                if mode == L.BORDER_MODES['alpha_pad'] and const:           # the padding's alpha is 0: only an all-0 plane stays constant
-                    const = None
-                alpha = C in (2, 4) and const is None
-                pad = 0 if mode is None else U.SEAMLESS_PAD
-                ps = min(H + 2 * pad, W + 2 * pad, 200)
-                _, ys, xs = L.chop_plan(H + 2 * pad, W + 2 * pad, ps, 0.5)
-                n = len(ys) * len(xs)
-                tiles = torch.empty(((2 if alpha else 1) * n, 3, ps, ps), dtype=dt, device=d.device)
-                if mode is None:
-                    L.check(L.lib.innfer_extract_tiles_u8_fit(d.data_ptr(), C, H, W, int(bool(normalize)), ps, 0.5, 0, n, int(alpha), tiles.data_ptr(), code, stream))
-                else:
-                    L.check(L.lib.innfer_extract_tiles_u8_fit_seamless(d.data_ptr(), C, H, W, int(bool(normalize)), ps, 0.5, 0, n, int(alpha), pad, mode,
-                                                                       tiles.data_ptr(), code, stream))
-                hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=self._tile_buffer(tiles))
-                if hr.shape[1] != 3:
-                    raise ValueError(f'run_u8: fit_channels needs a 3-channel result, the network returned {hr.shape[1]}')
-                hr = hr.contiguous()
-                if out is None:
-                    out = torch.empty(shape, dtype=torch.uint8, device=d.device)
-                if mode is None:
-                    L.check(L.lib.innfer_recompose_u8_fit(hr.data_ptr(), U._dt(hr), n, hr.shape[2], H, W, 0.5, s, U._dt(hr), int(bool(normalize)), C,
-                                                          int(alpha), -1 if const is None else const, out.data_ptr(), stream))
-                else:
-                    L.check(L.lib.innfer_recompose_u8_fit_seamless(hr.data_ptr(), U._dt(hr), n, hr.shape[2], H + 2 * pad, W + 2 * pad, 0.5, s, U._dt(hr),
-                                                                   int(bool(normalize)), C, int(alpha), -1 if const is None else const, pad, out.data_ptr(), stream))
+                out = self._chop_u8(d, normalize, fp16, out, fit_C=C, mode=mode)
             else:
                 colour, alpha, const = U.fit_split(d, normalize=normalize, dtype=dt)
                 y = self._predict(colour)

@@ -159,7 +159,7 @@ def tensor2np(img, rgb2bgr=True, remove_batch=True, data_range=255, denormalize=
 # ---------------------------------------------------------------- fit_channels: gray, gray + alpha and BGRA images through an RGB network
 # The colour plane goes through the network as (g, g, g) or RGB, the alpha plane as (a, a, a); a gray or alpha result is mean3 of the network's
 # three channels, ((y0 + y1) + y2) / 3 in fp32 rounded to the result dtype, quantised as tensor2np.  A constant alpha plane is not run: its value is
-# copied.  Kernels: csrc/tiles.hip (include/innfer_amd.h, ABI 115).  The reference runs such images as they are and fails (utils.py:164-248).
+# copied.  Kernels: csrc/tiles.hip, csrc/tiles_u8.hip (include/innfer_amd.h, ABI 115).  The reference runs such images as they are and fails (utils.py:164-248).
 
 def fit_channels_plan(shape, dtype, in_nc, out_nc):
     """How Model.run_u8(fit_channels=True) / `-fit_channels` run an image of `shape` (HWC or HW) with an in_nc -> out_nc network:
@@ -256,7 +256,7 @@ def fit_channels_forward(fn, img, normalize=False, device='cuda', dtype=torch.fl
 
 # ---------------------------------------------------------------- seamless modes: tileable textures without a seam at the border
 # The image is run as if it had been padded by SEAMLESS_PAD pixels with its own continuation ('tile', 'mirror', 'replicate') or with transparent black
-# ('alpha_pad') and the padding cut off the result.  Kernels: csrc/tiles_seamless.hip (include/innfer_amd.h, ABI 117).  Not in the reference.
+# ('alpha_pad') and the padding cut off the result.  Kernels: csrc/tiles_u8.hip (include/innfer_amd.h, ABI 117).  Not in the reference.
 SEAMLESS_MODES = tuple(L.BORDER_MODES)
 _NP_PAD_MODE = {'tile': 'wrap', 'mirror': 'reflect', 'replicate': 'edge', 'alpha_pad': 'constant'}
 

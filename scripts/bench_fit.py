@@ -5,8 +5,8 @@ each, with the shader clock rocm-smi reports after the run.
 
     python scripts/bench_fit.py [--steps 5] [--warmup 2]
 
-Kernel times: run it under `rocprofv3 --kernel-trace --stats` (a run of its own) and compare k_extract_u8_fit / k_recompose_u8_fit with
-k_extract_u8 / k_recompose (U8OUT) of the BGR frame."""
+Kernel times: run it under `rocprofv3 --kernel-trace --stats` (a run of its own) and compare the FIT instantiations of k_extract_u8 /
+k_recompose_u8 with those of the BGR frame, or run `scripts/bench_seamless.py --kernels-only`."""
 import argparse
 import json
 import os

@@ -8,8 +8,10 @@
 as host images (numpy in, numpy out: PCIe and the host passes are in the time -- the explicit route only exists there) and, for the first two, as
 device images (tensor in, `out=`: GPU time only).  The forms are interleaved round by round; medians, one JSON line per (image, form, residence).
 
-Then the two new kernels alone against the kernels they extend, at the same shapes on the same box: device events around `--reps` launches, the
-pairs alternated, median of `--steps` windows; the rate is the algorithm's bytes (image + tiles) over that time.
+Then the gather and the blend alone (`--kernels-only`: nothing else), the seamless entry points on the image against the plain entry points on the
+padded image -- the same kernel at pad 16 / crop 16 and at pad 0 / crop 0 -- at the same shapes on the same box: device events around `--reps`
+launches, the pairs alternated, median of `--steps` windows; the rate is the algorithm's bytes (image + tiles) over that time.  `extended_ms` is the
+time of the plain and fit entry points: the figure to compare across revisions.
 
     python scripts/bench_seamless.py [--steps 5] [--warmup 2] [--reps 20]"""
 import argparse
@@ -89,7 +91,7 @@ def main(argv=None):
         del m
         torch.cuda.empty_cache()
 
-    # ---- the kernels alone: seamless gather / blend on the image vs the kernel it extends on the padded image (same lattice, same tile bytes)
+    # ---- the kernels alone: seamless gather / blend on the image vs the plain entry point on the padded image (same lattice, same tile bytes)
     stream = torch.cuda.current_stream(dev).cuda_stream
 
     def window(fn):
