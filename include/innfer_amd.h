@@ -45,8 +45,8 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  innfer_version() returns the library's; a binding should compare. */
-#define INNFER_ABI_VERSION 117
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  innfer_version() returns the library's; a binding should compare. */
+#define INNFER_ABI_VERSION 118
 int innfer_version(void);
 const char* innfer_last_error(void);
 
@@ -660,6 +660,41 @@ int innfer_color_fix(const uint8_t* d_lr, int h_lr, int w_lr, const uint8_t* d_s
  * Workspace: h * w * C floats.  (104) */
 int innfer_linear_resize(const uint8_t* d_img, int h, int w, int C, uint8_t* d_out, int oh, int ow,
                          void* d_workspace, size_t workspace_bytes, void* stream);
+
+/* Resampling to any final size (118, `-outscale`): an antialiased separable resampler in the Pillow / ATen `antialias=True` convention, uint8 / uint16 HWC
+ * images of 1 .. 4 channels, enlarging and reducing.  Not in the reference, whose users download the full result and resize on the host.  innfer_linear_resize
+ * above (OpenCV's 4-tap cubic, enlarging only, no antialiasing) is another function and is unchanged.
+ *
+ * The tables of one axis of n_in samples and n_out outputs, filter f of support S
+ *   INNFER_RESAMPLE_BOX       1 on (-0.5, 0.5], S = 0.5          INNFER_RESAMPLE_BILINEAR  triangle, S = 1
+ *   INNFER_RESAMPLE_BICUBIC   Keys a = -0.5, S = 2               INNFER_RESAMPLE_LANCZOS   sinc(x) sinc(x / 3) on [-3, 3), S = 3
+ * for output i: scale = n_in / n_out, fs = max(scale, 1), support = S fs, c = (i + 0.5) scale, lo = floor(c - support + 0.5), hi = floor(c + support + 0.5);
+ * wrap = 0: lo is clamped to >= 0 and hi to <= n_in (the window is truncated at the border and renormalised); wrap != 0: lo and hi stay and tap j reads
+ * sample j mod n_in (a tileable texture stays tileable).  w_j = f((j - c + 0.5) / fs) for j in [lo, hi), computed in float64, divided by their sum,
+ * rounded once to float32.
+ *
+ * innfer_resample_taps (host only): T, the largest hi - lo of any output, wrapped or not; < 0 on a bad argument.
+ * innfer_resample_plan (host only, no HIP call): start[i] = lo (may be negative when wrapping), count[i] = hi - lo, weights [n_out][T] zero-padded
+ *   behind count[i]; T >= innfer_resample_taps.  n_in, n_out 1 .. 2^28.
+ * innfer_resample_inthwc: d_src [h, w, C] -> d_dst [oh, ow, C], bits 8 / 16, C 1 .. 4, with DEVICE copies of the horizontal plan (w -> ow, width Th)
+ *   and the vertical one (h -> oh, width Tv).  Channels are filtered independently (alpha is straight, not premultiplied).  The horizontal pass runs
+ *   first, on every source row the vertical pass needs; its float32 result is the input of the vertical pass.  In each pass the float32 accumulator
+ *   starts at 0 and takes acc = acc + w x per tap in ascending j, the multiply and the add each rounded to float32 (no FMA); the stored code is
+ *   clamp(floor(acc + 0.5f), 0, 255 | 65535).  An axis with n_out == n_in goes through its table like any other.  One launch with the intermediate
+ *   in LDS wherever a block of output pixels fits (innfer_resample_workspace_bytes returns 0); otherwise (reductions by hundreds) two launches
+ *   through the float32 intermediate [h, ow, C] in d_workspace -- the same arithmetic in the same order, so the same bytes; too small a workspace:
+ *   INNFER_ERR_WORKSPACE.  Offsets are size_t.  Arguments are checked before any device call (INNFER_ERR_INVALID). */
+#define INNFER_RESAMPLE_BOX 0
+#define INNFER_RESAMPLE_BILINEAR 1
+#define INNFER_RESAMPLE_BICUBIC 2
+#define INNFER_RESAMPLE_LANCZOS 3
+int innfer_resample_taps(int n_in, int n_out, int filter);
+int innfer_resample_plan(int n_in, int n_out, int filter, int wrap, int* start, int* count, float* weights, int T);
+size_t innfer_resample_workspace_bytes(int h, int w, int C, int oh, int ow, int Th, int Tv);
+int innfer_resample_inthwc(const void* d_src, int bits, int h, int w, int C, void* d_dst, int oh, int ow,
+                           const int* d_hstart, const int* d_hcount, const float* d_hweights, int Th,
+                           const int* d_vstart, const int* d_vcount, const float* d_vweights, int Tv,
+                           int wrap, void* d_workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

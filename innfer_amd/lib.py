@@ -223,6 +223,11 @@ SIGNATURES = {
     "innfer_extract_tiles_u8_fit_seamless": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_recompose_u8_seamless": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_double] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "innfer_recompose_u8_fit_seamless": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
+    "innfer_resample_taps": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "innfer_resample_plan": (C.c_int, [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "innfer_resample_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
+    "innfer_resample_inthwc": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] * 2
+                               + [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "innfer_f32conv_packed_floats": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "innfer_pack_f32conv": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "innfer_f32conv": (C.c_int, [C.POINTER(F32ConvArgs), C.c_void_p]),
@@ -248,7 +253,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 lib = _lib
 
-ABI_VERSION = 117          # the header revision this binding was written against (INNFER_ABI_VERSION)
+ABI_VERSION = 118          # the header revision this binding was written against (INNFER_ABI_VERSION)
 if _lib.innfer_version() != ABI_VERSION and not _ABI_ANY:
     raise ImportError(f"{LIB_PATH} speaks ABI {_lib.innfer_version()}, this binding {ABI_VERSION}: rebuild with `make`")
 
@@ -301,6 +306,37 @@ def border_index(i, n, mode):
     if r < BORDER_OUTSIDE:
         raise ValueError(last_error())
     return r
+
+
+RESAMPLE_FILTERS = {"box": 0, "bilinear": 1, "bicubic": 2, "lanczos": 3}     # INNFER_RESAMPLE_*: the filters of the resampler (-outfilter)
+
+
+def resample_filter(filter):
+    """The INNFER_RESAMPLE_* code of a filter name (or the code itself); ValueError for anything else."""
+    code = RESAMPLE_FILTERS.get(filter, -1) if isinstance(filter, str) else filter
+    if code not in RESAMPLE_FILTERS.values():
+        raise ValueError(f"resample: filter must be one of {', '.join(RESAMPLE_FILTERS)}, got {filter!r}")
+    return int(code)
+
+
+def resample_taps(n_in, n_out, filter="lanczos"):
+    """innfer_resample_taps (host only): the widest window of the axis n_in -> n_out, wrapped or not."""
+    T = _lib.innfer_resample_taps(int(n_in), int(n_out), resample_filter(filter))
+    if T < 0:
+        raise ValueError(last_error())
+    return T
+
+
+def resample_plan(n_in, n_out, filter="lanczos", wrap=False, T=None):
+    """innfer_resample_plan (host only): (start int32 [n_out], count int32 [n_out], weights float32 [n_out, T]) of one axis; T defaults to
+    resample_taps.  Output i is the sum over t < count[i] of weights[i, t] * sample (start[i] + t) (mod n_in when wrapping)."""
+    import numpy as np
+    code = resample_filter(filter)
+    T = resample_taps(n_in, n_out, code) if T is None else int(T)
+    start, count = np.empty(n_out, np.int32), np.empty(n_out, np.int32)
+    weights = np.empty((n_out, T), np.float32)
+    check(_lib.innfer_resample_plan(int(n_in), int(n_out), code, int(bool(wrap)), start.ctypes.data, count.ctypes.data, weights.ctypes.data, T))
+    return start, count, weights
 
 
 F32_PLAN_KEYS = ("direct", "NKT", "NPT", "IMG", "CC", "vec4", "workgroups", "lds")

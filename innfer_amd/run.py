@@ -221,7 +221,7 @@ class Model:
         with torch.no_grad():
             return self._predict(data)
 
-    def run_u8(self, img, normalize=False, fp16=True, out=None, fit_channels=False, seamless=None):
+    def run_u8(self, img, normalize=False, fp16=True, out=None, fit_channels=False, seamless=None, outscale=None, outfilter='lanczos'):
         """Image in, image out: tensor2np(self(np2tensor(img, normalize)[.half()]), denormalize=normalize) (run.py:421-431) with the two
         conversions fused into the neighbouring kernels -- the tile gather / the blend on the chop path (_chop_u8: innfer_extract_tiles_u8_seamless,
         innfer_recompose_u8_seamless and their _fit forms, at pad = 0 / crop = 0 without a seamless mode), the first / last conv otherwise (EngineModule.forward_u8).  Bit-identical to the separate passes.
@@ -230,8 +230,13 @@ class Model:
         as (g, g, g) / RGB, a non-constant alpha plane as (a, a, a); returns the input's layout at the network's scale.
         seamless: 'tile', 'mirror', 'replicate' or 'alpha_pad' -- the result of the image padded by SEAMLESS_PAD pixels that way (utils.seamless_pad_np),
         without the padding: bit for bit run_u8(seamless_pad_np(img, mode))[PAD s:-PAD s, PAD s:-PAD s].  On the chop path the tile gather reads the
-        image through the border map and the blend stores the crop window only: neither the padded image nor the padded result exists.  Otherwise the image is padded on the GPU, run and cropped."""
+        image through the border map and the blend stores the crop window only: neither the padded image nor the padded result exists.  Otherwise the image is padded on the GPU, run and cropped.
+        outscale: the final size relative to the INPUT, int(H outscale) x int(W outscale) (Real-ESRGAN's --outscale) -- the device result is resampled
+        (utils.resample, filter `outfilter`: lanczos, bicubic, bilinear, box) before it is downloaded: bit for bit utils.resample_np(run_u8(img), ...).
+        Under seamless='tile' the taps wrap around, so the texture still tiles; alpha is filtered straight, not premultiplied.  `out` then has the final shape."""
         import numpy as np
+        if outscale is not None:
+            return self._run_u8_outscale(img, outscale, outfilter, normalize, fp16, out, fit_channels, seamless)
         from . import lib as L
         from .architectures.engine_module import EngineModule
         from .utils import utils as U
@@ -271,6 +276,24 @@ class Model:
                     out = torch.empty((y.shape[2], y.shape[3], y.shape[1]), dtype=torch.uint8, device=d.device)
                 L.check(L.lib.innfer_nchw_to_u8hwc(y.data_ptr(), U._dt(y), y.shape[2], y.shape[3], y.shape[1], int(bool(normalize)), out.data_ptr(), stream))
         return out.cpu().numpy() if host else out
+
+    def _run_u8_outscale(self, img, outscale, outfilter, normalize, fp16, out, fit_channels, seamless):
+        """run_u8(outscale=): the plain call on the device, then utils.resample to int(H outscale) x int(W outscale) before the download.  A final size
+        equal to the network's own result is the plain result: nothing is resampled."""
+        import numpy as np
+        from . import lib as L
+        from .utils import utils as U
+        host = isinstance(img, np.ndarray)
+        oh, ow = U.resample_size(img.shape[0], img.shape[1], outscale)
+        L.resample_filter(outfilter)
+        d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img
+        r = self.run_u8(d, normalize=normalize, fp16=fp16, fit_channels=fit_channels, seamless=seamless)
+        shape = (oh, ow) + tuple(r.shape[2:])
+        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous()):
+            raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {shape}')
+        with torch.cuda.device(r.device):
+            r = U.resample(r, size=(oh, ow), filter=outfilter, wrap=seamless == 'tile', out=out)
+        return r.cpu().numpy() if host else r
 
     def _chop_u8(self, d, normalize, fp16, out, fit_C=None, mode=None):
         """The chop path of run_u8 for the uint8 device image d: plan, gather, run the tiles, blend -- one gather and one blend call for all four forms.
@@ -409,6 +432,7 @@ def get_scale_name(model_path, scale=None):
 
 
 SEAMLESS_CHOICES = ('tile', 'mirror', 'replicate', 'alpha_pad')           # utils.SEAMLESS_MODES
+OUTFILTER_CHOICES = ('lanczos', 'bicubic', 'bilinear', 'box')             # utils.RESAMPLE_FILTERS
 
 pix2pix_extras = {'meval': False, 'strict': True, 'normalize': True}       # run.py:299-303
 cyglegan_extras = {'meval': True, 'strict': False, 'normalize': True}      # run.py:305-309
@@ -435,6 +459,10 @@ def build_parser():
     parser.add_argument('-seamless', required=False, choices=SEAMLESS_CHOICES, default=argparse.SUPPRESS,
                         help='Upscale tileable textures without a seam: the image is padded by 16 px (tile: wrap around, mirror, replicate: edge pixels, '
                              'alpha_pad: transparent black) and the padding is cut off the result.')
+    parser.add_argument('-outscale', required=False, type=float, default=argparse.SUPPRESS,
+                        help='Final size relative to the input, e.g. 2 or 2.5 with a 4x model: the result is resampled on the GPU before it is downloaded.')
+    parser.add_argument('-outfilter', required=False, choices=OUTFILTER_CHOICES, default=argparse.SUPPRESS,
+                        help='Filter of -outscale (default lanczos); antialiased when it reduces.')
     return parser
 
 
@@ -468,6 +496,9 @@ def main(argv=None):
     if seamless and resize:
         raise ValueError(f"-seamless {seamless} with '{args.arch}': the preset enlarges every image to a multiple of {resize} px first, which no tileable "
                          "texture survives; resize the texture yourself and run it without the preset")
+    outscale, outfilter = getattr(args, 'outscale', None), getattr(args, 'outfilter', 'lanczos')
+    if outscale is not None:
+        U.resample_size(1, 1, outscale)                     # ValueError unless 0 < F < inf
     meval, strict = defaults['meval'], defaults['strict']
     normalize = defaults['normalize'] or args.norm
     device = torch.device('cuda')
@@ -541,6 +572,9 @@ def main(argv=None):
                 img = img[:, :, None]
             single = len(models) == 1 and not use_guided_filter and img.dtype == np.uint8
             sm = {'seamless': seamless} if seamless else {}                             # run_u8 pads and crops inside its kernels
+            final = U.resample_size(img.shape[0], img.shape[1], outscale) if outscale is not None else None      # relative to the image fed to the chain
+            if final and not args.cf:                                                   # run_u8 resamples before the download
+                sm.update(outscale=outscale, outfilter=outfilter)
             src = img
             if seamless and not (single and (plan or img.ndim == 3)):                   # chains, 16-bit images, the guided filter: pad once in front, crop behind
                 img = U.seamless_pad(img, seamless)
@@ -565,6 +599,8 @@ def main(argv=None):
                 img, img_out = src, U.seamless_crop(img_out, total)
             if args.cf:
                 img_out = U.color_fix(img, img_out)
+            if final and img_out.shape[:2] != final:                                    # not done inside run_u8: chains, -cf, 16-bit images, the guided filter
+                img_out = U.resample(img_out, size=final, filter=outfilter, wrap=seamless == 'tile')
             if flat:
                 img, img_out = img[:, :, 0], img_out[:, :, 0]
             out_path = osp.join(args.output, f'{img_name:s}.png')

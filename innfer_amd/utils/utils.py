@@ -8,6 +8,7 @@ HIP kernels (csrc/tiles.hip) through the C ABI:
 Same names, argument meaning and error behaviour.  Tensors must live on the
 GPU; there is no CPU fallback.
 """
+import functools
 import os
 import os.path as osp
 
@@ -314,6 +315,102 @@ def seamless_crop(img_out, scale, pad=SEAMLESS_PAD):
         raise ValueError(f'seamless_crop: nothing is left of {H}x{W} after {c} pixels off every side')
     r = img_out[c:H - c, c:W - c]
     return np.ascontiguousarray(r) if isinstance(img_out, np.ndarray) else r.contiguous()
+
+
+# ---------------------------------------------------------------- resampling to any final size (-outscale)
+# An antialiased separable resampler in the Pillow / ATen antialias=True convention (include/innfer_amd.h, ABI 118; csrc/resample.hip).  Channels are
+# filtered independently: alpha is straight, NOT premultiplied, so colour under a transparent pixel does bleed into its neighbours' colour.  Not in the reference.
+RESAMPLE_FILTERS = tuple(L.RESAMPLE_FILTERS)
+
+
+def resample_size(h, w, scale):
+    """The size of an h x w image at `scale`, by Real-ESRGAN's rule: max(1, int(h scale)) x max(1, int(w scale)).  ValueError unless 0 < scale < inf."""
+    scale = float(scale)
+    if not (scale > 0 and scale != float('inf')):
+        raise ValueError(f'resample: the scale must be a positive finite number, got {scale!r}')
+    return max(1, int(h * scale)), max(1, int(w * scale))
+
+
+def _resample_axis0_np(x, plan, wrap):
+    """One pass along axis 0 of the float32 array x: acc = acc + w * x per tap in ascending order, every operation rounded to float32."""
+    start, count, weights = plan
+    n = x.shape[0]
+    acc = np.zeros((len(start),) + x.shape[1:], np.float32)
+    tail = (1,) * (x.ndim - 1)
+    for t in range(weights.shape[1]):                       # behind count[i] the weight is +0: acc + 0 * x == acc
+        idx = start.astype(np.int64) + t
+        idx = idx % n if wrap else np.clip(idx, 0, n - 1)
+        acc = acc + weights[:, t].reshape((-1,) + tail) * x[idx]
+    return acc
+
+
+def resample_np(img, oh, ow, filter='lanczos', wrap=False):
+    """The contract of the resampler in numpy: the HW / HWC uint8 or uint16 image at oh x ow, built from innfer_resample_plan's tables -- the
+    horizontal pass, then the vertical one, float32 throughout, taps in ascending order, the code clamp(floor(acc + 0.5), 0, maxval)."""
+    if not isinstance(img, np.ndarray) or img.ndim not in (2, 3) or img.dtype not in (np.uint8, np.uint16):
+        raise TypeError('resample_np: expected an HW / HWC uint8 or uint16 numpy image')
+    h, w = img.shape[:2]
+    x = img.astype(np.float32)
+    x = np.swapaxes(_resample_axis0_np(np.swapaxes(x, 0, 1), L.resample_plan(w, ow, filter, wrap), wrap), 0, 1)
+    x = _resample_axis0_np(np.ascontiguousarray(x), L.resample_plan(h, oh, filter, wrap), wrap)
+    maxval = 255 if img.dtype == np.uint8 else 65535
+    return np.clip(np.floor(x + np.float32(0.5)), 0, maxval).astype(img.dtype)
+
+
+@functools.lru_cache(maxsize=64)
+def _resample_plan_dev(n_in, n_out, code, wrap, device):
+    """The plan of one axis on `device`, uploaded once per (n_in, n_out, filter, wrap): (start, count, weights, T)."""
+    start, count, weights = L.resample_plan(n_in, n_out, code, wrap)
+    return tuple(torch.from_numpy(a).to(device) for a in (start, count, weights)) + (weights.shape[1],)
+
+
+def resample(img, size=None, scale=None, filter='lanczos', wrap=False, out=None):
+    """resample_np on the GPU (innfer_resample_inthwc): img is an HW / HWC (C 1 .. 4) uint8 or uint16 numpy image (a numpy image comes back) or a uint8 /
+    int16-viewed uint16 GPU tensor (a GPU tensor comes back).  size = (oh, ow), or scale: resample_size.  wrap: taps wrap around, for tileable textures.
+    A target equal to the source size returns img itself: no kernel runs.  out: a contiguous GPU tensor of the result's shape to write into."""
+    host = isinstance(img, np.ndarray)
+    if img.ndim not in (2, 3):
+        raise TypeError('resample: expected an HW / HWC image')
+    if (size is None) == (scale is None):
+        raise ValueError('resample: give exactly one of size and scale')
+    h, w = img.shape[:2]
+    oh, ow = resample_size(h, w, scale) if size is None else (int(size[0]), int(size[1]))
+    code = L.resample_filter(filter)
+    if oh < 1 or ow < 1:
+        raise ValueError(f'resample: bad size {oh}x{ow}')
+    if (oh, ow) == (h, w) and out is None:
+        return img
+    if host:
+        if img.dtype not in (np.uint8, np.uint16):
+            raise TypeError(f'resample: uint8 / uint16 images, got {img.dtype}')
+        a = np.ascontiguousarray(img)
+        d = torch.from_numpy(a if a.dtype == np.uint8 else a.view(np.int16)).cuda()
+    else:
+        if img.dtype not in (torch.uint8, torch.int16):
+            raise TypeError(f'resample: uint8 / int16-viewed uint16 tensors, got {img.dtype}')
+        _need_cuda(img, 'resample')
+        d = img.contiguous()
+    Cc = d.shape[2] if d.dim() == 3 else 1
+    shape = (oh, ow) + tuple(d.shape[2:])
+    if out is None:
+        out = torch.empty(shape, dtype=d.dtype, device=d.device)
+    elif tuple(out.shape) != shape or out.dtype != d.dtype or out.device != d.device or not out.is_contiguous():
+        raise ValueError(f'resample: out must be a contiguous {d.dtype} tensor of shape {shape} on {d.device}')
+    if (oh, ow) == (h, w):
+        out.copy_(d)
+        return out
+    wrap = bool(wrap)
+    hs, hc, hw, Th = _resample_plan_dev(w, ow, code, wrap, d.device)
+    vs, vc, vw, Tv = _resample_plan_dev(h, oh, code, wrap, d.device)
+    nbytes = L.lib.innfer_resample_workspace_bytes(h, w, Cc, oh, ow, Th, Tv)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=d.device) if nbytes else None
+    with _on(d):
+        L.check(L.lib.innfer_resample_inthwc(d.data_ptr(), _bits(d), h, w, Cc, out.data_ptr(), oh, ow, hs.data_ptr(), hc.data_ptr(), hw.data_ptr(), Th,
+                                             vs.data_ptr(), vc.data_ptr(), vw.data_ptr(), Tv, int(wrap), ws.data_ptr() if nbytes else None, nbytes, _stream(d)))
+    if not host:
+        return out
+    arr = out.cpu().numpy()
+    return arr.view(np.uint16) if img.dtype == np.uint16 else arr
 
 
 # ---------------------------------------------------------------- files (utils.py:36-133): the image loop's codec hand-off
