@@ -45,8 +45,8 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  innfer_version() returns the library's; a binding should compare. */
-#define INNFER_ABI_VERSION 118
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  innfer_version() returns the library's; a binding should compare. */
+#define INNFER_ABI_VERSION 119
 int innfer_version(void);
 const char* innfer_last_error(void);
 
@@ -640,6 +640,32 @@ int innfer_recompose_u8_seamless(const void* d_tiles, int dtype, int n_tiles, in
                                  int via_dtype, int denormalize, int crop, uint8_t* d_img, void* stream);
 int innfer_recompose_u8_fit_seamless(const void* d_tiles, int dtype, int n_tiles, int P, int height, int width, double step, int scale,
                                      int via_dtype, int denormalize, int C, int alpha, int alpha_const, int crop, uint8_t* d_img, void* stream);
+
+/* Self-ensemble (119, `-tta`; ESRGAN's / EDSR's --self_ensemble, "x8"): the image runs through the network in its eight dihedral orientations and the
+ * eight results, turned back, are averaged BEFORE quantisation.  Not in the reference.  t_k(x), k = 0 .. 7: transpose (H, W) if k & 4, then flip the
+ * columns if k & 1, then flip the rows if k & 2; t_0 is the identity and t_k^-1 undoes the steps in reverse order.  For k >= 4 the oriented image is
+ * W x H and has the chop lattice of a W x H image: nh and nw swap, the tile count n stays.  Every orientation has its OWN lattice (the lattice clamps its
+ * last row and column, so the tiles of t_k(x) are not the turned tiles of x).  The result is, in tensor terms,
+ *   acc = t_0^-1(f(t_0(x))) as float32;  acc += t_k^-1(f(t_k(x))) as float32 for k = 1 .. 7 in this order;  (acc * 0.125) rounded to the tensor dtype
+ * with f = chop, run, blend (Model.forward_tta), then quantised as innfer_recompose_u8 / _fit does.
+ *
+ * innfer_dihedral_index (host only): *sy, *sx = the pixel of the H x W image that pixel (y, x) of t_k(image) shows.  INNFER_ERR_INVALID for k outside
+ *   0 .. 7 or a pixel outside the oriented image.
+ * innfer_extract_tiles_u8_tta: all tiles of the eight orientations of d_img [H, W, C] into d_tiles [8 n (16 n with alpha), C | 3, ps, ps], n the tile count
+ *   of innfer_chop_plan(H + 2 pad, W + 2 pad, patch, step).  Orientation k occupies slots [k n, (k + 1) n), with alpha its alpha tiles [8 n + k n, ..).
+ *   Slot k n + i holds what innfer_extract_tiles_u8[_fit][_seamless] returns as tile i of the image t_k(d_img): arithmetic, channel flip and the border
+ *   map (pad, mode; the padding is pad on every side, so t_k(pad(x)) == pad(t_k(x))) are theirs.  fit = 0, pad = 0 is the plain form; fit != 0 the
+ *   fit_channels form (C 1, 2, 4; alpha only then).  C 1 .. 4, else INNFER_ERR_UNSUPPORTED.
+ * innfer_recompose_u8_tta: d_tiles [8 n (16 n), C | 3, P, P] in that slot order -> d_img [scale (height - 2 crop), scale (width - 2 crop), C].  height,
+ *   width, crop, n, fit, alpha, alpha_const as for innfer_recompose_u8[_fit]_seamless (n = tiles of ONE orientation; crop = 0: the whole blend).  Per
+ *   output pixel and orientation the blend of innfer_recompose_u8 at the pixel's place in that orientation's frame, rounded to via_dtype; the eight are
+ *   added as float32 in the order k = 0 .. 7, multiplied by 0.125f and rounded to via_dtype; then mean3 / the constant alpha (fit) and the quantisation.
+ *   C 1 .. 4, else INNFER_ERR_UNSUPPORTED. */
+int innfer_dihedral_index(int k, int H, int W, int y, int x, int* sy, int* sx);
+int innfer_extract_tiles_u8_tta(const uint8_t* d_img, int C, int H, int W, int normalize, int patch, double step, int fit, int alpha,
+                                int pad, int mode, void* d_tiles, int tile_dtype, void* stream);
+int innfer_recompose_u8_tta(const void* d_tiles, int dtype, int n, int C, int P, int height, int width, double step, int scale,
+                            int via_dtype, int denormalize, int fit, int alpha, int alpha_const, int crop, uint8_t* d_img, void* stream);
 
 /* srgb2linear / linear2srgb (utils/colors.py:29-46, 49-60), the pointwise halves of the `-cf` colour
  * fix: uint8 sRGB -> float32 linear, and float32 linear -> uint8 sRGB (clip, gamma, *255, TRUNCATING

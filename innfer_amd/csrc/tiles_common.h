@@ -1,4 +1,4 @@
-// Device helpers and host geometry shared by the tile kernels (tiles.hip, tiles_u8.hip): the blend profile, one pixel's bytes as one load / store,
+// Device helpers and host geometry shared by the tile kernels (tiles.hip, tiles_u8.hip, tiles_tta.hip): the blend profile, one pixel's bytes as one load / store,
 // the np2tensor / tensor2np element ops, the blend overlap and the blend's geometry check.  Every rounding is explicit (__f*_rn), so the values do not depend on the including file's
 // contraction setting.
 #pragma once
@@ -71,6 +71,37 @@ inline int blend_geo(const char* who, int n, int P, int height, int width, doubl
     if (batch && n % (g->nh * g->nw)) return set_error(INNFER_ERR_INVALID, "%s: %d tiles is not a multiple of %dx%d", who, n, g->nh, g->nw);
     if (!batch && n != g->nh * g->nw) return set_error(INNFER_ERR_INVALID, "%s: one image of %dx%d tiles expected, got %d tiles", who, g->nh, g->nw, n);
     g->cs = scale * crop;
+    return INNFER_OK;
+}
+
+// Source index of position i (relative to the image: -pad .. n + pad - 1) on an axis of n pixels; -1: outside under INNFER_BORDER_ALPHA_PAD.  Inside the
+// image no division is made.  INNFER_BORDER_MIRROR needs n >= 2 (its period is 2 (n - 1)): the entry points refuse n < 2 before anything is launched.
+__host__ __device__ __forceinline__ int border_index(int i, int n, int mode) {
+    if ((unsigned)i < (unsigned)n) return i;
+    if (mode == INNFER_BORDER_TILE) {
+        const int r = i % n;
+        return r < 0 ? r + n : r;
+    }
+    if (mode == INNFER_BORDER_MIRROR) {
+        const int p = 2 * (n - 1);
+        int j = i % p;
+        if (j < 0) j += p;
+        return j < n ? j : p - j;
+    }
+    if (mode == INNFER_BORDER_REPLICATE) return i < 0 ? 0 : n - 1;
+    return -1;
+}
+
+// N elements in one load / store at alignment A bytes (3-channel pixels: four of them are 12 bytes at 4, one is three byte accesses)
+template <typename T, int N, int A> struct alignas(A) Run { T v[N]; };
+
+// what every entry point checks of (H, W, pad, mode); 0 or the error already set
+inline int check_border(const char* who, int H, int W, int pad, int mode) {
+    if (H <= 0 || W <= 0 || pad < 0) return set_error(INNFER_ERR_INVALID, "%s: bad sizes H=%d W=%d pad=%d", who, H, W, pad);
+    if (mode < INNFER_BORDER_TILE || mode > INNFER_BORDER_ALPHA_PAD) return set_error(INNFER_ERR_INVALID, "%s: border mode %d (0 tile, 1 mirror, 2 replicate, 3 alpha_pad)", who, mode);
+    if (mode == INNFER_BORDER_MIRROR && (H < 2 || W < 2))
+        return set_error(INNFER_ERR_INVALID, "%s: mirror needs at least 2 rows and 2 columns, the image is %dx%d", who, H, W);
+    if ((long)H + 2L * pad > 0x3fffffffL || (long)W + 2L * pad > 0x3fffffffL) return set_error(INNFER_ERR_INVALID, "%s: padded size overflows", who);
     return INNFER_OK;
 }
 

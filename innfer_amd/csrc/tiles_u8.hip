@@ -14,27 +14,6 @@
 namespace innfer {
 namespace {
 
-// Source index of position i (relative to the image: -pad .. n + pad - 1) on an axis of n pixels; -1: outside under INNFER_BORDER_ALPHA_PAD.  Inside the
-// image no division is made.  INNFER_BORDER_MIRROR needs n >= 2 (its period is 2 (n - 1)): the entry points refuse n < 2 before anything is launched.
-__host__ __device__ __forceinline__ int border_index(int i, int n, int mode) {
-    if ((unsigned)i < (unsigned)n) return i;
-    if (mode == INNFER_BORDER_TILE) {
-        const int r = i % n;
-        return r < 0 ? r + n : r;
-    }
-    if (mode == INNFER_BORDER_MIRROR) {
-        const int p = 2 * (n - 1);
-        int j = i % p;
-        if (j < 0) j += p;
-        return j < n ? j : p - j;
-    }
-    if (mode == INNFER_BORDER_REPLICATE) return i < 0 ? 0 : n - 1;
-    return -1;
-}
-
-// N elements in one load / store at alignment A bytes (3-channel pixels: four of them are 12 bytes at 4, one is three byte accesses)
-template <typename T, int N, int A> struct alignas(A) Run { T v[N]; };
-
 template <typename T, int C>
 __global__ void __launch_bounds__(256) k_pad_inthwc(const T* img, T* out, int H, int W, int pad, int mode, int WP) {
     const int X = blockIdx.x * 256 + threadIdx.x, Y = blockIdx.y;
@@ -209,16 +188,6 @@ __global__ void __launch_bounds__(256) k_recompose_u8(const TI* tiles, int n, in
         }
     }
     *(Run<uint8_t, C, C == 3 ? 1 : C>*)(img + ((long)Yo * OW + Xo) * C) = o;
-}
-
-// what every entry point checks of (H, W, pad, mode); 0 or the error already set
-int check_border(const char* who, int H, int W, int pad, int mode) {
-    if (H <= 0 || W <= 0 || pad < 0) return set_error(INNFER_ERR_INVALID, "%s: bad sizes H=%d W=%d pad=%d", who, H, W, pad);
-    if (mode < INNFER_BORDER_TILE || mode > INNFER_BORDER_ALPHA_PAD) return set_error(INNFER_ERR_INVALID, "%s: border mode %d (0 tile, 1 mirror, 2 replicate, 3 alpha_pad)", who, mode);
-    if (mode == INNFER_BORDER_MIRROR && (H < 2 || W < 2))
-        return set_error(INNFER_ERR_INVALID, "%s: mirror needs at least 2 rows and 2 columns, the image is %dx%d", who, H, W);
-    if ((long)H + 2L * pad > 0x3fffffffL || (long)W + 2L * pad > 0x3fffffffL) return set_error(INNFER_ERR_INVALID, "%s: padded size overflows", who);
-    return INNFER_OK;
 }
 
 }  // namespace

@@ -223,6 +223,9 @@ SIGNATURES = {
     "innfer_extract_tiles_u8_fit_seamless": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_recompose_u8_seamless": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_double] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "innfer_recompose_u8_fit_seamless": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
+    "innfer_dihedral_index": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "innfer_extract_tiles_u8_tta": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_double] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_recompose_u8_tta": (C.c_int, [C.c_void_p] + [C.c_int] * 6 + [C.c_double] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p]),
     "innfer_resample_taps": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "innfer_resample_plan": (C.c_int, [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "innfer_resample_workspace_bytes": (C.c_size_t, [C.c_int] * 7),
@@ -253,7 +256,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 lib = _lib
 
-ABI_VERSION = 118          # the header revision this binding was written against (INNFER_ABI_VERSION)
+ABI_VERSION = 119          # the header revision this binding was written against (INNFER_ABI_VERSION)
 if _lib.innfer_version() != ABI_VERSION and not _ABI_ANY:
     raise ImportError(f"{LIB_PATH} speaks ABI {_lib.innfer_version()}, this binding {ABI_VERSION}: rebuild with `make`")
 
@@ -306,6 +309,14 @@ def border_index(i, n, mode):
     if r < BORDER_OUTSIDE:
         raise ValueError(last_error())
     return r
+
+
+def dihedral_index(k, H, W, y, x):
+    """innfer_dihedral_index (host only): (sy, sx), the pixel of an H x W image that pixel (y, x) of its orientation k shows (t_k: transpose if k & 4,
+    then flip the columns if k & 1, then flip the rows if k & 2).  ValueError for k outside 0 .. 7 or a pixel outside the oriented image."""
+    sy, sx = C.c_int(), C.c_int()
+    check(_lib.innfer_dihedral_index(int(k), int(H), int(W), int(y), int(x), C.byref(sy), C.byref(sx)))
+    return sy.value, sx.value
 
 
 RESAMPLE_FILTERS = {"box": 0, "bilinear": 1, "bicubic": 2, "lanczos": 3}     # INNFER_RESAMPLE_*: the filters of the resampler (-outfilter)

@@ -221,7 +221,18 @@ class Model:
         with torch.no_grad():
             return self._predict(data)
 
-    def run_u8(self, img, normalize=False, fp16=True, out=None, fit_channels=False, seamless=None, outscale=None, outfilter='lanczos'):
+    def forward_tta(self, data):
+        """The self-ensemble (`-tta`, "x8"): the mean of the eight dihedral orientations' results, turned back -- the definition run_u8(tta=True) is held
+        to.  t_k = utils.dihedral(., k) on the last two axes; self(...) is __call__ (chop or whole image, PPON's pick); the sum is float32 in the order
+        k = 0 .. 7 and the mean is rounded to data's dtype."""
+        from .utils.utils import dihedral, dihedral_inv
+        acc = None
+        for k in range(8):
+            y = dihedral_inv(self(dihedral(data, k)), k).float()
+            acc = y if acc is None else acc + y
+        return (acc * 0.125).to(data.dtype)
+
+    def run_u8(self, img, normalize=False, fp16=True, out=None, fit_channels=False, seamless=None, outscale=None, outfilter='lanczos', tta=False):
         """Image in, image out: tensor2np(self(np2tensor(img, normalize)[.half()]), denormalize=normalize) (run.py:421-431) with the two
         conversions fused into the neighbouring kernels -- the tile gather / the blend on the chop path (_chop_u8: innfer_extract_tiles_u8_seamless,
         innfer_recompose_u8_seamless and their _fit forms, at pad = 0 / crop = 0 without a seamless mode), the first / last conv otherwise (EngineModule.forward_u8).  Bit-identical to the separate passes.
@@ -233,10 +244,15 @@ class Model:
         image through the border map and the blend stores the crop window only: neither the padded image nor the padded result exists.  Otherwise the image is padded on the GPU, run and cropped.
         outscale: the final size relative to the INPUT, int(H outscale) x int(W outscale) (Real-ESRGAN's --outscale) -- the device result is resampled
         (utils.resample, filter `outfilter`: lanczos, bicubic, bilinear, box) before it is downloaded: bit for bit utils.resample_np(run_u8(img), ...).
-        Under seamless='tile' the taps wrap around, so the texture still tiles; alpha is filtered straight, not premultiplied.  `out` then has the final shape."""
+        Under seamless='tile' the taps wrap around, so the texture still tiles; alpha is filtered straight, not premultiplied.  `out` then has the final shape.
+        tta: the self-ensemble -- bit for bit tensor2np(self.forward_tta(np2tensor(img, normalize)[.half()]), denormalize=normalize); with seamless the
+        same of the padded image without the padding, with fit_channels utils.fit_channels_forward(self.forward_tta, img, ...), with outscale resampled
+        as above.  On the chop path one gather fills the tiles of all eight orientations (innfer_extract_tiles_u8_tta), they run as one tile stream and
+        one blend averages the eight results before it quantises (innfer_recompose_u8_tta); without chop, or where that tile buffer does not fit
+        (_tta_fits), forward_tta runs on the device tensor between the existing conversions -- the same bits."""
         import numpy as np
         if outscale is not None:
-            return self._run_u8_outscale(img, outscale, outfilter, normalize, fp16, out, fit_channels, seamless)
+            return self._run_u8_outscale(img, outscale, outfilter, normalize, fp16, out, fit_channels, seamless, tta)
         from . import lib as L
         from .architectures.engine_module import EngineModule
         from .utils import utils as U
@@ -245,15 +261,15 @@ class Model:
         if seamless is not None:
             mode = U.seamless_mode(seamless, *img.shape[:2])
             if not self.chop:
-                return self._run_u8_padded(img, seamless, normalize, fp16, out, fit_channels)
+                return self._run_u8_padded(img, seamless, normalize, fp16, out, fit_channels, tta)
         if fit_channels:
             dtype = img.dtype if host else (np.uint8 if img.dtype == torch.uint8 else np.float32)
             plan = U.fit_channels_plan(tuple(img.shape), dtype, getattr(self.model, 'in_nc', self.in_nc), getattr(self.model, 'out_nc', self.out_nc))
             if plan == 0:                                       # a 2-D image for a 1-channel network: run as H x W x 1, return H x W
-                r = self.run_u8(img[:, :, None], normalize=normalize, fp16=fp16, out=None if out is None else out[:, :, None], seamless=seamless)
+                r = self.run_u8(img[:, :, None], normalize=normalize, fp16=fp16, out=None if out is None else out[:, :, None], seamless=seamless, tta=tta)
                 return r[:, :, 0]
             if plan is not None:
-                return self._run_u8_fit(img, plan, normalize, fp16, out, mode)
+                return self._run_u8_fit(img, plan, normalize, fp16, out, mode, tta)
         d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img.contiguous()
         if d.dtype != torch.uint8 or d.dim() != 3:
             raise TypeError('run_u8: expected a uint8 HWC image')
@@ -265,19 +281,19 @@ class Model:
         fused_net = isinstance(self.model, EngineModule) and self.arch != 'ppon'
         with torch.no_grad(), torch.cuda.device(d.device):
             if self.chop:
-                out = self._chop_u8(d, normalize, fp16, out, mode=mode)
-            elif fused_net:
+                out = self._chop_u8(d, normalize, fp16, out, mode=mode, tta=tta)
+            elif fused_net and not tta:
                 out = self.model.forward_u8(d, normalize=normalize, fp16=fp16, out=out)
             else:
                 x = torch.empty((1, Cc, H, W), dtype=dt, device=d.device)
                 L.check(L.lib.innfer_u8hwc_to_nchw(d.data_ptr(), H, W, Cc, int(bool(normalize)), x.data_ptr(), code, stream))
-                y = self._predict(x).contiguous()
+                y = (self.forward_tta(x) if tta else self._predict(x)).contiguous()
                 if out is None:
                     out = torch.empty((y.shape[2], y.shape[3], y.shape[1]), dtype=torch.uint8, device=d.device)
                 L.check(L.lib.innfer_nchw_to_u8hwc(y.data_ptr(), U._dt(y), y.shape[2], y.shape[3], y.shape[1], int(bool(normalize)), out.data_ptr(), stream))
         return out.cpu().numpy() if host else out
 
-    def _run_u8_outscale(self, img, outscale, outfilter, normalize, fp16, out, fit_channels, seamless):
+    def _run_u8_outscale(self, img, outscale, outfilter, normalize, fp16, out, fit_channels, seamless, tta=False):
         """run_u8(outscale=): the plain call on the device, then utils.resample to int(H outscale) x int(W outscale) before the download.  A final size
         equal to the network's own result is the plain result: nothing is resampled."""
         import numpy as np
@@ -287,7 +303,7 @@ class Model:
         oh, ow = U.resample_size(img.shape[0], img.shape[1], outscale)
         L.resample_filter(outfilter)
         d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img
-        r = self.run_u8(d, normalize=normalize, fp16=fp16, fit_channels=fit_channels, seamless=seamless)
+        r = self.run_u8(d, normalize=normalize, fp16=fp16, fit_channels=fit_channels, seamless=seamless, tta=tta)
         shape = (oh, ow) + tuple(r.shape[2:])
         if out is not None and (tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous()):
             raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {shape}')
@@ -295,10 +311,47 @@ class Model:
             r = U.resample(r, size=(oh, ow), filter=outfilter, wrap=seamless == 'tile', out=out)
         return r.cpu().numpy() if host else r
 
-    def _chop_u8(self, d, normalize, fp16, out, fit_C=None, mode=None):
+    def _tta_fits(self, nbytes, device):
+        """Whether the tile buffers of the eight orientations (nbytes: low-resolution tiles and their results) may be allocated: at most half of the free memory."""
+        return nbytes <= torch.cuda.mem_get_info(device)[0] // 2
+
+    def _tta_tensor_u8(self, d, normalize, fp16, out, fit_C, mode):
+        """run_u8(tta=True) of the uint8 device image d without the fused kernels: forward_tta on the device tensor between the existing conversions
+        (pad, np2tensor / fit_split, tensor2np / fit_merge, crop).  fit_C, mode as for _chop_u8."""
+        from . import lib as L
+        from .utils import utils as U
+        s = int(self.scale or 1)
+        dt = torch.float16 if fp16 else torch.float32
+        stream = torch.cuda.current_stream(d.device).cuda_stream
+        src = d if mode is None else U.seamless_pad(d, next(name for name, code in L.BORDER_MODES.items() if code == mode))
+        if fit_C:
+            colour, alpha, const = U.fit_split(src, normalize=normalize, dtype=dt)
+            y = self.forward_tta(colour)
+            ya = self.forward_tta(alpha) if alpha is not None else None
+            r = U.fit_merge(y, ya, const, fit_C, denormalize=normalize, bits=8)
+            r = r.view(U.fit_channels_out_shape(tuple(src.shape), s))
+        else:
+            H, W, Cc = src.shape
+            x = torch.empty((1, Cc, H, W), dtype=dt, device=d.device)
+            L.check(L.lib.innfer_u8hwc_to_nchw(src.data_ptr(), H, W, Cc, int(bool(normalize)), x.data_ptr(), L.F16 if fp16 else L.F32, stream))
+            y = self.forward_tta(x).contiguous()
+            r = torch.empty((y.shape[2], y.shape[3], y.shape[1]), dtype=torch.uint8, device=d.device)
+            L.check(L.lib.innfer_nchw_to_u8hwc(y.data_ptr(), U._dt(y), y.shape[2], y.shape[3], y.shape[1], int(bool(normalize)), r.data_ptr(), stream))
+        if mode is not None:
+            r = U.seamless_crop(r, s)
+        if out is None:
+            return r
+        if tuple(out.shape) != tuple(r.shape) or out.dtype != torch.uint8:
+            raise ValueError(f'run_u8: out must be a uint8 tensor of shape {tuple(r.shape)}')
+        out.copy_(r)
+        return out
+
+    def _chop_u8(self, d, normalize, fp16, out, fit_C=None, mode=None, tta=False):
         """The chop path of run_u8 for the uint8 device image d: plan, gather, run the tiles, blend -- one gather and one blend call for all four forms.
         fit_C: the fit_channels plan (1, 2, 4) or None; mode: the border code of run_u8(seamless=) or None, which is the same two kernels at pad = 0 /
-        crop = 0.  out is checked here under a seamless mode (_run_u8_fit has checked its own); the plain form takes it as given, as it always has."""
+        crop = 0.  out is checked here under a seamless mode (_run_u8_fit has checked its own); the plain form takes it as given, as it always has.
+        tta: the tiles of all eight orientations in one buffer (8 n, with alpha 16 n), one tile stream, one blend (innfer_extract_tiles_u8_tta,
+        innfer_recompose_u8_tta); where the buffers do not fit (_tta_fits, or the allocator says so) _tta_tensor_u8 returns the same bits."""
         from . import lib as L
         from .parallel import run_tile_batches
         from .utils import utils as U
@@ -314,6 +367,35 @@ class Model:
         ps = min(H + 2 * pad, W + 2 * pad, 200)
         _, ys, xs = L.chop_plan(H + 2 * pad, W + 2 * pad, ps, 0.5)
         n = len(ys) * len(xs)
+        if tta:
+            count, Ct = (16 if alpha else 8) * n, 3 if fit_C else d.shape[2]
+            buf = None
+            if self._tta_fits(count * Ct * ps * ps * (1 + s * s) * (2 if fp16 else 4), d.device):
+                try:
+                    tiles = torch.empty((count, Ct, ps, ps), dtype=dt, device=d.device)
+                    buf = self._tile_buffer(tiles)
+                except torch.OutOfMemoryError:
+                    tiles = buf = None
+            else:
+                tiles = None
+            if tiles is None:
+                return self._tta_tensor_u8(d, normalize, fp16, out, fit_C, mode)
+            L.check(L.lib.innfer_extract_tiles_u8_tta(d.data_ptr(), fit_C or d.shape[2], H, W, int(bool(normalize)), ps, 0.5, int(bool(fit_C)), int(alpha), pad, border,
+                                                      tiles.data_ptr(), code, stream))
+            hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=buf)
+            del tiles
+            if fit_C and hr.shape[1] != 3:
+                raise ValueError(f'run_u8: fit_channels needs a 3-channel result, the network returned {hr.shape[1]}')
+            hr = hr.contiguous()
+            Co, P = hr.shape[1], hr.shape[2]
+            shape = U.fit_channels_out_shape(tuple(d.shape), s) if fit_C else (H * s, W * s, Co)
+            if out is None:
+                out = torch.empty(shape, dtype=torch.uint8, device=d.device)
+            elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
+                raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {shape}')
+            L.check(L.lib.innfer_recompose_u8_tta(hr.data_ptr(), U._dt(hr), n, fit_C or Co, P, H + 2 * pad, W + 2 * pad, 0.5, s, U._dt(hr), int(bool(normalize)),
+                                                  int(bool(fit_C)), int(alpha), -1 if const is None else const, pad, out.data_ptr(), stream))
+            return out
         tiles = torch.empty(((2 if alpha else 1) * n, 3 if fit_C else d.shape[2], ps, ps), dtype=dt, device=d.device)
         gather = (d.data_ptr(), fit_C or d.shape[2], H, W, int(bool(normalize)), ps, 0.5, 0, n) + ((int(alpha),) if fit_C else ())
         L.check((L.lib.innfer_extract_tiles_u8_fit_seamless if fit_C else L.lib.innfer_extract_tiles_u8_seamless)(*gather, pad, border, tiles.data_ptr(), code, stream))
@@ -332,7 +414,7 @@ class Model:
         L.check((L.lib.innfer_recompose_u8_fit_seamless if fit_C else L.lib.innfer_recompose_u8_seamless)(*blend, pad, out.data_ptr(), stream))
         return out
 
-    def _run_u8_padded(self, img, seamless, normalize, fp16, out, fit_channels):
+    def _run_u8_padded(self, img, seamless, normalize, fp16, out, fit_channels, tta=False):
         """run_u8(seamless=) where the chop kernels do not apply (whole-image forwards): pad on the GPU (innfer_pad_inthwc), run as without the switch,
         crop on the GPU."""
         import numpy as np
@@ -341,7 +423,7 @@ class Model:
         d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img
         if d.dtype != torch.uint8:
             raise TypeError('run_u8: expected a uint8 image')
-        r = self.run_u8(U.seamless_pad(d, seamless), normalize=normalize, fp16=fp16, fit_channels=fit_channels)
+        r = self.run_u8(U.seamless_pad(d, seamless), normalize=normalize, fp16=fp16, fit_channels=fit_channels, tta=tta)
         r = U.seamless_crop(r, int(self.scale or 1))
         if out is not None:
             if tuple(out.shape) != tuple(r.shape) or out.dtype != torch.uint8:
@@ -350,7 +432,7 @@ class Model:
             r = out
         return r.cpu().numpy() if host else r
 
-    def _run_u8_fit(self, img, C, normalize, fp16, out, mode=None):
+    def _run_u8_fit(self, img, C, normalize, fp16, out, mode=None, tta=False):
         """run_u8(fit_channels=True) of an HW / HWC (C 1, 2, 4) uint8 image with a 3 -> 3 network.  Chop: the colour tiles and the alpha tiles
         (none when the alpha plane is constant) are gathered into one buffer, run as one tile stream and blended in one pass
         (_chop_u8: the FIT forms of the gather and the blend).  Otherwise the two planes are split, run as separate forwards (never one batch:
@@ -368,11 +450,12 @@ class Model:
             raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {shape}')
         with torch.no_grad(), torch.cuda.device(d.device):
             if self.chop:
-                out = self._chop_u8(d, normalize, fp16, out, fit_C=C, mode=mode)
+                out = self._chop_u8(d, normalize, fp16, out, fit_C=C, mode=mode, tta=tta)
             else:
+                fwd = self.forward_tta if tta else self._predict
                 colour, alpha, const = U.fit_split(d, normalize=normalize, dtype=dt)
-                y = self._predict(colour)
-                ya = self._predict(alpha) if alpha is not None else None
+                y = fwd(colour)
+                ya = fwd(alpha) if alpha is not None else None
                 r = U.fit_merge(y, ya, const, C, denormalize=normalize, bits=8)
                 if out is None:
                     out = r.view(shape)
@@ -463,6 +546,9 @@ def build_parser():
                         help='Final size relative to the input, e.g. 2 or 2.5 with a 4x model: the result is resampled on the GPU before it is downloaded.')
     parser.add_argument('-outfilter', required=False, choices=OUTFILTER_CHOICES, default=argparse.SUPPRESS,
                         help='Filter of -outscale (default lanczos); antialiased when it reduces.')
+    parser.add_argument('-tta', required=False, action='store_true', default=argparse.SUPPRESS,
+                        help='Self-ensemble ("x8"): run the image in its eight flipped / rotated orientations and average the results before quantisation; '
+                             'eight times the network cost.')
     return parser
 
 
@@ -496,6 +582,7 @@ def main(argv=None):
     if seamless and resize:
         raise ValueError(f"-seamless {seamless} with '{args.arch}': the preset enlarges every image to a multiple of {resize} px first, which no tileable "
                          "texture survives; resize the texture yourself and run it without the preset")
+    tta = getattr(args, 'tta', False)
     outscale, outfilter = getattr(args, 'outscale', None), getattr(args, 'outfilter', 'lanczos')
     if outscale is not None:
         U.resample_size(1, 1, outscale)                     # ValueError unless 0 < F < inf
@@ -526,7 +613,7 @@ def main(argv=None):
         def fit_chain(t_in):                # the tensor path of one plane: the chain [with the guided filter, the plane's own input as the guide]
             t = t_in
             for mod in models:
-                t = mod(t)
+                t = mod.forward_tta(t) if tta else mod(t)
                 if use_guided_filter:
                     t = U.guided_filter(t_in, t, r=1, eps=5e-3)
             return t
@@ -572,6 +659,8 @@ def main(argv=None):
                 img = img[:, :, None]
             single = len(models) == 1 and not use_guided_filter and img.dtype == np.uint8
             sm = {'seamless': seamless} if seamless else {}                             # run_u8 pads and crops inside its kernels
+            if tta:
+                sm['tta'] = True
             final = U.resample_size(img.shape[0], img.shape[1], outscale) if outscale is not None else None      # relative to the image fed to the chain
             if final and not args.cf:                                                   # run_u8 resamples before the download
                 sm.update(outscale=outscale, outfilter=outfilter)
@@ -588,7 +677,7 @@ def main(argv=None):
                 t_img = U.np2tensor(img, normalize=normalize, device=device, dtype=torch.float16 if fp16 else torch.float32)
                 t_out = t_img
                 for mod in models:
-                    t_out = mod(t_out)
+                    t_out = mod.forward_tta(t_out) if tta else mod(t_out)
                     if use_guided_filter:
                         t_out = U.guided_filter(t_img, t_out, r=1, eps=5e-3)
                 img_out = U.tensor2np(t_out.detach(), denormalize=normalize)

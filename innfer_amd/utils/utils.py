@@ -317,6 +317,65 @@ def seamless_crop(img_out, scale, pad=SEAMLESS_PAD):
     return np.ascontiguousarray(r) if isinstance(img_out, np.ndarray) else r.contiguous()
 
 
+# ---------------------------------------------------------------- self-ensemble (-tta): the eight dihedral orientations, averaged before quantisation
+# t_k, k = 0 .. 7: transpose (H, W) if k & 4, then flip the columns if k & 1, then flip the rows if k & 2; t_k^-1 undoes the steps in reverse order.
+# Kernels: csrc/tiles_tta.hip (include/innfer_amd.h, ABI 119); the tensor form is run.Model.forward_tta.  Not in the reference.
+
+def _image_axes(img):
+    """(row axis, column axis) of an HW / HWC numpy image or of a torch tensor, whose image axes are its last two (NCHW, CHW, HW)."""
+    if isinstance(img, np.ndarray):
+        if img.ndim not in (2, 3):
+            raise TypeError('dihedral: expected an HW / HWC numpy image')
+        return 0, 1
+    if not isinstance(img, torch.Tensor) or img.dim() < 2:
+        raise TypeError('dihedral: expected a numpy image or a tensor with at least two axes')
+    return img.dim() - 2, img.dim() - 1
+
+
+def _check_k(k):
+    if not 0 <= int(k) <= 7:
+        raise ValueError(f'dihedral: orientation k must be 0 .. 7, got {k}')
+    return int(k)
+
+
+def dihedral(img, k):
+    """t_k of an HW / HWC numpy image or of a tensor (its last two axes): a contiguous copy."""
+    k = _check_k(k)
+    r, c = _image_axes(img)
+    host = isinstance(img, np.ndarray)
+    if k & 4:
+        img = np.swapaxes(img, r, c) if host else img.transpose(r, c)
+    if k & 1:
+        img = np.flip(img, c) if host else img.flip(c)
+    if k & 2:
+        img = np.flip(img, r) if host else img.flip(r)
+    return np.ascontiguousarray(img) if host else img.contiguous()
+
+
+def dihedral_inv(img, k):
+    """t_k^-1: dihedral_inv(dihedral(a, k), k) == a."""
+    k = _check_k(k)
+    r, c = _image_axes(img)
+    host = isinstance(img, np.ndarray)
+    if k & 2:
+        img = np.flip(img, r) if host else img.flip(r)
+    if k & 1:
+        img = np.flip(img, c) if host else img.flip(c)
+    if k & 4:
+        img = np.swapaxes(img, r, c) if host else img.transpose(r, c)
+    return np.ascontiguousarray(img) if host else img.contiguous()
+
+
+def tta_np(fn, img):
+    """The self-ensemble of a host function over a numpy image, the definition in numpy: the float32 sum of t_k^-1(fn(t_k(img))) in the order
+    k = 0 .. 7, times 0.125, in fn's result dtype.  For tests on the CPU."""
+    acc = None
+    for k in range(8):
+        y = dihedral_inv(np.asarray(fn(dihedral(img, k))), k)
+        acc = y.astype(np.float32) if acc is None else acc + y.astype(np.float32)
+    return (acc * np.float32(0.125)).astype(y.dtype)
+
+
 # ---------------------------------------------------------------- resampling to any final size (-outscale)
 # An antialiased separable resampler in the Pillow / ATen antialias=True convention (include/innfer_amd.h, ABI 118; csrc/resample.hip).  Channels are
 # filtered independently: alpha is straight, NOT premultiplied, so colour under a transparent pixel does bleed into its neighbours' colour.  Not in the reference.
