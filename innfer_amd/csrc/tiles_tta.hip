@@ -3,11 +3,13 @@
 //   - k_extract_u8_tta / k_extract_u8_tta_t fill tiles [8 n (x 2 with alpha), C | 3, ps, ps]: slots [k n, (k + 1) n) hold the tiles of t_k(padded image) on
 //     that orientation's OWN lattice (for k >= 4 that of a (W + 2 pad) x (H + 2 pad) image), every element read from the uint8 image through t_k^-1 and the
 //     border index map.  Because the padding is `pad` on every side, t_k(pad(x)) == pad(t_k(x)).
-//   - k_recompose_u8_tta computes, per output pixel, the blend of each orientation at the pixel's place in that orientation's frame (the loop of
-//     k_recompose_u8, rounded to TO), sums the eight in fp32 in the order k = 0 .. 7, multiplies by 0.125, rounds to TO and quantises.
-// No rotated image, no per-orientation result and no accumulator image exists.  The element arithmetic is that of tiles_u8.hip, every rounding explicit.
+//   - k_recompose_u8_tta computes, per output pixel, the blend of each orientation at the pixel's place in that orientation's frame (blend_at, the loop
+//     of k_recompose_u8, rounded to TO), sums the eight in fp32 in the order k = 0 .. 7, multiplies by 0.125, rounds to TO and quantises.
+// No rotated image, no per-orientation result and no accumulator image exists.  The element arithmetic IS that of tiles_u8.hip: load_run, put_run,
+// blend_at and store_px of tiles_u8_common.h are the bodies of both files' kernels (k_extract_u8_tta_t keeps its own load, through LDS), and the host's
+// form dispatch and refusals are that header's too.  tiles.hip deliberately shares none of it: its separate passes are what the tests hold all this to.
 #include "common.h"
-#include "tiles_common.h"
+#include "tiles_u8_common.h"
 
 #pragma clang fp contract(off)
 
@@ -22,40 +24,9 @@ __host__ __device__ __forceinline__ void dihedral_src(int k, int H, int W, int y
     *sx = k & 4 ? a : b;
 }
 
-// The tile stores of k_extract_u8 for V pixels p (C bytes each, image order) at offset o of the colour slot `slot` and, FIT with alpha, the alpha slot `aslot`.
-template <typename TO, int C, int V, bool FIT>
-__device__ __forceinline__ void put_run(const Run<uint8_t, C * V, 1>& p, TO* tiles, long slot, long aslot, long pp, long o, int normalize, int alpha) {
-    typedef TO vo __attribute__((ext_vector_type(V)));
-    if constexpr (FIT) {
-        vo col[3], a;
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c)                             // RGB from BGR(A); (g, g, g) from gray
-                col[c][j] = (TO)to_unit((float)p.v[j * C + (C == 4 ? 2 - c : 0)], 255.0f, normalize);
-            if (C > 1) a[j] = (TO)to_unit((float)p.v[j * C + C - 1], 255.0f, normalize);
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *(vo*)(tiles + (slot * 3 + c) * pp + o) = col[c];
-        if (C > 1 && alpha) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) *(vo*)(tiles + (aslot * 3 + c) * pp + o) = a;
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int sc = C == 3 ? 2 - c : (C == 4 && c < 3 ? 2 - c : c);      // np2tensor's flip: BGR -> RGB, BGRA -> RGBA
-            vo v;
-#pragma unroll
-            for (int j = 0; j < V; ++j) v[j] = (TO)to_unit((float)p.v[j * C + sc], 255.0f, normalize);
-            *(vo*)(tiles + (slot * C + c) * pp + o) = v;
-        }
-    }
-}
-
 // The gather of the orientations k = 0 .. 3 (no transpose): k_extract_u8 with the row map and the column map behind t_k^-1.  grid.y runs over the slots
-// [slot_begin, ..) of [0, 4 n); slot = k n + tile.  A thread's V pixels lie along an image row, descending under a column flip: the one load is then made at
-// the run's low end and reversed; where the run crosses a fold of the map or its bytes are misaligned it is one load per pixel through the map.
+// [slot_begin, ..) of [0, 4 n); slot = k n + tile.  A thread's V pixels lie along an image row, descending under a column flip: load_run is then called at
+// the run's low end with `rev`.
 template <typename TO, int C, int V, bool FIT>
 __global__ void __launch_bounds__(256) k_extract_u8_tta(const uint8_t* img, TO* tiles, int H, int W, int pad, int mode, int ps, int R, int step_int, int nw,
                                                          int n, int slot_begin, int normalize, int alpha) {
@@ -72,37 +43,9 @@ __global__ void __launch_bounds__(256) k_extract_u8_tta(const uint8_t* img, TO* 
     const bool rev = k & 1;
     const int Y = k & 2 ? HP - 1 - (oy + y) : oy + y;         // row of the padded image
     const int X0 = rev ? WP - 1 - (ox + x) - (V - 1) : ox + x; // lowest column of the run in the padded image
-    constexpr int AP = C == 3 ? 1 : C, AV = C == 3 ? 4 : 4 * C;
-    Run<uint8_t, C * V, 1> p;
-#pragma unroll
-    for (int e = 0; e < C * V; ++e) p.v[e] = 0;
+    Run<uint8_t, C * V, 1> p = {};
     const int sy = border_index(Y - pad, H, mode);
-    if (sy >= 0) {
-        const int x0 = X0 - pad;
-        const int m0 = border_index(x0, W, mode);
-        const uint8_t* row = img + (long)sy * W * C;
-        bool run = false;
-        if (V == 4) run = m0 >= 0 && border_index(x0 + 3, W, mode) == m0 + 3 && ((uintptr_t)(row + (long)m0 * C) & (AV - 1)) == 0;
-        if (run) {
-            const Run<uint8_t, C * V, AV> r = *(const Run<uint8_t, C * V, AV>*)(row + (long)m0 * C);
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-#pragma unroll
-                for (int c = 0; c < C; ++c) p.v[j * C + c] = rev ? r.v[(V - 1 - j) * C + c] : r.v[j * C + c];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                const int jj = rev ? V - 1 - j : j;
-                const int m = jj == 0 ? m0 : border_index(x0 + jj, W, mode);
-                if (m >= 0) {
-                    const Run<uint8_t, C, AP> r = *(const Run<uint8_t, C, AP>*)(row + (long)m * C);
-#pragma unroll
-                    for (int c = 0; c < C; ++c) p.v[j * C + c] = r.v[c];
-                }
-            }
-        }
-    }
+    if (sy >= 0) p = load_run<C, V>(img + (long)sy * W * C, X0 - pad, W, mode, rev);
     put_run<TO, C, V, FIT>(p, tiles, slot, (long)8 * n + slot, (long)ps * ps, (long)y * ps + x, normalize, alpha);
 }
 
@@ -153,76 +96,33 @@ __global__ void __launch_bounds__(256) k_extract_u8_tta_t(const uint8_t* img, TO
 
 // The blend.  Tiles [8 n, C, P, P], orientation k in slots [k n, (k + 1) n) on its own lattice (FIT: colour tiles [0, 8 n), alpha tiles [8 n, 16 n), three
 // channels each).  Output pixel (Yo, Xo) is pixel (Yo + cs, Xo + cs) of the FH x FW frame; in orientation k's frame (FW x FH for k >= 4) it lies where t_k
-// moves it, and its blend there is the loop of k_recompose_u8: the same tiles in the same (h, w) order with the same weights, den per orientation, the
-// quotient rounded to TO.  The eight are added as floats in the order k = 0 .. 7 (from 0.f: x + 0 is x), times 0.125f, rounded to TO; then k_recompose_u8's
-// tail.  One thread per output pixel in blocks of 16 x 16 pixels: a block reads 16 consecutive elements of 16 tile rows in the straight and in the
-// transposed orientations alike.  No LDS, no atomics; the pixel's C bytes are one store.
+// moves it, and its blend there is blend_at, as in k_recompose_u8: den per orientation, the quotient rounded to TO.  The eight are added as floats in
+// the order k = 0 .. 7 (from 0.f: x + 0 is x), times 0.125f, rounded to TO; then store_px.  One thread per output pixel in blocks of 16 x 16 pixels: a
+// block reads 16 consecutive elements of 16 tile rows in the straight and in the transposed orientations alike.  No LDS, no atomics.
 template <typename TI, typename TO, int C, bool FIT>
 __global__ void __launch_bounds__(256) k_recompose_u8_tta(const TI* tiles, int n, int P, int FH, int FW, int eff, int nh, int nw, int ov, int cs, int OH, int OW,
                                                            int alpha, int aconst, int denormalize, uint8_t* img) {
     const int Xo = blockIdx.x * 16 + (threadIdx.x & 15), Yo = blockIdx.y * 16 + (threadIdx.x >> 4);
     if (Xo >= OW || Yo >= OH) return;
-    constexpr int NT = FIT ? 3 : C;                            // channels of a tile
-    constexpr int NC = FIT && C > 1 ? 6 : NT;
-    float sum[NC];
+    using F = Form<C, FIT>;
+    float sum[F::NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) sum[c] = 0.f;
-    const long pp = (long)P * P, aoff = (long)8 * n * 3 * pp;
+    for (int c = 0; c < F::NC; ++c) sum[c] = 0.f;
+    const long pp = (long)P * P;
+    TO r[F::NC];
     for (int k = 0; k < 8; ++k) {
         const bool tr = k & 4;
-        const int A = tr ? FW : FH, B = tr ? FH : FW, na = tr ? nw : nh, nb = tr ? nh : nw;      // orientation k: an A x B frame of na x nb tiles
+        const int A = tr ? FW : FH, B = tr ? FH : FW;                     // orientation k: an A x B frame, its lattice nh x nw swapped with it
         int Y = tr ? Xo + cs : Yo + cs, X = tr ? Yo + cs : Xo + cs;
         if (k & 2) Y = A - 1 - Y;
         if (k & 1) X = B - 1 - X;
-        const TI* base = tiles + (long)k * n * NT * pp;
-        float num[NC], den = 0.f;
+        blend_at<TI, TO, F::NT, F::NC>(tiles + (long)k * n * F::NT * pp, (long)8 * n * 3 * pp, alpha, P, A, B, tr ? nw : nh, tr ? nh : nw, eff, ov, Y, X, r);
 #pragma unroll
-        for (int c = 0; c < NC; ++c) num[c] = 0.f;
-        const int h0 = max(0, (Y - P + eff) / eff), w0 = max(0, (X - P + eff) / eff);
-        for (int h = h0; h < na; ++h) {
-            const int oy = min(h * eff, A - P);
-            if (oy > Y) break;
-            if (Y - oy >= P) continue;
-            const float wy = profile(Y - oy, P, ov);
-            for (int w = w0; w < nb; ++w) {
-                const int ox = min(w * eff, B - P);
-                if (ox > X) break;
-                if (X - ox >= P) continue;
-                const float wgt = __fmul_rn(profile(X - ox, P, ov), wy);
-                den = __fadd_rn(den, wgt);
-                const long i = (long)h * nb + w;
-                const TI* tp = base + (i * NT * P + (Y - oy)) * (long)P + (X - ox);
-#pragma unroll
-                for (int c = 0; c < NT; ++c) num[c] = __fadd_rn(num[c], __fmul_rn((float)tp[c * pp], wgt));
-                if constexpr (FIT && C > 1) if (alpha) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) num[3 + c] = __fadd_rn(num[3 + c], __fmul_rn((float)tp[aoff + c * pp], wgt));
-                }
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) sum[c] = __fadd_rn(sum[c], (float)(TO)__fdiv_rn(num[c], den));
+        for (int c = 0; c < F::NC; ++c) sum[c] = __fadd_rn(sum[c], (float)r[c]);
     }
-    TO r[NC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) r[c] = (TO)__fmul_rn(sum[c], 0.125f);
-    Run<uint8_t, C, C == 3 ? 1 : C> o;
-    if constexpr (FIT) {
-        if (C == 4) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o.v[2 - c] = (uint8_t)quantise((float)r[c], denormalize, 255.0f);
-        } else {
-            o.v[0] = (uint8_t)quantise((float)mean3(r[0], r[1], r[2]), denormalize, 255.0f);
-        }
-        if (C > 1) o.v[C - 1] = alpha ? (uint8_t)quantise((float)mean3(r[NC - 3], r[NC - 2], r[NC - 1]), denormalize, 255.0f) : (uint8_t)aconst;
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int sc = (C == 3 || (C == 4 && c < 3)) ? 2 - c : c;           // tensor2np's flip: RGB -> BGR, RGBA -> BGRA
-            o.v[sc] = (uint8_t)quantise((float)r[c], denormalize, 255.0f);
-        }
-    }
-    *(Run<uint8_t, C, C == 3 ? 1 : C>*)(img + ((long)Yo * OW + Xo) * C) = o;
+    for (int c = 0; c < F::NC; ++c) r[c] = (TO)__fmul_rn(sum[c], 0.125f);
+    store_px<TO, C, FIT>(r, alpha, aconst, denormalize, img + ((long)Yo * OW + Xo) * C);
 }
 
 }  // namespace
@@ -242,13 +142,13 @@ extern "C" int innfer_extract_tiles_u8_tta(const uint8_t* d_img, int C, int H, i
                                            int pad, int mode, void* d_tiles, int tile_dtype, void* stream) {
     const char* who = "extract_tiles_u8_tta";
     if (!d_img || !d_tiles) return set_error(INNFER_ERR_INVALID, "%s: null argument", who);
-    if (fit ? (C != 1 && C != 2 && C != 4) : C < 1) return set_error(INNFER_ERR_INVALID, "%s: %d channels (%s)", who, C, fit ? "1, 2 or 4" : "at least 1");
+    if (int rc = check_u8_form(who, fit, C, alpha, -1, false)) return rc;
     if (C > 4) return set_error(INNFER_ERR_UNSUPPORTED, "%s: %d channels (built: 1 .. 4, what innfer_recompose_u8_tta stores)", who, C);
     if (alpha && (C == 1 || !fit)) return set_error(INNFER_ERR_INVALID, "%s: alpha tiles need fit and an image with an alpha plane", who);
     if (int rc = check_border(who, H, W, pad, mode)) return rc;
     int ps, nh, nw;
     if (int rc = innfer_chop_plan(H + 2 * pad, W + 2 * pad, patch, step, &ps, &nh, &nw, nullptr, nullptr)) return rc;
-    if (tile_dtype != INNFER_F16 && tile_dtype != INNFER_F32) return set_error(INNFER_ERR_INVALID, "%s: bad dtype %d", who, tile_dtype);
+    if (!is_float_dtype(tile_dtype)) return set_error(INNFER_ERR_INVALID, "%s: bad dtype %d", who, tile_dtype);
     const int step_int = (int)(ps * step);
     const long n = (long)nh * nw;
     if (16 * n > 0x7fffffffL) return set_error(INNFER_ERR_INVALID, "%s: %ld tiles per orientation overflow", who, n);
@@ -257,18 +157,19 @@ extern "C" int innfer_extract_tiles_u8_tta(const uint8_t* d_img, int C, int H, i
     const bool x4 = ps % 4 == 0;
     const int q = x4 ? ps / 4 : ps, R = ps < (1 << 28) / q ? ps : (1 << 28) / q;      // R * q threads per tile and block layer fit an int
     const int a = alpha ? 1 : 0, nn = (int)n;
-#define EX(TO, CC, V, F) hipLaunchKernelGGL((k_extract_u8_tta<TO, CC, V, F>), g, dim3(256), 0, s, d_img, (TO*)d_tiles, H, W, pad, mode, ps, R, step_int, nw, nn, (int)b, normalize, a)
-#define EXT(TO, CC, F) hipLaunchKernelGGL((k_extract_u8_tta_t<TO, CC, F>), gt, dim3(256), 0, s, d_img, (TO*)d_tiles, H, W, pad, mode, ps, step_int, nh, nn, (int)(4 * n + b), normalize, a)
-#define EX_V(TO, CC, F) do { if (x4) EX(TO, CC, 4, F); else EX(TO, CC, 1, F); EXT(TO, CC, F); } while (0)
-#define EX_C(TO) do { if (fit) { if (C == 1) EX_V(TO, 1, true); else if (C == 2) EX_V(TO, 2, true); else EX_V(TO, 4, true); } \
-                      else { if (C == 1) EX_V(TO, 1, false); else if (C == 2) EX_V(TO, 2, false); else if (C == 3) EX_V(TO, 3, false); else EX_V(TO, 4, false); } } while (0)
+#define EX(V) hipLaunchKernelGGL((k_extract_u8_tta<TO, CC, V, F>), g, dim3(256), 0, s, d_img, (TO*)d_tiles, H, W, pad, mode, ps, R, step_int, nw, nn, (int)b, normalize, a)
+#define EXT() hipLaunchKernelGGL((k_extract_u8_tta_t<TO, CC, F>), gt, dim3(256), 0, s, d_img, (TO*)d_tiles, H, W, pad, mode, ps, step_int, nh, nn, (int)(4 * n + b), normalize, a)
     for (long b = 0; b < 4 * n; b += 65535) {                 // slots are the grid's y: at most 65535 per launch, the straight and the transposed half alike
         const unsigned cnt = (unsigned)(4 * n - b < 65535 ? 4 * n - b : 65535);
         const dim3 g(blocks((long)R * q, 256), cnt, (ps + R - 1) / R), gt((ps + 31) / 32, cnt, (ps + 31) / 32);
-        if (tile_dtype == INNFER_F16) EX_C(f16); else EX_C(float);
+        with_dtype(tile_dtype, [&](auto to) { with_form(fit, C, [&](auto c, auto f) {
+            using TO = decltype(to);
+            constexpr int CC = decltype(c)::value;
+            constexpr bool F = decltype(f)::value;
+            if (x4) EX(4); else EX(1);
+            EXT();
+        }); });
     }
-#undef EX_C
-#undef EX_V
 #undef EXT
 #undef EX
     INNFER_HIP(hipGetLastError());
@@ -280,9 +181,7 @@ extern "C" int innfer_recompose_u8_tta(const void* d_tiles, int dtype, int n, in
     const char* who = "recompose_u8_tta";
     if (!d_tiles || !d_img) return set_error(INNFER_ERR_INVALID, "%s: null argument", who);
     if (C > 4) return set_error(INNFER_ERR_UNSUPPORTED, "%s: %d channels (built: 1 .. 4)", who, C);
-    if (fit ? (C != 1 && C != 2 && C != 4) : C < 1) return set_error(INNFER_ERR_INVALID, "%s: %d channels (%s)", who, C, fit ? "1, 2 or 4" : "1 .. 4");
-    if (fit ? (C == 1 ? alpha != 0 : (!alpha && (alpha_const < 0 || alpha_const > 255))) : alpha != 0)
-        return set_error(INNFER_ERR_INVALID, "%s: a %d-channel image needs %s", who, C, !fit || C == 1 ? "no alpha tiles" : "alpha tiles or a constant alpha in [0, 255]");
+    if (int rc = check_u8_form(who, fit, C, alpha, alpha_const, true)) return rc;
     BlendGeo g;
     if (int rc = blend_geo(who, n, P, height, width, step, scale, crop, false, &g)) return rc;
     if (16L * n > 0x7fffffffL) return set_error(INNFER_ERR_INVALID, "%s: %d tiles per orientation overflow", who, n);
@@ -291,17 +190,11 @@ extern "C" int innfer_recompose_u8_tta(const void* d_tiles, int dtype, int n, in
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((OW + 15) / 16, (OH + 15) / 16), block(256);
     const int a = alpha ? 1 : 0;
-#define RC(TI, TO, CC, F) hipLaunchKernelGGL((k_recompose_u8_tta<TI, TO, CC, F>), grid, block, 0, s, (const TI*)d_tiles, n, P, g.FH, g.FW, g.eff, g.nh, g.nw, g.ov, g.cs, OH, OW, \
-                                             a, alpha_const, denormalize, d_img)
-#define RC_C(TI, TO) do { if (fit) { if (C == 1) RC(TI, TO, 1, true); else if (C == 2) RC(TI, TO, 2, true); else RC(TI, TO, 4, true); } \
-                          else { if (C == 1) RC(TI, TO, 1, false); else if (C == 2) RC(TI, TO, 2, false); else if (C == 3) RC(TI, TO, 3, false); else RC(TI, TO, 4, false); } } while (0)
-    if (dtype == INNFER_F16 && via_dtype == INNFER_F16) RC_C(f16, f16);
-    else if (dtype == INNFER_F16 && via_dtype == INNFER_F32) RC_C(f16, float);
-    else if (dtype == INNFER_F32 && via_dtype == INNFER_F32) RC_C(float, float);
-    else if (dtype == INNFER_F32 && via_dtype == INNFER_F16) RC_C(float, f16);
-    else return set_error(INNFER_ERR_INVALID, "%s: bad dtype", who);
-#undef RC_C
-#undef RC
+    if (!is_float_dtype(dtype) || !is_float_dtype(via_dtype)) return set_error(INNFER_ERR_INVALID, "%s: bad dtype", who);
+    with_dtype(dtype, [&](auto ti) { with_dtype(via_dtype, [&](auto to) { with_form(fit, C, [&](auto c, auto f) {
+        hipLaunchKernelGGL((k_recompose_u8_tta<decltype(ti), decltype(to), decltype(c)::value, decltype(f)::value>), grid, block, 0, s, (const decltype(ti)*)d_tiles, n, P,
+                           g.FH, g.FW, g.eff, g.nh, g.nw, g.ov, g.cs, OH, OW, a, alpha_const, denormalize, d_img);
+    }); }); });
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
 }

@@ -6,8 +6,10 @@
 // Neither the padded image nor the padded result ever exists on the chop path.  One read + one write per element like the kernels of tiles.hip; no LDS, no
 // atomics.  The element arithmetic is the helpers of tiles_common.h in the order of the separate passes (k_u8_to_nchw + k_extract, k_recompose +
 // k_nchw_to_u8 of tiles.hip), so the results are theirs bit for bit.
+// The kernels' bodies -- load_run, put_run, blend_at, store_px -- and the host's form dispatch and refusals are tiles_u8_common.h, shared with the
+// self-ensemble's kernels (tiles_tta.hip) and deliberately NOT with tiles.hip, whose separate passes stay the independent anchors of the tests.
 #include "common.h"
-#include "tiles_common.h"
+#include "tiles_u8_common.h"
 
 #pragma clang fp contract(off)
 
@@ -42,13 +44,11 @@ __global__ void __launch_bounds__(256) k_pad_inthwc_n(const T* img, T* out, int 
 // The gather.  FIT false: tiles [count, C, ps, ps], channels flipped BGR(A) -> RGB(A) (np2tensor + extract_patches_2d).  FIT true: colour tile k at slot
 // k - tile_begin ((g, g, g) from gray, RGB from BGRA), its alpha tile (a, a, a) at slot count + k - tile_begin when `alpha`, [3, ps, ps] each.  The lattice is
 // that of the virtual padded image.  One block row of the grid per tile, V consecutive pixels of one tile row per thread, R tile rows per block layer
-// (grid.z; R = ps unless ps * ps / V would overflow an int).  The row map is computed once per thread; the column map at the run's two ends -- where the run
-// does not cross a fold of the map (source indices m0 .. m0 + 3) and its bytes are aligned it is one load, else one load per pixel through the map.  Outside
-// the image under alpha_pad every byte is 0 and takes the same arithmetic.  V = 4 needs ps % 4 == 0 (the tile stores are then aligned).
+// (grid.z; R = ps unless ps * ps / V would overflow an int).  The row map is computed once per thread; the run along the row is load_run's, the stores
+// put_run's.  Outside the image under alpha_pad every byte is 0 and takes the same arithmetic.  V = 4 needs ps % 4 == 0 (the tile stores are then aligned).
 template <typename TO, int C, int V, bool FIT>
 __global__ void __launch_bounds__(256) k_extract_u8(const uint8_t* img, TO* tiles, int H, int W, int pad, int mode, int ps, int R, int step_int, int nw,
                                                      int tile_begin, int count, int normalize, int alpha) {
-    typedef TO vo __attribute__((ext_vector_type(V)));
     const int q = ps / V;
     const int t = blockIdx.x * 256 + threadIdx.x;             // over R * (ps / V)
     const int yr = t / q, y = blockIdx.z * R + yr, x = (t - yr * q) * V;
@@ -58,59 +58,10 @@ __global__ void __launch_bounds__(256) k_extract_u8(const uint8_t* img, TO* tile
     const int HP = H + 2 * pad, WP = W + 2 * pad;
     int oy = th * step_int; if (oy > HP - ps) oy = HP - ps;
     int ox = tw * step_int; if (ox > WP - ps) ox = WP - ps;
-    constexpr int AP = C == 3 ? 1 : C, AV = C == 3 ? 4 : 4 * C;
-    Run<uint8_t, C * V, 1> p;
-#pragma unroll
-    for (int e = 0; e < C * V; ++e) p.v[e] = 0;
+    Run<uint8_t, C * V, 1> p = {};
     const int sy = border_index(oy + y - pad, H, mode);
-    if (sy >= 0) {
-        const int x0 = ox + x - pad;
-        const int m0 = border_index(x0, W, mode);
-        const uint8_t* row = img + (long)sy * W * C;
-        bool run = false;
-        if (V == 4) run = m0 >= 0 && border_index(x0 + 3, W, mode) == m0 + 3 && ((uintptr_t)(row + (long)m0 * C) & (AV - 1)) == 0;
-        if (run) {
-            const Run<uint8_t, C * V, AV> r = *(const Run<uint8_t, C * V, AV>*)(row + (long)m0 * C);
-#pragma unroll
-            for (int e = 0; e < C * V; ++e) p.v[e] = r.v[e];
-        } else {
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                const int m = j == 0 ? m0 : border_index(x0 + j, W, mode);
-                if (m >= 0) {
-                    const Run<uint8_t, C, AP> r = *(const Run<uint8_t, C, AP>*)(row + (long)m * C);
-#pragma unroll
-                    for (int c = 0; c < C; ++c) p.v[j * C + c] = r.v[c];
-                }
-            }
-        }
-    }
-    const long pp = (long)ps * ps, o = (long)y * ps + x;
-    if constexpr (FIT) {
-        vo col[3], a;
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c)                             // RGB from BGR(A); (g, g, g) from gray
-                col[c][j] = (TO)to_unit((float)p.v[j * C + (C == 4 ? 2 - c : 0)], 255.0f, normalize);
-            if (C > 1) a[j] = (TO)to_unit((float)p.v[j * C + C - 1], 255.0f, normalize);
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) *(vo*)(tiles + ((long)kk * 3 + c) * pp + o) = col[c];
-        if (C > 1 && alpha) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) *(vo*)(tiles + ((long)(count + kk) * 3 + c) * pp + o) = a;
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int sc = C == 3 ? 2 - c : (C == 4 && c < 3 ? 2 - c : c);      // np2tensor's flip: BGR -> RGB, BGRA -> RGBA
-            vo v;
-#pragma unroll
-            for (int j = 0; j < V; ++j) v[j] = (TO)to_unit((float)p.v[j * C + sc], 255.0f, normalize);
-            *(vo*)(tiles + ((long)kk * C + c) * pp + o) = v;
-        }
-    }
+    if (sy >= 0) p = load_run<C, V>(img + (long)sy * W * C, ox + x - pad, W, mode, false);
+    put_run<TO, C, V, FIT>(p, tiles, kk, count + kk, (long)ps * ps, (long)y * ps + x, normalize, alpha);
 }
 
 // any channel count (pad = 0 only): one element per thread, 3 n channels fully flipped
@@ -132,62 +83,17 @@ __global__ void k_extract_u8_n(const uint8_t* img, TO* tiles, int C, int H, int 
 // The blend: k_recompose of tiles.hip with tensor2np as the store.  FIT false: tiles [n, C, P, P], each blended channel rounded to TO (the tensor
 // recompose_tensor would have returned), quantised and flipped RGB(A) -> BGR(A).  FIT true: colour tiles [0, n) and, with `alpha`, alpha tiles [n, 2 n),
 // three channels each; B, G, R (C 4) or mean3 (gray) of the colour result, mean3 of the alpha result or the constant alpha `aconst` (>= 0).  Only the crop
-// window is computed: output pixel (Yo, Xo) is pixel (Yo + cs, Xo + cs) of the full FH x FW blend, cs = scale * crop; its sums run over the same tiles in
-// the same (h, w) order with the same weights, each tile's weight computed once for all numerators.  One thread per output pixel, its C bytes in one store.
+// window is computed: output pixel (Yo, Xo) is pixel (Yo + cs, Xo + cs) of the full FH x FW blend, cs = scale * crop: blend_at there, then store_px.  One
+// thread per output pixel, its C bytes in one store.
 template <typename TI, typename TO, int C, bool FIT>
 __global__ void __launch_bounds__(256) k_recompose_u8(const TI* tiles, int n, int P, int FH, int FW, int eff, int nh, int nw, int ov, int cs, int OW,
                                                                 int alpha, int aconst, int denormalize, uint8_t* img) {
     const int Xo = blockIdx.x * 256 + threadIdx.x, Yo = blockIdx.y;
     if (Xo >= OW) return;
-    const int X = Xo + cs, Y = Yo + cs;
-    constexpr int NT = FIT ? 3 : C;                            // channels of a tile
-    constexpr int NC = FIT && C > 1 ? 6 : NT;
-    float num[NC], den = 0.f;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) num[c] = 0.f;
-    const long pp = (long)P * P, aoff = (long)n * 3 * pp;
-    const int h0 = max(0, (Y - P + eff) / eff), w0 = max(0, (X - P + eff) / eff);
-    for (int h = h0; h < nh; ++h) {
-        const int oy = min(h * eff, FH - P);
-        if (oy > Y) break;
-        if (Y - oy >= P) continue;
-        const float wy = profile(Y - oy, P, ov);
-        for (int w = w0; w < nw; ++w) {
-            const int ox = min(w * eff, FW - P);
-            if (ox > X) break;
-            if (X - ox >= P) continue;
-            const float wgt = __fmul_rn(profile(X - ox, P, ov), wy);
-            den = __fadd_rn(den, wgt);
-            const long k = (long)h * nw + w;
-            const TI* tp = tiles + (k * NT * P + (Y - oy)) * (long)P + (X - ox);
-#pragma unroll
-            for (int c = 0; c < NT; ++c) num[c] = __fadd_rn(num[c], __fmul_rn((float)tp[c * pp], wgt));
-            if constexpr (FIT && C > 1) if (alpha) {
-#pragma unroll
-                for (int c = 0; c < 3; ++c) num[3 + c] = __fadd_rn(num[3 + c], __fmul_rn((float)tp[aoff + c * pp], wgt));
-            }
-        }
-    }
-    TO r[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) r[c] = (TO)__fdiv_rn(num[c], den);
-    Run<uint8_t, C, C == 3 ? 1 : C> o;
-    if constexpr (FIT) {
-        if (C == 4) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o.v[2 - c] = (uint8_t)quantise((float)r[c], denormalize, 255.0f);
-        } else {
-            o.v[0] = (uint8_t)quantise((float)mean3(r[0], r[1], r[2]), denormalize, 255.0f);
-        }
-        if (C > 1) o.v[C - 1] = alpha ? (uint8_t)quantise((float)mean3(r[NC - 3], r[NC - 2], r[NC - 1]), denormalize, 255.0f) : (uint8_t)aconst;
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-            const int sc = (C == 3 || (C == 4 && c < 3)) ? 2 - c : c;           // tensor2np's flip: RGB -> BGR, RGBA -> BGRA
-            o.v[sc] = (uint8_t)quantise((float)r[c], denormalize, 255.0f);
-        }
-    }
-    *(Run<uint8_t, C, C == 3 ? 1 : C>*)(img + ((long)Yo * OW + Xo) * C) = o;
+    using F = Form<C, FIT>;
+    TO r[F::NC];
+    blend_at<TI, TO, F::NT, F::NC>(tiles, (long)n * 3 * P * P, alpha, P, FH, FW, nh, nw, eff, ov, Yo + cs, Xo + cs, r);
+    store_px<TO, C, FIT>(r, alpha, aconst, denormalize, img + ((long)Yo * OW + Xo) * C);
 }
 
 }  // namespace
@@ -228,7 +134,7 @@ extern "C" int innfer_pad_inthwc(const void* d_img, int bits, int H, int W, int 
 static int extract_u8(const char* who, bool fit, const uint8_t* d_img, int C, int H, int W, int normalize, int patch, double step, int tile_begin,
                       int tile_count, int alpha, int pad, int mode, void* d_tiles, int tile_dtype, hipStream_t s) {
     if (!d_img || !d_tiles) return set_error(INNFER_ERR_INVALID, "%s: null argument", who);
-    if (fit ? (C != 1 && C != 2 && C != 4) : C < 1) return set_error(INNFER_ERR_INVALID, "%s: %d channels (%s)", who, C, fit ? "1, 2 or 4" : "at least 1");
+    if (int rc = check_u8_form(who, fit, C, alpha, -1, false)) return rc;
     if (alpha && C == 1) return set_error(INNFER_ERR_INVALID, "%s: a 1-channel image has no alpha", who);
     if (C > 4 && pad > 0) return set_error(INNFER_ERR_UNSUPPORTED, "%s: %d channels with a border (built: 1 .. 4, what innfer_recompose_u8 stores)", who, C);
     if (int rc = check_border(who, H, W, pad, mode)) return rc;
@@ -238,7 +144,7 @@ static int extract_u8(const char* who, bool fit, const uint8_t* d_img, int C, in
     if (tile_begin < 0 || tile_count < 0 || tile_begin + tile_count > nh * nw)
         return set_error(INNFER_ERR_INVALID, "%s: tile range [%d,+%d) outside %d tiles", who, tile_begin, tile_count, nh * nw);
     if (tile_count == 0) return INNFER_OK;
-    if (tile_dtype != INNFER_F16 && tile_dtype != INNFER_F32) return set_error(INNFER_ERR_INVALID, "%s: bad dtype %d", who, tile_dtype);
+    if (!is_float_dtype(tile_dtype)) return set_error(INNFER_ERR_INVALID, "%s: bad dtype %d", who, tile_dtype);
     const long pp = (long)ps * ps;
     if (C > 4) {
         const long total = (long)tile_count * C * pp;
@@ -252,17 +158,17 @@ static int extract_u8(const char* who, bool fit, const uint8_t* d_img, int C, in
     const bool x4 = ps % 4 == 0;
     const int q = x4 ? ps / 4 : ps, R = ps < (1 << 28) / q ? ps : (1 << 28) / q;      // R * q threads per tile and block layer fit an int
     const int a = alpha ? 1 : 0;
-#define EX(TO, CC, V, F) hipLaunchKernelGGL((k_extract_u8<TO, CC, V, F>), g, dim3(256), 0, s, d_img, (TO*)d_tiles + b * (F ? 3 : CC) * pp, H, W, pad, mode, ps, R, step_int, nw, \
-                                            tile_begin + (int)b, tile_count, normalize, a)
-#define EX_V(TO, CC, F) do { if (x4) EX(TO, CC, 4, F); else EX(TO, CC, 1, F); } while (0)
-#define EX_C(TO) do { if (fit) { if (C == 1) EX_V(TO, 1, true); else if (C == 2) EX_V(TO, 2, true); else EX_V(TO, 4, true); } \
-                      else { if (C == 1) EX_V(TO, 1, false); else if (C == 2) EX_V(TO, 2, false); else if (C == 3) EX_V(TO, 3, false); else EX_V(TO, 4, false); } } while (0)
+#define EX(V) hipLaunchKernelGGL((k_extract_u8<TO, CC, V, F>), g, dim3(256), 0, s, d_img, dst, H, W, pad, mode, ps, R, step_int, nw, tile_begin + (int)b, tile_count, normalize, a)
     for (long b = 0; b < tile_count; b += 65535) {            // tiles are the grid's y: at most 65535 per launch; `count` stays the alpha slot base
         const dim3 g(blocks((long)R * q, 256), (unsigned)(tile_count - b < 65535 ? tile_count - b : 65535), (ps + R - 1) / R);
-        if (tile_dtype == INNFER_F16) EX_C(f16); else EX_C(float);
+        with_dtype(tile_dtype, [&](auto to) { with_form(fit, C, [&](auto c, auto f) {
+            using TO = decltype(to);
+            constexpr int CC = decltype(c)::value;
+            constexpr bool F = decltype(f)::value;
+            TO* dst = (TO*)d_tiles + b * Form<CC, F>::NT * pp;
+            if (x4) EX(4); else EX(1);
+        }); });
     }
-#undef EX_C
-#undef EX_V
 #undef EX
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
@@ -296,26 +202,18 @@ extern "C" int innfer_extract_tiles_u8_fit_seamless(const uint8_t* d_img, int C,
 static int recompose_u8(const char* who, bool fit, const void* d_tiles, int dtype, int n, int C, int P, int height, int width, double step, int scale,
                         int via_dtype, int denormalize, int alpha, int alpha_const, int crop, uint8_t* d_img, hipStream_t s) {
     if (!d_tiles || !d_img) return set_error(INNFER_ERR_INVALID, "%s: null argument", who);
-    if (fit ? (C != 1 && C != 2 && C != 4) : (C < 1 || C > 4)) return set_error(INNFER_ERR_INVALID, "%s: %d channels (%s)", who, C, fit ? "1, 2 or 4" : "1 .. 4");
-    if (fit && (C == 1 ? alpha != 0 : (!alpha && (alpha_const < 0 || alpha_const > 255))))
-        return set_error(INNFER_ERR_INVALID, "%s: a %d-channel image needs %s", who, C, C == 1 ? "no alpha tiles" : "alpha tiles or a constant alpha in [0, 255]");
+    if (int rc = check_u8_form(who, fit, C, alpha, alpha_const, true)) return rc;
     BlendGeo g;
     if (int rc = blend_geo(who, n, P, height, width, step, scale, crop, false, &g)) return rc;
     const int OH = g.FH - 2 * g.cs, OW = g.FW - 2 * g.cs;
     if (OH > 65535) return set_error(INNFER_ERR_UNSUPPORTED, "%s: %d output rows exceed the launch grid", who, OH);
     const dim3 grid((OW + 255) / 256, OH), block(256);
     const int a = alpha ? 1 : 0;
-#define RC(TI, TO, CC, F) hipLaunchKernelGGL((k_recompose_u8<TI, TO, CC, F>), grid, block, 0, s, (const TI*)d_tiles, n, P, g.FH, g.FW, g.eff, g.nh, g.nw, g.ov, g.cs, OW, \
-                                             a, alpha_const, denormalize, d_img)
-#define RC_C(TI, TO) do { if (fit) { if (C == 1) RC(TI, TO, 1, true); else if (C == 2) RC(TI, TO, 2, true); else RC(TI, TO, 4, true); } \
-                          else { if (C == 1) RC(TI, TO, 1, false); else if (C == 2) RC(TI, TO, 2, false); else if (C == 3) RC(TI, TO, 3, false); else RC(TI, TO, 4, false); } } while (0)
-    if (dtype == INNFER_F16 && via_dtype == INNFER_F16) RC_C(f16, f16);
-    else if (dtype == INNFER_F16 && via_dtype == INNFER_F32) RC_C(f16, float);
-    else if (dtype == INNFER_F32 && via_dtype == INNFER_F32) RC_C(float, float);
-    else if (dtype == INNFER_F32 && via_dtype == INNFER_F16) RC_C(float, f16);
-    else return set_error(INNFER_ERR_INVALID, "%s: bad dtype", who);
-#undef RC_C
-#undef RC
+    if (!is_float_dtype(dtype) || !is_float_dtype(via_dtype)) return set_error(INNFER_ERR_INVALID, "%s: bad dtype", who);
+    with_dtype(dtype, [&](auto ti) { with_dtype(via_dtype, [&](auto to) { with_form(fit, C, [&](auto c, auto f) {
+        hipLaunchKernelGGL((k_recompose_u8<decltype(ti), decltype(to), decltype(c)::value, decltype(f)::value>), grid, block, 0, s, (const decltype(ti)*)d_tiles, n, P,
+                           g.FH, g.FW, g.eff, g.nh, g.nw, g.ov, g.cs, OW, a, alpha_const, denormalize, d_img);
+    }); }); });
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
 }

@@ -128,6 +128,18 @@ def _infer_ppon(state_dict, scale, in_nc, out_nc):
                 state_dict=state_dict, net_params=get_network_G_config(cfg, int(scale)))
 
 
+def _check_out(out, shape):
+    """run_u8's `out`: None, or a contiguous uint8 tensor of the result's shape."""
+    if out is not None and (tuple(out.shape) != tuple(shape) or out.dtype != torch.uint8 or not out.is_contiguous()):
+        raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {tuple(shape)}')
+
+
+def _into_out(r, out):
+    """r, or `out` (checked) holding it."""
+    _check_out(out, r.shape)
+    return r if out is None else out.copy_(r)
+
+
 class Model:
     def __init__(self, model_path, arch=None, scale=None, in_nc=3, out_nc=3, device='cuda',
                  meval=True, strict=True, chop=True, tile_batch=None, state_dict=None):
@@ -253,7 +265,6 @@ class Model:
         import numpy as np
         if outscale is not None:
             return self._run_u8_outscale(img, outscale, outfilter, normalize, fp16, out, fit_channels, seamless, tta)
-        from . import lib as L
         from .architectures.engine_module import EngineModule
         from .utils import utils as U
         host = isinstance(img, np.ndarray)
@@ -270,43 +281,37 @@ class Model:
                 return r[:, :, 0]
             if plan is not None:
                 return self._run_u8_fit(img, plan, normalize, fp16, out, mode, tta)
-        d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img.contiguous()
-        if d.dtype != torch.uint8 or d.dim() != 3:
+        d, host = self._as_device_u8(img)
+        if d.dim() != 3:
             raise TypeError('run_u8: expected a uint8 HWC image')
-        H, W, Cc = d.shape
-        s = int(self.scale or 1)
-        dt = torch.float16 if fp16 else torch.float32
-        code = L.F16 if fp16 else L.F32
-        stream = torch.cuda.current_stream(d.device).cuda_stream
-        fused_net = isinstance(self.model, EngineModule) and self.arch != 'ppon'
         with torch.no_grad(), torch.cuda.device(d.device):
             if self.chop:
                 out = self._chop_u8(d, normalize, fp16, out, mode=mode, tta=tta)
-            elif fused_net and not tta:
+            elif isinstance(self.model, EngineModule) and self.arch != 'ppon' and not tta:
                 out = self.model.forward_u8(d, normalize=normalize, fp16=fp16, out=out)
             else:
-                x = torch.empty((1, Cc, H, W), dtype=dt, device=d.device)
-                L.check(L.lib.innfer_u8hwc_to_nchw(d.data_ptr(), H, W, Cc, int(bool(normalize)), x.data_ptr(), code, stream))
-                y = (self.forward_tta(x) if tta else self._predict(x)).contiguous()
-                if out is None:
-                    out = torch.empty((y.shape[2], y.shape[3], y.shape[1]), dtype=torch.uint8, device=d.device)
-                L.check(L.lib.innfer_nchw_to_u8hwc(y.data_ptr(), U._dt(y), y.shape[2], y.shape[3], y.shape[1], int(bool(normalize)), out.data_ptr(), stream))
+                out = self._tensor_u8(d, normalize, fp16, None, self.forward_tta if tta else self._predict, out)
         return out.cpu().numpy() if host else out
+
+    def _as_device_u8(self, img):
+        """(the uint8 image on the device, contiguous; whether it came as a numpy array, so that the result is downloaded)."""
+        import numpy as np
+        host = isinstance(img, np.ndarray)
+        d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img.contiguous()
+        if d.dtype != torch.uint8:
+            raise TypeError('run_u8: expected a uint8 HWC image')
+        return d, host
 
     def _run_u8_outscale(self, img, outscale, outfilter, normalize, fp16, out, fit_channels, seamless, tta=False):
         """run_u8(outscale=): the plain call on the device, then utils.resample to int(H outscale) x int(W outscale) before the download.  A final size
         equal to the network's own result is the plain result: nothing is resampled."""
-        import numpy as np
         from . import lib as L
         from .utils import utils as U
-        host = isinstance(img, np.ndarray)
         oh, ow = U.resample_size(img.shape[0], img.shape[1], outscale)
         L.resample_filter(outfilter)
-        d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img
+        d, host = self._as_device_u8(img)
         r = self.run_u8(d, normalize=normalize, fp16=fp16, fit_channels=fit_channels, seamless=seamless, tta=tta)
-        shape = (oh, ow) + tuple(r.shape[2:])
-        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous()):
-            raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {shape}')
+        _check_out(out, (oh, ow) + tuple(r.shape[2:]))
         with torch.cuda.device(r.device):
             r = U.resample(r, size=(oh, ow), filter=outfilter, wrap=seamless == 'tile', out=out)
         return r.cpu().numpy() if host else r
@@ -315,42 +320,45 @@ class Model:
         """Whether the tile buffers of the eight orientations (nbytes: low-resolution tiles and their results) may be allocated: at most half of the free memory."""
         return nbytes <= torch.cuda.mem_get_info(device)[0] // 2
 
-    def _tta_tensor_u8(self, d, normalize, fp16, out, fit_C, mode):
-        """run_u8(tta=True) of the uint8 device image d without the fused kernels: forward_tta on the device tensor between the existing conversions
-        (pad, np2tensor / fit_split, tensor2np / fit_merge, crop).  fit_C, mode as for _chop_u8."""
+    def _tensor_u8(self, d, normalize, fp16, fit_C, fwd, out=None):
+        """The uint8 device image d through fwd (self._predict or self.forward_tta) between the separate conversions: np2tensor / tensor2np, or under a
+        fit_channels plan fit_C (1, 2, 4) fit_split / fit_merge with one fwd per plane (never one batch: train-mode BatchNorm depends on the batch).
+        Returns the uint8 device result, in `out` where one is given."""
         from . import lib as L
         from .utils import utils as U
-        s = int(self.scale or 1)
-        dt = torch.float16 if fp16 else torch.float32
+        dt, code = (torch.float16, L.F16) if fp16 else (torch.float32, L.F32)
         stream = torch.cuda.current_stream(d.device).cuda_stream
-        src = d if mode is None else U.seamless_pad(d, next(name for name, code in L.BORDER_MODES.items() if code == mode))
         if fit_C:
-            colour, alpha, const = U.fit_split(src, normalize=normalize, dtype=dt)
-            y = self.forward_tta(colour)
-            ya = self.forward_tta(alpha) if alpha is not None else None
+            colour, alpha, const = U.fit_split(d, normalize=normalize, dtype=dt)
+            y = fwd(colour)
+            ya = fwd(alpha) if alpha is not None else None
             r = U.fit_merge(y, ya, const, fit_C, denormalize=normalize, bits=8)
-            r = r.view(U.fit_channels_out_shape(tuple(src.shape), s))
-        else:
-            H, W, Cc = src.shape
-            x = torch.empty((1, Cc, H, W), dtype=dt, device=d.device)
-            L.check(L.lib.innfer_u8hwc_to_nchw(src.data_ptr(), H, W, Cc, int(bool(normalize)), x.data_ptr(), L.F16 if fp16 else L.F32, stream))
-            y = self.forward_tta(x).contiguous()
-            r = torch.empty((y.shape[2], y.shape[3], y.shape[1]), dtype=torch.uint8, device=d.device)
-            L.check(L.lib.innfer_nchw_to_u8hwc(y.data_ptr(), U._dt(y), y.shape[2], y.shape[3], y.shape[1], int(bool(normalize)), r.data_ptr(), stream))
-        if mode is not None:
-            r = U.seamless_crop(r, s)
+            return _into_out(r.view(U.fit_channels_out_shape(tuple(d.shape), int(self.scale or 1))), out)
+        H, W, Cc = d.shape
+        x = torch.empty((1, Cc, H, W), dtype=dt, device=d.device)
+        L.check(L.lib.innfer_u8hwc_to_nchw(d.data_ptr(), H, W, Cc, int(bool(normalize)), x.data_ptr(), code, stream))
+        y = fwd(x).contiguous()
+        shape = (y.shape[2], y.shape[3], y.shape[1])
+        _check_out(out, shape)
         if out is None:
-            return r
-        if tuple(out.shape) != tuple(r.shape) or out.dtype != torch.uint8:
-            raise ValueError(f'run_u8: out must be a uint8 tensor of shape {tuple(r.shape)}')
-        out.copy_(r)
+            out = torch.empty(shape, dtype=torch.uint8, device=d.device)
+        L.check(L.lib.innfer_nchw_to_u8hwc(y.data_ptr(), U._dt(y), y.shape[2], y.shape[3], y.shape[1], int(bool(normalize)), out.data_ptr(), stream))
         return out
+
+    def _tta_tensor_u8(self, d, normalize, fp16, out, fit_C, mode):
+        """run_u8(tta=True) of the uint8 device image d without the fused kernels: _tensor_u8 with forward_tta, under a border code `mode` of the image
+        padded in front and cropped behind."""
+        from . import lib as L
+        from .utils import utils as U
+        if mode is None:
+            return self._tensor_u8(d, normalize, fp16, fit_C, self.forward_tta, out)
+        src = U.seamless_pad(d, next(name for name, code in L.BORDER_MODES.items() if code == mode))
+        return _into_out(U.seamless_crop(self._tensor_u8(src, normalize, fp16, fit_C, self.forward_tta), int(self.scale or 1)), out)
 
     def _chop_u8(self, d, normalize, fp16, out, fit_C=None, mode=None, tta=False):
         """The chop path of run_u8 for the uint8 device image d: plan, gather, run the tiles, blend -- one gather and one blend call for all four forms.
         fit_C: the fit_channels plan (1, 2, 4) or None; mode: the border code of run_u8(seamless=) or None, which is the same two kernels at pad = 0 /
-        crop = 0.  out is checked here under a seamless mode (_run_u8_fit has checked its own); the plain form takes it as given, as it always has.
-        tta: the tiles of all eight orientations in one buffer (8 n, with alpha 16 n), one tile stream, one blend (innfer_extract_tiles_u8_tta,
+        crop = 0.  tta: the tiles of all eight orientations in one buffer (8 n, with alpha 16 n), one tile stream, one blend (innfer_extract_tiles_u8_tta,
         innfer_recompose_u8_tta); where the buffers do not fit (_tta_fits, or the allocator says so) _tta_tensor_u8 returns the same bits."""
         from . import lib as L
         from .parallel import run_tile_batches
@@ -367,69 +375,50 @@ class Model:
         ps = min(H + 2 * pad, W + 2 * pad, 200)
         _, ys, xs = L.chop_plan(H + 2 * pad, W + 2 * pad, ps, 0.5)
         n = len(ys) * len(xs)
+        count, Cin, Ct = (8 if tta else 1) * (2 if alpha else 1) * n, fit_C or d.shape[2], 3 if fit_C else d.shape[2]
+        if tta and not self._tta_fits(count * Ct * ps * ps * (1 + s * s) * (2 if fp16 else 4), d.device):
+            return self._tta_tensor_u8(d, normalize, fp16, out, fit_C, mode)
+        try:
+            tiles = torch.empty((count, Ct, ps, ps), dtype=dt, device=d.device)
+            buf = self._tile_buffer(tiles)
+        except torch.OutOfMemoryError:
+            if not tta:
+                raise
+            tiles = None
+            return self._tta_tensor_u8(d, normalize, fp16, out, fit_C, mode)
         if tta:
-            count, Ct = (16 if alpha else 8) * n, 3 if fit_C else d.shape[2]
-            buf = None
-            if self._tta_fits(count * Ct * ps * ps * (1 + s * s) * (2 if fp16 else 4), d.device):
-                try:
-                    tiles = torch.empty((count, Ct, ps, ps), dtype=dt, device=d.device)
-                    buf = self._tile_buffer(tiles)
-                except torch.OutOfMemoryError:
-                    tiles = buf = None
-            else:
-                tiles = None
-            if tiles is None:
-                return self._tta_tensor_u8(d, normalize, fp16, out, fit_C, mode)
-            L.check(L.lib.innfer_extract_tiles_u8_tta(d.data_ptr(), fit_C or d.shape[2], H, W, int(bool(normalize)), ps, 0.5, int(bool(fit_C)), int(alpha), pad, border,
+            L.check(L.lib.innfer_extract_tiles_u8_tta(d.data_ptr(), Cin, H, W, int(bool(normalize)), ps, 0.5, int(bool(fit_C)), int(alpha), pad, border,
                                                       tiles.data_ptr(), code, stream))
-            hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=buf)
-            del tiles
-            if fit_C and hr.shape[1] != 3:
-                raise ValueError(f'run_u8: fit_channels needs a 3-channel result, the network returned {hr.shape[1]}')
-            hr = hr.contiguous()
-            Co, P = hr.shape[1], hr.shape[2]
-            shape = U.fit_channels_out_shape(tuple(d.shape), s) if fit_C else (H * s, W * s, Co)
-            if out is None:
-                out = torch.empty(shape, dtype=torch.uint8, device=d.device)
-            elif tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous():
-                raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {shape}')
-            L.check(L.lib.innfer_recompose_u8_tta(hr.data_ptr(), U._dt(hr), n, fit_C or Co, P, H + 2 * pad, W + 2 * pad, 0.5, s, U._dt(hr), int(bool(normalize)),
-                                                  int(bool(fit_C)), int(alpha), -1 if const is None else const, pad, out.data_ptr(), stream))
-            return out
-        tiles = torch.empty(((2 if alpha else 1) * n, 3 if fit_C else d.shape[2], ps, ps), dtype=dt, device=d.device)
-        gather = (d.data_ptr(), fit_C or d.shape[2], H, W, int(bool(normalize)), ps, 0.5, 0, n) + ((int(alpha),) if fit_C else ())
-        L.check((L.lib.innfer_extract_tiles_u8_fit_seamless if fit_C else L.lib.innfer_extract_tiles_u8_seamless)(*gather, pad, border, tiles.data_ptr(), code, stream))
-        hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=self._tile_buffer(tiles))
+        else:
+            gather = (d.data_ptr(), Cin, H, W, int(bool(normalize)), ps, 0.5, 0, n) + ((int(alpha),) if fit_C else ())
+            L.check((L.lib.innfer_extract_tiles_u8_fit_seamless if fit_C else L.lib.innfer_extract_tiles_u8_seamless)(*gather, pad, border, tiles.data_ptr(), code, stream))
+        hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=buf)
+        del tiles
         if fit_C and hr.shape[1] != 3:
             raise ValueError(f'run_u8: fit_channels needs a 3-channel result, the network returned {hr.shape[1]}')
         hr = hr.contiguous()
         Co, P = hr.shape[1], hr.shape[2]
         shape = U.fit_channels_out_shape(tuple(d.shape), s) if fit_C else (H * s, W * s, Co)
+        _check_out(out, shape)
         if out is None:
             out = torch.empty(shape, dtype=torch.uint8, device=d.device)
-        elif mode is not None and (tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous()):
-            raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {shape}')
-        blend = (hr.data_ptr(), U._dt(hr), n) + (() if fit_C else (Co,)) + (P, H + 2 * pad, W + 2 * pad, 0.5, s, U._dt(hr), int(bool(normalize)))
-        blend += (fit_C, int(alpha), -1 if const is None else const) if fit_C else ()
-        L.check((L.lib.innfer_recompose_u8_fit_seamless if fit_C else L.lib.innfer_recompose_u8_seamless)(*blend, pad, out.data_ptr(), stream))
+        aconst = -1 if const is None else const
+        if tta:
+            L.check(L.lib.innfer_recompose_u8_tta(hr.data_ptr(), U._dt(hr), n, fit_C or Co, P, H + 2 * pad, W + 2 * pad, 0.5, s, U._dt(hr), int(bool(normalize)),
+                                                  int(bool(fit_C)), int(alpha), aconst, pad, out.data_ptr(), stream))
+        else:
+            blend = (hr.data_ptr(), U._dt(hr), n) + (() if fit_C else (Co,)) + (P, H + 2 * pad, W + 2 * pad, 0.5, s, U._dt(hr), int(bool(normalize)))
+            blend += (fit_C, int(alpha), aconst) if fit_C else ()
+            L.check((L.lib.innfer_recompose_u8_fit_seamless if fit_C else L.lib.innfer_recompose_u8_seamless)(*blend, pad, out.data_ptr(), stream))
         return out
 
     def _run_u8_padded(self, img, seamless, normalize, fp16, out, fit_channels, tta=False):
         """run_u8(seamless=) where the chop kernels do not apply (whole-image forwards): pad on the GPU (innfer_pad_inthwc), run as without the switch,
         crop on the GPU."""
-        import numpy as np
         from .utils import utils as U
-        host = isinstance(img, np.ndarray)
-        d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img
-        if d.dtype != torch.uint8:
-            raise TypeError('run_u8: expected a uint8 image')
+        d, host = self._as_device_u8(img)
         r = self.run_u8(U.seamless_pad(d, seamless), normalize=normalize, fp16=fp16, fit_channels=fit_channels, tta=tta)
-        r = U.seamless_crop(r, int(self.scale or 1))
-        if out is not None:
-            if tuple(out.shape) != tuple(r.shape) or out.dtype != torch.uint8:
-                raise ValueError(f'run_u8: out must be a uint8 tensor of shape {tuple(r.shape)}')
-            out.copy_(r)
-            r = out
+        r = _into_out(U.seamless_crop(r, int(self.scale or 1)), out)
         return r.cpu().numpy() if host else r
 
     def _run_u8_fit(self, img, C, normalize, fp16, out, mode=None, tta=False):
@@ -438,29 +427,14 @@ class Model:
         (_chop_u8: the FIT forms of the gather and the blend).  Otherwise the two planes are split, run as separate forwards (never one batch:
         train-mode BatchNorm depends on the batch) and merged (innfer_inthwc_to_nchw_fit / innfer_nchw_to_inthwc_fit).
         mode: the border code of run_u8(seamless=) on the chop path."""
-        import numpy as np
         from .utils import utils as U
-        host = isinstance(img, np.ndarray)
-        d = torch.from_numpy(np.ascontiguousarray(img)).to(self.device) if host else img.contiguous()
-        if d.dtype != torch.uint8:
-            raise TypeError('run_u8: expected a uint8 image')
-        dt = torch.float16 if fp16 else torch.float32
-        shape = U.fit_channels_out_shape(tuple(d.shape), int(self.scale or 1))
-        if out is not None and (tuple(out.shape) != shape or out.dtype != torch.uint8 or not out.is_contiguous()):
-            raise ValueError(f'run_u8: out must be a contiguous uint8 tensor of shape {shape}')
+        d, host = self._as_device_u8(img)
+        _check_out(out, U.fit_channels_out_shape(tuple(d.shape), int(self.scale or 1)))
         with torch.no_grad(), torch.cuda.device(d.device):
             if self.chop:
                 out = self._chop_u8(d, normalize, fp16, out, fit_C=C, mode=mode, tta=tta)
             else:
-                fwd = self.forward_tta if tta else self._predict
-                colour, alpha, const = U.fit_split(d, normalize=normalize, dtype=dt)
-                y = fwd(colour)
-                ya = fwd(alpha) if alpha is not None else None
-                r = U.fit_merge(y, ya, const, C, denormalize=normalize, bits=8)
-                if out is None:
-                    out = r.view(shape)
-                else:
-                    out.copy_(r.view(shape))
+                out = self._tensor_u8(d, normalize, fp16, C, self.forward_tta if tta else self._predict, out)
         return out.cpu().numpy() if host else out
 
 
@@ -610,13 +584,13 @@ def main(argv=None):
             plan = U.fit_channels_plan(im.shape, im.dtype, ins[0], outs[-1])
             return plan if plan == 0 or all(i == o == 3 for i, o in zip(ins, outs)) else None
 
-        def fit_chain(t_in):                # the tensor path of one plane: the chain [with the guided filter, the plane's own input as the guide]
-            t = t_in
-            for mod in models:
-                t = mod.forward_tta(t) if tta else mod(t)
-                if use_guided_filter:
-                    t = U.guided_filter(t_in, t, r=1, eps=5e-3)
-            return t
+    def chain(t_in):                        # the tensor path of an image or of one fit_channels plane: the chain [with the guided filter, its own input as the guide]
+        t = t_in
+        for mod in models:
+            t = mod.forward_tta(t) if tta else mod(t)
+            if use_guided_filter:
+                t = U.guided_filter(t_in, t, r=1, eps=5e-3)
+        return t
     images = U.get_images_paths(args.input)
     os.makedirs(args.output, exist_ok=True)
     # The loop is pipelined over the images: one thread decodes the next image file while the GPU works on this one, up to sixteen threads
@@ -670,17 +644,12 @@ def main(argv=None):
             if plan and single:                                                         # plan 1, 2, 4: colour (+ alpha) planes
                 img_out = models[0].run_u8(img, normalize=normalize, fp16=fp16, fit_channels=True, **sm)
             elif plan:
-                img_out = U.fit_channels_forward(fit_chain, img, normalize=normalize, device=device, dtype=torch.float16 if fp16 else torch.float32)
+                img_out = U.fit_channels_forward(chain, img, normalize=normalize, device=device, dtype=torch.float16 if fp16 else torch.float32)
             elif single and img.ndim == 3:
                 img_out = models[0].run_u8(img, normalize=normalize, fp16=fp16, **sm)    # conversions fused into the tile gather / blend / first and last conv
             else:
                 t_img = U.np2tensor(img, normalize=normalize, device=device, dtype=torch.float16 if fp16 else torch.float32)
-                t_out = t_img
-                for mod in models:
-                    t_out = mod.forward_tta(t_out) if tta else mod(t_out)
-                    if use_guided_filter:
-                        t_out = U.guided_filter(t_img, t_out, r=1, eps=5e-3)
-                img_out = U.tensor2np(t_out.detach(), denormalize=normalize)
+                img_out = U.tensor2np(chain(t_img).detach(), denormalize=normalize)
             if img is not src:                                                          # padded in front of the chain: PAD x the chain's scale off every side
                 total = 1
                 for mod in models:

@@ -44,14 +44,14 @@ def _model(tmp_path, chop, seed=80, scale=2, name=None):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1. the gather
-def _gather_ref(d, C, h, w, normalize, dt, mode, fit, alpha):
+def _gather_ref(d, C, h, w, normalize, dt, mode, fit, alpha, patch=200):
     """All tiles of the [h, w, C] device image by the existing gathers: [n (x 2 with alpha), C | 3, ps, ps]."""
     from innfer_amd import lib as L
     pad = 0 if mode is None else PAD
-    ps, ys, xs = L.chop_plan(h + 2 * pad, w + 2 * pad, 200, 0.5)
+    ps, ys, xs = L.chop_plan(h + 2 * pad, w + 2 * pad, patch, 0.5)
     n = len(ys) * len(xs)
     tiles = torch.full(((2 if alpha else 1) * n, 3 if fit else C, ps, ps), 7.0, dtype=dt, device=d.device)
-    head = (d.data_ptr(), C, h, w, int(normalize), 200, 0.5, 0, n)
+    head = (d.data_ptr(), C, h, w, int(normalize), patch, 0.5, 0, n)
     tail = (tiles.data_ptr(), L.F16 if dt == torch.float16 else L.F32, _stream())
     if mode is None:
         rc = L.lib.innfer_extract_tiles_u8_fit(*head, int(alpha), *tail) if fit else L.lib.innfer_extract_tiles_u8(*head, *tail)
@@ -97,6 +97,36 @@ def test_gather(dev, mode, fit):
                             assert torch.equal(got[k * n:(k + 1) * n], refs[k][0][:n]), tag + (k,)
                             if alpha:
                                 assert torch.equal(got[8 * n + k * n:8 * n + (k + 1) * n], refs[k][0][n:]), tag + (k, "alpha")
+
+
+def test_gather_launch_split(dev):
+    """More slots than one launch takes (the grid's y ends at 65535): a 120 x 141 image of 2 channels at patch 2 is a 119 x 140 lattice, n = 16 660, so
+    each half of the gather (4 n = 66 640 slots, straight and transposed) is a launch of 65 535 slots and one of 1 105 that starts at slot_begin 65 535;
+    the sides differ, so the transposed lattice is 140 x 119.  The plain form and the fit form with alpha tiles, whose slot base is 8 n whatever the
+    launch: fp16, every orientation's slots held to the existing gather (one launch of n tiles) of utils.dihedral(img, k), the buffer's tail untouched."""
+    from innfer_amd import lib as L
+    from innfer_amd.utils import utils as U
+    h, w, C, patch = 120, 141, 2, 2
+    ps, ys, xs = L.chop_plan(h, w, patch, 0.5)
+    n = len(ys) * len(xs)
+    assert (ps, len(ys), len(xs)) == (2, 119, 140) and 4 * n == 65535 + 1105
+    img = _image(h, w, C, 27)
+    d = torch.from_numpy(img).to(dev)
+    turned = [torch.from_numpy(U.dihedral(img, k)).to(dev) for k in range(8)]
+    for fit, alpha in ((False, False), (True, True)):
+        refs = [_gather_ref(t, C, t.shape[0], t.shape[1], False, torch.float16, None, fit, alpha, patch) for t in turned]
+        assert all(r[1:] == (n, ps) for r in refs), fit
+        count, Ct = (16 if alpha else 8) * n, 3 if fit else C
+        numel = count * Ct * ps * ps
+        buf = torch.full((numel + 64,), 7.0, dtype=torch.float16, device=dev)
+        L.check(L.lib.innfer_extract_tiles_u8_tta(d.data_ptr(), C, h, w, 0, patch, 0.5, int(fit), int(alpha), 0, L.BORDER_MODES["replicate"], buf.data_ptr(), L.F16,
+                                                  _stream()))
+        got = buf[:numel].view(count, Ct, ps, ps)
+        assert bool((buf[numel:] == 7.0).all()), fit
+        for k in range(8):
+            assert torch.equal(got[k * n:(k + 1) * n], refs[k][0][:n]), (fit, k)
+            if alpha:
+                assert torch.equal(got[8 * n + k * n:8 * n + (k + 1) * n], refs[k][0][n:]), (fit, k, "alpha")
 
 
 def test_refusals(dev):
