@@ -45,8 +45,8 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  innfer_version() returns the library's; a binding should compare. */
-#define INNFER_ABI_VERSION 119
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  innfer_version() returns the library's; a binding should compare. */
+#define INNFER_ABI_VERSION 120
 int innfer_version(void);
 const char* innfer_last_error(void);
 
@@ -412,6 +412,13 @@ typedef struct {
                                            != 0 (plain 3x3 slab convs and transposed2x with K % 64 == 0): d_packed comes from innfer_pack_conv3x3_rows(.., 1) /
                                            innfer_pack_convt2x_rows(.., 1) -- the row order in which a lane's sixteen output channels are 16 bytes in each of the group's two
                                            32-channel slab planes (what the networks use for their 64-output layers: one plane per store instruction); results are the same (109) */
+    float* d_stats_part;                /* != NULL: the launch also writes the partial norm statistics of its fp32 result (bias included, before the fp16 rounding) that the
+                                           pix2pix UNet and the CycleGAN ResNet take out of their convs: innfer_conv_stats_records(H, W, phases) records of (count, mean, M2)
+                                           per image and channel, d_stats_part[((n * records + r) * channels + c) * 3], r = ((tile row * tile columns + tile column) [* 4 +
+                                           phase]) * 8 + consumer wave -- tiles of 16 x 32 pixels of the kernel's grid (transposed2x: the input grid, 4 phases), a wave owns
+                                           2 rows.  The 64-channel slab kernels without activation / residual: plain 3x3 (K % 64 == 0, any K), stride2_k4, transposed2x
+                                           (lane-contiguous panels), column7 with K = 64; anything else is INNFER_ERR_UNSUPPORTED.  Merged by innfer_norm_combine_parts. (120) */
+    int64_t stats_part_floats;          /* floats behind d_stats_part: at least N * records * K * 3, else INNFER_ERR_WORKSPACE (nothing is launched) (120) */
 } innfer_conv_args;
 
 size_t innfer_conv3x3_packed_bytes(int K, int C);
@@ -469,6 +476,27 @@ int innfer_f32conv_plan(const innfer_f32conv_args* a, int* plan);
 int innfer_f32_norm(const float* d_in, int64_t in_ns, int64_t in_cs, float* d_out, int64_t out_ns, int64_t out_cs, int N, int C, int64_t HW, int mode, float eps,
                     const float* d_weight, const float* d_bias, const float* d_rmean, const float* d_rvar, int act,
                     const float* d_res, int64_t res_ns, int64_t res_cs, int form, void* stream);
+
+/* (120) The norm statistics of the fp16 engine (csrc/norm_stats.h; train-mode BatchNorm2d of the pix2pix UNet, InstanceNorm2d of the CycleGAN ResNet) as single
+ * launches, for tests.  alpha / shift: [N][C] floats with  norm(x) = x * alpha + shift,  alpha = gamma / sqrt(var + eps), shift = beta - mean * alpha  (biased variance
+ * per image and channel; d_gamma / d_beta [C] or NULL for 1 / 0).  All pointers are device pointers.
+ * innfer_conv_stats_records: host only -- the records per image (and channel) a conv with d_stats_part writes for an H x W grid with `phases` (1 | 4) phases.
+ * innfer_norm_combine_parts: merges the records d_part[N][nper][C][3] of such a conv (Chan's update, fixed order).
+ * innfer_norm_stats: the re-read forms -- slab 0: d_src is fp32 [N][HW][cpad] (norm::launch_stats), slab != 0: d_src is an fp16 slab of group stride `gs` elements
+ * (norm::launch_stats_slab; cpad unused).  d_part: scratch of part_floats >= N * C * ceil(HW / 1024) * 2 floats when HW > 1024 (else INNFER_ERR_WORKSPACE).
+ * innfer_resnet_post_slab_parts / innfer_unet_post_slab_parts: merge + normalisation + activation in one launch, as the two networks run them behind such a conv
+ *   (rn_post_slab_parts / unet_post_slab_parts), on the grid the networks choose; eps is the networks' 1e-5.  C % 32 == 0.
+ *   resnet: d_dst = [relu](x * alpha + shift) [+ d_res]; d_src, d_res, d_dst are slabs of one group stride gs.
+ *   unet: d_dst0 (group stride dst0_gs, channel offset dst0_coff % 8 == 0, act0 1 LeakyReLU(0.2) | 2 ReLU) and, when d_dst1 is not NULL, the same for d_dst1. */
+int innfer_conv_stats_records(int H, int W, int phases);
+int innfer_norm_combine_parts(const float* d_part, int nper, int64_t HW, float eps, const float* d_gamma, const float* d_beta, float* d_alpha, float* d_shift,
+                              int C, int N, void* stream);
+int innfer_norm_stats(const void* d_src, int slab, int64_t gs, int cpad, int64_t HW, float eps, const float* d_gamma, const float* d_beta, float* d_alpha, float* d_shift,
+                      int C, int N, float* d_part, int64_t part_floats, void* stream);
+int innfer_resnet_post_slab_parts(const void* d_src, int64_t gs, int C, int64_t HW, int N, const float* d_part, int nper, const float* d_gamma, const float* d_beta,
+                                  int relu, const void* d_res, void* d_dst, void* stream);
+int innfer_unet_post_slab_parts(const void* d_src, int64_t src_gs, int C, int64_t HW, int N, const float* d_part, int nper, const float* d_gamma, const float* d_beta,
+                                void* d_dst0, int64_t dst0_gs, int dst0_coff, int act0, void* d_dst1, int64_t dst1_gs, int dst1_coff, int act1, void* stream);
 
 /* NCHW (f16/f32) <-> blocked-NHWC f16 slab helpers used by tests of the single conv. */
 int innfer_nchw_to_slab(const void* d_src, int src_dtype, void* d_slab, int64_t group_stride, int ch_off,

@@ -8,6 +8,7 @@
 //   Upsample(nearest 2x) -> folded into the next conv's input addressing
 //   PixelShuffle(2)      -> folded into the conv's store
 #include "common.h"
+#include "norm_stats.h"
 
 #include <cmath>
 #include <cstring>
@@ -1114,6 +1115,41 @@ extern "C" int innfer_pack_convt2x(const float* w, int K, int C, int k, void* pa
     return INNFER_OK;
 }
 
+// innfer_conv_args.d_stats_part -> ConvLaunch.stats_part, behind the size check (conv_launch decides which forms take statistics)
+static int conv_args_stats(const innfer_conv_args* a, int phases, ConvLaunch& L) {
+    if (!a->d_stats_part) return INNFER_OK;
+    if (a->N <= 0 || a->H <= 0 || a->W <= 0 || a->K <= 0) return set_error(INNFER_ERR_INVALID, "conv3x3: statistics of an empty launch (N=%d H=%d W=%d K=%d)", a->N, a->H, a->W, a->K);
+    const long long need = (long long)a->N * conv_stats_nper(a->H, a->W, phases) * a->K * 3;
+    if ((long long)a->stats_part_floats < need)
+        return set_error(INNFER_ERR_WORKSPACE, "conv3x3: stats_part_floats %lld < %lld (N * records * channels * 3)", (long long)a->stats_part_floats, need);
+    L.stats_part = a->d_stats_part;
+    return INNFER_OK;
+}
+
+extern "C" int innfer_conv_stats_records(int H, int W, int phases) {
+    if (H <= 0 || W <= 0 || (phases != 1 && phases != 4)) return set_error(INNFER_ERR_INVALID, "conv_stats_records: H=%d W=%d phases=%d (1 | 4)", H, W, phases);
+    return conv_stats_nper(H, W, phases);
+}
+
+extern "C" int innfer_norm_combine_parts(const float* d_part, int nper, int64_t HW, float eps, const float* d_gamma, const float* d_beta, float* d_alpha, float* d_shift,
+                                         int C, int N, void* stream) {
+    if (!d_part || !d_alpha || !d_shift || nper <= 0 || HW <= 0 || C <= 0 || N <= 0 || N > 65535)
+        return set_error(INNFER_ERR_INVALID, "norm_combine_parts: null argument or nper=%d HW=%lld C=%d N=%d", nper, (long long)HW, C, N);
+    return norm::launch_combine_parts(d_part, nper, (long)HW, eps, d_gamma, d_beta, d_alpha, d_shift, C, N, (hipStream_t)stream);
+}
+
+extern "C" int innfer_norm_stats(const void* d_src, int slab, int64_t gs, int cpad, int64_t HW, float eps, const float* d_gamma, const float* d_beta, float* d_alpha,
+                                 float* d_shift, int C, int N, float* d_part, int64_t part_floats, void* stream) {
+    if (!d_src || !d_alpha || !d_shift || HW <= 0 || C <= 0 || N <= 0 || N > 65535 || (HW + norm::SEG - 1) / norm::SEG > 65535)
+        return set_error(INNFER_ERR_INVALID, "norm_stats: null argument or HW=%lld C=%d N=%d", (long long)HW, C, N);
+    if (slab ? gs < (int64_t)N * HW * 32 : (cpad < C || cpad % 32))
+        return set_error(INNFER_ERR_INVALID, "norm_stats: group stride %lld < N * HW * 32 (slab), or cpad=%d below C=%d / not a multiple of 32 (fp32)", (long long)gs, cpad, C);
+    if (HW > norm::SEG && (!d_part || part_floats < 0 || (unsigned long long)part_floats < (unsigned long long)N * norm::part_floats(C, (long)HW)))
+        return set_error(INNFER_ERR_WORKSPACE, "norm_stats: part_floats %lld < %llu", (long long)part_floats, (unsigned long long)N * norm::part_floats(C, (long)HW));
+    return slab ? norm::launch_stats_slab((const f16*)d_src, (long)gs, (long)HW, eps, d_gamma, d_beta, d_alpha, d_shift, C, N, d_part, (hipStream_t)stream)
+                : norm::launch_stats((const float*)d_src, cpad, (long)HW, eps, d_gamma, d_beta, d_alpha, d_shift, C, N, d_part, (hipStream_t)stream);
+}
+
 extern "C" int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream) {
     if (!a || !a->d_in || !a->d_packed || !a->d_bias || !a->d_out) return set_error(INNFER_ERR_INVALID, "conv3x3: null argument");
     if (a->column7) {
@@ -1126,6 +1162,7 @@ extern "C" int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream) {
         L.out = a->d_out; L.out_gstride = a->out_group_stride; L.K = a->K;
         L.N = a->N; L.H = a->H; L.W = a->W; L.act = a->act; L.s1 = L.s2 = 1.f; L.y0 = 0; L.y1 = a->H; L.out_mode = OUT_SLAB;
         L.conv7v = 1; L.reflect = a->reflect_pad ? 1 : 0;
+        if (int rc = conv_args_stats(a, 1, L)) return rc;
         return conv_launch(L, (hipStream_t)stream);
     }
     if (a->stride2_k4 || a->transposed2x) {
@@ -1140,13 +1177,14 @@ extern "C" int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream) {
         L.N = a->N; L.H = a->H; L.W = a->W; L.act = a->act; L.s1 = L.s2 = 1.f; L.y0 = 0; L.y1 = a->H; L.out_mode = OUT_SLAB;
         if (a->stride2_k4) L.stride2 = 1;
         else { L.K = 4 * a->K; L.phase_c = a->K; L.deconv_phases = 1; L.rowp = a->plane_rows ? 1 : 0; }
+        if (int rc = conv_args_stats(a, a->stride2_k4 ? 1 : 4, L)) return rc;
         return conv_launch(L, (hipStream_t)stream);
     }
     if (a->pixel_shuffle2) {
         if (a->K <= 0 || a->K % 64 || a->out_ch_off || a->row_begin || a->row_end || a->dilation > 1 || a->dilation_groups || a->reflect_pad || a->act < 0 || a->act > 2)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the PixelShuffle(2) store needs K %% 64 == 0 (K=%d), out_ch_off 0, act 0..2, all rows, plain zero padding", a->K);
-    } else if (a->dilation_groups > 0 ? a->K != 32 * a->dilation_groups : (a->K <= 0 || a->K % 16 || a->K > 64))
-        return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: K=%d (need K %% 16 == 0, K <= 64; K = 32 * dilation_groups)", a->K);
+    } else if (a->dilation_groups > 0 ? a->K != 32 * a->dilation_groups : (a->K <= 0 || a->K % 16 || (a->K > 64 && !(a->d_stats_part && a->K % 64 == 0))))
+        return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: K=%d (need K %% 16 == 0, K <= 64 -- with d_stats_part any K %% 64 == 0; K = 32 * dilation_groups)", a->K);
     ConvLaunch L{};
     if (a->out_ch_off % 16 || (a->out_ch_off % 32 && a->K > 16))
         return set_error(INNFER_ERR_INVALID, "conv3x3: out_ch_off=%d must keep the %d output channels inside 32-channel groups", a->out_ch_off, a->K);
@@ -1169,6 +1207,7 @@ extern "C" int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream) {
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3 (split): K in {32, 64} (K=%d), slab output, the lo distances of every tensor given", a->K);
         L.split = 1; L.in_lo = a->in_lo; L.out_lo = a->out_lo; L.res1_lo = a->res1_lo; L.res2_lo = a->res2_lo;
     }
+    if (int rc = conv_args_stats(a, 1, L)) return rc;
     return conv_launch(L, (hipStream_t)stream);
 }
 

@@ -232,6 +232,16 @@ __global__ __launch_bounds__(256) void rn_post_slab_parts(const f16* src, int C,
     }
 }
 
+// The launch of rn_post_slab_parts as the network makes it (grid and pxb included): shared by the ResnetBlock conv below and by the test entry point
+// innfer_resnet_post_slab_parts, so a test of the kernel runs the network's launch.
+static int launch_rn_post_slab_parts(const f16* src, int C, long HW, int N, const float* part, int nper, const float* gamma, const float* beta, int relu,
+                                     const f16* res, f16* dst, long G, hipStream_t s) {
+    const int pxb = ((HW + 1023) / 1024) * (C / 32) * N >= 256 ? 1024 : 256;
+    hipLaunchKernelGGL(rn_post_slab_parts, dim3((unsigned)((HW + pxb - 1) / pxb), C / 32, N), dim3(256), 0, s, src, C, HW, part, nper, 1e-5f, gamma, beta, relu, res, dst, G, pxb);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
 // NCHW input -> "row patch" slab of the reflection-padded first 7x7 conv: channel kx*C + c of pixel (y, x) holds in[c][y][reflect(x + kx - 3)]
 // (zero beyond 7*C <= 32 channels), so the 49-tap conv becomes 7 vertical taps (reflected by the GEMM's gather) over ONE 32-channel group.
 // C > 4: plain copy into a zero-padded group (49 taps).  One thread per pixel, 16-byte stores.
@@ -317,6 +327,15 @@ static void add_layer(innfer_resnet* r, const std::string& key, int cin, int cou
         RP(r, norm + ".num_batches_tracked", {});
     }
     r->layers.push_back(l);
+}
+
+// rn_post_slab_parts alone, for tests: the network's launch (launch_rn_post_slab_parts) on a caller's slab, records and destination
+extern "C" int innfer_resnet_post_slab_parts(const void* d_src, int64_t gs, int C, int64_t HW, int N, const float* d_part, int nper, const float* d_gamma, const float* d_beta,
+                                             int relu, const void* d_res, void* d_dst, void* stream) {
+    if (!d_src || !d_part || !d_dst || C <= 0 || C % 32 || HW <= 0 || N <= 0 || N > 65535 || nper <= 0 || gs < (int64_t)N * HW * 32)
+        return set_error(INNFER_ERR_INVALID, "resnet_post_slab_parts: null argument, C=%d (%% 32), HW=%lld, N=%d, nper=%d or group stride %lld < N * HW * 32", C, (long long)HW, N, nper,
+                         (long long)gs);
+    return launch_rn_post_slab_parts((const f16*)d_src, C, (long)HW, N, d_part, nper, d_gamma, d_beta, relu ? 1 : 0, (const f16*)d_res, (f16*)d_dst, (long)gs, (hipStream_t)stream);
 }
 
 extern "C" int innfer_resnet_create(innfer_resnet** out, int in_nc, int out_nc, int ngf, int n_blocks) {
@@ -779,11 +798,8 @@ extern "C" int innfer_resnet_forward(innfer_resnet* r, const void* d_in, int in_
         } else if (l.cout % 64 == 0 && l.cout <= 256) {      // statistics as per-tile partials out of the conv epilogue: the slab is not read again for them
             L.stats_part = part;
             CK(conv_launch(L, s));
-            const int pxb = ((HW + 1023) / 1024) * (l.cout / 32) * N >= 256 ? 1024 : 256;
-            hipLaunchKernelGGL(rn_post_slab_parts, dim3((unsigned)((HW + pxb - 1) / pxb), l.cout / 32, N), dim3(256), 0, s, (const f16*)Y, l.cout, HW,
-                               (const float*)part, conv_stats_nper(Hc, Wc, 1), 1e-5f, (const float*)l.d_gamma, (const float*)l.d_beta, relu, res, dst, G, pxb);
-            INNFER_HIP(hipGetLastError());
-            return INNFER_OK;
+            return launch_rn_post_slab_parts((const f16*)Y, l.cout, HW, N, (const float*)part, conv_stats_nper(Hc, Wc, 1), (const float*)l.d_gamma, (const float*)l.d_beta,
+                                             relu, res, dst, G, s);
         } else {
         CK(conv_launch(L, s));
         CK(norm::launch_stats_slab(Y, G, HW, 1e-5f, l.d_gamma, l.d_beta, alpha, shift, l.cout, N, part, s));

@@ -469,6 +469,18 @@ static int add_param(innfer_unet* u, const std::string& key, std::vector<int> sh
     return (int)u->params.size() - 1;
 }
 
+// unet_post_slab_parts alone, for tests: the network's launch (launch_post_slab_parts: its grid and pixel-block choice) on a caller's slab, records and destinations
+extern "C" int innfer_unet_post_slab_parts(const void* d_src, int64_t src_gs, int C, int64_t HW, int N, const float* d_part, int nper, const float* d_gamma, const float* d_beta,
+                                           void* d_dst0, int64_t dst0_gs, int dst0_coff, int act0, void* d_dst1, int64_t dst1_gs, int dst1_coff, int act1, void* stream) {
+    const int64_t px32 = (int64_t)N * HW * 32;
+    if (!d_src || !d_part || !d_dst0 || C <= 0 || C % 32 || HW <= 0 || N <= 0 || N > 65535 || nper <= 0 || src_gs < px32 || dst0_gs < px32 || dst0_coff < 0 || dst0_coff % 8 ||
+        (act0 != 1 && act0 != 2) || (d_dst1 && (dst1_gs < px32 || dst1_coff < 0 || dst1_coff % 8 || (act1 != 1 && act1 != 2))))
+        return set_error(INNFER_ERR_INVALID, "unet_post_slab_parts: null argument, C=%d (%% 32), HW=%lld, N=%d, nper=%d, a group stride below N * HW * 32, a channel offset (%% 8) or an "
+                         "activation outside 1 | 2", C, (long long)HW, N, nper);
+    const PostDst d0{(f16*)d_dst0, (long)dst0_gs, dst0_coff, act0}, d1{(f16*)d_dst1, (long)dst1_gs, dst1_coff, d_dst1 ? act1 : 0};
+    return launch_post_slab_parts((const f16*)d_src, (long)src_gs, C, (long)HW, N, d_part, nper, d_gamma, d_beta, d0, d1, (hipStream_t)stream);
+}
+
 extern "C" int innfer_unet_create(innfer_unet** out, int in_nc, int out_nc, int num_downs, int ngf) {
     return innfer_unet_create_ex(out, in_nc, out_nc, num_downs, ngf, 0, 0);
 }

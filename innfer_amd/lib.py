@@ -49,6 +49,7 @@ class ConvArgs(C.Structure):
         ("stride2_k4", C.c_int), ("transposed2x", C.c_int), ("column7", C.c_int),
         ("split", C.c_int), ("in_lo", C.c_int64), ("out_lo", C.c_int64), ("res1_lo", C.c_int64), ("res2_lo", C.c_int64),
         ("reserved0", C.c_int), ("res1_from_input", C.c_int), ("plane_rows", C.c_int),
+        ("d_stats_part", C.c_void_p), ("stats_part_floats", C.c_int64),
     ]
 
 
@@ -237,6 +238,14 @@ SIGNATURES = {
     "innfer_f32conv_plan": (C.c_int, [C.POINTER(F32ConvArgs), C.POINTER(C.c_int)]),
     "innfer_f32_norm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_float,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
+    "innfer_conv_stats_records": (C.c_int, [C.c_int, C.c_int, C.c_int]),
+    "innfer_norm_combine_parts": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "innfer_norm_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_int64, C.c_void_p]),
+    "innfer_resnet_post_slab_parts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
+    "innfer_unet_post_slab_parts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
 }
 
 # INNFER_ABI_ANY=1 (measurement only: scripts/evidence_r5.sh A/Bs an OLDER build of the library against the current one on one box): bind the entry points that
@@ -256,7 +265,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 lib = _lib
 
-ABI_VERSION = 119          # the header revision this binding was written against (INNFER_ABI_VERSION)
+ABI_VERSION = 120          # the header revision this binding was written against (INNFER_ABI_VERSION)
 if _lib.innfer_version() != ABI_VERSION and not _ABI_ANY:
     raise ImportError(f"{LIB_PATH} speaks ABI {_lib.innfer_version()}, this binding {ABI_VERSION}: rebuild with `make`")
 
