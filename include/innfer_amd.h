@@ -45,8 +45,8 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  innfer_version() returns the library's; a binding should compare. */
-#define INNFER_ABI_VERSION 120
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  innfer_version() returns the library's; a binding should compare. */
+#define INNFER_ABI_VERSION 121
 int innfer_version(void);
 const char* innfer_last_error(void);
 
@@ -419,6 +419,27 @@ typedef struct {
                                            2 rows.  The 64-channel slab kernels without activation / residual: plain 3x3 (K % 64 == 0, any K), stride2_k4, transposed2x
                                            (lane-contiguous panels), column7 with K = 64; anything else is INNFER_ERR_UNSUPPORTED.  Merged by innfer_norm_combine_parts. (120) */
     int64_t stats_part_floats;          /* floats behind d_stats_part: at least N * records * K * 3, else INNFER_ERR_WORKSPACE (nothing is launched) (120) */
+    /* (121) The remaining forms of the kernel as single launches, for tests.  Zero keeps the behaviour of 120.  None of them combines with column7 / stride2_k4 /
+     * transposed2x / pixel_shuffle2 / dilation / dilation_groups / d_stats_part (INNFER_ERR_UNSUPPORTED); which other combinations exist is the launcher's decision
+     * and its message (csrc/conv3x3.hip conv_launch). */
+    int conv1x1;                        /* != 0: 1x1 conv; d_packed from innfer_pack_conv1x1() (with split: innfer_pack_conv1x1_split()); slab outputs, K in {32, 64};
+                                           act 0 / 1 / 2 / 4 / 5, residuals, out_ch_off */
+    int prefix_lrelu;                   /* != 0 (with conv1x1, K = 64): the operand of input group g is fp16(LeakyReLU(0.2)(group 0 + .. + group g)), the sums running
+                                           in fp32 over the stored fp16 values (PPON's c2) */
+    const void* d_gate_packed;          /* != NULL: the self gate (PAN's pixel attention behind an up-conv) -- out = act(v * sigmoid(Wg v + bg)), v = fp16(conv + bias):
+                                           d_gate_packed from innfer_pack_selfgate() (Wg [32][32]), d_gate_bias 32 floats; K = 32, slab output, act 0 / 1 / 2 applied
+                                           AFTER the gate, upsample2x allowed, no residuals */
+    const float* d_gate_bias;
+    int in_relu;                        /* != 0: the operand is max(stored input, 0) -- the planar kernel of <= 16 channels only (the UNet's outermost transposed conv) */
+    int conv7x7;                        /* != 0: nn.Conv2d(C, K, 7, padding=3), zero padding or reflect_pad; d_packed from innfer_pack_conv7x7(); out_planar, K <= 16 */
+    int out_planar;                     /* 1 / 2: d_out is the planar [N][K][H][W] tensor in fp16 / fp32 instead of a slab (the networks' last convs): any K <= 64
+                                           (d_bias padded with zeros to a multiple of 64 floats), act 0 / 1 / 2 / 3 tanh / 6 sigmoid, out_ch_off 0, no residuals.
+                                           3: d_out is the uint8 [N][H][W][K] image tensor2np makes of that result (K <= 4; BGR / BGRA byte order for K = 3 / 4) */
+    int out_denorm, out_round16;        /* out_planar 3: (v + 1) / 2 before the quantisation; v rounded to fp16 first */
+    int planar_phases;                  /* != 0 (out_planar 1 / 2): K = the channels of a ConvTranspose2d(C, K, 4, 2, 1) written as ONE 3x3 conv of 4 K channels over the
+                                           H x W INPUT grid, channel (2 a + b) K + c = output pixel (2 y + a, 2 x + b) of channel c; d_out is [N][K][2H][2W]; d_packed from
+                                           innfer_pack_conv3x3(4 K, C) over those 3x3 weights, d_bias the K biases four times; act 0 / 3 (the networks: 4 K <= 16) */
+    int outm;                           /* out_planar with K <= 16: 1 (tanh + 1) / 2, 2 tanh, 3 sigmoid, 4 clamp(0, 1), applied after act */
 } innfer_conv_args;
 
 size_t innfer_conv3x3_packed_bytes(int K, int C);
@@ -436,6 +457,17 @@ size_t innfer_conv4x4s2_packed_bytes(int K, int C);
 int innfer_pack_conv4x4s2(const float* h_weight_oihw, int K, int C, void* h_packed);
 size_t innfer_convt2x_packed_bytes(int K, int C);
 int innfer_pack_convt2x(const float* h_weight_iohw, int K, int C, int k, void* h_packed);
+/* (121) Panels of the forms above.  1x1: h_weight [K][C]; innfer_conv1x1_packed_bytes(K, C) bytes, the split form three times that.  Self gate: h_weight [32][32]
+ * (out, in), 2048 bytes.  7x7: h_weight [K][C][7][7].  innfer_pack_up2x_phases: nearest-2x + 3x3 conv (h_weight [K][C][3][3], K % 64 == 0) as the four 2x2-tap phases of a
+ * transposed conv, the taps that meet the same source pixel summed in fp32 and rounded to fp16 ONCE -- innfer_convt2x_packed_bytes(K, C) bytes that run through
+ * transposed2x = 4 with the same plane_rows (d_in the [N,H,W,C] slab, d_out the [N,2H,2W,K] slab, d_bias the K biases four times). */
+size_t innfer_conv1x1_packed_bytes(int K, int C);
+int innfer_pack_conv1x1(const float* h_weight_oi, int K, int C, void* h_packed);
+int innfer_pack_conv1x1_split(const float* h_weight_oi, int K, int C, void* h_packed);
+int innfer_pack_selfgate(const float* h_weight_32x32, void* h_packed_2k);
+size_t innfer_conv7x7_packed_bytes(int K, int C);
+int innfer_pack_conv7x7(const float* h_weight_oihw, int K, int C, void* h_packed);
+int innfer_pack_up2x_phases(const float* h_weight_oihw, int K, int C, int plane_rows, void* h_packed);
 int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream);
 /* Panels of the split form: 3 * innfer_conv3x3_packed_bytes(K, C) bytes ((w - wh) * 2^11 | wh | wh, in the order the kernel's virtual chunks meet them).  (106) */
 int innfer_pack_conv3x3_split(const float* h_weight_oihw, int K, int C, void* h_packed);

@@ -1115,6 +1115,35 @@ extern "C" int innfer_pack_convt2x(const float* w, int K, int C, int k, void* pa
     return INNFER_OK;
 }
 
+// (121) the panels of the forms innfer_conv_args reaches since then
+extern "C" size_t innfer_conv1x1_packed_bytes(int K, int C) { return (K > 0 && C > 0 && C % 32 == 0) ? conv_packed_bytes_taps(K, C, 0x10) : 0; }
+extern "C" int innfer_pack_conv1x1(const float* w, int K, int C, void* packed) {
+    if (!w || !packed || K <= 0 || C <= 0 || C % 32) return set_error(INNFER_ERR_INVALID, "pack_conv1x1: K=%d C=%d (%% 32)", K, C);
+    conv_pack_1x1(w, K, C, packed);
+    return INNFER_OK;
+}
+extern "C" int innfer_pack_conv1x1_split(const float* w, int K, int C, void* packed) {
+    if (!w || !packed || K <= 0 || C <= 0 || C % 32) return set_error(INNFER_ERR_INVALID, "pack_conv1x1_split: K=%d C=%d (%% 32)", K, C);
+    conv_pack_1x1_split(w, K, C, packed);
+    return INNFER_OK;
+}
+extern "C" int innfer_pack_selfgate(const float* w32x32, void* packed_2k) {
+    if (!w32x32 || !packed_2k) return set_error(INNFER_ERR_INVALID, "pack_selfgate: null argument");
+    conv_pack_selfgate(w32x32, packed_2k);
+    return INNFER_OK;
+}
+extern "C" size_t innfer_conv7x7_packed_bytes(int K, int C) { return (K > 0 && C > 0 && C % 32 == 0) ? conv_packed_bytes7x7(K, C) : 0; }
+extern "C" int innfer_pack_conv7x7(const float* w, int K, int C, void* packed) {
+    if (!w || !packed || K <= 0 || C <= 0 || C % 32) return set_error(INNFER_ERR_INVALID, "pack_conv7x7: K=%d C=%d (%% 32)", K, C);
+    conv_pack7x7(w, K, C, packed);
+    return INNFER_OK;
+}
+extern "C" int innfer_pack_up2x_phases(const float* w, int K, int C, int plane_rows, void* packed) {
+    if (!w || !packed || K <= 0 || K % 64 || C <= 0 || C % 32) return set_error(INNFER_ERR_INVALID, "pack_up2x_phases: K=%d (%% 64) C=%d (%% 32)", K, C);
+    conv_pack_up2x_phases(w, K, C, packed, plane_rows ? 1 : 0);
+    return INNFER_OK;
+}
+
 // innfer_conv_args.d_stats_part -> ConvLaunch.stats_part, behind the size check (conv_launch decides which forms take statistics)
 static int conv_args_stats(const innfer_conv_args* a, int phases, ConvLaunch& L) {
     if (!a->d_stats_part) return INNFER_OK;
@@ -1152,6 +1181,18 @@ extern "C" int innfer_norm_stats(const void* d_src, int slab, int64_t gs, int cp
 
 extern "C" int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream) {
     if (!a || !a->d_in || !a->d_packed || !a->d_bias || !a->d_out) return set_error(INNFER_ERR_INVALID, "conv3x3: null argument");
+    // (121) the fields that reach the remaining forms of the kernel: mapped onto ConvLaunch below, conv_launch decides what is built
+    const bool forms121 = a->conv1x1 || a->prefix_lrelu || a->d_gate_packed || a->d_gate_bias || a->in_relu || a->conv7x7 || a->out_planar || a->out_denorm || a->out_round16 ||
+                          a->planar_phases || a->outm;
+    if (forms121 && (a->column7 || a->stride2_k4 || a->transposed2x || a->pixel_shuffle2 || a->dilation > 1 || a->dilation_groups || a->d_stats_part))
+        return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: conv1x1 / prefix_lrelu / the self gate / in_relu / conv7x7 / out_planar / planar_phases / outm do not combine with "
+                                                 "column7 / stride2_k4 / transposed2x / pixel_shuffle2 / dilation / d_stats_part");
+    if ((a->act == 3 || a->act == 6) && !a->out_planar) return set_error(INNFER_ERR_INVALID, "conv3x3: act %d (tanh / sigmoid) is an activation of planar outputs (out_planar)", a->act);
+    if (a->out_planar < 0 || a->out_planar > 3 || (!a->out_planar && (a->out_denorm || a->out_round16 || a->planar_phases)) || ((a->out_denorm || a->out_round16) && a->out_planar != 3))
+        return set_error(INNFER_ERR_INVALID, "conv3x3: out_planar=%d (0..3); planar_phases needs out_planar, out_denorm / out_round16 the uint8 image (3)", a->out_planar);
+    if (a->prefix_lrelu && !a->conv1x1) return set_error(INNFER_ERR_INVALID, "conv3x3: prefix_lrelu is an operand form of conv1x1");
+    if ((a->d_gate_packed != nullptr) != (a->d_gate_bias != nullptr)) return set_error(INNFER_ERR_INVALID, "conv3x3: the self gate takes d_gate_packed and d_gate_bias");
+    if (a->conv7x7 && !a->out_planar) return set_error(INNFER_ERR_UNSUPPORTED, "conv7x7: planar output (out_planar) with K <= 16 only");
     if (a->column7) {
         if (a->K <= 0 || a->K % 32 || a->K > 64 || a->out_ch_off || a->row_begin || a->row_end || a->dilation > 1 || a->dilation_groups || a->pixel_shuffle2 ||
             a->upsample2x || a->d_res1 || a->d_res2 || a->stride2_k4 || a->transposed2x || a->act < 0 || a->act > 2)
@@ -1180,7 +1221,11 @@ extern "C" int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream) {
         if (int rc = conv_args_stats(a, a->stride2_k4 ? 1 : 4, L)) return rc;
         return conv_launch(L, (hipStream_t)stream);
     }
-    if (a->pixel_shuffle2) {
+    const int Kl = a->planar_phases ? 4 * a->K : a->K;           // planar_phases: the launch's channels are the four phases of K
+    if (a->out_planar) {
+        if (a->K <= 0 || a->K > 64 || Kl > 64 || a->out_ch_off)
+            return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: a planar output holds 1 .. 64 channels (K=%d%s) at out_ch_off 0", a->K, a->planar_phases ? ", four phases each" : "");
+    } else if (a->pixel_shuffle2) {
         if (a->K <= 0 || a->K % 64 || a->out_ch_off || a->row_begin || a->row_end || a->dilation > 1 || a->dilation_groups || a->reflect_pad || a->act < 0 || a->act > 2)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the PixelShuffle(2) store needs K %% 64 == 0 (K=%d), out_ch_off 0, act 0..2, all rows, plain zero padding", a->K);
     } else if (a->dilation_groups > 0 ? a->K != 32 * a->dilation_groups : (a->K <= 0 || a->K % 16 || (a->K > 64 && !(a->d_stats_part && a->K % 64 == 0))))
@@ -1202,8 +1247,16 @@ extern "C" int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream) {
     if (a->pixel_shuffle2 && a->plane_rows == 2) L.rowp = 2;          // phase-major panels + bias from innfer_pack_conv3x3_shuffle2: the producer / consumer kernel's store
     else if (a->pixel_shuffle2 && a->plane_rows) return set_error(INNFER_ERR_INVALID, "conv3x3: pixel_shuffle2 takes plane_rows 0 (innfer_pack_conv3x3 panels) or 2 (innfer_pack_conv3x3_shuffle2 panels)");
     if (a->reserved0) return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: innfer_conv_args.reserved0 (the row-Winograd experiment until ABI 111) must be 0");
+    L.conv1x1 = a->conv1x1 ? 1 : 0; L.prefix_lrelu = a->prefix_lrelu ? 1 : 0; L.in_relu = a->in_relu ? 1 : 0; L.conv7 = a->conv7x7 ? 1 : 0;
+    L.gate_w = (const f16*)a->d_gate_packed; L.gate_bias = a->d_gate_bias;
+    L.outm = a->outm;
+    if (a->out_planar) {               // d_out is the planar tensor / the uint8 image
+        L.out = a->d_out; L.out_coff = 0; L.K = Kl; L.out_mode = OUT_NCHW;
+        L.out_f32 = a->out_planar == 2; L.out_u8 = a->out_planar == 3; L.out_denorm = a->out_denorm ? 1 : 0; L.out_round16 = a->out_round16 ? 1 : 0;
+        L.phase_c = a->planar_phases ? a->K : 0;
+    }
     if (a->split) {
-        if (a->pixel_shuffle2 || a->K % 32 || a->in_lo <= 0 || a->out_lo <= 0 || (a->d_res1 && a->res1_lo <= 0) || (a->d_res2 && a->res2_lo <= 0))
+        if (a->pixel_shuffle2 || (!a->out_planar && (a->K % 32 || a->out_lo <= 0)) || a->in_lo <= 0 || (a->d_res1 && a->res1_lo <= 0) || (a->d_res2 && a->res2_lo <= 0))
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3 (split): K in {32, 64} (K=%d), slab output, the lo distances of every tensor given", a->K);
         L.split = 1; L.in_lo = a->in_lo; L.out_lo = a->out_lo; L.res1_lo = a->res1_lo; L.res2_lo = a->res2_lo;
     }

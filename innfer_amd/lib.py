@@ -50,6 +50,9 @@ class ConvArgs(C.Structure):
         ("split", C.c_int), ("in_lo", C.c_int64), ("out_lo", C.c_int64), ("res1_lo", C.c_int64), ("res2_lo", C.c_int64),
         ("reserved0", C.c_int), ("res1_from_input", C.c_int), ("plane_rows", C.c_int),
         ("d_stats_part", C.c_void_p), ("stats_part_floats", C.c_int64),
+        ("conv1x1", C.c_int), ("prefix_lrelu", C.c_int), ("d_gate_packed", C.c_void_p), ("d_gate_bias", C.c_void_p),
+        ("in_relu", C.c_int), ("conv7x7", C.c_int), ("out_planar", C.c_int), ("out_denorm", C.c_int), ("out_round16", C.c_int),
+        ("planar_phases", C.c_int), ("outm", C.c_int),
     ]
 
 
@@ -171,6 +174,13 @@ SIGNATURES = {
     "innfer_pack_conv3x3_shuffle2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "innfer_pack_convt2x_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "innfer_conv3x3_f16": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
+    "innfer_conv1x1_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "innfer_pack_conv1x1": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "innfer_pack_conv1x1_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "innfer_pack_selfgate": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "innfer_conv7x7_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "innfer_pack_conv7x7": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "innfer_pack_up2x_phases": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "innfer_filter2d": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "innfer_conv7x1_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "innfer_pack_conv7x1": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -265,7 +275,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 lib = _lib
 
-ABI_VERSION = 120          # the header revision this binding was written against (INNFER_ABI_VERSION)
+ABI_VERSION = 121          # the header revision this binding was written against (INNFER_ABI_VERSION)
 if _lib.innfer_version() != ABI_VERSION and not _ABI_ANY:
     raise ImportError(f"{LIB_PATH} speaks ABI {_lib.innfer_version()}, this binding {ABI_VERSION}: rebuild with `make`")
 

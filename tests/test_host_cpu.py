@@ -534,3 +534,64 @@ def test_scpa_panel_layout_is_bank_conflict_free():
                     s = (tap * K_TAP + a) % 16
                     assert s not in slots, (f.__name__, g, tap, a, slots[s])
                     slots[s] = a
+
+
+# ------------------------------------------------------------------ ABI 121: the single-conv test hooks
+def _header_conv_args_fields():
+    """(name, ctypes type) of every field of innfer_conv_args, in order, read from the header the library was compiled against."""
+    hdr = open(os.path.join(REPO, "include", "innfer_amd.h")).read()
+    body = re.search(r"typedef struct \{((?:(?!typedef struct).)*?)\} innfer_conv_args;", hdr, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    types = {"int": C.c_int, "float": C.c_float, "int64_t": C.c_int64}
+    out = []
+    for decl in body.split(";"):
+        decl = " ".join(decl.split())
+        if not decl:
+            continue
+        m = re.fullmatch(r"(const )?(void|float|int|int64_t)(\*)? (.+)", decl)
+        assert m, decl
+        for name in m.group(4).split(","):
+            out.append((name.strip(), C.c_void_p if m.group(3) else types[m.group(2)]))
+    return out
+
+
+def test_conv_args_layout_and_new_packer_sizes():
+    """The binding's ConvArgs is the header's innfer_conv_args field for field (names, order, C types: so offsets and size agree with what the library was compiled
+    against), the library reads the struct's LAST field where the binding puts it, and the packers of ABI 121 size their panels as conv_packed_bytes_taps /
+    conv_packed_bytes7x7 do (a 1x1 panel is one tap of nine; a 7x7 panel is the 3x3 panel over 9 C virtual channels)."""
+    want = _header_conv_args_fields()
+    have = [(n, C.c_void_p if t in (C.c_void_p, C.c_char_p) else t) for n, t in L.ConvArgs._fields_]
+    assert have == want
+    mirror = type("Mirror", (C.Structure,), {"_fields_": want})
+    assert C.sizeof(L.ConvArgs()) == C.sizeof(mirror) and L.ConvArgs._fields_[-1][0] == "outm"
+    assert not any(bytes(L.ConvArgs())), "a fresh ConvArgs is all zero"
+    fake = 0x1000
+    a = L.ConvArgs(d_in=fake, d_packed=fake, d_bias=fake, d_out=fake, C=32, K=32, N=1, H=4, W=4, in_group_stride=512, out_group_stride=512)
+    a.outm = 1                              # the last field, refused on the host before any launch (the pointers are never dereferenced)
+    assert L.lib.innfer_conv3x3_f16(C.byref(a), None) == L.ERR_UNSUPPORTED and "outm" in L.last_error()
+    for K, Cc in ((32, 64), (64, 160)):
+        assert L.lib.innfer_conv1x1_packed_bytes(K, Cc) == L.lib.innfer_conv3x3_packed_bytes(K, Cc) // 9 == (K // 16) * 16 * 64 * (Cc // 32)
+    for K, Cc in ((3, 32), (16, 64)):
+        assert L.lib.innfer_conv7x7_packed_bytes(K, Cc) == L.lib.innfer_conv3x3_packed_bytes(K, 9 * Cc) == 9 * (Cc // 32) * 9 * 16 * 64
+    for K, Cc in ((64, 64), (128, 96)):     # the up-conv phases are panels of the transposed conv
+        assert L.lib.innfer_convt2x_packed_bytes(K, Cc) == L.lib.innfer_conv3x3_packed_bytes(4 * K, Cc) // 9 * 4
+    assert L.lib.innfer_conv1x1_packed_bytes(32, 48) == 0 == L.lib.innfer_conv7x7_packed_bytes(3, 40)
+    w = np.zeros((64, 64, 3, 3), np.float32)
+    assert L.lib.innfer_pack_up2x_phases(w.ctypes.data, 32, 64, 0, w.ctypes.data) == L.ERR_INVALID
+    assert L.lib.innfer_pack_conv1x1(None, 32, 32, w.ctypes.data) == L.ERR_INVALID
+
+
+def test_up2x_phase_packer_sums_taps_in_float32_and_rounds_once():
+    """innfer_pack_up2x_phases == innfer_pack_convt2x of Wt, Wt[ci][co][ky][kx] = the float32 sum of the 3x3 taps that meet the same source pixel (rows / columns
+    ky <-> 3: {0}, 1: {1, 2}, 2: {0, 1}, 0: {2}): the ONE fp16 rounding is the packer's.  tests/_conv_ref.py up2x_phase_weights is that statement, used as the reference's
+    weights by the GPU test."""
+    import _conv_ref as R
+    K, Cc = 64, 64
+    w = (synth.uniform((K, Cc, 3, 3), 5, -1, 1) / np.sqrt(9 * Cc)).astype(np.float32)
+    wt = R.up2x_phase_weights(torch.from_numpy(w)).numpy()            # float32 [C][K][4][4]
+    n = L.lib.innfer_convt2x_packed_bytes(K, Cc)
+    for rows in (0, 1):
+        p1, p2 = np.zeros(n, np.uint8), np.ones(n, np.uint8)
+        L.check(L.lib.innfer_pack_up2x_phases(w.ctypes.data, K, Cc, rows, p1.ctypes.data))
+        L.check(L.lib.innfer_pack_convt2x_rows(np.ascontiguousarray(wt).ctypes.data, K, Cc, 4, rows, p2.ctypes.data))
+        assert np.array_equal(p1, p2)
