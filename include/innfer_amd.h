@@ -45,7 +45,7 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  innfer_version() returns the library's; a binding should compare. */
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  innfer_version() returns the library's; a binding should compare. */
 #define INNFER_ABI_VERSION 121
 int innfer_version(void);
 const char* innfer_last_error(void);
@@ -95,6 +95,21 @@ int innfer_srresnet_create_ex(innfer_net_t* out, int in_nc, int out_nc, int nf, 
  * act (0 none, 1 LeakyReLU(0.2), 2 ReLU), one elementwise launch in front of the conv.  Built for the first conv of an SRResNet block and LR_conv
  * (the norm in front of a block's second conv follows the first conv and is folded into its weights by the host).  All of NULL, NULL, 0 removes the map.  (105) */
 int innfer_net_set_conv_input_map(innfer_net_t net, int idx, const float* h_alpha, const float* h_shift, int act);
+
+/* BasicSR's SRVGGNetCompact (realesr-animevideov3, realesr-general-x4v3 and the community "compact" checkpoints; the reference has no such architecture):
+ *   body.0 = Conv2d(in_nc, nf, 3, 1, 1) + activation; body.2i = Conv2d(nf, nf, 3, 1, 1) + activation for i = 1 .. num_conv; body.<2 num_conv + 2> =
+ *   Conv2d(nf, out_nc scale^2, 3, 1, 1); out = PixelShuffle(scale)(body(x)) + nearest_upsample(x, scale)
+ * on the engine of innfer_net_*: innfer_net_conv_info reports the convs under the keys `body.<i>` (the last one with K = out_nc scale^2), innfer_net_set_conv loads
+ * them, innfer_net_set_conv_slope the activation behind each conv but the last, innfer_net_forward[_timed] / innfer_net_workspace_bytes / innfer_net_flops /
+ * innfer_net_set_u8_io work as for the other networks (uint8 images at either end included; band rows and the RRDBNet scheduling knobs do not apply).
+ * nf in {32, 64} (fewer features: zero-pad weights, bias and slopes), in_nc == out_nc in 1 .. 4, num_conv >= 0, scale in 1 .. 4; anything else is
+ * INNFER_ERR_UNSUPPORTED.  fp16 mode only: fp16 or uint8 input, fp16 / fp32 / uint8 output; innfer_net_set_precision(net, 1) and fp32 input are INNFER_ERR_UNSUPPORTED.
+ * Every layer is ONE launch (the activation is the conv's epilogue, act 8); the workspace holds two nf-channel slabs and the last conv's 32- / 64-channel slab.
+ * Arithmetic of the tail, per output value: fp16(float(fp16 conv value) + float(fp16 input value)) -- torch's half `out += base` -- then float() or tensor2np. */
+int innfer_compact_create(innfer_net_t* out, int in_nc, int out_nc, int nf, int num_conv, int scale);
+/* The activation behind conv `idx` as K host floats: y = x >= 0 ? x : h_slope[c] * x -- nn.PReLU(num_parameters = K).weight, or the constant 0 (ReLU) / 0.1
+ * (LeakyReLU(0.1)).  Load time, synchronous.  Every conv of an SRVGGNetCompact except the last needs one before the first forward; other convs refuse it. */
+int innfer_net_set_conv_slope(innfer_net_t net, int idx, const float* h_slope);
 
 /* Arithmetic precision of innfer_net_forward, the reference's fp16 switch (`fp16 = not args.no_fp16 and gpu`, then `model.half()` / `t_img.half()`:
  * run.py:345,383,421-422).  fp32 = 0 (default): fp16 activations and weights, fp32 accumulation.  fp32 = 1: the fp32-accurate forward -- every activation
@@ -469,6 +484,17 @@ size_t innfer_conv7x7_packed_bytes(int K, int C);
 int innfer_pack_conv7x7(const float* h_weight_oihw, int K, int C, void* h_packed);
 int innfer_pack_up2x_phases(const float* h_weight_oihw, int K, int C, int plane_rows, void* h_packed);
 int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream);
+/* The same launch with the per-channel slope activation: a->act = 8 computes f >= 0 ? f : d_slope[c] * f (nn.PReLU; d_slope: device floats padded like d_bias and
+ * indexed by the same channel, whatever plane_rows / out_ch_off).  Built as the epilogue of the plain 3x3 slab convs with K = 64 (plane_rows 0 / 1) and K = 32, row
+ * ranges and batches included; every other form (split, d_stats_part, the self gate, conv1x1, out_planar, the stride-2 / phase / column / dilated forms, residuals,
+ * upsample2x, reflect_pad) answers INNFER_ERR_UNSUPPORTED and act 8 without d_slope -- innfer_conv3x3_f16 included -- INNFER_ERR_INVALID; nothing is launched. */
+int innfer_conv3x3_f16_slope(const innfer_conv_args* a, const float* d_slope, void* stream);
+/* SRVGGNetCompact's tail as a single launch (for tests): d_out = PixelShuffle(scale)(slab) + nearest_upsample(base, scale).  d_slab: fp16 blocked slab of N x H x W
+ * pixels whose first C scale^2 channels are the conv result (channel c s^2 + a s + b -> output channel c at (s y + a, s x + b)); d_base: planar fp16 [N][C][H][W]
+ * (INNFER_F16) or N uint8 HWC BGR(A) images (INNFER_U8: np2tensor with `normalize`, rounded to fp16); d_out: planar fp16 / fp32 [N][C][sH][sW], or N uint8 HWC BGR(A)
+ * images (tensor2np of the fp16 result, denormalize = `normalize`).  r = fp16(float(slab) + float(base)): one fp32 add, one rounding.  C 1 .. 4, scale 1 .. 4. */
+int innfer_shuffle_add(const void* d_slab, int64_t group_stride, const void* d_base, int base_dtype, int normalize, void* d_out, int out_dtype,
+                       int N, int C, int H, int W, int scale, void* stream);
 /* Panels of the split form: 3 * innfer_conv3x3_packed_bytes(K, C) bytes ((w - wh) * 2^11 | wh | wh, in the order the kernel's virtual chunks meet them).  (106) */
 int innfer_pack_conv3x3_split(const float* h_weight_oihw, int K, int C, void* h_packed);
 

@@ -27,6 +27,8 @@ def get_network(opt_net):
         from .RRDBNet_arch import MRRDBNet as net
     elif kind == 'realesrgan_net':
         from .RRDBNet_arch import RealESRGANNet as net
+    elif kind == 'compact_net':
+        from .SRVGG_arch import SRVGGNetCompact as net
     else:
         raise NotImplementedError('Model [{:s}] not recognized'.format(kind))
     return net(**opt_net)

@@ -128,6 +128,24 @@ def realesrgan_shapes(num_in_ch=3, num_out_ch=3, scale=4, num_feat=64, num_block
     return s
 
 
+def compact_shapes(num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=4, act_type='prelu'):
+    """State-dict key -> shape of BasicSR's SRVGGNetCompact (realesr-animevideov3, realesr-general-x4v3, the "compact" community models): `body`, a ModuleList
+    of 2 num_conv + 3 entries -- body.0 the first conv, body.2i (i = 1 .. num_conv) the nf -> nf convs, each followed by its activation at the next index
+    (a PReLU(num_feat) carries `weight` [num_feat]; ReLU / LeakyReLU carry nothing), body.<2 num_conv + 2> the last conv to num_out_ch * upscale^2 channels."""
+    s = {}
+    cin = num_in_ch
+    for i in range(num_conv + 1):
+        s[f"body.{2 * i}.weight"] = (num_feat, cin, 3, 3)
+        s[f"body.{2 * i}.bias"] = (num_feat,)
+        if act_type == 'prelu':
+            s[f"body.{2 * i + 1}.weight"] = (num_feat,)
+        cin = num_feat
+    last = 2 * num_conv + 2
+    s[f"body.{last}.weight"] = (num_out_ch * upscale * upscale, num_feat, 3, 3)
+    s[f"body.{last}.bias"] = (num_out_ch * upscale * upscale,)
+    return s
+
+
 def srresnet_layout(nb, norm=False, mode='CNA'):
     """Positions of a ResNetBlock's / LR_conv's layers inside the flattened Sequentials (SRResNet_arch.py:23-27,68-86; block.py:242-254,
     B.sequential flattens nested Sequentials): {engine key -> (conv key, BatchNorm in front of the conv or None, BatchNorm behind it or None)}.

@@ -67,7 +67,7 @@ struct ConvLaunch {
     int out_coff;                                 // channel offset inside that group (0 or 16)
     int K;                                        // valid output channels
     int N, H, W;                                  // conv (output) size
-    int act; int up;                              // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 3 tanh (OUT_NCHW only) / 4, 5 res1 * sigmoid(conv) with / without LeakyReLU (slab) / 6 sigmoid (OUT_NCHW only) / 7 pair gate: 64 rows -> 32 outputs, row 16 lg + r (r < 8) times sigmoid(row 16 lg + r + 8) (slab, PAN's PAConv); up: input read through nearest 2x
+    int act; int up;                              // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 8 per-channel slope (`slope`) / 3 tanh (OUT_NCHW only) / 4, 5 res1 * sigmoid(conv) with / without LeakyReLU (slab) / 6 sigmoid (OUT_NCHW only) / 7 pair gate: 64 rows -> 32 outputs, row 16 lg + r (r < 8) times sigmoid(row 16 lg + r + 8) (slab, PAN's PAConv); up: input read through nearest 2x
     const f16* res1; long res1_gstride; float s1;
     const f16* res2; long res2_gstride; float s2;
     int y0, y1;                                   // output rows [y0,y1)
@@ -107,6 +107,8 @@ struct ConvLaunch {
                                                   // <= 16-output kernel: the UNet stores a skip tensor once (LeakyReLU form) and its up conv reads relu(cat) from it
     const f16* gate_w; const float* gate_bias;    // != nullptr (32-output slab convs): out = act(v * sigmoid(W v + b)) with v = fp16(conv + bias) -- PAN's pixel attention behind an up-conv
                                                   // as this conv's epilogue; panels from conv_pack_selfgate (2 KB), 32 biases; `act` is the activation AFTER the gate
+    const float* slope;                           // act 8: per-channel slopes, f >= 0 ? f : slope[c] * f (nn.PReLU; constant vectors: ReLU, LeakyReLU(a)) -- device floats padded and indexed like
+                                                  // `bias`.  Built as the epilogue of the plain 3x3 slab convs of 64 (rowp 0 / 1) and 32 outputs (conv3x3_pc PRELU); every other form refuses act 8
     int res1_lds;                                 // 1: when res1 is the conv's own input (groups 0, 1: the dense block's x5 * 0.2 + x), act 0 and K = 64, take it from the staged LDS tiles
                                                   // (conv3x3_pc RLDS: chunk order 2, 3, .., 0, 1; the residual enters the fp32 accumulators as x / s1) instead of re-reading it in the epilogue
 };
@@ -151,8 +153,9 @@ struct FirstConvLaunch {
     const float* w;                               // [Cin*9][K] fp32 (k-major), device
     const float* bias;
     f16* out; long out_gstride; f16* out2; long out2_gstride;
-    int K; int N, H, W; int act;
+    int K; int N, H, W; int act;                  // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 8 per-channel slope (`slope`)
     long out_lo, out2_lo;                         // != 0: split output (ConvLaunch.split): the lo part of every value goes this many elements behind its hi part
+    const float* slope;                           // act 8: K device floats, f >= 0 ? f : slope[c] * f (ConvLaunch.slope); fp16 outputs only (no split output)
 };
 int first_conv_launch(const FirstConvLaunch& L, hipStream_t s);
 
@@ -170,6 +173,16 @@ struct FirstUnshuffleLaunch {
 size_t first_unshuffle_packed_bytes(int K, int r);
 void first_unshuffle_pack(const float* w_oihw, int K, int r, void* packed);   // host; w [K][3 r^2][3][3]
 int first_unshuffle_launch(const FirstUnshuffleLaunch& L, hipStream_t s);
+
+// ---- PixelShuffle(s) of a conv slab + the nearest-upsampled network input: SRVGGNetCompact's tail (shuffle_add.hip) ----
+struct ShuffleAddLaunch {
+    const f16* slab; long gstride;                // the last conv's result on the LR grid: C s^2 valid channels (channel c s^2 + a s + b -> output channel c at (s y + a, s x + b))
+    const void* base; int base_u8, base_norm;     // the network's input: planar fp16 [N][C][H][W], or the uint8 HWC BGR(A) image as the first conv reads it in the fp16 mode (FirstConvLaunch.in_u8, in_norm, in_round16 = 1)
+    void* out; int out_mode;                      // 0 fp16 / 1 fp32 planar [N][C][sH][sW]; 2 the uint8 HWC BGR(A) image (tensor2np as the store: out_denorm, as ConvLaunch.out_u8 with out_round16)
+    int out_denorm;
+    int C, s, N, H, W;                            // C 1..4, s 1..4; H x W: the LR grid
+};
+int shuffle_add_launch(const ShuffleAddLaunch& L, hipStream_t s);
 
 // ---- layout / tiles / blend / pre-post (tiles.hip) ---------------------------
 int nchw_to_slab(const void* src, int src_f32, f16* slab, long gstride, int ch_off, int N, int C, int H, int W, hipStream_t s);

@@ -555,7 +555,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     constexpr bool UP4 = (TMF & 0x200000) != 0;
     // + 0x400000 (ROWP): the plane row order of the 64-channel groups (see toff_slab): plain 3x3 slab convs (canvas, RLDS, FUSE forms included) and the one-pass up-conv
     constexpr bool ROWP = (TMF & 0x400000) != 0;
-    static_assert(!ROWP || (RPW == 2 && NT == 4 && NCW == 8 && OUTMODE == OUT_SLAB && (TMF & 0x1FF) == 0x1FF && (TMF & ~0xE601FF) == 0 && !S9 && !POLY), "plane row order: the 64-channel slab kernels");
+    static_assert(!ROWP || (RPW == 2 && NT == 4 && NCW == 8 && OUTMODE == OUT_SLAB && (TMF & 0x1FF) == 0x1FF && (TMF & ~0x1E601FF) == 0 && !S9 && !POLY), "plane row order: the 64-channel slab kernels");
     // + 0x800000 (PSH): nn.PixelShuffle(2) as the store of a conv nf -> 4 nf (pixelshuffle_block, block.py:333-346; SRResNet's up stages, RRDBNet(upsample_mode=
     // 'pixelshuffle')) on THIS kernel -- until round 4 those launches ran on the two-workgroup kernel of round 1 (0.30 of the MFMA peak, a third of an SRResNet frame).
     // The panels are phase-major (conv_pack_shuffle2) in the plane row order, so a channel group is one output phase of 64 channels and the epilogue is the
@@ -564,6 +564,13 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     static_assert(!PSH || (ROWP && (TMF & ~0xC001FF) == 0 && NSI == 2 && !CV), "pixel-shuffle store: the plain 64-channel plane-order instantiation");
     static_assert(!UP4 || (RPW == 2 && NT == 4 && NCW == 8 && NSI == 3 && OUTMODE == OUT_SLAB && (TMF & 0x1FFFFF) == 0x1FF && !S9 && !POLY && !CV), "one-pass phases: the 64-channel slab kernel on three input slots");
     constexpr bool FUSE = (TMF & 0x20000) != 0;
+    // + 0x1000000 (PRELU): ConvLaunch.act 8 -- f >= 0 ? f : slope[c] * f with a per-channel slope vector (nn.PReLU(num_parameters = K); constant vectors serve ReLU and
+    // LeakyReLU(a)) as the slab epilogue of the plain nine-tap kernels: the chain of 64 -> 64 convs of BasicSR's SRVGGNetCompact, one launch per layer.  The slopes are
+    // NOT kept in registers beside the bias (sixteen more live registers across the MFMA loop spill the 64-output kernel): every consumer wave parks the launch's one
+    // channel group of slopes (K = 16 NT) in 256 bytes of its own behind the two stages and reads its lane's values back at each tile's end -- same-wave LDS traffic,
+    // in order, no barrier.  Instantiations of their own: the other kernels' code does not change.
+    constexpr bool PRELU = (TMF & 0x1000000) != 0;
+    static_assert(!PRELU || (OUTMODE == OUT_SLAB && (NT == 4 || NT == 2) && NCW == 8 && NSI == 2 && (TMF & ~0x14001FF) == 0 && (TMF & 0x1FF) == 0x1FF && !S9 && !POLY && !CV), "PReLU epilogue: the plain 64- / 32-output slab kernels");
     static_assert(!FUSE || (RPW == 2 && (NT == 4 || (NT == 2 && !ROWP)) && NCW == 8 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & 0x1FFFF) == 0x1FF && !S9 && !POLY && !CV), "the fused last conv: the plain 64-channel instantiation (and the 32-channel one on 16-row tiles)");
     constexpr int TH = NCW * RPW;
     constexpr int LH = TH + 2;
@@ -740,6 +747,8 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
 #include "conv3x3_pc_up4.inc"
     int islot = 0;                                                // NSI == 3: g % 3
     f32x4 bias_r[NT];
+    [[maybe_unused]] float* slope_lds = (float*)(smem + 2 * STAGE) + cw * 64;
+    if constexpr (PRELU) { if (lane < WROWS) slope_lds[lane] = p.slope[lane]; }
     int bias_kg = -1;
     f32x4 acc[NT][MT];
     float pfx[PFX ? MT : 1][8];          // (cleared after a tile's last chunk, in front of its epilogue: live sums there would cost the epilogue's registers)
@@ -996,7 +1005,7 @@ int canvas_grid(const KP& k, int N, int* gy, long* tiles) {
 template <int RPW, int NT, int NLW, int OUTMODE, bool S9, bool POLY, int TM, bool CV, int NSI, int NCW>
 int launch_pc(const KP& kp, int N, hipStream_t s) {
     constexpr int TH = NCW * RPW;
-    constexpr int LDS = NSI * ((((TH + 2) * LWP + 15) / 16) * 1024) + 2 * (((TM & 0x200000) ? 4 : __builtin_popcount(TM & 0x1FF)) * NT * 16 * 64) + ((TM & 0x20000) ? 4096 : 0) + ((TM & 0x200000) ? 1024 : 0);      // (UP4: + the four phases' biases)
+    constexpr int LDS = NSI * ((((TH + 2) * LWP + 15) / 16) * 1024) + 2 * (((TM & 0x200000) ? 4 : __builtin_popcount(TM & 0x1FF)) * NT * 16 * 64) + ((TM & 0x20000) ? 4096 : 0) + ((TM & 0x200000) ? 1024 : 0) + ((TM & 0x1000000) ? NCW * 256 : 0);      // (UP4: + the four phases' biases; PRELU: + the slopes, once per consumer wave)
     static_assert(LDS <= 160 * 1024, "the stages must fit the CU's LDS");
     static_assert(NSI == 2 || (NSI == 3 && !S9 && !POLY), "the three-slot input ring exists for the plain and the canvas loader");
     if constexpr (OUTMODE == OUT_SLAB && !S9 && !POLY && (TM & ~0x4C2000) == 0x1FF && !CV) {      // a batch of images whose size is not a whole number of tiles
@@ -1111,7 +1120,7 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
     if (L.act == 7 && (L.out_mode != OUT_SLAB || conv_nt_for(L.K) != 4 || L.K % 64 || L.res1 || L.res2 || L.conv1x1 || L.dilation > 1 || L.dilation_groups ||
                        L.deconv_phases || L.stride2 || L.conv7v || L.stats_part))
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the pair gate is an epilogue of the plain 64-row slab conv (32 gated outputs per 64 rows)");
-    if (L.act < 0 || L.act > 7 || (L.phase_c > 0 && (L.K % L.phase_c || L.K / L.phase_c != 4)))
+    if (L.act < 0 || L.act > 8 || (L.phase_c > 0 && (L.K % L.phase_c || L.K / L.phase_c != 4)))
         return set_error(INNFER_ERR_INVALID, "conv3x3: act=%d phase_c=%d K=%d", L.act, L.phase_c, L.K);
     k.act = L.act;
     k.res1 = L.res1; k.res1_gstride = L.res1_gstride; k.s1 = L.s1;
@@ -1138,6 +1147,17 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
     const int rpw64 = INNFER_KNOB("INNFER_RPW64", 3);
     const int rpw32 = INNFER_KNOB("INNFER_RPW32", 5);
     const int pc = INNFER_KNOB("INNFER_PC", 1);     // producer / consumer kernel for slab outputs
+    if (L.act == 8) {        // per-channel slopes (PReLU): conv3x3_pc<.., TMF | 0x1000000>, the plain nine-tap slab kernels of 64 (either row order) and 32 outputs
+        if (!L.slope) return set_error(INNFER_ERR_INVALID, "conv3x3: act 8 (per-channel slope) needs the slope vector");
+        if (!pc || L.out_mode != OUT_SLAB || (nt != 4 && nt != 2) || L.K != 16 * nt || L.split || L.stats_part || L.gate_w || L.conv1x1 || L.prefix_lrelu || L.deconv_phases || L.stride2 ||
+            L.conv7v || L.conv7 || L.fuse_w || L.dilation > 1 || L.dilation_groups || L.in_relu || L.res1 || L.res2 || L.up || L.reflect || L.phase_c || L.outm || L.out_u8 ||
+            (L.rowp && (L.rowp != 1 || nt != 4 || (L.out_coff & 31))))
+            return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: act 8 (per-channel slope) is built as the epilogue of the plain 3x3 slab convs of 64 or 32 outputs -- not the split / "
+                                                     "statistics / gate / 1x1 / planar / phase / stride-2 / dilated / fused-last forms, no residual, upsampling or reflection padding");
+        k.slope = L.slope;
+        if (nt == 2) return launch_pc<3, 2, 4, OUT_SLAB, false, false, 0x10001FF>(k, L.N, s);
+        return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x14001FF>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x10001FF>(k, L.N, s);
+    }
     if (L.rowp && !(L.rowp == 2 && L.out_mode == OUT_SHUFFLE2) && (nt != 4 || !pc || L.out_mode != OUT_SLAB || L.split || L.stats_part || L.stride2 || L.conv1x1 || L.conv7 || L.conv7v || L.prefix_lrelu ||
                    L.gate_w || L.act > 2 || L.dilation > 1 || L.dilation_groups || (L.out_coff & 31)))
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the plane row order (rowp) belongs to plain 3x3 slab convs and transposed-conv phases with 64-channel output groups");

@@ -99,7 +99,7 @@ __device__ __forceinline__ void epilogue_slab_cv(const KP& p, f32x4 (&acc)[NT][2
 // 64 consecutive output channels: the DCV store without the lattice shift -- pixel (y, x) of the conv grid goes to (2y + a, 2x + b).
 template <int RPW, int NT, int ACT, bool R1, bool R2, bool HOIST, bool POLY = false, bool DCV = false, bool PAIR = false, bool SC1 = false, bool ROWP = false, bool PSH = false>
 __device__ __forceinline__ void epilogue_slab(const KP& p, f32x4 (&acc)[NT][2 * RPW], int n, int ty0, int tx0,
-                                              int wave, int li, int cbase, int dil = 1) {
+                                              int wave, int li, int cbase, int dil = 1, const f32x4* slope = nullptr) {
     constexpr int MT = 2 * RPW;
     constexpr int NTS = ACT == 7 ? NT / 2 : NT;              // ACT 7: pair gate (see epilogue_slab_cv)
     int oc0 = (ACT == 7 ? cbase >> 1 : cbase) + p.out_coff;
@@ -193,12 +193,13 @@ __device__ __forceinline__ void epilogue_slab(const KP& p, f32x4 (&acc)[NT][2 * 
                 float f = acc[t][m][j];
                 if (ACT == 7) {
                     f = f * fast_sigmoid(acc[t + NT / 2][m][j]);
-                } else if (ACT >= 4) {           // pixel-attention gate (PAN): res1 * sigmoid(conv), ACT 4: LeakyReLU(0.2) after it
+                } else if (ACT == 4 || ACT == 5) {           // pixel-attention gate (PAN): res1 * sigmoid(conv), ACT 4: LeakyReLU(0.2) after it
                     f = (float)r1[R1 ? m : 0][t][j] * (fast_sigmoid(f));
                     if (ACT == 4) f = fmaxf(f, 0.2f * f);
                 } else {
                     if (ACT == 1) f = __builtin_amdgcn_fmed3f(f, 0.2f * f, ACT_TOP);
                     else if (ACT == 2) f = __builtin_amdgcn_fmed3f(f, 0.f, ACT_TOP);
+                    else if (ACT == 8) f = f >= 0.f ? f : slope[t][j] * f;       // PReLU: slope[t] = the slopes of the channels bias_r[t] holds (conv3x3_pc PRELU)
                     if (SC1) { f = f * p.s1; FP32_VALUE(f); }          // RLDS: res1 is inside the accumulator as x / s1
                     if (R1) f = __builtin_fmaf(f, p.s1, (float)r1[R1 ? m : 0][t][j]);
                     if (R2) f = __builtin_fmaf(f, p.s2, (float)r2[R2 ? m : 0][t][j]);

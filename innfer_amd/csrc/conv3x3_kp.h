@@ -40,7 +40,11 @@ struct KP {
     float* fl_side;          //   per tile 192 x 3 partial sums of the pixels within one pixel of a tile edge (conv_fuse_combine finishes them)
     void* fl_out;            //   the planar [N, fl_oc, H, W] result
     int fl_oc, fl_out_mode;  //   0 fp16, 1 fp32 planar; 2 the uint8 HWC image (out_denorm / out_round16 as for the planar kernels)
-    const f16* sg_w; const float* sg_bias;   // SGATE kernels (TMF | 0x80000): a 1x1 conv of this conv's own fp16 result gates it -- out = v * sigmoid(W v + b): two A fragments [t][lane][8] (conv_pack_selfgate), 32 biases
+    const f16* sg_w;         // SGATE kernels (TMF | 0x80000): a 1x1 conv of this conv's own fp16 result gates it -- out = v * sigmoid(W v + b): two A fragments [t][lane][8] (conv_pack_selfgate), 32 biases
+    union {                  // (one slot: no kernel is both, and the argument block of every other instantiation keeps its layout)
+        const float* sg_bias;
+        const float* slope;  // PRELU kernels (TMF | 0x1000000): per-channel slopes of the act-8 epilogue, padded and indexed like `bias`
+    };
     float rs1;               // RLDS kernels (TMF | 0x40000): 1 / s1 -- the residual res1 (= the conv's own input groups 0, 1) is added to the accumulators as x / s1 from the live LDS stage
     long in_lo_bytes;        // SPLIT kernels (TMF | 0x2000): the low-part twin of the input slab lies this many bytes behind it,
     long out_lo, res1_lo, res2_lo;   //   those of the output / residual slabs this many ELEMENTS behind them

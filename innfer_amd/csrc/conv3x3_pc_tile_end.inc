@@ -34,6 +34,12 @@
             } else if constexpr (FUSE) {
                 const int lidf = run_start + (p.rev ? run_len - 1 - (jt - slots) : (jt - slots));         // (jt was advanced above; KG == 1: the tile index)
                 fused_last_epilogue<RPW, NT>(p, acc, smem + ((g & 1) * STAGE), smem + 2 * STAGE, n, ty0, tx0, cw, lane, lidf);
+            } else if constexpr (PRELU) {
+                // act 8 (SRVGGNetCompact): the lane's slopes come back from the wave's LDS copy (same channels as bias_r[t]; KG == 1); plain slab store, no residual
+                f32x4 slope_r[NT];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) slope_r[t] = *(const f32x4*)(slope_lds + lane_cbase<NT, ROWP>(lg) + toff_lin<NT, ROWP>(t));
+                epilogue_slab<RPW, NT, 8, false, false, true, false, false, false, false, ROWP, false>(p, acc, n, ty0, tx0, cw, li, cbase, dcur, slope_r);
             } else if constexpr (OUTMODE == OUT_SLAB) {
             if constexpr (STATS) {
                 const int lid = run_start + (p.rev ? run_len - 1 - (jt - slots) : (jt - slots));         // (jt was advanced above)

@@ -105,6 +105,9 @@ struct ConvSlot {
     float* d_bps = nullptr;
     void* d_fuse = nullptr;      // a last conv of 64 -> <= 3 channels: its panel for the epilogue of HR_conv0 (conv_pack_fuse_last), built with d_w
     float* d_b = nullptr;        // bias padded to the panel width
+    int Kp = 0;                  // SRVGGNetCompact's last conv (K = out_nc * scale^2 = 1 .. 64): the width of the zero-padded panel it runs on as a slab conv, 32 or 64
+    bool slope_ok = false;       // SRVGGNetCompact's activated convs: the conv's epilogue is act 8 with the per-channel slopes of innfer_net_set_conv_slope
+    float* d_slope = nullptr;    //   those slopes, padded with zeros like d_b
     bool loaded = false;
     // mode 'NAC' conv blocks (block.py:246-254: norm -> act -> conv): the conv reads act(alpha[c] * x + shift[c]); an elementwise pass in front of it
     bool map_ok = false;         // slot may carry an input map (first conv of an SRResNet block, LR_conv)
@@ -113,7 +116,7 @@ struct ConvSlot {
 };
 
 struct innfer_net {
-    int kind = 0;                // 0 rrdbnet, 1 srresnet
+    int kind = 0;                // 0 rrdbnet, 1 srresnet, 2 BasicSR's SRVGGNetCompact (innfer_compact_create; compact_forward)
     int in_nc = 3, out_nc = 3, nf = 64, nb = 23, gc = 32, scale = 4, n_up = 2;
     int final_act = 0;           // `finalact` of the reference constructors: activation after the last conv (ConvLaunch.act codes)
     int band_rows = 0;
@@ -254,6 +257,46 @@ extern "C" int innfer_srresnet_create_ex(innfer_net_t* out, int in_nc, int out_n
     return INNFER_OK;
 }
 
+// BasicSR's SRVGGNetCompact (realesr-animevideov3, realesr-general-x4v3, the community "compact" models): `body`, a chain of 3x3 convs on the LR grid -- body.0
+// (in_nc -> nf) and num_conv convs nf -> nf, each followed by its activation (PReLU(nf) / ReLU / LeakyReLU(0.1): per-channel slopes, innfer_net_set_conv_slope),
+// then body.<2 num_conv + 2> (nf -> out_nc scale^2, no activation); out = PixelShuffle(scale)(body(x)) + nearest_upsample(x, scale).  fp16 engine only.
+extern "C" int innfer_compact_create(innfer_net_t* out, int in_nc, int out_nc, int nf, int num_conv, int scale) {
+    if (!out) return set_error(INNFER_ERR_INVALID, "compact_create: null out");
+    if (nf != 32 && nf != 64) return set_error(INNFER_ERR_UNSUPPORTED, "compact_create: nf=%d (built: 32, 64; fewer features are zero-padded by the caller)", nf);
+    if (in_nc < 1 || in_nc > 4 || in_nc != out_nc)
+        return set_error(INNFER_ERR_UNSUPPORTED, "compact_create: in_nc=%d out_nc=%d (built: in_nc == out_nc in 1..4 -- the network adds its upsampled input to its result)", in_nc, out_nc);
+    if (num_conv < 0 || num_conv > 4096) return set_error(INNFER_ERR_UNSUPPORTED, "compact_create: num_conv=%d", num_conv);
+    if (scale < 1 || scale > 4) return set_error(INNFER_ERR_UNSUPPORTED, "compact_create: scale %d (built: 1, 2, 3, 4)", scale);
+    innfer_net* net = new innfer_net();
+    net->kind = 2; net->in_nc = in_nc; net->out_nc = out_nc; net->nf = nf; net->nb = num_conv;
+    net->gc = 0; net->scale = scale; net->n_up = 0;
+    add_conv(net, "body.0", nf, in_nc, true);
+    net->convs.back().slope_ok = true;
+    for (int i = 1; i <= num_conv; ++i) {
+        add_conv(net, "body." + std::to_string(2 * i), nf, nf);
+        net->convs.back().slope_ok = true;
+    }
+    add_conv(net, "body." + std::to_string(2 * num_conv + 2), out_nc * scale * scale, nf);
+    net->convs.back().Kp = out_nc * scale * scale <= 32 ? 32 : 64;
+    *out = net;
+    return INNFER_OK;
+}
+
+// The activation behind conv `idx` of an SRVGGNetCompact as K per-channel slopes (host floats): y = x >= 0 ? x : slope[c] * x -- nn.PReLU's weight, or the
+// constant 0 (ReLU) / 0.1 (LeakyReLU(0.1)).  Load time, synchronous, like innfer_net_set_conv.
+extern "C" int innfer_net_set_conv_slope(innfer_net_t net, int idx, const float* h_slope) {
+    if (!net || idx < 0 || idx >= (int)net->convs.size() || !h_slope) return set_error(INNFER_ERR_INVALID, "set_conv_slope: bad arguments");
+    ConvSlot& c = net->convs[idx];
+    if (!c.slope_ok) return set_error(INNFER_ERR_UNSUPPORTED, "set_conv_slope: '%s' has no per-channel activation (built: the convs of an SRVGGNetCompact except its last)", c.key.c_str());
+    const int per = 16 * conv_nt_for(c.K);
+    const size_t n = (size_t)((c.K + per - 1) / per) * per;
+    std::vector<float> h(n, 0.f);
+    for (int k = 0; k < c.K; ++k) h[k] = h_slope[k];
+    if (!c.d_slope) INNFER_HIP(hipMalloc((void**)&c.d_slope, n * sizeof(float)));
+    INNFER_HIP(hipMemcpy(c.d_slope, h.data(), n * sizeof(float), hipMemcpyHostToDevice));
+    return INNFER_OK;
+}
+
 extern "C" int innfer_net_set_outm(innfer_net_t net, int outm) {
     if (!net || outm < 0 || outm > 4) return set_error(INNFER_ERR_INVALID, "set_outm: 0 none, 1 scaltanh, 2 tanh, 3 sigmoid, 4 clamp");
     net->outm = outm;
@@ -273,6 +316,7 @@ extern "C" void innfer_net_destroy(innfer_net_t net) {
         if (c.d_bps) (void)hipFree(c.d_bps);
         if (c.d_b4) (void)hipFree(c.d_b4);
         if (c.d_map) (void)hipFree(c.d_map);
+        if (c.d_slope) (void)hipFree(c.d_slope);
     }
     delete net;
 }
@@ -325,13 +369,19 @@ extern "C" int innfer_net_set_conv(innfer_net_t net, int idx, const float* w, co
         if (c.ksize == 1) {          // [K,C,1,1]: the one-tap panel of the kernel's 1x1 instantiation
             host.resize(conv_packed_bytes_taps(c.K, c.C, 0x10));
             conv_pack_1x1(w, c.K, c.C, host.data());
+        } else if (c.Kp) {           // SRVGGNetCompact's last conv: K valid rows of a 32- / 64-output panel, the rest zero
+            std::vector<float> wp((size_t)c.Kp * c.C * 9, 0.f);
+            std::copy(w, w + (size_t)c.K * c.C * 9, wp.begin());
+            host.resize(conv_packed_bytes(c.Kp, c.C));
+            c.rowp = INNFER_ROWP_DEFAULT && c.Kp == 64;
+            conv_pack(wp.data(), c.Kp, c.C, host.data(), c.rowp);
         } else {
             host.resize(conv_packed_bytes(c.K, c.C));
             c.rowp = INNFER_ROWP_DEFAULT && c.K == 64;
             conv_pack(w, c.K, c.C, host.data(), c.rowp);
         }
-        const int per = 16 * conv_nt_for(c.K);
-        bias_n = (size_t)((c.K + per - 1) / per) * per;
+        const int per = 16 * conv_nt_for(c.Kp ? c.Kp : c.K);
+        bias_n = (size_t)(((c.Kp ? c.Kp : c.K) + per - 1) / per) * per;
         c.h_w.assign(w, w + (size_t)c.K * c.C * c.ksize * c.ksize);
         if (c.d_w32) { (void)hipFree(c.d_w32); c.d_w32 = nullptr; }
         if (c.up2x && c.ksize == 3 && c.K % 64 == 0 && c.C % 32 == 0) {
@@ -402,6 +452,7 @@ extern "C" int innfer_net_set_conv_input_map(innfer_net_t net, int idx, const fl
 // work and twice the bytes of the fp16 forward.  The reference's fp32 mode on the GPU (`-no_fp16`: run.py:345,421-422).
 extern "C" int innfer_net_set_precision(innfer_net_t net, int fp32) {
     if (!net || (fp32 != 0 && fp32 != 1)) return set_error(INNFER_ERR_INVALID, "set_precision: 0 (fp16 arithmetic) or 1 (fp32-accurate)");
+    if (fp32 && net->kind == 2) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SRVGGNetCompact is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32) {
         // The (wl | wh | wh) panels of every loaded conv are built HERE -- a load-time call, with its hipMalloc and synchronous copies -- never inside
         // innfer_net_forward (stream capture, concurrent callers).  Idempotent: a conv that already has its panels is skipped; innfer_net_set_conv
@@ -505,6 +556,15 @@ static Carve carve(const innfer_net* net, int N, int H, int W) {
     Carve c{};
     const size_t px = (size_t)N * H * W;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    if (net->kind == 2) {        // SRVGGNetCompact: the two ping-pong feature slabs (one when there is no nf -> nf conv) and the last conv's 32- / 64-channel slab
+        size_t off = 0;
+        c.slab_w = net->nf;
+        c.slab[0] = off; off += al(px * net->nf * 2);
+        c.slab[1] = off; if (net->nb > 0) off += al(px * net->nf * 2);
+        c.hr = off; off += al(px * net->convs.back().Kp * 2);
+        c.total = off;
+        return c;
+    }
     c.slab_w = net->kind == 0 ? net->nf + 4 * net->gc : net->nf;
     size_t off = 0;
     c.fea = off; off += al(px * net->nf * 2);
@@ -745,6 +805,54 @@ ConvLaunch mk_launch(const ConvSlot& cs, const f16* in, long in_g, void* out, lo
     return L;
 }
 
+// SRVGGNetCompact (kind 2): first conv -> slab A; num_conv convs ping-pong A <-> B, ONE launch each with the activation (act 8) in its epilogue; the last conv -> the tail
+// slab; shuffle_add_launch writes PixelShuffle(scale)(tail) + nearest_upsample(input) to d_out.  Whole-frame launches (band_rows is not used here).
+int compact_forward(innfer_net* net, const void* d_in, int in_dtype, void* d_out, int out_dtype, int N, int H, int W, char* ws, const Carve& cv, hipStream_t s) {
+    if (in_dtype == INNFER_F32 || net->fp32) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SRVGGNetCompact is built for the fp16 mode only: fp16 or uint8 input");
+    if (net->outm || net->final_act) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SRVGGNetCompact has no outm / final activation");
+    if (in_dtype == INNFER_U8 && !net->u8_round16) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SRVGGNetCompact is built for the fp16 mode only (innfer_net_set_u8_io fp16_mode = 1)");
+    for (auto& c : net->convs)
+        if (c.slope_ok && !c.d_slope) return set_error(INNFER_ERR_INVALID, "forward: the activation slopes of '%s' were never set (innfer_net_set_conv_slope)", c.key.c_str());
+    const long G = (long)N * H * W * 32;
+    f16* ab[2] = {(f16*)(ws + cv.slab[0]), (f16*)(ws + cv.slab[1])};
+    f16* tail = (f16*)(ws + cv.hr);
+    int ci = 0;
+    {
+        const ConvSlot& c0 = net->convs[ci++];
+        FirstConvLaunch F{};
+        F.in = d_in; F.in_f32 = 0; F.Cin = c0.C; F.w = (const float*)c0.d_w; F.bias = c0.d_b;
+        F.in_u8 = in_dtype == INNFER_U8; F.in_norm = net->u8_normalize; F.in_round16 = 1;
+        F.out = ab[0]; F.out_gstride = G;
+        F.K = net->nf; F.N = N; F.H = H; F.W = W; F.act = 8; F.slope = c0.d_slope;
+        if (int rc = do_first(F, s)) return rc;
+    }
+    int cur = 0;
+    for (int i = 0; i < net->nb; ++i) {
+        const ConvSlot& cs = net->convs[ci++];
+        ConvLaunch L = mk_launch(cs, ab[cur], G, ab[cur ^ 1], G, N, H, W, 8, 0);
+        L.slope = cs.d_slope;
+        if (int rc = do_conv(L, s)) return rc;
+        cur ^= 1;
+    }
+    const ConvSlot& cl = net->convs[ci++];
+    {
+        ConvLaunch L = mk_launch(cl, ab[cur], G, tail, G, N, H, W, 0, 0);
+        L.K = cl.Kp;
+        if (int rc = do_conv(L, s)) return rc;
+    }
+    ShuffleAddLaunch T{};
+    T.slab = tail; T.gstride = G;
+    T.base = d_in; T.base_u8 = in_dtype == INNFER_U8; T.base_norm = net->u8_normalize;
+    T.out = d_out; T.out_mode = out_dtype == INNFER_U8 ? 2 : out_dtype == INNFER_F32 ? 1 : 0; T.out_denorm = net->u8_normalize;
+    T.C = net->out_nc; T.s = net->scale; T.N = N; T.H = H; T.W = W;
+    if (int rc = timed_begin(s)) return rc;
+    if (int rc = shuffle_add_launch(T, s)) return rc;
+    if (int rc = debug_after("shuffle_add", s)) return rc;
+    const double px = (double)N * H * W, k = (double)cl.K;
+    // launch kind 6000: the tail -- one add per output value; bytes: the K valid slab channels and the input in, the result out
+    return timed_end(s, px * k, px * (k * 2.0 + net->in_nc * (T.base_u8 ? 1.0 : 2.0) + k * (T.out_mode == 2 ? 1.0 : T.out_mode == 1 ? 4.0 : 2.0)), 6000);
+}
+
 // Launch a dependent chain of same-resolution convs.  band_rows == 0: one launch per
 // layer over the whole frame.  band_rows > 0: skewed row bands -- layer l of band b
 // covers rows [b*R - l, (b+1)*R - l), so every row a layer reads from its predecessor
@@ -791,6 +899,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     if (ws_bytes < cv.total) return set_error(INNFER_ERR_WORKSPACE, "forward: workspace %zu < %zu bytes", ws_bytes, cv.total);
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)d_ws;
+    if (net->kind == 2) return compact_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     const int nf = net->nf, gc = net->gc;
     const long G = (long)N * H * W * 32;          // group stride of every LR-resolution slab
     const long LO = (long)(cv.lo / 2);            // fp32-accurate mode: elements from a slab to its lo twin (0: fp16 mode)
@@ -1179,7 +1288,25 @@ extern "C" int innfer_norm_stats(const void* d_src, int slab, int64_t gs, int cp
                 : norm::launch_stats((const float*)d_src, cpad, (long)HW, eps, d_gamma, d_beta, d_alpha, d_shift, C, N, d_part, (hipStream_t)stream);
 }
 
-extern "C" int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream) {
+static int conv3x3_f16_impl(const innfer_conv_args* a, const float* d_slope, void* stream);
+extern "C" int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream) { return conv3x3_f16_impl(a, nullptr, stream); }
+// The same launch with act = 8: f >= 0 ? f : d_slope[c] * f, d_slope padded like d_bias (for tests; the SRVGGNetCompact engine's layers)
+extern "C" int innfer_conv3x3_f16_slope(const innfer_conv_args* a, const float* d_slope, void* stream) { return conv3x3_f16_impl(a, d_slope, stream); }
+
+// PixelShuffle(scale) of a conv slab + the nearest-upsampled input, as a single launch (for tests; SRVGGNetCompact's tail, csrc/shuffle_add.hip)
+extern "C" int innfer_shuffle_add(const void* d_slab, int64_t group_stride, const void* d_base, int base_dtype, int normalize, void* d_out, int out_dtype,
+                                  int N, int C, int H, int W, int scale, void* stream) {
+    if ((base_dtype != INNFER_F16 && base_dtype != INNFER_U8) || (out_dtype != INNFER_F16 && out_dtype != INNFER_F32 && out_dtype != INNFER_U8))
+        return set_error(INNFER_ERR_UNSUPPORTED, "shuffle_add: base fp16 or uint8, result fp16, fp32 or uint8");
+    ShuffleAddLaunch T{};
+    T.slab = (const f16*)d_slab; T.gstride = group_stride;
+    T.base = d_base; T.base_u8 = base_dtype == INNFER_U8; T.base_norm = normalize != 0;
+    T.out = d_out; T.out_mode = out_dtype == INNFER_U8 ? 2 : out_dtype == INNFER_F32 ? 1 : 0; T.out_denorm = normalize != 0;
+    T.C = C; T.s = scale; T.N = N; T.H = H; T.W = W;
+    return shuffle_add_launch(T, (hipStream_t)stream);
+}
+
+static int conv3x3_f16_impl(const innfer_conv_args* a, const float* d_slope, void* stream) {
     if (!a || !a->d_in || !a->d_packed || !a->d_bias || !a->d_out) return set_error(INNFER_ERR_INVALID, "conv3x3: null argument");
     // (121) the fields that reach the remaining forms of the kernel: mapped onto ConvLaunch below, conv_launch decides what is built
     const bool forms121 = a->conv1x1 || a->prefix_lrelu || a->d_gate_packed || a->d_gate_bias || a->in_relu || a->conv7x7 || a->out_planar || a->out_denorm || a->out_round16 ||
@@ -1243,6 +1370,7 @@ extern "C" int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream) {
     L.y0 = a->row_begin; L.y1 = a->row_end > 0 ? a->row_end : a->H;
     L.out_mode = a->pixel_shuffle2 ? OUT_SHUFFLE2 : OUT_SLAB; L.reflect = a->reflect_pad; L.dilation = a->dilation; L.dilation_groups = a->dilation_groups;
     L.res1_lds = a->res1_from_input ? 2 : 0;                 // (the single-conv call: wherever the shape qualifies, one residual or two)
+    L.slope = d_slope;
     L.rowp = a->plane_rows ? 1 : 0;
     if (a->pixel_shuffle2 && a->plane_rows == 2) L.rowp = 2;          // phase-major panels + bias from innfer_pack_conv3x3_shuffle2: the producer / consumer kernel's store
     else if (a->pixel_shuffle2 && a->plane_rows) return set_error(INNFER_ERR_INVALID, "conv3x3: pixel_shuffle2 takes plane_rows 0 (innfer_pack_conv3x3 panels) or 2 (innfer_pack_conv3x3_shuffle2 panels)");

@@ -174,6 +174,10 @@ SIGNATURES = {
     "innfer_pack_conv3x3_shuffle2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "innfer_pack_convt2x_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "innfer_conv3x3_f16": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
+    "innfer_conv3x3_f16_slope": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p, C.c_void_p]),
+    "innfer_shuffle_add": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 5 + [C.c_void_p]),
+    "innfer_compact_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 5),
+    "innfer_net_set_conv_slope": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_conv1x1_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "innfer_pack_conv1x1": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "innfer_pack_conv1x1_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

@@ -24,6 +24,7 @@ _SNIFF = (
     ('SCPA_trunk.0.conv1_a.weight', 'pan'),
     ('model.1.sub.0.res.0.weight', 'srgan'),
     ('body.0.rdb1.conv1.weight', 'realesrgan'),      # BasicSR's RRDBNet (with conv_first.weight): ahead of the new-arch probe, which shares conv_first
+    ('body.0.weight', 'compact'),                    # BasicSR's SRVGGNetCompact: `body` is a ModuleList whose entry 0 is a conv (no body.0.rdb1.*)
     ('conv_first.weight', 'mesrgan'),
     ('model.0.weight', 'esrgan'),
     ('CFEM.0.weight', 'ppon'),
@@ -49,6 +50,8 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
         arch = 'esrgan'
     if arch == 'realesrgan':
         return _infer_realesrgan(state_dict, in_nc)
+    if arch == 'compact':
+        return _infer_compact(state_dict)
     if arch == 'pan':
         return _infer_pan(state_dict, scale, in_nc, out_nc)
     if arch == 'ppon':
@@ -103,6 +106,34 @@ def _infer_realesrgan(state_dict, in_nc=3):
     cfg = {'type': 'realesrgan', 'in_nc': in_nc, 'out_nc': out_nc, 'nf': nf, 'nb': nb, 'gc': gc, 'scale': scale}
     return dict(arch='realesrgan', scale=scale, in_nc=in_nc, out_nc=out_nc, nf=nf, nb=nb, plus=False, state_dict=state_dict,
                 net_params=get_network_G_config(cfg, scale))
+
+
+def _infer_compact(state_dict):
+    """BasicSR SRVGGNetCompact checkpoints (realesr-animevideov3, realesr-general-x4v3, "compact" community models): num_feat, num_in_ch and num_conv are read
+    off the keys, upscale = sqrt(last conv's channels / num_in_ch).  ReLU and LeakyReLU nets carry no activation parameters and cannot be told apart from the
+    keys: only PReLU checkpoints are inferred."""
+    import math
+    w0 = state_dict['body.0.weight']
+    if w0.dim() != 4 or any(k.startswith('body.0.rdb') for k in state_dict):
+        raise Exception("Could not infer model parameters.")
+    convs = sorted(int(k.split('.')[1]) for k, v in state_dict.items() if k.startswith('body.') and k.endswith('.weight') and v.dim() == 4)
+    last = convs[-1]
+    if len(convs) < 2 or convs != list(range(0, last + 1, 2)):
+        raise Exception("Could not infer model parameters.")
+    nf, in_nc = int(w0.shape[0]), int(w0.shape[1])
+    num_conv = len(convs) - 2
+    k_last = int(state_dict[f'body.{last}.weight'].shape[0])
+    up = math.isqrt(k_last // in_nc) if k_last % in_nc == 0 else 0
+    if up * up * in_nc != k_last:
+        raise NotImplementedError(f'SRVGGNetCompact checkpoint: the last conv has {k_last} channels, not num_in_ch ({in_nc}) times a square '
+                                  '(num_out_ch != num_in_ch is not built on the HIP path)')
+    a1 = state_dict.get('body.1.weight')
+    if a1 is None or a1.dim() != 1 or any(f'body.{i + 1}.weight' not in state_dict for i in convs[:-1]):
+        raise NotImplementedError("SRVGGNetCompact checkpoint without PReLU weights: ReLU and LeakyReLU(0.1) nets cannot be told apart from the keys -- "
+                                  "build SRVGGNetCompact(act_type=...) and load the state dict instead of arch='infer'")
+    cfg = {'type': 'compact', 'in_nc': in_nc, 'out_nc': in_nc, 'nf': nf, 'nb': num_conv, 'scale': up, 'act_type': 'prelu'}
+    return dict(arch='compact', scale=up, in_nc=in_nc, out_nc=in_nc, nf=nf, nb=num_conv, plus=False, state_dict=state_dict,
+                net_params=get_network_G_config(cfg, up))
 
 
 def _infer_pan(state_dict, scale, in_nc, out_nc):
@@ -572,7 +603,7 @@ def main(argv=None):
         # mode (float32 tensors select them).  The check stays for an engine built fp16-only: it must refuse, not hand out fp16 accuracy under the flag.
         from .architectures.engine_module import EngineModule
         for m in models:
-            if not isinstance(m.model, EngineModule) and not getattr(m.model, '_has_fp32', False):
+            if not getattr(m.model, '_has_fp32', isinstance(m.model, EngineModule)):      # (an EngineModule has the fp32-accurate engine unless it says otherwise: SRVGGNetCompact)
                 raise NotImplementedError(f"-no_fp16: no fp32-accurate engine is built for '{m.arch}' ({type(m.model).__name__}); drop the flag to run its fp16 engine")
     fit_channels = getattr(args, 'fit_channels', False)
     if fit_channels:

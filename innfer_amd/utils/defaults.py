@@ -115,6 +115,14 @@ def get_network_G_config(network_G, scale):
         cfg['num_feat'] = _pick(opts, 'nf', 64)
         cfg['num_block'] = _pick(opts, 'nb', 23)
         cfg['num_grow_ch'] = _pick(opts, 'gc', 32)
+    elif kind in ('compact_net', 'compact'):               # BasicSR's SRVGGNetCompact (realesr-animevideov3 / general-x4v3, "compact" models): its own constructor surface
+        cfg['type'] = 'compact_net'
+        cfg['num_in_ch'] = _pick(opts, 'in_nc', 3)
+        cfg['num_out_ch'] = _pick(opts, 'out_nc', 3)
+        cfg['num_feat'] = _pick(opts, 'nf', 64)
+        cfg['num_conv'] = _pick(opts, 'nb', 16)
+        cfg['upscale'] = _pick(opts, 'scale', scale)
+        cfg['act_type'] = _pick(opts, 'act_type', 'prelu')
     else:
         raise NotImplementedError(f'Generator model [{kind:s}] not recognized')
 
