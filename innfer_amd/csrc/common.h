@@ -1,6 +1,7 @@
 // Shared declarations of the innfer_amd HIP library (gfx950 only).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -54,8 +55,43 @@ struct GtScope {                                   // brackets the enclosing blo
                                      hipGetErrorString(_e), __FILE__, __LINE__);      \
     } while (0)
 
+// Per-device state (a process may drive several GPUs, one host thread each).
+inline int current_device() {
+    int dev = 0;
+    return hipGetDevice(&dev) == hipSuccess && dev >= 0 ? dev : 0;
+}
+// Sets a kernel's dynamic-LDS limit once per device: function attributes belong to the device's copy of the code object.  `done` is the launcher's own
+// mask of devices (bit dev & 63) that carry it; concurrent first calls may both set the attribute (idempotent).
+template <typename F>
+hipError_t ensure_lds_attr(F* kernel, int lds_bytes, std::atomic<unsigned long long>& done) {
+    const unsigned long long bit = 1ull << (current_device() & 63);
+    if (!(done.load(std::memory_order_acquire) & bit)) {
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+        if (e != hipSuccess) return e;
+        done.fetch_or(bit, std::memory_order_release);
+    }
+    return hipSuccess;
+}
+
+// workgroup -> tiles, for every persistent kernel that walks a tile list of `total` entries.
+// Blocks b and b+8 share an XCD (round-robin dispatch): each XCD gets a contiguous run of the
+// tile list, so neighbouring halos and the next layer's reads of the same region meet in one L2,
+// and its workgroups walk that run round-robin.  With fewer workgroups than tiles (the default)
+// a workgroup is PERSISTENT: it goes on to its next tile while the stores of the last
+// one drain, instead of holding its LDS and wave slots idle until they are acknowledged
+// (s_endpgm waits for them; profiles/r1/ablation_conv.txt).  Speed only, never correctness.
+// The workgroup's tiles are entries start + j of the list, j = j0, j0 + slots, .. < len.
+// (`total` by value: a reference to a member of the kernel-argument struct would put the struct in scratch memory)
+struct XcdRun { int start, len, slots, j0; };       // slots: this launch's workgroups on this XCD
+__device__ __forceinline__ XcdRun xcd_run(int total) {
+    const int bid = blockIdx.x, xcd = bid & 7;
+    const int q = total >> 3, r = total & 7;
+    return {xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q, q + (xcd < r ? 1 : 0), ((int)gridDim.x + 7 - xcd) >> 3, bid >> 3};
+}
+
 // ---- 3x3 convolution on fp16 NHWC slabs (conv3x3.hip) -----------------------
 enum OutMode { OUT_SLAB = 0, OUT_NCHW = 1, OUT_SHUFFLE2 = 2 };
+#include "conv3x3_modes.h"
 
 // Slab layout ("blocked NHWC"): channels in groups of 32; element (n,y,x,c) of a slab lives at
 //   base + (c/32)*gstride + ((n*H + y)*W + x)*32 + c%32        (gstride in elements, >= N*H*W*32)
@@ -74,9 +110,9 @@ struct ConvLaunch {
     int out_mode; int out_f32;                    // OUT_NCHW: planar, f16 or f32
     int rev;                                      // traverse the tiles in reverse order (speed only: see conv3x3.hip)
     int deconv_phases;                            // ConvTranspose2d(4, 2, 1) as four 2x2-tap phase convs: K = 4 * phase_c (phase-major, phase_c % 64 == 0), panels from
-                                                  // conv_pack_taps(mask 0x1B), H x W = the INPUT grid, fp16 slab output of 2H x 2W pixels and phase_c channels
+                                                  // conv_pack_taps(mask TAPS_PHASE), H x W = the INPUT grid, fp16 slab output of 2H x 2W pixels and phase_c channels
     int stride2;                                  // Conv2d(k 4, s 2, p 1) as the 2x2-tap conv of the space-to-depth source (gathered by the loader): H x W = the OUTPUT grid,
-                                                  // the source slab holds 2H x 2W pixels; panels from conv_pack_taps(K, 4 * C, 0x1B0)
+                                                  // the source slab holds 2H x 2W pixels; panels from conv_pack_taps(K, 4 * C, TAPS_S2)
     float* stats_part;                            // != nullptr: the kernel also writes partial norm statistics of its result (count, mean, M2 per tile, consumer wave and
                                                   // channel; conv_stats_nper records per image, merged by norm::launch_combine_parts): 64-channel slab kernels, act 0, no residual
     int prefix_lrelu;                             // with conv1x1: the operand of input group k is LeakyReLU(0.2)(group 0 + .. + group k) (fp32 running sums): PPON's c2
@@ -89,7 +125,7 @@ struct ConvLaunch {
     int conv7;                                    // 7x7 conv, padding 3 (zero or `reflect`), panels from conv_pack7x7: OUT_NCHW, K <= 16 only
     int reflect;                                  // 1: ReflectionPad2d(1) instead of zero padding (slab / planar outputs of the producer-consumer kernel);
                                                   // 2: ReplicationPad2d(1) (3x3 slab convs)
-    // HR_conv0 -> conv_last fused (conv3x3_pc<.., TMF | 0x20000>): this conv (64 -> 64, slab semantics, `out` unused) carries the network's last conv in its epilogue
+    // HR_conv0 -> conv_last fused (conv3x3_pc<.., TMF | PC_FUSE>): this conv (64 -> 64, slab semantics, `out` unused) carries the network's last conv in its epilogue
     const f16* fuse_w;                            //   conv_pack_fuse_last() panel of the last conv (4 KB, device), nullptr = not fused
     const float* fuse_bias; float* fuse_side; void* fuse_out; int fuse_oc, fuse_out_mode;  // its bias, the rim buffer (conv_fuse_side_bytes), the result: 0 fp16 / 1 fp32 planar, 2 the uint8 HWC image (out_denorm, out_round16)
     int phase_c;                                  // OUT_NCHW: K = 4*phase_c channels are the 4 output phases of a stride-2 transposed conv (unet.hip)
@@ -119,7 +155,7 @@ size_t conv_packed_bytes(int K, int C);
 void conv_pack_shuffle2(const float* w_oihw, const float* bias, int K, int C, void* packed, float* bias_out);   // host; phase-major plane-order panels of the PixelShuffle(2) store (ConvLaunch.rowp = 2, OUT_SHUFFLE2): K % 256 == 0
 void conv_pack(const float* w_oihw, int K, int C, void* packed, int rowp = 0);   // host; rowp: the plane row order of 64-channel groups (ConvLaunch.rowp)
 void conv_pack_split(const float* w_oihw, int K, int C, void* packed);     // host; 3 * conv_packed_bytes(K, C): the (wl | wh | wh) panels of ConvLaunch.split
-void conv_pack_1x1_split(const float* w_oi, int K, int C, void* packed);   // host; 3 * conv_packed_bytes_taps(K, C, 0x10)
+void conv_pack_1x1_split(const float* w_oi, int K, int C, void* packed);   // host; 3 * conv_packed_bytes_taps(K, C, TAPS_1X1)
 int conv_launch(const ConvLaunch& L, hipStream_t s);
 size_t conv_packed_bytes_taps(int K, int C, int mask);
 void conv_pack_selfgate(const float* w32x32, void* packed_2k);      // host; ConvLaunch.gate_w

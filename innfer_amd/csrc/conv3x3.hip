@@ -82,7 +82,7 @@ namespace {
 #define ABL_AND(x)
 #endif
 // The B (pixel) fragments a chunk of a tap-mask kernel multiplies, in (tap column, halo row, segment) order, with the kernel rows that use each:
-// the walk of the software-pipelined four-tap loop (conv3x3_pc, TM 0x1B / 0x1B0).
+// the walk of the software-pipelined four-tap loop (conv3x3_pc, TM TAPS_PHASE / TAPS_S2).
 struct TapWalk { int n; int s[3 * 8 * 2], rr[3 * 8 * 2], seg[3 * 8 * 2]; };
 constexpr TapWalk make_tap_walk(int tm, int rpw, int nseg) {
     TapWalk w{};
@@ -125,18 +125,12 @@ __global__ __launch_bounds__(256, (RPW == 3 && NT == 2) ? 3 : 2) void conv3x3_mf
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     STAMP(0);
-    // ---- workgroup -> tiles ---------------------------------------------------------
-    // Blocks b and b+8 share an XCD (round-robin dispatch): each XCD gets a contiguous run of the
-    // tile list, so neighbouring halos and the next layer's reads of the same region meet in one L2,
-    // and its workgroups walk that run round-robin.  With fewer workgroups than tiles (the default:
-    // two per CU) a workgroup is PERSISTENT: it goes on to its next tile while the stores of the last
-    // one drain, instead of holding its LDS and wave slots idle until they are acknowledged
-    // (s_endpgm waits for them; profiles/r1/ablation_conv.txt).  Speed only, never correctness.
+    // workgroup -> tiles: xcd_run (common.h) written out -- through the helper this kernel's code changes beyond its prologue
     const int bid = blockIdx.x, xcd = bid & 7;
     const int run_q = p.total >> 3, run_r = p.total & 7;
     const int run_start = xcd < run_r ? xcd * (run_q + 1) : run_r * (run_q + 1) + (xcd - run_r) * run_q;
     const int run_len = run_q + (xcd < run_r ? 1 : 0);
-    const int slots = ((int)gridDim.x + 7 - xcd) >> 3;            // this launch's workgroups on this XCD
+    const int slots = ((int)gridDim.x + 7 - xcd) >> 3;
     const int per_img = p.tiles_x * p.tiles_y;
     const int li = lane & 15, lg = lane >> 4;
     constexpr int OOB = (int)0x80000000;
@@ -470,7 +464,7 @@ __device__ __forceinline__ f16x8 relu_frag(f16x8 b) {
 // is staged 9 times instead of 49 (gather GEMM).  Padding 3: zero, or mirrored (`reflect`).
 // POLY: a dilation-d 3x3 conv (zero padding d) as ordinary 3x3 convs on the d*d polyphase components of the image ("space to batch"
 // folded into the addressing): the loader's pixel steps and the epilogue's store steps are d pixels, everything else is unchanged.
-// TM: tap mask (bit r*3 + s).  A 1x1 conv is the centre tap only (TM = 0x10): the weight panel then holds, the loaders stage and the consumers
+// TM: tap mask (bit r*3 + s).  A 1x1 conv is the centre tap only (TM = TAPS_1X1): the weight panel then holds, the loaders stage and the consumers
 // multiply ONE tap instead of nine (panels from conv_pack_taps).
 // CV: image canvas.  A batch of N equally sized images (the 200 x 200 tiles of chop_forward: 7 x 32 columns and 9 x 24 rows cover 224 x 216, 21 %
 // of the MFMA work on pixels that do not exist) is tiled as ONE canvas: the images are the cells of a cv_gx x cv_gy grid with a one-pixel gutter
@@ -485,106 +479,103 @@ __device__ __forceinline__ f16x8 relu_frag(f16x8 b) {
 // request stream into HBM never pauses.
 // NCW: consumer waves (8: two per SIMD; 4: one per SIMD with twice the rows each -- the same tile with 0.25 instead of 0.42 ds_read_b128 per MFMA,
 // 256 registers per wave).
-// TMF: bits 0..8 the tap mask of the 3x3 lattice (bit r * 3 + s; the weight panel holds the set taps in that order) + mode flags:
-//   0x1FF  3x3 conv (software-pipelined fragment reads)          0x010  1x1 conv                      0x092  column taps (S9: 7 x 1 conv as three blocks)
-//   0x01B  ConvTranspose2d(k, 2, 1): one output phase per channel group on a lattice shifted by the phase, scatter into the 2x slab
-//   0x1B0 | 0x200  Conv2d(4, 2, 1): the loader gathers the space-to-depth source (chunk = (phase, channel group))
-//   | 0x400  grids <= 16 wide: two images per tile row (PAIR)           | 0x800  (1x1) operand = LeakyReLU(running sum over the chunks) (PPON's c2)
-//   | 0x1000 partial norm statistics out of the epilogue (epilogue_stats)
-// Every flag is compile-time: the instantiations of the SR path (0x1FF without flags) contain none of the other modes' code.
-template <int RPW, int NT, int NLW, int OUTMODE, bool S9 = false, bool POLY = false, int TMF = 0x1FF, bool CV = false, int NSI = 2, int NCW = 8>
+// TMF: bits 0..8 the tap mask of the 3x3 lattice (bit r * 3 + s; the weight panel holds the set taps in that order) + mode flags: the TAPS_* / PC_* constants
+// of conv3x3_modes.h, where each has its value and its meaning.  Every flag is compile-time: the instantiations of the SR path (TAPS_3X3 without flags) contain
+// none of the other modes' code.
+template <int RPW, int NT, int NLW, int OUTMODE, bool S9 = false, bool POLY = false, int TMF = TAPS_3X3, bool CV = false, int NSI = 2, int NCW = 8>
 __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
-    // TMF: tap mask (bits 0..8) + 0x200 = the stride-2 gather loader (S2): Conv2d(k 4, s 2, p 1) as the 2x2-tap conv of the space-to-depth input --
+    // TMF: tap mask (bits 0..8) + PC_S2 = the stride-2 gather loader: Conv2d(k 4, s 2, p 1) as the 2x2-tap conv of the space-to-depth input --
     // chunk c is (phase (pa, pb) = c / ncg, channel group c % ncg); cell (cy, cx) of phase (pa, pb) is source pixel (2cy + pa - 1, 2cx + pb - 1)
-    // (the lattice of the image padded by one pixel), so output (y, x) reads cells y, y + 1 (taps r, s in {1, 2}: mask 0x1B0) and the padding
+    // (the lattice of the image padded by one pixel), so output (y, x) reads cells y, y + 1 (taps r, s in {1, 2}: mask TAPS_S2) and the padding
     // is the loader's range check.  H, W: the OUTPUT grid; the source image is Hs x Ws = 2H x 2W.
-    // + 0x400 (PAIR): images at most 16 pixels wide -- a tile row is TWO images side by side: LDS columns 0..17 the halo row of image 2q, 18..35 that of
+    // + PC_PAIR: images at most 16 pixels wide -- a tile row is TWO images side by side: LDS columns 0..17 the halo row of image 2q, 18..35 that of
     // image 2q + 1 (the 36-pixel pitch is exactly two 18-pixel halo rows), segment 0 / 1 of the MFMA walk = image 2q / 2q + 1 (the deep UNet levels;
     // until round 3 the second segment was idle).  Every output pixel sees the same operands in the same order as in a tile of its own.
-    constexpr int TM = TMF & 0x1FF;
-    constexpr bool S2 = (TMF & 0x200) != 0;
-    constexpr bool PAIR = (TMF & 0x400) != 0;
+    constexpr int TM = TMF & TAPS_3X3;
+    constexpr bool S2 = (TMF & PC_S2) != 0;
+    constexpr bool PAIR = (TMF & PC_PAIR) != 0;
     constexpr int NSEG = 2;
     constexpr int TWI = PAIR ? 16 : TW;                 // image columns a tile row segment set covers per image
-    static_assert(!PAIR || (__builtin_popcount(TMF & 0x1FF) == 4 && !S9 && !POLY && !CV), "image pairs: the four-tap kernels");
-    // + 0x800 (one-tap kernels): the B operand of chunk k is LeakyReLU(0.2) of the running sum of chunks 0 .. k of the pixel -- PPON's
+    static_assert(!PAIR || (__builtin_popcount(TM) == 4 && !S9 && !POLY && !CV), "image pairs: the four-tap kernels");
+    // + PC_PFX (one-tap kernels): the B operand of chunk k is LeakyReLU(0.2) of the running sum of chunks 0 .. k of the pixel -- PPON's
     // cat(d1, d1 + d2, .., d1 + .. + d8) -> act -> c2 (PPON_arch.py:104-114) without the pass that materialises it: the consumer keeps the
     // fp32 running sums of its own pixels in registers (same additions in the same order as that pass made: same bits)
-    constexpr bool PFX = (TMF & 0x800) != 0;
-    constexpr bool STATS = (TMF & 0x1000) != 0;          // + 0x1000: partial norm statistics out of the epilogue (epilogue_stats)
-    // + 0x2000: fp32-accurate mode on split operands.  A tensor is a pair of fp16 slabs (hi, lo = (x - hi) * 2^11; see epilogue_slab_split), a weight
+    constexpr bool PFX = (TMF & PC_PFX) != 0;
+    constexpr bool STATS = (TMF & PC_STATS) != 0;       // + PC_STATS: partial norm statistics out of the epilogue (epilogue_stats)
+    // + PC_SPLIT: fp32-accurate mode on split operands.  A tensor is a pair of fp16 slabs (hi, lo = (x - hi) * 2^11; see epilogue_slab_split), a weight
     // likewise a pair of panels, and x * w = xh * wh + 2^-11 (xh * wl + xl * wh) (the 2^-22 term is dropped): the launch runs 3 * ncg virtual chunks --
     // [0, ncg) stage (xh, wl), [ncg, 2 ncg) (xl, wh), [2 ncg, 3 ncg) (xh, wh) (panels packed in that order by conv_pack_split); the accumulators start
     // at zero, are scaled by 2^-11 (exact) and receive the bias when the third part begins: ONE accumulator set, the fp16 kernel's MFMA stream.
-    constexpr bool SPLIT = (TMF & 0x2000) != 0;
-    static_assert(!SPLIT || (!S9 && !POLY && !S2 && !PFX && !STATS && (TM == 0x1FF || TM == 0x10)), "split operands: plain 3x3 and 1x1 convs");
-    // + 0x20000 (FUSE): HR_conv0 -> conv_last in one kernel (RRDBNet_arch.py:36-42: HR_conv0 = conv + LeakyReLU, conv_last = conv, both 3x3) without recomputing a
+    constexpr bool SPLIT = (TMF & PC_SPLIT) != 0;
+    static_assert(!SPLIT || (!S9 && !POLY && !S2 && !PFX && !STATS && (TM == TAPS_3X3 || TM == TAPS_1X1)), "split operands: plain 3x3 and 1x1 convs");
+    // + PC_FUSE: HR_conv0 -> conv_last in one kernel (RRDBNet_arch.py:36-42: HR_conv0 = conv + LeakyReLU, conv_last = conv, both 3x3) without recomputing a
     // halo.  The epilogue turns the tile's LeakyReLU'd result into the MFMA's B operand in registers (the k order of the last conv's panel is chosen so that a
     // lane's sixteen accumulator channels ARE its two k-step fragments), multiplies it by the 27 x 64 matrix W_last[(c, dy, dx)][k] (16 MFMAs per wave), parks
     // the 27 products per pixel in the LDS stage the tile has finished with (fp32, 64 KB), and every output pixel of the tile's 18 x 34 neighbourhood sums the
     // nine that lie inside the tile.  Pixels at least one pixel inside the tile are complete (+ bias -> planar output); the 92 pixels on the tile's rim and the
     // 100 just outside it get partial sums (fl_side), finished by conv_fuse_combine from the two to four tiles that meet there, in a fixed order.  The 4.25 GB
     // HR slab of a 1080p -> 4K frame is neither written nor read.  Two more workgroup barriers on a tile's last chunk (loaders included).
-    // + 0x40000 (RLDS): the dense block's last conv (RRDBNet_arch.py:161-165: x5 = conv5(cat(x, x1 .. x4)); x5 * 0.2 + x) takes its residual x from LDS instead
+    // + PC_RLDS: the dense block's last conv (RRDBNet_arch.py:161-165: x5 = conv5(cat(x, x1 .. x4)); x5 * 0.2 + x) takes its residual x from LDS instead
     // of re-reading it from memory in the epilogue: x IS the conv's input channel groups 0 and 1, so the chunks are walked in the order 2, 3, .., 0, 1 (loader:
     // chunk c stages group (c + 2) mod nchunks and its panel) and at the end of the last two steps the live stage holds exactly the 32 residual channels half of
     // the lanes need, at the centre tap's position of their own pixels: those lanes add x / s1 to their accumulators (s1 = 0.2: x * 5, exact product, one fp32
     // rounding of the sum), the epilogue scales by s1.  265 MB of every 1327 MB launch (1080p) are no longer read twice; the RRDB-end launches, whose two
     // residuals' loads did not fit the registers as one batch, keep ONE memory residual and hoist its loads like the others.
-    constexpr bool RLDS = (TMF & 0x40000) != 0;
-    static_assert(!RLDS || (RPW == 2 && NT == 4 && NCW == 8 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & 0x3FFFF) == 0x1FF && !S9 && !POLY), "residual from LDS: the plain 64-channel instantiation (and its canvas form)");
-    // + 0x80000 (SGATE): PAN's pixel attention behind an up-conv (PAN_arch.py:11-35: upconv -> PA: x * sigmoid(conv1x1(x)) -> LeakyReLU) inside the up-conv's
+    constexpr bool RLDS = (TMF & PC_RLDS) != 0;
+    static_assert(!RLDS || (RPW == 2 && NT == 4 && NCW == 8 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_RLDS) == TAPS_3X3 && !S9 && !POLY), "residual from LDS: the plain 64-channel instantiation (and its canvas form)");
+    // + PC_SGATE: PAN's pixel attention behind an up-conv (PAN_arch.py:11-35: upconv -> PA: x * sigmoid(conv1x1(x)) -> LeakyReLU) inside the up-conv's
     // epilogue: a lane's accumulators are 8 consecutive channels of its pixel (NT = 2 row order), i.e. after the fp16 conversion -- the value the two-launch
     // schedule stored -- the B fragment of the 1x1 conv; two MFMAs per pixel tile against the 32 x 32 gate matrix held in registers, then v * sigmoid(g) goes
     // through the ordinary epilogue (its LeakyReLU, the store).  Same fp16 operands and the same MFMA as the two launches; the sigmoid is the fast form, so results
     // agree to the last fp16 rounding -- without the round trip of the 32-channel HR tensor (531 MB written and read again at 2160 x 3840).
-    constexpr bool SGATE = (TMF & 0x80000) != 0;
-    static_assert(!SGATE || (RPW == 3 && NT == 2 && NCW == 8 && OUTMODE == OUT_SLAB && ((TMF & 0x7FFFF) == 0x1FF || (TMF & 0x7FFFF) == 0x21FF) && !S9 && !POLY), "self gate: the 32-output slab kernel (its canvas form, its split-operand form)");
-    // + 0x100000 (BRELU): the pixel operand is max(x, 0) of the stored slab -- the UNet keeps ONE stored form of a skip tensor (LeakyReLU, the down conv's operand);
+    constexpr bool SGATE = (TMF & PC_SGATE) != 0;
+    static_assert(!SGATE || (RPW == 3 && NT == 2 && NCW == 8 && OUTMODE == OUT_SLAB && ((TMF & PC_BELOW_SGATE) == TAPS_3X3 || (TMF & PC_BELOW_SGATE) == (TAPS_3X3 | PC_SPLIT)) && !S9 && !POLY), "self gate: the 32-output slab kernel (its canvas form, its split-operand form)");
+    // + PC_BRELU: the pixel operand is max(x, 0) of the stored slab -- the UNet keeps ONE stored form of a skip tensor (LeakyReLU, the down conv's operand);
     // the up conv that reads the concatenation applies the ReLU as it takes a fragment from LDS (4 v_pk_max_f16 per fragment, i.e. per 2 .. 8 MFMAs).
     // max(lrelu(v), 0) == relu(v) bit for bit in fp16, so the results are those of the two-view form.
-    constexpr bool BRELU = (TMF & 0x100000) != 0;
-    // + 0x200000 (UP4): all four output phases of a 2x transposed conv (the SR networks' up-convs as phase convs, net.hip) in ONE visit of a tile.  The
-    // phase-lattice form (TM 0x1B) visits a tile once per phase and stages its input tile each time: the launch moves 4 x 128 B of input per LR pixel beside
+    constexpr bool BRELU = (TMF & PC_BRELU) != 0;
+    // + PC_UP4: all four output phases of a 2x transposed conv (the SR networks' up-convs as phase convs, net.hip) in ONE visit of a tile.  The
+    // phase-lattice form (TM TAPS_PHASE) visits a tile once per phase and stages its input tile each time: the launch moves 4 x 128 B of input per LR pixel beside
     // 512 B of output, and the ablation (profiles/r4/upconv_bound.txt) shows the input stream is 0.9 of the 2.35 ms the frame's two up-convs take.  Here the
     // tile's two input groups (C = 64) stay in two of three LDS slots while the eight weight panels (phase, group) stream through the two weight slots:
     // step g of a workgroup is (tile g / 8, phase (g % 8) / 2, group g % 2); phase (a, b) multiplies the 2 x 2 tap block (a .. a + 1) x (b .. b + 1) of
     // the UNSHIFTED 3 x 3 halo tile (= the shifted lattice's taps {-1, 0}^2 at virtual pixel (y + a, x + b)) and stores through the phase-lattice
     // epilogue after its second group.  The loaders fetch the next tile's group 0 into the free slot at step 0 and its group 1 into the slot the
     // current tile's group 0 leaves after step 6.  Same MFMAs, same operands, same order per output value as the four-visit form: same bits.
-    constexpr bool UP4 = (TMF & 0x200000) != 0;
-    // + 0x400000 (ROWP): the plane row order of the 64-channel groups (see toff_slab): plain 3x3 slab convs (canvas, RLDS, FUSE forms included) and the one-pass up-conv
-    constexpr bool ROWP = (TMF & 0x400000) != 0;
-    static_assert(!ROWP || (RPW == 2 && NT == 4 && NCW == 8 && OUTMODE == OUT_SLAB && (TMF & 0x1FF) == 0x1FF && (TMF & ~0x1E601FF) == 0 && !S9 && !POLY), "plane row order: the 64-channel slab kernels");
-    // + 0x800000 (PSH): nn.PixelShuffle(2) as the store of a conv nf -> 4 nf (pixelshuffle_block, block.py:333-346; SRResNet's up stages, RRDBNet(upsample_mode=
+    constexpr bool UP4 = (TMF & PC_UP4) != 0;
+    // + PC_ROWP: the plane row order of the 64-channel groups (see toff_slab): plain 3x3 slab convs (canvas, RLDS, FUSE forms included) and the one-pass up-conv
+    constexpr bool ROWP = (TMF & PC_ROWP) != 0;
+    static_assert(!ROWP || (RPW == 2 && NT == 4 && NCW == 8 && OUTMODE == OUT_SLAB && TM == TAPS_3X3 && (TMF & ~(TAPS_3X3 | PC_FUSE | PC_RLDS | PC_UP4 | PC_ROWP | PC_PSH | PC_PRELU)) == 0 && !S9 && !POLY), "plane row order: the 64-channel slab kernels");
+    // + PC_PSH: nn.PixelShuffle(2) as the store of a conv nf -> 4 nf (pixelshuffle_block, block.py:333-346; SRResNet's up stages, RRDBNet(upsample_mode=
     // 'pixelshuffle')) on THIS kernel -- until round 4 those launches ran on the two-workgroup kernel of round 1 (0.30 of the MFMA peak, a third of an SRResNet frame).
     // The panels are phase-major (conv_pack_shuffle2) in the plane row order, so a channel group is one output phase of 64 channels and the epilogue is the
     // transposed-conv phase store without the lattice shift (epilogue_slab PSH).  Same MFMAs in the same order per value as the old form: same bits.
-    constexpr bool PSH = (TMF & 0x800000) != 0;
-    static_assert(!PSH || (ROWP && (TMF & ~0xC001FF) == 0 && NSI == 2 && !CV), "pixel-shuffle store: the plain 64-channel plane-order instantiation");
-    static_assert(!UP4 || (RPW == 2 && NT == 4 && NCW == 8 && NSI == 3 && OUTMODE == OUT_SLAB && (TMF & 0x1FFFFF) == 0x1FF && !S9 && !POLY && !CV), "one-pass phases: the 64-channel slab kernel on three input slots");
-    constexpr bool FUSE = (TMF & 0x20000) != 0;
-    // + 0x1000000 (PRELU): ConvLaunch.act 8 -- f >= 0 ? f : slope[c] * f with a per-channel slope vector (nn.PReLU(num_parameters = K); constant vectors serve ReLU and
+    constexpr bool PSH = (TMF & PC_PSH) != 0;
+    static_assert(!PSH || (ROWP && (TMF & ~(TAPS_3X3 | PC_ROWP | PC_PSH)) == 0 && NSI == 2 && !CV), "pixel-shuffle store: the plain 64-channel plane-order instantiation");
+    static_assert(!UP4 || (RPW == 2 && NT == 4 && NCW == 8 && NSI == 3 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_UP4) == TAPS_3X3 && !S9 && !POLY && !CV), "one-pass phases: the 64-channel slab kernel on three input slots");
+    constexpr bool FUSE = (TMF & PC_FUSE) != 0;
+    // + PC_PRELU: ConvLaunch.act 8 -- f >= 0 ? f : slope[c] * f with a per-channel slope vector (nn.PReLU(num_parameters = K); constant vectors serve ReLU and
     // LeakyReLU(a)) as the slab epilogue of the plain nine-tap kernels: the chain of 64 -> 64 convs of BasicSR's SRVGGNetCompact, one launch per layer.  The slopes are
     // NOT kept in registers beside the bias (sixteen more live registers across the MFMA loop spill the 64-output kernel): every consumer wave parks the launch's one
     // channel group of slopes (K = 16 NT) in 256 bytes of its own behind the two stages and reads its lane's values back at each tile's end -- same-wave LDS traffic,
     // in order, no barrier.  Instantiations of their own: the other kernels' code does not change.
-    constexpr bool PRELU = (TMF & 0x1000000) != 0;
-    static_assert(!PRELU || (OUTMODE == OUT_SLAB && (NT == 4 || NT == 2) && NCW == 8 && NSI == 2 && (TMF & ~0x14001FF) == 0 && (TMF & 0x1FF) == 0x1FF && !S9 && !POLY && !CV), "PReLU epilogue: the plain 64- / 32-output slab kernels");
-    static_assert(!FUSE || (RPW == 2 && (NT == 4 || (NT == 2 && !ROWP)) && NCW == 8 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & 0x1FFFF) == 0x1FF && !S9 && !POLY && !CV), "the fused last conv: the plain 64-channel instantiation (and the 32-channel one on 16-row tiles)");
-    constexpr int TH = NCW * RPW;
+    constexpr bool PRELU = (TMF & PC_PRELU) != 0;
+    static_assert(!PRELU || (OUTMODE == OUT_SLAB && (NT == 4 || NT == 2) && NCW == 8 && NSI == 2 && (TMF & ~(TAPS_3X3 | PC_ROWP | PC_PRELU)) == 0 && TM == TAPS_3X3 && !S9 && !POLY && !CV), "PReLU epilogue: the plain 64- / 32-output slab kernels");
+    static_assert(!FUSE || (RPW == 2 && (NT == 4 || (NT == 2 && !ROWP)) && NCW == 8 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_FUSE) == TAPS_3X3 && !S9 && !POLY && !CV), "the fused last conv: the plain 64-channel instantiation (and the 32-channel one on 16-row tiles)");
+    using L = PcLayout<RPW, NT, NSI, NCW, TMF>;                   // the LDS layout, shared with launch_pc
+    constexpr int TH = L::TH;
     constexpr int LH = TH + 2;
     constexpr int NPX = LH * LWP;
-    constexpr int NQ = (NPX + 15) / 16;
+    constexpr int IN_BYTES = L::IN_BYTES;
+    constexpr int NQ = IN_BYTES / 1024;
     constexpr int KQ = (NQ + NLW - 1) / NLW;
-    constexpr int IN_BYTES = NQ * 1024;
     constexpr int WROWS = NT * 16;
-    constexpr int NTAP = UP4 ? 4 : __builtin_popcount(TM);        // taps in the panel, in (r, s) order (UP4: a phase's 2 x 2 block)
-    constexpr int W_BYTES = NTAP * WROWS * 64;
+    constexpr int NTAP = L::NTAP;
+    constexpr int W_BYTES = L::W_BYTES;
     constexpr int WQ = W_BYTES / 1024;
     constexpr int KW = (WQ + NLW - 1) / NLW;
     constexpr int MT = RPW * 2;
-    constexpr int STAGE = IN_BYTES + W_BYTES;
+    constexpr int STAGE = L::STAGE;
     constexpr int OOB = (int)0x80000000;
 #ifdef INNFER_NO_PIPE
     constexpr bool PIPE = false;                 // A/B build: the compiler's own placement of the fragment reads
@@ -603,13 +594,9 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
 
-    const int bid = blockIdx.x, xcd = bid & 7;
-    const int run_q = p.total >> 3, run_r = p.total & 7;
-    const int run_start = xcd < run_r ? xcd * (run_q + 1) : run_r * (run_q + 1) + (xcd - run_r) * run_q;
-    const int run_len = run_q + (xcd < run_r ? 1 : 0);
-    const int slots = ((int)gridDim.x + 7 - xcd) >> 3;
+    const XcdRun run = xcd_run(p.total);
+    const int run_start = run.start, run_len = run.len, slots = run.slots, j0 = run.j0;
     const int per_img = p.tiles_x * p.tiles_y;
-    const int j0 = bid >> 3;
     if (j0 >= run_len) return;                                   // whole workgroup: no tiles
     const int ntiles = (run_len - j0 + slots - 1) / slots;
     const int G = ntiles * p.nchunks;                            // chunks this workgroup goes through
@@ -624,7 +611,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
         const int ty = tile / p.tiles_x;
         ty0_ = p.y0 + ty * TH;
         tx0_ = (tile - ty * p.tiles_x) * TW;
-        if constexpr (TM == 0x1B) {
+        if constexpr (TM == TAPS_PHASE) {
             // one phase of a 2x transposed conv per channel group: phase (a, b) of ConvTranspose2d(4, 2, 1) is the conv of taps (dy, dx) in
             // {-1, 0}^2 taken at the virtual pixel (y + a, x + b) -- the same four-tap kernel on a tile lattice shifted by (a, b)
             const int ph = kg_ * WROWS / p.phase_c;
@@ -708,7 +695,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
         constexpr const TapWalk& WK = TapWalkOf<TMX, RPW, NSEG>::value;      // (a class-scope constant: a local copy indexed by a loop variable may land in scratch)
         constexpr int NBW = TapWalkOf<TMX, RPW, NSEG>::value.n;
         constexpr int R0 = (TMX & 0x007) ? 0 : 1, S0 = (TMX & 0x049) ? 0 : 1;          // the mask is the 2 x 2 block of taps (R0 .. R0 + 1) x (S0 .. S0 + 1)
-        static_assert(TMX == (0x1B << (3 * R0 + S0)), "four taps: a 2 x 2 block of the 3 x 3 lattice");
+        static_assert(TMX == (TAPS_PHASE << (3 * R0 + S0)), "four taps: a 2 x 2 block of the 3 x 3 lattice");
         f16x8 a[2][NT];                                                              // the weight fragments of the current tap column, by tap row - R0
         auto lda = [&](int sc, int q) {
 #pragma unroll
@@ -747,7 +734,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
 #include "conv3x3_pc_up4.inc"
     int islot = 0;                                                // NSI == 3: g % 3
     f32x4 bias_r[NT];
-    [[maybe_unused]] float* slope_lds = (float*)(smem + 2 * STAGE) + cw * 64;
+    [[maybe_unused]] float* slope_lds = (float*)(smem + L::TAIL) + cw * 64;
     if constexpr (PRELU) { if (lane < WROWS) slope_lds[lane] = p.slope[lane]; }
     int bias_kg = -1;
     f32x4 acc[NT][MT];
@@ -797,7 +784,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
         constexpr bool abl_no_mfma = false;
 #endif
         if (abl_no_mfma) {
-        } else if constexpr (TM == 0x1FF && PIPE && !UP4) {
+        } else if constexpr (TM == TAPS_3X3 && PIPE && !UP4) {
             // Software-pipelined fragment reads (the nine-tap kernels).  The B fragments of a chunk are walked in (s, rr, seg) order through
             // a three-register ring, each read issued two MFMA groups (>= 8 MFMAs = 128 pipe cycles) ahead of its use; the weight fragments
             // of tap column s + 1 overwrite those of column s as soon as their last MFMA has been issued (A(s,0,*) after row RPW - 1,
@@ -865,7 +852,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
                     f16x8 b = *(const f16x8*)(st + ((PAIR && seg) ? boffp[PAIR ? s : 0][rr & 1] + rr * LWP * 64 : boffs[s][rr & 1] + (rr * LWP + seg * 16) * 64));
                     if constexpr (BRELU) b = relu_frag(b);
                     if constexpr (PFX) {           // (one tap: row rr feeds output row rr - 1 only)
-                        static_assert(!PFX || TM == 0x10, "the running-sum operand belongs to the one-tap kernels");
+                        static_assert(!PFX || TM == TAPS_1X1, "the running-sum operand belongs to the one-tap kernels");
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             float& run = pfx[PFX ? (rr - 1) * 2 + seg : 0][e];
@@ -924,16 +911,10 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
 #endif
 }
 
-template <int RPW, int NT, int NLW, int OUTMODE = OUT_SLAB, bool S9 = false, bool POLY = false, int TM = 0x1FF, bool CV = false, int NSI = 2, int NCW = 8>
+template <int RPW, int NT, int NLW, int OUTMODE = OUT_SLAB, bool S9 = false, bool POLY = false, int TM = TAPS_3X3, bool CV = false, int NSI = 2, int NCW = 8>
 int launch_pc(const KP& kp, int N, hipStream_t s);
 
-// Per-device state (a process may drive several GPUs): CU count, and which devices already carry a kernel's
-// dynamic-LDS attribute (function attributes belong to the device's copy of the code object).
-int current_device() {
-    int dev = 0;
-    return hipGetDevice(&dev) == hipSuccess && dev >= 0 ? dev : 0;
-}
-
+// CU count of the current device (a process may drive several GPUs)
 int num_cus() {
     static int n[64] = {};
     const int dev = current_device() & 63;
@@ -945,23 +926,12 @@ int num_cus() {
     return n[dev];
 }
 
-template <typename F>
-int ensure_lds_attr(F* kernel, int lds_bytes, unsigned long long& done_mask) {
-    const unsigned long long bit = 1ull << (current_device() & 63);
-    if (!(done_mask & bit)) {
-        INNFER_HIP(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes));
-        done_mask |= bit;
-    }
-    return INNFER_OK;
-}
-
-
 template <int RPW, int NT, int OUTMODE>
 int launch_t(const KP& kp, int N, hipStream_t s) {
     constexpr int TH = 4 * RPW;
     constexpr int LDS = (((TH + 2) * LWP + 15) / 16) * 1024 + 9 * NT * 16 * 64 + ((RPW == 3 && NT == 2) ? 0 : 2048);   // + prefetch scratch
-    static unsigned long long attr_done = 0;
-    if (int rc = ensure_lds_attr(conv3x3_mfma<RPW, NT, OUTMODE>, LDS, attr_done)) return rc;
+    static std::atomic<unsigned long long> attr_done{0};
+    INNFER_HIP(ensure_lds_attr(conv3x3_mfma<RPW, NT, OUTMODE>, LDS, attr_done));
     KP k = kp;
     k.tiles_x = (k.W + TW - 1) / TW;
     k.tiles_y = (k.y1 - k.y0 + TH - 1) / TH;
@@ -1005,10 +975,10 @@ int canvas_grid(const KP& k, int N, int* gy, long* tiles) {
 template <int RPW, int NT, int NLW, int OUTMODE, bool S9, bool POLY, int TM, bool CV, int NSI, int NCW>
 int launch_pc(const KP& kp, int N, hipStream_t s) {
     constexpr int TH = NCW * RPW;
-    constexpr int LDS = NSI * ((((TH + 2) * LWP + 15) / 16) * 1024) + 2 * (((TM & 0x200000) ? 4 : __builtin_popcount(TM & 0x1FF)) * NT * 16 * 64) + ((TM & 0x20000) ? 4096 : 0) + ((TM & 0x200000) ? 1024 : 0) + ((TM & 0x1000000) ? NCW * 256 : 0);      // (UP4: + the four phases' biases; PRELU: + the slopes, once per consumer wave)
+    constexpr int LDS = PcLayout<RPW, NT, NSI, NCW, TM>::LDS_BYTES;
     static_assert(LDS <= 160 * 1024, "the stages must fit the CU's LDS");
     static_assert(NSI == 2 || (NSI == 3 && !S9 && !POLY), "the three-slot input ring exists for the plain and the canvas loader");
-    if constexpr (OUTMODE == OUT_SLAB && !S9 && !POLY && (TM & ~0x4C2000) == 0x1FF && !CV) {      // a batch of images whose size is not a whole number of tiles
+    if constexpr (OUTMODE == OUT_SLAB && !S9 && !POLY && (TM & ~(PC_SPLIT | PC_RLDS | PC_SGATE | PC_ROWP)) == TAPS_3X3 && !CV) {      // a batch of images whose size is not a whole number of tiles
         int gy = 0; long t = 0;
         const int gx = INNFER_KNOB("INNFER_CANVAS", 1) ? canvas_grid<TH>(kp, N, &gy, &t) : 0;
         if (gx > 0) {
@@ -1017,8 +987,8 @@ int launch_pc(const KP& kp, int N, hipStream_t s) {
             return launch_pc<RPW, NT, NLW, OUTMODE, false, false, TM, true, NSI, NCW>(kc, N, s);
         }
     }
-    static unsigned long long attr_done = 0;
-    if (int rc = ensure_lds_attr(conv3x3_pc<RPW, NT, NLW, OUTMODE, S9, POLY, TM, CV, NSI, NCW>, LDS, attr_done)) return rc;
+    static std::atomic<unsigned long long> attr_done{0};
+    INNFER_HIP(ensure_lds_attr(conv3x3_pc<RPW, NT, NLW, OUTMODE, S9, POLY, TM, CV, NSI, NCW>, LDS, attr_done));
     KP k = kp;
     k.tiles_x = (k.W + TW - 1) / TW;
     k.tiles_y = (k.y1 - k.y0 + TH - 1) / TH;
@@ -1026,7 +996,7 @@ int launch_pc(const KP& kp, int N, hipStream_t s) {
 #ifdef INNFER_ABLATE
     k.abl = getenv("INNFER_ABL") ? atoi(getenv("INNFER_ABL")) : 0;     // read per launch: scripts/ablate.py changes it between runs
 #endif
-    long total = (long)((TM & 0x400) ? (N + 1) / 2 : N) * k.tiles_x * k.tiles_y * k.KG;      // (0x400: two images per tile row)
+    long total = (long)((TM & PC_PAIR) ? (N + 1) / 2 : N) * k.tiles_x * k.tiles_y * k.KG;      // (PAIR: two images per tile row)
     if constexpr (CV) {                       // one canvas instead of N images
         k.tiles_x = (k.cv_gx * k.cv_w1 + TW - 1) / TW;
         k.tiles_y = (k.cv_gy * k.cv_h1 + TH - 1) / TH;
@@ -1147,7 +1117,7 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
     const int rpw64 = INNFER_KNOB("INNFER_RPW64", 3);
     const int rpw32 = INNFER_KNOB("INNFER_RPW32", 5);
     const int pc = INNFER_KNOB("INNFER_PC", 1);     // producer / consumer kernel for slab outputs
-    if (L.act == 8) {        // per-channel slopes (PReLU): conv3x3_pc<.., TMF | 0x1000000>, the plain nine-tap slab kernels of 64 (either row order) and 32 outputs
+    if (L.act == 8) {        // per-channel slopes (PReLU): conv3x3_pc<.., TMF | PC_PRELU>, the plain nine-tap slab kernels of 64 (either row order) and 32 outputs
         if (!L.slope) return set_error(INNFER_ERR_INVALID, "conv3x3: act 8 (per-channel slope) needs the slope vector");
         if (!pc || L.out_mode != OUT_SLAB || (nt != 4 && nt != 2) || L.K != 16 * nt || L.split || L.stats_part || L.gate_w || L.conv1x1 || L.prefix_lrelu || L.deconv_phases || L.stride2 ||
             L.conv7v || L.conv7 || L.fuse_w || L.dilation > 1 || L.dilation_groups || L.in_relu || L.res1 || L.res2 || L.up || L.reflect || L.phase_c || L.outm || L.out_u8 ||
@@ -1155,32 +1125,32 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: act 8 (per-channel slope) is built as the epilogue of the plain 3x3 slab convs of 64 or 32 outputs -- not the split / "
                                                      "statistics / gate / 1x1 / planar / phase / stride-2 / dilated / fused-last forms, no residual, upsampling or reflection padding");
         k.slope = L.slope;
-        if (nt == 2) return launch_pc<3, 2, 4, OUT_SLAB, false, false, 0x10001FF>(k, L.N, s);
-        return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x14001FF>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x10001FF>(k, L.N, s);
+        if (nt == 2) return launch_pc<3, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_PRELU>(k, L.N, s);
+        return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP | PC_PRELU>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_PRELU>(k, L.N, s);
     }
     if (L.rowp && !(L.rowp == 2 && L.out_mode == OUT_SHUFFLE2) && (nt != 4 || !pc || L.out_mode != OUT_SLAB || L.split || L.stats_part || L.stride2 || L.conv1x1 || L.conv7 || L.conv7v || L.prefix_lrelu ||
                    L.gate_w || L.act > 2 || L.dilation > 1 || L.dilation_groups || (L.out_coff & 31)))
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the plane row order (rowp) belongs to plain 3x3 slab convs and transposed-conv phases with 64-channel output groups");
     if (L.outm && (L.out_mode != OUT_NCHW || !pc || nt != 1 || L.res1 || L.res2 || L.outm < 0 || L.outm > 4))
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: outm belongs to the planar last conv (<= 16 channels)");
-    if (L.split) {           // fp32-accurate mode on (hi, lo) slab pairs: 3 * C / 32 virtual chunks (conv3x3_pc<.., TMF | 0x2000>)
+    if (L.split) {           // fp32-accurate mode on (hi, lo) slab pairs: 3 * C / 32 virtual chunks (conv3x3_pc<.., TMF | PC_SPLIT>)
         if (!pc || (L.act > 2 && !((L.act == 3 || L.act == 6) && L.out_mode == OUT_NCHW) && !((L.act == 4 || L.act == 5) && L.conv1x1 && nt == 2)) || L.reflect || L.dilation > 1 || L.dilation_groups || L.deconv_phases || L.stride2 || L.conv7v || L.conv7 || L.stats_part ||
             L.prefix_lrelu || L.phase_c || (long)3 * L.C / 32 > 0x7fff)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3 (fp32 mode): plain 3x3 / 1x1 convs with act 0..2 (the 32-channel 1x1 conv also the PA gate), residuals, upsampled input");
         k.nchunks = 3 * k.ncg;
         k.in_lo_bytes = L.in_lo * 2; k.out_lo = L.out_lo; k.res1_lo = L.res1_lo; k.res2_lo = L.res2_lo;
         if (L.out_mode == OUT_SLAB && L.conv1x1 && (nt == 2 || nt == 4))
-            return nt == 4 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x2010, false, 3>(k, L.N, s) : launch_pc<2, 2, 4, OUT_SLAB, false, false, 0x2010, false, 3>(k, L.N, s);
+            return nt == 4 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_1X1 | PC_SPLIT, false, 3>(k, L.N, s) : launch_pc<2, 2, 4, OUT_SLAB, false, false, TAPS_1X1 | PC_SPLIT, false, 3>(k, L.N, s);
         if (L.conv1x1) return set_error(INNFER_ERR_UNSUPPORTED, "conv1x1 (fp32 mode): slab outputs of 32- / 64-channel tiles");
         if (L.gate_w) {      // out = act(v * sigmoid(W v + b)) on the conv's fp32 result: gate_w = the hi | lo fragments of conv_pack_selfgate (4 KB)
             if (L.out_mode != OUT_SLAB || nt != 2 || L.K != 32 || L.res1 || L.res2 || L.act > 2)
                 return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3 (fp32 mode): the self gate belongs to 32-output slab convs without residuals");
             k.sg_w = L.gate_w; k.sg_bias = L.gate_bias;
-            return launch_pc<3, 2, 4, OUT_SLAB, false, false, 0x821FF>(k, L.N, s);
+            return launch_pc<3, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_SPLIT | PC_SGATE>(k, L.N, s);
         }
-        if (L.out_mode == OUT_SLAB && nt == 2) return launch_pc<3, 2, 4, OUT_SLAB, false, false, 0x21FF>(k, L.N, s);
-        if (L.out_mode == OUT_SLAB && nt == 4) return launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x21FF>(k, L.N, s);
-        if (L.out_mode == OUT_NCHW && nt == 1 && !L.res1 && !L.res2) return launch_pc<3, 1, 4, OUT_NCHW, false, false, 0x21FF>(k, L.N, s);
+        if (L.out_mode == OUT_SLAB && nt == 2) return launch_pc<3, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_SPLIT>(k, L.N, s);
+        if (L.out_mode == OUT_SLAB && nt == 4) return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_SPLIT>(k, L.N, s);
+        if (L.out_mode == OUT_NCHW && nt == 1 && !L.res1 && !L.res2) return launch_pc<3, 1, 4, OUT_NCHW, false, false, TAPS_3X3 | PC_SPLIT>(k, L.N, s);
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3 (fp32 mode): slab outputs of 32- / 64-channel tiles or a planar output of <= 16 channels (K=%d)", L.K);
     }
     if (L.dilation_groups > 0) {   // K = 32 * groups: output channel group g (its own 32-output panel) is the conv of dilation g + 1
@@ -1211,67 +1181,67 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         if (L.rowp && (L.C != 64 || L.phase_c != 64 || L.stats_part || L.W <= 16 || L.deconv_phases == 2))
             return set_error(INNFER_ERR_UNSUPPORTED, "deconv phases: plane-order panels belong to the one-visit form (C = 64, 64-channel phases, grids wider than 16, no statistics)");
         if (L.rowp) {
-            // the SR networks' up-convs (64 -> 64): all four phases in one visit of a tile, the input tile staged once (conv3x3_pc<.., TMF | 0x200000>), panels in the
+            // the SR networks' up-convs (64 -> 64): all four phases in one visit of a tile, the input tile staged once (conv3x3_pc<.., TMF | PC_UP4>), panels in the
             // plane row order; lane-contiguous panels (rowp 0) run the one-phase-per-visit form below
             k.KG = 1; k.nchunks = 8;
-            return launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x6001FF, false, 3>(k, L.N, s);
+            return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_UP4 | PC_ROWP, false, 3>(k, L.N, s);
         }
-        if (L.stats_part) return L.W <= 16 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x141B, false, UNET_NSI>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x101B, false, UNET_NSI>(k, L.N, s);
-        return L.W <= 16 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x41B, false, UNET_NSI>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x1B, false, UNET_NSI>(k, L.N, s);
+        if (L.stats_part) return L.W <= 16 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_PHASE | PC_PAIR | PC_STATS, false, UNET_NSI>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_PHASE | PC_STATS, false, UNET_NSI>(k, L.N, s);
+        return L.W <= 16 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_PHASE | PC_PAIR, false, UNET_NSI>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_PHASE, false, UNET_NSI>(k, L.N, s);
     }
-    if (L.in_relu) {         // operand = max(stored, 0) (conv3x3_pc<.., TMF | 0x100000>): the planar 16-output kernel -- the UNet's outermost transposed conv
+    if (L.in_relu) {         // operand = max(stored, 0) (conv3x3_pc<.., TMF | PC_BRELU>): the planar 16-output kernel -- the UNet's outermost transposed conv
         if (!(pc && L.out_mode == OUT_NCHW && nt == 1 && !L.res1 && !L.res2 && !L.conv7 && !L.stride2 && !L.conv7v && !L.conv1x1 && !L.gate_w && !L.fuse_w && !L.up && !L.reflect))
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: in_relu is built for the planar <= 16-output kernel");
-        return launch_pc<3, 1, 4, OUT_NCHW, false, false, 0x1001FF>(k, L.N, s);
+        return launch_pc<3, 1, 4, OUT_NCHW, false, false, TAPS_3X3 | PC_BRELU>(k, L.N, s);
     }
-    if (L.stride2) {         // Conv2d(k 4, s 2, p 1): H x W = the OUTPUT grid, source image 2H x 2W; panels from conv_pack_taps(K, 4C, 0x1B0), virtual channel
+    if (L.stride2) {         // Conv2d(k 4, s 2, p 1): H x W = the OUTPUT grid, source image 2H x 2W; panels from conv_pack_taps(K, 4C, TAPS_S2), virtual channel
                              // (2 pa + pb) * C + ci, tap (1 + dy, 1 + dx) = w[co][ci][2 dy + pa][2 dx + pb]
         if (!pc || L.out_mode != OUT_SLAB || (nt != 4 && nt != 2) || L.res1 || L.res2 || L.up || L.reflect || L.act > 2 || L.y0 != 0 || k.y1 != L.H ||
             L.dilation > 1 || L.dilation_groups || (long)L.H * L.W * 4 * 64 >= 0x7fffffffL || (nt == 2 && L.stats_part))
             return set_error(INNFER_ERR_UNSUPPORTED, "stride-2 conv: slab output of 32- / 64-channel tiles, no residual / upsampling / padding modes, sources below 33 M pixels");
         k.Hs = 2 * L.H; k.Ws = 2 * L.W; k.in_img_stride = (long)k.Hs * k.Ws * 32;
         k.nchunks = 4 * k.ncg;
-        if (nt == 2) return launch_pc<3, 2, 4, OUT_SLAB, false, false, 0x3B0>(k, L.N, s);
-        if (L.stats_part) return L.W <= 16 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x17B0, false, UNET_NSI>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x13B0, false, UNET_NSI>(k, L.N, s);
-        return L.W <= 16 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x7B0, false, UNET_NSI>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x3B0, false, UNET_NSI>(k, L.N, s);
+        if (nt == 2) return launch_pc<3, 2, 4, OUT_SLAB, false, false, TAPS_S2 | PC_S2>(k, L.N, s);
+        if (L.stats_part) return L.W <= 16 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_S2 | PC_S2 | PC_PAIR | PC_STATS, false, UNET_NSI>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_S2 | PC_S2 | PC_STATS, false, UNET_NSI>(k, L.N, s);
+        return L.W <= 16 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_S2 | PC_S2 | PC_PAIR, false, UNET_NSI>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_S2 | PC_S2, false, UNET_NSI>(k, L.N, s);
     }
     if (L.conv7v) {        // 7 x 1 column conv (padding 3 rows, zero or reflected) as three vertically displaced 3-tap blocks: panels from conv_pack7v, slab output
         if (!pc || L.out_mode != OUT_SLAB || (nt != 2 && nt != 4) || L.res1 || L.res2 || L.up || L.act > 2 || L.y0 != 0 || k.y1 != L.H || L.reflect == 2 ||
             (long)L.H * L.W * 64 >= 0x7fffffffL)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv7x1: slab output of 32- / 64-channel tiles, no residual / upsampling, images below 33 M pixels");
         k.nchunks = 3 * k.ncg; k.s9v = 1;
-        if (L.stats_part) return launch_pc<2, 4, 4, OUT_SLAB, true, false, 0x1092>(k, L.N, s);
-        return nt == 4 ? launch_pc<2, 4, 4, OUT_SLAB, true, false, 0x92>(k, L.N, s) : launch_pc<3, 2, 4, OUT_SLAB, true, false, 0x92>(k, L.N, s);
+        if (L.stats_part) return launch_pc<2, 4, 4, OUT_SLAB, true, false, TAPS_COL | PC_STATS>(k, L.N, s);
+        return nt == 4 ? launch_pc<2, 4, 4, OUT_SLAB, true, false, TAPS_COL>(k, L.N, s) : launch_pc<3, 2, 4, OUT_SLAB, true, false, TAPS_COL>(k, L.N, s);
     }
     if (L.conv1x1) {        // centre tap only: panels from conv_pack_1x1
         if (!pc || L.out_mode != OUT_SLAB || (nt != 2 && nt != 4))
             return set_error(INNFER_ERR_UNSUPPORTED, "conv1x1: slab outputs of 32- / 64-channel tiles on the producer-consumer kernel");
         if (L.prefix_lrelu) {
             if (nt != 4) return set_error(INNFER_ERR_UNSUPPORTED, "conv1x1: the running-sum operand is built for 64-channel tiles");
-            return launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x810>(k, L.N, s);
+            return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_1X1 | PC_PFX>(k, L.N, s);
         }
         // three input slots (a 1x1 stage has no halo): the loaders never pause between chunks -- about 1 % on PAN / PPON (kernel_experiments.txt 32)
-        return nt == 4 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x10, false, 3>(k, L.N, s) : launch_pc<2, 2, 4, OUT_SLAB, false, false, 0x10, false, 3>(k, L.N, s);
+        return nt == 4 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_1X1, false, 3>(k, L.N, s) : launch_pc<2, 2, 4, OUT_SLAB, false, false, TAPS_1X1, false, 3>(k, L.N, s);
     }
-    if (L.gate_w) {          // out = act(v * sigmoid(W v + b)), v = this conv's fp16 result (PAN's PA block behind an up-conv): conv3x3_pc<.., TMF | 0x80000>
+    if (L.gate_w) {          // out = act(v * sigmoid(W v + b)), v = this conv's fp16 result (PAN's PA block behind an up-conv): conv3x3_pc<.., TMF | PC_SGATE>
         if (!pc || L.out_mode != OUT_SLAB || nt != 2 || L.K != 32 || L.res1 || L.res2 || L.act > 2 || L.reflect || L.stats_part)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the self gate belongs to 32-output slab convs without residuals (act = the activation AFTER the gate)");
         k.sg_w = L.gate_w; k.sg_bias = L.gate_bias;
-        return launch_pc<3, 2, 4, OUT_SLAB, false, false, 0x801FF>(k, L.N, s);
+        return launch_pc<3, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_SGATE>(k, L.N, s);
     }
     if (pc && L.out_mode == OUT_SLAB && nt == 2 && !L.fuse_w) {
         // 32-output layers: 24-row tiles, two LDS stages.  pc 5 (diagnostic builds): 16-row tiles on the three-slot input ring (continuous LDS-DMA
         // issue) -- measured within +-1 % of the default on the frame and on the chop path (profiles/r2/kernel_experiments.txt), so the simpler form ships
-        if (pc == 5) return launch_pc<2, 2, 4, OUT_SLAB, false, false, 0x1FF, false, 3>(k, L.N, s);
-        if (INNFER_KNOB("INNFER_FAT", 0) & 1) return launch_pc<6, 2, 4, OUT_SLAB, false, false, 0x1FF, false, 2, 4>(k, L.N, s);
+        if (pc == 5) return launch_pc<2, 2, 4, OUT_SLAB, false, false, TAPS_3X3, false, 3>(k, L.N, s);
+        if (INNFER_KNOB("INNFER_FAT", 0) & 1) return launch_pc<6, 2, 4, OUT_SLAB, false, false, TAPS_3X3, false, 2, 4>(k, L.N, s);
         return pc == 2 ? launch_pc<3, 2, 8>(k, L.N, s) : pc == 3 ? launch_pc<2, 2, 4>(k, L.N, s) : launch_pc<3, 2, 4>(k, L.N, s);
     }
-    if (L.fuse_w) {          // HR_conv0 with the network's last conv in its epilogue (conv3x3_pc<.., TMF | 0x20000>) + the rim pass
+    if (L.fuse_w) {          // HR_conv0 with the network's last conv in its epilogue (conv3x3_pc<.., TMF | PC_FUSE>) + the rim pass
         if (!conv_fuse_last_ok(L)) return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the fused last conv needs 64 or 32 output channels, whole 16 x 32 tiles, act 0..2, no residual / upsampling / row range");
         k.fl_w = L.fuse_w; k.fl_bias = L.fuse_bias; k.fl_side = L.fuse_side; k.fl_out = L.fuse_out; k.fl_oc = L.fuse_oc; k.fl_out_mode = L.fuse_out_mode;
         if (nt == 2 && L.rowp) return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the fused last conv behind a 32-channel conv takes lane-contiguous panels");
-        if (int rc = nt == 2 ? launch_pc<2, 2, 4, OUT_SLAB, false, false, 0x201FF>(k, L.N, s)
-                             : L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x4201FF>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x201FF>(k, L.N, s)) return rc;
+        if (int rc = nt == 2 ? launch_pc<2, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_FUSE>(k, L.N, s)
+                             : L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_FUSE | PC_ROWP>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_FUSE>(k, L.N, s)) return rc;
         const long nthr = (long)L.N * (L.H / 16) * (L.W / 32) * 92;
         hipLaunchKernelGGL(fuse_combine_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, (const float*)L.fuse_side, L.fuse_bias, L.fuse_out, L.fuse_out_mode, L.out_denorm, L.out_round16, L.fuse_oc,
                            L.N, L.H, L.W);
@@ -1283,23 +1253,23 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
             (long)L.N * L.H * L.W * 64 * 4 >= 0x7fffffffL)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the phase-major PixelShuffle(2) store needs K %% 256 == 0 (64-channel phases), act 0..2, no residual / upsampling / row range, < 2 GiB per output group");
         k.phase_c = L.K / 4;
-        return launch_pc<2, 4, 4, OUT_SLAB, false, false, 0xC001FF>(k, L.N, s);
+        return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP | PC_PSH>(k, L.N, s);
     }
-    if (pc && L.out_mode == OUT_SLAB && nt == 4 && L.stats_part) return launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x11FF>(k, L.N, s);
+    if (pc && L.out_mode == OUT_SLAB && nt == 4 && L.stats_part) return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_STATS>(k, L.N, s);
     if (pc && L.out_mode == OUT_SLAB && nt == 4 && L.res1_lds && L.res1 && L.res1 == L.in && L.res1_gstride == L.in_gstride && L.act == 0 && L.K == 64 && L.C >= 96 &&
         !L.up && !L.reflect && L.s1 != 0.f && (L.res1_lds == 2 || L.res2)) {
-        // the dense block's last conv: the residual is the conv's own input groups 0 and 1 -- taken from the live LDS stages (conv3x3_pc<.., TMF | 0x40000>).
+        // the dense block's last conv: the residual is the conv's own input groups 0 and 1 -- taken from the live LDS stages (conv3x3_pc<.., TMF | PC_RLDS>).
         // res1_lds 1 (the networks' default): only where a SECOND residual follows (the last dense block of an RRDB) -- there the epilogue could not batch two
         // residuals' loads beside the accumulators and ran 15 % behind the one-residual layers; with x from LDS it keeps ONE memory residual and batches it
         // (0.4096 -> 0.3945 ms per launch at 1080p).  The one-residual layers' batched loads were L2 hits already hidden behind the tile's last MFMAs: the LDS
         // form costs them +0.9 % (0.3574 -> 0.3607 ms), so they keep the epilogue load; res1_lds 2 forces the LDS form everywhere (profiles/r4/rlds_ab.txt).
         k.rs1 = 1.0f / L.s1;
-        return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x4401FF>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x401FF>(k, L.N, s);
+        return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_RLDS | PC_ROWP>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_RLDS>(k, L.N, s);
     }
     if (pc && L.out_mode == OUT_SLAB && nt == 4) {
         // diagnostic builds: four consumer waves of twice the rows (measured within +-1 %: profiles/r2/kernel_experiments.txt 10)
-        if (!L.rowp && (INNFER_KNOB("INNFER_FAT", 0) & 2)) return launch_pc<4, 4, 4, OUT_SLAB, false, false, 0x1FF, false, 2, 4>(k, L.N, s);
-        return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, 0x4001FF>(k, L.N, s) : launch_pc<2, 4, 4>(k, L.N, s);
+        if (!L.rowp && (INNFER_KNOB("INNFER_FAT", 0) & 2)) return launch_pc<4, 4, 4, OUT_SLAB, false, false, TAPS_3X3, false, 2, 4>(k, L.N, s);
+        return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP>(k, L.N, s) : launch_pc<2, 4, 4>(k, L.N, s);
     }
     if (L.conv7) {         // 7x7 (padding 3) as nine displaced 3x3 convs: planar output, <= 16 output channels, panels from conv_pack7x7
         if (!pc || L.out_mode != OUT_NCHW || nt != 1 || L.res1 || L.res2 || L.up || (long)L.H * L.W * 64 >= 0x7fffffffL)

@@ -3,7 +3,7 @@
 // included there, inside namespace innfer { namespace { .. } }, after KP / the tile constants.  Not a stand-alone header.
 
 // Offsets of accumulator tile t of a lane from the lane's first channel, in a slab of group stride g (f16 elements) and in a linear channel array (bias), and the lane's
-// first channel inside its 16 NT-channel group.  ROWP (conv3x3_pc<.., TMF | 0x400000>, 64-channel groups): the PLANE row order -- accumulator (tile t, row 4 lg + j) is
+// first channel inside its 16 NT-channel group.  ROWP (conv3x3_pc<.., TMF | PC_ROWP>, 64-channel groups): the PLANE row order -- accumulator (tile t, row 4 lg + j) is
 // channel 32 (t >> 1) + 8 lg + 4 (t & 1) + j instead of 16 lg + 4 t + j: a lane's sixteen channels are 16 bytes in EACH of the group's two 32-channel slab planes, lanes
 // lg = 0..3 cover a pixel's whole 64 bytes of one plane, and a store / residual-load instruction touches ONE plane -- half the lines per instruction (measured as an
 // ablation first: frame -1.4 %, profiles/r4/upconv_bound.txt).  Panels from conv_pack*(.., rowp = 1).
@@ -92,9 +92,9 @@ __device__ __forceinline__ void epilogue_slab_cv(const KP& p, f32x4 (&acc)[NT][2
     }
 }
 
-// DCV (conv3x3_pc<.., TM = 0x1B>: one output phase of ConvTranspose2d(4, 2, 1) per 16*NT-channel group): (ty0, tx0) are coordinates of the phase's
+// DCV (conv3x3_pc<.., TM = TAPS_PHASE>: one output phase of ConvTranspose2d(4, 2, 1) per 16*NT-channel group): (ty0, tx0) are coordinates of the phase's
 // shifted lattice (see decode); virtual pixel (y', x') of phase (a, b) is output pixel (2y' - a, 2x' - b) of the 2H x 2W slab, channel ch % phase_c.
-// PSH (conv3x3_pc<.., TMF | 0x800000>: nn.PixelShuffle(2) as the store, block.py:333-346): the K = 4 * phase_c conv channels arrive PHASE-MAJOR (panels from
+// PSH (conv3x3_pc<.., TMF | PC_PSH>: nn.PixelShuffle(2) as the store, block.py:333-346): the K = 4 * phase_c conv channels arrive PHASE-MAJOR (panels from
 // conv_pack_shuffle2: channel ph * phase_c + oc is reference channel 4 oc + ph), so a 64-channel group is one output phase (a, b) = (ph >> 1, ph & 1) of
 // 64 consecutive output channels: the DCV store without the lattice shift -- pixel (y, x) of the conv grid goes to (2y + a, 2x + b).
 template <int RPW, int NT, int ACT, bool R1, bool R2, bool HOIST, bool POLY = false, bool DCV = false, bool PAIR = false, bool SC1 = false, bool ROWP = false, bool PSH = false>
@@ -212,7 +212,7 @@ __device__ __forceinline__ void epilogue_slab(const KP& p, f32x4 (&acc)[NT][2 * 
     }
 }
 
-// SPLIT (fp32-accurate mode, conv3x3_pc<.., TMF | 0x2000>): a tensor is a PAIR of fp16 slabs -- hi = fp16(x) and lo = fp16((x - hi) * 2^11), the lo slab a
+// SPLIT (fp32-accurate mode, conv3x3_pc<.., TMF | PC_SPLIT>): a tensor is a PAIR of fp16 slabs -- hi = fp16(x) and lo = fp16((x - hi) * 2^11), the lo slab a
 // fixed distance behind the hi slab -- i.e. 22 significant bits per value with the fp16 kernels' data path.  The epilogue works on the fp32
 // accumulators exactly like the fp16 one (activation, *s1 + res1, *s2 + res2 with explicit fmaf) but reads its residuals as hi + lo * 2^-11 (exact
 // in fp32) and stores both parts.  CV: image-canvas addressing (see epilogue_slab_cv).

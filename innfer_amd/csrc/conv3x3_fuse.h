@@ -1,8 +1,8 @@
-// FUSE (conv3x3_pc<.., TMF | 0x20000>): HR_conv0 -> conv_last in one kernel -- ring index, pixel store, the fused epilogue and the rim pass.
+// FUSE (conv3x3_pc<.., TMF | PC_FUSE>): HR_conv0 -> conv_last in one kernel -- ring index, pixel store, the fused epilogue and the rim pass.
 // Part of csrc/conv3x3.hip (split out in round 5, VERDICT r4 item 7: no functional change -- the device assembly of the translation unit is identical);
 // included there, inside namespace innfer { namespace { .. } }, after KP / the tile constants.  Not a stand-alone header.
 
-// FUSE (conv3x3_pc<.., TMF | 0x20000>): index of a pixel of a tile's 18 x 34 neighbourhood (Y in [-1, 16], X in [-1, 32]) that is NOT at least one pixel inside
+// FUSE (conv3x3_pc<.., TMF | PC_FUSE>): index of a pixel of a tile's 18 x 34 neighbourhood (Y in [-1, 16], X in [-1, 32]) that is NOT at least one pixel inside
 // the tile, among the 192 such pixels: rows -1, 0 (34 each), rows 15, 16 (34 each), then columns -1, 0, 31, 32 of rows 1 .. 14
 __host__ __device__ inline int fuse_ring_index(int Y, int X) {
     if (Y <= 0) return (Y + 1) * 34 + X + 1;

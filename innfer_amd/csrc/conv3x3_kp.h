@@ -5,6 +5,23 @@ constexpr int TW = 32;        // tile width (pixels)
 constexpr int LWP = 36;       // LDS row pitch (pixels): 36 px = 2304 B = 9 x 256 B, so every row starts on bank 0
 constexpr int LVALID = TW + 2;
 
+// The dynamic LDS of conv3x3_pc<RPW, NT, .., TMF, .., NSI, NCW>, for the kernel and its launcher alike: NSI input slots (a halo tile each) and two weight
+// slots (a panel each) -- NSI 2: two stages [tile | panel]; NSI 3: three tiles, then two panels -- and behind them the tail of the ONE mode that has one.
+template <int RPW, int NT, int NSI, int NCW, int TMF>
+struct PcLayout {
+    static constexpr int TH = NCW * RPW;                                       // tile rows
+    static constexpr int IN_BYTES = (((TH + 2) * LWP + 15) / 16) * 1024;       // halo tile: whole 1 KB LDS-DMA pieces of 16 pixels
+    static constexpr int NTAP = (TMF & PC_UP4) ? 4 : __builtin_popcount(TMF & TAPS_3X3);   // taps in the panel, in (r, s) order (UP4: a phase's 2 x 2 block)
+    static constexpr int W_BYTES = NTAP * NT * 16 * 64;
+    static constexpr int STAGE = IN_BYTES + W_BYTES;
+    static constexpr int TAIL = NSI * IN_BYTES + 2 * W_BYTES;                  // (NSI 2: 2 * STAGE)
+    static constexpr int FUSE_BYTES = (TMF & PC_FUSE) ? 4096 : 0;              // the last conv's panel
+    static constexpr int UP4_BYTES = (TMF & PC_UP4) ? 1024 : 0;                // the four phases' biases
+    static constexpr int PRELU_BYTES = (TMF & PC_PRELU) ? NCW * 256 : 0;       // the slopes, once per consumer wave
+    static_assert((FUSE_BYTES != 0) + (UP4_BYTES != 0) + (PRELU_BYTES != 0) <= 1, "the tail users share one offset: at most one per instantiation");
+    static constexpr int LDS_BYTES = TAIL + FUSE_BYTES + UP4_BYTES + PRELU_BYTES;
+};
+
 
 struct KP {
     const f16* in; long in_img_stride; long in_gbytes; int nchunks;   // gbytes: bytes between channel groups
@@ -27,26 +44,26 @@ struct KP {
                              // tiles [rate_start[g], rate_start[g+1]) of the launch belong to it (dil unused)
     int dil, fullH, fullW;   // POLY kernels: dilation d; H, W, N are those of the d*d polyphase sub-images (ceil(fullH/d) x ceil(fullW/d), N*d*d of them)
     int ncg;                 // S9 kernels: real 32-channel groups of the input (nchunks = 9 * ncg virtual chunks)
-    float* stats_part;       // STATS kernels (TMF | 0x1000): per-(tile[, phase], consumer wave, channel) partial statistics (count, mean, M2) of the conv result
+    float* stats_part;       // STATS kernels (TMF | PC_STATS): per-(tile[, phase], consumer wave, channel) partial statistics (count, mean, M2) of the conv result
     int stats_cn;            //   channels of the output slab (K, or phase_c behind the phase lattice)
     int s9v;                 // S9 kernels: only the three VERTICAL displacements (a 7-tap column conv as three 3-tap blocks; nchunks = 3 * ncg)
     int reflect;             // out-of-image taps read the mirrored pixel (nn.ReflectionPad2d(1)) instead of zero; not with `up`
     int phase_c;             // OUT_NCHW: > 0 = channel ch is phase (ch / phase_c) of a 2x transposed conv: channel ch % phase_c at (2y + ph/2, 2x + ph%2)
     int total;               // tiles x channel groups of this launch
     int cv_gx, cv_gy, cv_h1, cv_w1;   // CV kernels (image canvas): the N images are the cells of a cv_gx x cv_gy grid, cell pitch (H + 1) x (W + 1)
-    // FUSE kernels (TMF | 0x20000): the network's LAST conv (64 -> fl_oc <= 3 planar channels, no activation) inside this conv's epilogue -- see fused_last_epilogue
+    // FUSE kernels (TMF | PC_FUSE): the network's LAST conv (64 -> fl_oc <= 3 planar channels, no activation) inside this conv's epilogue -- see fused_last_epilogue
     const f16* fl_w;         //   its weights as four MFMA A fragments [row tile 2][k-step 2][lane 64][8] (conv_pack_fuse_last)
     const float* fl_bias;    //   fl_oc biases
     float* fl_side;          //   per tile 192 x 3 partial sums of the pixels within one pixel of a tile edge (conv_fuse_combine finishes them)
     void* fl_out;            //   the planar [N, fl_oc, H, W] result
     int fl_oc, fl_out_mode;  //   0 fp16, 1 fp32 planar; 2 the uint8 HWC image (out_denorm / out_round16 as for the planar kernels)
-    const f16* sg_w;         // SGATE kernels (TMF | 0x80000): a 1x1 conv of this conv's own fp16 result gates it -- out = v * sigmoid(W v + b): two A fragments [t][lane][8] (conv_pack_selfgate), 32 biases
+    const f16* sg_w;         // SGATE kernels (TMF | PC_SGATE): a 1x1 conv of this conv's own fp16 result gates it -- out = v * sigmoid(W v + b): two A fragments [t][lane][8] (conv_pack_selfgate), 32 biases
     union {                  // (one slot: no kernel is both, and the argument block of every other instantiation keeps its layout)
         const float* sg_bias;
-        const float* slope;  // PRELU kernels (TMF | 0x1000000): per-channel slopes of the act-8 epilogue, padded and indexed like `bias`
+        const float* slope;  // PRELU kernels (TMF | PC_PRELU): per-channel slopes of the act-8 epilogue, padded and indexed like `bias`
     };
-    float rs1;               // RLDS kernels (TMF | 0x40000): 1 / s1 -- the residual res1 (= the conv's own input groups 0, 1) is added to the accumulators as x / s1 from the live LDS stage
-    long in_lo_bytes;        // SPLIT kernels (TMF | 0x2000): the low-part twin of the input slab lies this many bytes behind it,
+    float rs1;               // RLDS kernels (TMF | PC_RLDS): 1 / s1 -- the residual res1 (= the conv's own input groups 0, 1) is added to the accumulators as x / s1 from the live LDS stage
+    long in_lo_bytes;        // SPLIT kernels (TMF | PC_SPLIT): the low-part twin of the input slab lies this many bytes behind it,
     long out_lo, res1_lo, res2_lo;   //   those of the output / residual slabs this many ELEMENTS behind them
 #ifdef INNFER_ABLATE
     int abl;                 // diagnostic build only: 1 no stores, 2 no weight DMA, 4 no input DMA, 8 no MFMA phase

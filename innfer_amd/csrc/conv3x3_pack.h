@@ -44,7 +44,7 @@ void conv_pack(const float* w, int K, int C, void* packed, int rowp) {
 
 // PixelShuffle(2) behind a conv (block.py:333-346): the K conv channels in PHASE-MAJOR order -- packed channel ph * (K / 4) + oc is reference channel 4 oc + ph,
 // ph = 2 a + b the position (a, b) inside the 2 x 2 output block (nn.PixelShuffle: out[oc][2y + a][2x + b] = in[4 oc + 2a + b][y][x]) -- in the plane row order:
-// the panels of conv3x3_pc<.., TMF | 0x800000> (ConvLaunch.rowp = 2 with OUT_SHUFFLE2).  bias_out (K floats, may be null with bias null) in the same order.
+// the panels of conv3x3_pc<.., TMF | PC_PSH> (ConvLaunch.rowp = 2 with OUT_SHUFFLE2).  bias_out (K floats, may be null with bias null) in the same order.
 void conv_pack_shuffle2(const float* w, const float* bias, int K, int C, void* packed, float* bias_out) {
     const int pc = K / 4;
     std::vector<float> wp((size_t)K * C * 9);
@@ -56,7 +56,7 @@ void conv_pack_shuffle2(const float* w, const float* bias, int K, int C, void* p
     conv_pack(wp.data(), K, C, packed, 1);
 }
 
-// Panels holding only the taps of `mask` (bit r*3+s), in (r, s) order: [group][chunk][tap rank][row R][slot][8 ch]; mask 0x10 = a 1x1 conv,
+// Panels holding only the taps of `mask` (bit r*3+s), in (r, s) order: [group][chunk][tap rank][row R][slot][8 ch]; mask TAPS_1X1 = a 1x1 conv,
 // w then is [K][C] (one value per pair) -- the counterpart of conv3x3_pc<.., TM>
 // The gate matrix of ConvLaunch.gate_w: w [32][32] (out, in; zero rows / columns beyond the real channels) as the two MFMA A fragments [t][lane][8]:
 // lane (rho = lane & 15, octet = lane >> 4) of tile t holds w[8 (rho >> 2) + 4 t + (rho & 3)][8 octet .. + 7] (the NT = 2 row order of conv_pack)
@@ -69,7 +69,7 @@ void conv_pack_selfgate(const float* w32x32, void* packed_2k) {
         }
 }
 
-size_t conv_packed_bytes_taps(int K, int C, int mask) { return conv_packed_bytes(K, C) / 9 * __builtin_popcount(mask & 0x1FF); }
+size_t conv_packed_bytes_taps(int K, int C, int mask) { return conv_packed_bytes(K, C) / 9 * __builtin_popcount(mask & TAPS_3X3); }
 // any mask: w is [K][C][9] (taps outside the mask are not read)
 void conv_pack_taps(const float* w, int K, int C, int mask, void* packed, int rowp) {
     const int nt = conv_nt_for(K), rows = nt * 16, groups = conv_groups(K), nch = C / 32;
@@ -129,9 +129,9 @@ void conv_pack_1x1(const float* w, int K, int C, void* packed) {
 
 // 7x7 weights [K][C][7][7] -> panels of the equivalent conv over 9*C virtual channels (conv3x3_pc<.., S9>): virtual channel sub*C + ci,
 // tap (r, s) holds w[k][ci][3*(sub/3) + r - 1][3*(sub%3) + s - 1] (zero outside the 7x7 kernel: the 9x9 padding ring)
-// Conv2d(k 4, s 2, p 1) for the stride-2 gather loader (ConvLaunch.stride2): w [K][C][4][4] -> panels over 4 * C virtual channels, mask 0x1B0;
+// Conv2d(k 4, s 2, p 1) for the stride-2 gather loader (ConvLaunch.stride2): w [K][C][4][4] -> panels over 4 * C virtual channels, mask TAPS_S2;
 // virtual channel (2 pa + pb) * C + ci, tap (1 + dy, 1 + dx) = w[co][ci][2 dy + pa][2 dx + pb]
-size_t conv_packed_bytes_s2k4(int K, int C) { return conv_packed_bytes_taps(K, 4 * C, 0x1B0); }
+size_t conv_packed_bytes_s2k4(int K, int C) { return conv_packed_bytes_taps(K, 4 * C, TAPS_S2); }
 void conv_pack_s2k4(const float* w, int K, int C, void* packed) {
     const int C4 = 4 * C;
     std::vector<float> w3((size_t)K * C4 * 9, 0.f);
@@ -141,14 +141,14 @@ void conv_pack_s2k4(const float* w, int K, int C, void* packed) {
                 for (int dy = 0; dy < 2; ++dy)
                     for (int dx = 0; dx < 2; ++dx)
                         w3[((size_t)co * C4 + ph * C + ci) * 9 + (1 + dy) * 3 + 1 + dx] = w[(((size_t)co * C + ci) * 4 + 2 * dy + (ph >> 1)) * 4 + 2 * dx + (ph & 1)];
-    conv_pack_taps(w3.data(), K, C4, 0x1B0, packed);
+    conv_pack_taps(w3.data(), K, C4, TAPS_S2, packed);
 }
 
 // ConvTranspose2d(k, stride 2, padding 1[, output_padding 1 for k == 3]) for ConvLaunch.deconv_phases: w [C][K][k][k] (torch's layout) -> panels of
-// 4 * K phase-major output channels, mask 0x1B.  Output phase (a, b) taken at the virtual pixel (y + a, x + b) reads taps (dy, dx) in {-1, 0}^2;
+// 4 * K phase-major output channels, mask TAPS_PHASE.  Output phase (a, b) taken at the virtual pixel (y + a, x + b) reads taps (dy, dx) in {-1, 0}^2;
 // tap (r, s) of the 3x3 lattice (r, s in {0, 1}) carries w[ci][c][3 - 2r - a][3 - 2s - b] (oy = 2 iy - 1 + ky); a kernel index of 3 does not
 // exist for k == 3: a structural zero (9 of the 16 phase taps are real there)
-size_t conv_packed_bytes_deconv2x(int K, int C) { return conv_packed_bytes_taps(4 * K, C, 0x1B); }
+size_t conv_packed_bytes_deconv2x(int K, int C) { return conv_packed_bytes_taps(4 * K, C, TAPS_PHASE); }
 void conv_pack_deconv2x(const float* w, int K, int C, int k, void* packed, int rowp) {
     const int K4 = 4 * K;
     std::vector<float> w3((size_t)K4 * C * 9, 0.f);
@@ -161,7 +161,7 @@ void conv_pack_deconv2x(const float* w, int K, int C, int k, void* packed, int r
                 for (int ci = 0; ci < C; ++ci) w3[((size_t)co * C + ci) * 9 + r * 3 + sx] = w[(((size_t)ci * K + c) * k + ky) * k + kx];
             }
     }
-    conv_pack_taps(w3.data(), K4, C, 0x1B, packed, rowp);
+    conv_pack_taps(w3.data(), K4, C, TAPS_PHASE, packed, rowp);
 }
 
 // nearest-2x + conv3x3 (upconv_block, block.py:348-361) as ConvTranspose2d(4, 2, 1): w [K][C][3][3] -> the phase panels of conv_pack_deconv2x with the taps that meet the same
@@ -184,8 +184,8 @@ void conv_pack_up2x_phases(const float* w, int K, int C, void* packed, int rowp)
 }
 
 // 7 x 1 column conv (ConvLaunch.conv7v): w [K][C][7] -> three 3-tap blocks (the 7 taps zero-padded to 9: tap k9 = k7 + 1), virtual channel
-// block * C + ci, centre-column taps only (mask 0x92)
-size_t conv_packed_bytes7v(int K, int C) { return conv_packed_bytes_taps(K, 3 * C, 0x92); }
+// block * C + ci, centre-column taps only (mask TAPS_COL)
+size_t conv_packed_bytes7v(int K, int C) { return conv_packed_bytes_taps(K, 3 * C, TAPS_COL); }
 void conv_pack7v(const float* w, int K, int C, void* packed) {
     const int C3 = 3 * C;
     std::vector<float> w3((size_t)K * C3 * 9, 0.f);
@@ -196,7 +196,7 @@ void conv_pack7v(const float* w, int K, int C, void* packed) {
                 if (ky < 0 || ky > 6) continue;
                 for (int ci = 0; ci < C; ++ci) w3[((size_t)co * C3 + sb * C + ci) * 9 + r * 3 + 1] = w[((size_t)co * C + ci) * 7 + ky];
             }
-    conv_pack_taps(w3.data(), K, C3, 0x92, packed);
+    conv_pack_taps(w3.data(), K, C3, TAPS_COL, packed);
 }
 
 // partial-statistics records (3 floats each per channel) an image contributes with ConvLaunch.stats_part: tiles of 16 x 32 pixels over the kernel's

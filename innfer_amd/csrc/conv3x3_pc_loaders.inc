@@ -318,7 +318,7 @@
         if constexpr (FUSE) {                 // the last conv's four A fragments (4 KB) behind the two stages, once per workgroup
 #if defined(__HIP_DEVICE_COMPILE__)
             const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)p.fl_w, 0, 4096, 0x00020000);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rf, (__attribute__((address_space(3))) void*)(smem + 2 * STAGE + lw * 1024), 16, lane * 16, lw * 1024, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rf, (__attribute__((address_space(3))) void*)(smem + L::TAIL + lw * 1024), 16, lane * 16, lw * 1024, 0, 0);
 #endif
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

@@ -7,8 +7,8 @@
                 if (p.act == 1) EPI(1, false, false); else if (p.act == 2) EPI(2, false, false); else EPI(0, false, false);
             } else if (!p.res2) {
                 if (p.act == 1) EPI(1, true, false); else if (p.act == 2) EPI(2, true, false);
-                else if (NT == 2 && TM == 0x10 && p.act == 4) EPI((NT == 2 && TM == 0x10) ? 4 : 0, true, false);         // (the PA gate: the 32-channel 1x1 kernel only)
-                else if (NT == 2 && TM == 0x10 && p.act == 5) EPI((NT == 2 && TM == 0x10) ? 5 : 0, true, false);
+                else if (NT == 2 && TM == TAPS_1X1 && p.act == 4) EPI((NT == 2 && TM == TAPS_1X1) ? 4 : 0, true, false);         // (the PA gate: the 32-channel 1x1 kernel only)
+                else if (NT == 2 && TM == TAPS_1X1 && p.act == 5) EPI((NT == 2 && TM == TAPS_1X1) ? 5 : 0, true, false);
                 else EPI(0, true, false);
             } else {
                 if (p.act == 1) EPI(1, true, true); else if (p.act == 2) EPI(2, true, true); else EPI(0, true, true);
@@ -33,7 +33,7 @@
 #undef EPI
             } else if constexpr (FUSE) {
                 const int lidf = run_start + (p.rev ? run_len - 1 - (jt - slots) : (jt - slots));         // (jt was advanced above; KG == 1: the tile index)
-                fused_last_epilogue<RPW, NT>(p, acc, smem + ((g & 1) * STAGE), smem + 2 * STAGE, n, ty0, tx0, cw, lane, lidf);
+                fused_last_epilogue<RPW, NT>(p, acc, smem + ((g & 1) * STAGE), smem + L::TAIL, n, ty0, tx0, cw, lane, lidf);
             } else if constexpr (PRELU) {
                 // act 8 (SRVGGNetCompact): the lane's slopes come back from the wave's LDS copy (same channels as bias_r[t]; KG == 1); plain slab store, no residual
                 f32x4 slope_r[NT];
@@ -43,12 +43,12 @@
             } else if constexpr (OUTMODE == OUT_SLAB) {
             if constexpr (STATS) {
                 const int lid = run_start + (p.rev ? run_len - 1 - (jt - slots) : (jt - slots));         // (jt was advanced above)
-                epilogue_stats<RPW, NT, TM == 0x1B, PAIR, NCW>(p, acc, bias_r, ty0, tx0, cw, li, cbase, lid / p.KG);
+                epilogue_stats<RPW, NT, TM == TAPS_PHASE, PAIR, NCW>(p, acc, bias_r, ty0, tx0, cw, li, cbase, lid / p.KG);
             }
-#define EPI(A, B, C) epilogue_slab<RPW, NT, A, B, C, !(C), POLY, TM == 0x1B, PAIR, false, ROWP, PSH>(p, acc, n, ty0, tx0, cw, li, cbase, dcur)
+#define EPI(A, B, C) epilogue_slab<RPW, NT, A, B, C, !(C), POLY, TM == TAPS_PHASE, PAIR, false, ROWP, PSH>(p, acc, n, ty0, tx0, cw, li, cbase, dcur)
             if (!p.res1) {
                 if (p.act == 1) EPI(1, false, false); else if (p.act == 2) EPI(2, false, false);
-                else if (NT == 4 && TM == 0x1FF && !POLY && !ROWP && p.act == 7) EPI((NT == 4 && TM == 0x1FF && !POLY && !ROWP) ? 7 : 0, false, false); else EPI(0, false, false);
+                else if (NT == 4 && TM == TAPS_3X3 && !POLY && !ROWP && p.act == 7) EPI((NT == 4 && TM == TAPS_3X3 && !POLY && !ROWP) ? 7 : 0, false, false); else EPI(0, false, false);
             } else if (!p.res2) {
                 if (p.act == 1) EPI(1, true, false); else if (p.act == 2) EPI(2, true, false); else if (p.act == 4) EPI(4, true, false);
                 else if (p.act == 5) EPI(5, true, false); else EPI(0, true, false);

@@ -1,4 +1,4 @@
-// conv3x3_pc, UP4 (TMF | 0x200000): the consumer waves' own walk of the one-visit up-conv -- four phases per tile as straight-line code.
+// conv3x3_pc, UP4 (TMF | PC_UP4): the consumer waves' own walk of the one-visit up-conv -- four phases per tile as straight-line code.
 // A fragment of the BODY of conv3x3_pc (csrc/conv3x3.hip), included there textually (round 5, VERDICT r4 item 7: the kernel body was 940 lines; no functional
 // change -- the device assembly of the translation unit is identical).  It uses the kernel's locals and compile-time flags; not a stand-alone file.
     if constexpr (UP4) {
@@ -6,7 +6,7 @@
         // a `switch` over the phase inside the generic step loop made the allocator carry them across all four unrolled bodies: 344 bytes of scratch per lane) ----
         // the four phases' biases (256 floats) in the 1 KB behind the weight ring: a phase starts from four ds_read_b128 instead of holding sixteen bias registers
         // across the phase before it (the kernel sits at the 168-register budget of a 12-wave workgroup)
-        float* const bias_lds = (float*)(smem + 3 * IN_BYTES + 2 * W_BYTES);
+        float* const bias_lds = (float*)(smem + L::TAIL);
         if (cw == 0) *(f32x4*)(bias_lds + 4 * lane) = *(const f32x4*)(p.bias + 4 * lane);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         asm volatile("s_barrier" ::: "memory");                   // both groups of the first tile and the first panel have landed
@@ -38,7 +38,7 @@
                     const int sl = slot0 + cg;
                     const char* st = smem + (sl >= 3 ? sl - 3 : sl) * IN_BYTES;
                     const char* sw = smem + 3 * IN_BYTES + cg * W_BYTES;              // (eight steps per tile: the step's parity is the group)
-                    if (!no_mfma) four_tap(std::integral_constant<int, (0x1B << (3 * A + B))>{}, acc, st, sw);
+                    if (!no_mfma) four_tap(std::integral_constant<int, (TAPS_PHASE << (3 * A + B))>{}, acc, st, sw);
                     if (cg == 1) {       // the phase's 16 x 32 virtual pixels go out through the phase-lattice epilogue (tile origin shifted by (a, b))
                         if (p.act == 1) epilogue_slab<RPW, NT, 1, false, false, true, false, true, false, false, ROWP>(p, acc, n, ty0 + A, tx0 + B, cw, li_t, cbase);
                         else if (p.act == 2) epilogue_slab<RPW, NT, 2, false, false, true, false, true, false, false, ROWP>(p, acc, n, ty0 + A, tx0 + B, cw, li_t, cbase);

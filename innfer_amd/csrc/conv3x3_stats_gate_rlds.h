@@ -74,7 +74,7 @@ __device__ __forceinline__ void epilogue_stats(const KP& p, const f32x4 (&acc)[N
     }
 }
 
-// SGATE (conv3x3_pc<.., TMF | 0x80000>): v = fp16(acc) is the B fragment of the 32 x 32 gate matrix (a lane's 8 accumulators are 8 consecutive channels of its pixel);
+// SGATE (conv3x3_pc<.., TMF | PC_SGATE>): v = fp16(acc) is the B fragment of the 32 x 32 gate matrix (a lane's 8 accumulators are 8 consecutive channels of its pixel);
 // acc <- v * sigmoid(W v + b).  Sigmoid on the hardware exponential / reciprocal: at 2160 x 3840 this epilogue evaluates 265 M of them (the libm forms were 0.3 of the launch).
 template <int MT>
 __device__ __forceinline__ void self_gate(f32x4 (&acc)[2][MT], const f16x8* sgw, const f32x4* sgb) {
@@ -122,7 +122,7 @@ __device__ __forceinline__ void self_gate_split(f32x4 (&acc)[2][MT], const f16x8
     }
 }
 
-// RLDS (conv3x3_pc<.., TMF | 0x40000>): the lane's 16 residual channels of each of its MT pixel tiles from the live LDS stage `st` (byte offsets roffs), added to the fp32
+// RLDS (conv3x3_pc<.., TMF | PC_RLDS>): the lane's 16 residual channels of each of its MT pixel tiles from the live LDS stage `st` (byte offsets roffs), added to the fp32
 // accumulators as x / s1 (rs1 = 1 / s1)
 template <int MT>
 __device__ __forceinline__ void residual_from_lds(f32x4 (&acc)[4][MT], const char* st, const int* roffs, float rs1) {

@@ -133,20 +133,11 @@ __global__ __launch_bounds__(256) void first_conv_unshuffle(const UP p) {
     }
 }
 
-int current_dev() {
-    int dev = 0;
-    return hipGetDevice(&dev) == hipSuccess && dev >= 0 ? dev : 0;
-}
-
 template <int NT, int R, int KIND>
 int launch_one(const UP& p, dim3 grid, hipStream_t s) {
     constexpr int LDS = unsh_steps(R) * NT * 2048;
-    static unsigned long long attr_done = 0;                          // (per device, as conv3x3.hip's ensure_lds_attr)
-    const unsigned long long bit = 1ull << (current_dev() & 63);
-    if (!(attr_done & bit)) {
-        INNFER_HIP(hipFuncSetAttribute((const void*)first_conv_unshuffle<NT, R, KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
-        attr_done |= bit;
-    }
+    static std::atomic<unsigned long long> attr_done{0};
+    INNFER_HIP(ensure_lds_attr(first_conv_unshuffle<NT, R, KIND>, LDS, attr_done));
     hipLaunchKernelGGL((first_conv_unshuffle<NT, R, KIND>), grid, dim3(256), LDS, s, p);
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;

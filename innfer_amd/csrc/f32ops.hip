@@ -13,7 +13,6 @@
 //   * zero padding = the validity test of a tap; input views with a channel offset / stride: torch.cat is an offset, never a copy
 //   epilogue: v = acc + bias; v = mul * sigmoid(v) (pixel attention, PAN_arch.py:21-55); activation; + residual; stored through an output view
 // GEMM view: rows = 16 output channels (A = weights), columns = 16 consecutive output pixels (B = gathered input), reduction = (tap, 4 channels) per MFMA.
-#include <atomic>
 #include <algorithm>
 #include "common.h"
 
@@ -428,13 +427,7 @@ __global__ __launch_bounds__(256) void f32conv_tiled(const F32Conv p, const F32T
 template <int NKT, int NPT>
 static int f32conv_tiled_launch(const F32Conv& k, const F32Tile& t, int tiles, int zgroups, size_t lds, hipStream_t s) {
     static std::atomic<unsigned long long> attr_done{0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        INNFER_HIP(hipFuncSetAttribute((const void*)f32conv_tiled<NKT, NPT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_done.fetch_or(bit, std::memory_order_release);
-    }
+    INNFER_HIP(ensure_lds_attr(f32conv_tiled<NKT, NPT>, 160 * 1024, attr_done));
 #ifdef INNFER_ABLATE
     if (getenv("INNFER_F32_OCC")) {
         int nb = -1;

@@ -97,14 +97,10 @@ __global__ __launch_bounds__(512, 1) void hr_chain_kernel(const ChainP p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lg = lane >> 4;
 
-    // ---- workgroup -> tiles: as conv3x3_pc (blocks b, b + 8, .. share an XCD and walk a contiguous run of the tile list) ----
-    const int bid = blockIdx.x, xcd = bid & 7;
-    const int run_q = p.total >> 3, run_r = p.total & 7;
-    const int run_start = xcd < run_r ? xcd * (run_q + 1) : run_r * (run_q + 1) + (xcd - run_r) * run_q;
-    const int run_len = run_q + (xcd < run_r ? 1 : 0);
-    const int slots = ((int)gridDim.x + 7 - xcd) >> 3;
+    // ---- workgroup -> tiles: the XCD's run of the tile list (xcd_run) ----
+    const XcdRun run = xcd_run(p.total);
+    const int run_start = run.start, run_len = run.len, slots = run.slots, j0 = run.j0;
     const int per_img = p.tiles_x * p.tiles_y;
-    const int j0 = bid >> 3;
     if (j0 >= run_len) return;
     auto decode = [&](int jj, int& lid_, int& n_, int& ty0_, int& tx0_) __attribute__((always_inline)) {
         lid_ = run_start + (p.rev ? run_len - 1 - jj : jj);
@@ -418,14 +414,9 @@ int hr_chain_launch(const ConvLaunch& L, const f16* up_in, long up_in_gstride, c
     }
     GtScope gt(s, "hr_chain: upconv -> HR_conv0 -> conv_last", gt_flops, gt_bytes);
     if (!hr_chain_ok(L) || (up_act != 1 && up_act != 2)) return set_error(INNFER_ERR_UNSUPPORTED, "hr_chain: 64 -> 64 -> 64 -> <= 3 channels on whole 16 x 32 HR tiles, act 1 / 2");
-    static int attr_dev_mask = 0;
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (!(attr_dev_mask & (1 << (dev & 31)))) {
-        INNFER_HIP(hipFuncSetAttribute((const void*)hr_chain_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS));
-        INNFER_HIP(hipFuncSetAttribute((const void*)hr_chain_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, CH_LDS));
-        attr_dev_mask |= 1 << (dev & 31);
-    }
+    static std::atomic<unsigned long long> attr_done[2] = {};
+    INNFER_HIP(ensure_lds_attr(hr_chain_kernel<1>, CH_LDS, attr_done[0]));
+    INNFER_HIP(ensure_lds_attr(hr_chain_kernel<2>, CH_LDS, attr_done[1]));
     ChainP c{};
     c.kp.H = L.H; c.kp.W = L.W; c.kp.act = L.act;
     c.kp.fl_w = L.fuse_w; c.kp.fl_bias = L.fuse_bias; c.kp.fl_side = L.fuse_side; c.kp.fl_out = L.fuse_out; c.kp.fl_oc = L.fuse_oc; c.kp.fl_out_mode = L.fuse_out_mode;
@@ -441,7 +432,7 @@ int hr_chain_launch(const ConvLaunch& L, const f16* up_in, long up_in_gstride, c
     c.abl = getenv("INNFER_ABL") ? atoi(getenv("INNFER_ABL")) : 0;
 #endif
     int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, current_device()) != hipSuccess || cus <= 0) cus = 256;
     const long grid = total < cus ? total : cus;
     if (up_act == 1) hipLaunchKernelGGL(hr_chain_kernel<1>, dim3((unsigned)grid), dim3(512), CH_LDS, s, c);
     else hipLaunchKernelGGL(hr_chain_kernel<2>, dim3((unsigned)grid), dim3(512), CH_LDS, s, c);

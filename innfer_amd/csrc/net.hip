@@ -335,7 +335,7 @@ extern "C" int innfer_net_conv_info(innfer_net_t net, int idx, char* key, size_t
 
 // The (wl | wh | wh) panels of one loaded conv for the fp32-accurate mode (conv_pack_split), from the fp32 weights kept at innfer_net_set_conv.
 static int build_split_panels(ConvSlot& c) {
-    std::vector<char> host(3 * (c.ksize == 1 ? conv_packed_bytes_taps(c.K, c.C, 0x10) : conv_packed_bytes(c.K, c.C)));
+    std::vector<char> host(3 * (c.ksize == 1 ? conv_packed_bytes_taps(c.K, c.C, TAPS_1X1) : conv_packed_bytes(c.K, c.C)));
     if (c.ksize == 1) conv_pack_1x1_split(c.h_w.data(), c.K, c.C, host.data());
     else conv_pack_split(c.h_w.data(), c.K, c.C, host.data());
     if (hipMalloc(&c.d_w32, host.size()) != hipSuccess) {
@@ -367,7 +367,7 @@ extern "C" int innfer_net_set_conv(innfer_net_t net, int idx, const float* w, co
         bias_n = c.K;
     } else {
         if (c.ksize == 1) {          // [K,C,1,1]: the one-tap panel of the kernel's 1x1 instantiation
-            host.resize(conv_packed_bytes_taps(c.K, c.C, 0x10));
+            host.resize(conv_packed_bytes_taps(c.K, c.C, TAPS_1X1));
             conv_pack_1x1(w, c.K, c.C, host.data());
         } else if (c.Kp) {           // SRVGGNetCompact's last conv: K valid rows of a 32- / 64-output panel, the rest zero
             std::vector<float> wp((size_t)c.Kp * c.C * 9, 0.f);
@@ -660,8 +660,8 @@ int do_conv(const ConvLaunch& L, hipStream_t s) {
         const double ob = L.fuse_out_mode == 2 ? 1.0 : L.fuse_out_mode == 1 ? 4.0 : 2.0;
         return timed_end(s, 2.0 * 9.0 * (L.K * (double)L.C + 64.0 * L.fuse_oc) * px, px * (L.C * 2.0 + L.fuse_oc * ob) + 9.0 * (L.K * L.C + 64.0 * L.fuse_oc) * 2.0, 2000 + 16 * conv_nt_for(L.K) + L.out_mode);
     }
-    // launch kinds: 16 * NT + out_mode, + 1000 fp32-accurate (split) form, + 2000 fused HR_conv0 + conv_last (TMF 0x201FF), + 3000 the four 2x2-tap phases
-    // of an upconv_block (TM 0x1B, K = 4 * phase_c on the LR grid), + 4000 the PixelShuffle(2) store on the producer / consumer kernel (TMF 0xC001FF): their own
+    // launch kinds: 16 * NT + out_mode, + 1000 fp32-accurate (split) form, + 2000 fused HR_conv0 + conv_last (TMF TAPS_3X3 | PC_FUSE), + 3000 the four 2x2-tap phases
+    // of an upconv_block (TM TAPS_PHASE, K = 4 * phase_c on the LR grid), + 4000 the PixelShuffle(2) store on the producer / consumer kernel (TMF TAPS_3X3 | PC_ROWP | PC_PSH): their own
     // instantiations, their own rows in the bench's per-kernel table.
     // The phase form's FLOPs are the ALGORITHMIC ones of the layer it replaces (nine taps on the 2H x 2W grid = 2 * 9 * 4K * C per LR pixel); it executes 4/9 of them.
     // (fp32-accurate mode: the same algorithmic FLOPs -- executed: 3x --, two slabs per tensor, three panels per weight)
@@ -1085,7 +1085,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
         }
         if (!net->ps_up && net->up_phases && !net->fp32 && cs.d_up4 && !cs.d_map && net->trunk_act <= 2) {
             // Upsample(nearest 2x) -> conv -> act as the four output phases of the equivalent transposed conv: 2x2 taps on the LR grid instead of 3x3 on the
-            // HR grid (2.25 x fewer MACs), on the phase-lattice instantiation (conv3x3_pc<.., TM = 0x1B>)
+            // HR grid (2.25 x fewer MACs), on the phase-lattice instantiation (conv3x3_pc<.., TM = TAPS_PHASE>)
             ConvLaunch L = mk(cs, t, gi, dst, go, N, h, w, net->trunk_act);
             const bool one_visit = net->up_phases == 1 && cs.d_up4p && w > 16;       // all four phases in one visit of a tile (C = 64, plane-order panels); else one phase per visit
             L.wpk = (const f16*)(one_visit ? cs.d_up4p : cs.d_up4); L.bias = cs.d_b4;
@@ -1225,7 +1225,7 @@ extern "C" int innfer_pack_convt2x(const float* w, int K, int C, int k, void* pa
 }
 
 // (121) the panels of the forms innfer_conv_args reaches since then
-extern "C" size_t innfer_conv1x1_packed_bytes(int K, int C) { return (K > 0 && C > 0 && C % 32 == 0) ? conv_packed_bytes_taps(K, C, 0x10) : 0; }
+extern "C" size_t innfer_conv1x1_packed_bytes(int K, int C) { return (K > 0 && C > 0 && C % 32 == 0) ? conv_packed_bytes_taps(K, C, TAPS_1X1) : 0; }
 extern "C" int innfer_pack_conv1x1(const float* w, int K, int C, void* packed) {
     if (!w || !packed || K <= 0 || C <= 0 || C % 32) return set_error(INNFER_ERR_INVALID, "pack_conv1x1: K=%d C=%d (%% 32)", K, C);
     conv_pack_1x1(w, K, C, packed);

@@ -904,7 +904,7 @@ int upload(innfer_pan* p) {
             }
             g.one_tap = g.K3 >= 32;                     // slab outputs only (the planar last conv keeps the 3x3 kernel)
             for (size_t i = 0; i < w3.size() && g.one_tap; ++i) if (i % 9 != 4 && w3[i] != 0.f) g.one_tap = false;
-            std::vector<char> packed(g.one_tap ? conv_packed_bytes_taps(g.K3, g.cin_pad, 0x10) : conv_packed_bytes(g.K3, g.cin_pad));
+            std::vector<char> packed(g.one_tap ? conv_packed_bytes_taps(g.K3, g.cin_pad, TAPS_1X1) : conv_packed_bytes(g.K3, g.cin_pad));
             if (g.one_tap) {
                 std::vector<float> w1((size_t)g.K3 * g.cin_pad);
                 for (size_t i = 0; i < w1.size(); ++i) w1[i] = w3[i * 9 + 4];
@@ -1252,7 +1252,7 @@ extern "C" int innfer_pan_set_precision(innfer_pan* p, int fp32) {
             for (int co = 0; co < g.cout; ++co)
                 for (int ci = 0; ci < g.cin_pad; ++ci)
                     for (int t = 0; t < 9; ++t) w3[((size_t)co * g.cin_pad + ci) * 9 + t] = g.weight(co, ci, t);
-            std::vector<char> packed(3 * (g.one_tap ? conv_packed_bytes_taps(g.K3, g.cin_pad, 0x10) : conv_packed_bytes(g.K3, g.cin_pad)));
+            std::vector<char> packed(3 * (g.one_tap ? conv_packed_bytes_taps(g.K3, g.cin_pad, TAPS_1X1) : conv_packed_bytes(g.K3, g.cin_pad)));
             if (g.one_tap) {
                 std::vector<float> w1((size_t)g.K3 * g.cin_pad);
                 for (size_t j = 0; j < w1.size(); ++j) w1[j] = w3[j * 9 + 4];

@@ -16,7 +16,6 @@
 // launch; the next tile's X is fetched while P2 / P3 run.  Arithmetic per value as in the five-launch schedule: fp16 operands, fp32
 // accumulation, A / B / Y / a' / b' rounded to fp16 where that schedule stored them -- the same roundings, different summation order of the
 // MFMA k-steps only where a conv's taps are walked in another order (none: taps in (dy, dx) order, one k-step per tap).
-#include <atomic>
 #include <type_traits>
 #include "common.h"
 #include "pan_scpa_layout.h"
@@ -167,7 +166,7 @@ __global__ __launch_bounds__(512, 1) void pan_scpa_fused(const ScpaKP p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li_w = lane & 15, lg_w = lane >> 4;
 
-    // the XCD's workgroups (blocks b, b + 8, ..) walk that XCD's contiguous run of the tile list: halos meet in one L2
+    // workgroup -> tiles: xcd_run (common.h) written out -- through the helper this kernel's code changes beyond its prologue
     const int bid = blockIdx.x, xcd = bid & 7;
     const int run_q = p.total >> 3, run_r = p.total & 7;
     const int run_start = xcd < run_r ? xcd * (run_q + 1) : run_r * (run_q + 1) + (xcd - run_r) * run_q;
@@ -449,6 +448,7 @@ __global__ __launch_bounds__(256, 2) void pan_scpa_duo(const ScpaKP p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li_w = lane & 15, lg_w = lane >> 4;
+    // workgroup -> tiles: xcd_run (common.h) written out -- through the helper this kernel's code changes beyond its prologue
     const int bid = blockIdx.x, xcd = bid & 7;
     const int run_q = p.total >> 3, run_r = p.total & 7;
     const int run_start = xcd < run_r ? xcd * (run_q + 1) : run_r * (run_q + 1) + (xcd - run_r) * run_q;
@@ -733,18 +733,10 @@ int pan_scpa_launch(const f16* in, f16* out, long G, const void* d_blob, int N, 
     const int num_cus = scpa_num_cus();
     constexpr int TH = 16;
     constexpr int LDS = 160 * 1024;
-    static std::atomic<unsigned long long> attr_done{0};    // function attributes belong to the device's copy of the code object; concurrent first calls may both set it (idempotent)
-    {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-            if (hipFuncSetAttribute((const void*)pan_scpa_fused<TH>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) {
-                (void)hipGetLastError();
-                return set_error(INNFER_ERR_UNSUPPORTED, "pan_scpa: the fused SCPA block needs 160 KB of LDS per workgroup (gfx950); innfer_pan_set_fused_scpa(pan, 0) selects the five-launch schedule");
-            }
-            attr_done.fetch_or(bit, std::memory_order_release);
-        }
+    static std::atomic<unsigned long long> attr_done{0};
+    if (ensure_lds_attr(pan_scpa_fused<TH>, LDS, attr_done) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_error(INNFER_ERR_UNSUPPORTED, "pan_scpa: the fused SCPA block needs 160 KB of LDS per workgroup (gfx950); innfer_pan_set_fused_scpa(pan, 0) selects the five-launch schedule");
     }
     if ((long)N * H * W * 64 + 2 * G >= 0x7fffffffL) return set_error(INNFER_ERR_UNSUPPORTED, "pan_scpa: slab too large for 32-bit buffer offsets");
     ScpaKP k{};
@@ -765,15 +757,9 @@ int pan_scpa_launch(const f16* in, f16* out, long G, const void* d_blob, int N, 
     if (duo < 0) duo = 1;
     if (duo) {           // two 4-wave workgroups per CU on 8 x 32 tiles (pan_scpa_duo)
         static std::atomic<unsigned long long> duo_done{0};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) dev = 0;
-        const unsigned long long bit = 1ull << (dev & 63);
-        if (!(duo_done.load(std::memory_order_acquire) & bit)) {
-            if (hipFuncSetAttribute((const void*)pan_scpa_duo, hipFuncAttributeMaxDynamicSharedMemorySize, D_LDS) != hipSuccess) {
-                (void)hipGetLastError();
-                return set_error(INNFER_ERR_UNSUPPORTED, "pan_scpa: the two-workgroup form needs 78 KB of LDS per workgroup");
-            }
-            duo_done.fetch_or(bit, std::memory_order_release);
+        if (ensure_lds_attr(pan_scpa_duo, D_LDS, duo_done) != hipSuccess) {
+            (void)hipGetLastError();
+            return set_error(INNFER_ERR_UNSUPPORTED, "pan_scpa: the two-workgroup form needs 78 KB of LDS per workgroup");
         }
         k.tiles_y = (H + D_TH - 1) / D_TH;
         const long tot8 = (long)N * k.tiles_x * k.tiles_y;

@@ -21,7 +21,6 @@
 //     nothing reads with a non-zero weight), lanes of k-octet 3 the tap's zero slot -- whose residue no real fragment of their group has.  Every fragment address is
 //     lane constant + immediate: no select, no address arithmetic per read.
 // Tensor layout in memory ("split planes", npx = N * H * W pixels): [hi, channels 0..31: 64 B per pixel][hi, 32..39: 16 B][lo, 0..31: 64 B][lo, 32..39: 16 B].
-#include <atomic>
 #include <type_traits>
 #include <vector>
 #include "common.h"
@@ -128,7 +127,7 @@ __global__ __launch_bounds__(512, 1) void pan_scpa_split(const SplitKP p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li_w = lane & 15, lg_w = lane >> 4;
 
-    // the XCD's workgroups (blocks b, b + 8, ..) walk that XCD's contiguous run of the tile list: halos meet in one L2
+    // workgroup -> tiles: xcd_run (common.h) written out -- through the helper this kernel's code changes beyond its prologue
     const int bid = blockIdx.x, xcd = bid & 7;
     const int run_q = p.total >> 3, run_r = p.total & 7;
     const int run_start = xcd < run_r ? xcd * (run_q + 1) : run_r * (run_q + 1) + (xcd - run_r) * run_q;
@@ -486,13 +485,9 @@ int pan_scpa_split_launch(const void* in, void* out, const void* d_blob, int N, 
         cus[dev & 63].store(num_cus, std::memory_order_relaxed);
     }
     static std::atomic<unsigned long long> attr_done{0};
-    const unsigned long long bit = 1ull << (dev & 63);
-    if (!(attr_done.load(std::memory_order_acquire) & bit)) {
-        if (hipFuncSetAttribute((const void*)pan_scpa_split, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) {
-            (void)hipGetLastError();
-            return set_error(INNFER_ERR_UNSUPPORTED, "pan_scpa_split: the fused SCPA block needs 149 KB of LDS per workgroup (gfx950)");
-        }
-        attr_done.fetch_or(bit, std::memory_order_release);
+    if (ensure_lds_attr(pan_scpa_split, LDS_BYTES, attr_done) != hipSuccess) {
+        (void)hipGetLastError();
+        return set_error(INNFER_ERR_UNSUPPORTED, "pan_scpa_split: the fused SCPA block needs 149 KB of LDS per workgroup (gfx950)");
     }
     SplitKP k{};
     k.in = (const char*)in; k.out = (char*)out; k.w = (const char*)d_blob; k.npx = N * H * W; k.N = N; k.H = H; k.W = W;

@@ -331,7 +331,7 @@ int upload(innfer_ppon* p) {
         INNFER_HIP(hipMalloc((void**)&r.d_c2, panel.size() * sizeof(f16)));
         INNFER_HIP(hipMemcpy(r.d_c2, panel.data(), panel.size() * sizeof(f16), hipMemcpyHostToDevice));
         if (nf == 64) {
-            std::vector<char> pk(conv_packed_bytes_taps(nf, 4 * nf, 0x10));
+            std::vector<char> pk(conv_packed_bytes_taps(nf, 4 * nf, TAPS_1X1));
             conv_pack_1x1(w2.data(), nf, 4 * nf, pk.data());
             INNFER_HIP(hipMalloc(&r.d_c2t, pk.size()));
             INNFER_HIP(hipMemcpy(r.d_c2t, pk.data(), pk.size(), hipMemcpyHostToDevice));

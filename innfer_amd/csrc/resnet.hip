@@ -540,7 +540,7 @@ int rn_upload(innfer_resnet* r) {
             INNFER_HIP(hipMemcpy(l.d_z32, z32.data(), z32.size() * sizeof(float), hipMemcpyHostToDevice));
         }
         if (l.transposed && k == 3 && l.cout % 64 == 0 && l.cin % 32 == 0) {
-            // ConvTranspose2d(3, stride 2, padding 1, output_padding 1) on the halo-tile kernel (conv3x3_pc<.., TM = 0x1B>, see unet.hip): output phase
+            // ConvTranspose2d(3, stride 2, padding 1, output_padding 1) on the halo-tile kernel (conv3x3_pc<.., TM = TAPS_PHASE>, see unet.hip): output phase
             // (a, b) at the virtual pixel (y + a, x + b) reads taps (dy, dx) in {-1, 0}^2 with ky = 1 - a - 2 dy (oy = 2 iy - 1 + ky); ky = 3 does not
             // exist in a 3-tap kernel: a structural zero (9 of the 16 phase taps are real)
             std::vector<float> b4((size_t)4 * l.cout);

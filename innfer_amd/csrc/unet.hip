@@ -654,7 +654,7 @@ static int upload_all(innfer_unet* u) {
                             const int t = j / l.cin, ci = j - t * l.cin;
                             w1[(size_t)co * 64 + j] = w[(((size_t)co * l.cin + ci) * 4 + (t >> 2)) * 4 + (t & 3)];
                         }
-                    std::vector<char> packed(conv_packed_bytes_taps(l.cout, 64, 0x10));
+                    std::vector<char> packed(conv_packed_bytes_taps(l.cout, 64, TAPS_1X1));
                     conv_pack_1x1(w1.data(), l.cout, 64, packed.data());
                     if (!l.d_w3) INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
                     INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
@@ -720,7 +720,7 @@ static int upload_all(innfer_unet* u) {
                 }
             } else {
                 if (l.tile4) {
-                    // phase (a, b) of ConvTranspose2d(4, 2, 1) = taps (dy, dx) in {-1, 0}^2 at the virtual pixel (y + a, x + b) (conv3x3_pc<.., TM = 0x1B>):
+                    // phase (a, b) of ConvTranspose2d(4, 2, 1) = taps (dy, dx) in {-1, 0}^2 at the virtual pixel (y + a, x + b) (conv3x3_pc<.., TM = TAPS_PHASE>):
                     // tap (r, s) of the 3x3 lattice (r, s in {0, 1}) carries w[ci][c][3 - 2r - a][3 - 2s - b]  (oy = 2 iy - 1 + ky)
                     std::vector<float> b3((size_t)4 * l.cout, 0.f);
                     if (l.bias >= 0) for (int co = 0; co < 4 * l.cout; ++co) b3[co] = u->params[l.bias].host[co % l.cout];
