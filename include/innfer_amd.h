@@ -45,8 +45,8 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  innfer_version() returns the library's; a binding should compare. */
-#define INNFER_ABI_VERSION 121
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  innfer_version() returns the library's; a binding should compare. */
+#define INNFER_ABI_VERSION 122
 int innfer_version(void);
 const char* innfer_last_error(void);
 
@@ -555,6 +555,45 @@ int innfer_resnet_post_slab_parts(const void* d_src, int64_t gs, int C, int64_t 
                                   int relu, const void* d_res, void* d_dst, void* stream);
 int innfer_unet_post_slab_parts(const void* d_src, int64_t src_gs, int C, int64_t HW, int N, const float* d_part, int nper, const float* d_gamma, const float* d_beta,
                                 void* d_dst0, int64_t dst0_gs, int dst0_coff, int act0, void* d_dst1, int64_t dst1_gs, int dst1_coff, int act1, void* stream);
+
+/* (122) The gather GEMM (csrc/gather_gemm.h gg::gemm_gather: the second conv engine -- the pix2pix UNet's deep levels, every conv of the CycleGAN ResNet, the WBC UNet,
+ * PPON's fallback dilated convs and c2, PAN's attention projections) as a single launch, for tests.  The struct carries what gg::launch takes, and the entry runs the
+ * decision code of the five families (gg::decide) before it fires (gg::fire):
+ *   raw[n, oy * os + ooy, ox * os + oox, co] = sum over taps t and input channels ci of in[n, oy * stride + dy[t] * m, ox * stride + dx[t] * m, ci] * w[co, ci, t]
+ * in fp32 over fp16 operands; m = 1 + g * g_tapmul is group g's tap multiplier; out-of-image taps read zero, or the mirrored pixel with reflect; with up the input is
+ * read through nearest 2x (Hin, Win = the source size).  d_in: blocked-NHWC fp16 slab, 32-channel chunks in_group_stride elements apart; d_raw: fp32 rows of raw_stride
+ * floats per pixel of the N x Hfull x Wfull grid (0 = cout_pad; a positive multiple of 4), of which channels [0, cout_store) are written (0 = min(raw_stride, cout_pad)).
+ * ngroup > 1: several convs of the same input as one launch -- weights d_packed + g * g_wbytes BYTES, output d_raw + g * g_outoff FLOATS.  g_phase (ngroup == 4, os == 2,
+ * ntaps <= 12): group g uses taps [g * ntaps, (g + 1) * ntaps) of dy / dx and writes output pixel (2 oy + (g >> 1), 2 ox + (g & 1)); ooy / oox unused.
+ * d_scratch / scratch_bytes (optional): where the layer's geometry asks for a split over K and the partial results fit, the launch writes ksplit partial results of
+ * N * Hfull * Wfull * raw_stride floats each into d_scratch and reduces them into d_raw in split order; with keep_partials they stay in d_scratch unreduced (d_raw is
+ * not written), as the UNet's deep levels use the launch.  The in-call reduction covers channels [0, cout_store) only, so a raw row wider than cout_store (several
+ * GEMMs filling one row) keeps its other columns when the launch is split (until 121 it ran over the whole row: unwritten scratch stored over the neighbours' columns;
+ * no network formed that launch).
+ * Refused, with nothing launched: raw_stride not a positive multiple of 4, ntaps outside 1 .. 49, g_phase without 4 groups of <= 12 taps (INNFER_ERR_INVALID), an input
+ * of N * Hin * Win * 64 >= 2^31 - 1 bytes per chunk (INNFER_ERR_UNSUPPORTED) -- as gg::launch refuses them -- and, by this entry only: cout_store not a multiple of 4 or
+ * beyond raw_stride (INNFER_ERR_INVALID); reflect with a tap that one reflection does not bring back into the image (|dy| * m >= Hin for a stride-1 same-size conv),
+ * reflect together with up or g_phase (INNFER_ERR_UNSUPPORTED).
+ * info[5] (may be NULL for innfer_gather_gemm) = {tile shape (0: 128 px x 64 co, 1: 256 x 128, 2: 256 x 256 on eight waves), ksplit, seg (k-steps per segment), taps kept
+ * per group after the dead-tap drop, scratch bytes a split of this layer needs (0: never split)}.  innfer_gather_gemm_plan: host only, no device call, pointers unread
+ * (d_scratch only compared with NULL).
+ * Panels: h_w [cout][cin][ntaps] float32 -> innfer_gather_gemm_packed_bytes(cout, cin_pad, ntaps) bytes through gg::pack_panels, the packer of every family: cout_pad =
+ * ceil(cout / 64) * 64 rows, cin_pad % 32 == 0, padding zero; [channel tile][tap][chunk][64 rows][4 slots of 8], slot s of row R = channels 8 * (s ^ 2 * bit2(R)) .. + 7. */
+typedef struct {
+    const void* d_in; int64_t in_group_stride; int cin_pad;
+    const void* d_packed; int cout_pad;
+    float* d_raw; int raw_stride, cout_store;
+    int N, Hin, Win, Ho, Wo, stride;
+    int ntaps, dy[49], dx[49];
+    int Hfull, Wfull, os, ooy, oox, up, reflect;
+    int ngroup; int64_t g_wbytes, g_outoff; int g_tapmul, g_phase;
+    float* d_scratch; int64_t scratch_bytes;
+    int keep_partials;
+} innfer_gather_gemm_args;
+size_t innfer_gather_gemm_packed_bytes(int cout, int cin_pad, int ntaps);
+int innfer_pack_gather_gemm(const float* h_w, int cout, int cin, int cin_pad, int ntaps, void* h_packed);
+int innfer_gather_gemm(const innfer_gather_gemm_args* a, int* info, void* stream);
+int innfer_gather_gemm_plan(const innfer_gather_gemm_args* a, int* info);
 
 /* NCHW (f16/f32) <-> blocked-NHWC f16 slab helpers used by tests of the single conv. */
 int innfer_nchw_to_slab(const void* d_src, int src_dtype, void* d_slab, int64_t group_stride, int ch_off,

@@ -221,10 +221,11 @@ inline void pack_panels(std::vector<f16>& dst, int cout, int cin, int cin_pad, i
 }
 
 
-// raw[pixel][0:cout_pad] = sum over the ksplit partial results, in split order (deterministic)
-static __global__ void splitk_reduce(const float* part, long split_elems, int ksplit, float* raw, int cout_pad,
+// raw[pixel][0:cstore] = sum over the ksplit partial results, in split order (deterministic).  Rows of `stride` floats; only the cstore channels the GEMM wrote
+// into the partials are read and stored (a row wider than that belongs to other writers: see launch)
+static __global__ void splitk_reduce(const float* part, long split_elems, int ksplit, float* raw, int stride, int cstore,
                                      int N, int Ho, int Wo, int Hfull, int Wfull, int os, int ooy, int oox) {
-    const int c4 = cout_pad >> 2;
+    const int c4 = cstore >> 2;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long M = (long)N * Ho * Wo;
     if (i >= M * c4) return;
@@ -232,7 +233,7 @@ static __global__ void splitk_reduce(const float* part, long split_elems, int ks
     const int c = (int)(i - m * c4) * 4;
     const int ox = (int)(m % Wo), oy = (int)((m / Wo) % Ho);
     const long n = m / ((long)Wo * Ho);
-    const long o = ((n * Hfull + (long)oy * os + ooy) * Wfull + (long)ox * os + oox) * cout_pad + c;
+    const long o = ((n * Hfull + (long)oy * os + ooy) * Wfull + (long)ox * os + oox) * stride + c;
     f32x4 a = *(const f32x4*)(part + o);
     for (int z = 1; z < ksplit; ++z) {
         const f32x4 b = *(const f32x4*)(part + z * split_elems + o);
@@ -241,17 +242,25 @@ static __global__ void splitk_reduce(const float* part, long split_elems, int ks
     *(f32x4*)(raw + o) = a;
 }
 
-// One launch.  dy/dx: ntaps displacements; stride: input step per output pixel (2 for the 4x4 s2 conv).
-// scratch (optional): when the launch would not fill the chip (deep UNet layers: few pixels, a K loop of up
-// to 256 steps) the K range is split over blockIdx.z into partial results that splitk_reduce adds up.
-inline int launch(const f16* wpk, int cin_pad, int cout_pad, const f16* in, long in_g, int N, int Hin, int Win,
+// What one launch will do, decided on the host without touching a device (decide) and then fired (fire): the five families' launch() and the single-launch
+// test entry (innfer_gather_gemm / innfer_gather_gemm_plan) run this one decision code.
+struct Plan {
+    GP g;
+    int shape;                  // 0: <2,1,4> 128 x 64, 1: <4,2,3> 256 x 128, 2: <4,4,3,2> 256 x 256
+    int ks;                     // split-K segments (1 = not split)
+    size_t split_bytes;         // scratch a split of this layer needs (segments x the full-resolution raw buffer); 0 where the layer is never split
+    long M;                     // output pixels of the launch's grid (0: nothing to launch)
+    int cin_pad, ngroup, g_phase;
+    int rN, rh, rw, ros, rooy, roox;      // the in-call reduction's grid
+};
+
+inline int decide(Plan& P, int cin_pad, int cout_pad, const f16* in, long in_g, int N, int Hin, int Win,
                   float* raw, int Ho, int Wo, int stride, int ntaps, const int* dy, const int* dx,
-                  int Hfull, int Wfull, int os, int ooy, int oox, int up, hipStream_t s,
-                  float* scratch = nullptr, size_t scratch_bytes = 0, int raw_stride = 0, int reflect = 0,
-                  int ngroup = 1, long g_wbytes = 0, long g_outoff = 0, int g_tapmul = 0, int cout_store = 0, int g_phase = 0,
-                  int* ksplit_out = nullptr) {      // ksplit_out: the caller reduces the partial results itself (scratch, *ksplit_out segments of
-                                                     // N*Hfull*Wfull*raw_stride floats; 1 = not split, the result is in raw)
-    GP g{};
+                  int Hfull, int Wfull, int os, int ooy, int oox, int up, const f16* wpk,
+                  float* scratch, size_t scratch_bytes, int raw_stride, int reflect,
+                  int ngroup, long g_wbytes, long g_outoff, int g_tapmul, int cout_store, int g_phase) {
+    P = Plan{};
+    GP& g = P.g;
     g.in = in; g.in_g = in_g; g.nchunks = cin_pad / 32; g.N = N; g.Hin = Hin; g.Win = Win;
     g.wpk = wpk; g.out = raw; g.cout_pad = cout_pad;
     g.raw_stride = raw_stride > 0 ? raw_stride : cout_pad;
@@ -290,11 +299,11 @@ inline int launch(const f16* wpk, int cin_pad, int cout_pad, const f16* in, long
 #ifdef INNFER_ABLATE
     g.abl = getenv("INNFER_GG_ABL") ? atoi(getenv("INNFER_GG_ABL")) : 0;
 #endif
+    P.cin_pad = cin_pad; P.ngroup = ngroup; P.g_phase = g_phase;
     const long M = (long)N * Ho * Wo;
+    P.M = M > 0 ? M : 0;
+    P.ks = 1;
     if (M <= 0) return INNFER_OK;
-    // (launch timer: the GEMM and, where it is split over K inside this call, its reduction as one entry)
-    GtScope gt(s, "gemm_gather (+ split-K reduce)", 2.0 * M * ngroup * (double)cout_pad * ntaps * cin_pad,
-               (double)N * Hin * Win * cin_pad * 2.0 + (double)M * ngroup * cout_pad * 4.0 + (double)ngroup * ntaps * cin_pad * cout_pad * 2.0);
     if ((long)N * Hin * Win * 64 >= 0x7fffffffL) return set_error(INNFER_ERR_UNSUPPORTED, "gather GEMM: input of %d x %d x %d pixels exceeds the 2 GiB buffer window", N, Hin, Win);
     const int nsteps = ntaps * g.nchunks;
     const size_t full = (size_t)N * Hfull * Wfull * g.raw_stride * sizeof(float);
@@ -309,9 +318,11 @@ inline int launch(const f16* wpk, int cin_pad, int cout_pad, const f16* in, long
     g.seg = (nsteps + want - 1) / want;
     const int segs = (nsteps + g.seg - 1) / g.seg;
     int ks = 1;
-    if (scratch && (nsteps >= 32 || (tiny && segs > 1)) && (long)Ho * Wo <= split_max_px() && (size_t)segs * full <= scratch_bytes) ks = segs;
-    if (ngroup > 1 && !g_phase) ks = 1;        // phase groups may be split over K: every segment buffer then holds the whole full-resolution grid
-    g.ksplit = ks;
+    const bool splittable = (nsteps >= 32 || (tiny && segs > 1)) && (long)Ho * Wo <= split_max_px() && !(ngroup > 1 && !g_phase);
+    P.split_bytes = splittable && segs > 1 ? (size_t)segs * full : 0;
+    if (scratch && splittable && (size_t)segs * full <= scratch_bytes) ks = segs;      // (dilated groups are never split; phase groups may be split over K: every
+    g.ksplit = ks;                                                                      //  segment buffer then holds the whole full-resolution grid)
+    P.ks = ks;
     g.cout_store = cout_store > 0 ? cout_store : (g.raw_stride < cout_pad ? g.raw_stride : cout_pad);
     g.ngroup = ngroup; g.g_wbytes = g_wbytes; g.g_outoff = g_outoff; g.g_tapmul = g_tapmul; g.g_phase = g_phase;
     g.split_elems = ks > 1 ? (long)(full / sizeof(float)) : 0;
@@ -324,10 +335,27 @@ inline int launch(const f16* wpk, int cin_pad, int cout_pad, const f16* in, long
     // (256 x 256 tiles where they still give every CU a workgroup: two thirds of the LDS-DMA bytes per MFMA of the 256 x 128 form)
     const bool big2 = big && cout_pad % 256 == 0 && INNFER_KNOB("INNFER_GG_BIG2", 1) &&
                       ((M + 255) / 256) * (cout_pad / 256) * ngroup * ks >= 256;
-    if (big2) {
+    P.shape = big2 ? 2 : big ? 1 : 0;
+    // (phase groups: the four launches' worth of partials interleave into the full grid, reduced in one pass)
+    P.rN = N; P.rh = g_phase ? Hfull : Ho; P.rw = g_phase ? Wfull : Wo;
+    P.ros = g_phase ? 1 : os; P.rooy = g_phase ? 0 : ooy; P.roox = g_phase ? 0 : oox;
+    return INNFER_OK;
+}
+
+// Fires what decide() planned.  reduce: a split launch is reduced into raw here (over the cout_store channels the GEMM wrote -- a raw row wider than that, shared
+// with other writers, keeps their columns); otherwise the partials stay in scratch for the caller.
+inline int fire(const Plan& P, float* raw, float* scratch, bool reduce, hipStream_t s) {
+    const GP& g = P.g;
+    const long M = P.M;
+    if (M <= 0) return INNFER_OK;
+    const int cout_pad = g.cout_pad, ks = P.ks, ngroup = P.ngroup;
+    // (launch timer: the GEMM and, where it is split over K inside this call, its reduction as one entry)
+    GtScope gt(s, "gemm_gather (+ split-K reduce)", 2.0 * M * ngroup * (double)cout_pad * g.ntaps * P.cin_pad,
+               (double)g.N * g.Hin * g.Win * P.cin_pad * 2.0 + (double)M * ngroup * cout_pad * 4.0 + (double)ngroup * g.ntaps * P.cin_pad * cout_pad * 2.0);
+    if (P.shape == 2) {
         dim3 grid((unsigned)((M + 255) / 256), (unsigned)(cout_pad / 256), (unsigned)(ks * ngroup));
         hipLaunchKernelGGL((gemm_gather<4, 4, 3, 2>), grid, dim3(512), 0, s, g);
-    } else if (big) {
+    } else if (P.shape == 1) {
         dim3 grid((unsigned)((M + 255) / 256), (unsigned)(cout_pad / 128), (unsigned)(ks * ngroup));
         hipLaunchKernelGGL((gemm_gather<4, 2, 3>), grid, dim3(256), 0, s, g);
     } else {
@@ -335,15 +363,31 @@ inline int launch(const f16* wpk, int cin_pad, int cout_pad, const f16* in, long
         hipLaunchKernelGGL((gemm_gather<2, 1, 4>), grid, dim3(256), 0, s, g);
     }
     INNFER_HIP(hipGetLastError());
-    if (ksplit_out) *ksplit_out = ks;
-    if (ks > 1 && !ksplit_out) {
-        // (phase groups: the four launches' worth of partials interleave into the full grid, reduced in one pass)
-        const int rh = g_phase ? Hfull : Ho, rw = g_phase ? Wfull : Wo;
-        const long nthr = (long)N * rh * rw * (g.raw_stride / 4);
+    if (ks > 1 && reduce) {
+        const long nthr = (long)P.rN * P.rh * P.rw * (g.cout_store / 4);
         hipLaunchKernelGGL(splitk_reduce, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, (const float*)scratch, g.split_elems, ks,
-                           raw, g.raw_stride, N, rh, rw, Hfull, Wfull, g_phase ? 1 : os, g_phase ? 0 : ooy, g_phase ? 0 : oox);
+                           raw, g.raw_stride, g.cout_store, P.rN, P.rh, P.rw, g.Hfull, g.Wfull, P.ros, P.rooy, P.roox);
         INNFER_HIP(hipGetLastError());
     }
+    return INNFER_OK;
+}
+
+// One launch.  dy/dx: ntaps displacements; stride: input step per output pixel (2 for the 4x4 s2 conv).
+// scratch (optional): when the launch would not fill the chip (deep UNet layers: few pixels, a K loop of up
+// to 256 steps) the K range is split over blockIdx.z into partial results that splitk_reduce adds up.
+inline int launch(const f16* wpk, int cin_pad, int cout_pad, const f16* in, long in_g, int N, int Hin, int Win,
+                  float* raw, int Ho, int Wo, int stride, int ntaps, const int* dy, const int* dx,
+                  int Hfull, int Wfull, int os, int ooy, int oox, int up, hipStream_t s,
+                  float* scratch = nullptr, size_t scratch_bytes = 0, int raw_stride = 0, int reflect = 0,
+                  int ngroup = 1, long g_wbytes = 0, long g_outoff = 0, int g_tapmul = 0, int cout_store = 0, int g_phase = 0,
+                  int* ksplit_out = nullptr) {      // ksplit_out: the caller reduces the partial results itself (scratch, *ksplit_out segments of
+                                                     // N*Hfull*Wfull*raw_stride floats; 1 = not split, the result is in raw)
+    Plan P;
+    if (int rc = decide(P, cin_pad, cout_pad, in, in_g, N, Hin, Win, raw, Ho, Wo, stride, ntaps, dy, dx, Hfull, Wfull, os, ooy, oox, up, wpk,
+                        scratch, scratch_bytes, raw_stride, reflect, ngroup, g_wbytes, g_outoff, g_tapmul, cout_store, g_phase)) return rc;
+    if (P.M <= 0) return INNFER_OK;
+    if (int rc = fire(P, raw, scratch, ksplit_out == nullptr, s)) return rc;
+    if (ksplit_out) *ksplit_out = P.ks;
     return INNFER_OK;
 }
 

@@ -1268,3 +1268,69 @@ extern "C" int innfer_unet_forward(innfer_unet* u, const void* d_in, int in_dtyp
     }
     return INNFER_OK;
 }
+
+// ---- (122) the gather GEMM as a single launch, for tests --------------------------------------------------------------------------------
+extern "C" size_t innfer_gather_gemm_packed_bytes(int cout, int cin_pad, int ntaps) {
+    if (cout <= 0 || cin_pad <= 0 || cin_pad % 32 || ntaps < 1 || ntaps > 49) return 0;
+    return (size_t)((cout + 63) / 64) * ntaps * (cin_pad / 32) * 64 * 32 * sizeof(f16);
+}
+
+extern "C" int innfer_pack_gather_gemm(const float* h_w, int cout, int cin, int cin_pad, int ntaps, void* h_packed) {
+    if (!h_w || !h_packed || cout <= 0 || cin <= 0 || cin > cin_pad || cin_pad % 32 || ntaps < 1 || ntaps > 49)
+        return set_error(INNFER_ERR_INVALID, "pack_gather_gemm: cout=%d cin=%d cin_pad=%d ntaps=%d", cout, cin, cin_pad, ntaps);
+    std::vector<f16> panel;
+    gg::pack_panels(panel, cout, cin, cin_pad, ntaps, [&](int co, int ci, int t) { return h_w[((size_t)co * cin + ci) * ntaps + t]; });
+    std::memcpy(h_packed, panel.data(), panel.size() * sizeof(f16));
+    return INNFER_OK;
+}
+
+namespace {
+// the entry's own refusals (what the kernel assumes and gg::decide does not check), then gg::decide -- the decision code of every family's launch
+int gather_gemm_decide(const innfer_gather_gemm_args* a, gg::Plan& P) {
+    if (!a) return set_error(INNFER_ERR_INVALID, "gather GEMM: null arguments");
+    if (a->cin_pad <= 0 || a->cin_pad % 32 || a->cout_pad <= 0 || a->cout_pad % 64 || a->N < 0 || a->Hin < 1 || a->Win < 1 || a->Ho < 0 || a->Wo < 0 || a->stride < 1 ||
+        a->os < 1 || a->ooy < 0 || a->oox < 0 || a->ooy >= a->os || a->oox >= a->os || a->ngroup < 1 || a->scratch_bytes < 0 ||
+        (long)(a->Ho - 1) * a->os + a->ooy >= a->Hfull || (long)(a->Wo - 1) * a->os + a->oox >= a->Wfull)
+        return set_error(INNFER_ERR_INVALID, "gather GEMM: bad geometry");
+    if (a->g_phase && (a->os != 2 || a->Hfull < 2 * a->Ho || a->Wfull < 2 * a->Wo)) return set_error(INNFER_ERR_INVALID, "gather GEMM: phase groups write a 2x grid (os = 2)");
+    if (a->raw_stride < 0) return set_error(INNFER_ERR_INVALID, "gather GEMM: bad raw stride %d", a->raw_stride);
+    if (a->cout_store < 0 || (a->cout_store & 3)) return set_error(INNFER_ERR_INVALID, "gather GEMM: cout_store %d is not a multiple of 4 (the kernel stores channel quads)", a->cout_store);
+    if (a->raw_stride > 0 && a->cout_store > a->raw_stride) return set_error(INNFER_ERR_INVALID, "gather GEMM: cout_store %d beyond the raw row of %d", a->cout_store, a->raw_stride);
+    if (a->reflect && a->ntaps >= 1 && a->ntaps <= 49) {
+        if (a->up || a->g_phase) return set_error(INNFER_ERR_UNSUPPORTED, "gather GEMM: reflect does not combine with up / phase groups");
+        // one reflection per axis is all the kernel makes: every tap of every output pixel must land in [-(n - 1), 2 n - 2]
+        const int mul = a->ngroup > 1 ? 1 + (a->ngroup - 1) * a->g_tapmul : 1;
+        for (int t = 0; t < a->ntaps; ++t) {
+            const long ylo = (long)a->dy[t] * (a->dy[t] < 0 ? mul : 1), yhi = (long)(a->Ho - 1) * a->stride + (long)a->dy[t] * (a->dy[t] > 0 ? mul : 1);
+            const long xlo = (long)a->dx[t] * (a->dx[t] < 0 ? mul : 1), xhi = (long)(a->Wo - 1) * a->stride + (long)a->dx[t] * (a->dx[t] > 0 ? mul : 1);
+            if (ylo < -(long)(a->Hin - 1) || yhi > 2L * a->Hin - 2 || xlo < -(long)(a->Win - 1) || xhi > 2L * a->Win - 2)
+                return set_error(INNFER_ERR_UNSUPPORTED, "gather GEMM: reflected tap (%d, %d) reaches beyond one reflection of the %d x %d image", a->dy[t], a->dx[t], a->Hin, a->Win);
+        }
+    }
+    return gg::decide(P, a->cin_pad, a->cout_pad, (const f16*)a->d_in, (long)a->in_group_stride, a->N, a->Hin, a->Win, a->d_raw, a->Ho, a->Wo, a->stride,
+                      a->ntaps, a->dy, a->dx, a->Hfull, a->Wfull, a->os, a->ooy, a->oox, a->up, (const f16*)a->d_packed, a->d_scratch, (size_t)a->scratch_bytes,
+                      a->raw_stride, a->reflect, a->ngroup, (long)a->g_wbytes, (long)a->g_outoff, a->g_tapmul, a->cout_store, a->g_phase);
+}
+
+void gather_gemm_info(const gg::Plan& P, int* info) {
+    if (!info) return;
+    info[0] = P.shape; info[1] = P.ks; info[2] = P.g.seg; info[3] = P.g.ntaps;
+    info[4] = (int)std::min<size_t>(P.split_bytes, 0x7fffffff);
+}
+}  // namespace
+
+extern "C" int innfer_gather_gemm_plan(const innfer_gather_gemm_args* a, int* info) {
+    if (!info) return set_error(INNFER_ERR_INVALID, "gather GEMM: null info");
+    gg::Plan P;
+    if (int rc = gather_gemm_decide(a, P)) return rc;
+    gather_gemm_info(P, info);
+    return INNFER_OK;
+}
+
+extern "C" int innfer_gather_gemm(const innfer_gather_gemm_args* a, int* info, void* stream) {
+    gg::Plan P;
+    if (int rc = gather_gemm_decide(a, P)) return rc;
+    if (!a->d_in || !a->d_packed || !a->d_raw) return set_error(INNFER_ERR_INVALID, "gather GEMM: null device pointer");
+    gather_gemm_info(P, info);
+    return gg::fire(P, a->d_raw, a->d_scratch, !a->keep_partials, (hipStream_t)stream);
+}

@@ -75,6 +75,20 @@ class F32ConvArgs(C.Structure):
     ]
 
 
+class GatherGemmArgs(C.Structure):
+    _fields_ = [
+        ("d_in", C.c_void_p), ("in_group_stride", C.c_int64), ("cin_pad", C.c_int),
+        ("d_packed", C.c_void_p), ("cout_pad", C.c_int),
+        ("d_raw", C.c_void_p), ("raw_stride", C.c_int), ("cout_store", C.c_int),
+        ("N", C.c_int), ("Hin", C.c_int), ("Win", C.c_int), ("Ho", C.c_int), ("Wo", C.c_int), ("stride", C.c_int),
+        ("ntaps", C.c_int), ("dy", C.c_int * 49), ("dx", C.c_int * 49),
+        ("Hfull", C.c_int), ("Wfull", C.c_int), ("os", C.c_int), ("ooy", C.c_int), ("oox", C.c_int), ("up", C.c_int), ("reflect", C.c_int),
+        ("ngroup", C.c_int), ("g_wbytes", C.c_int64), ("g_outoff", C.c_int64), ("g_tapmul", C.c_int), ("g_phase", C.c_int),
+        ("d_scratch", C.c_void_p), ("scratch_bytes", C.c_int64),
+        ("keep_partials", C.c_int),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/innfer_amd.h
 SIGNATURES = {
     "innfer_version": (C.c_int, []),
@@ -252,6 +266,10 @@ SIGNATURES = {
     "innfer_f32conv_plan": (C.c_int, [C.POINTER(F32ConvArgs), C.POINTER(C.c_int)]),
     "innfer_f32_norm": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_float,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p]),
+    "innfer_gather_gemm_packed_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "innfer_pack_gather_gemm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "innfer_gather_gemm": (C.c_int, [C.POINTER(GatherGemmArgs), C.POINTER(C.c_int), C.c_void_p]),
+    "innfer_gather_gemm_plan": (C.c_int, [C.POINTER(GatherGemmArgs), C.POINTER(C.c_int)]),
     "innfer_conv_stats_records": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "innfer_norm_combine_parts": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "innfer_norm_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -279,7 +297,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 lib = _lib
 
-ABI_VERSION = 121          # the header revision this binding was written against (INNFER_ABI_VERSION)
+ABI_VERSION = 122          # the header revision this binding was written against (INNFER_ABI_VERSION)
 if _lib.innfer_version() != ABI_VERSION and not _ABI_ANY:
     raise ImportError(f"{LIB_PATH} speaks ABI {_lib.innfer_version()}, this binding {ABI_VERSION}: rebuild with `make`")
 
@@ -390,6 +408,27 @@ def f32conv_plan(a):
     plan = (C.c_int * 8)()
     check(_lib.innfer_f32conv_plan(C.byref(a), plan))
     return dict(zip(F32_PLAN_KEYS, plan))
+
+
+GATHER_GEMM_INFO_KEYS = ("shape", "ksplit", "seg", "taps", "split_bytes")
+
+
+def gather_gemm_args(dy, dx, **fields):
+    """GatherGemmArgs from keyword fields (names of the struct) and the tap displacements dy / dx (for g_phase: the four groups' lists back to back, ntaps per
+    group given as a field); pointers as integers."""
+    a = GatherGemmArgs(**fields)
+    if "ntaps" not in fields:
+        a.ntaps = len(dy)
+    for i, (y, x) in enumerate(zip(dy, dx)):
+        a.dy[i], a.dx[i] = y, x
+    return a
+
+
+def gather_gemm_plan(a):
+    """innfer_gather_gemm_plan (host only): what innfer_gather_gemm would launch for the GatherGemmArgs `a`, as a dict of GATHER_GEMM_INFO_KEYS."""
+    info = (C.c_int * 5)()
+    check(_lib.innfer_gather_gemm_plan(C.byref(a), info))
+    return dict(zip(GATHER_GEMM_INFO_KEYS, info))
 
 
 def blend_profile(P, step=0.5, scale=1):
