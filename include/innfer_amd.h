@@ -45,7 +45,7 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  innfer_version() returns the library's; a binding should compare. */
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  innfer_version() returns the library's; a binding should compare. */
 #define INNFER_ABI_VERSION 122
 int innfer_version(void);
 const char* innfer_last_error(void);
@@ -791,6 +791,42 @@ int innfer_extract_tiles_u8_tta(const uint8_t* d_img, int C, int H, int W, int n
                                 int pad, int mode, void* d_tiles, int tile_dtype, void* stream);
 int innfer_recompose_u8_tta(const void* d_tiles, int dtype, int n, int C, int P, int height, int width, double step, int scale,
                             int via_dtype, int denormalize, int fit, int alpha, int alpha_const, int crop, uint8_t* d_img, void* stream);
+
+/* The stitched tile path (122, additive; `-tile N -tile_pad P`, Real-ESRGAN's --tile / --tile_pad; csrc/tiles_stitch.hip).  Large rectangular tiles that
+ * carry a halo of context pixels; the halo is thrown away, every output pixel comes from exactly one tile (its owner) and nothing is averaged.  Not in the
+ * reference, whose chop blends 200 x 200 tiles at step 0.5 (3.7 .. 3.9x the image's pixels through the network; this lattice: 1.05 .. 1.12x).
+ * Per axis of A pixels, tile core `tile` = T >= 1 and `halo` = h >= 0, in low-resolution pixels:
+ *   A <= T + 2h :  n = 1, P = A, origin 0
+ *   otherwise   :  n = ceil((A - 2h) / T);  P = ceil((A + 2h (n - 1)) / n);  S = P - 2h;  o_i = min(i S, A - P), i = 0 .. n - 1
+ *   owner(y)    =  the largest i with i == 0 or o_i + h <= y
+ * Tiles are P_h x P_w, all equal (balanced: 1080 rows at T = 1024 are two tiles of 556 rows), row-major, wholly inside the image.  Pixel (Y, X) of the
+ * scale H x scale W result is pixel (Y - scale o_ky, X - scale o_kx) of tile (ky, kx)'s result, ky = owner(Y / scale), kx = owner(X / scale): an owned
+ * pixel is at least h away from every tile edge that is not an image edge.
+ *
+ * innfer_tile_plan (host only): P_h, P_w, the tile counts and the origins (ys [nh] / xs [nw], either may be NULL, as may every other output).
+ *   INNFER_ERR_INVALID for a non-positive H, W or tile, or a negative halo.
+ * innfer_tile_owner (host only): the owner as the kernels compute it -- *index = owner(X / scale) and *origin = scale o_index for position X of the
+ *   scale * A output axis.
+ * innfer_extract_tiles_rect: d_img [1, C, H, W] (INNFER_F16 / INNFER_F32, any C) -> d_tiles [tile_count, C, P_h, P_w], tiles tile_begin .. of the lattice.
+ * innfer_extract_tiles_u8_rect: the same of np2tensor(image) for a uint8 HWC BGR(A) image, C 1 .. 4, without the float image: /255, BGR(A) -> RGB(A),
+ *   `normalize`, cast to tile_dtype -- innfer_extract_tiles_u8's arithmetic.  The lattice is that of the virtual (H + 2 pad) x (W + 2 pad) image and every
+ *   element is read through the border map `mode`, exactly as innfer_extract_tiles_u8_seamless reads it; pad = 0 is the plain form.
+ * innfer_stitch_tiles: d_tiles [n, C, scale P_h, scale P_w] -> d_out [1, C, scale height, scale width] of the same dtype, a copy from the owner tile;
+ *   n must be the lattice's tile count.
+ * innfer_stitch_tiles_u8: the same with tensor2np as the store (denormalise, RGB(A) -> BGR(A), clip, * 255, round half to even: innfer_recompose_u8's
+ *   quantisation without a blend in front), C 1 .. 4.  height and width are those of the PADDED image, crop (2 crop < height, width) is cut off every side:
+ *   d_img is [scale (height - 2 crop), scale (width - 2 crop), C]; pixels outside that window are neither read nor stored.  crop = 0: the whole frame.
+ * One read and one write per element; all offsets are 64-bit (an 8K frame's tiles at scale 4 pass 2^31 elements).  More than 65535 tile rows (gathers) or
+ * output rows (stitches): INNFER_ERR_UNSUPPORTED.  The 200 / 0.5 chop, its kernels and entry points are unchanged. */
+int innfer_tile_plan(int H, int W, int tile, int halo, int* ph, int* pw, int* nh, int* nw, int* ys, int* xs);
+int innfer_tile_owner(int A, int tile, int halo, int scale, int X, int* index, int* origin);
+int innfer_extract_tiles_rect(const void* d_img, int dtype, int C, int H, int W, int tile, int halo, int tile_begin, int tile_count,
+                              void* d_tiles, void* stream);
+int innfer_extract_tiles_u8_rect(const uint8_t* d_img, int C, int H, int W, int normalize, int tile, int halo, int tile_begin, int tile_count,
+                                 int pad, int mode, void* d_tiles, int tile_dtype, void* stream);
+int innfer_stitch_tiles(const void* d_tiles, int dtype, int n, int C, int height, int width, int tile, int halo, int scale, void* d_out, void* stream);
+int innfer_stitch_tiles_u8(const void* d_tiles, int dtype, int n, int C, int height, int width, int tile, int halo, int scale, int denormalize,
+                           int crop, uint8_t* d_img, void* stream);
 
 /* srgb2linear / linear2srgb (utils/colors.py:29-46, 49-60), the pointwise halves of the `-cf` colour
  * fix: uint8 sRGB -> float32 linear, and float32 linear -> uint8 sRGB (clip, gamma, *255, TRUNCATING

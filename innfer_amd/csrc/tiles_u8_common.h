@@ -1,6 +1,7 @@
 // What the uint8 chop kernels of tiles_u8.hip and tiles_tta.hip share, each body once: the row-run load through the border map (load_run), the tile
 // stores of the gather (put_run), the blend of one frame at one pixel (blend_at), the quantise-and-store tail (store_px), and on the host the dispatch
-// from the runtime (fit, C, dtype) to the kernels' template arguments and the channel / alpha refusals (check_u8_form).  A header of its own rather than
+// from the runtime (fit, C, dtype) to the kernels' template arguments and the channel / alpha refusals (check_u8_form).  The stitched tile path
+// (tiles_stitch.hip) builds its uint8 gather and stitch from load_run, put_run and store_px too, so its conversions are these.  A header of its own rather than
 // a section of tiles_common.h because tiles.hip must NOT use any of it: its k_extract, k_recompose, k_u8_to_nchw and k_nchw_to_u8 are the independent
 // anchors the tests hold these kernels to, and sharing a loop with them would make those tests compare code with itself.  Every rounding is explicit.
 #pragma once

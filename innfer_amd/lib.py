@@ -278,6 +278,12 @@ SIGNATURES = {
                                                 C.c_void_p, C.c_void_p]),
     "innfer_unet_post_slab_parts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "innfer_tile_plan": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)] * 6),
+    "innfer_tile_owner": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2),
+    "innfer_extract_tiles_rect": (C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
+    "innfer_extract_tiles_u8_rect": (C.c_int, [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_stitch_tiles": (C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
+    "innfer_stitch_tiles_u8": (C.c_int, [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_void_p]),
 }
 
 # INNFER_ABI_ANY=1 (measurement only: scripts/evidence_r5.sh A/Bs an OLDER build of the library against the current one on one box): bind the entry points that
@@ -337,6 +343,24 @@ def chop_plan(H, W, patch=200, step=0.5):
     ys, xs = (C.c_int * nh.value)(), (C.c_int * nw.value)()
     check(_lib.innfer_chop_plan(H, W, patch, step, C.byref(ps), C.byref(nh), C.byref(nw), ys, xs))
     return ps.value, list(ys), list(xs)
+
+
+def tile_plan(H, W, tile, halo=16):
+    """innfer_tile_plan (host only): (ph, pw, ys, xs), the lattice of the stitched tile path (`-tile N -tile_pad P`) -- per axis of A pixels
+    n = 1, P = A where A <= tile + 2 halo, else n = ceil((A - 2 halo) / tile), P = ceil((A + 2 halo (n - 1)) / n), origins min(i (P - 2 halo), A - P)."""
+    ph, pw, nh, nw = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+    check(_lib.innfer_tile_plan(int(H), int(W), int(tile), int(halo), C.byref(ph), C.byref(pw), C.byref(nh), C.byref(nw), None, None))
+    ys, xs = (C.c_int * nh.value)(), (C.c_int * nw.value)()
+    check(_lib.innfer_tile_plan(int(H), int(W), int(tile), int(halo), None, None, None, None, ys, xs))
+    return ph.value, pw.value, list(ys), list(xs)
+
+
+def tile_owner(A, tile, halo, X, scale=1):
+    """innfer_tile_owner (host only): (index, origin) of the tile that owns position X of the scale * A output axis, as the stitch kernels compute it:
+    index = the largest i with i == 0 or o_i + halo <= X // scale, origin = scale * o_index."""
+    index, origin = C.c_int(), C.c_int()
+    check(_lib.innfer_tile_owner(int(A), int(tile), int(halo), int(scale), int(X), C.byref(index), C.byref(origin)))
+    return index.value, origin.value
 
 
 BORDER_MODES = {"tile": 0, "mirror": 1, "replicate": 2, "alpha_pad": 3}       # INNFER_BORDER_*: the seamless modes

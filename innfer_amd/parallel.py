@@ -24,6 +24,7 @@ one-GPU rehearsal):
 
 No collective sits inside the per-tile compute.
 """
+import math
 import time
 
 import torch
@@ -114,7 +115,8 @@ def run_tile_batches(model_fn, tiles, tile_batch=None, sink=None, pick=None, out
     n = tiles.shape[0]
     outs = []
     lands = out is not None and pick is None and bool(getattr(model_fn, '_accepts_out', False))
-    cap = None if tile_batch else engine_tile_cap(model_fn, tiles.shape[-1], tiles.dtype, tiles.device)
+    ph, pw = tiles.shape[-2:]                       # rectangular tiles (Model.tile_forward): the cost of the square of the same area, an estimate -- the ladder below is the safety net
+    cap = None if tile_batch else engine_tile_cap(model_fn, pw if ph == pw else math.isqrt(ph * pw - 1) + 1, tiles.dtype, tiles.device)
     i = 0
     while i < n:
         sizes = tile_batches(n - i, tile_batch, cap)

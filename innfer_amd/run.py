@@ -171,9 +171,32 @@ def _into_out(r, out):
     return r if out is None else out.copy_(r)
 
 
+TILE_MIN = 32            # the smallest -tile: below it the halo outweighs the core
+TILE_PAD = 16            # the default -tile_pad (Real-ESRGAN's is 10; 16 = utils.SEAMLESS_PAD)
+
+
+def check_tile(tile, tile_pad=TILE_PAD, chop=True):
+    """The refusals of Model(tile=, tile_pad=) / `-tile N -tile_pad P`, made before anything touches the GPU: tile is None (the 200 / 0.5 chop), 0 (the whole
+    image) or an int >= TILE_MIN; tile_pad an int >= 0; a tile needs chop=True (a preset that already runs whole images has nothing to tile)."""
+    def is_int(v):
+        return isinstance(v, int) and not isinstance(v, bool)
+    if not is_int(tile_pad) or tile_pad < 0:
+        raise ValueError(f'tile_pad must be an int >= 0, got {tile_pad!r}')
+    if tile is None:
+        return
+    if not is_int(tile) or (tile != 0 and tile < TILE_MIN):
+        raise ValueError(f'tile must be None (the 200 / 0.5 chop), 0 (the whole image) or an int >= {TILE_MIN}, got {tile!r}')
+    if not chop:
+        raise ValueError(f'tile={tile} with chop=False: this model already runs whole images')
+
+
 class Model:
     def __init__(self, model_path, arch=None, scale=None, in_nc=3, out_nc=3, device='cuda',
-                 meval=True, strict=True, chop=True, tile_batch=None, state_dict=None):
+                 meval=True, strict=True, chop=True, tile_batch=None, state_dict=None, tile=None, tile_pad=TILE_PAD):
+        """tile: None -- the reference's chop (200 x 200 tiles at step 0.5, blended); 0 -- the whole image in one forward; N >= 32 -- stitched tiles of
+        about N x N low-resolution pixels plus a halo of tile_pad pixels that is thrown away (tile_forward; Real-ESRGAN's --tile / --tile_pad)."""
+        check_tile(tile, tile_pad, chop)
+        self.tile, self.tile_pad = tile, tile_pad
         self.model_path = model_path
         self.arch = arch
         self.scale = scale
@@ -241,15 +264,64 @@ class Model:
         return recompose_tensor(hr, H, W, step=step, scale=self.scale)
 
     def _tile_buffer(self, tiles):
-        """The [n, C', P, P] buffer the blend reads, allocated once so that every batch's result is written in place (no per-batch tensor + torch.cat):
-        known for the engines that state their output shape; None (concatenate) otherwise."""
+        """The [n, C', s P_h, s P_w] buffer the blend or the stitch reads (tiles: [n, C, P_h, P_w], square on the chop path), allocated once so that every
+        batch's result is written in place (no per-batch tensor + torch.cat): known for the engines that state their output shape; None (concatenate) otherwise."""
         m = self.model
         if self.arch == 'ppon' or not getattr(m, '_accepts_out', False):
             return None
-        n, _, ps, _ = tiles.shape
+        n, _, ph, pw = tiles.shape
         from .architectures.engine_module import EngineModule
-        shape = m._out_shape(n, ps, ps, device=tiles.device) if isinstance(m, EngineModule) else m._out_shape(n, ps, ps)
+        shape = m._out_shape(n, ph, pw, device=tiles.device) if isinstance(m, EngineModule) else m._out_shape(n, ph, pw)
         return torch.empty(tuple(shape), dtype=tiles.dtype, device=tiles.device)
+
+    def _run_tiles(self, tiles):
+        """The [n, C, P_h, P_w] tiles through the network in batches (parallel.run_tile_batches, PPON's pick), into the tile buffer where the engine states
+        its output shape; returns the contiguous [n, C', s P_h, s P_w] results and the scale s they show."""
+        from .parallel import run_tile_batches
+        hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=self._tile_buffer(tiles)).contiguous()
+        ph, pw = tiles.shape[2:]
+        s = hr.shape[2] // ph
+        if s < 1 or tuple(hr.shape[2:]) != (s * ph, s * pw):
+            raise ValueError(f'tile_forward: tiles of {ph}x{pw} came back as {hr.shape[2]}x{hr.shape[3]}, not an integer multiple')
+        return hr, s
+
+    def tile_forward(self, data, tile=None, tile_pad=None):
+        """Gather, run, stitch: the [1, C, H, W] tensor as equal tiles of about tile x tile pixels plus a halo of tile_pad pixels on every side that is not an
+        image edge (lib.tile_plan), each through the network on its own (in batches), every result pixel copied from the one tile that owns it
+        (innfer_extract_tiles_rect, innfer_stitch_tiles) -- nothing is blended, so with a halo no smaller than the network's receptive radius the result is the
+        whole-image forward's bit for bit.  tile / tile_pad default to the model's."""
+        from . import lib as L
+        from .utils import utils as U
+        tile = self.tile if tile is None else tile
+        tile_pad = self.tile_pad if tile_pad is None else tile_pad
+        check_tile(tile, tile_pad)
+        if not tile:
+            raise ValueError('tile_forward: needs a tile size (Model(tile=N) or tile=N)')
+        if data.dim() != 4 or data.shape[0] != 1:
+            raise NotImplementedError('tile_forward: one [1, C, H, W] image at a time')
+        U._need_cuda(data, 'tile_forward')
+        data = data.contiguous()
+        _, Cc, H, W = data.shape
+        ph, pw, ys, xs = L.tile_plan(H, W, tile, tile_pad)
+        n = len(ys) * len(xs)
+        with torch.no_grad(), torch.cuda.device(data.device):
+            stream = torch.cuda.current_stream(data.device).cuda_stream
+            tiles = torch.empty((n, Cc, ph, pw), dtype=data.dtype, device=data.device)
+            L.check(L.lib.innfer_extract_tiles_rect(data.data_ptr(), U._dt(data), Cc, H, W, tile, tile_pad, 0, n, tiles.data_ptr(), stream))
+            hr, s = self._run_tiles(tiles)
+            del tiles
+            out = torch.empty((1, hr.shape[1], s * H, s * W), dtype=hr.dtype, device=hr.device)
+            L.check(L.lib.innfer_stitch_tiles(hr.data_ptr(), U._dt(hr), n, hr.shape[1], H, W, tile, tile_pad, s, out.data_ptr(), stream))
+        return out
+
+    def _whole(self, fwd, *args, **kwargs):
+        """fwd(...) on a whole image; under tile=0 an allocator out-of-memory names the way out."""
+        try:
+            return fwd(*args, **kwargs)
+        except torch.OutOfMemoryError as e:
+            if self.tile == 0:
+                raise torch.OutOfMemoryError(f'the whole image does not fit the GPU in one forward (-tile 0): run it in tiles, e.g. -tile 1024 or -tile 512 ({e})') from e
+            raise
 
     def _pick(self, y):
         """PPON returns (content, structure, perceptual) and run.py keeps the last (run.py:191-192,220-221)."""
@@ -258,11 +330,18 @@ class Model:
     def _predict(self, x):
         return self._pick(self.model(x))
 
+    @property
+    def _whole_image(self):
+        """Whether forwards take the whole image: chop=False, or tile=0."""
+        return not self.chop or self.tile == 0
+
     def __call__(self, data):
-        if self.chop:
+        if self.chop and self.tile is None:
             return self.chop_forward(data, patch_size=200, step=0.5)
+        if self.chop and self.tile:
+            return self.tile_forward(data)
         with torch.no_grad():
-            return self._predict(data)
+            return self._whole(self._predict, data)
 
     def forward_tta(self, data):
         """The self-ensemble (`-tta`, "x8"): the mean of the eight dihedral orientations' results, turned back -- the definition run_u8(tta=True) is held
@@ -292,7 +371,10 @@ class Model:
         same of the padded image without the padding, with fit_channels utils.fit_channels_forward(self.forward_tta, img, ...), with outscale resampled
         as above.  On the chop path one gather fills the tiles of all eight orientations (innfer_extract_tiles_u8_tta), they run as one tile stream and
         one blend averages the eight results before it quantises (innfer_recompose_u8_tta); without chop, or where that tile buffer does not fit
-        (_tta_fits), forward_tta runs on the device tensor between the existing conversions -- the same bits."""
+        (_tta_fits), forward_tta runs on the device tensor between the existing conversions -- the same bits.
+        Model(tile=N): self(...) above is tile_forward, and every definition holds with it inside.  Plain and seamless= images go through the uint8 gather
+        and stitch (_tile_u8: innfer_extract_tiles_u8_rect, innfer_stitch_tiles_u8 -- neither the float image nor the padded image exists); fit_channels
+        and tta run the tensor path with the tiled __call__ as the forward.  Model(tile=0) runs as chop=False does."""
         import numpy as np
         if outscale is not None:
             return self._run_u8_outscale(img, outscale, outfilter, normalize, fp16, out, fit_channels, seamless, tta)
@@ -302,7 +384,7 @@ class Model:
         mode = None
         if seamless is not None:
             mode = U.seamless_mode(seamless, *img.shape[:2])
-            if not self.chop:
+            if self._whole_image:
                 return self._run_u8_padded(img, seamless, normalize, fp16, out, fit_channels, tta)
         if fit_channels:
             dtype = img.dtype if host else (np.uint8 if img.dtype == torch.uint8 else np.float32)
@@ -316,12 +398,14 @@ class Model:
         if d.dim() != 3:
             raise TypeError('run_u8: expected a uint8 HWC image')
         with torch.no_grad(), torch.cuda.device(d.device):
-            if self.chop:
+            if self.chop and self.tile is None:
                 out = self._chop_u8(d, normalize, fp16, out, mode=mode, tta=tta)
+            elif not self._whole_image:                         # tile=N: the uint8 gather and stitch; tta through the tensor path with the tiled __call__ inside
+                out = self._tta_tensor_u8(d, normalize, fp16, out, None, mode) if tta else self._tile_u8(d, normalize, fp16, out, mode)
             elif isinstance(self.model, EngineModule) and self.arch != 'ppon' and not tta:
-                out = self.model.forward_u8(d, normalize=normalize, fp16=fp16, out=out)
+                out = self._whole(self.model.forward_u8, d, normalize=normalize, fp16=fp16, out=out)
             else:
-                out = self._tensor_u8(d, normalize, fp16, None, self.forward_tta if tta else self._predict, out)
+                out = self._whole(self._tensor_u8, d, normalize, fp16, None, self.forward_tta if tta else self._predict, out)
         return out.cpu().numpy() if host else out
 
     def _as_device_u8(self, img):
@@ -376,15 +460,42 @@ class Model:
         L.check(L.lib.innfer_nchw_to_u8hwc(y.data_ptr(), U._dt(y), y.shape[2], y.shape[3], y.shape[1], int(bool(normalize)), out.data_ptr(), stream))
         return out
 
-    def _tta_tensor_u8(self, d, normalize, fp16, out, fit_C, mode):
-        """run_u8(tta=True) of the uint8 device image d without the fused kernels: _tensor_u8 with forward_tta, under a border code `mode` of the image
-        padded in front and cropped behind."""
+    def _tta_tensor_u8(self, d, normalize, fp16, out, fit_C, mode, fwd=None):
+        """run_u8(tta=True) of the uint8 device image d without the fused kernels: _tensor_u8 with forward_tta (or another forward `fwd`), under a border
+        code `mode` of the image padded in front and cropped behind."""
         from . import lib as L
         from .utils import utils as U
+        fwd = fwd or self.forward_tta
         if mode is None:
-            return self._tensor_u8(d, normalize, fp16, fit_C, self.forward_tta, out)
+            return self._tensor_u8(d, normalize, fp16, fit_C, fwd, out)
         src = U.seamless_pad(d, next(name for name, code in L.BORDER_MODES.items() if code == mode))
-        return _into_out(U.seamless_crop(self._tensor_u8(src, normalize, fp16, fit_C, self.forward_tta), int(self.scale or 1)), out)
+        return _into_out(U.seamless_crop(self._tensor_u8(src, normalize, fp16, fit_C, fwd), int(self.scale or 1)), out)
+
+    def _tile_u8(self, d, normalize, fp16, out, mode=None):
+        """The stitched tile path of run_u8 (tile=N) for the uint8 device image d: plan, gather, run the tiles, stitch -- innfer_extract_tiles_u8_rect and
+        innfer_stitch_tiles_u8, np2tensor in the gather's load and tensor2np in the stitch's store, so the float image never exists.  mode: the border code
+        of run_u8(seamless=): the lattice is the padded image's, the gather reads through the border map and the stitch stores the crop window only, so the
+        padded image never exists either."""
+        from . import lib as L
+        from .utils import utils as U
+        H, W, Cc = d.shape
+        dt, code = (torch.float16, L.F16) if fp16 else (torch.float32, L.F32)
+        stream = torch.cuda.current_stream(d.device).cuda_stream
+        pad, border = (0, L.BORDER_MODES['replicate']) if mode is None else (U.SEAMLESS_PAD, mode)
+        ph, pw, ys, xs = L.tile_plan(H + 2 * pad, W + 2 * pad, self.tile, self.tile_pad)
+        n = len(ys) * len(xs)
+        tiles = torch.empty((n, Cc, ph, pw), dtype=dt, device=d.device)
+        L.check(L.lib.innfer_extract_tiles_u8_rect(d.data_ptr(), Cc, H, W, int(bool(normalize)), self.tile, self.tile_pad, 0, n, pad, border,
+                                                   tiles.data_ptr(), code, stream))
+        hr, s = self._run_tiles(tiles)
+        del tiles
+        shape = (H * s, W * s, hr.shape[1])
+        _check_out(out, shape)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint8, device=d.device)
+        L.check(L.lib.innfer_stitch_tiles_u8(hr.data_ptr(), U._dt(hr), n, hr.shape[1], H + 2 * pad, W + 2 * pad, self.tile, self.tile_pad, s,
+                                             int(bool(normalize)), pad, out.data_ptr(), stream))
+        return out
 
     def _chop_u8(self, d, normalize, fp16, out, fit_C=None, mode=None, tta=False):
         """The chop path of run_u8 for the uint8 device image d: plan, gather, run the tiles, blend -- one gather and one blend call for all four forms.
@@ -462,10 +573,12 @@ class Model:
         d, host = self._as_device_u8(img)
         _check_out(out, U.fit_channels_out_shape(tuple(d.shape), int(self.scale or 1)))
         with torch.no_grad(), torch.cuda.device(d.device):
-            if self.chop:
+            if self.chop and self.tile is None:
                 out = self._chop_u8(d, normalize, fp16, out, fit_C=C, mode=mode, tta=tta)
+            elif not self._whole_image:                         # tile=N: the tensor path, one tiled __call__ per plane
+                out = self._tta_tensor_u8(d, normalize, fp16, out, C, mode, self.forward_tta if tta else self)
             else:
-                out = self._tensor_u8(d, normalize, fp16, C, self.forward_tta if tta else self._predict, out)
+                out = self._whole(self._tensor_u8, d, normalize, fp16, C, self.forward_tta if tta else self._predict, out)
         return out.cpu().numpy() if host else out
 
 
@@ -554,6 +667,11 @@ def build_parser():
     parser.add_argument('-tta', required=False, action='store_true', default=argparse.SUPPRESS,
                         help='Self-ensemble ("x8"): run the image in its eight flipped / rotated orientations and average the results before quantisation; '
                              'eight times the network cost.')
+    parser.add_argument('-tile', required=False, type=int, default=argparse.SUPPRESS,
+                        help=f'Stitch large tiles instead of blending 200 x 200 ones: tiles of about N x N pixels (N >= {TILE_MIN}, e.g. 512 or 1024) plus a halo '
+                             'that is thrown away, about 1.1x the image through the network where the default runs 3.7x or more.  0: the whole image in one forward.')
+    parser.add_argument('-tile_pad', required=False, type=int, default=argparse.SUPPRESS,
+                        help=f'Halo of -tile in pixels (default {TILE_PAD}): context on every tile side that is not an image edge.')
     return parser
 
 
@@ -587,6 +705,12 @@ def main(argv=None):
     if seamless and resize:
         raise ValueError(f"-seamless {seamless} with '{args.arch}': the preset enlarges every image to a multiple of {resize} px first, which no tileable "
                          "texture survives; resize the texture yourself and run it without the preset")
+    tile, tile_pad = getattr(args, 'tile', None), getattr(args, 'tile_pad', TILE_PAD)
+    if tile is None and hasattr(args, 'tile_pad'):
+        raise ValueError('-tile_pad is the halo of -tile N: give both')
+    if tile is not None and not chop:
+        raise ValueError(f"-tile {tile} with '{args.arch}': the preset already runs every image whole, there is nothing to tile")
+    check_tile(tile, tile_pad, chop)
     tta = getattr(args, 'tta', False)
     outscale, outfilter = getattr(args, 'outscale', None), getattr(args, 'outfilter', 'lanczos')
     if outscale is not None:
@@ -597,7 +721,7 @@ def main(argv=None):
     scale = args.scale if args.scale != -1 else None        # (sic) the string '-1' never equals -1: the flag's value is what parse_models ignores
     del scale
     model_chain, scale_chain = parse_models(args.models)
-    models = [Model(mc, args.arch, sc, device=device, meval=meval, strict=strict, chop=chop) for mc, sc in zip(model_chain, scale_chain)]
+    models = [Model(mc, args.arch, sc, device=device, meval=meval, strict=strict, chop=chop, tile=tile, tile_pad=tile_pad) for mc, sc in zip(model_chain, scale_chain)]
     if not fp16:
         # -no_fp16 = fp32 arithmetic on the GPU (run.py:345,421-422).  RRDBNet / SRResNet have an fp32-accurate engine, every other shipped generator an fp32
         # mode (float32 tensors select them).  The check stays for an engine built fp16-only: it must refuse, not hand out fp16 accuracy under the flag.
