@@ -53,6 +53,7 @@ class EngineModule(nn.Module):
                                      # phases in one visit of a tile, 2: one phase per visit (rounds 3's form; same bits), False / 0: nine taps on the HR grid
         self.hr_chain = True         # innfer_net_set_hr_chain: the last upconv_block -> HR_conv0 -> conv_last as ONE kernel chained through LDS (bit-identical to the launches it replaces)
         self.fused_tail = True       # innfer_net_set_fused_tail: HR_conv0 -> conv_last as one kernel where the shapes allow it (results agree to the last fp16 rounding with the two-launch form)
+        self.consumer_grid = 1       # innfer_net_set_consumer_grid: RRDBNet's 64-output trunk convs on the 2 x 4 consumer-wave grid with the residual prefetched (1, default) or the 8 x 1 form (0): bit-identical
         self.residual_lds = 1        # innfer_net_set_residual_lds: the dense block's `x5 * 0.2 + x` takes x from the conv's own staged LDS tiles -- 1 the RRDB-end blocks (measured gain), 2 every block, 0 never (all agree to the last fp16 rounding)
 
     unshuffle = 1                    # pixel_unshuffle factor the engine folds into its first conv (RealESRGANNet: 2 / 4): the result has (engine scale // unshuffle) x the input's size
@@ -199,6 +200,8 @@ class EngineModule(nn.Module):
         L.check(L.lib.innfer_net_set_fused_tail(self._handle, int(bool(self.fused_tail))))
         L.check(L.lib.innfer_net_set_hr_chain(self._handle, int(bool(self.hr_chain))))
         L.check(L.lib.innfer_net_set_residual_lds(self._handle, int(self.residual_lds)))
+        if hasattr(L.lib, 'innfer_net_set_consumer_grid'):      # (absent from an older library bound with INNFER_ABI_ANY=1 for an A/B run)
+            L.check(L.lib.innfer_net_set_consumer_grid(self._handle, int(self.consumer_grid)))
         L.check(L.lib.innfer_net_set_upconv_phases(self._handle, int(self.upconv_phases)))
         L.check(L.lib.innfer_net_set_outm(self._handle, int(getattr(self, '_outm', 0))))
         L.check(L.lib.innfer_net_set_precision(self._handle, int(x.dtype == torch.float32)))
@@ -234,6 +237,8 @@ class EngineModule(nn.Module):
             L.check(L.lib.innfer_net_set_fused_tail(self._handle, int(bool(self.fused_tail))))
             L.check(L.lib.innfer_net_set_hr_chain(self._handle, int(bool(self.hr_chain))))
             L.check(L.lib.innfer_net_set_residual_lds(self._handle, int(self.residual_lds)))
+            if hasattr(L.lib, 'innfer_net_set_consumer_grid'):
+                L.check(L.lib.innfer_net_set_consumer_grid(self._handle, int(self.consumer_grid)))
             L.check(L.lib.innfer_net_set_upconv_phases(self._handle, int(self.upconv_phases)))
             L.check(L.lib.innfer_net_set_u8_io(self._handle, int(bool(normalize)), int(bool(fp16))))
             L.check(L.lib.innfer_net_set_precision(self._handle, int(not fp16)))

@@ -147,6 +147,8 @@ struct ConvLaunch {
                                                   // `bias`.  Built as the epilogue of the plain 3x3 slab convs of 64 (rowp 0 / 1) and 32 outputs (conv3x3_pc PRELU); every other form refuses act 8
     int res1_lds;                                 // 1: when res1 is the conv's own input (groups 0, 1: the dense block's x5 * 0.2 + x), act 0 and K = 64, take it from the staged LDS tiles
                                                   // (conv3x3_pc RLDS: chunk order 2, 3, .., 0, 1; the residual enters the fp32 accumulators as x / s1) instead of re-reading it in the epilogue
+    int grid2;                                    // 1: the plain / RLDS 3x3 slab conv with K = 64 and plane-order panels (rowp 1) runs its consumer waves as a 2 x 4 grid with the memory
+                                                  // residual prefetched (conv3x3_pc GRID2) wherever that form exists -- not on an image canvas; same bits as the 8 x 1 form
 };
 
 // Panel geometry of packed weights.

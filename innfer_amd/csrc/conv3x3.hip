@@ -522,7 +522,16 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     // rounding of the sum), the epilogue scales by s1.  265 MB of every 1327 MB launch (1080p) are no longer read twice; the RRDB-end launches, whose two
     // residuals' loads did not fit the registers as one batch, keep ONE memory residual and hoist its loads like the others.
     constexpr bool RLDS = (TMF & PC_RLDS) != 0;
-    static_assert(!RLDS || (RPW == 2 && NT == 4 && NCW == 8 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_RLDS) == TAPS_3X3 && !S9 && !POLY), "residual from LDS: the plain 64-channel instantiation (and its canvas form)");
+    // + PC_GRID2: the eight consumer waves of a 64-output slab conv as a 2 x 4 grid -- wave cw owns channel half cw >> 2 (32 channels: accumulator tiles 2 half, 2 half + 1 of
+    // the plane row order, panel rows 32 half .. 32 half + 31) of row group cw & 3 (4 rows) of the same 16 x 32 tile, i.e. RPW 4, NT 2 over the 64-row panels: the same 64
+    // accumulator registers, 24 weight-fragment registers instead of 48, 54 instead of 60 ds_read_b128 per 144 MFMAs.  The freed registers hold the tile's one memory residual
+    // (res1; behind RLDS res2), loaded at the top of the tile's LAST chunk instead of the top of the epilogue (residual_prefetch_grid2 / epilogue_slab_grid2).  Every accumulator
+    // sees the same MFMAs in the same order (chunk, tap column, halo row, tap row) and the same epilogue arithmetic: same bits as the 8 x 1 form.  Loaders, barriers, LDS layout
+    // and tile walk are those of <2, 4>.
+    constexpr bool GRID2 = (TMF & PC_GRID2) != 0;
+    static_assert(!GRID2 || (RPW == 4 && NT == 2 && NCW == 8 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & ~(TAPS_3X3 | PC_RLDS | PC_ROWP | PC_GRID2)) == 0 && (TMF & PC_ROWP) && TM == TAPS_3X3 && !S9 && !POLY && !CV),
+                  "2 x 4 consumer grid: the plain and the RLDS 64-output plane-order slab conv");
+    static_assert(!RLDS || (((RPW == 2 && NT == 4) || GRID2) && NCW == 8 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_RLDS) == TAPS_3X3 && !S9 && !POLY), "residual from LDS: the plain 64-channel instantiation (its canvas form, its 2 x 4 consumer grid)");
     // + PC_SGATE: PAN's pixel attention behind an up-conv (PAN_arch.py:11-35: upconv -> PA: x * sigmoid(conv1x1(x)) -> LeakyReLU) inside the up-conv's
     // epilogue: a lane's accumulators are 8 consecutive channels of its pixel (NT = 2 row order), i.e. after the fp16 conversion -- the value the two-launch
     // schedule stored -- the B fragment of the 1x1 conv; two MFMAs per pixel tile against the 32 x 32 gate matrix held in registers, then v * sigmoid(g) goes
@@ -545,7 +554,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     constexpr bool UP4 = (TMF & PC_UP4) != 0;
     // + PC_ROWP: the plane row order of the 64-channel groups (see toff_slab): plain 3x3 slab convs (canvas, RLDS, FUSE forms included) and the one-pass up-conv
     constexpr bool ROWP = (TMF & PC_ROWP) != 0;
-    static_assert(!ROWP || (RPW == 2 && NT == 4 && NCW == 8 && OUTMODE == OUT_SLAB && TM == TAPS_3X3 && (TMF & ~(TAPS_3X3 | PC_FUSE | PC_RLDS | PC_UP4 | PC_ROWP | PC_PSH | PC_PRELU)) == 0 && !S9 && !POLY), "plane row order: the 64-channel slab kernels");
+    static_assert(!ROWP || (((RPW == 2 && NT == 4) || GRID2) && NCW == 8 && OUTMODE == OUT_SLAB && TM == TAPS_3X3 && (TMF & ~(TAPS_3X3 | PC_FUSE | PC_RLDS | PC_UP4 | PC_ROWP | PC_PSH | PC_PRELU | PC_GRID2)) == 0 && !S9 && !POLY), "plane row order: the 64-channel slab kernels");
     // + PC_PSH: nn.PixelShuffle(2) as the store of a conv nf -> 4 nf (pixelshuffle_block, block.py:333-346; SRResNet's up stages, RRDBNet(upsample_mode=
     // 'pixelshuffle')) on THIS kernel -- until round 4 those launches ran on the two-workgroup kernel of round 1 (0.30 of the MFMA peak, a third of an SRResNet frame).
     // The panels are phase-major (conv_pack_shuffle2) in the plane row order, so a channel group is one output phase of 64 channels and the epilogue is the
@@ -569,7 +578,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     constexpr int IN_BYTES = L::IN_BYTES;
     constexpr int NQ = IN_BYTES / 1024;
     constexpr int KQ = (NQ + NLW - 1) / NLW;
-    constexpr int WROWS = NT * 16;
+    constexpr int WROWS = L::WROWS;
     constexpr int NTAP = L::NTAP;
     constexpr int W_BYTES = L::W_BYTES;
     constexpr int WQ = W_BYTES / 1024;
@@ -641,13 +650,14 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     __builtin_amdgcn_s_setprio(INNFER_CPRIO);
 #endif
     const int cw = wave;
+    const int cwr = GRID2 ? (cw & 3) : cw;                        // the wave's row group (GRID2: cw = 4 * channel half + row group)
     int boffs[3][2];
 #pragma unroll
     for (int s = 0; s < 3; ++s)
 #pragma unroll
         for (int par = 0; par < 2; ++par) {
-            const int pb = cw * RPW * LWP + li + s;
-            const int rowpar = ((cw * RPW) & 1) ^ par;
+            const int pb = cwr * RPW * LWP + li + s;
+            const int rowpar = ((cwr * RPW) & 1) ^ par;
             boffs[s][par] = pb * 64 + ((lg ^ (((((li + s) >> 2) & 1) ^ rowpar) << 1)) << 4);
         }
     // PAIR: segment 1 starts at LDS column 18 (the second image's halo row), not 16: its own swizzle term
@@ -662,14 +672,19 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
                 boffp[s][par] = pb * 64 + ((lg ^ (((((18 + li + s) >> 2) & 1) ^ rowpar) << 1)) << 4);
             }
     }
-    const int aoffs = li * 64 + ((lg ^ (((li >> 2) & 1) << 1)) << 4);
+    const int aoffs = li * 64 + ((lg ^ (((li >> 2) & 1) << 1)) << 4) + (GRID2 ? (cw >> 2) * 32 * 64 : 0);      // (GRID2: the half's 32 panel rows)
     // RLDS: byte offset of the lane's 16 residual channels (two 16-byte slots; the swizzle swaps slot PAIRS, so they stay adjacent) of its pixel tile m inside a
     // stage: LDS pixel P = the centre tap's operand of output pixel (cw * RPW + m / 2, li + 16 (m % 2))
-    int roffs[RLDS ? MT : 1];
-    if constexpr (RLDS) {
+    int roffs[RLDS ? (GRID2 ? 2 : MT) : 1];
+    if constexpr (RLDS && GRID2) {
+        // eight pixel tiles: one base per row parity (the swizzle term, as for boffs) + immediates -- six registers fewer than one offset per tile
+#pragma unroll
+        for (int par = 0; par < 2; ++par)
+            roffs[par] = ((cwr * RPW + 1) * LWP + li + 1) * 64 + ((lg ^ (((((li + 1) >> 2) & 1) ^ par) << 1)) << 4);
+    } else if constexpr (RLDS) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
-            const int P = (cw * RPW + (m >> 1) + 1) * LWP + li + (m & 1) * 16 + 1;
+            const int P = (cwr * RPW + (m >> 1) + 1) * LWP + li + (m & 1) * 16 + 1;
             roffs[m] = P * 64 + (((lg & 1) ^ ((P >> 2) & 1)) << 5);
             if constexpr (ROWP) roffs[m] = P * 64 + ((lg ^ (((P >> 2) & 1) << 1)) << 4);      // plane order: the ONE 16-byte slot with channels 8 lg .. 8 lg + 7 of the staged group
         }
@@ -745,6 +760,13 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
         for (int e = 0; e < 8; ++e) pfx[m][e] = 0.f;
     int jt = j0, c = 0;
     int kg = 0, n = 0, ty0 = 0, tx0 = 0, cbase = 0, dcur = 1;
+    [[maybe_unused]] f16x4 rpre[GRID2 ? MT : 1][NT];              // GRID2: the prefetched residual of the current tile
+    if constexpr (GRID2) {
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) rpre[m][t] = f16x4{0, 0, 0, 0};
+    }
     asm volatile("s_barrier" ::: "memory");                       // chunk 0 of the first tile has landed
 #ifdef INNFER_STAMPS
     const unsigned long long k_c0 = clock64(), k_w0 = wall_clock64();
@@ -753,7 +775,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
         if (c == 0) {
             if constexpr (POLY) decode_poly(jt, kg, n, ty0, tx0, dcur);
             else decode(jt, kg, n, ty0, tx0);
-            cbase = kg * WROWS + lane_cbase<NT, ROWP>(lg);
+            cbase = kg * WROWS + (GRID2 ? (cw >> 2) * 32 : 0) + lane_cbase<NT, ROWP>(lg);
             if (kg != bias_kg) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) bias_r[t] = *(const f32x4*)(p.bias + cbase + toff_lin<NT, ROWP>(t));
@@ -774,6 +796,15 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
                         for (int j = 0; j < 4; ++j) acc[t][m][j] = __builtin_fmaf(acc[t][m][j], SPLIT_DOWN, bias_r[t][j]);
             }
         }
+#ifndef INNFER_GRID2_LATE
+        if constexpr (GRID2) {
+            // the tile's one memory residual, issued a whole chunk of MFMAs ahead of the epilogue that adds it (the coordinates are known since the tile's first chunk)
+            if (c == p.nchunks - 1) {
+                if constexpr (RLDS) { if (p.res2) residual_prefetch_grid2(p, p.res2, p.res2_gstride, rpre, n, ty0, tx0, cwr, li, cbase); }
+                else { if (p.res1) residual_prefetch_grid2(p, p.res1, p.res1_gstride, rpre, n, ty0, tx0, cwr, li, cbase); }
+            }
+        }
+#endif
         const char* st = NSI == 3 ? smem + islot * IN_BYTES : smem + (g & 1) * STAGE;                       // halo tile
         const char* sw = NSI == 3 ? smem + 3 * IN_BYTES + (g & 1) * W_BYTES : st + IN_BYTES;              // weight panel
         if constexpr (NSI == 3) islot = islot == 2 ? 0 : islot + 1;
@@ -794,8 +825,10 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
             // same order: results are unchanged.
             constexpr int GPS = 2 * (RPW + 2);                     // B fragments (= MFMA groups) per tap column
             constexpr int NB = 3 * GPS;
+            // (GRID2: a ring of FOUR, each read three groups ahead -- its groups are 2 .. 6 MFMAs, two groups can be as few as 6 MFMAs of cover)
+            constexpr int RING = GRID2 ? 4 : 3, AHEAD = RING - 1;
             f16x8 a[3][NT];
-            f16x8 bq[3];
+            f16x8 bq[RING];
             auto lda = [&](int sc, int r) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) a[r][t] = *(const f16x8*)(sw + aoffs + ((r * 3 + sc) * WROWS + t * 16) * 64);
@@ -805,22 +838,23 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
                 return *(const f16x8*)(st + boffs[sc][rr & 1] + (rr * LWP + seg * 16) * 64);
             };
             lda(0, 0); lda(0, 1); lda(0, 2);
-            bq[0] = ldb(0); bq[1] = ldb(1);
+#pragma unroll
+            for (int i = 0; i < AHEAD; ++i) bq[i] = ldb(i);
             if constexpr (BRELU) bq[0] = relu_frag(bq[0]);
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
                 const int sc = i / GPS, j = i - sc * GPS, rr = j >> 1, seg = j & 1;
-                if (i + 2 < NB) bq[(i + 2) % 3] = ldb(i + 2);
+                if (i + AHEAD < NB) bq[(i + AHEAD) % RING] = ldb(i + AHEAD);
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
                     const int rw = rr - r;
                     if (rw >= 0 && rw < RPW) {
 #pragma unroll
                         for (int t = 0; t < NT; ++t)
-                            acc[t][rw * 2 + seg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[r][t], bq[i % 3], acc[t][rw * 2 + seg], 0, 0, 0);
+                            acc[t][rw * 2 + seg] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[r][t], bq[i % RING], acc[t][rw * 2 + seg], 0, 0, 0);
                     }
                 }
-                if constexpr (BRELU) { if (i + 1 < NB) bq[(i + 1) % 3] = relu_frag(bq[(i + 1) % 3]); }      // the NEXT group's fragment, in the shadow of this group's MFMAs
+                if constexpr (BRELU) { if (i + 1 < NB) bq[(i + 1) % RING] = relu_frag(bq[(i + 1) % RING]); }      // the NEXT group's fragment, in the shadow of this group's MFMAs
                 if (sc < 2 && seg == 1) {
                     if (rr == RPW - 1) lda(sc + 1, 0);
                     if (rr == RPW) lda(sc + 1, 1);
@@ -876,7 +910,9 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
         }
         if constexpr (RLDS) {
             // chunk nchunks - 2 is input group 0 = residual channels 0..31 (lanes lg 0, 1), chunk nchunks - 1 group 1 = channels 32..63 (lanes lg 2, 3)
-            if constexpr (ROWP) {        // plane order: every lane takes 8 channels from each of the two groups -- tiles 0, 1 from group 0, tiles 2, 3 from group 1
+            if constexpr (GRID2) {       // the wave's half IS one group: half h takes its 8 channels per lane at chunk nchunks - 2 + h only
+                if (c == p.nchunks - 2 + (cw >> 2)) residual_from_lds_grid2<MT>(acc, st, roffs, p.rs1);
+            } else if constexpr (ROWP) {        // plane order: every lane takes 8 channels from each of the two groups -- tiles 0, 1 from group 0, tiles 2, 3 from group 1
                 if (c == p.nchunks - 2) residual_from_lds_plane<MT, 0>(acc, st, roffs, p.rs1);
                 else if (c == p.nchunks - 1) residual_from_lds_plane<MT, 1>(acc, st, roffs, p.rs1);
             } else {
@@ -974,7 +1010,7 @@ int canvas_grid(const KP& k, int N, int* gy, long* tiles) {
 
 template <int RPW, int NT, int NLW, int OUTMODE, bool S9, bool POLY, int TM, bool CV, int NSI, int NCW>
 int launch_pc(const KP& kp, int N, hipStream_t s) {
-    constexpr int TH = NCW * RPW;
+    constexpr int TH = PcLayout<RPW, NT, NSI, NCW, TM>::TH;
     constexpr int LDS = PcLayout<RPW, NT, NSI, NCW, TM>::LDS_BYTES;
     static_assert(LDS <= 160 * 1024, "the stages must fit the CU's LDS");
     static_assert(NSI == 2 || (NSI == 3 && !S9 && !POLY), "the three-slot input ring exists for the plain and the canvas loader");
@@ -1256,6 +1292,10 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP | PC_PSH>(k, L.N, s);
     }
     if (pc && L.out_mode == OUT_SLAB && nt == 4 && L.stats_part) return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_STATS>(k, L.N, s);
+    // the 2 x 4 consumer grid (conv3x3_pc<4, 2, .., TMF | PC_GRID2>) of the plain and the RLDS plane-order conv with one 64-channel output group -- except where the launch
+    // would be laid out as an image canvas (launch_pc), a form the grid does not have
+    bool grid2 = pc && L.grid2 && L.out_mode == OUT_SLAB && nt == 4 && L.rowp == 1 && L.K == 64 && L.act <= 2 && INNFER_KNOB("INNFER_GRID2", 1);
+    if (grid2 && INNFER_KNOB("INNFER_CANVAS", 1)) { int gy = 0; long t = 0; grid2 = canvas_grid<16>(k, L.N, &gy, &t) == 0; }
     if (pc && L.out_mode == OUT_SLAB && nt == 4 && L.res1_lds && L.res1 && L.res1 == L.in && L.res1_gstride == L.in_gstride && L.act == 0 && L.K == 64 && L.C >= 96 &&
         !L.up && !L.reflect && L.s1 != 0.f && (L.res1_lds == 2 || L.res2)) {
         // the dense block's last conv: the residual is the conv's own input groups 0 and 1 -- taken from the live LDS stages (conv3x3_pc<.., TMF | PC_RLDS>).
@@ -1264,11 +1304,13 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         // (0.4096 -> 0.3945 ms per launch at 1080p).  The one-residual layers' batched loads were L2 hits already hidden behind the tile's last MFMAs: the LDS
         // form costs them +0.9 % (0.3574 -> 0.3607 ms), so they keep the epilogue load; res1_lds 2 forces the LDS form everywhere (profiles/r4/rlds_ab.txt).
         k.rs1 = 1.0f / L.s1;
+        if (grid2) return launch_pc<4, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_RLDS | PC_ROWP | PC_GRID2>(k, L.N, s);
         return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_RLDS | PC_ROWP>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_RLDS>(k, L.N, s);
     }
     if (pc && L.out_mode == OUT_SLAB && nt == 4) {
         // diagnostic builds: four consumer waves of twice the rows (measured within +-1 %: profiles/r2/kernel_experiments.txt 10)
         if (!L.rowp && (INNFER_KNOB("INNFER_FAT", 0) & 2)) return launch_pc<4, 4, 4, OUT_SLAB, false, false, TAPS_3X3, false, 2, 4>(k, L.N, s);
+        if (grid2) return launch_pc<4, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP | PC_GRID2>(k, L.N, s);
         return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP>(k, L.N, s) : launch_pc<2, 4, 4>(k, L.N, s);
     }
     if (L.conv7) {         // 7x7 (padding 3) as nine displaced 3x3 convs: planar output, <= 16 output channels, panels from conv_pack7x7

@@ -148,11 +148,12 @@ __device__ __forceinline__ void epilogue_slab(const KP& p, f32x4 (&acc)[NT][2 * 
     for (int m = 0; m < MT; ++m) {
         ok[m] = PAIR ? (2 * n + (m & 1) < p.N && yw + (m >> 1) < ylim && xl < xlim) : ((yw + (m >> 1) < ylim) && (xl + (m & 1) * 16 < xlim));
         const long o = (m >> 1) * rowstep + (m & 1) * colstep;
-        if (HOIST && R1 && ok[m]) {
+        // (abl 512, wrong results by construction: no hoisted residual loads -- what the epilogue's loads cost a launch beyond the work they feed: docs/EXPERIMENTS.md 134)
+        if (HOIST && R1 && ok[m] ABL_AND(!(p.abl & 512))) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) r1[R1 ? m : 0][t] = *(const f16x4*)(r1b + o + toff_slab<NT, ROWP>(t, p.res1_gstride));
         }
-        if (HOIST && R2 && ok[m]) {
+        if (HOIST && R2 && ok[m] ABL_AND(!(p.abl & 512))) {
 #pragma unroll
             for (int t = 0; t < NT; ++t) r2[R2 ? m : 0][t] = *(const f16x4*)(r2b + o + toff_slab<NT, ROWP>(t, p.res2_gstride));
         }
@@ -208,6 +209,80 @@ __device__ __forceinline__ void epilogue_slab(const KP& p, f32x4 (&acc)[NT][2 * 
                 h[j] = (f16)f;
             }
             *(f16x4*)(op + toff_slab<NT, ROWP>(t, p.out_gstride)) = h;
+        }
+    }
+}
+
+// GRID2 (conv3x3_pc<4, 2, .., TMF | PC_ROWP | PC_GRID2>: a wave owns 4 rows x 32 channels of ONE slab plane): the plain slab epilogue (no POLY / DCV / PAIR / PSH) with one
+// residual already in registers.  grid2_tile: the wave's part of the tile -- element offset of (pixel tile 0, channel cbase) inside plane 0 of a tensor, and which of its
+// eight pixel tiles lie inside the launch's rows / the image; the prefetch and the epilogue both take their addresses and validity from it.
+struct Grid2Tile { long pix; long rowstep; bool ok[8]; };
+__device__ __forceinline__ Grid2Tile grid2_tile(const KP& p, int n, int ty0, int tx0, int rg, int li, int cbase) {
+    Grid2Tile g;
+    const int yw = ty0 + rg * 4, xl = tx0 + li;
+    g.pix = (((long)n * p.H + yw) * p.W + xl) * 32 + (cbase & 31);
+    g.rowstep = (long)p.W * 32;
+#pragma unroll
+    for (int m = 0; m < 8; ++m) g.ok[m] = (yw + (m >> 1) < p.y1) && (xl + (m & 1) * 16 < p.W);
+    return g;
+}
+// The loads of residual `res` (16 x f16x4 per lane) for the wave's part of tile (n, ty0, tx0), issued at the top of the tile's last chunk.  Straight-line code: a pixel
+// tile outside the launch's rows / the image (ragged tiles; never added, never stored) loads the nearest pixel inside instead of being branched around -- the rows are
+// wave-uniform, the columns two per-lane offsets; every other pixel tile reads exactly the address the epilogue would have read.
+__device__ __forceinline__ void residual_prefetch_grid2(const KP& p, const f16* res, long gstride, f16x4 (&rpre)[8][2], int n, int ty0, int tx0, int rg, int li, int cbase) {
+    const int yw = ty0 + rg * 4, xl = tx0 + li;
+    const f16* rb = res + (cbase >> 5) * gstride + (cbase & 31);
+    const int xo[2] = {min(xl, p.W - 1) * 32, min(xl + 16, p.W - 1) * 32};
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const long ro = ((long)n * p.H + min(yw + r, p.y1 - 1)) * p.W * 32;
+#pragma unroll
+        for (int sg = 0; sg < 2; ++sg)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) rpre[2 * r + sg][t] = *(const f16x4*)(rb + ro + xo[sg] + 4 * t);
+    }
+}
+// PRE: which residual `rpre` holds -- 1: res1 (R1), 2: res2 (R2), 0: none.  A second memory residual (R1 && R2: PRE 1, res2) is loaded here, for all pixel tiles first.
+// The arithmetic is epilogue_slab's: act -> [* s1 (SC1)] -> * s1 + res1 -> * s2 + res2, explicit fmaf, one pinned fp32 value, one conversion.
+template <int ACT, bool R1, bool R2, bool SC1, int PRE>
+__device__ __forceinline__ void epilogue_slab_grid2(const KP& p, f32x4 (&acc)[2][8], const f16x4 (&rpre)[8][2], int n, int ty0, int tx0, int rg, int li, int cbase) {
+    static_assert((PRE == 0 && !R1 && !R2) || (PRE == 1 && R1) || (PRE == 2 && R2 && !R1), "the prefetched residual is the one memory residual (res1 when there are two)");
+    const Grid2Tile g = grid2_tile(p, n, ty0, tx0, rg, li, cbase);
+    const int oc0 = cbase + p.out_coff;
+    f16* ob = (f16*)p.out + (oc0 >> 5) * p.out_gstride + (g.pix - (cbase & 31)) + (oc0 & 31);
+    f16x4 r2[(R1 && R2) ? 8 : 1][2];
+    if constexpr (R1 && R2) {
+        const f16* r2b = p.res2 + (cbase >> 5) * p.res2_gstride + g.pix;
+#pragma unroll
+        for (int m = 0; m < 8; ++m) {
+            if (!g.ok[m]) continue;
+#pragma unroll
+            for (int t = 0; t < 2; ++t) r2[m][t] = *(const f16x4*)(r2b + (m >> 1) * g.rowstep + (m & 1) * (16 * 32) + 4 * t);
+        }
+    }
+    // the prefetched residual (in flight since the top of the chunk) and the loads above: everything has landed before the first value is used.  One wait in front of
+    // the per-tile branches and in EVERY variant (free where nothing is in flight): no path, taken or not, reaches the next tile's prefetch with a load into rpre
+    // still counted as pending, which would make the compiler wait in front of the prefetch instead.
+    __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0) (expcnt / lgkmcnt untouched)
+#pragma unroll
+    for (int m = 0; m < 8; ++m) {
+        if (!g.ok[m]) continue;
+        f16* op = ob + (m >> 1) * g.rowstep + (m & 1) * (16 * 32);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            f16x4 h;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float f = acc[t][m][j];
+                if (ACT == 1) f = __builtin_amdgcn_fmed3f(f, 0.2f * f, ACT_TOP);
+                else if (ACT == 2) f = __builtin_amdgcn_fmed3f(f, 0.f, ACT_TOP);
+                if (SC1) { f = f * p.s1; FP32_VALUE(f); }
+                if (R1) f = __builtin_fmaf(f, p.s1, (float)rpre[m][t][j]);
+                if (R2) f = __builtin_fmaf(f, p.s2, (float)(PRE == 2 ? rpre[m][t][j] : r2[(R1 && R2) ? m : 0][t][j]));
+                FP32_VALUE(f);
+                h[j] = (f16)f;
+            }
+            *(f16x4*)(op + 4 * t) = h;
         }
     }
 }

@@ -9,10 +9,12 @@ constexpr int LVALID = TW + 2;
 // slots (a panel each) -- NSI 2: two stages [tile | panel]; NSI 3: three tiles, then two panels -- and behind them the tail of the ONE mode that has one.
 template <int RPW, int NT, int NSI, int NCW, int TMF>
 struct PcLayout {
-    static constexpr int TH = NCW * RPW;                                       // tile rows
+    static constexpr bool GRID2 = (TMF & PC_GRID2) != 0;                       // 2 x 4 consumer grid: NCW / 2 row groups, two NT-tile halves of the panel's rows
+    static constexpr int TH = (GRID2 ? NCW / 2 : NCW) * RPW;                   // tile rows
+    static constexpr int WROWS = (GRID2 ? 2 : 1) * NT * 16;                    // output channels (panel rows per tap) of a channel group
     static constexpr int IN_BYTES = (((TH + 2) * LWP + 15) / 16) * 1024;       // halo tile: whole 1 KB LDS-DMA pieces of 16 pixels
     static constexpr int NTAP = (TMF & PC_UP4) ? 4 : __builtin_popcount(TMF & TAPS_3X3);   // taps in the panel, in (r, s) order (UP4: a phase's 2 x 2 block)
-    static constexpr int W_BYTES = NTAP * NT * 16 * 64;
+    static constexpr int W_BYTES = NTAP * WROWS * 64;
     static constexpr int STAGE = IN_BYTES + W_BYTES;
     static constexpr int TAIL = NSI * IN_BYTES + 2 * W_BYTES;                  // (NSI 2: 2 * STAGE)
     static constexpr int FUSE_BYTES = (TMF & PC_FUSE) ? 4096 : 0;              // the last conv's panel

@@ -10,7 +10,7 @@
 #ifdef INNFER_PRIO
         __builtin_amdgcn_s_setprio(INNFER_PRIO);
 #else
-        if constexpr (NT <= 2) __builtin_amdgcn_s_setprio(3);
+        if constexpr (NT <= 2 && !GRID2) __builtin_amdgcn_s_setprio(3);       // (GRID2 is a 64-output kernel: WROWS 64)
 #endif
 #endif
         const int lw = wave - NCW;

@@ -1,7 +1,25 @@
 // conv3x3_pc: what the consumer waves do after a tile's last chunk -- the epilogue of the instantiation (split / canvas / RLDS / fused last conv / statistics / slab / planar).
 // A fragment of the BODY of conv3x3_pc (csrc/conv3x3.hip), included there textually (round 5, VERDICT r4 item 7: the kernel body was 940 lines; no functional
 // change -- the device assembly of the translation unit is identical).  It uses the kernel's locals and compile-time flags; not a stand-alone file.
-            if constexpr (OUTMODE == OUT_SLAB && SPLIT) {
+#ifdef INNFER_GRID2_LATE
+            // A/B build: the grid alone -- the residual loaded here, at the top of the epilogue, as the 8 x 1 form does
+            if constexpr (GRID2 && RLDS) { if (p.res2) residual_prefetch_grid2(p, p.res2, p.res2_gstride, rpre, n, ty0, tx0, cwr, li, cbase); }
+            else if constexpr (GRID2) { if (p.res1) residual_prefetch_grid2(p, p.res1, p.res1_gstride, rpre, n, ty0, tx0, cwr, li, cbase); }
+#endif
+            if constexpr (GRID2 && RLDS) {           // res1 is inside the accumulators (x / s1); res2, where there is one, was prefetched
+                if (p.res2) epilogue_slab_grid2<0, false, true, true, 2>(p, acc, rpre, n, ty0, tx0, cwr, li, cbase);
+                else epilogue_slab_grid2<0, false, false, true, 0>(p, acc, rpre, n, ty0, tx0, cwr, li, cbase);
+            } else if constexpr (GRID2) {            // res1 was prefetched; a second memory residual is loaded in the epilogue
+#define EPI(A, B, C) epilogue_slab_grid2<A, B, C, false, (B) ? 1 : 0>(p, acc, rpre, n, ty0, tx0, cwr, li, cbase)
+            if (!p.res1) {
+                if (p.act == 1) EPI(1, false, false); else if (p.act == 2) EPI(2, false, false); else EPI(0, false, false);
+            } else if (!p.res2) {
+                if (p.act == 1) EPI(1, true, false); else if (p.act == 2) EPI(2, true, false); else EPI(0, true, false);
+            } else {
+                if (p.act == 1) EPI(1, true, true); else if (p.act == 2) EPI(2, true, true); else EPI(0, true, true);
+            }
+#undef EPI
+            } else if constexpr (OUTMODE == OUT_SLAB && SPLIT) {
 #define EPI(A, B, C) epilogue_slab_split<RPW, NT, A, B, C, CV>(p, acc, n, ty0, tx0, cw, li, cbase)
             if (!p.res1) {
                 if (p.act == 1) EPI(1, false, false); else if (p.act == 2) EPI(2, false, false); else EPI(0, false, false);

@@ -149,3 +149,18 @@ __device__ __forceinline__ void residual_from_lds_plane(f32x4 (&acc)[4][MT], con
             for (int j = 0; j < 4; ++j) acc[2 * HALF + tt][m][j] = __builtin_fmaf((float)x[tt * 4 + j], rs1, acc[2 * HALF + tt][m][j]);
     }
 }
+
+// The same for the 2 x 4 consumer grid (GRID2): the wave's two tiles ARE one plane -- the staged group of the wave's own half holds the lane's 8 residual channels
+// (the additions of residual_from_lds_plane<MT, half> on tiles 2 half, 2 half + 1, in the same order)
+// roffs: the lane's offset of pixel tile 0 for the parity of its LDS row (row group * 4 + 1 + m / 2: parity (m / 2 + 1) & 1), the other tiles at immediates
+template <int MT>
+__device__ __forceinline__ void residual_from_lds_grid2(f32x4 (&acc)[2][MT], const char* st, const int* roffs, float rs1) {
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+        const f16x8 x = *(const f16x8*)(st + roffs[((m >> 1) + 1) & 1] + ((m >> 1) * LWP + (m & 1) * 16) * 64);
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[tt][m][j] = __builtin_fmaf((float)x[tt * 4 + j], rs1, acc[tt][m][j]);
+    }
+}

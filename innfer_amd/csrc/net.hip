@@ -139,6 +139,7 @@ struct innfer_net {
 #define INNFER_PS_PC_DEFAULT 1
 #endif
     int ps_pc = INNFER_PS_PC_DEFAULT;   // PixelShuffle(2) stages on the producer / consumer kernel (phase-major panels); 0 (A/B builds): the two-workgroup kernel of rounds 1-4
+    int consumer_grid = 1;       // the 64-output 3x3 slab convs of the RRDBNet trunk on the 2 x 4 consumer grid (innfer_net_set_consumer_grid; conv3x3_pc GRID2); 0: the 8 x 1 form
     int res_lds = 1;             // the dense block's x5 * 0.2 + x with x taken from the conv's own staged LDS tiles (innfer_net_set_residual_lds; conv3x3_pc RLDS): 1 = where the RRDB's residual follows, 2 = every block
     bool plus = false;           // ESRGAN+ residual paths (RRDBNet_arch.py:155-160)
     int unshuffle = 1;           // innfer_rrdbnet_create_ex2: pixel_unshuffle(r) in front of the first conv (BasicSR RRDBNet scale 2 / 1), folded into that conv (conv_first_unshuffle.hip);
@@ -489,6 +490,13 @@ extern "C" int innfer_net_set_residual_lds(innfer_net_t net, int on) {
     if (!net) return set_error(INNFER_ERR_INVALID, "set_residual_lds: null network");
     if (on < 0 || on > 2) return set_error(INNFER_ERR_INVALID, "set_residual_lds: 0 (epilogue loads), 1 (the RRDB-end layers: default) or 2 (every dense block)");
     net->res_lds = on;
+    return INNFER_OK;
+}
+
+extern "C" int innfer_net_set_consumer_grid(innfer_net_t net, int mode) {
+    if (!net) return set_error(INNFER_ERR_INVALID, "set_consumer_grid: null network");
+    if (mode < 0 || mode > 1) return set_error(INNFER_ERR_INVALID, "set_consumer_grid: 1 (2 x 4 consumer grid with the residual prefetch: default) or 0 (the 8 x 1 form)");
+    net->consumer_grid = mode;
     return INNFER_OK;
 }
 
@@ -909,7 +917,9 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
             if (!c.first && !c.d_w32) return set_error(INNFER_ERR_INVALID, "forward: the fp32-accurate panels of '%s' are missing: call innfer_net_set_precision(net, 1) after the last innfer_net_set_conv", c.key.c_str());
     }
     auto mk = [&](const ConvSlot& cs, const f16* in, long in_g, void* out, long out_g, int N_, int H_, int W_, int act) {
-        return mk_launch(cs, in, in_g, out, out_g, N_, H_, W_, act, LO);
+        ConvLaunch L = mk_launch(cs, in, in_g, out, out_g, N_, H_, W_, act, LO);
+        L.grid2 = net->kind == 0 ? net->consumer_grid : 0;          // (taken only by the launches that have the form: conv_launch)
+        return L;
     };
     f16* fea = (f16*)(ws + cv.fea);
     f16* slab[3] = {(f16*)(ws + cv.slab[0]), (f16*)(ws + cv.slab[1]), (f16*)(ws + cv.slab[2])};
@@ -1288,8 +1298,12 @@ extern "C" int innfer_norm_stats(const void* d_src, int slab, int64_t gs, int cp
                 : norm::launch_stats((const float*)d_src, cpad, (long)HW, eps, d_gamma, d_beta, d_alpha, d_shift, C, N, d_part, (hipStream_t)stream);
 }
 
-static int conv3x3_f16_impl(const innfer_conv_args* a, const float* d_slope, void* stream);
+static int conv3x3_f16_impl(const innfer_conv_args* a, const float* d_slope, void* stream, int consumer_grid = 1);
 extern "C" int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream) { return conv3x3_f16_impl(a, nullptr, stream); }
+extern "C" int innfer_conv3x3_f16_grid(const innfer_conv_args* a, int consumer_grid, void* stream) {
+    if (consumer_grid < 0 || consumer_grid > 1) return set_error(INNFER_ERR_INVALID, "conv3x3: consumer_grid is 1 (the 2 x 4 consumer grid where the launch has that form) or 0 (the 8 x 1 form)");
+    return conv3x3_f16_impl(a, nullptr, stream, consumer_grid);
+}
 // The same launch with act = 8: f >= 0 ? f : d_slope[c] * f, d_slope padded like d_bias (for tests; the SRVGGNetCompact engine's layers)
 extern "C" int innfer_conv3x3_f16_slope(const innfer_conv_args* a, const float* d_slope, void* stream) { return conv3x3_f16_impl(a, d_slope, stream); }
 
@@ -1306,7 +1320,7 @@ extern "C" int innfer_shuffle_add(const void* d_slab, int64_t group_stride, cons
     return shuffle_add_launch(T, (hipStream_t)stream);
 }
 
-static int conv3x3_f16_impl(const innfer_conv_args* a, const float* d_slope, void* stream) {
+static int conv3x3_f16_impl(const innfer_conv_args* a, const float* d_slope, void* stream, int consumer_grid) {
     if (!a || !a->d_in || !a->d_packed || !a->d_bias || !a->d_out) return set_error(INNFER_ERR_INVALID, "conv3x3: null argument");
     // (121) the fields that reach the remaining forms of the kernel: mapped onto ConvLaunch below, conv_launch decides what is built
     const bool forms121 = a->conv1x1 || a->prefix_lrelu || a->d_gate_packed || a->d_gate_bias || a->in_relu || a->conv7x7 || a->out_planar || a->out_denorm || a->out_round16 ||
@@ -1371,6 +1385,7 @@ static int conv3x3_f16_impl(const innfer_conv_args* a, const float* d_slope, voi
     L.out_mode = a->pixel_shuffle2 ? OUT_SHUFFLE2 : OUT_SLAB; L.reflect = a->reflect_pad; L.dilation = a->dilation; L.dilation_groups = a->dilation_groups;
     L.res1_lds = a->res1_from_input ? 2 : 0;                 // (the single-conv call: wherever the shape qualifies, one residual or two)
     L.slope = d_slope;
+    L.grid2 = consumer_grid;
     L.rowp = a->plane_rows ? 1 : 0;
     if (a->pixel_shuffle2 && a->plane_rows == 2) L.rowp = 2;          // phase-major panels + bias from innfer_pack_conv3x3_shuffle2: the producer / consumer kernel's store
     else if (a->pixel_shuffle2 && a->plane_rows) return set_error(INNFER_ERR_INVALID, "conv3x3: pixel_shuffle2 takes plane_rows 0 (innfer_pack_conv3x3 panels) or 2 (innfer_pack_conv3x3_shuffle2 panels)");

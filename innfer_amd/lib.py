@@ -124,6 +124,7 @@ SIGNATURES = {
     "innfer_net_set_fused_tail": (C.c_int, [C.c_void_p, C.c_int]),
     "innfer_net_set_hr_chain": (C.c_int, [C.c_void_p, C.c_int]),
     "innfer_net_set_residual_lds": (C.c_int, [C.c_void_p, C.c_int]),
+    "innfer_net_set_consumer_grid": (C.c_int, [C.c_void_p, C.c_int]),
     "innfer_net_set_upconv_phases": (C.c_int, [C.c_void_p, C.c_int]),
     "innfer_net_set_final_act": (C.c_int, [C.c_void_p, C.c_int]),
     "innfer_net_flops": (C.c_double, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -189,6 +190,7 @@ SIGNATURES = {
     "innfer_pack_convt2x_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "innfer_conv3x3_f16": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p]),
     "innfer_conv3x3_f16_slope": (C.c_int, [C.POINTER(ConvArgs), C.c_void_p, C.c_void_p]),
+    "innfer_conv3x3_f16_grid": (C.c_int, [C.POINTER(ConvArgs), C.c_int, C.c_void_p]),
     "innfer_shuffle_add": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 5 + [C.c_void_p]),
     "innfer_compact_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 5),
     "innfer_net_set_conv_slope": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
