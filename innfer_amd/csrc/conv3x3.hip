@@ -27,9 +27,14 @@
 //                                epilogue: S9 (a 7x7 conv as nine displaced 3x3 convs) and POLY (a dilated conv as
 //                                ordinary convs on the polyphase components of the image);
 //   conv3x3_mfma<RPW,NT,OUT>     two independent 4-wave workgroups per CU, tile = 4*RPW rows x 32 px, one LDS
-//                                stage each (round 1's kernel; kept as the FALLBACK some launches still reach): PixelShuffle(2) stores whose output group is
-//                                2 GiB or more (64-bit indices: SRResNet chop batches beyond 209 tiles, net.hip), PixelShuffle on plain panels (ABI plane_rows 0), planar
-//                                outputs with residuals or 32 / 64 planar channels, and every slab conv of the diagnostic builds' INNFER_PC=0.
+//                                stage each (round 1's kernel; kept as the FALLBACK of the launches conv3x3_pc has no form for).  Five instantiations, each
+//                                reached by the last switch of conv_launch only (tests/test_host_cpu.py holds the shipped library to exactly this list):
+//                                  <4,1,OUT_SLAB>      slab output of K = 16 channels (conv_nt_for(K) 1: K < 32);
+//                                  <2,4,OUT_NCHW>      planar output of K = 64, 128 .. channels (conv_nt_for 4), with or without residuals;
+//                                  <4,2,OUT_NCHW>      planar output of K >= 32 channels in 32-channel groups (conv_nt_for 2: 32 .. 63, 96 ..) WITH a residual;
+//                                  <4,1,OUT_NCHW>      planar output of K < 32 channels WITH a residual;
+//                                  <2,4,OUT_SHUFFLE2>  PixelShuffle(2) store from lane-contiguous panels (rowp != 2): output groups of 2 GiB or more (64-bit indices:
+//                                                      SRResNet chop batches beyond 209 tiles, net.hip) and the ABI's plane_rows 0.
 // Per 32-channel chunk the halo tile ((rows+2) x 34 px x 64 B) and the weight panel (9 x 16*NT x 64 B) are
 // staged with LDS-DMA (buffer_load_dwordx4 ... lds; out-of-image lanes are zero-filled by the buffer range
 // check = the conv's zero padding).  LDS rows are 36 px (2304 B = 9 x 256 B: every row starts on bank 0);
@@ -60,18 +65,11 @@
 
 namespace innfer {
 
-// Diagnostic build only (-DINNFER_STAMPS): s_memtime stamps of one wave per workgroup, written to a
+// Diagnostic build only (-DINNFER_STAMPS): clock sums of conv3x3_pc's consumer wave 0 per workgroup (PCT / PCACC below), written to a
 // buffer nothing else reads.  Never enabled in the shipped library; never quote its run time.
 #ifdef INNFER_STAMPS
 #define NSTAMP 16
 __device__ unsigned long long g_stamps[8192 * NSTAMP];
-#define STAMP(i)                                                                              \
-    do {                                                                                      \
-        if (blockIdx.x < 8192 && threadIdx.x == 0)                                            \
-            g_stamps[blockIdx.x * NSTAMP + (i)] = (unsigned long long)clock64();              \
-    } while (0)
-#else
-#define STAMP(i) do { } while (0)
 #endif
 
 namespace {
@@ -104,7 +102,7 @@ template <int TM_, int RPW_, int NSEG_> struct TapWalkOf { static constexpr TapW
 #include "conv3x3_epilogue_slab.h"
 
 template <int RPW, int NT, int OUTMODE>
-__global__ __launch_bounds__(256, (RPW == 3 && NT == 2) ? 3 : 2) void conv3x3_mfma(const KP p) {
+__global__ __launch_bounds__(256, 2) void conv3x3_mfma(const KP p) {
     constexpr int TH = 4 * RPW;
     constexpr int LH = TH + 2;
     constexpr int NPX = LH * LWP;
@@ -124,13 +122,8 @@ __global__ __launch_bounds__(256, (RPW == 3 && NT == 2) ? 3 : 2) void conv3x3_mf
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    STAMP(0);
-    // workgroup -> tiles: xcd_run (common.h) written out -- through the helper this kernel's code changes beyond its prologue
-    const int bid = blockIdx.x, xcd = bid & 7;
-    const int run_q = p.total >> 3, run_r = p.total & 7;
-    const int run_start = xcd < run_r ? xcd * (run_q + 1) : run_r * (run_q + 1) + (xcd - run_r) * run_q;
-    const int run_len = run_q + (xcd < run_r ? 1 : 0);
-    const int slots = ((int)gridDim.x + 7 - xcd) >> 3;
+    const XcdRun run = xcd_run(p.total);
+    const int run_start = run.start, run_len = run.len, slots = run.slots;
     const int per_img = p.tiles_x * p.tiles_y;
     const int li = lane & 15, lg = lane >> 4;
     constexpr int OOB = (int)0x80000000;
@@ -169,57 +162,27 @@ __global__ __launch_bounds__(256, (RPW == 3 && NT == 2) ? 3 : 2) void conv3x3_mf
         }
     const char* abase = lds_w + li * 64 + ((lg ^ (((li >> 2) & 1) << 1)) << 4);
     const int wvoff = lane * 16;
-    // L2 prefetch plan (p.pf): LDS-DMA streams several times faster from L2 than from HBM and a
-    // workgroup keeps only one chunk of LDS-DMA in flight, so while chunk c is landing / being computed
-    // every thread touches one dword in (up to) two 128-B lines of the NEXT stage's halo tile -- chunk
-    // c+1 of this tile, or chunk 0 of the workgroup's next tile: results discarded (2 KiB LDS scratch),
-    // nothing waits for them until a whole compute phase later.
-    constexpr int LPR = (LVALID * 64 + 127) / 128 + 1;        // 128-B lines per tile row (18)
-    constexpr int NLINES = LH * LPR;
-    int pfl[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int id = tid + 256 * i;
-        const int r = id / LPR, l = id - r * LPR;
-        pfl[i] = (p.pf && !p.up && id < NLINES) ? r * p.Ws * 64 + (l - 1) * 128 : OOB;   // relative to (row ty0-1, col tx0)
-    }
-    // 3-per-CU shape: no scratch (prefetch must stay off for it)
-    char* lds_pf = smem + IN_BYTES + W_BYTES + ((RPW == 3 && NT == 2) ? 0 : wave * 512);
     f32x4 bias_r[NT];
     int bias_kg = -1;
 
-    auto decode = [&](int jj, int& kg_, int& n_, int& ty0_, int& tx0_) {
-        // rev: consecutive layers walk the frame in opposite directions, so a layer starts on the region
-        // its predecessor touched last -- the part of the activations that is still in the 256 MiB
-        // Infinity Cache (a cyclic sweep of a larger working set would never hit).
-        const int lid = run_start + (p.rev ? run_len - 1 - jj : jj);
-        kg_ = lid % p.KG;
-        int tile = lid / p.KG;
-        n_ = tile / per_img;
-        tile -= n_ * per_img;
-        const int ty = tile / p.tiles_x;
-        ty0_ = p.y0 + ty * TH;
-        tx0_ = (tile - ty * p.tiles_x) * TW;
-    };
-    auto is_edge = [&](int ty0_, int tx0_) {
-        return ty0_ == 0 || ty0_ + TH + 1 > p.H || tx0_ == 0 || tx0_ + TW + 1 > p.W;
-    };
-
-    for (int j = bid >> 3; j < run_len; j += slots) {
-    STAMP(0);
-#ifdef INNFER_STAMPS
-    if (blockIdx.x < 8192 && threadIdx.x == 0) g_stamps[blockIdx.x * NSTAMP + 14] = (unsigned long long)wall_clock64();
-#endif
-    int kg, n, ty0, tx0;
-    decode(j, kg, n, ty0, tx0);
-    const bool edge = is_edge(ty0, tx0);
+    for (int j = run.j0; j < run_len; j += slots) {
+    // rev: consecutive layers walk the frame in opposite directions, so a layer starts on the region
+    // its predecessor touched last -- the part of the activations that is still in the 256 MiB
+    // Infinity Cache (a cyclic sweep of a larger working set would never hit).
+    const int lid = run_start + (p.rev ? run_len - 1 - j : j);
+    const int kg = lid % p.KG;
+    int tile = lid / p.KG;
+    const int n = tile / per_img;
+    tile -= n * per_img;
+    const int ty = tile / p.tiles_x;
+    const int ty0 = p.y0 + ty * TH;
+    const int tx0 = (tile - ty * p.tiles_x) * TW;
+    const bool edge = ty0 == 0 || ty0 + TH + 1 > p.H || tx0 == 0 || tx0 + TW + 1 > p.W;
     const char* img = (const char*)(p.in + (long)n * p.in_img_stride);
     const char* in_tile = img + ((long)((ty0 - 1) >> p.up) * p.Ws + ((tx0 >> p.up) - 1)) * 64;
-    const char* pf_tile = img + ((long)(ty0 - 1) * p.Ws + tx0) * 64;         // prefetch only runs with up == 0
-    int voff[KQ], pfo[2];
+    int voff[KQ];
 #pragma unroll
     for (int k = 0; k < KQ; ++k) voff[k] = loff[k];
-    pfo[0] = pfl[0]; pfo[1] = pfl[1];
     if (edge) {
 #pragma unroll
         for (int k = 0; k < KQ; ++k) {                   // border tiles only: recomputed, not kept in registers
@@ -228,21 +191,6 @@ __global__ __launch_bounds__(256, (RPW == 3 && NT == 2) ? 3 : 2) void conv3x3_mf
             const int Y = ty0 - 1 + ly, X = tx0 - 1 + lx;
             if (Y < 0 || Y >= p.H || X < 0 || X >= p.W) voff[k] = OOB;
         }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int id = tid + 256 * i;
-            const int r = id / LPR, l = id - r * LPR;
-            const int Y = ty0 - 1 + r, lb = tx0 * 64 + (l - 1) * 128;
-            if (Y < 0 || Y >= p.H || lb < 0 || lb >= p.W * 64) pfo[i] = OOB;
-        }
-    }
-    // the workgroup's next tile, for the cross-tile prefetch (border tiles are not prefetched)
-    const char* pf_next = nullptr;
-    if (p.pf >= 2 && !p.up && j + slots < run_len) {
-        int kg2, n2, ty2, tx2;
-        decode(j + slots, kg2, n2, ty2, tx2);
-        if (!is_edge(ty2, tx2))
-            pf_next = (const char*)(p.in + (long)n2 * p.in_img_stride) + ((long)(ty2 - 1) * p.Ws + tx2) * 64;
     }
 
     // ---- accumulators start at the bias ----------------------------------------
@@ -258,7 +206,6 @@ __global__ __launch_bounds__(256, (RPW == 3 && NT == 2) ? 3 : 2) void conv3x3_mf
 #pragma unroll
         for (int m = 0; m < MT; ++m) acc[t][m] = bias_r[t];
     const char* w_tile = (const char*)p.wpk + (long)kg * p.nchunks * W_BYTES;
-    STAMP(1);
 
     for (int c = 0; c < p.nchunks; ++c) {
         // stage chunk c: halo tile + weight panel, straight into LDS
@@ -283,24 +230,11 @@ __global__ __launch_bounds__(256, (RPW == 3 && NT == 2) ? 3 : 2) void conv3x3_mf
                         rw, (__attribute__((address_space(3))) void*)(lds_w + j * 1024), 16, wvoff, j * 1024, 0, 0);
             }
         }
-        asm volatile("" ::: "memory");                      // keep the prefetch loads BEHIND the DMA pieces
-        const bool last = c + 1 == p.nchunks;
-        const bool do_pf = p.pf && !p.up && (!last || pf_next != nullptr);
-        if (do_pf) {
-            const __amdgpu_buffer_rsrc_t rp = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)(last ? pf_next : pf_tile + (c + 1) * p.in_gbytes), 0, 0x7fffffff, 0x00020000);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rp, (__attribute__((address_space(3))) void*)lds_pf, 4, last ? pfl[0] : pfo[0], 0, 0, 0);
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rp, (__attribute__((address_space(3))) void*)(lds_pf + 256), 4, last ? pfl[1] : pfo[1], 0, 0, 0);
-            asm volatile("s_waitcnt vmcnt(2)" ::: "memory");  // the DMA pieces, not the two prefetch loads
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
-        (void)voff; (void)wvoff; (void)w_tile; (void)in_tile; (void)pf_tile; (void)pf_next; (void)KW; (void)pfo; (void)lds_pf;
+        (void)voff; (void)wvoff; (void)w_tile; (void)in_tile; (void)KW;
 #endif
-        if (c < 3) STAMP(2 + 3 * c);
-        asm volatile("s_barrier" ::: "memory");             // raw: __syncthreads() would drain vmcnt to 0
-        if (c < 3) STAMP(3 + 3 * c);
+        asm volatile("s_barrier" ::: "memory");
 
 #ifdef INNFER_ABLATE
         if (!(p.abl & 8))
@@ -332,9 +266,7 @@ __global__ __launch_bounds__(256, (RPW == 3 && NT == 2) ? 3 : 2) void conv3x3_mf
             }
         }
         asm volatile("s_barrier" ::: "memory");
-        if (c < 3) STAMP(4 + 3 * c);
     }
-    STAMP(11);
 
     // ---- epilogue: act -> residuals -> store -----------------------------------
     if constexpr (OUTMODE == OUT_SLAB) {
@@ -417,12 +349,6 @@ __global__ __launch_bounds__(256, (RPW == 3 && NT == 2) ? 3 : 2) void conv3x3_mf
             }
         }
     }
-#ifdef INNFER_STAMPS
-    STAMP(13);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    STAMP(12);
-    if (blockIdx.x < 8192 && threadIdx.x == 0) g_stamps[blockIdx.x * NSTAMP + 15] = (unsigned long long)wall_clock64();   // 100 MHz
-#endif
     }   // tiles of this workgroup
 }
 
@@ -477,12 +403,10 @@ __device__ __forceinline__ f16x8 relu_frag(f16x8 b) {
 // flight.  3 (16-row tiles, 32-output layers): a ring of three input slots and two weight slots; during step g the loaders issue the weight
 // panel of chunk g + 1 and the halo tile of chunk g + 2 and wait (counted vmcnt) only for what was issued a whole step earlier, so the
 // request stream into HBM never pauses.
-// NCW: consumer waves (8: two per SIMD; 4: one per SIMD with twice the rows each -- the same tile with 0.25 instead of 0.42 ds_read_b128 per MFMA,
-// 256 registers per wave).
 // TMF: bits 0..8 the tap mask of the 3x3 lattice (bit r * 3 + s; the weight panel holds the set taps in that order) + mode flags: the TAPS_* / PC_* constants
 // of conv3x3_modes.h, where each has its value and its meaning.  Every flag is compile-time: the instantiations of the SR path (TAPS_3X3 without flags) contain
 // none of the other modes' code.
-template <int RPW, int NT, int NLW, int OUTMODE, bool S9 = false, bool POLY = false, int TMF = TAPS_3X3, bool CV = false, int NSI = 2, int NCW = 8>
+template <int RPW, int NT, int NLW, int OUTMODE, bool S9 = false, bool POLY = false, int TMF = TAPS_3X3, bool CV = false, int NSI = 2>
 __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     // TMF: tap mask (bits 0..8) + PC_S2 = the stride-2 gather loader: Conv2d(k 4, s 2, p 1) as the 2x2-tap conv of the space-to-depth input --
     // chunk c is (phase (pa, pb) = c / ncg, channel group c % ncg); cell (cy, cx) of phase (pa, pb) is source pixel (2cy + pa - 1, 2cx + pb - 1)
@@ -529,16 +453,16 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     // sees the same MFMAs in the same order (chunk, tap column, halo row, tap row) and the same epilogue arithmetic: same bits as the 8 x 1 form.  Loaders, barriers, LDS layout
     // and tile walk are those of <2, 4>.
     constexpr bool GRID2 = (TMF & PC_GRID2) != 0;
-    static_assert(!GRID2 || (RPW == 4 && NT == 2 && NCW == 8 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & ~(TAPS_3X3 | PC_RLDS | PC_ROWP | PC_GRID2)) == 0 && (TMF & PC_ROWP) && TM == TAPS_3X3 && !S9 && !POLY && !CV),
+    static_assert(!GRID2 || (RPW == 4 && NT == 2 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & ~(TAPS_3X3 | PC_RLDS | PC_ROWP | PC_GRID2)) == 0 && (TMF & PC_ROWP) && TM == TAPS_3X3 && !S9 && !POLY && !CV),
                   "2 x 4 consumer grid: the plain and the RLDS 64-output plane-order slab conv");
-    static_assert(!RLDS || (((RPW == 2 && NT == 4) || GRID2) && NCW == 8 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_RLDS) == TAPS_3X3 && !S9 && !POLY), "residual from LDS: the plain 64-channel instantiation (its canvas form, its 2 x 4 consumer grid)");
+    static_assert(!RLDS || (((RPW == 2 && NT == 4) || GRID2) && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_RLDS) == TAPS_3X3 && !S9 && !POLY), "residual from LDS: the plain 64-channel instantiation (its canvas form, its 2 x 4 consumer grid)");
     // + PC_SGATE: PAN's pixel attention behind an up-conv (PAN_arch.py:11-35: upconv -> PA: x * sigmoid(conv1x1(x)) -> LeakyReLU) inside the up-conv's
     // epilogue: a lane's accumulators are 8 consecutive channels of its pixel (NT = 2 row order), i.e. after the fp16 conversion -- the value the two-launch
     // schedule stored -- the B fragment of the 1x1 conv; two MFMAs per pixel tile against the 32 x 32 gate matrix held in registers, then v * sigmoid(g) goes
     // through the ordinary epilogue (its LeakyReLU, the store).  Same fp16 operands and the same MFMA as the two launches; the sigmoid is the fast form, so results
     // agree to the last fp16 rounding -- without the round trip of the 32-channel HR tensor (531 MB written and read again at 2160 x 3840).
     constexpr bool SGATE = (TMF & PC_SGATE) != 0;
-    static_assert(!SGATE || (RPW == 3 && NT == 2 && NCW == 8 && OUTMODE == OUT_SLAB && ((TMF & PC_BELOW_SGATE) == TAPS_3X3 || (TMF & PC_BELOW_SGATE) == (TAPS_3X3 | PC_SPLIT)) && !S9 && !POLY), "self gate: the 32-output slab kernel (its canvas form, its split-operand form)");
+    static_assert(!SGATE || (RPW == 3 && NT == 2 && OUTMODE == OUT_SLAB && ((TMF & PC_BELOW_SGATE) == TAPS_3X3 || (TMF & PC_BELOW_SGATE) == (TAPS_3X3 | PC_SPLIT)) && !S9 && !POLY), "self gate: the 32-output slab kernel (its canvas form, its split-operand form)");
     // + PC_BRELU: the pixel operand is max(x, 0) of the stored slab -- the UNet keeps ONE stored form of a skip tensor (LeakyReLU, the down conv's operand);
     // the up conv that reads the concatenation applies the ReLU as it takes a fragment from LDS (4 v_pk_max_f16 per fragment, i.e. per 2 .. 8 MFMAs).
     // max(lrelu(v), 0) == relu(v) bit for bit in fp16, so the results are those of the two-view form.
@@ -554,14 +478,14 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     constexpr bool UP4 = (TMF & PC_UP4) != 0;
     // + PC_ROWP: the plane row order of the 64-channel groups (see toff_slab): plain 3x3 slab convs (canvas, RLDS, FUSE forms included) and the one-pass up-conv
     constexpr bool ROWP = (TMF & PC_ROWP) != 0;
-    static_assert(!ROWP || (((RPW == 2 && NT == 4) || GRID2) && NCW == 8 && OUTMODE == OUT_SLAB && TM == TAPS_3X3 && (TMF & ~(TAPS_3X3 | PC_FUSE | PC_RLDS | PC_UP4 | PC_ROWP | PC_PSH | PC_PRELU | PC_GRID2)) == 0 && !S9 && !POLY), "plane row order: the 64-channel slab kernels");
+    static_assert(!ROWP || (((RPW == 2 && NT == 4) || GRID2) && OUTMODE == OUT_SLAB && TM == TAPS_3X3 && (TMF & ~(TAPS_3X3 | PC_FUSE | PC_RLDS | PC_UP4 | PC_ROWP | PC_PSH | PC_PRELU | PC_GRID2)) == 0 && !S9 && !POLY), "plane row order: the 64-channel slab kernels");
     // + PC_PSH: nn.PixelShuffle(2) as the store of a conv nf -> 4 nf (pixelshuffle_block, block.py:333-346; SRResNet's up stages, RRDBNet(upsample_mode=
     // 'pixelshuffle')) on THIS kernel -- until round 4 those launches ran on the two-workgroup kernel of round 1 (0.30 of the MFMA peak, a third of an SRResNet frame).
     // The panels are phase-major (conv_pack_shuffle2) in the plane row order, so a channel group is one output phase of 64 channels and the epilogue is the
     // transposed-conv phase store without the lattice shift (epilogue_slab PSH).  Same MFMAs in the same order per value as the old form: same bits.
     constexpr bool PSH = (TMF & PC_PSH) != 0;
     static_assert(!PSH || (ROWP && (TMF & ~(TAPS_3X3 | PC_ROWP | PC_PSH)) == 0 && NSI == 2 && !CV), "pixel-shuffle store: the plain 64-channel plane-order instantiation");
-    static_assert(!UP4 || (RPW == 2 && NT == 4 && NCW == 8 && NSI == 3 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_UP4) == TAPS_3X3 && !S9 && !POLY && !CV), "one-pass phases: the 64-channel slab kernel on three input slots");
+    static_assert(!UP4 || (RPW == 2 && NT == 4 && NSI == 3 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_UP4) == TAPS_3X3 && !S9 && !POLY && !CV), "one-pass phases: the 64-channel slab kernel on three input slots");
     constexpr bool FUSE = (TMF & PC_FUSE) != 0;
     // + PC_PRELU: ConvLaunch.act 8 -- f >= 0 ? f : slope[c] * f with a per-channel slope vector (nn.PReLU(num_parameters = K); constant vectors serve ReLU and
     // LeakyReLU(a)) as the slab epilogue of the plain nine-tap kernels: the chain of 64 -> 64 convs of BasicSR's SRVGGNetCompact, one launch per layer.  The slopes are
@@ -569,9 +493,9 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     // channel group of slopes (K = 16 NT) in 256 bytes of its own behind the two stages and reads its lane's values back at each tile's end -- same-wave LDS traffic,
     // in order, no barrier.  Instantiations of their own: the other kernels' code does not change.
     constexpr bool PRELU = (TMF & PC_PRELU) != 0;
-    static_assert(!PRELU || (OUTMODE == OUT_SLAB && (NT == 4 || NT == 2) && NCW == 8 && NSI == 2 && (TMF & ~(TAPS_3X3 | PC_ROWP | PC_PRELU)) == 0 && TM == TAPS_3X3 && !S9 && !POLY && !CV), "PReLU epilogue: the plain 64- / 32-output slab kernels");
-    static_assert(!FUSE || (RPW == 2 && (NT == 4 || (NT == 2 && !ROWP)) && NCW == 8 && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_FUSE) == TAPS_3X3 && !S9 && !POLY && !CV), "the fused last conv: the plain 64-channel instantiation (and the 32-channel one on 16-row tiles)");
-    using L = PcLayout<RPW, NT, NSI, NCW, TMF>;                   // the LDS layout, shared with launch_pc
+    static_assert(!PRELU || (OUTMODE == OUT_SLAB && (NT == 4 || NT == 2) && NSI == 2 && (TMF & ~(TAPS_3X3 | PC_ROWP | PC_PRELU)) == 0 && TM == TAPS_3X3 && !S9 && !POLY && !CV), "PReLU epilogue: the plain 64- / 32-output slab kernels");
+    static_assert(!FUSE || (RPW == 2 && (NT == 4 || (NT == 2 && !ROWP)) && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_FUSE) == TAPS_3X3 && !S9 && !POLY && !CV), "the fused last conv: the plain 64-channel instantiation (and the 32-channel one on 16-row tiles)");
+    using L = PcLayout<RPW, NT, NSI, TMF>;                  // the LDS layout, shared with launch_pc
     constexpr int TH = L::TH;
     constexpr int LH = TH + 2;
     constexpr int NPX = LH * LWP;
@@ -947,7 +871,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
 #endif
 }
 
-template <int RPW, int NT, int NLW, int OUTMODE = OUT_SLAB, bool S9 = false, bool POLY = false, int TM = TAPS_3X3, bool CV = false, int NSI = 2, int NCW = 8>
+template <int RPW, int NT, int NLW, int OUTMODE = OUT_SLAB, bool S9 = false, bool POLY = false, int TM = TAPS_3X3, bool CV = false, int NSI = 2>
 int launch_pc(const KP& kp, int N, hipStream_t s);
 
 // CU count of the current device (a process may drive several GPUs)
@@ -965,66 +889,63 @@ int num_cus() {
 template <int RPW, int NT, int OUTMODE>
 int launch_t(const KP& kp, int N, hipStream_t s) {
     constexpr int TH = 4 * RPW;
-    constexpr int LDS = (((TH + 2) * LWP + 15) / 16) * 1024 + 9 * NT * 16 * 64 + ((RPW == 3 && NT == 2) ? 0 : 2048);   // + prefetch scratch
+    constexpr int LDS = (((TH + 2) * LWP + 15) / 16) * 1024 + 9 * NT * 16 * 64;      // halo tile + weight panel
     static std::atomic<unsigned long long> attr_done{0};
     INNFER_HIP(ensure_lds_attr(conv3x3_mfma<RPW, NT, OUTMODE>, LDS, attr_done));
     KP k = kp;
     k.tiles_x = (k.W + TW - 1) / TW;
     k.tiles_y = (k.y1 - k.y0 + TH - 1) / TH;
-    {
-        const int pf = INNFER_KNOB("INNFER_PREFETCH", 0);   // 1: next chunk, 2: + next tile
-        k.pf = (RPW == 3 && NT == 2) ? 0 : pf;
 #ifdef INNFER_ABLATE
-        k.abl = getenv("INNFER_ABL") ? atoi(getenv("INNFER_ABL")) : 0;     // read per launch: scripts/ablate.py changes it between runs
+    k.abl = getenv("INNFER_ABL") ? atoi(getenv("INNFER_ABL")) : 0;     // read per launch: scripts/ablate.py changes it between runs
 #endif
-    }
     const long total = (long)N * k.tiles_x * k.tiles_y * k.KG;
     if (total <= 0) return INNFER_OK;
     if (total > 0x7fffffffL) return set_error(INNFER_ERR_INVALID, "conv grid too large");
     k.total = (int)total;
-    const int persist = INNFER_KNOB("INNFER_PERSIST", 2);   // workgroups per CU, 0 = one per tile
-    const long slots = (long)((persist == 2 && RPW == 3 && NT == 2) ? 3 : persist) * num_cus();   // = workgroups resident per CU
-    const long grid = (persist > 0 && total > slots) ? slots : total;
+    const long slots = 2L * num_cus();                      // persistent: the two workgroups resident per CU
+    const long grid = total > slots ? slots : total;
     hipLaunchKernelGGL((conv3x3_mfma<RPW, NT, OUTMODE>), dim3((unsigned)grid), dim3(256), LDS, s, k);
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
 }
 
-// Image canvas for a batch (conv3x3_pc<.., CV>): the grid (columns x rows of cells) with the fewest tiles, or 0 columns when the per-image lattice
-// is at least as good (one image, images that already are whole tiles) or the form does not apply.
+// Image canvas for a batch (conv3x3_pc<.., CV>) on TH-row tiles: the grid (columns x rows of cells) with the fewest tiles, or 0 columns when the per-image
+// lattice is at least as good (one image, images that already are whole tiles) or the form does not apply.  The ONE place that decides whether a launch is a
+// canvas: launch_pc asks for the form it is about to launch, conv_launch for the 8 x 1 form a 2 x 4 consumer grid would replace.
 template <int TH>
-int canvas_grid(const KP& k, int N, int* gy, long* tiles) {
+int canvas_grid(const KP& k, int N, int* gy) {
     const long plain = (long)N * ((k.W + TW - 1) / TW) * ((k.H + TH - 1) / TH);
-    *tiles = plain; *gy = 0;
-    if (N < 2 || k.up || k.reflect || (k.act >= 3 && k.act != 7) || k.y0 != 0 || k.y1 != k.H || k.H < TH + 2 || k.W < LVALID || k.nrate || k.dil > 1 || k.stats_part ||
-        (long)N * k.H * k.W * 64 >= 0x7fffffffL)
+    long tiles = plain;
+    *gy = 0;
+    if (!INNFER_KNOB("INNFER_CANVAS", 1) || N < 2 || k.up || k.reflect || (k.act >= 3 && k.act != 7) || k.y0 != 0 || k.y1 != k.H || k.H < TH + 2 || k.W < LVALID || k.nrate || k.dil > 1 ||
+        k.stats_part || (long)N * k.H * k.W * 64 >= 0x7fffffffL)
         return 0;
     int best = 0;
     for (int gx = 1; gx <= N; ++gx) {
         const int g_y = (N + gx - 1) / gx;
         const long t = (long)((gx * (k.W + 1) + TW - 1) / TW) * ((g_y * (k.H + 1) + TH - 1) / TH);
-        if (t < *tiles) { *tiles = t; best = gx; *gy = g_y; }
+        if (t < tiles) { tiles = t; best = gx; *gy = g_y; }
     }
-    return *tiles * 100 <= plain * 98 ? best : 0;         // worth it from 2 % fewer tiles
+    return tiles * 100 <= plain * 98 ? best : 0;         // worth it from 2 % fewer tiles
 }
 
-template <int RPW, int NT, int NLW, int OUTMODE, bool S9, bool POLY, int TM, bool CV, int NSI, int NCW>
+template <int RPW, int NT, int NLW, int OUTMODE, bool S9, bool POLY, int TM, bool CV, int NSI>
 int launch_pc(const KP& kp, int N, hipStream_t s) {
-    constexpr int TH = PcLayout<RPW, NT, NSI, NCW, TM>::TH;
-    constexpr int LDS = PcLayout<RPW, NT, NSI, NCW, TM>::LDS_BYTES;
+    constexpr int TH = PcLayout<RPW, NT, NSI, TM>::TH;
+    constexpr int LDS = PcLayout<RPW, NT, NSI, TM>::LDS_BYTES;
     static_assert(LDS <= 160 * 1024, "the stages must fit the CU's LDS");
     static_assert(NSI == 2 || (NSI == 3 && !S9 && !POLY), "the three-slot input ring exists for the plain and the canvas loader");
     if constexpr (OUTMODE == OUT_SLAB && !S9 && !POLY && (TM & ~(PC_SPLIT | PC_RLDS | PC_SGATE | PC_ROWP)) == TAPS_3X3 && !CV) {      // a batch of images whose size is not a whole number of tiles
-        int gy = 0; long t = 0;
-        const int gx = INNFER_KNOB("INNFER_CANVAS", 1) ? canvas_grid<TH>(kp, N, &gy, &t) : 0;
+        int gy = 0;
+        const int gx = canvas_grid<TH>(kp, N, &gy);
         if (gx > 0) {
             KP kc = kp;
             kc.cv_gx = gx; kc.cv_gy = gy; kc.cv_h1 = kp.H + 1; kc.cv_w1 = kp.W + 1;
-            return launch_pc<RPW, NT, NLW, OUTMODE, false, false, TM, true, NSI, NCW>(kc, N, s);
+            return launch_pc<RPW, NT, NLW, OUTMODE, false, false, TM, true, NSI>(kc, N, s);
         }
     }
     static std::atomic<unsigned long long> attr_done{0};
-    INNFER_HIP(ensure_lds_attr(conv3x3_pc<RPW, NT, NLW, OUTMODE, S9, POLY, TM, CV, NSI, NCW>, LDS, attr_done));
+    INNFER_HIP(ensure_lds_attr(conv3x3_pc<RPW, NT, NLW, OUTMODE, S9, POLY, TM, CV, NSI>, LDS, attr_done));
     KP k = kp;
     k.tiles_x = (k.W + TW - 1) / TW;
     k.tiles_y = (k.y1 - k.y0 + TH - 1) / TH;
@@ -1051,7 +972,7 @@ int launch_pc(const KP& kp, int N, hipStream_t s) {
     if (total > 0x7fffffffL) return set_error(INNFER_ERR_INVALID, "conv grid too large");
     k.total = (int)total;
     const long grid = total < num_cus() ? total : num_cus();
-    hipLaunchKernelGGL((conv3x3_pc<RPW, NT, NLW, OUTMODE, S9, POLY, TM, CV, NSI, NCW>), dim3((unsigned)grid), dim3(64 * (NCW + NLW)), LDS, s, k);
+    hipLaunchKernelGGL((conv3x3_pc<RPW, NT, NLW, OUTMODE, S9, POLY, TM, CV, NSI>), dim3((unsigned)grid), dim3(64 * (NCW + NLW)), LDS, s, k);
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
 }
@@ -1150,12 +1071,9 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
     const int nt = conv_nt_for(L.K);
     if (L.out_mode != OUT_NCHW && L.K % (16 * nt))
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: K=%d must be a multiple of %d for slab output", L.K, 16 * nt);
-    const int rpw64 = INNFER_KNOB("INNFER_RPW64", 3);
-    const int rpw32 = INNFER_KNOB("INNFER_RPW32", 5);
-    const int pc = INNFER_KNOB("INNFER_PC", 1);     // producer / consumer kernel for slab outputs
     if (L.act == 8) {        // per-channel slopes (PReLU): conv3x3_pc<.., TMF | PC_PRELU>, the plain nine-tap slab kernels of 64 (either row order) and 32 outputs
         if (!L.slope) return set_error(INNFER_ERR_INVALID, "conv3x3: act 8 (per-channel slope) needs the slope vector");
-        if (!pc || L.out_mode != OUT_SLAB || (nt != 4 && nt != 2) || L.K != 16 * nt || L.split || L.stats_part || L.gate_w || L.conv1x1 || L.prefix_lrelu || L.deconv_phases || L.stride2 ||
+        if (L.out_mode != OUT_SLAB || (nt != 4 && nt != 2) || L.K != 16 * nt || L.split || L.stats_part || L.gate_w || L.conv1x1 || L.prefix_lrelu || L.deconv_phases || L.stride2 ||
             L.conv7v || L.conv7 || L.fuse_w || L.dilation > 1 || L.dilation_groups || L.in_relu || L.res1 || L.res2 || L.up || L.reflect || L.phase_c || L.outm || L.out_u8 ||
             (L.rowp && (L.rowp != 1 || nt != 4 || (L.out_coff & 31))))
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: act 8 (per-channel slope) is built as the epilogue of the plain 3x3 slab convs of 64 or 32 outputs -- not the split / "
@@ -1164,13 +1082,13 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         if (nt == 2) return launch_pc<3, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_PRELU>(k, L.N, s);
         return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP | PC_PRELU>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_PRELU>(k, L.N, s);
     }
-    if (L.rowp && !(L.rowp == 2 && L.out_mode == OUT_SHUFFLE2) && (nt != 4 || !pc || L.out_mode != OUT_SLAB || L.split || L.stats_part || L.stride2 || L.conv1x1 || L.conv7 || L.conv7v || L.prefix_lrelu ||
+    if (L.rowp && !(L.rowp == 2 && L.out_mode == OUT_SHUFFLE2) && (nt != 4 || L.out_mode != OUT_SLAB || L.split || L.stats_part || L.stride2 || L.conv1x1 || L.conv7 || L.conv7v || L.prefix_lrelu ||
                    L.gate_w || L.act > 2 || L.dilation > 1 || L.dilation_groups || (L.out_coff & 31)))
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the plane row order (rowp) belongs to plain 3x3 slab convs and transposed-conv phases with 64-channel output groups");
-    if (L.outm && (L.out_mode != OUT_NCHW || !pc || nt != 1 || L.res1 || L.res2 || L.outm < 0 || L.outm > 4))
+    if (L.outm && (L.out_mode != OUT_NCHW || nt != 1 || L.res1 || L.res2 || L.outm < 0 || L.outm > 4))
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: outm belongs to the planar last conv (<= 16 channels)");
     if (L.split) {           // fp32-accurate mode on (hi, lo) slab pairs: 3 * C / 32 virtual chunks (conv3x3_pc<.., TMF | PC_SPLIT>)
-        if (!pc || (L.act > 2 && !((L.act == 3 || L.act == 6) && L.out_mode == OUT_NCHW) && !((L.act == 4 || L.act == 5) && L.conv1x1 && nt == 2)) || L.reflect || L.dilation > 1 || L.dilation_groups || L.deconv_phases || L.stride2 || L.conv7v || L.conv7 || L.stats_part ||
+        if ((L.act > 2 && !((L.act == 3 || L.act == 6) && L.out_mode == OUT_NCHW) && !((L.act == 4 || L.act == 5) && L.conv1x1 && nt == 2)) || L.reflect || L.dilation > 1 || L.dilation_groups || L.deconv_phases || L.stride2 || L.conv7v || L.conv7 || L.stats_part ||
             L.prefix_lrelu || L.phase_c || (long)3 * L.C / 32 > 0x7fff)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3 (fp32 mode): plain 3x3 / 1x1 convs with act 0..2 (the 32-channel 1x1 conv also the PA gate), residuals, upsampled input");
         k.nchunks = 3 * k.ncg;
@@ -1190,7 +1108,7 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3 (fp32 mode): slab outputs of 32- / 64-channel tiles or a planar output of <= 16 channels (K=%d)", L.K);
     }
     if (L.dilation_groups > 0) {   // K = 32 * groups: output channel group g (its own 32-output panel) is the conv of dilation g + 1
-        if (!pc || L.out_mode != OUT_SLAB || L.K != 32 * L.dilation_groups || L.dilation_groups > 8 || L.res1 || L.res2 || L.up || L.reflect ||
+        if (L.out_mode != OUT_SLAB || L.K != 32 * L.dilation_groups || L.dilation_groups > 8 || L.res1 || L.res2 || L.up || L.reflect ||
             L.y0 != 0 || k.y1 != L.H || (long)L.H * L.W * 64 >= 0x7fffffffL)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: dilation groups are 32-output slab convs (K = 32 * groups <= 256), no residual / upsampling");
         k.nrate = L.dilation_groups; k.KG = L.dilation_groups; k.dil = 1; k.fullH = L.H; k.fullW = L.W;
@@ -1199,7 +1117,7 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
     }
     if (L.dilation > 1) {  // dilated 3x3 conv (zero padding = dilation) on the polyphase components: 32-output slab tiles, plain epilogue
         const int d = L.dilation;
-        if (!pc || L.out_mode != OUT_SLAB || nt != 2 || L.res1 || L.res2 || L.up || L.reflect || L.y0 != 0 || k.y1 != L.H ||
+        if (L.out_mode != OUT_SLAB || nt != 2 || L.res1 || L.res2 || L.up || L.reflect || L.y0 != 0 || k.y1 != L.H ||
             (long)L.H * L.W * 64 >= 0x7fffffffL || d > 64)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: dilated convs are 32-output slab convs without residual / upsampling, images below 33 M pixels");
         k.dil = d; k.fullH = L.H; k.fullW = L.W;
@@ -1208,7 +1126,7 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         return launch_pc<3, 2, 4, OUT_SLAB, false, true>(k, L.N * d * d, s);
     }
     if (L.deconv_phases) {   // ConvTranspose2d(4, 2, 1): K = 4 * phase_c, group g = phase g / (phase_c / 64); H, W: the input grid; output slab 2H x 2W
-        if (!pc || L.out_mode != OUT_SLAB || nt != 4 || L.phase_c <= 0 || L.phase_c % 64 || L.K != 4 * L.phase_c || L.res1 || L.res2 || L.up || L.reflect ||
+        if (L.out_mode != OUT_SLAB || nt != 4 || L.phase_c <= 0 || L.phase_c % 64 || L.K != 4 * L.phase_c || L.res1 || L.res2 || L.up || L.reflect ||
             L.act > 2 || L.y0 != 0 || k.y1 != L.H || L.dilation > 1 || L.dilation_groups)
             return set_error(INNFER_ERR_UNSUPPORTED, "deconv phases: slab output, 64-channel phase groups, no residual / upsampling / padding modes");
         // (in_relu on the phase lattice was built and measured -- scripts/r4/unet_one_view.sh: the four v_pk_max_f16 per fragment share the issue port with the MFMAs of
@@ -1226,13 +1144,13 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         return L.W <= 16 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_PHASE | PC_PAIR, false, UNET_NSI>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_PHASE, false, UNET_NSI>(k, L.N, s);
     }
     if (L.in_relu) {         // operand = max(stored, 0) (conv3x3_pc<.., TMF | PC_BRELU>): the planar 16-output kernel -- the UNet's outermost transposed conv
-        if (!(pc && L.out_mode == OUT_NCHW && nt == 1 && !L.res1 && !L.res2 && !L.conv7 && !L.stride2 && !L.conv7v && !L.conv1x1 && !L.gate_w && !L.fuse_w && !L.up && !L.reflect))
+        if (!(L.out_mode == OUT_NCHW && nt == 1 && !L.res1 && !L.res2 && !L.conv7 && !L.stride2 && !L.conv7v && !L.conv1x1 && !L.gate_w && !L.fuse_w && !L.up && !L.reflect))
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: in_relu is built for the planar <= 16-output kernel");
         return launch_pc<3, 1, 4, OUT_NCHW, false, false, TAPS_3X3 | PC_BRELU>(k, L.N, s);
     }
     if (L.stride2) {         // Conv2d(k 4, s 2, p 1): H x W = the OUTPUT grid, source image 2H x 2W; panels from conv_pack_taps(K, 4C, TAPS_S2), virtual channel
                              // (2 pa + pb) * C + ci, tap (1 + dy, 1 + dx) = w[co][ci][2 dy + pa][2 dx + pb]
-        if (!pc || L.out_mode != OUT_SLAB || (nt != 4 && nt != 2) || L.res1 || L.res2 || L.up || L.reflect || L.act > 2 || L.y0 != 0 || k.y1 != L.H ||
+        if (L.out_mode != OUT_SLAB || (nt != 4 && nt != 2) || L.res1 || L.res2 || L.up || L.reflect || L.act > 2 || L.y0 != 0 || k.y1 != L.H ||
             L.dilation > 1 || L.dilation_groups || (long)L.H * L.W * 4 * 64 >= 0x7fffffffL || (nt == 2 && L.stats_part))
             return set_error(INNFER_ERR_UNSUPPORTED, "stride-2 conv: slab output of 32- / 64-channel tiles, no residual / upsampling / padding modes, sources below 33 M pixels");
         k.Hs = 2 * L.H; k.Ws = 2 * L.W; k.in_img_stride = (long)k.Hs * k.Ws * 32;
@@ -1242,7 +1160,7 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         return L.W <= 16 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_S2 | PC_S2 | PC_PAIR, false, UNET_NSI>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_S2 | PC_S2, false, UNET_NSI>(k, L.N, s);
     }
     if (L.conv7v) {        // 7 x 1 column conv (padding 3 rows, zero or reflected) as three vertically displaced 3-tap blocks: panels from conv_pack7v, slab output
-        if (!pc || L.out_mode != OUT_SLAB || (nt != 2 && nt != 4) || L.res1 || L.res2 || L.up || L.act > 2 || L.y0 != 0 || k.y1 != L.H || L.reflect == 2 ||
+        if (L.out_mode != OUT_SLAB || (nt != 2 && nt != 4) || L.res1 || L.res2 || L.up || L.act > 2 || L.y0 != 0 || k.y1 != L.H || L.reflect == 2 ||
             (long)L.H * L.W * 64 >= 0x7fffffffL)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv7x1: slab output of 32- / 64-channel tiles, no residual / upsampling, images below 33 M pixels");
         k.nchunks = 3 * k.ncg; k.s9v = 1;
@@ -1250,7 +1168,7 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         return nt == 4 ? launch_pc<2, 4, 4, OUT_SLAB, true, false, TAPS_COL>(k, L.N, s) : launch_pc<3, 2, 4, OUT_SLAB, true, false, TAPS_COL>(k, L.N, s);
     }
     if (L.conv1x1) {        // centre tap only: panels from conv_pack_1x1
-        if (!pc || L.out_mode != OUT_SLAB || (nt != 2 && nt != 4))
+        if (L.out_mode != OUT_SLAB || (nt != 2 && nt != 4))
             return set_error(INNFER_ERR_UNSUPPORTED, "conv1x1: slab outputs of 32- / 64-channel tiles on the producer-consumer kernel");
         if (L.prefix_lrelu) {
             if (nt != 4) return set_error(INNFER_ERR_UNSUPPORTED, "conv1x1: the running-sum operand is built for 64-channel tiles");
@@ -1260,18 +1178,14 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         return nt == 4 ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_1X1, false, 3>(k, L.N, s) : launch_pc<2, 2, 4, OUT_SLAB, false, false, TAPS_1X1, false, 3>(k, L.N, s);
     }
     if (L.gate_w) {          // out = act(v * sigmoid(W v + b)), v = this conv's fp16 result (PAN's PA block behind an up-conv): conv3x3_pc<.., TMF | PC_SGATE>
-        if (!pc || L.out_mode != OUT_SLAB || nt != 2 || L.K != 32 || L.res1 || L.res2 || L.act > 2 || L.reflect || L.stats_part)
+        if (L.out_mode != OUT_SLAB || nt != 2 || L.K != 32 || L.res1 || L.res2 || L.act > 2 || L.reflect || L.stats_part)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the self gate belongs to 32-output slab convs without residuals (act = the activation AFTER the gate)");
         k.sg_w = L.gate_w; k.sg_bias = L.gate_bias;
         return launch_pc<3, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_SGATE>(k, L.N, s);
     }
-    if (pc && L.out_mode == OUT_SLAB && nt == 2 && !L.fuse_w) {
-        // 32-output layers: 24-row tiles, two LDS stages.  pc 5 (diagnostic builds): 16-row tiles on the three-slot input ring (continuous LDS-DMA
-        // issue) -- measured within +-1 % of the default on the frame and on the chop path (profiles/r2/kernel_experiments.txt), so the simpler form ships
-        if (pc == 5) return launch_pc<2, 2, 4, OUT_SLAB, false, false, TAPS_3X3, false, 3>(k, L.N, s);
-        if (INNFER_KNOB("INNFER_FAT", 0) & 1) return launch_pc<6, 2, 4, OUT_SLAB, false, false, TAPS_3X3, false, 2, 4>(k, L.N, s);
-        return pc == 2 ? launch_pc<3, 2, 8>(k, L.N, s) : pc == 3 ? launch_pc<2, 2, 4>(k, L.N, s) : launch_pc<3, 2, 4>(k, L.N, s);
-    }
+    // 32-output layers: 24-row tiles, two LDS stages (16-row tiles on the three-slot input ring measured within +-1 % on the frame and on the chop path --
+    // profiles/r2/kernel_experiments.txt -- so the simpler form ships)
+    if (L.out_mode == OUT_SLAB && nt == 2 && !L.fuse_w) return launch_pc<3, 2, 4>(k, L.N, s);
     if (L.fuse_w) {          // HR_conv0 with the network's last conv in its epilogue (conv3x3_pc<.., TMF | PC_FUSE>) + the rim pass
         if (!conv_fuse_last_ok(L)) return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the fused last conv needs 64 or 32 output channels, whole 16 x 32 tiles, act 0..2, no residual / upsampling / row range");
         k.fl_w = L.fuse_w; k.fl_bias = L.fuse_bias; k.fl_side = L.fuse_side; k.fl_out = L.fuse_out; k.fl_oc = L.fuse_oc; k.fl_out_mode = L.fuse_out_mode;
@@ -1285,18 +1199,18 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         return INNFER_OK;
     }
     if (L.out_mode == OUT_SHUFFLE2 && L.rowp == 2) {          // PixelShuffle(2) store on the producer / consumer kernel: phase-major plane-order panels (conv_pack_shuffle2)
-        if (!pc || nt != 4 || L.K % 256 || L.res1 || L.res2 || L.up || L.reflect || L.act > 2 || L.y0 != 0 || k.y1 != L.H || L.stats_part ||
+        if (nt != 4 || L.K % 256 || L.res1 || L.res2 || L.up || L.reflect || L.act > 2 || L.y0 != 0 || k.y1 != L.H || L.stats_part ||
             (long)L.N * L.H * L.W * 64 * 4 >= 0x7fffffffL)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the phase-major PixelShuffle(2) store needs K %% 256 == 0 (64-channel phases), act 0..2, no residual / upsampling / row range, < 2 GiB per output group");
         k.phase_c = L.K / 4;
         return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP | PC_PSH>(k, L.N, s);
     }
-    if (pc && L.out_mode == OUT_SLAB && nt == 4 && L.stats_part) return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_STATS>(k, L.N, s);
+    if (L.out_mode == OUT_SLAB && nt == 4 && L.stats_part) return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_STATS>(k, L.N, s);
     // the 2 x 4 consumer grid (conv3x3_pc<4, 2, .., TMF | PC_GRID2>) of the plain and the RLDS plane-order conv with one 64-channel output group -- except where the launch
-    // would be laid out as an image canvas (launch_pc), a form the grid does not have
-    bool grid2 = pc && L.grid2 && L.out_mode == OUT_SLAB && nt == 4 && L.rowp == 1 && L.K == 64 && L.act <= 2 && INNFER_KNOB("INNFER_GRID2", 1);
-    if (grid2 && INNFER_KNOB("INNFER_CANVAS", 1)) { int gy = 0; long t = 0; grid2 = canvas_grid<16>(k, L.N, &gy, &t) == 0; }
-    if (pc && L.out_mode == OUT_SLAB && nt == 4 && L.res1_lds && L.res1 && L.res1 == L.in && L.res1_gstride == L.in_gstride && L.act == 0 && L.K == 64 && L.C >= 96 &&
+    // would be laid out as an image canvas (launch_pc asks canvas_grid the same question for the 8 x 1 form, on the same tile height), a form the grid does not have
+    bool grid2 = L.grid2 && L.out_mode == OUT_SLAB && nt == 4 && L.rowp == 1 && L.K == 64 && L.act <= 2;
+    if (grid2) { int gy = 0; grid2 = canvas_grid<PcLayout<2, 4, 2, TAPS_3X3 | PC_ROWP>::TH>(k, L.N, &gy) == 0; }
+    if (L.out_mode == OUT_SLAB && nt == 4 && L.res1_lds && L.res1 && L.res1 == L.in && L.res1_gstride == L.in_gstride && L.act == 0 && L.K == 64 && L.C >= 96 &&
         !L.up && !L.reflect && L.s1 != 0.f && (L.res1_lds == 2 || L.res2)) {
         // the dense block's last conv: the residual is the conv's own input groups 0 and 1 -- taken from the live LDS stages (conv3x3_pc<.., TMF | PC_RLDS>).
         // res1_lds 1 (the networks' default): only where a SECOND residual follows (the last dense block of an RRDB) -- there the epilogue could not batch two
@@ -1307,26 +1221,23 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
         if (grid2) return launch_pc<4, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_RLDS | PC_ROWP | PC_GRID2>(k, L.N, s);
         return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_RLDS | PC_ROWP>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_RLDS>(k, L.N, s);
     }
-    if (pc && L.out_mode == OUT_SLAB && nt == 4) {
-        // diagnostic builds: four consumer waves of twice the rows (measured within +-1 %: profiles/r2/kernel_experiments.txt 10)
-        if (!L.rowp && (INNFER_KNOB("INNFER_FAT", 0) & 2)) return launch_pc<4, 4, 4, OUT_SLAB, false, false, TAPS_3X3, false, 2, 4>(k, L.N, s);
+    if (L.out_mode == OUT_SLAB && nt == 4) {
         if (grid2) return launch_pc<4, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP | PC_GRID2>(k, L.N, s);
         return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP>(k, L.N, s) : launch_pc<2, 4, 4>(k, L.N, s);
     }
     if (L.conv7) {         // 7x7 (padding 3) as nine displaced 3x3 convs: planar output, <= 16 output channels, panels from conv_pack7x7
-        if (!pc || L.out_mode != OUT_NCHW || nt != 1 || L.res1 || L.res2 || L.up || (long)L.H * L.W * 64 >= 0x7fffffffL)
+        if (L.out_mode != OUT_NCHW || nt != 1 || L.res1 || L.res2 || L.up || (long)L.H * L.W * 64 >= 0x7fffffffL)
             return set_error(INNFER_ERR_UNSUPPORTED, "conv7x7: planar output with K <= 16, no residual / upsampling, images below 33 M pixels");
         k.nchunks = 9 * k.ncg;
         return launch_pc<3, 1, 4, OUT_NCHW, true>(k, L.N, s);
     }
-    if (pc && L.out_mode == OUT_NCHW && nt == 1 && !L.res1 && !L.res2) return launch_pc<3, 1, 4, OUT_NCHW>(k, L.N, s);
-    if (pc && L.out_mode == OUT_NCHW && nt == 2 && !L.res1 && !L.res2 && !L.phase_c && !L.reflect && !L.out_u8) return launch_pc<3, 2, 4, OUT_NCHW>(k, L.N, s);
+    if (L.out_mode == OUT_NCHW && nt == 1 && !L.res1 && !L.res2) return launch_pc<3, 1, 4, OUT_NCHW>(k, L.N, s);
+    if (L.out_mode == OUT_NCHW && nt == 2 && !L.res1 && !L.res2 && !L.phase_c && !L.reflect && !L.out_u8) return launch_pc<3, 2, 4, OUT_NCHW>(k, L.N, s);
     if (L.act >= 3 || L.phase_c > 0 || L.reflect)
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: tanh / phase output / gate epilogues / reflection padding exist only in the producer-consumer kernel");
+    // what is left runs on the two-workgroup kernel (conv3x3_mfma): the five forms of this file's header comment
     switch (L.out_mode) {
-        case OUT_SLAB:
-            if (nt == 4) return rpw64 == 4 ? launch_t<4, 4, OUT_SLAB>(k, L.N, s) : rpw64 == 3 ? launch_t<3, 4, OUT_SLAB>(k, L.N, s) : launch_t<2, 4, OUT_SLAB>(k, L.N, s);
-            if (nt == 2) return rpw32 == 6 ? launch_t<6, 2, OUT_SLAB>(k, L.N, s) : rpw32 == 5 ? launch_t<5, 2, OUT_SLAB>(k, L.N, s) : rpw32 == 3 ? launch_t<3, 2, OUT_SLAB>(k, L.N, s) : launch_t<4, 2, OUT_SLAB>(k, L.N, s);
+        case OUT_SLAB:      // (nt 2 and 4 have returned above)
             return launch_t<4, 1, OUT_SLAB>(k, L.N, s);
         case OUT_NCHW:
             if (nt == 4) return launch_t<2, 4, OUT_NCHW>(k, L.N, s);

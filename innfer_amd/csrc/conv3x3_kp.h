@@ -4,10 +4,11 @@
 constexpr int TW = 32;        // tile width (pixels)
 constexpr int LWP = 36;       // LDS row pitch (pixels): 36 px = 2304 B = 9 x 256 B, so every row starts on bank 0
 constexpr int LVALID = TW + 2;
+constexpr int NCW = 8;        // consumer (MFMA) waves of a conv3x3_pc workgroup: two per SIMD, in front of its NLW loader waves
 
-// The dynamic LDS of conv3x3_pc<RPW, NT, .., TMF, .., NSI, NCW>, for the kernel and its launcher alike: NSI input slots (a halo tile each) and two weight
+// The dynamic LDS of conv3x3_pc<RPW, NT, .., TMF, .., NSI>, for the kernel and its launcher alike: NSI input slots (a halo tile each) and two weight
 // slots (a panel each) -- NSI 2: two stages [tile | panel]; NSI 3: three tiles, then two panels -- and behind them the tail of the ONE mode that has one.
-template <int RPW, int NT, int NSI, int NCW, int TMF>
+template <int RPW, int NT, int NSI, int TMF>
 struct PcLayout {
     static constexpr bool GRID2 = (TMF & PC_GRID2) != 0;                       // 2 x 4 consumer grid: NCW / 2 row groups, two NT-tile halves of the panel's rows
     static constexpr int TH = (GRID2 ? NCW / 2 : NCW) * RPW;                   // tile rows
@@ -40,7 +41,7 @@ struct KP {
     int outm;                // planar kernels: RRDBNet / SRResNet.forward(outm=...) after the activation
     int out_u8, out_denorm, out_round16;   // planar kernels with <= 4 channels: uint8 HWC BGR(A) image instead of planar floats (tensor2np as the epilogue)
     int N;
-    int pf;                  // L2 prefetch of the next chunk's input lines
+    float rs1;               // RLDS kernels (TMF | PC_RLDS): 1 / s1 -- the residual res1 (= the conv's own input groups 0, 1) is added to the accumulators as x / s1 from the live LDS stage
     int rev;                 // each XCD walks its run of tiles backwards
     int nrate, rate_start[9];// POLY kernels with nrate > 0: output channel group g (32 channels) is a conv of dilation g + 1 over its own tile grid;
                              // tiles [rate_start[g], rate_start[g+1]) of the launch belong to it (dil unused)
@@ -64,9 +65,10 @@ struct KP {
         const float* sg_bias;
         const float* slope;  // PRELU kernels (TMF | PC_PRELU): per-channel slopes of the act-8 epilogue, padded and indexed like `bias`
     };
-    float rs1;               // RLDS kernels (TMF | PC_RLDS): 1 / s1 -- the residual res1 (= the conv's own input groups 0, 1) is added to the accumulators as x / s1 from the live LDS stage
-    long in_lo_bytes;        // SPLIT kernels (TMF | PC_SPLIT): the low-part twin of the input slab lies this many bytes behind it,
-    long out_lo, res1_lo, res2_lo;   //   those of the output / residual slabs this many ELEMENTS behind them
+    // (rs1 above and res2_lo here stand in slots that a removed field left: the argument block of every instantiation that reads neither keeps its layout)
+    long res2_lo;            // SPLIT kernels (TMF | PC_SPLIT): the low-part twin of a slab lies behind it -- res2's this many ELEMENTS,
+    long in_lo_bytes;        //   the input slab's this many bytes,
+    long out_lo, res1_lo;    //   those of the output / first residual slabs this many ELEMENTS
 #ifdef INNFER_ABLATE
     int abl;                 // diagnostic build only: 1 no stores, 2 no weight DMA, 4 no input DMA, 8 no MFMA phase
 #endif

@@ -61,7 +61,7 @@
             } else if constexpr (OUTMODE == OUT_SLAB) {
             if constexpr (STATS) {
                 const int lid = run_start + (p.rev ? run_len - 1 - (jt - slots) : (jt - slots));         // (jt was advanced above)
-                epilogue_stats<RPW, NT, TM == TAPS_PHASE, PAIR, NCW>(p, acc, bias_r, ty0, tx0, cw, li, cbase, lid / p.KG);
+                epilogue_stats<RPW, NT, TM == TAPS_PHASE, PAIR>(p, acc, bias_r, ty0, tx0, cw, li, cbase, lid / p.KG);
             }
 #define EPI(A, B, C) epilogue_slab<RPW, NT, A, B, C, !(C), POLY, TM == TAPS_PHASE, PAIR, false, ROWP, PSH>(p, acc, n, ty0, tx0, cw, li, cbase, dcur)
             if (!p.res1) {

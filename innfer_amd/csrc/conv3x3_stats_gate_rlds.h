@@ -8,7 +8,7 @@
 //   part[((slot * NCW + wave) * cn + channel) * 3],  slot = tile index over the batch (x 4 + phase behind the phase lattice).
 // norm::combine_parts merges an image's partials in index order (Chan's update): deterministic, no atomics, and the pass that re-read the conv
 // output for its statistics is gone.
-template <int RPW, int NT, bool DCV, bool PAIR, int NCW>
+template <int RPW, int NT, bool DCV, bool PAIR>
 __device__ __forceinline__ void epilogue_stats(const KP& p, const f32x4 (&acc)[NT][2 * RPW], const f32x4 (&bias)[NT], int ty0, int tx0, int wave, int li,
                                                int cbase, int tile) {
     static_assert(NT == 4, "sixteen channels per lane: one per pixel lane after the transposing reduction");

@@ -80,12 +80,6 @@ extern "C" int innfer_timer_stop(void* stream, int cap, char* names, int name_ca
     return rc;
 }
 
-#ifndef INNFER_ROWP_DEFAULT
-#define INNFER_ROWP_DEFAULT 1      // (A/B builds: 0 = the lane-contiguous row order everywhere)
-#endif
-#ifndef INNFER_FUSE_LAST
-#define INNFER_FUSE_LAST 1
-#endif
 struct ConvSlot {
     std::string key;
     int K = 0, C = 0;
@@ -126,19 +120,9 @@ struct innfer_net {
     float res_scale = 1.f;       // SRResNet: x + res * res_scale (SRResNet_arch.py:88-91)
     int outm = 0;                // `outm` of RRDBNet / SRResNet.forward (RRDBNet_arch.py:50-62): 0 none, 1 scaltanh, 2 tanh, 3 sigmoid, 4 clamp
     int u8_normalize = 0, u8_round16 = 1;   // innfer_net_forward with INNFER_U8 images: normalize / denormalize flags of np2tensor / tensor2np, fp16 mode
-#ifndef INNFER_UP_PHASES_DEFAULT
-#define INNFER_UP_PHASES_DEFAULT 1
-#endif
-    int up_phases = INNFER_UP_PHASES_DEFAULT;   // upconv_block convs as four 2x2-tap phases on the LR grid (innfer_net_set_upconv_phases; the macro: A/B builds)
+    int up_phases = 1;           // upconv_block convs as four 2x2-tap phases on the LR grid (innfer_net_set_upconv_phases)
     int fused_tail = 1;          // HR_conv0 -> conv_last as one kernel where the shapes allow it (innfer_net_set_fused_tail)
-#ifndef INNFER_HR_CHAIN_DEFAULT
-#define INNFER_HR_CHAIN_DEFAULT 1
-#endif
-    int hr_chain = INNFER_HR_CHAIN_DEFAULT;   // the LAST upconv_block -> HR_conv0 -> conv_last as one kernel chained through LDS (hr_chain.hip; innfer_net_set_hr_chain): the 64-channel HR tensor is never written
-#ifndef INNFER_PS_PC_DEFAULT
-#define INNFER_PS_PC_DEFAULT 1
-#endif
-    int ps_pc = INNFER_PS_PC_DEFAULT;   // PixelShuffle(2) stages on the producer / consumer kernel (phase-major panels); 0 (A/B builds): the two-workgroup kernel of rounds 1-4
+    int hr_chain = 1;            // the LAST upconv_block -> HR_conv0 -> conv_last as one kernel chained through LDS (hr_chain.hip; innfer_net_set_hr_chain): the 64-channel HR tensor is never written
     int consumer_grid = 1;       // the 64-output 3x3 slab convs of the RRDBNet trunk on the 2 x 4 consumer grid (innfer_net_set_consumer_grid; conv3x3_pc GRID2); 0: the 8 x 1 form
     int res_lds = 1;             // the dense block's x5 * 0.2 + x with x taken from the conv's own staged LDS tiles (innfer_net_set_residual_lds; conv3x3_pc RLDS): 1 = where the RRDB's residual follows, 2 = every block
     bool plus = false;           // ESRGAN+ residual paths (RRDBNet_arch.py:155-160)
@@ -374,11 +358,11 @@ extern "C" int innfer_net_set_conv(innfer_net_t net, int idx, const float* w, co
             std::vector<float> wp((size_t)c.Kp * c.C * 9, 0.f);
             std::copy(w, w + (size_t)c.K * c.C * 9, wp.begin());
             host.resize(conv_packed_bytes(c.Kp, c.C));
-            c.rowp = INNFER_ROWP_DEFAULT && c.Kp == 64;
+            c.rowp = c.Kp == 64;
             conv_pack(wp.data(), c.Kp, c.C, host.data(), c.rowp);
         } else {
             host.resize(conv_packed_bytes(c.K, c.C));
-            c.rowp = INNFER_ROWP_DEFAULT && c.K == 64;
+            c.rowp = c.K == 64;
             conv_pack(w, c.K, c.C, host.data(), c.rowp);
         }
         const int per = 16 * conv_nt_for(c.Kp ? c.Kp : c.K);
@@ -412,7 +396,7 @@ extern "C" int innfer_net_set_conv(innfer_net_t net, int idx, const float* w, co
         }
         if (c.ksize == 3 && c.C == 64 && c.K <= 3) {          // (only the network's last conv has this shape)
             std::vector<char> fp(4096);
-            conv_pack_fuse_last(w, c.K, fp.data(), INNFER_ROWP_DEFAULT);          // (fused behind HR_conv0, a 64-output conv: its row order)
+            conv_pack_fuse_last(w, c.K, fp.data(), 1);          // (fused behind HR_conv0, a 64-output conv: its row order)
             if (!c.d_fuse) INNFER_HIP(hipMalloc(&c.d_fuse, fp.size()));
             INNFER_HIP(hipMemcpy(c.d_fuse, fp.data(), fp.size(), hipMemcpyHostToDevice));
         }
@@ -791,10 +775,6 @@ int do_first_unshuffle(const FirstUnshuffleLaunch& F, hipStream_t s) {
     return timed_end(s, 2.0 * 9.0 * F.K * cin * px, px * (cin * (F.in_u8 ? 1.0 : F.in_f32 ? 4.0 : 2.0) + F.K * 2.0 * (F.out2 ? 2 : 1)), 0);
 }
 
-struct Plan {                    // one MFMA conv in the launch list
-    ConvLaunch L;
-};
-
 // in/out point at channel 0 of the tensors; *_g are their group strides (elements).
 // lo > 0: fp32-accurate mode, every slab's lo twin `lo` elements behind it
 ConvLaunch mk_launch(const ConvSlot& cs, const f16* in, long in_g, void* out, long out_g,
@@ -1063,7 +1043,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
             continue;
         }
         if (u == net->n_up - 1 && !net->ps_up && net->up_phases == 1 && net->hr_chain && !net->fp32 && cs.d_up4p && !cs.d_map && (net->trunk_act == 1 || net->trunk_act == 2) && w > 16 &&
-            INNFER_FUSE_LAST && net->fused_tail && !any_map && net->band_rows == 0 && net->final_act == 0 && net->outm == 0) {
+            net->fused_tail && !any_map && net->band_rows == 0 && net->final_act == 0 && net->outm == 0) {
             // The last upconv_block -> HR_conv0 -> conv_last as ONE kernel (hr_chain.hip): the [64 ch, 2h x 2w] tensor between them (4.25 GB of a 1080p -> 4K frame, written
             // by a store-bound launch and read back by the next) stays in LDS tile by tile.  Same operands in the same order per value as the two launches below: same bits.
             const ConvSlot& ch = net->convs[ci];           // HR_conv0
@@ -1110,7 +1090,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
             L.out_mode = OUT_SHUFFLE2;
             // the store of the producer / consumer kernel (conv3x3_pc PSH) while an output group stays below 2 GiB (conv_launch's bound for that form: chop batches of
             // more than 209 tiles of 200 x 200 at the first stage and 4x frames beyond 8.39 M LR pixels at the second take the two-workgroup kernel, whose indices are 64-bit)
-            if (cs.d_ps && net->ps_pc && !cs.d_map && (long)N * h * w * 256 < 0x7fffffffL) { L.wpk = (const f16*)cs.d_ps; L.bias = cs.d_bps; L.rowp = 2; }
+            if (cs.d_ps && !cs.d_map && (long)N * h * w * 256 < 0x7fffffffL) { L.wpk = (const f16*)cs.d_ps; L.bias = cs.d_bps; L.rowp = 2; }
             rc = do_conv(L, s);
         }
         if (rc) return rc;
@@ -1123,7 +1103,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
         // HR_conv0 -> conv_last in one kernel (conv3x3.hip, FUSE) where the shapes allow it: fp16 engine, 64 features, <= 3 planar float outputs without final
         // activation / outm, whole 16 x 32 tiles.  The rim buffer lives where the HR slab would have been.
         const ConvSlot& cl = net->convs[ci];
-        if (INNFER_FUSE_LAST && net->fused_tail && !net->fp32 && !any_map && net->band_rows == 0 && cl.d_fuse && cl.loaded && net->final_act == 0 && net->outm == 0 &&
+        if (net->fused_tail && !net->fp32 && !any_map && net->band_rows == 0 && cl.d_fuse && cl.loaded && net->final_act == 0 && net->outm == 0 &&
             (out_dtype == INNFER_F16 || out_dtype == INNFER_F32 || out_dtype == INNFER_U8) && conv_fuse_side_bytes(N, h, w) <= (size_t)gh * 2 * (net->nf / 32)) {
             L.fuse_w = (const f16*)cl.d_fuse; L.fuse_bias = cl.d_b; L.fuse_side = (float*)(ws + cv.hr); L.fuse_out = d_out; L.fuse_oc = cl.K;
             L.fuse_out_mode = out_dtype == INNFER_U8 ? 2 : out_dtype == INNFER_F32 ? 1 : 0;

@@ -5,7 +5,7 @@ cache-resident window.  Results are wrong
 by construction; only the launch times mean anything."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-# INNFER_PC=0: the two-workgroup kernel (conv3x3_mfma); default: the producer / consumer kernels (bits 1, 2, 4, 8)
+# these three layer classes run on the producer / consumer kernels (conv3x3_pc: bits 1, 2, 4, 8)
 os.environ.setdefault("INNFER_LIB", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                  "innfer_amd", "lib", "libinnfer_amd_ablate.so"))
 from scripts.bench_conv import run

@@ -1,4 +1,5 @@
 #!/bin/bash
+# (needs a checkout of a1ebe9b: the INNFER_FAT knob and its instantiations were removed after it)
 # A/B of the fat-consumer-wave instantiations on ONE box (diagnostic library reads INNFER_FAT: 1 = 32-output layers, 2 = 64-output layers)
 cd ${GRAFT_REPO_ROOT:-.}
 for rep in 1 2; do

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# (needs a checkout of a1ebe9b: INNFER_PC, INNFER_PERSIST and the STAMP hooks of conv3x3_mfma were removed after it)
 """Diagnostic: WG timeline of the v1 conv kernel from in-kernel s_memtime stamps
 (needs `make stamps`; run with INNFER_LIB=innfer_amd/lib/libinnfer_amd_stamps.so INNFER_PERSIST=0: one workgroup per tile)."""
 import ctypes as C

@@ -18,6 +18,9 @@ Measured on the MI355X (largest e32 of the family's cases; worst err / bound ove
     planar 3x3, reflection padding                       1.6e-06    0.993
     planar 3x3, K = 32                                   6.4e-07    0.997
     planar 3x3, K = 64 (launch_t)                        6.9e-07    0.994
+    two-workgroup kernel, slab K = 16                    5.0e-07    0.994
+    two-workgroup kernel, planar K = 16, residuals       4.1e-07    0.994   (fp32 stores: 0.046 of 8 e32)
+    two-workgroup kernel, planar K = 32, residuals       5.9e-07    0.993   (fp32 stores: 0.038 of 8 e32)
     planar uint8 image                                   5.4e-07    7e-5 of the codes differ (cap 1e-2), each by one, next to a boundary
     planar phase scatter                                 8.5e-07    0.998
     planar phase scatter + in_relu                       5.8e-07    0.995
@@ -136,7 +139,7 @@ def _run(dev, c, out="slab", act=0, res1=None, s1=1.0, res2=None, s2=1.0, out_gr
     keep = []
     for name, r, sc in (("1", res1, s1), ("2", res2, s2)):
         if r is not None:
-            rs = R.to_slab(r).to(dev)
+            rs = R.to_slab(F.pad(r, (0, 0, 0, 0, 0, -r.shape[1] % 32))).to(dev)      # (a residual of 16 channels lies in a 32-channel group)
             setattr(a, f"d_res{name}", rs.data_ptr()); setattr(a, f"res{name}_group_stride", N * Ho * Wo * 32); setattr(a, f"res{name}_scale", sc)
             keep.append(rs)
     if gate:
@@ -236,6 +239,23 @@ def test_planar_3x3_k_32_and_64(dev, K):
         for act in (3, 6):
             _run(dev, c, "f16", act=act, expect=L.ERR_UNSUPPORTED)
     _run(dev, c, "f16", outm=1, expect=L.ERR_UNSUPPORTED)
+
+
+@pytest.mark.parametrize("K,out", [(16, "slab"), (16, "planar"), (32, "planar")])
+def test_two_workgroup_kernel_forms_without_another_test(dev, K, out):
+    """conv3x3_mfma's instantiations beside <2, 4, OUT_NCHW> (the K = 64 case above) and <2, 4, OUT_SHUFFLE2> (the sweep's PixelShuffle(2) store): launch_t<4, 1, OUT_SLAB>
+    (a slab of 16 channels: the other half of its 32-channel group keeps the fill), <4, 1, OUT_NCHW> and <4, 2, OUT_NCHW> (planar outputs WITH residuals; without one they
+    run on conv3x3_pc).  Tiles are 16 x 32: both sizes are ragged on both axes, the second is a batch."""
+    fam = f"two-workgroup kernel, {out} K = {K}"
+    for (N, H, W) in [(1, 25, 33), (2, 37, 45)]:
+        c = Case("3x3", N, 64, K, H, W, seed=50 + K + (out == "slab"))
+        if out == "slab":
+            for act in (0, 1, 2):
+                _check(dev, c, fam, act=act)
+        else:
+            _check(dev, c, fam, "f16", act=1, nres=1, s1=0.2)
+            _check(dev, c, fam, "f32", act=0, nres=2, s1=0.2, s2=0.5)
+            _check(dev, c, fam, "f16", act=2, nres=2, s1=0.2, s2=0.5)
 
 
 # ------------------------------------------------------------------------------------------------ the uint8 image

@@ -363,12 +363,26 @@ def _kernel_metadata(so_path):
 def test_no_shipped_kernel_uses_scratch_memory():
     """A kernel whose per-lane arrays land in scratch memory stays correct and gets slow without a trace in any parity test (the 7x7 instantiation
     of conv3x3_pc ran 11 x slower for a while because a loader lambda was no longer inlined).  Every kernel of the shipped library must have a
-    private segment of 0 bytes and no spilled vector registers; the one exception is a fallback instantiation no launch path selects."""
+    private segment of 0 bytes and no spilled vector registers."""
     ks = _kernel_metadata(L.LIB_PATH)
     assert len(ks) >= 60, len(ks)
-    allowed = ("conv3x3_mfmaILi4ELi4ELi0E",)          # 16-row x 64-channel two-workgroup form: diagnostic builds only (INNFER_PC=0, INNFER_RPW64=4)
-    bad = [(n, priv, vs) for (n, priv, _v, _ss, vs) in ks if (priv or vs) and not any(a in n for a in allowed)]
+    bad = [(n, priv, vs) for (n, priv, _v, _ss, vs) in ks if priv or vs]
     assert not bad, bad
+
+
+def test_shipped_conv3x3_instantiations_are_the_reachable_ones():
+    """The shipped library holds no conv kernel that no launch can select: conv3x3_mfma<RPW, NT, OUT> exists in exactly the five forms the last switch of
+    conv_launch reaches (the header comment of csrc/conv3x3.hip names the launch behind each), and every conv3x3_pc<RPW, NT, NLW, ..> has four loader waves.
+    A form that comes back has to be added here on purpose."""
+    names = [k[0] for k in _kernel_metadata(L.LIB_PATH)]
+    out_slab, out_nchw, out_shuffle2 = 0, 1, 2                       # enum OutMode (csrc/common.h)
+    mfma = [re.search(r"conv3x3_mfmaILi(\d+)ELi(\d+)ELi(\d+)EE", n) for n in names if "conv3x3_mfma" in n]
+    assert mfma and all(mfma), [n for n in names if "conv3x3_mfma" in n]
+    got = sorted(tuple(int(v) for v in m.groups()) for m in mfma)
+    assert got == sorted([(4, 1, out_slab), (2, 4, out_nchw), (4, 2, out_nchw), (4, 1, out_nchw), (2, 4, out_shuffle2)]), got
+    pc = [(n, re.search(r"conv3x3_pcILi(\d+)ELi(\d+)ELi(\d+)ELi(\d+)E", n)) for n in names if "conv3x3_pc" in n]
+    assert len(pc) >= 40, len(pc)
+    assert all(m and int(m.group(3)) == 4 for _n, m in pc), [n for n, m in pc if not m or int(m.group(3)) != 4]
 
 
 def test_chop_plan_equals_oracle_geometry_on_random_sizes():
