@@ -564,12 +564,23 @@ __global__ void f32_maxpool4_kernel(const float* in, float* out, long planes, in
     out[i] = m;
 }
 
-__device__ __forceinline__ float cub1(float x, float A) { return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f; }
-__device__ __forceinline__ float cub2(float x, float A) { return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A; }
+// The two combine kernels below promise the SAME BITS per output, so their arithmetic is spelled out: `#pragma clang fp contract(off)` in the weights and in both bodies --
+// every product and sum rounded on its own, as ATen's CPU kernel rounds them -- and fmaf where a fused multiply-add is meant (the tap sums, gamma * v + inp).  Left to
+// the compiler's contraction the two differed in the last bit: the one-pixel kernel's tap sums were vectorised into v_pk_mul_f32 + v_add_f32, the strip kernel's became
+// v_fmac_f32 -- 188 of the 1280 values of a 4 x 4 frame, 19 348 of 81 920 at 16 x 64 (tests/test_gpu_pan_fsa.py test_combine_vs_float64, fp32, W == 4 wp).
+__device__ __forceinline__ float cub1(float x, float A) {
+#pragma clang fp contract(off)
+    return ((A + 2.f) * x - (A + 3.f)) * x * x + 1.f;
+}
+__device__ __forceinline__ float cub2(float x, float A) {
+#pragma clang fp contract(off)
+    return ((A * x - 5.f * A) * x + 8.f * A) * x - 4.f * A;
+}
 
 // out = gamma * bicubic(att, size = (H, W), align_corners = False) + inp   (block.py:463-471, ATen upsample_bicubic2d: A = -0.75, clamped taps);
 // att: fp32 rows [N][hp * wp][C]; inp / out: NCHW fp32
 __global__ void f32_fsa_combine_kernel(const float* att, int hp, int wp, int C, const float* inp, float* out, int N, int H, int W, const float* gamma) {
+#pragma clang fp contract(off)
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)N * C * H * W) return;
     const int X = (int)(i % W), Y = (int)((i / W) % H), c = (int)((i / ((long)W * H)) % C);
@@ -589,11 +600,11 @@ __global__ void f32_fsa_combine_kernel(const float* att, int hp, int wp, int C, 
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
             const int xx = min(max(ix - 1 + b, 0), wp - 1);
-            row += an[((long)yy * wp + xx) * C] * wx[b];
+            row = fmaf(an[((long)yy * wp + xx) * C], wx[b], row);
         }
-        v += row * wy[a];
+        v = fmaf(row, wy[a], v);
     }
-    out[i] = gamma[0] * v + inp[i];
+    out[i] = fmaf(gamma[0], v, inp[i]);
 }
 
 // The same for W == 4 wp (H / 4 x W / 4 pooling: every PAN frame whose width is a multiple of 4): a thread owns the strip X0 = 4 k + 2 .. 4 k + 5 of one row and channel,
@@ -602,6 +613,7 @@ __global__ void f32_fsa_combine_kernel(const float* att, int hp, int wp, int C, 
 // att here is CHANNEL-major ([N][C][hp * wp], f32_att_transpose_kernel below): the strips of a wave are consecutive k, so a tap's 64 reads are consecutive floats; with the
 // attention kernel's pixel-major rows they were 64 cache lines (160-byte stride) and the kernel sat at 0.76 TB/s.
 __global__ __launch_bounds__(256) void f32_fsa_combine_x4_kernel(const float* att, int hp, int wp, int C, const float* inp, float* out, int N, int H, int W, const float* gamma) {
+#pragma clang fp contract(off)
     const int ns = wp + 1;                                   // strips k = -1 .. wp - 1 of a row
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long)N * C * H * ns) return;
@@ -632,15 +644,15 @@ __global__ __launch_bounds__(256) void f32_fsa_combine_x4_kernel(const float* at
         for (int j = 0; j < 4; ++j) {
             float row = 0.f;
 #pragma unroll
-            for (int b = 0; b < 4; ++b) row += q[b] * wx[j][b];
-            v[j] += row * wy[a];
+            for (int b = 0; b < 4; ++b) row = fmaf(q[b], wx[j][b], row);
+            v[j] = fmaf(row, wy[a], v[j]);
         }
     }
     const float gm = gamma[0];
     const long o = ((n * C + c) * H + Y) * (long)W + X0;
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-        if (X0 + j >= 0 && X0 + j < W) out[o + j] = gm * v[j] + inp[o + j];
+        if (X0 + j >= 0 && X0 + j < W) out[o + j] = fmaf(gm, v[j], inp[o + j]);
 }
 
 // [N][Np][C] -> [N][C][Np] (the attention's rows, 5 MB at 540 x 960) through a 32 x 33 LDS tile

@@ -558,6 +558,60 @@ __global__ __launch_bounds__(256) void pan_fsa_combine_x4(const float* att, int 
     }
 }
 
+// ---- the FSA block's launches: one function each, called by both forwards and by the single-launch entries (innfer_pan_attention / _maxpool / _fsa_combine) ----
+// The attention's forms: 0 pan_attention (VALU, no workspace), 1 pan_attn_prep + pan_attention_mfma<false>, 2 the same pair with <true> (Vl written).
+// Its workspace, per image nblk 32-key blocks: {fh, fl', gh, gl'} rows (64 B per key), h fragments (3 KB per block) and, form 2, their lo parts (3 KB).
+struct AttWs { size_t qk, vt, vl, total; };
+AttWs att_ws(int N, long Np, int form) {
+    AttWs a{};
+    if (form != 1 && form != 2) return a;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t nblk = ((size_t)Np + ATT_KB - 1) / ATT_KB;
+    size_t off = 0;
+    a.qk = off; off += al((size_t)N * nblk * ATT_KB * 64 + 256);
+    a.vt = off; off += al((size_t)N * nblk * 3072 + 256);
+    if (form == 2) { a.vl = off; off += al((size_t)N * nblk * 3072 + 256); }
+    a.total = off;
+    return a;
+}
+
+// fgh: fp32 [N][Np][64] rows; out: fp32 [N][Np][ATT_C]; ws: att_ws(N, Np, form).total bytes (unused by form 0)
+int att_launch(const float* fgh, const float* bf, const float* bg, const float* bh, int N, int Np, int form, float* out, char* ws, hipStream_t s) {
+    if (form == 0) {
+        hipLaunchKernelGGL(pan_attention, dim3((Np + 63) / 64, N), dim3(256), 0, s, fgh, bf, bg, bh, Np, out);
+    } else {
+        const AttWs a = att_ws(N, Np, form);
+        const int nblk = (Np + ATT_KB - 1) / ATT_KB;
+        const long work = (long)nblk * 192 > (long)nblk * ATT_KB ? (long)nblk * 192 : (long)nblk * ATT_KB;
+        f16 *qk = (f16*)(ws + a.qk), *vt = (f16*)(ws + a.vt), *vl = form == 2 ? (f16*)(ws + a.vl) : nullptr;
+        hipLaunchKernelGGL(pan_attn_prep, dim3((unsigned)((work + 255) / 256), N), dim3(256), 0, s, fgh, bf, bg, bh, Np, nblk, qk, vt, vl);
+        if (form == 2) hipLaunchKernelGGL(pan_attention_mfma<true>, dim3((Np + 127) / 128, N), dim3(512), 0, s, (const f16*)qk, (const f16*)vt, (const f16*)vl, Np, nblk, out);
+        else hipLaunchKernelGGL(pan_attention_mfma<false>, dim3((Np + 127) / 128, N), dim3(512), 0, s, (const f16*)qk, (const f16*)vt, (const f16*)nullptr, Np, nblk, out);
+    }
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+// MaxPool2d(4) of a slab of group stride in_g into one of group stride out_g (H / 4 x W / 4 pixels per image)
+int maxpool_launch(const f16* in, long in_g, int C, int N, int H, int W, f16* out, long out_g, hipStream_t s) {
+    const int hp = H / 4, wp = W / 4;
+    const long np = (long)N * hp * wp;
+    hipLaunchKernelGGL(pan_maxpool, dim3((unsigned)((np * ((C + 31) / 32 * 4) + 255) / 256)), dim3(256), 0, s, in, in_g, C, N, H, W, hp, wp, out, out_g);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+// gamma * bicubic(att) + inp on slabs of group stride g: the strip kernel where W == 4 wp (form 0), else -- or with form 1 -- the one-pixel kernel
+int fsa_combine_launch(const float* att, int hp, int wp, int C, const f16* inp, long g, int N, int H, int W, const float* gamma, int form, f16* dst, hipStream_t s) {
+    const long px = (long)N * H * W;
+    if (W == 4 * wp && form == 0)
+        hipLaunchKernelGGL(pan_fsa_combine_x4, dim3((unsigned)(((long)N * H * (wp + 1) * ((C + 31) / 32 * 4) + 255) / 256)), dim3(256), 0, s, att, hp, wp, C, inp, g, N, H, W, gamma, dst);
+    else
+        hipLaunchKernelGGL(pan_fsa_combine, dim3((unsigned)((px * ((C + 31) / 32 * 4) + 255) / 256)), dim3(256), 0, s, att, hp, wp, C, inp, g, N, H, W, gamma, dst);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
 // F.interpolate(t, scale_factor=f, mode) on a blocked slab, f = 2 | 3.  bilinear (align_corners=False, ATen upsample_bilinear2d): source index
 // max(0, (dst + 0.5) / f - 0.5), the second tap clamped to the last pixel, fp32 arithmetic in ATen's association; nearest: source dst / f.
 // One thread per (output pixel, 8 channels) of `groups` 32-channel groups.
@@ -966,7 +1020,7 @@ int upload(innfer_pan* p) {
     return INNFER_OK;
 }
 
-struct PCarve { size_t x0, fea, xa, xb, ab, ab2, k3y, inp, t, pool, fgh, att, aqk, avt, raw, hr[2][3], ups, total, slab_end; };
+struct PCarve { size_t x0, fea, xa, xb, ab, ab2, k3y, inp, t, pool, fgh, att, aws, raw, hr[2][3], ups, total, slab_end; };
 
 PCarve pcarve(const innfer_pan* p, int N, int H, int W) {
     PCarve c{};
@@ -984,11 +1038,7 @@ PCarve pcarve(const innfer_pan* p, int N, int H, int W) {
     c.slab_end = off;
     c.fgh = off; off += al((np ? np : 1) * 64 * 4);
     c.att = off; off += al((np ? np : 1) * p->nf * 4);
-    {   // MFMA attention: per image nblk 32-key blocks of {fh, fl', gh, gl'} rows (64 B per key) and of h fragments (3 KB per block)
-        const size_t nblk = ((size_t)hp * wp + 31) / 32;
-        c.aqk = off; off += al((size_t)N * nblk * 32 * 64 + 256);
-        c.avt = off; off += al((size_t)N * nblk * 3072 + 256);
-    }
+    c.aws = off; off += att_ws(N, (long)(hp * wp), 1).total;          // MFMA attention (att_launch form 1)
     c.raw = off; off += al(px * m * (size_t)p->out_nc * 4);          // planar fp32 output of conv_last (every other conv writes fp16 slabs)
     c.total = off;
     return c;
@@ -998,7 +1048,7 @@ PCarve pcarve(const innfer_pan* p, int N, int H, int W) {
 
 namespace {
 // ---- the fp32 mode: PAN.forward on NCHW fp32 tensors with the generic fp32 ops (f32ops.hip); graph = oracle/nets.py pan_forward = PAN_arch.py:178-222 ----
-struct PCarve32 { size_t fea, xa, xb, ab, cat, k3y, yv, inp, t, pool, fgh, att, aqk, avt, avl, hr[2][3], ups, raw, total; };
+struct PCarve32 { size_t fea, xa, xb, ab, cat, k3y, yv, inp, t, pool, fgh, att, aws, hr[2][3], ups, raw, total; };
 PCarve32 pcarve32(const innfer_pan* p, int N, int H, int W) {
     PCarve32 c{};
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -1007,10 +1057,7 @@ PCarve32 pcarve32(const innfer_pan* p, int N, int H, int W) {
     auto buf = [&](size_t floats) { size_t o = off; off += al(floats * 4); return o; };
     c.fea = buf(px * nf); c.xa = buf(px * nf); c.xb = buf(px * nf); c.ab = buf(px * nf); c.cat = buf(px * nf); c.k3y = buf(px * gw); c.yv = buf(px * gw);
     c.inp = buf(px * nf); c.t = buf(px * nf); c.pool = buf((np ? np : 1) * nf); c.fgh = buf((np ? np : 1) * 64); c.att = buf((np ? np : 1) * nf);
-    {   // the attention on the matrix cores (pan_attention_mfma<true>): per image nblk 32-key blocks of {fh, fl', gh, gl'} rows (64 B per key) and of h fragments (3 KB hi + 3 KB lo)
-        const size_t nblk = (hp * wp + 31) / 32;
-        c.aqk = buf((size_t)N * nblk * 32 * 16 + 64); c.avt = buf((size_t)N * nblk * 768 + 64); c.avl = buf((size_t)N * nblk * 768 + 64);
-    }
+    c.aws = off; off += att_ws(N, (long)(hp * wp), 2).total;          // the attention on the matrix cores (pan_attention_mfma<true>: att_launch form 2)
     size_t m = 1, ups = 0;
     for (int u = 0; u < p->n_up; ++u) {
         const size_t cin = u == 0 ? nf : UF;
@@ -1098,18 +1145,12 @@ int pan_forward_f32(innfer_pan* p, const float* x, float* y, int N, int H, int W
             CK(f32conv_launch(c, s));
         }
         if (p->mfma_attention && nf == ATT_C) {      // softmax(f^T g) h on the matrix cores with (hi, lo) fp16 pairs of f, g, p and h (pan_attention_mfma<true>)
-            const int nblk = (Np + ATT_KB - 1) / ATT_KB;
             GtScope gt(s, "pan_attention_mfma, fp32 mode (+ prep)", 2.0 * N * (double)Np * Np * (2 * 5 + 40), (double)N * Np * (64.0 + nf) * 4.0);
-            const long work = (long)nblk * 192 > (long)nblk * ATT_KB ? (long)nblk * 192 : (long)nblk * ATT_KB;
-            hipLaunchKernelGGL(pan_attn_prep, dim3((unsigned)((work + 255) / 256), N), dim3(256), 0, s, (const float*)FGH, vec("FSA.conv_f.bias"), vec("FSA.conv_g.bias"),
-                               vec("FSA.conv_h.bias"), Np, nblk, (f16*)(ws + cv.aqk), (f16*)(ws + cv.avt), (f16*)(ws + cv.avl));
-            hipLaunchKernelGGL(pan_attention_mfma<true>, dim3((Np + 127) / 128, N), dim3(512), 0, s, (const f16*)(ws + cv.aqk), (const f16*)(ws + cv.avt), (const f16*)(ws + cv.avl),
-                               Np, nblk, ATT);
+            CK(att_launch(FGH, vec("FSA.conv_f.bias"), vec("FSA.conv_g.bias"), vec("FSA.conv_h.bias"), N, Np, 2, ATT, ws + cv.aws, s));
         } else {
             GtScope gt(s, "pan_attention (fp32 VALU)", 2.0 * N * (double)Np * Np * (2 * 5 + 40), (double)N * Np * (64.0 + nf) * 4.0);
-            hipLaunchKernelGGL(pan_attention, dim3((Np + 63) / 64, N), dim3(256), 0, s, (const float*)FGH, vec("FSA.conv_f.bias"), vec("FSA.conv_g.bias"), vec("FSA.conv_h.bias"), Np, ATT);
+            CK(att_launch(FGH, vec("FSA.conv_f.bias"), vec("FSA.conv_g.bias"), vec("FSA.conv_h.bias"), N, Np, 0, ATT, nullptr, s));
         }
-        INNFER_HIP(hipGetLastError());
         { GtScope gt(s, "f32 fsa_combine (bicubic + gamma * out + in)", 0.0, (double)N * nf * hw * 8.0); CK(f32_fsa_combine_launch(ATT, hp, wp, nf, INP, T, N, H, W, vec("FSA.gamma"), s, FGH)); }      // (FGH: dead behind the attention, 64 >= nf floats per pooled pixel)
         cur = T;
     }
@@ -1388,34 +1429,20 @@ extern "C" int innfer_pan_forward(innfer_pan* p, const void* d_in, int in_dtype,
         const int hp = H / 4, wp = W / 4;
         const long np = (long)N * hp * wp, Gp = np * 32;
         {   GtScope gt(s, "pan_maxpool", 0.0, (double)px * nf * 2.0 + (double)np * 128.0);
-            hipLaunchKernelGGL(pan_maxpool, dim3((unsigned)((np * ((nf + 31) / 32 * 4) + 255) / 256)), dim3(256), 0, s, INP, G, nf, N, H, W, hp, wp, POOL, Gp);
-            INNFER_HIP(hipGetLastError()); }
+            CK(maxpool_launch(INP, G, nf, N, H, W, POOL, Gp, s)); }
         float* save = raw;
         raw = (float*)(ws + cv.fgh);
         CK(gemm(POOL, Gp, hp, wp, hp, wp, 0, true));                                  // [f | g | h], 64-float rows for pan_attention
         raw = save;
+        const int Np = hp * wp;
         if (p->mfma_attention && nf == ATT_C) {   // softmax(f^T g) h on the matrix cores: Np^2 (5 + 40) multiply-adds per image (the scores twice: max pass, accumulate pass)
-            const int Np = hp * wp, nblk = (Np + ATT_KB - 1) / ATT_KB;
             GtScope gt(s, "pan_attention_mfma (+ prep)", 2.0 * N * (double)Np * Np * (2 * 5 + 40), (double)np * (64.0 + nf) * 4.0);
-            const long work = (long)nblk * 192 > (long)nblk * ATT_KB ? (long)nblk * 192 : (long)nblk * ATT_KB;
-            hipLaunchKernelGGL(pan_attn_prep, dim3((unsigned)((work + 255) / 256), N), dim3(256), 0, s, (const float*)(ws + cv.fgh), vec("FSA.conv_f.bias"),
-                               vec("FSA.conv_g.bias"), vec("FSA.conv_h.bias"), Np, nblk, (f16*)(ws + cv.aqk), (f16*)(ws + cv.avt), (f16*)nullptr);
-            hipLaunchKernelGGL(pan_attention_mfma<false>, dim3((Np + 127) / 128, N), dim3(512), 0, s, (const f16*)(ws + cv.aqk), (const f16*)(ws + cv.avt), (const f16*)nullptr, Np, nblk,
-                               (float*)(ws + cv.att));
-            INNFER_HIP(hipGetLastError());
+            CK(att_launch((const float*)(ws + cv.fgh), vec("FSA.conv_f.bias"), vec("FSA.conv_g.bias"), vec("FSA.conv_h.bias"), N, Np, 1, (float*)(ws + cv.att), ws + cv.aws, s));
         } else {
-            GtScope gt(s, "pan_attention", 2.0 * N * (double)(hp * wp) * (hp * wp) * (2 * 5 + 40), (double)np * (64.0 + nf) * 4.0);
-            hipLaunchKernelGGL(pan_attention, dim3((hp * wp + 63) / 64, N), dim3(256), 0, s, (const float*)(ws + cv.fgh), vec("FSA.conv_f.bias"),
-                               vec("FSA.conv_g.bias"), vec("FSA.conv_h.bias"), hp * wp, (float*)(ws + cv.att));
-            INNFER_HIP(hipGetLastError()); }
+            GtScope gt(s, "pan_attention", 2.0 * N * (double)Np * Np * (2 * 5 + 40), (double)np * (64.0 + nf) * 4.0);
+            CK(att_launch((const float*)(ws + cv.fgh), vec("FSA.conv_f.bias"), vec("FSA.conv_g.bias"), vec("FSA.conv_h.bias"), N, Np, 0, (float*)(ws + cv.att), nullptr, s)); }
         {   GtScope gt(s, "pan_fsa_combine (bicubic + gamma * out + in)", 0.0, (double)px * nf * 4.0 + (double)np * nf * 4.0);
-            if (W == 4 * wp)
-                hipLaunchKernelGGL(pan_fsa_combine_x4, dim3((unsigned)(((long)N * H * (wp + 1) * ((nf + 31) / 32 * 4) + 255) / 256)), dim3(256), 0, s, (const float*)(ws + cv.att), hp, wp, nf,
-                                   INP, G, N, H, W, vec("FSA.gamma"), T);
-            else
-            hipLaunchKernelGGL(pan_fsa_combine, dim3((unsigned)((px * ((nf + 31) / 32 * 4) + 255) / 256)), dim3(256), 0, s, (const float*)(ws + cv.att), hp, wp, nf,
-                               INP, G, N, H, W, vec("FSA.gamma"), T);
-            INNFER_HIP(hipGetLastError()); }
+            CK(fsa_combine_launch((const float*)(ws + cv.att), hp, wp, nf, INP, G, N, H, W, vec("FSA.gamma"), 0, T, s)); }
     }
     const f16* cur = p->self_attention ? T : INP;
     long cur_g = G;
@@ -1472,4 +1499,41 @@ extern "C" int innfer_pan_forward(innfer_pan* p, const void* d_in, int in_dtype,
     }
 #undef CK
     return INNFER_OK;
+}
+
+// ---- the FSA block's launches one at a time, for tests (include/innfer_amd.h): the launch functions above, as the forwards call them ----
+extern "C" size_t innfer_pan_attention_workspace_bytes(int N, int Np, int form) {
+    if (N < 1 || Np < 1) return 0;
+    return att_ws(N, Np, form).total;
+}
+
+extern "C" int innfer_pan_attention(const float* d_fgh, const float* d_bf, const float* d_bg, const float* d_bh, int N, int Np, int form, float* d_out,
+                                    void* d_ws, size_t ws_bytes, void* stream) {
+    if (!d_fgh || !d_bf || !d_bg || !d_bh || !d_out) return set_error(INNFER_ERR_INVALID, "pan_attention: null argument");
+    if (form < 0 || form > 2) return set_error(INNFER_ERR_INVALID, "pan_attention: form %d (0 VALU, 1 MFMA, 2 MFMA on (hi, lo) pairs)", form);
+    if (N < 1 || N > 65535 || Np < 1) return set_error(INNFER_ERR_INVALID, "pan_attention: N = %d (1 .. 65535), Np = %d (>= 1)", N, Np);
+    const size_t need = att_ws(N, Np, form).total;
+    if (need && (!d_ws || ws_bytes < need)) return set_error(INNFER_ERR_WORKSPACE, "pan_attention: workspace %zu < %zu bytes", d_ws ? ws_bytes : (size_t)0, need);
+    return att_launch(d_fgh, d_bf, d_bg, d_bh, N, Np, form, d_out, (char*)d_ws, (hipStream_t)stream);
+}
+
+extern "C" int innfer_pan_maxpool(const void* d_in, int dtype, int N, int C, int H, int W, void* d_out, void* stream) {
+    if (!d_in || !d_out) return set_error(INNFER_ERR_INVALID, "pan_maxpool: null argument");
+    if (N < 1 || C < 1 || H < 4 || W < 4) return set_error(INNFER_ERR_INVALID, "pan_maxpool: N = %d, C = %d, %d x %d: at least one 4 x 4 window (MaxPool2d(4))", N, C, H, W);
+    if (dtype == INNFER_F32) return f32_maxpool4_launch((const float*)d_in, (float*)d_out, (long)N * C, H, W, (hipStream_t)stream);
+    if (dtype != INNFER_F16) return set_error(INNFER_ERR_INVALID, "pan_maxpool: dtype %d (fp16 slabs or fp32 NCHW)", dtype);
+    if (C % 8) return set_error(INNFER_ERR_INVALID, "pan_maxpool: the slab form takes C %% 8 == 0, not %d", C);
+    return maxpool_launch((const f16*)d_in, (long)N * H * W * 32, C, N, H, W, (f16*)d_out, (long)N * (H / 4) * (W / 4) * 32, (hipStream_t)stream);
+}
+
+extern "C" int innfer_pan_fsa_combine(const float* d_att, int hp, int wp, int C, const void* d_inp, int dtype, int N, int H, int W, const float* d_gamma, int form,
+                                      void* d_out, float* d_scratch, void* stream) {
+    if (!d_att || !d_inp || !d_gamma || !d_out) return set_error(INNFER_ERR_INVALID, "pan_fsa_combine: null argument");
+    if (N < 1 || C < 1 || hp < 1 || wp < 1 || H < 1 || W < 1 || (form != 0 && form != 1))
+        return set_error(INNFER_ERR_INVALID, "pan_fsa_combine: N = %d, C = %d, att %d x %d, out %d x %d, form %d", N, C, hp, wp, H, W, form);
+    if (dtype == INNFER_F32)
+        return f32_fsa_combine_launch(d_att, hp, wp, C, (const float*)d_inp, (float*)d_out, N, H, W, d_gamma, (hipStream_t)stream, form == 1 ? nullptr : d_scratch);
+    if (dtype != INNFER_F16) return set_error(INNFER_ERR_INVALID, "pan_fsa_combine: dtype %d (fp16 slabs or fp32 NCHW)", dtype);
+    if (C % 8) return set_error(INNFER_ERR_INVALID, "pan_fsa_combine: the slab form takes C %% 8 == 0, not %d", C);
+    return fsa_combine_launch(d_att, hp, wp, C, (const f16*)d_inp, (long)N * H * W * 32, N, H, W, d_gamma, form, (f16*)d_out, (hipStream_t)stream);
 }

@@ -272,6 +272,10 @@ SIGNATURES = {
     "innfer_pack_gather_gemm": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "innfer_gather_gemm": (C.c_int, [C.POINTER(GatherGemmArgs), C.POINTER(C.c_int), C.c_void_p]),
     "innfer_gather_gemm_plan": (C.c_int, [C.POINTER(GatherGemmArgs), C.POINTER(C.c_int)]),
+    "innfer_pan_attention_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "innfer_pan_attention": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "innfer_pan_maxpool": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "innfer_pan_fsa_combine": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "innfer_conv_stats_records": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "innfer_norm_combine_parts": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "innfer_norm_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
