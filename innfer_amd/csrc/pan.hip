@@ -1537,3 +1537,41 @@ extern "C" int innfer_pan_fsa_combine(const float* d_att, int hp, int wp, int C,
     if (C % 8) return set_error(INNFER_ERR_INVALID, "pan_fsa_combine: the slab form takes C %% 8 == 0, not %d", C);
     return fsa_combine_launch(d_att, hp, wp, C, (const f16*)d_inp, (long)N * H * W * 32, N, H, W, d_gamma, form, (f16*)d_out, (hipStream_t)stream);
 }
+
+// ---- one SCPA block as a single launch, for tests (include/innfer_amd.h): pan_scpa_launch / pan_scpa_split_launch exactly as the forwards call them ----
+extern "C" size_t innfer_pan_scpa_blob_bytes(int split) { return split ? pan_scpa_split_blob_bytes() : pan_scpa_blob_bytes(); }
+
+extern "C" int innfer_pack_pan_scpa(const float* c1a, const float* c1b, const float* k1, const float* k2, const float* k2_bias, const float* k3, const float* k4,
+                                    const float* c3, int split, void* h_blob) {
+    if (!c1a || !c1b || !k1 || !k2 || !k2_bias || !k3 || !k4 || !c3 || !h_blob) return set_error(INNFER_ERR_INVALID, "pack_pan_scpa: null argument");
+    if (split) pan_scpa_split_pack(c1a, c1b, k1, k2, k2_bias, k3, k4, c3, h_blob);
+    else pan_scpa_pack(c1a, c1b, k1, k2, k2_bias, k3, k4, c3, h_blob);
+    return INNFER_OK;
+}
+
+extern "C" int innfer_pan_scpa_block(const void* d_in, void* d_out, int64_t group_stride, const void* d_blob, int N, int H, int W, int form, int in_c8, int out_c8,
+                                     void* stream) {
+    if (!d_in || !d_out || !d_blob) return set_error(INNFER_ERR_INVALID, "pan_scpa_block: null argument");
+    if (N < 1 || H < 1 || W < 1) return set_error(INNFER_ERR_INVALID, "pan_scpa_block: N = %d, %d x %d", N, H, W);
+    if (form < -1 || form > 2) return set_error(INNFER_ERR_INVALID, "pan_scpa_block: form %d (0 one 8-wave workgroup, 1 two 4-wave workgroups, -1 the forward's choice, 2 split operands)", form);
+    if (form == 2) {
+        if (group_stride != 0 || in_c8 || out_c8) return set_error(INNFER_ERR_INVALID, "pan_scpa_block: the split form takes split planes (group_stride 0, no compact plane)");
+        return pan_scpa_split_launch(d_in, d_out, d_blob, N, H, W, (hipStream_t)stream);
+    }
+    if (group_stride < (int64_t)N * H * W * 32) return set_error(INNFER_ERR_INVALID, "pan_scpa_block: group stride %lld < N H W 32", (long long)group_stride);
+    return pan_scpa_launch((const f16*)d_in, (f16*)d_out, (long)group_stride, d_blob, N, H, W, (hipStream_t)stream, in_c8 ? 1 : 0, out_c8 ? 1 : 0, form);
+}
+
+extern "C" int innfer_pan_split_from_nchw(const float* d_x, void* d_planes, int N, int H, int W, void* stream) {
+    if (!d_x || !d_planes) return set_error(INNFER_ERR_INVALID, "pan_split_from_nchw: null argument");
+    if (N < 1 || H < 1 || W < 1) return set_error(INNFER_ERR_INVALID, "pan_split_from_nchw: N = %d, %d x %d", N, H, W);
+    if (!pan_scpa_split_ok(N, H, W)) return set_error(INNFER_ERR_UNSUPPORTED, "pan_split_from_nchw: tensor too large for 32-bit offsets");
+    return pan_split_from_nchw(d_x, d_planes, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int innfer_pan_split_to_nchw(const void* d_planes, float* d_x, int N, int H, int W, void* stream) {
+    if (!d_x || !d_planes) return set_error(INNFER_ERR_INVALID, "pan_split_to_nchw: null argument");
+    if (N < 1 || H < 1 || W < 1) return set_error(INNFER_ERR_INVALID, "pan_split_to_nchw: N = %d, %d x %d", N, H, W);
+    if (!pan_scpa_split_ok(N, H, W)) return set_error(INNFER_ERR_UNSUPPORTED, "pan_split_to_nchw: tensor too large for 32-bit offsets");
+    return pan_split_to_nchw(d_planes, d_x, N, H, W, (hipStream_t)stream);
+}

@@ -276,6 +276,11 @@ SIGNATURES = {
     "innfer_pan_attention": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "innfer_pan_maxpool": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "innfer_pan_fsa_combine": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "innfer_pan_scpa_blob_bytes": (C.c_size_t, [C.c_int]),
+    "innfer_pack_pan_scpa": (C.c_int, [C.c_void_p] * 8 + [C.c_int, C.c_void_p]),
+    "innfer_pan_scpa_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "innfer_pan_split_from_nchw": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "innfer_pan_split_to_nchw": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
     "innfer_conv_stats_records": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "innfer_norm_combine_parts": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "innfer_norm_stats": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
