@@ -45,8 +45,8 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  innfer_version() returns the library's; a binding should compare. */
-#define INNFER_ABI_VERSION 122
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  innfer_version() returns the library's; a binding should compare. */
+#define INNFER_ABI_VERSION 123
 int innfer_version(void);
 const char* innfer_last_error(void);
 
@@ -607,6 +607,49 @@ int innfer_resnet_post_slab_parts(const void* d_src, int64_t gs, int C, int64_t 
                                   int relu, const void* d_res, void* d_dst, void* stream);
 int innfer_unet_post_slab_parts(const void* d_src, int64_t src_gs, int C, int64_t HW, int N, const float* d_part, int nper, const float* d_gamma, const float* d_beta,
                                 void* d_dst0, int64_t dst0_gs, int dst0_coff, int act0, void* d_dst1, int64_t dst1_gs, int dst1_coff, int act1, void* stream);
+
+/* (123) The pass kernels that carry the pix2pix UNet (csrc/unet.hip) and the CycleGAN ResNet (csrc/resnet.hip) from one conv to the next, as single launches, for tests.
+ * Every entry checks its arguments and then calls the launcher the network calls (grid, block and instantiation are the network's); on a refusal (INNFER_ERR_INVALID /
+ * INNFER_ERR_UNSUPPORTED, innfer_last_error says why) nothing is launched.  All pointers are device pointers but h_w / h_packed.  Slabs are blocked-NHWC fp16 with
+ * 32-channel groups `gs` elements apart (gs >= pixels * 32); a destination view is (pointer, group stride, channel offset % 8 == 0, act 1 LeakyReLU(0.2) | 2 ReLU).
+ * innfer_unet_pre: NCHW (in_dtype INNFER_F16 | INNFER_F32) -> one zero-padded group (patch 0; C <= 32), or -> the 64-channel patch slab of the 4x4 stride-2 window at
+ *   half resolution, channel (ky * 4 + kx) * C + c, zero outside the image (patch 1; 16 * C <= 64, H and W even, gs = group stride of the two groups).
+ * innfer_unet_post / innfer_unet_post_slab: fp32 rows [N * HW][cpad] / an fp16 slab -> act(x * alpha + shift) into one or two views (d_dst1 may be NULL); alpha / shift
+ *   [N][C] (nstride = C) or [C] (nstride = 0); innfer_unet_post takes d_alpha = d_shift = NULL for act(x).  C % 8 == 0, cpad % 4 == 0.
+ * innfer_unet_deep_post: d_part = ks segments, split_elems floats apart, of fp32 rows [N * HW][cpad]; their sum in segment order -> train-mode BatchNorm of each image
+ *   (d_gamma, d_beta; eps 1e-5) | y = x * ev_alpha + ev_shift | x -> one or two views.  HW <= 256 (INNFER_ERR_UNSUPPORTED beyond); the kernel instantiation follows HW.
+ * innfer_unet_final / innfer_resnet_final: tanh(raw[.., c] + bias[c]) -> NCHW (out_dtype INNFER_F16 | INNFER_F32); rows of cpad / rs >= C floats.
+ * innfer_pack_unet_first: h_w [64][C][4][4] -> the 8192-byte panel (innfer_unet_first_packed_bytes) of innfer_unet_first_conv: Conv2d(C, 64, 4, 2, 1) [+ bias] straight
+ *   from the NCHW input; d_dst0 = LeakyReLU(0.2), d_dst1 (may be NULL) = ReLU, two-group slabs at half resolution.  16 * C <= 64, H and W even, (W / 2) % 16 == 0
+ *   (INNFER_ERR_UNSUPPORTED otherwise: the kernel walks 16-pixel segments), C * H * W < 2^31 - 1.
+ * innfer_resnet_pre: NCHW -> one zero-padded group (patch 0) or the row-patch slab, channel kx * C + c = in[c][y][reflect(x + kx - 3)] (patch 1; 7 * C <= 32, H, W >= 4).
+ * innfer_resnet_post / innfer_resnet_post_slab: [relu](x * alpha + shift) [+ d_res]; alpha / shift [N][C]; source fp32 rows / a slab of the destination's group stride
+ *   (d_dst may be d_src for the slab form).  C % 8 == 0.
+ * innfer_resnet_post_slab_pad: the same (no residual) into the (H + 8) x (W + 8) slab of ReflectionPad2d(3) plus one ring of zeros, image at (4, 4): the zero-ring
+ *   launch and the pass, as the network issues them.  C % 32 == 0, H, W >= 4.
+ * innfer_resnet_sum9_tanh: Q planar fp32 [N][9 K][H + 8][W + 8] -> out[n][k][y][x] = tanh(bias[k] + sum over (sr, sc) of Q[n][9 k + 3 sr + sc][y + 3 sr + 1][x + 3 sc + 1]). */
+int innfer_unet_pre(const void* d_in, int in_dtype, int C, int H, int W, int N, void* d_slab, int64_t gs, int patch, void* stream);
+int innfer_unet_post(const float* d_raw, int cpad, int C, int64_t HW, int N, const float* d_alpha, const float* d_shift, int nstride,
+                     void* d_dst0, int64_t dst0_gs, int dst0_coff, int act0, void* d_dst1, int64_t dst1_gs, int dst1_coff, int act1, void* stream);
+int innfer_unet_post_slab(const void* d_src, int64_t src_gs, int C, int64_t HW, int N, const float* d_alpha, const float* d_shift, int nstride,
+                          void* d_dst0, int64_t dst0_gs, int dst0_coff, int act0, void* d_dst1, int64_t dst1_gs, int dst1_coff, int act1, void* stream);
+int innfer_unet_deep_post(const float* d_part, int64_t split_elems, int ks, int cpad, int C, int HW, int N, const float* d_gamma, const float* d_beta,
+                          const float* d_ev_alpha, const float* d_ev_shift, void* d_dst0, int64_t dst0_gs, int dst0_coff, int act0,
+                          void* d_dst1, int64_t dst1_gs, int dst1_coff, int act1, void* stream);
+int innfer_unet_final(const float* d_raw, int cpad, int C, int64_t HW, int N, const float* d_bias, void* d_out, int out_dtype, void* stream);
+size_t innfer_unet_first_packed_bytes(void);
+int innfer_pack_unet_first(const float* h_w, int C, void* h_packed);
+int innfer_unet_first_conv(const void* d_in, int in_dtype, int C, int H, int W, int N, const void* d_packed, const float* d_bias, void* d_dst0, void* d_dst1, int64_t gs,
+                           void* stream);
+int innfer_resnet_pre(const void* d_in, int in_dtype, int C, int H, int W, int N, void* d_slab, int patch, void* stream);
+int innfer_resnet_post(const float* d_raw, int cpad, int C, int64_t HW, int N, const float* d_alpha, const float* d_shift, int relu, const void* d_res, void* d_dst,
+                       int64_t gs, void* stream);
+int innfer_resnet_post_slab(const void* d_src, int C, int64_t HW, int N, const float* d_alpha, const float* d_shift, int relu, const void* d_res, void* d_dst, int64_t gs,
+                            void* stream);
+int innfer_resnet_post_slab_pad(const void* d_src, int64_t src_gs, int C, int H, int W, int N, const float* d_alpha, const float* d_shift, int relu, void* d_dst,
+                                int64_t dst_gs, void* stream);
+int innfer_resnet_sum9_tanh(const float* d_q, const float* d_bias, void* d_out, int out_dtype, int K, int H, int W, int N, void* stream);
+int innfer_resnet_final(const float* d_raw, int rs, int C, int64_t HW, int N, const float* d_bias, void* d_out, int out_dtype, void* stream);
 
 /* (122) The gather GEMM (csrc/gather_gemm.h gg::gemm_gather: the second conv engine -- the pix2pix UNet's deep levels, every conv of the CycleGAN ResNet, the WBC UNet,
  * PPON's fallback dilated convs and c2, PAN's attention projections) as a single launch, for tests.  The struct carries what gg::launch takes, and the entry runs the

@@ -284,6 +284,51 @@ __global__ void rn_final(const float* raw, int rs, int C, long HW, int N, const 
     }
 }
 
+// ---- the launches of the pass kernels above as the network makes them: shared by innfer_resnet_forward and by the single-launch entry points of ABI 123
+// ---- (innfer_resnet_pre .. innfer_resnet_sum9_tanh), so a test of a kernel runs the network's launch
+int launch_rn_post(const float* raw, int cpad, int C, long HW, int N, const float* alpha, const float* shift, int relu, const f16* res, f16* dst, long g, hipStream_t s) {
+    const long total = (long)N * HW * (C / 8);
+    hipLaunchKernelGGL(rn_post, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, raw, cpad, C, HW, N, alpha, shift, relu, res, dst, g);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int launch_rn_post_slab(const f16* src, int C, long HW, int N, const float* alpha, const float* shift, int relu, const f16* res, f16* dst, long g, hipStream_t s) {
+    const long total = (long)N * HW * (C / 8);
+    hipLaunchKernelGGL(rn_post_slab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, C, HW, N, alpha, shift, relu, res, dst, g);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+// norm + [ReLU] into the reflection-padded (H + 8) x (W + 8) slab the sub-block form of the last conv reads: the outer ring of zeros, then the image and its mirrors
+int launch_rn_post_slab_pad(const f16* src, int C, int H, int W, int N, const float* alpha, const float* shift, int relu, f16* dst, long gsrc, long gdst, hipStream_t s) {
+    const long total = (long)N * H * W * (C / 8);
+    const long ring = (long)N * (C / 32) * (2 * (W + 8) + 2 * (H + 6)) * 4;
+    hipLaunchKernelGGL(rn_zero_ring, dim3((unsigned)((ring + 255) / 256)), dim3(256), 0, s, dst, C / 32, H, W, N, gdst);
+    hipLaunchKernelGGL(rn_post_slab_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, C, H, W, N, alpha, shift, relu, dst, gsrc, gdst);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int launch_rn_sum9_tanh(const float* Q, const float* bias, void* out, int out_f32, int K, int H, int W, int N, hipStream_t s) {
+    const long total = (long)N * K * H * W;
+    hipLaunchKernelGGL(rn_sum9_tanh, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, Q, bias, out, out_f32, K, H, W, N);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int launch_rn_pre(const void* in, int in_f32, int C, int H, int W, int N, f16* slab, int patch, hipStream_t s) {
+    hipLaunchKernelGGL(rn_pre, dim3((unsigned)(((long)N * H * W + 255) / 256)), dim3(256), 0, s, in, in_f32, C, H, W, N, slab, patch);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int launch_rn_final(const float* raw, int rs, int C, long HW, int N, const float* bias, void* out, int out_f32, hipStream_t s) {
+    hipLaunchKernelGGL(rn_final, dim3((unsigned)(((long)N * HW + 255) / 256)), dim3(256), 0, s, raw, rs, C, HW, N, bias, out, out_f32);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
 struct Param { std::string key; std::vector<int> shape; std::vector<float> host; bool set = false; };
 struct Layer { int w = -1, b = -1, cin = 0, cout = 0, k = 3; bool transposed = false; std::vector<f16*> d_w; float* d_b = nullptr;
                void* d_w3 = nullptr;
@@ -336,6 +381,53 @@ extern "C" int innfer_resnet_post_slab_parts(const void* d_src, int64_t gs, int 
         return set_error(INNFER_ERR_INVALID, "resnet_post_slab_parts: null argument, C=%d (%% 32), HW=%lld, N=%d, nper=%d or group stride %lld < N * HW * 32", C, (long long)HW, N, nper,
                          (long long)gs);
     return launch_rn_post_slab_parts((const f16*)d_src, C, (long)HW, N, d_part, nper, d_gamma, d_beta, relu ? 1 : 0, (const f16*)d_res, (f16*)d_dst, (long)gs, (hipStream_t)stream);
+}
+
+// ---- (123) the pass kernels as single launches, for tests: argument checks, then the launcher innfer_resnet_forward uses; nothing is launched on refusal --------
+extern "C" int innfer_resnet_pre(const void* d_in, int in_dtype, int C, int H, int W, int N, void* d_slab, int patch, void* stream) {
+    if (!d_in || !d_slab || (in_dtype != INNFER_F16 && in_dtype != INNFER_F32) || C <= 0 || H <= 0 || W <= 0 || N <= 0)
+        return set_error(INNFER_ERR_INVALID, "resnet_pre: null argument, dtype %d, C=%d, %d x %d, N=%d", in_dtype, C, H, W, N);
+    if (patch && 7 * C > 32) return set_error(INNFER_ERR_UNSUPPORTED, "resnet_pre: the row-patch slab holds 7 * C <= 32 values (C=%d)", C);
+    if (patch && (H < 4 || W < 4)) return set_error(INNFER_ERR_INVALID, "resnet_pre: ReflectionPad2d(3) needs at least 4 x 4 (%d x %d)", H, W);
+    if (C > 32) return set_error(INNFER_ERR_UNSUPPORTED, "resnet_pre: one 32-channel group (C=%d)", C);
+    return launch_rn_pre(d_in, in_dtype == INNFER_F32, C, H, W, N, (f16*)d_slab, patch ? 1 : 0, (hipStream_t)stream);
+}
+
+extern "C" int innfer_resnet_post(const float* d_raw, int cpad, int C, int64_t HW, int N, const float* d_alpha, const float* d_shift, int relu, const void* d_res,
+                                  void* d_dst, int64_t gs, void* stream) {
+    if (!d_raw || !d_alpha || !d_shift || !d_dst || C <= 0 || C % 8 || cpad < C || cpad % 4 || HW <= 0 || N <= 0 || gs < (int64_t)N * HW * 32)
+        return set_error(INNFER_ERR_INVALID, "resnet_post: null argument, C=%d (%% 8), cpad=%d, HW=%lld, N=%d or group stride %lld < N * HW * 32", C, cpad, (long long)HW, N,
+                         (long long)gs);
+    return launch_rn_post(d_raw, cpad, C, (long)HW, N, d_alpha, d_shift, relu ? 1 : 0, (const f16*)d_res, (f16*)d_dst, (long)gs, (hipStream_t)stream);
+}
+
+extern "C" int innfer_resnet_post_slab(const void* d_src, int C, int64_t HW, int N, const float* d_alpha, const float* d_shift, int relu, const void* d_res,
+                                       void* d_dst, int64_t gs, void* stream) {
+    if (!d_src || !d_alpha || !d_shift || !d_dst || C <= 0 || C % 8 || HW <= 0 || N <= 0 || gs < (int64_t)N * HW * 32)
+        return set_error(INNFER_ERR_INVALID, "resnet_post_slab: null argument, C=%d (%% 8), HW=%lld, N=%d or group stride %lld < N * HW * 32", C, (long long)HW, N, (long long)gs);
+    return launch_rn_post_slab((const f16*)d_src, C, (long)HW, N, d_alpha, d_shift, relu ? 1 : 0, (const f16*)d_res, (f16*)d_dst, (long)gs, (hipStream_t)stream);
+}
+
+extern "C" int innfer_resnet_post_slab_pad(const void* d_src, int64_t src_gs, int C, int H, int W, int N, const float* d_alpha, const float* d_shift, int relu,
+                                           void* d_dst, int64_t dst_gs, void* stream) {
+    if (!d_src || !d_alpha || !d_shift || !d_dst || C <= 0 || C % 32 || H <= 0 || W <= 0 || N <= 0 || src_gs < (int64_t)N * H * W * 32 ||
+        dst_gs < (int64_t)N * (H + 8) * (W + 8) * 32)
+        return set_error(INNFER_ERR_INVALID, "resnet_post_slab_pad: null argument, C=%d (%% 32), %d x %d, N=%d, source group stride %lld < N * H * W * 32 or destination "
+                         "group stride %lld < N * (H + 8) * (W + 8) * 32", C, H, W, N, (long long)src_gs, (long long)dst_gs);
+    if (H < 4 || W < 4) return set_error(INNFER_ERR_INVALID, "resnet_post_slab_pad: ReflectionPad2d(3) needs at least 4 x 4 (%d x %d)", H, W);
+    return launch_rn_post_slab_pad((const f16*)d_src, C, H, W, N, d_alpha, d_shift, relu ? 1 : 0, (f16*)d_dst, (long)src_gs, (long)dst_gs, (hipStream_t)stream);
+}
+
+extern "C" int innfer_resnet_sum9_tanh(const float* d_q, const float* d_bias, void* d_out, int out_dtype, int K, int H, int W, int N, void* stream) {
+    if (!d_q || !d_bias || !d_out || (out_dtype != INNFER_F16 && out_dtype != INNFER_F32) || K <= 0 || H <= 0 || W <= 0 || N <= 0)
+        return set_error(INNFER_ERR_INVALID, "resnet_sum9_tanh: null argument, dtype %d, K=%d, %d x %d, N=%d", out_dtype, K, H, W, N);
+    return launch_rn_sum9_tanh(d_q, d_bias, d_out, out_dtype == INNFER_F32, K, H, W, N, (hipStream_t)stream);
+}
+
+extern "C" int innfer_resnet_final(const float* d_raw, int rs, int C, int64_t HW, int N, const float* d_bias, void* d_out, int out_dtype, void* stream) {
+    if (!d_raw || !d_bias || !d_out || (out_dtype != INNFER_F16 && out_dtype != INNFER_F32) || C <= 0 || rs < C || HW <= 0 || N <= 0)
+        return set_error(INNFER_ERR_INVALID, "resnet_final: null argument, dtype %d, C=%d, row of %d floats, HW=%lld, N=%d", out_dtype, C, rs, (long long)HW, N);
+    return launch_rn_final(d_raw, rs, C, (long)HW, N, d_bias, d_out, out_dtype == INNFER_F32, (hipStream_t)stream);
 }
 
 extern "C" int innfer_resnet_create(innfer_resnet** out, int in_nc, int out_nc, int ngf, int n_blocks) {
@@ -754,11 +846,7 @@ extern "C" int innfer_resnet_forward(innfer_resnet* r, const void* d_in, int in_
         const int cpad = (l.cout + 63) / 64 * 64;
         if (bn_eval) { int rc = fill_ev(l); if (rc) return rc; }
         else { int rc = norm::launch_stats(raw, cpad, HW, 1e-5f, l.d_gamma, l.d_beta, alpha, shift, l.cout, N, part, s); if (rc) return rc; }
-        const long total = (long)N * HW * (l.cout / 8);
-        hipLaunchKernelGGL(rn_post, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)raw, cpad, l.cout, HW, N,
-                           (const float*)alpha, (const float*)shift, relu, res, dst, (long)N * HW * 32);
-        INNFER_HIP(hipGetLastError());
-        return INNFER_OK;
+        return launch_rn_post((const float*)raw, cpad, l.cout, HW, N, (const float*)alpha, (const float*)shift, relu, res, dst, (long)N * HW * 32, s);
     };
     auto conv = [&](const Layer& l, const f16* in, int Hi, int Wi, int Ho, int Wo, int stride, int reflect) -> int {
         const int cin_pad = (l.cin + 31) / 32 * 32, cout_pad = (l.cout + 63) / 64 * 64;
@@ -804,19 +892,14 @@ extern "C" int innfer_resnet_forward(innfer_resnet* r, const void* d_in, int in_
         CK(conv_launch(L, s));
         CK(norm::launch_stats_slab(Y, G, HW, 1e-5f, l.d_gamma, l.d_beta, alpha, shift, l.cout, N, part, s));
         }
-        const long total = (long)N * HW * (l.cout / 8);
-        hipLaunchKernelGGL(rn_post_slab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const f16*)Y, l.cout, HW, N,
-                           (const float*)alpha, (const float*)shift, relu, res, dst, G);
-        INNFER_HIP(hipGetLastError());
-        return INNFER_OK;
+        return launch_rn_post_slab((const f16*)Y, l.cout, HW, N, (const float*)alpha, (const float*)shift, relu, res, dst, G, s);
     };
     f16 *X0 = (f16*)(ws + cv.x0), *S1 = (f16*)(ws + cv.s1), *S2 = (f16*)(ws + cv.s2), *A = (f16*)(ws + cv.a), *B = (f16*)(ws + cv.b),
         *Cc = (f16*)(ws + cv.c), *U1 = (f16*)(ws + cv.u1), *U2 = (f16*)(ws + cv.u2);
     const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
     size_t li = 0;
     const int patch = 7 * r->in_nc <= 32;
-    hipLaunchKernelGGL(rn_pre, dim3((unsigned)(((long)N * H * W + 255) / 256)), dim3(256), 0, s, d_in, in_dtype == INNFER_F32, r->in_nc, H, W, N, X0, patch);
-    INNFER_HIP(hipGetLastError());
+    CK(launch_rn_pre(d_in, in_dtype == INNFER_F32, r->in_nc, H, W, N, X0, patch, s));
     if (patch && r->layers[li].d_w3 && H >= 4 && (long)H * W * 64 < 0x7fffffffL) {
         // c7s1-64 as a 7 x 1 column conv over the row-patch slab on the halo-tile kernel (rows reflected by its loader), fp16 slab out, norm on the slab
         const Layer& l = r->layers[li];
@@ -839,10 +922,7 @@ extern "C" int innfer_resnet_forward(innfer_resnet* r, const void* d_in, int in_
         CK(conv_launch(L, s));
         CK(norm::launch_stats_slab(Y, G, HW, 1e-5f, l.d_gamma, l.d_beta, alpha, shift, l.cout, N, part, s));
         }
-        const long total = (long)N * HW * (l.cout / 8);
-        hipLaunchKernelGGL(rn_post_slab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const f16*)Y, l.cout, HW, N,
-                           (const float*)alpha, (const float*)shift, 1, (const f16*)nullptr, S1, G);
-        INNFER_HIP(hipGetLastError());
+        CK(launch_rn_post_slab((const f16*)Y, l.cout, HW, N, (const float*)alpha, (const float*)shift, 1, (const f16*)nullptr, S1, G, s));
         ++li;
     } else {
     if (patch) {
@@ -866,19 +946,8 @@ extern "C" int innfer_resnet_forward(innfer_resnet* r, const void* d_in, int in_
     // norm + ReLU of an fp16 conv result; pad: into the reflection-padded (Ho + 8) x (Wo + 8) slab the sub-block form of the last conv reads
     auto post_relu = [&](const Layer& l, const f16* Y, int Ho, int Wo, f16* dst, bool pad) -> int {
         const long HW = (long)Ho * Wo, G = (long)N * HW * 32;
-        const long total = (long)N * HW * (l.cout / 8);
-        if (pad) {
-            const long Gp = (long)N * (Ho + 8) * (Wo + 8) * 32;
-            const long ring = (long)N * (l.cout / 32) * (2 * (Wo + 8) + 2 * (Ho + 6)) * 4;
-            hipLaunchKernelGGL(rn_zero_ring, dim3((unsigned)((ring + 255) / 256)), dim3(256), 0, s, dst, l.cout / 32, Ho, Wo, N, Gp);
-            hipLaunchKernelGGL(rn_post_slab_pad, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, Y, l.cout, Ho, Wo, N,
-                               (const float*)alpha, (const float*)shift, 1, dst, G, Gp);
-        } else {
-            hipLaunchKernelGGL(rn_post_slab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, Y, l.cout, HW, N,
-                               (const float*)alpha, (const float*)shift, 1, (const f16*)nullptr, dst, G);
-        }
-        INNFER_HIP(hipGetLastError());
-        return INNFER_OK;
+        if (pad) return launch_rn_post_slab_pad(Y, l.cout, Ho, Wo, N, (const float*)alpha, (const float*)shift, 1, dst, G, (long)N * (Ho + 8) * (Wo + 8) * 32, s);
+        return launch_rn_post_slab(Y, l.cout, HW, N, (const float*)alpha, (const float*)shift, 1, (const f16*)nullptr, dst, G, s);
     };
     auto up_conv = [&](const Layer& l, const f16* in, int Hi, int Wi, f16* dst, bool pad) -> int {
         const int Ho = 2 * Hi, Wo = 2 * Wi;
@@ -951,11 +1020,7 @@ extern "C" int innfer_resnet_forward(innfer_resnet* r, const void* d_in, int in_
             L.s1 = L.s2 = 1.f; L.y0 = 0; L.y1 = Hp;
             L.out_mode = OUT_NCHW; L.out_f32 = 1;
             CK(conv_launch(L, s));
-            const long total = (long)N * l.cout * H * W;
-            hipLaunchKernelGGL(rn_sum9_tanh, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float*)raw, (const float*)l.d_b, d_out,
-                               out_dtype == INNFER_F32, l.cout, H, W, N);
-            INNFER_HIP(hipGetLastError());
-            return INNFER_OK;
+            return launch_rn_sum9_tanh((const float*)raw, (const float*)l.d_b, d_out, out_dtype == INNFER_F32, l.cout, H, W, N, s);
         }
         if (l.d_w3) {       // tanh(conv7x7(reflect3(x)) + bias) -> NCHW in the conv's planar epilogue
             ConvLaunch L{};
@@ -969,9 +1034,7 @@ extern "C" int innfer_resnet_forward(innfer_resnet* r, const void* d_in, int in_
         }
         const int rs = (l.cout + 3) / 4 * 4;
         CK(gg::launch(l.d_w[0], (l.cin + 31) / 32 * 32, 64, U2, (long)N * H * W * 32, N, H, W, raw, H, W, 1, 49, dy49, dx49, H, W, 1, 0, 0, 0, s, nullptr, 0, rs, 1));
-        hipLaunchKernelGGL(rn_final, dim3((unsigned)(((long)N * H * W + 255) / 256)), dim3(256), 0, s, (const float*)raw, rs, l.cout, (long)H * W, N,
-                           (const float*)l.d_b, d_out, out_dtype == INNFER_F32);
-        INNFER_HIP(hipGetLastError());
+        CK(launch_rn_final((const float*)raw, rs, l.cout, (long)H * W, N, (const float*)l.d_b, d_out, out_dtype == INNFER_F32, s));
     }
 #undef CK
     return INNFER_OK;

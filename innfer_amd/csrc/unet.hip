@@ -427,6 +427,81 @@ __global__ __launch_bounds__(256) void unet_first_mfma(const TI* in, int C, int 
     }
 }
 
+// ---- the launches of the pass kernels above as the network makes them (grid, block and instantiation): shared by innfer_unet_forward and by the single-launch
+// ---- entry points of ABI 123 (innfer_unet_pre .. innfer_unet_first_conv), so a test of a kernel runs the network's launch
+int launch_unet_post(const float* raw, int cpad, int C, long HW, int N, const float* alpha, const float* shift, int nstride, PostDst d0, PostDst d1, hipStream_t s) {
+    const long total = (long)N * HW * (C / 8);
+    hipLaunchKernelGGL(unet_post, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, raw, cpad, C, HW, N, alpha, shift, nstride, d0, d1);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int launch_unet_post_slab(const f16* src, long sg, int C, long HW, int N, const float* alpha, const float* shift, int nstride, PostDst d0, PostDst d1, hipStream_t s) {
+    const long total = (long)N * HW * (C / 8);
+    hipLaunchKernelGGL(unet_post_slab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, sg, C, HW, N, alpha, shift, nstride, d0, d1);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+// unet_deep_post: the instantiation follows the pixels per image (HW <= DEEP_PX); part: ks segments of split_elems floats
+int launch_deep_post(const float* part, long split_elems, int ks, int cpad, int C, int HW, int N, const float* gamma, const float* beta,
+                     const float* ev_alpha, const float* ev_shift, PostDst d0, PostDst d1, hipStream_t s) {
+#define INNFER_DEEP_POST(NPX_, PL_) hipLaunchKernelGGL((unet_deep_post<NPX_, PL_>), dim3((C + 31) / 32, N), dim3(32 * PL_), 0, s, part, split_elems, ks, cpad, C, HW, 1e-5f, \
+                                                       gamma, beta, ev_alpha, ev_shift, d0, d1)
+    if (HW == 1) INNFER_DEEP_POST(1, 1);
+    else if (HW <= 4) INNFER_DEEP_POST(1, 4);
+    else if (HW <= 16) INNFER_DEEP_POST(1, 16);
+    else if (HW <= 64) INNFER_DEEP_POST(2, 32);
+    else INNFER_DEEP_POST(8, 32);
+#undef INNFER_DEEP_POST
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int launch_unet_final(const float* raw, int cpad, int C, long HW, int N, const float* bias, void* out, int out_f32, hipStream_t s) {
+    hipLaunchKernelGGL(unet_final, dim3((unsigned)((N * HW + 255) / 256)), dim3(256), 0, s, raw, cpad, C, HW, N, bias, out, out_f32);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int launch_unet_pre(const void* in, int in_f32, int C, long HW, int N, f16* slab, hipStream_t s) {
+    hipLaunchKernelGGL(unet_pre, dim3((unsigned)((N * HW + 255) / 256)), dim3(256), 0, s, in, in_f32, C, HW, N, slab);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int launch_unet_pre_patch(const void* in, int in_f32, int C, int H, int W, int N, f16* slab, long g, hipStream_t s) {
+    const long M = (long)N * (H / 2) * (W / 2);
+    hipLaunchKernelGGL(unet_pre_patch, dim3((unsigned)((2 * M + 255) / 256)), dim3(256), 0, s, in, in_f32, C, H, W, N, slab, g);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+// unet_first_mfma: four output rows per workgroup, at most 2048 workgroups (the rows beyond are walked by the grid stride).  The kernel walks whole 16-pixel
+// segments of an output row and keeps its offsets in 32 bits: W / 2 must be a multiple of 16 and an image below 2^31 - 1 elements.
+int launch_unet_first(const void* in, int in_f32, int C, int H, int W, int N, const f16* wpk, const float* bias, f16* d0, f16* d1, long g, int abl, hipStream_t s) {
+    const int ho = H / 2, wo = W / 2;
+    if (wo <= 0 || wo % 16) return set_error(INNFER_ERR_UNSUPPORTED, "unet_first_mfma: %d output columns are not a multiple of 16", wo);
+    if ((long)C * H * W >= 0x7fffffffL || (long)N * ho >= 0x7fffffffL) return set_error(INNFER_ERR_UNSUPPORTED, "unet_first_mfma: image too large (C * H * W or N * H / 2 beyond 2^31 - 2)");
+    const unsigned grid = (unsigned)std::min<long>(((long)N * ho + 3) / 4, 256L * 8);
+    if (in_f32) hipLaunchKernelGGL(unet_first_mfma<float>, dim3(grid), dim3(256), 0, s, (const float*)in, C, H, W, N, wpk, bias, d0, d1, g, abl);
+    else hipLaunchKernelGGL(unet_first_mfma<f16>, dim3(grid), dim3(256), 0, s, (const f16*)in, C, H, W, N, wpk, bias, d0, d1, g, abl);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+// unet_first_mfma's weight panel (8192 bytes) from w [64][cin][4][4]: k = c * 16 + ky * 4 + kx, rows in the plane row order (see the kernel)
+void pack_unet_first(const float* w, int cin, f16* wf) {
+    for (int ks = 0; ks < 2; ++ks)
+        for (int t = 0; t < 4; ++t)
+            for (int rho = 0; rho < 16; ++rho)
+                for (int q = 0; q < 32; ++q) {
+                    const int co = 32 * (t >> 1) + 8 * (rho >> 2) + 4 * (t & 1) + (rho & 3), kk = ks * 32 + q, c = kk >> 4, tap = kk & 15;
+                    wf[((ks * 4 + t) * 16 + rho) * 32 + q] = (f16)(c < cin ? w[(((size_t)co * cin + c) * 4 + (tap >> 2)) * 4 + (tap & 3)] : 0.f);
+                }
+}
+constexpr int UNET_FIRST_PANEL = 2 * 4 * 16 * 32;      // f16 elements
+
 struct Param { std::string key; std::vector<int> shape; std::vector<float> host; bool set = false; };
 
 struct Layer {            // one conv / conv-transpose
@@ -479,6 +554,90 @@ extern "C" int innfer_unet_post_slab_parts(const void* d_src, int64_t src_gs, in
                          "activation outside 1 | 2", C, (long long)HW, N, nper);
     const PostDst d0{(f16*)d_dst0, (long)dst0_gs, dst0_coff, act0}, d1{(f16*)d_dst1, (long)dst1_gs, dst1_coff, d_dst1 ? act1 : 0};
     return launch_post_slab_parts((const f16*)d_src, (long)src_gs, C, (long)HW, N, d_part, nper, d_gamma, d_beta, d0, d1, (hipStream_t)stream);
+}
+
+// ---- (123) the pass kernels as single launches, for tests: argument checks, then the launcher innfer_unet_forward uses; nothing is launched on refusal ----------
+namespace {
+// a destination view: NULL pointer = absent (allowed where `optional`); else group stride >= N * HW * 32, channel offset % 8 == 0, act 1 | 2
+bool dst_ok(const void* p, int64_t gs, int coff, int act, int64_t px32, bool optional) {
+    if (!p) return optional;
+    return gs >= px32 && coff >= 0 && coff % 8 == 0 && (act == 1 || act == 2);
+}
+}  // namespace
+
+extern "C" int innfer_unet_pre(const void* d_in, int in_dtype, int C, int H, int W, int N, void* d_slab, int64_t gs, int patch, void* stream) {
+    if (!d_in || !d_slab || (in_dtype != INNFER_F16 && in_dtype != INNFER_F32) || C <= 0 || H <= 0 || W <= 0 || N <= 0)
+        return set_error(INNFER_ERR_INVALID, "unet_pre: null argument, dtype %d, C=%d, %d x %d, N=%d", in_dtype, C, H, W, N);
+    if (patch) {
+        if (16 * C > 64) return set_error(INNFER_ERR_UNSUPPORTED, "unet_pre: the patch slab holds 16 * C <= 64 window values (C=%d)", C);
+        if ((H & 1) || (W & 1)) return set_error(INNFER_ERR_INVALID, "unet_pre: the patch slab needs an even %d x %d", H, W);
+        if (gs < (int64_t)N * (H / 2) * (W / 2) * 32) return set_error(INNFER_ERR_INVALID, "unet_pre: group stride %lld below N * (H / 2) * (W / 2) * 32", (long long)gs);
+        return launch_unet_pre_patch(d_in, in_dtype == INNFER_F32, C, H, W, N, (f16*)d_slab, (long)gs, (hipStream_t)stream);
+    }
+    if (C > 32) return set_error(INNFER_ERR_UNSUPPORTED, "unet_pre: one 32-channel group (C=%d)", C);
+    if (gs < (int64_t)N * H * W * 32) return set_error(INNFER_ERR_INVALID, "unet_pre: group stride %lld below N * H * W * 32", (long long)gs);
+    return launch_unet_pre(d_in, in_dtype == INNFER_F32, C, (long)H * W, N, (f16*)d_slab, (hipStream_t)stream);
+}
+
+extern "C" int innfer_unet_post(const float* d_raw, int cpad, int C, int64_t HW, int N, const float* d_alpha, const float* d_shift, int nstride,
+                                void* d_dst0, int64_t dst0_gs, int dst0_coff, int act0, void* d_dst1, int64_t dst1_gs, int dst1_coff, int act1, void* stream) {
+    const int64_t px32 = (int64_t)N * HW * 32;
+    if (!d_raw || C <= 0 || C % 8 || cpad < C || cpad % 4 || HW <= 0 || N <= 0 || (!d_alpha != !d_shift) || (nstride != 0 && nstride != C) ||
+        !dst_ok(d_dst0, dst0_gs, dst0_coff, act0, px32, false) || !dst_ok(d_dst1, dst1_gs, dst1_coff, act1, px32, true))
+        return set_error(INNFER_ERR_INVALID, "unet_post: null argument, C=%d (%% 8), cpad=%d, HW=%lld, N=%d, alpha without shift, nstride=%d (0 | C), a group stride below "
+                         "N * HW * 32, a channel offset (%% 8) or an activation outside 1 | 2", C, cpad, (long long)HW, N, nstride);
+    const PostDst d0{(f16*)d_dst0, (long)dst0_gs, dst0_coff, act0}, d1{(f16*)d_dst1, (long)dst1_gs, dst1_coff, d_dst1 ? act1 : 0};
+    return launch_unet_post(d_raw, cpad, C, (long)HW, N, d_alpha, d_shift, nstride, d0, d1, (hipStream_t)stream);
+}
+
+extern "C" int innfer_unet_post_slab(const void* d_src, int64_t src_gs, int C, int64_t HW, int N, const float* d_alpha, const float* d_shift, int nstride,
+                                     void* d_dst0, int64_t dst0_gs, int dst0_coff, int act0, void* d_dst1, int64_t dst1_gs, int dst1_coff, int act1, void* stream) {
+    const int64_t px32 = (int64_t)N * HW * 32;
+    if (!d_src || !d_alpha || !d_shift || C <= 0 || C % 8 || HW <= 0 || N <= 0 || src_gs < px32 || (nstride != 0 && nstride != C) ||
+        !dst_ok(d_dst0, dst0_gs, dst0_coff, act0, px32, false) || !dst_ok(d_dst1, dst1_gs, dst1_coff, act1, px32, true))
+        return set_error(INNFER_ERR_INVALID, "unet_post_slab: null argument, C=%d (%% 8), HW=%lld, N=%d, nstride=%d (0 | C), a group stride below N * HW * 32, a channel "
+                         "offset (%% 8) or an activation outside 1 | 2", C, (long long)HW, N, nstride);
+    const PostDst d0{(f16*)d_dst0, (long)dst0_gs, dst0_coff, act0}, d1{(f16*)d_dst1, (long)dst1_gs, dst1_coff, d_dst1 ? act1 : 0};
+    return launch_unet_post_slab((const f16*)d_src, (long)src_gs, C, (long)HW, N, d_alpha, d_shift, nstride, d0, d1, (hipStream_t)stream);
+}
+
+extern "C" int innfer_unet_deep_post(const float* d_part, int64_t split_elems, int ks, int cpad, int C, int HW, int N, const float* d_gamma, const float* d_beta,
+                                     const float* d_ev_alpha, const float* d_ev_shift, void* d_dst0, int64_t dst0_gs, int dst0_coff, int act0,
+                                     void* d_dst1, int64_t dst1_gs, int dst1_coff, int act1, void* stream) {
+    if (HW > DEEP_PX) return set_error(INNFER_ERR_UNSUPPORTED, "unet_deep_post: %d pixels per image, at most %d", HW, DEEP_PX);
+    const int64_t px32 = (int64_t)N * HW * 32;
+    if (!d_part || C <= 0 || cpad < C || HW <= 0 || N <= 0 || N > 65535 || ks < 1 || (ks > 1 && split_elems < (int64_t)N * HW * cpad) || (!d_gamma != !d_beta) ||
+        (!d_ev_alpha != !d_ev_shift) || (d_gamma && d_ev_alpha) || !dst_ok(d_dst0, dst0_gs, dst0_coff, act0, px32, false) ||
+        !dst_ok(d_dst1, dst1_gs, dst1_coff, act1, px32, true))
+        return set_error(INNFER_ERR_INVALID, "unet_deep_post: null argument, C=%d, cpad=%d, HW=%d, N=%d, ks=%d, a segment stride below N * HW * cpad, gamma without beta, "
+                         "ev_alpha without ev_shift or both pairs, a group stride below N * HW * 32, a channel offset (%% 8) or an activation outside 1 | 2", C, cpad, HW, N, ks);
+    const PostDst d0{(f16*)d_dst0, (long)dst0_gs, dst0_coff, act0}, d1{(f16*)d_dst1, (long)dst1_gs, dst1_coff, d_dst1 ? act1 : 0};
+    return launch_deep_post(d_part, (long)split_elems, ks, cpad, C, HW, N, d_gamma, d_beta, d_ev_alpha, d_ev_shift, d0, d1, (hipStream_t)stream);
+}
+
+extern "C" int innfer_unet_final(const float* d_raw, int cpad, int C, int64_t HW, int N, const float* d_bias, void* d_out, int out_dtype, void* stream) {
+    if (!d_raw || !d_bias || !d_out || (out_dtype != INNFER_F16 && out_dtype != INNFER_F32) || C <= 0 || cpad < C || HW <= 0 || N <= 0)
+        return set_error(INNFER_ERR_INVALID, "unet_final: null argument, dtype %d, C=%d, row of %d floats, HW=%lld, N=%d", out_dtype, C, cpad, (long long)HW, N);
+    return launch_unet_final(d_raw, cpad, C, (long)HW, N, d_bias, d_out, out_dtype == INNFER_F32, (hipStream_t)stream);
+}
+
+extern "C" size_t innfer_unet_first_packed_bytes(void) { return UNET_FIRST_PANEL * sizeof(f16); }
+
+extern "C" int innfer_pack_unet_first(const float* h_w, int C, void* h_packed) {
+    if (!h_w || !h_packed || C < 1) return set_error(INNFER_ERR_INVALID, "pack_unet_first: null argument or C=%d", C);
+    if (16 * C > 64) return set_error(INNFER_ERR_UNSUPPORTED, "pack_unet_first: the panel holds 16 * C <= 64 window values (C=%d)", C);
+    pack_unet_first(h_w, C, (f16*)h_packed);
+    return INNFER_OK;
+}
+
+extern "C" int innfer_unet_first_conv(const void* d_in, int in_dtype, int C, int H, int W, int N, const void* d_packed, const float* d_bias,
+                                      void* d_dst0, void* d_dst1, int64_t gs, void* stream) {
+    if (!d_in || !d_packed || !d_dst0 || (in_dtype != INNFER_F16 && in_dtype != INNFER_F32) || C < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || N <= 0 ||
+        gs < (int64_t)N * (H / 2) * (W / 2) * 32)
+        return set_error(INNFER_ERR_INVALID, "unet_first_conv: null argument, dtype %d, C=%d, %d x %d (even), N=%d or group stride %lld below N * (H / 2) * (W / 2) * 32",
+                         in_dtype, C, H, W, N, (long long)gs);
+    if (16 * C > 64) return set_error(INNFER_ERR_UNSUPPORTED, "unet_first_conv: the window holds 16 * C <= 64 values (C=%d)", C);
+    return launch_unet_first(d_in, in_dtype == INNFER_F32, C, H, W, N, (const f16*)d_packed, d_bias, (f16*)d_dst0, (f16*)d_dst1, (long)gs, 0, (hipStream_t)stream);
 }
 
 extern "C" int innfer_unet_create(innfer_unet** out, int in_nc, int out_nc, int num_downs, int ngf) {
@@ -661,14 +820,8 @@ static int upload_all(innfer_unet* u) {
                     rc = upload_f32(&l.d_b3, b3); if (rc) return rc;
                 }
                 if (l.cout == 64) {            // unet_first_mfma's panel: k = c * 16 + ky * 4 + kx
-                    std::vector<f16> wf(2 * 4 * 16 * 32);
-                    for (int ks = 0; ks < 2; ++ks)
-                        for (int t = 0; t < 4; ++t)
-                            for (int rho = 0; rho < 16; ++rho)
-                                for (int q = 0; q < 32; ++q) {
-                                    const int co = 32 * (t >> 1) + 8 * (rho >> 2) + 4 * (t & 1) + (rho & 3), kk = ks * 32 + q, c = kk >> 4, tap = kk & 15;      // (plane row order: see unet_first_mfma)
-                                    wf[((ks * 4 + t) * 16 + rho) * 32 + q] = (f16)(c < l.cin ? w[(((size_t)co * l.cin + c) * 4 + (tap >> 2)) * 4 + (tap & 3)] : 0.f);
-                                }
+                    std::vector<f16> wf(UNET_FIRST_PANEL);
+                    pack_unet_first(w.data(), l.cin, wf.data());
                     rc = upload_f16(&l.d_wf, wf); if (rc) return rc;
                 }
             } else if (l.phases) {
@@ -1030,35 +1183,18 @@ extern "C" int innfer_unet_forward(innfer_unet* u, const void* d_in, int in_dtyp
         const bool nb = !bn && !l.transposed && l.d_bias && l.d_ones;
         if (HW <= DEEP_PX) {          // deep level: reduce + statistics + post in one launch
             GtScope gt(s, "unet_deep_post (split-K reduce + BatchNorm + views)", 0.0, (double)N * HW * l.cout_pad * 4.0 * ks_last + (double)N * HW * l.cout * 2.0 * ((d0.p ? 1 : 0) + (d1.p ? 1 : 0)));
-#define INNFER_DEEP_POST(NPX_, PL_) hipLaunchKernelGGL((unet_deep_post<NPX_, PL_>), dim3((l.cout + 31) / 32, N), dim3(32 * PL_), 0, s, ks_last > 1 ? (const float*)splitk : (const float*)raw, \
-                                   (long)N * HW * l.cout_pad, ks_last, l.cout_pad, l.cout, (int)HW, 1e-5f, bn && !ev ? l.d_gamma : nullptr, bn && !ev ? l.d_beta : nullptr, \
-                                   bn && ev ? l.d_ev_alpha : (nb ? l.d_ones : nullptr), bn && ev ? l.d_ev_shift : (nb ? l.d_bias : nullptr), d0, d1)
-            if (HW == 1) INNFER_DEEP_POST(1, 1);
-            else if (HW <= 4) INNFER_DEEP_POST(1, 4);
-            else if (HW <= 16) INNFER_DEEP_POST(1, 16);
-            else if (HW <= 64)
-                hipLaunchKernelGGL(unet_deep_post<2>, dim3((l.cout + 31) / 32, N), dim3(1024), 0, s, ks_last > 1 ? (const float*)splitk : (const float*)raw,
-                                   (long)N * HW * l.cout_pad, ks_last, l.cout_pad, l.cout, (int)HW, 1e-5f, bn && !ev ? l.d_gamma : nullptr, bn && !ev ? l.d_beta : nullptr,
-                                   bn && ev ? l.d_ev_alpha : (nb ? l.d_ones : nullptr), bn && ev ? l.d_ev_shift : (nb ? l.d_bias : nullptr), d0, d1);
-            else
-                hipLaunchKernelGGL(unet_deep_post<8>, dim3((l.cout + 31) / 32, N), dim3(1024), 0, s, ks_last > 1 ? (const float*)splitk : (const float*)raw,
-                                   (long)N * HW * l.cout_pad, ks_last, l.cout_pad, l.cout, (int)HW, 1e-5f, bn && !ev ? l.d_gamma : nullptr, bn && !ev ? l.d_beta : nullptr,
-                                   bn && ev ? l.d_ev_alpha : (nb ? l.d_ones : nullptr), bn && ev ? l.d_ev_shift : (nb ? l.d_bias : nullptr), d0, d1);
-            INNFER_HIP(hipGetLastError());
-            return INNFER_OK;
+            return launch_deep_post(ks_last > 1 ? (const float*)splitk : (const float*)raw, (long)N * HW * l.cout_pad, ks_last, l.cout_pad, l.cout, (int)HW, N,
+                                    bn && !ev ? l.d_gamma : nullptr, bn && !ev ? l.d_beta : nullptr, bn && ev ? l.d_ev_alpha : (nb ? l.d_ones : nullptr),
+                                    bn && ev ? l.d_ev_shift : (nb ? l.d_bias : nullptr), d0, d1, s);
         }
         if (bn && !ev) {
             GtScope gt(s, "norm statistics (fp32 rows)", 0.0, (double)N * HW * l.cout_pad * 4.0);
             int rc = norm::launch_stats(raw, l.cout_pad, HW, 1e-5f, l.d_gamma, l.d_beta, mean, rstd, l.cout, N, bnpart, s);
             if (rc) return rc;
         }
-        const long total = (long)N * HW * (l.cout / 8);
         GtScope gt(s, "unet_post (BatchNorm + views from fp32 rows)", 0.0, (double)N * HW * l.cout_pad * 4.0 + (double)N * HW * l.cout * 2.0 * ((d0.p ? 1 : 0) + (d1.p ? 1 : 0)));
-        hipLaunchKernelGGL(unet_post, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, raw, l.cout_pad, l.cout, HW, N,
-                           bn ? (ev ? l.d_ev_alpha : mean) : (nb ? l.d_ones : nullptr), bn ? (ev ? l.d_ev_shift : rstd) : (nb ? l.d_bias : nullptr),
-                           (bn && !ev) ? l.cout : 0, d0, d1);
-        INNFER_HIP(hipGetLastError());
-        return INNFER_OK;
+        return launch_unet_post(raw, l.cout_pad, l.cout, HW, N, bn ? (ev ? l.d_ev_alpha : mean) : (nb ? l.d_ones : nullptr),
+                                bn ? (ev ? l.d_ev_shift : rstd) : (nb ? l.d_bias : nullptr), (bn && !ev) ? l.cout : 0, d0, d1, s);
     };
 
     const bool first_mfma = u->down[0].patch && u->down[0].d_wf && L > 1;
@@ -1072,13 +1208,11 @@ extern "C" int innfer_unet_forward(innfer_unet* u, const void* d_in, int in_dtyp
     if (first_mfma) {          // the outermost down conv reads the NCHW input itself
     } else if (u->down[0].patch) {   // NCHW input -> 64-channel patch slab at half resolution
         const long M = (long)N * (H / 2) * (W / 2);
-        hipLaunchKernelGGL(unet_pre_patch, dim3((unsigned)((2 * M + 255) / 256)), dim3(256), 0, s, d_in, in_dtype == INNFER_F32, u->in_nc, H, W, N,
-                           (f16*)(ws + cv.x0), M * 32);
-        INNFER_HIP(hipGetLastError());
+        int rc = launch_unet_pre_patch(d_in, in_dtype == INNFER_F32, u->in_nc, H, W, N, (f16*)(ws + cv.x0), M * 32, s);
+        if (rc) return rc;
     } else {                  // NCHW input -> one zero-padded 32-channel group
-        const long HW = (long)H * W;
-        hipLaunchKernelGGL(unet_pre, dim3((unsigned)((N * HW + 255) / 256)), dim3(256), 0, s, d_in, in_dtype == INNFER_F32, u->in_nc, HW, N, (f16*)(ws + cv.x0));
-        INNFER_HIP(hipGetLastError());
+        int rc = launch_unet_pre(d_in, in_dtype == INNFER_F32, u->in_nc, (long)H * W, N, (f16*)(ws + cv.x0), s);
+        if (rc) return rc;
     }
     // ---- down path ----
     const f16* cur = (const f16*)(ws + cv.x0);
@@ -1090,21 +1224,14 @@ extern "C" int innfer_unet_forward(innfer_unet* u, const void* d_in, int in_dtyp
         int rc;
         if (k == 0 && first_mfma) {
             const long HWo = (long)ho * wo, Go = (long)N * HWo * 32;
-            if ((long)u->in_nc * H * W >= 0x7fffffffL || (long)N * ho >= 0x7fffffffL) return set_error(INNFER_ERR_UNSUPPORTED, "unet_forward: image too large");
-            const unsigned grid = (unsigned)std::min<long>(((long)N * ho + 3) / 4, 256L * 8);
             const int abl = INNFER_KNOB("INNFER_FIRST_ABL", 0);
             const bool ov = one_view(0);
             GtScope gt(s, "unet_first_mfma (3 -> 64, 4x4 s2)", 2.0 * 16 * u->in_nc * l.cout * (double)N * HWo,
                        (double)N * H * W * u->in_nc * (in_dtype == INNFER_F32 ? 4.0 : 2.0) + (ov ? 1.0 : 2.0) * N * HWo * l.cout * 2.0);
             f16* dl = (f16*)(ws + (ov ? cv.CAT[0] : cv.D[0]));
             f16* dr = ov ? nullptr : (f16*)(ws + cv.CAT[0]);
-            if (in_dtype == INNFER_F32)
-                hipLaunchKernelGGL(unet_first_mfma<float>, dim3(grid), dim3(256), 0, s, (const float*)d_in, u->in_nc, H, W, N, (const f16*)l.d_wf,
-                                   (const float*)(l.bias >= 0 ? l.d_bias : nullptr), dl, dr, Go, abl);
-            else
-                hipLaunchKernelGGL(unet_first_mfma<f16>, dim3(grid), dim3(256), 0, s, (const f16*)d_in, u->in_nc, H, W, N, (const f16*)l.d_wf,
-                                   (const float*)(l.bias >= 0 ? l.d_bias : nullptr), dl, dr, Go, abl);
-            INNFER_HIP(hipGetLastError());
+            rc = launch_unet_first(d_in, in_dtype == INNFER_F32, u->in_nc, H, W, N, (const f16*)l.d_wf, (const float*)(l.bias >= 0 ? l.d_bias : nullptr), dl, dr, Go, abl, s);
+            if (rc) return rc;
             cur = dl; cur_g = Go;
             h = ho; w = wo;
             continue;
@@ -1140,7 +1267,6 @@ extern "C" int innfer_unet_forward(innfer_unet* u, const void* d_in, int in_dtyp
             if (!ev) Lc.stats_part = bnpart;              // statistics as per-tile partials out of the conv epilogue
             rc = conv_launch(Lc, s);
             if (rc) return rc;
-            const long total = (long)N * HWo * (l.cout / 8);
             PostDst dl{(f16*)(ws + cv.D[k]), Go, 0, 1}, dr{(f16*)(ws + cv.CAT[k]), Go, 0, 2};
             if (one_view(k)) { dl.p = dr.p; dr = PostDst{nullptr, 0, 0, 0}; }
             if (!ev) {           // the records are merged inside the post pass
@@ -1148,9 +1274,8 @@ extern "C" int innfer_unet_forward(innfer_unet* u, const void* d_in, int in_dtyp
                 if (rc) return rc;
             } else {
                 GtScope gt(s, "unet_post_slab (eval-mode BatchNorm + views)", 0.0, (double)N * HWo * l.cout * 2.0 * 3);
-                hipLaunchKernelGGL(unet_post_slab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const f16*)Y, Go, l.cout, HWo, N,
-                                   (const float*)l.d_ev_alpha, (const float*)l.d_ev_shift, 0, dl, dr);
-                INNFER_HIP(hipGetLastError());
+                rc = launch_unet_post_slab((const f16*)Y, Go, l.cout, HWo, N, (const float*)l.d_ev_alpha, (const float*)l.d_ev_shift, 0, dl, dr, s);
+                if (rc) return rc;
             }
             cur = dl.p; cur_g = Go;
             h = ho; w = wo;
@@ -1217,11 +1342,10 @@ extern "C" int innfer_unet_forward(innfer_unet* u, const void* d_in, int in_dtyp
                         rc = norm::launch_stats_slab(Y, G, HW, 1e-5f, l.d_gamma, l.d_beta, mean, rstd, l.cout, N, bnpart, s);
                         if (rc) return rc;
                     }
-                    const long total = (long)N * HW * (l.cout / 8);
                     GtScope gt(s, "unet_post_slab (BatchNorm + views)", 0.0, (double)N * HW * l.cout * 2.0 * 2);
-                    hipLaunchKernelGGL(unet_post_slab, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const f16*)Y, G, l.cout, HW, N,
-                                       (const float*)(ev ? l.d_ev_alpha : mean), (const float*)(ev ? l.d_ev_shift : rstd), ev ? 0 : l.cout, dr, PostDst{nullptr, 0, 0, 0});
-                    INNFER_HIP(hipGetLastError());
+                    rc = launch_unet_post_slab((const f16*)Y, G, l.cout, HW, N, (const float*)(ev ? l.d_ev_alpha : mean), (const float*)(ev ? l.d_ev_shift : rstd),
+                                               ev ? 0 : l.cout, dr, PostDst{nullptr, 0, 0, 0}, s);
+                    if (rc) return rc;
                 }
             }
             h = hf; w = wf;
@@ -1260,9 +1384,8 @@ extern "C" int innfer_unet_forward(innfer_unet* u, const void* d_in, int in_dtyp
             if (rc) return rc;
         } else {
             GtScope gt(s, "unet_final (bias + tanh -> NCHW)", 0.0, (double)N * HW * ((l.cout + 3) / 4 * 4) * 4.0 + (double)N * HW * l.cout * (out_dtype == INNFER_F32 ? 4.0 : 2.0));
-            hipLaunchKernelGGL(unet_final, dim3((unsigned)((N * HW + 255) / 256)), dim3(256), 0, s, raw, (l.cout + 3) / 4 * 4, l.cout, HW, N,
-                               l.d_bias, d_out, out_dtype == INNFER_F32);
-            INNFER_HIP(hipGetLastError());
+            int rc = launch_unet_final(raw, (l.cout + 3) / 4 * 4, l.cout, HW, N, l.d_bias, d_out, out_dtype == INNFER_F32, s);
+            if (rc) return rc;
         }
         h = hf; w = wf;
     }

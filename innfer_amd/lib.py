@@ -289,6 +289,23 @@ SIGNATURES = {
                                                 C.c_void_p, C.c_void_p]),
     "innfer_unet_post_slab_parts": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    # (123) the UNet / ResNet engines' pass kernels, one launch at a time; a destination view = (pointer, group stride, channel offset, act)
+    "innfer_unet_pre": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "innfer_unet_post": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
+                         [C.c_void_p, C.c_int64, C.c_int, C.c_int] * 2 + [C.c_void_p]),
+    "innfer_unet_post_slab": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int] +
+                              [C.c_void_p, C.c_int64, C.c_int, C.c_int] * 2 + [C.c_void_p]),
+    "innfer_unet_deep_post": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_void_p, C.c_int64, C.c_int, C.c_int] * 2 + [C.c_void_p]),
+    "innfer_unet_final": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_unet_first_packed_bytes": (C.c_size_t, []),
+    "innfer_pack_unet_first": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_unet_first_conv": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p]),
+    "innfer_resnet_pre": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_resnet_post": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "innfer_resnet_post_slab": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "innfer_resnet_post_slab_pad": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
+    "innfer_resnet_sum9_tanh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    "innfer_resnet_final": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_tile_plan": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)] * 6),
     "innfer_tile_owner": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2),
     "innfer_extract_tiles_rect": (C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
@@ -314,7 +331,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 lib = _lib
 
-ABI_VERSION = 122          # the header revision this binding was written against (INNFER_ABI_VERSION)
+ABI_VERSION = 123         # the header revision this binding was written against (INNFER_ABI_VERSION)
 if _lib.innfer_version() != ABI_VERSION and not _ABI_ANY:
     raise ImportError(f"{LIB_PATH} speaks ABI {_lib.innfer_version()}, this binding {ABI_VERSION}: rebuild with `make`")
 
