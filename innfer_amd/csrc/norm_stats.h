@@ -1,6 +1,7 @@
 // Per-(image, channel) normalisation statistics shared by the pix2pix UNet (train-mode BatchNorm2d, unet.hip) and the CycleGAN
 // ResNet (InstanceNorm2d, resnet.hip): mean and biased variance over H*W of the fp32 conv output, emitted as the affine
-// transform  out = x * alpha + shift.
+// transform  out = x * alpha + shift.  Also the merge of the conv epilogues' partial records that both engines' post kernels run as their prologue
+// (merge_group_parts).
 #pragma once
 #include "common.h"
 
@@ -170,6 +171,38 @@ __device__ __forceinline__ void chan_merge(float& n, float& mu, float& m2, float
     m2 += m2b + d * d * (n * nb / tot);
     n = tot;
 }
+// The same merge as the prologue of a 256-thread post kernel (unet_post_slab_parts, rn_post_slab_parts): the workgroup turns the nper records of image n's
+// channels cb .. cb + 31 (C % 32 == 0) into sal[32] / ssh[32] in LDS, alpha = gamma / sqrt(m2 / HW + eps) (gamma, beta == nullptr: 1, 0), and leaves behind a
+// barrier.  8 lanes per channel; a lane takes four records per trip with their loads issued together (one record per trip was one exposed load latency per
+// record -- 32 trips for the 256 records of a 128 x 128 level, repeated by each of its pixel blocks), the index clamped to nper - 1 with a count of 0 (a no-op
+// of chan_merge); then the 8 lanes are merged in index order -- every workgroup of the group computes the same bits.
+__device__ __forceinline__ void merge_group_parts(const float* part, int nper, int n, int cb, int C, long HW, float eps, const float* gamma, const float* beta,
+                                                  float (&sal)[32], float (&ssh)[32]) {
+    __shared__ float sn[8][32], sm[8][32], sq[8][32];
+    const int cl = threadIdx.x & 31, lg = threadIdx.x >> 5, c = cb + cl;
+    float cnt = 0.f, mu = 0.f, m2 = 0.f;
+    for (int r = lg; r < nper; r += 32) {
+        float rec[4][3];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int rr = r + 8 * j;
+            const float* q = part + (((long)n * nper + min(rr, nper - 1)) * C + c) * 3;
+            rec[j][0] = rr < nper ? q[0] : 0.f; rec[j][1] = q[1]; rec[j][2] = q[2];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) chan_merge(cnt, mu, m2, rec[j][0], rec[j][1], rec[j][2]);
+    }
+    sn[lg][cl] = cnt; sm[lg][cl] = mu; sq[lg][cl] = m2;
+    __syncthreads();
+    if (lg == 0) {
+        for (int i = 1; i < 8; ++i) chan_merge(cnt, mu, m2, sn[i][cl], sm[i][cl], sq[i][cl]);
+        const float a = (1.0f / sqrtf(m2 / (float)HW + eps)) * (gamma ? gamma[c] : 1.0f);
+        sal[cl] = a;
+        ssh[cl] = (beta ? beta[c] : 0.f) - mu * a;
+    }
+    __syncthreads();
+}
+
 static __global__ __launch_bounds__(1024) void combine_parts_kernel(const float* part, int nper, long HW, float eps, const float* gamma, const float* beta,
                                                                     float* alpha, float* shift, int C) {
     __shared__ float sn[32][33], sm[32][33], sq[32][33];

@@ -20,6 +20,7 @@
 // Reference quirk kept: B.sequential() flattens with children(), which yields the shared LeakyReLU
 // of pa_upconv_block once, so NO activation follows HRconv (golden G8 confirms).
 #include "common.h"
+#include "engine_host.h"
 #include "gather_gemm.h"
 
 #include <cmath>
@@ -712,8 +713,6 @@ __global__ void pan_final_x4(const float* raw, int C, const void* x, int x_f32, 
     else *(f16x4*)((f16*)out + o) = f16x4{(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
 }
 
-struct Param { std::string key; std::vector<int> shape; std::vector<float> host; bool set = false; };
-
 struct Gemm {                       // one packed GEMM
     int cin_pad = 32, cout = 0, ntaps = 1;
     f16* d_w = nullptr;
@@ -737,7 +736,8 @@ struct innfer_pan {
     bool bilinear_up = false;              // ups_inter_mode 'bilinear': the up-blocks' Upsample(2) as its own pass (nearest rides in the conv's loader)
     bool self_attention = true;      // FSA after fea + trunk (PAN_arch.py:200-203)
     bool double_scpa = false;        // a second SCPA trunk + trunk_conv2 behind the first (PAN_arch.py:139-141,195-196)
-    std::vector<Param> params;
+    ParamTable params;
+    DeviceBufs weights, f32;         // every device block of the network / of its fp32 mode (f32_w, d_scpa32, the gemms' d_w3s and d_gate_s)
     std::vector<Gemm> gemms;
     std::vector<float*> d_vecs;      // device copies of bias vectors / gamma, by param index (nullptr if unused)
     bool fp32 = false;               // innfer_pan_set_precision(1): the fp32 forward on NCHW fp32 tensors (f32ops.hip), the reference's -no_fp16 mode
@@ -753,12 +753,6 @@ struct innfer_pan {
     bool uploaded = false;
 };
 
-static int P(innfer_pan* p, const std::string& key, std::vector<int> shape) {
-    Param q; q.key = key; q.shape = shape;
-    p->params.push_back(q);
-    return (int)p->params.size() - 1;
-}
-
 extern "C" int innfer_pan_create(innfer_pan** out, int in_nc, int out_nc, int nf, int unf, int nb, int scale) {
     return innfer_pan_create_ex(out, in_nc, out_nc, nf, unf, nb, scale, 1, 0, 0);
 }
@@ -773,46 +767,38 @@ extern "C" int innfer_pan_create_ex(innfer_pan** out, int in_nc, int out_nc, int
     p->n_up = scale == 4 ? 2 : (scale == 1 ? 0 : 1);          // scale 3: ONE Upsample(scale_factor=3) stage (PAN_arch.py:112-114,164-166)
     p->self_attention = self_attention != 0; p->double_scpa = double_scpa != 0; p->bilinear_up = bilinear_up != 0;
     const int gw = nf / 2, UF = p->unf;
-    P(p, "conv_first.weight", {nf, in_nc, 3, 3}); P(p, "conv_first.bias", {nf});
+    p->params.add("conv_first.weight", {nf, in_nc, 3, 3}); p->params.add("conv_first.bias", {nf});
     for (int k = 0; k < (p->double_scpa ? 2 : 1); ++k) {          // registration order of PAN.__init__ (PAN_arch.py:134-141)
         const std::string sfx = k ? "2" : "";
         for (int b = 0; b < nb; ++b) {
             const std::string s = "SCPA_trunk" + sfx + "." + std::to_string(b) + ".";
-            P(p, s + "conv1_a.weight", {gw, nf, 1, 1}); P(p, s + "conv1_b.weight", {gw, nf, 1, 1});
-            P(p, s + "k1.0.weight", {gw, gw, 3, 3});
-            P(p, s + "PACnv.k2.weight", {gw, gw, 1, 1}); P(p, s + "PACnv.k2.bias", {gw});
-            P(p, s + "PACnv.k3.weight", {gw, gw, 3, 3}); P(p, s + "PACnv.k4.weight", {gw, gw, 3, 3});
-            P(p, s + "conv3.weight", {nf, nf, 1, 1});
+            p->params.add(s + "conv1_a.weight", {gw, nf, 1, 1}); p->params.add(s + "conv1_b.weight", {gw, nf, 1, 1});
+            p->params.add(s + "k1.0.weight", {gw, gw, 3, 3});
+            p->params.add(s + "PACnv.k2.weight", {gw, gw, 1, 1}); p->params.add(s + "PACnv.k2.bias", {gw});
+            p->params.add(s + "PACnv.k3.weight", {gw, gw, 3, 3}); p->params.add(s + "PACnv.k4.weight", {gw, gw, 3, 3});
+            p->params.add(s + "conv3.weight", {nf, nf, 1, 1});
         }
-        P(p, "trunk_conv" + sfx + ".weight", {nf, nf, 3, 3}); P(p, "trunk_conv" + sfx + ".bias", {nf});
+        p->params.add("trunk_conv" + sfx + ".weight", {nf, nf, 3, 3}); p->params.add("trunk_conv" + sfx + ".bias", {nf});
     }
     if (p->self_attention) {
-        P(p, "FSA.gamma", {1});
-        P(p, "FSA.conv_f.weight", {nf / 8, nf, 1}); P(p, "FSA.conv_f.bias", {nf / 8});
-        P(p, "FSA.conv_g.weight", {nf / 8, nf, 1}); P(p, "FSA.conv_g.bias", {nf / 8});
-        P(p, "FSA.conv_h.weight", {nf, nf, 1}); P(p, "FSA.conv_h.bias", {nf});
+        p->params.add("FSA.gamma", {1});
+        p->params.add("FSA.conv_f.weight", {nf / 8, nf, 1}); p->params.add("FSA.conv_f.bias", {nf / 8});
+        p->params.add("FSA.conv_g.weight", {nf / 8, nf, 1}); p->params.add("FSA.conv_g.bias", {nf / 8});
+        p->params.add("FSA.conv_h.weight", {nf, nf, 1}); p->params.add("FSA.conv_h.bias", {nf});
     }
     for (int u = 0; u < p->n_up; ++u) {
         const int i = 5 * u, ci = u == 0 ? nf : UF;
         const std::string s = "upsample.";
-        P(p, s + std::to_string(i + 1) + ".weight", {UF, ci, 3, 3}); P(p, s + std::to_string(i + 1) + ".bias", {UF});
-        P(p, s + std::to_string(i + 2) + ".conv.weight", {UF, UF, 1, 1}); P(p, s + std::to_string(i + 2) + ".conv.bias", {UF});
-        P(p, s + std::to_string(i + 4) + ".weight", {UF, UF, 3, 3}); P(p, s + std::to_string(i + 4) + ".bias", {UF});
+        p->params.add(s + std::to_string(i + 1) + ".weight", {UF, ci, 3, 3}); p->params.add(s + std::to_string(i + 1) + ".bias", {UF});
+        p->params.add(s + std::to_string(i + 2) + ".conv.weight", {UF, UF, 1, 1}); p->params.add(s + std::to_string(i + 2) + ".conv.bias", {UF});
+        p->params.add(s + std::to_string(i + 4) + ".weight", {UF, UF, 3, 3}); p->params.add(s + std::to_string(i + 4) + ".bias", {UF});
     }
-    P(p, "conv_last.weight", {out_nc, UF, 3, 3}); P(p, "conv_last.bias", {out_nc});
+    p->params.add("conv_last.weight", {out_nc, UF, 3, 3}); p->params.add("conv_last.bias", {out_nc});
     *out = p;
     return INNFER_OK;
 }
 
-extern "C" void innfer_pan_destroy(innfer_pan* p) {
-    if (!p) return;
-    for (auto& g : p->gemms) { if (g.d_w) (void)hipFree(g.d_w); if (g.d_w3) (void)hipFree(g.d_w3); if (g.d_b3) (void)hipFree(g.d_b3); if (g.d_gate) (void)hipFree(g.d_gate); if (g.d_fuse) (void)hipFree(g.d_fuse); if (g.d_w3s) (void)hipFree(g.d_w3s); if (g.d_gate_s) (void)hipFree(g.d_gate_s); }
-    for (auto v : p->d_vecs) if (v) (void)hipFree(v);
-    for (auto v : p->d_scpa) if (v) (void)hipFree(v);
-    for (auto v : p->d_scpa32) if (v) (void)hipFree(v);
-    for (auto v : p->f32_w) if (v) (void)hipFree(v);
-    delete p;
-}
+extern "C" void innfer_pan_destroy(innfer_pan* p) { delete p; }
 
 extern "C" int innfer_pan_set_fused_scpa(innfer_pan* p, int on) {
     if (!p) return set_error(INNFER_ERR_INVALID, "pan_set_fused_scpa: null network");
@@ -829,37 +815,22 @@ extern "C" int innfer_pan_set_fused_scpa(innfer_pan* p, int on) {
 extern "C" int innfer_pan_num_params(innfer_pan* p) { return p ? (int)p->params.size() : INNFER_ERR_INVALID; }
 
 extern "C" int innfer_pan_param_info(innfer_pan* p, int idx, char* key, size_t key_cap, int* ndim, int* shape4) {
-    if (!p || idx < 0 || idx >= (int)p->params.size()) return set_error(INNFER_ERR_INVALID, "pan_param_info: bad index");
-    const Param& q = p->params[idx];
-    if (key && key_cap) { strncpy(key, q.key.c_str(), key_cap - 1); key[key_cap - 1] = 0; }
-    if (ndim) *ndim = (int)q.shape.size();
-    if (shape4) for (size_t i = 0; i < 4; ++i) shape4[i] = i < q.shape.size() ? q.shape[i] : 1;
-    return INNFER_OK;
+    return ParamTable::of(p).info("pan", idx, key, key_cap, ndim, shape4);
 }
 
 extern "C" int innfer_pan_set_param(innfer_pan* p, int idx, const float* h_data) {
-    if (!p || idx < 0 || idx >= (int)p->params.size() || !h_data) return set_error(INNFER_ERR_INVALID, "pan_set_param: bad arguments");
-    Param& q = p->params[idx];
-    size_t n = 1;
-    for (int s : q.shape) n *= (size_t)s;
-    q.host.assign(h_data, h_data + n);
-    q.set = true;
-    p->uploaded = false;
-    return INNFER_OK;
+    const int rc = ParamTable::of(p).set("pan", idx, h_data);
+    if (!rc) p->uploaded = false;
+    return rc;
 }
 
 namespace {
-
-int find(const innfer_pan* p, const std::string& key) {
-    for (size_t i = 0; i < p->params.size(); ++i) if (p->params[i].key == key) return (int)i;
-    return -1;
-}
 
 // GEMM list in forward order; weights are looked up in the host copies when packing
 int build_gemms(innfer_pan* p) {
     p->gemms.clear();
     const int nf = p->nf, gw = nf / 2, UF = p->unf;
-    auto W = [p](const std::string& key) -> const std::vector<float>& { return p->params[find(p, key)].host; };
+    auto W = [p](const std::string& key) -> const std::vector<float>& { return p->params[p->params.find(key)].host; };
     auto add = [&](int cin_pad, int cout, int ntaps, std::function<float(int, int, int)> f, const char* tile3_bias = nullptr) {
         Gemm g; g.cin_pad = cin_pad; g.cout = cout; g.ntaps = ntaps; g.weight = f;
         if (tile3_bias) { g.tile3 = true; g.bias_key = tile3_bias; }           // "" = a halo-tile conv without bias
@@ -928,17 +899,13 @@ int build_gemms(innfer_pan* p) {
 }
 
 int upload(innfer_pan* p) {
-    for (auto& q : p->params) if (!q.set) return set_error(INNFER_ERR_INVALID, "pan: parameter '%s' was never set", q.key.c_str());
-    for (auto& g : p->gemms) {
-        if (g.d_w) { (void)hipFree(g.d_w); g.d_w = nullptr; }
-        if (g.d_w3) { (void)hipFree(g.d_w3); g.d_w3 = nullptr; }
-        if (g.d_b3) { (void)hipFree(g.d_b3); g.d_b3 = nullptr; }
-        if (g.d_gate) { (void)hipFree(g.d_gate); g.d_gate = nullptr; }
-        if (g.d_fuse) { (void)hipFree(g.d_fuse); g.d_fuse = nullptr; }
-        if (g.d_w3s) { (void)hipFree(g.d_w3s); g.d_w3s = nullptr; }
-        if (g.d_gate_s) { (void)hipFree(g.d_gate_s); g.d_gate_s = nullptr; }
-    }
-    build_gemms(p);
+    int rc = p->params.require_all_set("pan", false);
+    if (rc) return rc;
+    DeviceBufs& dev = p->weights;
+    dev.clear();
+    p->f32.clear();                  // the fp32 mode's blocks follow the parameters: rebuilt by innfer_pan_set_precision
+    p->f32_w.clear(); p->d_scpa.clear(); p->d_scpa32.clear();
+    build_gemms(p);                  // (makes the Gemm records anew: every device view in them is null again)
     std::vector<f16> panel;
     for (auto& g : p->gemms) {
         if (g.tile3) {
@@ -950,7 +917,7 @@ int upload(innfer_pan* p) {
                 for (int ci = 0; ci < g.cin_pad; ++ci)
                     for (int t = 0; t < 9; ++t) w3[((size_t)co * g.cin_pad + ci) * 9 + t] = g.weight(co, ci, t);
             if (!g.bias_key.empty()) {
-                const std::vector<float>& hb = p->params[find(p, g.bias_key)].host;
+                const std::vector<float>& hb = p->params[p->params.find(g.bias_key)].host;
                 for (int co = 0; co < g.cout; ++co) {
                     const int bi = g.bias_row ? g.bias_row(co) : co;
                     if (bi >= 0) b3[co] = hb[bi];
@@ -966,55 +933,41 @@ int upload(innfer_pan* p) {
                 if (g.pa_gate && g.K3 == 32 && g.cin_pad == 32) {
                     std::vector<char> gp(2048);
                     conv_pack_selfgate(w1.data(), gp.data());
-                    INNFER_HIP(hipMalloc(&g.d_gate, gp.size()));
-                    INNFER_HIP(hipMemcpy(g.d_gate, gp.data(), gp.size(), hipMemcpyHostToDevice));
+                    rc = dev.put(&g.d_gate, gp); if (rc) return rc;
                 }
             } else {
                 conv_pack(w3.data(), g.K3, g.cin_pad, packed.data());
                 if (g.K3 <= 3 && g.cin_pad == 32 && &g == &p->gemms.back()) {      // conv_last behind the last stage's HRconv (unf <= 32 channels): also as that conv's fused epilogue
                     std::vector<char> fp(4096);
                     conv_pack_fuse_last(w3.data(), g.K3, fp.data(), 0, 32);
-                    INNFER_HIP(hipMalloc(&g.d_fuse, fp.size()));
-                    INNFER_HIP(hipMemcpy(g.d_fuse, fp.data(), fp.size(), hipMemcpyHostToDevice));
+                    rc = dev.put(&g.d_fuse, fp); if (rc) return rc;
                 }
             }
-            INNFER_HIP(hipMalloc(&g.d_w3, packed.size()));
-            INNFER_HIP(hipMemcpy(g.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
-            INNFER_HIP(hipMalloc((void**)&g.d_b3, b3.size() * sizeof(float)));
-            INNFER_HIP(hipMemcpy(g.d_b3, b3.data(), b3.size() * sizeof(float), hipMemcpyHostToDevice));
+            rc = dev.put(&g.d_w3, packed); if (rc) return rc;
+            rc = dev.put(&g.d_b3, b3); if (rc) return rc;
             continue;
         }
         gg::pack_panels(panel, g.cout, g.cin_pad, g.cin_pad, g.ntaps, g.weight);
-        INNFER_HIP(hipMalloc((void**)&g.d_w, panel.size() * sizeof(f16)));
-        INNFER_HIP(hipMemcpy(g.d_w, panel.data(), panel.size() * sizeof(f16), hipMemcpyHostToDevice));
+        rc = dev.put(&g.d_w, panel); if (rc) return rc;
     }
-    for (auto v : p->f32_w) if (v) (void)hipFree(v);                 // the fp32 panels follow the parameters: rebuilt by innfer_pan_set_precision
-    p->f32_w.clear();
-    for (auto v : p->d_scpa) if (v) (void)hipFree(v);
-    p->d_scpa.clear();
-    for (auto v : p->d_scpa32) if (v) (void)hipFree(v);
-    p->d_scpa32.clear();
     {   // one blob per SCPA block for the fused launch (pan_scpa.hip): the block's eight tensors as MFMA fragments
         std::vector<char> blob(pan_scpa_blob_bytes());
-        auto Wk = [p](const std::string& key) -> const float* { return p->params[find(p, key)].host.data(); };
+        auto Wk = [p](const std::string& key) -> const float* { return p->params[p->params.find(key)].host.data(); };
         for (int k = 0; k < (p->double_scpa ? 2 : 1); ++k)
             for (int b = 0; b < p->nb; ++b) {
                 const std::string s = "SCPA_trunk" + std::string(k ? "2" : "") + "." + std::to_string(b) + ".";
                 pan_scpa_pack(Wk(s + "conv1_a.weight"), Wk(s + "conv1_b.weight"), Wk(s + "k1.0.weight"), Wk(s + "PACnv.k2.weight"), Wk(s + "PACnv.k2.bias"),
                               Wk(s + "PACnv.k3.weight"), Wk(s + "PACnv.k4.weight"), Wk(s + "conv3.weight"), blob.data());
                 void* d = nullptr;
-                INNFER_HIP(hipMalloc(&d, blob.size()));
+                rc = dev.put(&d, blob); if (rc) return rc;
                 p->d_scpa.push_back(d);
-                INNFER_HIP(hipMemcpy(d, blob.data(), blob.size(), hipMemcpyHostToDevice));
             }
     }
-    for (auto v : p->d_vecs) if (v) (void)hipFree(v);
     p->d_vecs.assign(p->params.size(), nullptr);
     for (size_t i = 0; i < p->params.size(); ++i) {
         const Param& q = p->params[i];
         if (q.shape.size() != 1) continue;
-        INNFER_HIP(hipMalloc((void**)&p->d_vecs[i], q.host.size() * sizeof(float)));
-        INNFER_HIP(hipMemcpy(p->d_vecs[i], q.host.data(), q.host.size() * sizeof(float), hipMemcpyHostToDevice));
+        rc = dev.put(&p->d_vecs[i], q.host); if (rc) return rc;
     }
     p->uploaded = true;
     return INNFER_OK;
@@ -1077,7 +1030,7 @@ int pan_forward_f32(innfer_pan* p, const float* x, float* y, int N, int H, int W
     const long hw = (long)H * W;
     auto B = [&](size_t o) { return (float*)(ws + o); };
     float *FEA = B(cv.fea), *XA = B(cv.xa), *XB = B(cv.xb), *AB = B(cv.ab), *CAT = B(cv.cat), *K3Y = B(cv.k3y), *YV = B(cv.yv), *INP = B(cv.inp), *T = B(cv.t);
-    auto vec = [&](const std::string& key) -> const float* { const int i = find(p, key); return i >= 0 ? p->d_vecs[i] : nullptr; };
+    auto vec = [&](const std::string& key) -> const float* { const int i = p->params.find(key); return i >= 0 ? p->d_vecs[i] : nullptr; };
     int wi = 0;
     // conv of `ksz` x `ksz` taps (zero padding ksz / 2) over C input channels of a tensor with `ctot` channels at h x w (read through nearest-2x when `up`) -> K channels of a
     // tensor with `ktot` channels, starting at the pointer given
@@ -1239,16 +1192,15 @@ extern "C" int innfer_pan_set_precision(innfer_pan* p, int fp32) {
     if (!p->uploaded) { int rc = upload(p); if (rc) return rc; }
     if (!p->f32_w.empty()) return INNFER_OK;
     const int nf = p->nf, gw = nf / 2, UF = p->unf, cq = nf / 8;
-    auto Wk = [p](const std::string& key) -> const std::vector<float>& { return p->params[find(p, key)].host; };
+    auto Wk = [p](const std::string& key) -> const std::vector<float>& { return p->params[p->params.find(key)].host; };
     std::vector<float> host;
     auto put = [&](int K, int C, int ntap, const std::function<float(int, int, int)>& w) -> int {
         host.resize(f32conv_packed_floats(K, C, ntap));
         f32conv_pack(K, C, ntap, w, host.data());
         float* d = nullptr;
-        INNFER_HIP(hipMalloc((void**)&d, host.size() * sizeof(float)));
-        p->f32_w.push_back(d);
-        INNFER_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-        return INNFER_OK;
+        const int rc = p->f32.put(&d, host);
+        if (!rc) p->f32_w.push_back(d);
+        return rc;
     };
     auto plain = [&](const std::string& key, int K, int C, int ksz) -> int {      // torch layout [K][C][ksz][ksz]
         const std::vector<float>& w = Wk(key);
@@ -1283,7 +1235,6 @@ extern "C" int innfer_pan_set_precision(innfer_pan* p, int fp32) {
         CK(plain("upsample." + std::to_string(i + 4) + ".weight", UF, UF, 3));
     }
     CK(plain("conv_last.weight", p->out_nc, UF, 3));
-#undef CK
     {   // the HR side's convs (per stage: up-conv, the PA block's 1x1 conv, HRconv; conv_last) as split panels of the halo-tile kernel (conv3x3_pc SPLIT)
         const size_t first = p->gemms.size() - 1 - 3 * (size_t)p->n_up;
         for (size_t i = first; i < p->gemms.size(); ++i) {
@@ -1304,28 +1255,26 @@ extern "C" int innfer_pan_set_precision(innfer_pan* p, int fp32) {
                     std::vector<char> gp(4096);
                     conv_pack_selfgate(wh.data(), gp.data());
                     conv_pack_selfgate(wl.data(), gp.data() + 2048);
-                    INNFER_HIP(hipMalloc(&g.d_gate_s, gp.size()));
-                    INNFER_HIP(hipMemcpy(g.d_gate_s, gp.data(), gp.size(), hipMemcpyHostToDevice));
+                    CK(p->f32.put(&g.d_gate_s, gp));
                 }
             } else conv_pack_split(w3.data(), g.K3, g.cin_pad, packed.data());
-            INNFER_HIP(hipMalloc(&g.d_w3s, packed.size()));
-            INNFER_HIP(hipMemcpy(g.d_w3s, packed.data(), packed.size(), hipMemcpyHostToDevice));
+            CK(p->f32.put(&g.d_w3s, packed));
         }
     }
     {   // the SCPA blocks as (hi, lo) blob pairs for the fused split-operand launch (pan_scpa_split.hip)
         std::vector<char> blob(pan_scpa_split_blob_bytes());
-        auto Wp = [p](const std::string& key) -> const float* { return p->params[find(p, key)].host.data(); };
+        auto Wp = [p](const std::string& key) -> const float* { return p->params[p->params.find(key)].host.data(); };
         for (int k = 0; k < (p->double_scpa ? 2 : 1); ++k)
             for (int b = 0; b < p->nb; ++b) {
                 const std::string s = "SCPA_trunk" + std::string(k ? "2" : "") + "." + std::to_string(b) + ".";
                 pan_scpa_split_pack(Wp(s + "conv1_a.weight"), Wp(s + "conv1_b.weight"), Wp(s + "k1.0.weight"), Wp(s + "PACnv.k2.weight"), Wp(s + "PACnv.k2.bias"),
                                     Wp(s + "PACnv.k3.weight"), Wp(s + "PACnv.k4.weight"), Wp(s + "conv3.weight"), blob.data());
                 void* d = nullptr;
-                INNFER_HIP(hipMalloc(&d, blob.size()));
+                CK(p->f32.put(&d, blob));
                 p->d_scpa32.push_back(d);
-                INNFER_HIP(hipMemcpy(d, blob.data(), blob.size(), hipMemcpyHostToDevice));
             }
     }
+#undef CK
     return INNFER_OK;
 }
 
@@ -1359,7 +1308,7 @@ extern "C" int innfer_pan_forward(innfer_pan* p, const void* d_in, int in_dtype,
     int dy9[9], dx9[9], d0[1] = {0};
     for (int t = 0; t < 9; ++t) { dy9[t] = t / 3 - 1; dx9[t] = t % 3 - 1; }
     int gi = 0;
-    auto vec = [&](const std::string& key) { return p->d_vecs[find(p, key)]; };
+    auto vec = [&](const std::string& key) { return p->d_vecs[p->params.find(key)]; };
     // raw GEMM rows hold only the layer's channels (rounded to 4), not the whole 64-channel tile
     int raw_rs = 64;
     auto gemm = [&](const f16* in, long in_g, int Hin, int Win, int Ho, int Wo, int up, bool full_rows = false) -> int {

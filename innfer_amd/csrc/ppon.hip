@@ -15,6 +15,7 @@
 // Activations are blocked-NHWC fp16 slabs like everywhere else; the three reconstruction heads reuse one
 // set of HR buffers.  Returns (out_c, out_s, out_p) like the reference; run.py keeps out_p.
 #include "common.h"
+#include "engine_host.h"
 #include "gather_gemm.h"
 
 #include <cmath>
@@ -105,15 +106,16 @@ __global__ void ppon_axpy(const void* x, const void* y, void* dst, float a, long
     else ((f16*)dst)[i] = (f16)(a * (float)((const f16*)x)[i] + (float)((const f16*)y)[i]);
 }
 
-struct Param { std::string key; std::vector<int> shape; std::vector<float> host; bool set = false; };
-
-struct Conv3 { int w = -1, b = -1, K = 0, C = 0; void* d_w = nullptr; float* d_b = nullptr;      // conv3x3.hip panels
-               void* d_up4 = nullptr; float* d_b4 = nullptr;     // the conv of an upconv_block also as four 2x2-tap phases (conv_pack_up2x_phases, bias once per phase)
-               void* d_up4p = nullptr;                           //   64 -> 64: the same panels in the plane row order, for the one-visit form (conv3x3_pc UP4 | ROWP, as net.hip)
-               void* d_fuse = nullptr; };                        // a head's last conv (64 -> <= 3): its panel for the epilogue of HR_conv0 (conv_pack_fuse_last)
-struct ResB { Conv3 c1; int d_w[8], d_b[8], c2_w, c2_b; void* d_dw3[8] = {};   // [0]: halo-tile panels of the eight dilated convs, back to back
-              f16* d_dw = nullptr; long dw_bytes = 0; f16* d_c2 = nullptr; float* d_dbias = nullptr; float* d_c2b = nullptr;
-              void* d_c2t = nullptr; };        // c2 as a centre-tap panel for the halo-tile kernel
+// A record's views of the engine's device blocks (innfer_ppon.weights) sit in a base of their own: value-reset as one before every upload
+struct Conv3Dev { void* d_w = nullptr; float* d_b = nullptr;      // conv3x3.hip panels
+                  void* d_up4 = nullptr; float* d_b4 = nullptr;   // the conv of an upconv_block also as four 2x2-tap phases (conv_pack_up2x_phases, bias once per phase)
+                  void* d_up4p = nullptr;                         //   64 -> 64: the same panels in the plane row order, for the one-visit form (conv3x3_pc UP4 | ROWP, as net.hip)
+                  void* d_fuse = nullptr; };                      // a head's last conv (64 -> <= 3): its panel for the epilogue of HR_conv0 (conv_pack_fuse_last)
+struct Conv3 : Conv3Dev { int w = -1, b = -1, K = 0, C = 0; };
+struct ResBDev { void* d_dw3[8] = {};   // [0]: halo-tile panels of the eight dilated convs, back to back
+                 f16* d_dw = nullptr; f16* d_c2 = nullptr; float* d_dbias = nullptr; float* d_c2b = nullptr;
+                 void* d_c2t = nullptr; };     // c2 as a centre-tap panel for the halo-tile kernel
+struct ResB : ResBDev { Conv3 c1; int d_w[8], d_b[8], c2_w, c2_b; long dw_bytes = 0; };
 struct Head { Conv3 up[3]; Conv3 hr0, hr1; };
 
 }  // namespace
@@ -121,7 +123,8 @@ struct Head { Conv3 up[3]; Conv3 hr0, hr1; };
 struct innfer_ppon {
     int in_nc = 3, out_nc = 3, nf = 64, nb = 24, scale = 4, n_up = 2;
     float alpha = 1.f;
-    std::vector<Param> params;
+    ParamTable params;
+    DeviceBufs weights, f32;                 // every device block of the network / of its fp32 panels (f32_w)
     int fea_w = -1, fea_b = -1;
     float* d_fea_w = nullptr; float* d_fea_b = nullptr;
     std::vector<ResB> rbs;                   // (nb + 4) * 3 residual blocks: CFEM trunk, SFEM, PFEM
@@ -132,16 +135,10 @@ struct innfer_ppon {
     bool uploaded = false;
 };
 
-static int PP(innfer_ppon* p, const std::string& key, std::vector<int> shape) {
-    Param q; q.key = key; q.shape = shape;
-    p->params.push_back(q);
-    return (int)p->params.size() - 1;
-}
-
 static Conv3 add_conv3(innfer_ppon* p, const std::string& key, int K, int C) {
     Conv3 c; c.K = K; c.C = C;
-    c.w = PP(p, key + ".weight", {K, C, 3, 3});
-    c.b = PP(p, key + ".bias", {K});
+    c.w = p->params.add(key + ".weight", {K, C, 3, 3});
+    c.b = p->params.add(key + ".bias", {K});
     return c;
 }
 
@@ -152,11 +149,11 @@ static void add_rrblock(innfer_ppon* p, const std::string& prefix) {
         ResB r;
         r.c1 = add_conv3(p, b + "c1", nf, nf);
         for (int d = 0; d < 8; ++d) {
-            r.d_w[d] = PP(p, b + "d" + std::to_string(d + 1) + ".weight", {nf / 2, nf, 3, 3});
-            r.d_b[d] = PP(p, b + "d" + std::to_string(d + 1) + ".bias", {nf / 2});
+            r.d_w[d] = p->params.add(b + "d" + std::to_string(d + 1) + ".weight", {nf / 2, nf, 3, 3});
+            r.d_b[d] = p->params.add(b + "d" + std::to_string(d + 1) + ".bias", {nf / 2});
         }
-        r.c2_w = PP(p, b + "c2.weight", {nf, nf * 4, 1, 1});
-        r.c2_b = PP(p, b + "c2.bias", {nf});
+        r.c2_w = p->params.add(b + "c2.weight", {nf, nf * 4, 1, 1});
+        r.c2_b = p->params.add(b + "c2.bias", {nf});
         p->rbs.push_back(r);
     }
 }
@@ -168,8 +165,8 @@ extern "C" int innfer_ppon_create(innfer_ppon** out, int in_nc, int out_nc, int 
     innfer_ppon* p = new innfer_ppon();
     p->in_nc = in_nc; p->out_nc = out_nc; p->nf = nf; p->nb = nb; p->scale = scale; p->alpha = alpha;
     p->n_up = scale == 8 ? 3 : (scale == 4 ? 2 : (scale == 2 || scale == 3 ? 1 : 0));          // upscale 3: ONE Upsample(3) stage (PPON_arch.py:20-22,33-36)
-    p->fea_w = PP(p, "CFEM.0.weight", {nf, in_nc, 3, 3});
-    p->fea_b = PP(p, "CFEM.0.bias", {nf});
+    p->fea_w = p->params.add("CFEM.0.weight", {nf, in_nc, 3, 3});
+    p->fea_b = p->params.add("CFEM.0.bias", {nf});
     for (int b = 0; b < nb; ++b) add_rrblock(p, "CFEM.1.sub." + std::to_string(b) + ".");
     p->lr = add_conv3(p, "CFEM.1.sub." + std::to_string(nb), nf, nf);
     for (int b = 0; b < 2; ++b) add_rrblock(p, "SFEM." + std::to_string(b) + ".");
@@ -186,68 +183,23 @@ extern "C" int innfer_ppon_create(innfer_ppon** out, int in_nc, int out_nc, int 
     return INNFER_OK;
 }
 
-static void free_conv3(Conv3& c) {
-    if (c.d_w) (void)hipFree(c.d_w);
-    if (c.d_b) (void)hipFree(c.d_b);
-    if (c.d_up4) (void)hipFree(c.d_up4);
-    if (c.d_up4p) (void)hipFree(c.d_up4p);
-    if (c.d_b4) (void)hipFree(c.d_b4);
-    if (c.d_fuse) (void)hipFree(c.d_fuse);
-    c.d_w = nullptr; c.d_b = nullptr; c.d_up4 = nullptr; c.d_up4p = nullptr; c.d_b4 = nullptr; c.d_fuse = nullptr;
-}
-
-static void free_device(innfer_ppon* p) {
-    for (auto v : p->f32_w) if (v) (void)hipFree(v);
-    p->f32_w.clear();
-    if (p->d_fea_w) (void)hipFree(p->d_fea_w);
-    if (p->d_fea_b) (void)hipFree(p->d_fea_b);
-    p->d_fea_w = p->d_fea_b = nullptr;
-    for (auto& r : p->rbs) {
-        free_conv3(r.c1);
-        if (r.d_dw) (void)hipFree(r.d_dw);
-        r.d_dw = nullptr;
-        for (auto& w3 : r.d_dw3) { if (w3) (void)hipFree(w3); w3 = nullptr; }
-        if (r.d_c2) (void)hipFree(r.d_c2);
-        if (r.d_c2t) (void)hipFree(r.d_c2t);
-        r.d_c2t = nullptr;
-        if (r.d_dbias) (void)hipFree(r.d_dbias);
-        if (r.d_c2b) (void)hipFree(r.d_c2b);
-        r.d_c2 = nullptr; r.d_dbias = r.d_c2b = nullptr;
-    }
-    free_conv3(p->lr);
-    for (auto& H : p->heads) { for (auto& u : H.up) free_conv3(u); free_conv3(H.hr0); free_conv3(H.hr1); }
-}
-
-extern "C" void innfer_ppon_destroy(innfer_ppon* p) {
-    if (!p) return;
-    free_device(p);
-    delete p;
-}
+extern "C" void innfer_ppon_destroy(innfer_ppon* p) { delete p; }
 
 extern "C" int innfer_ppon_num_params(innfer_ppon* p) { return p ? (int)p->params.size() : INNFER_ERR_INVALID; }
 
 extern "C" int innfer_ppon_param_info(innfer_ppon* p, int idx, char* key, size_t key_cap, int* ndim, int* shape4) {
-    if (!p || idx < 0 || idx >= (int)p->params.size()) return set_error(INNFER_ERR_INVALID, "ppon_param_info: bad index");
-    const Param& q = p->params[idx];
-    if (key && key_cap) { strncpy(key, q.key.c_str(), key_cap - 1); key[key_cap - 1] = 0; }
-    if (ndim) *ndim = (int)q.shape.size();
-    if (shape4) for (size_t i = 0; i < 4; ++i) shape4[i] = i < q.shape.size() ? q.shape[i] : 1;
-    return INNFER_OK;
+    return ParamTable::of(p).info("ppon", idx, key, key_cap, ndim, shape4);
 }
 
 extern "C" int innfer_ppon_set_param(innfer_ppon* p, int idx, const float* h_data) {
-    if (!p || idx < 0 || idx >= (int)p->params.size() || !h_data) return set_error(INNFER_ERR_INVALID, "ppon_set_param: bad arguments");
-    Param& q = p->params[idx];
-    size_t n = 1;
-    for (int s : q.shape) n *= (size_t)s;
-    q.host.assign(h_data, h_data + n);
-    q.set = true;
-    p->uploaded = false;
-    return INNFER_OK;
+    const int rc = ParamTable::of(p).set("ppon", idx, h_data);
+    if (!rc) p->uploaded = false;
+    return rc;
 }
 
 namespace {
 
+#define CK(e) do { int _rc = (e); if (_rc) return _rc; } while (0)
 int upload_conv3(innfer_ppon* p, Conv3& c, int role = 0) {       // role 1: the conv of an upconv_block (factor 2), 2: a head's last conv
     const std::vector<float>& w = p->params[c.w].host;
     const std::vector<float>& b = p->params[c.b].host;
@@ -257,37 +209,36 @@ int upload_conv3(innfer_ppon* p, Conv3& c, int role = 0) {       // role 1: the 
     const size_t bias_n = (size_t)((c.K + per - 1) / per) * per;
     std::vector<float> bias(bias_n, 0.f);
     for (int k = 0; k < c.K; ++k) bias[k] = b[k];
-    INNFER_HIP(hipMalloc(&c.d_w, host.size()));
-    INNFER_HIP(hipMalloc((void**)&c.d_b, bias_n * sizeof(float)));
-    INNFER_HIP(hipMemcpy(c.d_w, host.data(), host.size(), hipMemcpyHostToDevice));
-    INNFER_HIP(hipMemcpy(c.d_b, bias.data(), bias_n * sizeof(float), hipMemcpyHostToDevice));
+    DeviceBufs& dev = p->weights;
+    static_cast<Conv3Dev&>(c) = Conv3Dev{};
+    CK(dev.put(&c.d_w, host));
+    CK(dev.put(&c.d_b, bias));
     if (role == 1 && c.K % 64 == 0 && c.C % 32 == 0) {
         std::vector<char> pk(conv_packed_bytes_deconv2x(c.K, c.C));
         conv_pack_up2x_phases(w.data(), c.K, c.C, pk.data());
         std::vector<float> b4((size_t)4 * c.K);
         for (int ph = 0; ph < 4; ++ph) for (int k = 0; k < c.K; ++k) b4[(size_t)ph * c.K + k] = b[k];
-        INNFER_HIP(hipMalloc(&c.d_up4, pk.size()));
-        INNFER_HIP(hipMalloc((void**)&c.d_b4, b4.size() * sizeof(float)));
-        INNFER_HIP(hipMemcpy(c.d_up4, pk.data(), pk.size(), hipMemcpyHostToDevice));
-        INNFER_HIP(hipMemcpy(c.d_b4, b4.data(), b4.size() * sizeof(float), hipMemcpyHostToDevice));
+        CK(dev.put(&c.d_up4, pk));
+        CK(dev.put(&c.d_b4, b4));
         if (c.K == 64 && c.C == 64) {
             conv_pack_up2x_phases(w.data(), c.K, c.C, pk.data(), 1);
-            INNFER_HIP(hipMalloc(&c.d_up4p, pk.size()));
-            INNFER_HIP(hipMemcpy(c.d_up4p, pk.data(), pk.size(), hipMemcpyHostToDevice));
+            CK(dev.put(&c.d_up4p, pk));
         }
     }
     if (role == 2 && c.C == 64 && c.K <= 3) {
         std::vector<char> fp(4096);
         conv_pack_fuse_last(w.data(), c.K, fp.data());
-        INNFER_HIP(hipMalloc(&c.d_fuse, fp.size()));
-        INNFER_HIP(hipMemcpy(c.d_fuse, fp.data(), fp.size(), hipMemcpyHostToDevice));
+        CK(dev.put(&c.d_fuse, fp));
     }
     return INNFER_OK;
 }
 
 int upload(innfer_ppon* p) {
-    for (auto& q : p->params) if (!q.set) return set_error(INNFER_ERR_INVALID, "ppon: parameter '%s' was never set", q.key.c_str());
-    free_device(p);
+    CK(p->params.require_all_set("ppon", false));
+    DeviceBufs& dev = p->weights;
+    dev.clear();
+    p->f32.clear();                          // the fp32 panels follow the parameters: rebuilt by innfer_ppon_set_precision
+    p->f32_w.clear();
     const int nf = p->nf;
     {   // first conv: [Cin*9][K] fp32, k-major (conv_first.hip)
         const std::vector<float>& w = p->params[p->fea_w].host;
@@ -295,16 +246,13 @@ int upload(innfer_ppon* p) {
         for (int ci = 0; ci < p->in_nc; ++ci)
             for (int tp = 0; tp < 9; ++tp)
                 for (int k = 0; k < nf; ++k) t[((size_t)ci * 9 + tp) * nf + k] = w[((size_t)k * p->in_nc + ci) * 9 + tp];
-        INNFER_HIP(hipMalloc((void**)&p->d_fea_w, t.size() * sizeof(float)));
-        INNFER_HIP(hipMemcpy(p->d_fea_w, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
-        const std::vector<float>& b = p->params[p->fea_b].host;
-        INNFER_HIP(hipMalloc((void**)&p->d_fea_b, nf * sizeof(float)));
-        INNFER_HIP(hipMemcpy(p->d_fea_b, b.data(), nf * sizeof(float), hipMemcpyHostToDevice));
+        CK(dev.put(&p->d_fea_w, t));
+        CK(dev.put(&p->d_fea_b, p->params[p->fea_b].host));
     }
     std::vector<f16> panel;
     for (auto& r : p->rbs) {
-        int rc = upload_conv3(p, r.c1);
-        if (rc) return rc;
+        static_cast<ResBDev&>(r) = ResBDev{};
+        CK(upload_conv3(p, r.c1));
         std::vector<float> dbias(256);
         std::vector<f16> all;                                     // the eight dilated convs' panels, back to back
         for (int d = 0; d < 8; ++d) {
@@ -319,36 +267,30 @@ int upload(innfer_ppon* p) {
             const size_t pb = conv_packed_bytes(nf / 2, nf);
             std::vector<char> packed(8 * pb);
             for (int d = 0; d < 8; ++d) conv_pack(p->params[r.d_w[d]].host.data(), nf / 2, nf, packed.data() + d * pb);
-            INNFER_HIP(hipMalloc(&r.d_dw3[0], packed.size()));
-            INNFER_HIP(hipMemcpy(r.d_dw3[0], packed.data(), packed.size(), hipMemcpyHostToDevice));
+            CK(dev.put(&r.d_dw3[0], packed));
         }
-        INNFER_HIP(hipMalloc((void**)&r.d_dw, all.size() * sizeof(f16)));
-        INNFER_HIP(hipMemcpy(r.d_dw, all.data(), all.size() * sizeof(f16), hipMemcpyHostToDevice));
-        INNFER_HIP(hipMalloc((void**)&r.d_dbias, 256 * sizeof(float)));
-        INNFER_HIP(hipMemcpy(r.d_dbias, dbias.data(), 256 * sizeof(float), hipMemcpyHostToDevice));
+        CK(dev.put(&r.d_dw, all));
+        CK(dev.put(&r.d_dbias, dbias));
         const std::vector<float>& w2 = p->params[r.c2_w].host;
         gg::pack_panels(panel, nf, 4 * nf, 4 * nf, 1, [&](int co, int ci, int) { return w2[(size_t)co * 4 * nf + ci]; });
-        INNFER_HIP(hipMalloc((void**)&r.d_c2, panel.size() * sizeof(f16)));
-        INNFER_HIP(hipMemcpy(r.d_c2, panel.data(), panel.size() * sizeof(f16), hipMemcpyHostToDevice));
+        CK(dev.put(&r.d_c2, panel));
         if (nf == 64) {
             std::vector<char> pk(conv_packed_bytes_taps(nf, 4 * nf, TAPS_1X1));
             conv_pack_1x1(w2.data(), nf, 4 * nf, pk.data());
-            INNFER_HIP(hipMalloc(&r.d_c2t, pk.size()));
-            INNFER_HIP(hipMemcpy(r.d_c2t, pk.data(), pk.size(), hipMemcpyHostToDevice));
+            CK(dev.put(&r.d_c2t, pk));
         }
-        INNFER_HIP(hipMalloc((void**)&r.d_c2b, nf * sizeof(float)));
-        INNFER_HIP(hipMemcpy(r.d_c2b, p->params[r.c2_b].host.data(), nf * sizeof(float), hipMemcpyHostToDevice));
+        CK(dev.put(&r.d_c2b, p->params[r.c2_b].host));
     }
-    int rc = upload_conv3(p, p->lr);
-    if (rc) return rc;
+    CK(upload_conv3(p, p->lr));
     for (auto& H : p->heads) {
-        for (int u = 0; u < p->n_up; ++u) { rc = upload_conv3(p, H.up[u], p->scale == 3 ? 0 : 1); if (rc) return rc; }
-        rc = upload_conv3(p, H.hr0); if (rc) return rc;
-        rc = upload_conv3(p, H.hr1, 2); if (rc) return rc;
+        for (int u = 0; u < p->n_up; ++u) CK(upload_conv3(p, H.up[u], p->scale == 3 ? 0 : 1));
+        CK(upload_conv3(p, H.hr0));
+        CK(upload_conv3(p, H.hr1, 2));
     }
     p->uploaded = true;
     return INNFER_OK;
 }
+#undef CK
 
 // nearest 3x of a 64-channel slab (two groups), 8 channels per thread
 __global__ void ppon_upsample3(const f16* src, long src_g, f16* dst, long dst_g, int N, int H, int W) {
@@ -515,10 +457,9 @@ extern "C" int innfer_ppon_set_precision(innfer_ppon* p, int fp32) {
         host.resize(f32conv_packed_floats(K, C, T));
         f32conv_pack(K, C, T, [&w, C, T](int k, int c, int t) { return w[((size_t)k * C + c) * T + t]; }, host.data());
         float* d = nullptr;
-        INNFER_HIP(hipMalloc((void**)&d, host.size() * sizeof(float)));
-        p->f32_w.push_back(d);
-        INNFER_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-        return INNFER_OK;
+        const int rc = p->f32.put(&d, host);
+        if (!rc) p->f32_w.push_back(d);
+        return rc;
     };
 #define CK(e) do { int _rc = (e); if (_rc) return _rc; } while (0)
     const int nf = p->nf;

@@ -12,9 +12,11 @@
 //   ConvTranspose2d(3, stride 2, padding 1, output_padding 1)         four output phases (1, 2, 2, 4 taps) of the same GEMM
 //   InstanceNorm2d (no affine, statistics of the instance also under eval)   norm_stats.h: per-(image, channel) mean / biased variance in
 //                                                                     fp32, one read; the conv bias cancels in the norm
-//   ReLU / residual add / Tanh                                        rn_post, rn_final
+//   ReLU / residual add / Tanh                                        rn_post, engine_pass.h
 // Activations are blocked-NHWC fp16 slabs, GEMM results fp32 rows.  A batch is N independent images.
 #include "common.h"
+#include "engine_host.h"
+#include "engine_pass.h"
 #include "gather_gemm.h"
 #include "norm_stats.h"
 
@@ -175,38 +177,14 @@ __global__ void rn_fill_ev(const float* ev_alpha, const float* ev_shift, float* 
 }
 
 // rn_post_slab behind a conv that left its statistics as partials (conv3x3.hip epilogue_stats): a workgroup owns PXB pixels of one (image, 32-channel
-// group), merges that group's records itself -- 8 lanes per channel, Chan's update, lanes merged in order: every workgroup of the group computes the
-// same (alpha, shift) -- and applies them: the combine launch between conv and post is gone.  pxb = 1024 pixels per workgroup where that still gives
+// group, C % 32 == 0), merges that group's records itself (norm::merge_group_parts) and applies them: the combine launch between conv and post is
+// gone.  pxb = 1024 pixels per workgroup where that still gives
 // the chip a workgroup per CU, 256 below (one image: 0.887 -> 0.858 ms with 256, sixteen: 2.50 -> 2.46 ms with 1024).
 __global__ __launch_bounds__(256) void rn_post_slab_parts(const f16* src, int C, long HW, const float* part, int nper, float eps, const float* gamma,
                                                           const float* beta, int relu, const f16* res, f16* dst, long g, int pxb) {
-    __shared__ float sn[8][32], sm[8][32], sq[8][32], sal[32], ssh[32];
+    __shared__ float sal[32], ssh[32];
     const int n = blockIdx.z, cb = blockIdx.y * 32, t = threadIdx.x;
-    {
-        const int cl = t & 31, lg = t >> 5, c = cb + cl;
-        float cnt = 0.f, mu = 0.f, m2 = 0.f;
-        if (c < C)
-            for (int r = lg; r < nper; r += 32) {          // four records per trip, their loads issued together (as unet_post_slab_parts, round 5): same merge order, same bits
-                float rec[4][3];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int rr = r + 8 * j;
-                    const float* q = part + (((long)n * nper + min(rr, nper - 1)) * C + c) * 3;
-                    rec[j][0] = rr < nper ? q[0] : 0.f; rec[j][1] = q[1]; rec[j][2] = q[2];
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j) norm::chan_merge(cnt, mu, m2, rec[j][0], rec[j][1], rec[j][2]);      // (count 0: no-op)
-            }
-        sn[lg][cl] = cnt; sm[lg][cl] = mu; sq[lg][cl] = m2;
-        __syncthreads();
-        if (lg == 0) {
-            for (int i = 1; i < 8; ++i) norm::chan_merge(cnt, mu, m2, sn[i][cl], sm[i][cl], sq[i][cl]);
-            const float a = (1.0f / sqrtf(m2 / (float)HW + eps)) * ((gamma && c < C) ? gamma[c] : 1.0f);
-            sal[cl] = a;
-            ssh[cl] = ((beta && c < C) ? beta[c] : 0.f) - mu * a;
-        }
-        __syncthreads();
-    }
+    norm::merge_group_parts(part, nper, n, cb, C, HW, eps, gamma, beta, sal, ssh);
     const int q8 = (t & 3) * 8, pl = t >> 2;
     float al[8], sh[8];
 #pragma unroll
@@ -273,17 +251,6 @@ __global__ void rn_pre(const void* in, int in_f32, int C, int H, int W, int N, f
     for (int q = 0; q < 4; ++q) *(f16x8*)(slab + i * 32 + 8 * q) = *(const f16x8*)(v + 8 * q);
 }
 
-__global__ void rn_final(const float* raw, int rs, int C, long HW, int N, const float* bias, void* out, int out_f32) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)N * HW) return;
-    const long n = i / HW, px = i % HW;
-    for (int c = 0; c < C; ++c) {
-        const float y = fast_tanh(raw[i * rs + c] + bias[c]);
-        const long o = (n * C + c) * HW + px;
-        if (out_f32) ((float*)out)[o] = y; else ((f16*)out)[o] = (f16)y;
-    }
-}
-
 // ---- the launches of the pass kernels above as the network makes them: shared by innfer_resnet_forward and by the single-launch entry points of ABI 123
 // ---- (innfer_resnet_pre .. innfer_resnet_sum9_tanh), so a test of a kernel runs the network's launch
 int launch_rn_post(const float* raw, int cpad, int C, long HW, int N, const float* alpha, const float* shift, int relu, const f16* res, f16* dst, long g, hipStream_t s) {
@@ -323,27 +290,24 @@ int launch_rn_pre(const void* in, int in_f32, int C, int H, int W, int N, f16* s
     return INNFER_OK;
 }
 
-int launch_rn_final(const float* raw, int rs, int C, long HW, int N, const float* bias, void* out, int out_f32, hipStream_t s) {
-    hipLaunchKernelGGL(rn_final, dim3((unsigned)(((long)N * HW + 255) / 256)), dim3(256), 0, s, raw, rs, C, HW, N, bias, out, out_f32);
-    INNFER_HIP(hipGetLastError());
-    return INNFER_OK;
-}
-
-struct Param { std::string key; std::vector<int> shape; std::vector<float> host; bool set = false; };
-struct Layer { int w = -1, b = -1, cin = 0, cout = 0, k = 3; bool transposed = false; std::vector<f16*> d_w; float* d_b = nullptr;
-               void* d_w3 = nullptr;
-               float* d_b4 = nullptr;      // ConvTranspose layers on the halo-tile kernel: the bias once per output phase
-               int g = -1, be = -1, rm = -1, rv = -1;          // norm_type 'batch': the BatchNorm2d behind this conv (weight, bias, running_mean, running_var)
-               float *d_gamma = nullptr, *d_beta = nullptr, *d_ev_alpha = nullptr, *d_ev_shift = nullptr;
-               void* d_w27 = nullptr; float* d_z32 = nullptr;   // last 7x7 conv as a 3x3 conv over nine sub-blocks (rn_sum9_tanh): panels [9 * cout][cin][3][3], zero bias
-               bool up2 = false; };        // upsample_mode 'upconv': Upsample(nearest 2x) + 3x3 conv on the halo-tile kernel (nearest-2x in the loader)    // residual-block convs: conv3x3.hip panels (reflection padding in the halo-tile loader)
+struct LayerDev {                      // a layer's views of the engine's device blocks (innfer_resnet.weights): value-reset as one before every upload
+    std::vector<f16*> d_w; float* d_b = nullptr;
+    void* d_w3 = nullptr;              // residual-block convs: conv3x3.hip panels (reflection padding in the halo-tile loader)
+    float* d_b4 = nullptr;             // ConvTranspose layers on the halo-tile kernel: the bias once per output phase
+    float *d_gamma = nullptr, *d_beta = nullptr, *d_ev_alpha = nullptr, *d_ev_shift = nullptr;
+    void* d_w27 = nullptr; float* d_z32 = nullptr;   // last 7x7 conv as a 3x3 conv over nine sub-blocks (rn_sum9_tanh): panels [9 * cout][cin][3][3], zero bias
+};
+struct Layer : LayerDev { int w = -1, b = -1, cin = 0, cout = 0, k = 3; bool transposed = false;
+                          int g = -1, be = -1, rm = -1, rv = -1;          // norm_type 'batch': the BatchNorm2d behind this conv (weight, bias, running_mean, running_var)
+                          bool up2 = false; };        // upsample_mode 'upconv': Upsample(nearest 2x) + 3x3 conv on the halo-tile kernel (nearest-2x in the loader)
 
 }  // namespace
 
 struct innfer_resnet {
     int in_nc = 3, out_nc = 3, ngf = 64, n_blocks = 9;
     int block_pad = 1;               // padding of the residual blocks' convs as a ConvLaunch.reflect code: 1 reflect, 2 replicate, 0 zero
-    std::vector<Param> params;
+    ParamTable params;
+    DeviceBufs weights, f32;         // every device block of the network / of its fp32 panels (f32_w)
     std::vector<Layer> layers;       // first, down1, down2, 2*n_blocks block convs, up1, up2, last
     bool fp32 = false;               // innfer_resnet_set_precision(1): the fp32 forward on NCHW fp32 tensors (f32ops.hip), the reference's -no_fp16 mode
     std::vector<std::vector<float*>> f32_w;   //   f32conv panels per layer (a ConvTranspose2d: one per output phase)
@@ -353,23 +317,17 @@ struct innfer_resnet {
     bool eval_mode = false;          // BatchNorm on its running statistics (nn.Module.eval()); train(): the statistics of the image, like pix2pix's UNet
 };
 
-static int RP(innfer_resnet* r, const std::string& key, std::vector<int> shape) {
-    Param q; q.key = key; q.shape = shape;
-    r->params.push_back(q);
-    return (int)r->params.size() - 1;
-}
-
 // norm: state-dict prefix of the norm layer that follows the conv ("" behind the last conv); with norm_type 'batch' the conv then has no bias and the
 // BatchNorm2d's parameters and buffers follow it in the state dict
 static void add_layer(innfer_resnet* r, const std::string& key, int cin, int cout, int k, bool transposed, const std::string& norm = "") {
     Layer l; l.cin = cin; l.cout = cout; l.k = k; l.transposed = transposed;
-    l.w = RP(r, key + ".weight", transposed ? std::vector<int>{cin, cout, k, k} : std::vector<int>{cout, cin, k, k});
+    l.w = r->params.add(key + ".weight", transposed ? std::vector<int>{cin, cout, k, k} : std::vector<int>{cout, cin, k, k});
     const bool bn = r->batch_norm && !norm.empty();
-    if (!bn) l.b = RP(r, key + ".bias", {cout});
+    if (!bn) l.b = r->params.add(key + ".bias", {cout});
     if (bn) {
-        l.g = RP(r, norm + ".weight", {cout}); l.be = RP(r, norm + ".bias", {cout});
-        l.rm = RP(r, norm + ".running_mean", {cout}); l.rv = RP(r, norm + ".running_var", {cout});
-        RP(r, norm + ".num_batches_tracked", {});
+        l.g = r->params.add(norm + ".weight", {cout}); l.be = r->params.add(norm + ".bias", {cout});
+        l.rm = r->params.add(norm + ".running_mean", {cout}); l.rv = r->params.add(norm + ".running_var", {cout});
+        r->params.add(norm + ".num_batches_tracked", {});
     }
     r->layers.push_back(l);
 }
@@ -427,7 +385,7 @@ extern "C" int innfer_resnet_sum9_tanh(const float* d_q, const float* d_bias, vo
 extern "C" int innfer_resnet_final(const float* d_raw, int rs, int C, int64_t HW, int N, const float* d_bias, void* d_out, int out_dtype, void* stream) {
     if (!d_raw || !d_bias || !d_out || (out_dtype != INNFER_F16 && out_dtype != INNFER_F32) || C <= 0 || rs < C || HW <= 0 || N <= 0)
         return set_error(INNFER_ERR_INVALID, "resnet_final: null argument, dtype %d, C=%d, row of %d floats, HW=%lld, N=%d", out_dtype, C, rs, (long long)HW, N);
-    return launch_rn_final(d_raw, rs, C, (long)HW, N, d_bias, d_out, out_dtype == INNFER_F32, (hipStream_t)stream);
+    return launch_tanh_bias_to_nchw(d_raw, rs, C, (long)HW, N, d_bias, d_out, out_dtype == INNFER_F32, (hipStream_t)stream);
 }
 
 extern "C" int innfer_resnet_create(innfer_resnet** out, int in_nc, int out_nc, int ngf, int n_blocks) {
@@ -473,52 +431,18 @@ extern "C" int innfer_resnet_create_ex(innfer_resnet** out, int in_nc, int out_n
     return INNFER_OK;
 }
 
-static void rn_free(innfer_resnet* r) {
-    for (auto& vv : r->f32_w) for (auto v : vv) if (v) (void)hipFree(v);          // (the fp32 panels follow the parameters: rebuilt by innfer_resnet_set_precision)
-    r->f32_w.clear();
-    for (auto& l : r->layers) {
-        for (auto w : l.d_w) if (w) (void)hipFree(w);
-        l.d_w.clear();
-        if (l.d_b) (void)hipFree(l.d_b);
-        l.d_b = nullptr;
-        if (l.d_w3) (void)hipFree(l.d_w3);
-        l.d_w3 = nullptr;
-        if (l.d_b4) (void)hipFree(l.d_b4);
-        l.d_b4 = nullptr;
-        for (float** q : {&l.d_gamma, &l.d_beta, &l.d_ev_alpha, &l.d_ev_shift}) { if (*q) (void)hipFree(*q); *q = nullptr; }
-        if (l.d_w27) (void)hipFree(l.d_w27);
-        l.d_w27 = nullptr;
-        if (l.d_z32) (void)hipFree(l.d_z32);
-        l.d_z32 = nullptr;
-    }
-}
-
-extern "C" void innfer_resnet_destroy(innfer_resnet* r) {
-    if (!r) return;
-    rn_free(r);
-    delete r;
-}
+extern "C" void innfer_resnet_destroy(innfer_resnet* r) { delete r; }
 
 extern "C" int innfer_resnet_num_params(innfer_resnet* r) { return r ? (int)r->params.size() : INNFER_ERR_INVALID; }
 
 extern "C" int innfer_resnet_param_info(innfer_resnet* r, int idx, char* key, size_t key_cap, int* ndim, int* shape4) {
-    if (!r || idx < 0 || idx >= (int)r->params.size()) return set_error(INNFER_ERR_INVALID, "resnet_param_info: bad index");
-    const Param& q = r->params[idx];
-    if (key && key_cap) { strncpy(key, q.key.c_str(), key_cap - 1); key[key_cap - 1] = 0; }
-    if (ndim) *ndim = (int)q.shape.size();
-    if (shape4) for (size_t i = 0; i < 4; ++i) shape4[i] = i < q.shape.size() ? q.shape[i] : 1;
-    return INNFER_OK;
+    return ParamTable::of(r).info("resnet", idx, key, key_cap, ndim, shape4);
 }
 
 extern "C" int innfer_resnet_set_param(innfer_resnet* r, int idx, const float* h_data) {
-    if (!r || idx < 0 || idx >= (int)r->params.size() || !h_data) return set_error(INNFER_ERR_INVALID, "resnet_set_param: bad arguments");
-    Param& q = r->params[idx];
-    size_t n = 1;
-    for (int s : q.shape) n *= (size_t)s;
-    q.host.assign(h_data, h_data + n);
-    q.set = true;
-    r->uploaded = false;
-    return INNFER_OK;
+    const int rc = ParamTable::of(r).set("resnet", idx, h_data);
+    if (!rc) r->uploaded = false;
+    return rc;
 }
 
 namespace {
@@ -531,12 +455,15 @@ int phase_taps1d(int a, int ky[2], int d[2]) {
 }
 
 int rn_upload(innfer_resnet* r) {
-    for (auto& q : r->params)
-        if (!q.set && q.key.find("running_") == std::string::npos && q.key.find("num_batches") == std::string::npos)
-            return set_error(INNFER_ERR_INVALID, "resnet: parameter '%s' was never set", q.key.c_str());
-    rn_free(r);
+    int rc = r->params.require_all_set("resnet", true);
+    if (rc) return rc;
+    DeviceBufs& dev = r->weights;
+    dev.clear();
+    r->f32.clear();                  // the fp32 panels follow the parameters: rebuilt by innfer_resnet_set_precision
+    r->f32_w.clear();
     std::vector<f16> panel;
     for (auto& l : r->layers) {
+        static_cast<LayerDev&>(l) = LayerDev{};
         const std::vector<float>& w = r->params[l.w].host;
         const std::vector<float> bias = l.b >= 0 ? r->params[l.b].host : std::vector<float>((size_t)l.cout, 0.f);     // no conv bias in front of a BatchNorm2d
         if (l.g >= 0) {
@@ -552,53 +479,46 @@ int rn_upload(innfer_resnet* r) {
             }
             for (auto pr : {std::make_pair(&l.d_gamma, &g), std::make_pair(&l.d_beta, &b), std::make_pair(&l.d_ev_alpha, (const std::vector<float>*)&al),
                             std::make_pair(&l.d_ev_shift, (const std::vector<float>*)&sh)}) {
-                INNFER_HIP(hipMalloc((void**)pr.first, l.cout * sizeof(float)));
-                INNFER_HIP(hipMemcpy(*pr.first, pr.second->data(), l.cout * sizeof(float), hipMemcpyHostToDevice));
+                rc = dev.put(pr.first, *pr.second); if (rc) return rc;
             }
         }
         const int cin_pad = (l.cin + 31) / 32 * 32, k = l.k;
         auto put = [&](int ntaps, auto weight_of) -> int {
             gg::pack_panels(panel, l.cout, l.cin, cin_pad, ntaps, weight_of);
             f16* d = nullptr;
-            INNFER_HIP(hipMalloc((void**)&d, panel.size() * sizeof(f16)));
-            INNFER_HIP(hipMemcpy(d, panel.data(), panel.size() * sizeof(f16), hipMemcpyHostToDevice));
-            l.d_w.push_back(d);
-            return INNFER_OK;
+            const int prc = dev.put(&d, panel);
+            if (!prc) l.d_w.push_back(d);
+            return prc;
         };
         if (!l.transposed && k == 7 && 7 * l.cin <= 32) {       // first conv on the row-patch slab (rn_pre): tap = ky, channel kx*cin + c
             gg::pack_panels(panel, l.cout, 7 * l.cin, 32, 7, [&](int co, int j, int ky) {
                 const int kx = j / l.cin, c = j - kx * l.cin;
                 return w[((size_t)co * l.cin + c) * 49 + ky * 7 + kx]; });
             f16* d = nullptr;
-            INNFER_HIP(hipMalloc((void**)&d, panel.size() * sizeof(f16)));
-            INNFER_HIP(hipMemcpy(d, panel.data(), panel.size() * sizeof(f16), hipMemcpyHostToDevice));
+            rc = dev.put(&d, panel); if (rc) return rc;
             l.d_w.push_back(d);
         } else if (!l.transposed) {
-            int rc = put(k * k, [&](int co, int ci, int t) { return w[((size_t)co * l.cin + ci) * k * k + t]; });
+            rc = put(k * k, [&](int co, int ci, int t) { return w[((size_t)co * l.cin + ci) * k * k + t]; });
             if (rc) return rc;
         } else {
             for (int ph = 0; ph < 4; ++ph) {
                 int kyv[2], dyv[2], kxv[2], dxv[2];
                 const int ny = phase_taps1d(ph >> 1, kyv, dyv), nx = phase_taps1d(ph & 1, kxv, dxv);
-                int rc = put(ny * nx, [&](int co, int ci, int t) {
+                rc = put(ny * nx, [&](int co, int ci, int t) {
                     const int ky = kyv[t / nx], kx = kxv[t % nx];
                     return w[(((size_t)ci * l.cout + co) * 3 + ky) * 3 + kx];          // ConvTranspose2d weight is [in, out, kH, kW]
                 });
                 if (rc) return rc;
             }
         }
-        INNFER_HIP(hipMalloc((void**)&l.d_b, l.cout * sizeof(float)));
-        INNFER_HIP(hipMemcpy(l.d_b, bias.data(), l.cout * sizeof(float), hipMemcpyHostToDevice));
+        rc = dev.put(&l.d_b, bias); if (rc) return rc;
         if (!l.transposed && k == 7 && l.cin % 32 == 0 && l.cout <= 16) {          // c7s1-out: nine displaced 3x3 convs, ReflectionPad2d(3)
             std::vector<char> packed(conv_packed_bytes7x7(l.cout, l.cin));
             conv_pack7x7(w.data(), l.cout, l.cin, packed.data());
-            INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-            INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
+            rc = dev.put(&l.d_w3, packed); if (rc) return rc;
             std::vector<float> b3(64, 0.f);
             for (int c = 0; c < l.cout; ++c) b3[c] = bias[c];
-            (void)hipFree(l.d_b); l.d_b = nullptr;
-            INNFER_HIP(hipMalloc((void**)&l.d_b, b3.size() * sizeof(float)));
-            INNFER_HIP(hipMemcpy(l.d_b, b3.data(), b3.size() * sizeof(float), hipMemcpyHostToDevice));
+            rc = dev.put(&l.d_b, b3); if (rc) return rc;      // replaces the cout-float bias above, whose block lives on until the next clear()
         }
         if (!l.transposed && k == 7 && 7 * l.cin <= 32 && l.cout % 32 == 0) {
             // first conv over the row-patch slab (rn_pre) as a 7 x 1 column conv on the halo-tile kernel (three vertically displaced 3-tap blocks,
@@ -610,8 +530,7 @@ int rn_upload(innfer_resnet* r) {
                         for (int ky = 0; ky < 7; ++ky) wv[((size_t)co * 32 + kx * l.cin + c) * 7 + ky] = w[((size_t)co * l.cin + c) * 49 + ky * 7 + kx];
             std::vector<char> packed(conv_packed_bytes7v(l.cout, 32));
             conv_pack7v(wv.data(), l.cout, 32, packed.data());
-            INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-            INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
+            rc = dev.put(&l.d_w3, packed); if (rc) return rc;
         }
         if (!l.transposed && k == 7 && l.cin % 32 == 0 && 9 * l.cout <= 32) {
             const int K9 = 9 * l.cout;
@@ -626,10 +545,8 @@ int rn_upload(innfer_resnet* r) {
                     }
             std::vector<char> packed(conv_packed_bytes(K9, l.cin));
             conv_pack(w27.data(), K9, l.cin, packed.data());
-            INNFER_HIP(hipMalloc(&l.d_w27, packed.size()));
-            INNFER_HIP(hipMemcpy(l.d_w27, packed.data(), packed.size(), hipMemcpyHostToDevice));
-            INNFER_HIP(hipMalloc((void**)&l.d_z32, z32.size() * sizeof(float)));
-            INNFER_HIP(hipMemcpy(l.d_z32, z32.data(), z32.size() * sizeof(float), hipMemcpyHostToDevice));
+            rc = dev.put(&l.d_w27, packed); if (rc) return rc;
+            rc = dev.put(&l.d_z32, z32); if (rc) return rc;
         }
         if (l.transposed && k == 3 && l.cout % 64 == 0 && l.cin % 32 == 0) {
             // ConvTranspose2d(3, stride 2, padding 1, output_padding 1) on the halo-tile kernel (conv3x3_pc<.., TM = TAPS_PHASE>, see unet.hip): output phase
@@ -639,16 +556,13 @@ int rn_upload(innfer_resnet* r) {
             for (int co = 0; co < 4 * l.cout; ++co) b4[co] = bias[co % l.cout];
             std::vector<char> packed(conv_packed_bytes_deconv2x(l.cout, l.cin));
             conv_pack_deconv2x(w.data(), l.cout, l.cin, 3, packed.data());
-            INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-            INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
-            INNFER_HIP(hipMalloc((void**)&l.d_b4, b4.size() * sizeof(float)));
-            INNFER_HIP(hipMemcpy(l.d_b4, b4.data(), b4.size() * sizeof(float), hipMemcpyHostToDevice));
+            rc = dev.put(&l.d_w3, packed); if (rc) return rc;
+            rc = dev.put(&l.d_b4, b4); if (rc) return rc;
         }
         if (l.up2 || (!l.transposed && k == 3 && l.cin == l.cout && l.cin % 64 == 0)) {       // ResnetBlock convs (stride 1, pad 1) and the upconv convs
             std::vector<char> packed(conv_packed_bytes(l.cout, l.cin));
             conv_pack(w.data(), l.cout, l.cin, packed.data());
-            INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-            INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
+            rc = dev.put(&l.d_w3, packed); if (rc) return rc;
         }
     }
     r->uploaded = true;
@@ -777,10 +691,9 @@ extern "C" int innfer_resnet_set_precision(innfer_resnet* r, int fp32) {
         host.resize(f32conv_packed_floats(K, C, ntap));
         f32conv_pack(K, C, ntap, w, host.data());
         float* d = nullptr;
-        INNFER_HIP(hipMalloc((void**)&d, host.size() * sizeof(float)));
-        dst.push_back(d);
-        INNFER_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-        return INNFER_OK;
+        const int rc = r->f32.put(&d, host);
+        if (!rc) dst.push_back(d);
+        return rc;
     };
     r->f32_w.assign(r->layers.size(), {});
     for (size_t li = 0; li < r->layers.size(); ++li) {
@@ -1034,7 +947,7 @@ extern "C" int innfer_resnet_forward(innfer_resnet* r, const void* d_in, int in_
         }
         const int rs = (l.cout + 3) / 4 * 4;
         CK(gg::launch(l.d_w[0], (l.cin + 31) / 32 * 32, 64, U2, (long)N * H * W * 32, N, H, W, raw, H, W, 1, 49, dy49, dx49, H, W, 1, 0, 0, 0, s, nullptr, 0, rs, 1));
-        CK(launch_rn_final((const float*)raw, rs, l.cout, (long)H * W, N, (const float*)l.d_b, d_out, out_dtype == INNFER_F32, s));
+        CK(launch_tanh_bias_to_nchw((const float*)raw, rs, l.cout, (long)H * W, N, (const float*)l.d_b, d_out, out_dtype == INNFER_F32, s));
     }
 #undef CK
     return INNFER_OK;

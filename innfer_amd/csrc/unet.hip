@@ -20,6 +20,8 @@
 // Activations are blocked-NHWC fp16 like the SR path; GEMM outputs stay fp32 until normalised.  Deep layers (<= 64 output
 // pixels per image) are split over K; whether a layer is split never depends on the batch, so a batch equals its batch-1 forwards.
 #include "common.h"
+#include "engine_host.h"
+#include "engine_pass.h"
 #include "gather_gemm.h"
 #include "norm_stats.h"
 
@@ -94,39 +96,13 @@ __global__ void unet_post_slab(const f16* src, long sg, int C, long HW, int N, c
     }
 }
 
-// The same with the statistics merge inside (as resnet.hip's rn_post_slab_parts): a workgroup = pxb pixels x 32 channels of one image; it merges that
-// image's per-tile records of its 32 channels itself (8 lanes per channel, Chan's update, lanes merged in order: every workgroup of the group
-// computes the same alpha / shift) and applies them -- the combine launch between conv and post is gone.
+// The same with the statistics merge inside: a workgroup = pxb pixels x 32 channels of one image; it merges that image's per-tile records of its
+// 32 channels itself (norm::merge_group_parts) and applies them -- the combine launch between conv and post is gone.
 __global__ __launch_bounds__(256) void unet_post_slab_parts(const f16* src, long sg, int C, long HW, const float* part, int nper, float eps,
                                                             const float* gamma, const float* beta, PostDst d, PostDst d1, int pxb) {
-    __shared__ float sn[8][32], sm[8][32], sq[8][32], sal[32], ssh[32];
+    __shared__ float sal[32], ssh[32];
     const int n = blockIdx.z, cb = blockIdx.y * 32, t = threadIdx.x;
-    {
-        const int cl = t & 31, lg = t >> 5, c = cb + cl;
-        float cnt = 0.f, mu = 0.f, m2 = 0.f;
-        // (four records per trip, their loads issued together: one record per trip was one exposed load latency per record -- 32 trips for the 256 records of the
-        //  128 x 128 level, repeated by each of its 16 pixel blocks: that launch ran at 3.2 TB/s against 4.6 for its siblings.  Same merge order: same bits.)
-        for (int r = lg; r < nper; r += 32) {
-            float rec[4][3];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int rr = r + 8 * j;
-                const float* q = part + (((long)n * nper + min(rr, nper - 1)) * C + c) * 3;
-                rec[j][0] = rr < nper ? q[0] : 0.f; rec[j][1] = q[1]; rec[j][2] = q[2];
-            }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) norm::chan_merge(cnt, mu, m2, rec[j][0], rec[j][1], rec[j][2]);      // (count 0: no-op)
-        }
-        sn[lg][cl] = cnt; sm[lg][cl] = mu; sq[lg][cl] = m2;
-        __syncthreads();
-        if (lg == 0) {
-            for (int i = 1; i < 8; ++i) norm::chan_merge(cnt, mu, m2, sn[i][cl], sm[i][cl], sq[i][cl]);
-            const float a = (1.0f / sqrtf(m2 / (float)HW + eps)) * (gamma ? gamma[c] : 1.0f);
-            sal[cl] = a;
-            ssh[cl] = (beta ? beta[c] : 0.f) - mu * a;
-        }
-        __syncthreads();
-    }
+    norm::merge_group_parts(part, nper, n, cb, C, HW, eps, gamma, beta, sal, ssh);
     const int q8 = (t & 3) * 8, pl = t >> 2;
     float al[8], sh[8];
 #pragma unroll
@@ -248,18 +224,6 @@ __global__ __launch_bounds__(32 * PL) void unet_deep_post(const float* part, lon
             const int ch = ds[k].coff + c;
             ds[k].p[(ch >> 5) * ds[k].g + ((long)n * HW + px) * 32 + (ch & 31)] = (f16)(ds[k].act == 1 ? fmaxf(y, 0.2f * y) : fmaxf(y, 0.f));
         }
-    }
-}
-
-// outermost: raw[.., 0:C] + bias -> tanh -> NCHW
-__global__ void unet_final(const float* raw, int cpad, int C, long HW, int N, const float* bias, void* out, int out_f32) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)N * HW) return;
-    const long n = i / HW, px = i % HW;
-    for (int c = 0; c < C; ++c) {
-        const float y = fast_tanh(raw[i * cpad + c] + bias[c]);
-        const long o = (n * C + c) * HW + px;
-        if (out_f32) ((float*)out)[o] = y; else ((f16*)out)[o] = (f16)y;
     }
 }
 
@@ -458,12 +422,6 @@ int launch_deep_post(const float* part, long split_elems, int ks, int cpad, int 
     return INNFER_OK;
 }
 
-int launch_unet_final(const float* raw, int cpad, int C, long HW, int N, const float* bias, void* out, int out_f32, hipStream_t s) {
-    hipLaunchKernelGGL(unet_final, dim3((unsigned)((N * HW + 255) / 256)), dim3(256), 0, s, raw, cpad, C, HW, N, bias, out, out_f32);
-    INNFER_HIP(hipGetLastError());
-    return INNFER_OK;
-}
-
 int launch_unet_pre(const void* in, int in_f32, int C, long HW, int N, f16* slab, hipStream_t s) {
     hipLaunchKernelGGL(unet_pre, dim3((unsigned)((N * HW + 255) / 256)), dim3(256), 0, s, in, in_f32, C, HW, N, slab);
     INNFER_HIP(hipGetLastError());
@@ -502,22 +460,23 @@ void pack_unet_first(const float* w, int cin, f16* wf) {
 }
 constexpr int UNET_FIRST_PANEL = 2 * 4 * 16 * 32;      // f16 elements
 
-struct Param { std::string key; std::vector<int> shape; std::vector<float> host; bool set = false; };
+struct LayerDev {         // a layer's views of the engine's device blocks (innfer_unet.weights): value-reset as one before every upload
+    f16* d_w[4] = {nullptr, nullptr, nullptr, nullptr};    // conv: [0]; convT: one panel set per phase, [1..3] point into [0]'s block
+    void* d_w3 = nullptr; float* d_b3 = nullptr;           // `phases` layer: conv3x3.hip panels [4*cout][cin][3][3] and the bias repeated per phase
+    float *d_bias = nullptr, *d_gamma = nullptr, *d_beta = nullptr;
+    float *d_ev_alpha = nullptr, *d_ev_shift = nullptr;    // eval-mode BatchNorm: weight / sqrt(running_var + eps), bias - running_mean * that
+    float* d_ones = nullptr;                               // instance-norm nets: the unit scale beside d_bias of a conv that no norm layer follows
+    f16* d_wf = nullptr;                                   // patch layer with 64 outputs: the panel of unet_first_mfma
+};
 
-struct Layer {            // one conv / conv-transpose
+struct Layer : LayerDev { // one conv / conv-transpose
     bool transposed = false;
     bool patch = false;                                    // outermost down conv as a 1-tap GEMM on the patch slab (unet_pre_patch)
     bool phases = false;                                   // outermost up conv: the four output phases as 4*cout channels of ONE 3x3-tap GEMM
     int cin = 0, cout = 0, cin_pad = 0, cout_pad = 0;
     int w = -1, bias = -1, gamma = -1, beta = -1, rmean = -1, rvar = -1;   // indices into params
-    f16* d_w[4] = {nullptr, nullptr, nullptr, nullptr};    // conv: [0]; convT: one panel set per phase, [1..3] point into [0]'s allocation
     long phase_elems = 0;
-    void* d_w3 = nullptr; float* d_b3 = nullptr;           // `phases` layer: conv3x3.hip panels [4*cout][cin][3][3] and the bias repeated per phase
-    float *d_bias = nullptr, *d_gamma = nullptr, *d_beta = nullptr;
-    float *d_ev_alpha = nullptr, *d_ev_shift = nullptr;    // eval-mode BatchNorm: weight / sqrt(running_var + eps), bias - running_mean * that
-    float* d_ones = nullptr;                               // instance-norm nets: the unit scale beside d_bias of a conv that no norm layer follows
     bool normed = false;                                   // a norm layer follows this conv
-    f16* d_wf = nullptr;                                   // patch layer with 64 outputs: the panel of unet_first_mfma
     bool tile4 = false;                                    // ConvTranspose2d also packed as four 2x2-tap phase panels for conv3x3.hip's halo-tile kernel (d_w3)
     bool upconv = false;                                   // upsample_mode 'upconv': Upsample(nearest 2x) + Conv2d(3x3) instead of ConvTranspose2d(4, 2, 1)
 };
@@ -526,7 +485,8 @@ struct Layer {            // one conv / conv-transpose
 
 struct innfer_unet {
     int in_nc = 3, out_nc = 3, num_downs = 8, ngf = 64;
-    std::vector<Param> params;
+    ParamTable params;
+    DeviceBufs weights, f32;           // every device block of the network / of its fp32 panels (f32_down, f32_up)
     std::vector<Layer> down, up;       // down[k], up[k] for level k = 0 .. num_downs-1
     std::vector<int> dc;               // down-path channels per level
     bool uploaded = false;
@@ -537,12 +497,6 @@ struct innfer_unet {
     bool instance_norm = false;        // norm_type 'instance' (UNet_arch.py:38-41): nn.InstanceNorm2d -- no parameters, no running statistics, always the
                                        // statistics of the image; every conv then has a bias (use_bias, :101-104), which only matters where no norm follows
 };
-
-static int add_param(innfer_unet* u, const std::string& key, std::vector<int> shape) {
-    Param p; p.key = key; p.shape = shape;
-    u->params.push_back(p);
-    return (int)u->params.size() - 1;
-}
 
 // unet_post_slab_parts alone, for tests: the network's launch (launch_post_slab_parts: its grid and pixel-block choice) on a caller's slab, records and destinations
 extern "C" int innfer_unet_post_slab_parts(const void* d_src, int64_t src_gs, int C, int64_t HW, int N, const float* d_part, int nper, const float* d_gamma, const float* d_beta,
@@ -618,7 +572,7 @@ extern "C" int innfer_unet_deep_post(const float* d_part, int64_t split_elems, i
 extern "C" int innfer_unet_final(const float* d_raw, int cpad, int C, int64_t HW, int N, const float* d_bias, void* d_out, int out_dtype, void* stream) {
     if (!d_raw || !d_bias || !d_out || (out_dtype != INNFER_F16 && out_dtype != INNFER_F32) || C <= 0 || cpad < C || HW <= 0 || N <= 0)
         return set_error(INNFER_ERR_INVALID, "unet_final: null argument, dtype %d, C=%d, row of %d floats, HW=%lld, N=%d", out_dtype, C, cpad, (long long)HW, N);
-    return launch_unet_final(d_raw, cpad, C, (long)HW, N, d_bias, d_out, out_dtype == INNFER_F32, (hipStream_t)stream);
+    return launch_tanh_bias_to_nchw(d_raw, cpad, C, (long)HW, N, d_bias, d_out, out_dtype == INNFER_F32, (hipStream_t)stream);
 }
 
 extern "C" size_t innfer_unet_first_packed_bytes(void) { return UNET_FIRST_PANEL * sizeof(f16); }
@@ -666,17 +620,17 @@ extern "C" int innfer_unet_create_ex(innfer_unet** out, int in_nc, int out_nc, i
         p.cin = inner ? u->dc[k] : 2 * u->dc[k]; p.cout = outer ? out_nc : u->dc[k - 1];
         d.normed = !outer && !inner;
         if (outer) {
-            d.w = add_param(u, blk + "0.weight", {d.cout, d.cin, 4, 4});
-            if (in_) d.bias = add_param(u, blk + "0.bias", {d.cout});
+            d.w = u->params.add(blk + "0.weight", {d.cout, d.cin, 4, 4});
+            if (in_) d.bias = u->params.add(blk + "0.bias", {d.cout});
         } else {
-            d.w = add_param(u, blk + "1.weight", {d.cout, d.cin, 4, 4});
-            if (in_) d.bias = add_param(u, blk + "1.bias", {d.cout});
+            d.w = u->params.add(blk + "1.weight", {d.cout, d.cin, 4, 4});
+            if (in_) d.bias = u->params.add(blk + "1.bias", {d.cout});
             if (!inner && !in_) {
-                d.gamma = add_param(u, blk + "2.weight", {d.cout});
-                d.beta = add_param(u, blk + "2.bias", {d.cout});
-                d.rmean = add_param(u, blk + "2.running_mean", {d.cout});
-                d.rvar = add_param(u, blk + "2.running_var", {d.cout});
-                add_param(u, blk + "2.num_batches_tracked", {});
+                d.gamma = u->params.add(blk + "2.weight", {d.cout});
+                d.beta = u->params.add(blk + "2.bias", {d.cout});
+                d.rmean = u->params.add(blk + "2.running_mean", {d.cout});
+                d.rvar = u->params.add(blk + "2.running_var", {d.cout});
+                u->params.add(blk + "2.num_batches_tracked", {});
             }
         }
         const std::string next = blk + (outer ? "1.model." : "3.model.");
@@ -703,53 +657,30 @@ extern "C" int innfer_unet_create_ex(innfer_unet** out, int in_nc, int out_nc, i
         const bool outer = k == 0, inner = k == L - 1;
         // upconv_block is a Sequential(Upsample, Conv2d) in the block's Sequential: its conv is `<i>.1`
         const std::string wi = std::string(outer ? "3" : (inner ? "3" : "5")) + (u->upconv ? ".1" : ""), ni = inner ? "4" : "6";
-        p.w = u->upconv ? add_param(u, b + wi + ".weight", {p.cout, p.cin, 3, 3}) : add_param(u, b + wi + ".weight", {p.cin, p.cout, 4, 4});
+        p.w = u->upconv ? u->params.add(b + wi + ".weight", {p.cout, p.cin, 3, 3}) : u->params.add(b + wi + ".weight", {p.cin, p.cout, 4, 4});
         p.normed = !outer;
         if (outer) {
-            p.bias = add_param(u, b + wi + ".bias", {p.cout});
+            p.bias = u->params.add(b + wi + ".bias", {p.cout});
         } else if (in_) {
-            p.bias = add_param(u, b + wi + ".bias", {p.cout});          // in front of an InstanceNorm2d: cancels in the mean subtraction, kept for the state dict
+            p.bias = u->params.add(b + wi + ".bias", {p.cout});          // in front of an InstanceNorm2d: cancels in the mean subtraction, kept for the state dict
         } else {
-            p.gamma = add_param(u, b + ni + ".weight", {p.cout});
-            p.beta = add_param(u, b + ni + ".bias", {p.cout});
-            p.rmean = add_param(u, b + ni + ".running_mean", {p.cout});
-            p.rvar = add_param(u, b + ni + ".running_var", {p.cout});
-            add_param(u, b + ni + ".num_batches_tracked", {});
+            p.gamma = u->params.add(b + ni + ".weight", {p.cout});
+            p.beta = u->params.add(b + ni + ".bias", {p.cout});
+            p.rmean = u->params.add(b + ni + ".running_mean", {p.cout});
+            p.rvar = u->params.add(b + ni + ".running_var", {p.cout});
+            u->params.add(b + ni + ".num_batches_tracked", {});
         }
     }
     *out = u;
     return INNFER_OK;
 }
 
-extern "C" void innfer_unet_destroy(innfer_unet* u) {
-    if (!u) return;
-    for (auto* v : {&u->down, &u->up})
-        for (auto& l : *v) {
-            if (l.d_w[0]) (void)hipFree(l.d_w[0]);
-            if (l.d_w3) (void)hipFree(l.d_w3);
-            if (l.d_wf) (void)hipFree(l.d_wf);
-            if (l.d_b3) (void)hipFree(l.d_b3);
-            if (l.d_bias) (void)hipFree(l.d_bias);
-            if (l.d_gamma) (void)hipFree(l.d_gamma);
-            if (l.d_beta) (void)hipFree(l.d_beta);
-            if (l.d_ev_alpha) (void)hipFree(l.d_ev_alpha);
-            if (l.d_ev_shift) (void)hipFree(l.d_ev_shift);
-            if (l.d_ones) (void)hipFree(l.d_ones);
-        }
-    for (auto v : u->f32_down) if (v) (void)hipFree(v);
-    for (auto& vv : u->f32_up) for (auto v : vv) if (v) (void)hipFree(v);
-    delete u;
-}
+extern "C" void innfer_unet_destroy(innfer_unet* u) { delete u; }
 
 extern "C" int innfer_unet_num_params(innfer_unet* u) { return u ? (int)u->params.size() : INNFER_ERR_INVALID; }
 
 extern "C" int innfer_unet_param_info(innfer_unet* u, int idx, char* key, size_t key_cap, int* ndim, int* shape4) {
-    if (!u || idx < 0 || idx >= (int)u->params.size()) return set_error(INNFER_ERR_INVALID, "unet_param_info: bad index");
-    const Param& p = u->params[idx];
-    if (key && key_cap) { strncpy(key, p.key.c_str(), key_cap - 1); key[key_cap - 1] = 0; }
-    if (ndim) *ndim = (int)p.shape.size();
-    if (shape4) for (size_t i = 0; i < 4; ++i) shape4[i] = i < p.shape.size() ? p.shape[i] : 1;
-    return INNFER_OK;
+    return ParamTable::of(u).info("unet", idx, key, key_cap, ndim, shape4);
 }
 
 extern "C" int innfer_unet_set_eval(innfer_unet* u, int eval_mode) {
@@ -759,26 +690,9 @@ extern "C" int innfer_unet_set_eval(innfer_unet* u, int eval_mode) {
 }
 
 extern "C" int innfer_unet_set_param(innfer_unet* u, int idx, const float* h_data) {
-    if (!u || idx < 0 || idx >= (int)u->params.size() || !h_data) return set_error(INNFER_ERR_INVALID, "unet_set_param: bad arguments");
-    Param& p = u->params[idx];
-    size_t n = 1;
-    for (int s : p.shape) n *= (size_t)s;
-    p.host.assign(h_data, h_data + n);
-    p.set = true;
-    u->uploaded = false;
-    return INNFER_OK;
-}
-
-static int upload_f32(float** dst, const std::vector<float>& v) {
-    if (!*dst) INNFER_HIP(hipMalloc((void**)dst, v.size() * sizeof(float)));
-    INNFER_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
-    return INNFER_OK;
-}
-
-static int upload_f16(f16** dst, const std::vector<f16>& v) {
-    if (!*dst) INNFER_HIP(hipMalloc((void**)dst, v.size() * sizeof(f16)));
-    INNFER_HIP(hipMemcpy(*dst, v.data(), v.size() * sizeof(f16), hipMemcpyHostToDevice));
-    return INNFER_OK;
+    const int rc = ParamTable::of(u).set("unet", idx, h_data);
+    if (!rc) u->uploaded = false;
+    return rc;
 }
 
 // taps of output phase (a, b) of ConvTranspose2d(k=4, s=2, p=1): oy = 2*iy - 1 + ky
@@ -790,21 +704,23 @@ static void phase_taps(int a, int b, int ky[4], int kx[4], int dy[4], int dx[4])
 }
 
 static int upload_all(innfer_unet* u) {
-    for (auto v : u->f32_down) if (v) (void)hipFree(v);               // the fp32 panels follow the parameters: rebuilt by innfer_unet_set_precision
+    int rc = u->params.require_all_set("unet", true);
+    if (rc) return rc;
+    u->weights.clear();
+    u->f32.clear();                                                   // the fp32 panels follow the parameters: rebuilt by innfer_unet_set_precision
     u->f32_down.clear();
-    for (auto& vv : u->f32_up) { for (auto v : vv) if (v) (void)hipFree(v); vv.clear(); }
-    for (auto& p : u->params)
-        if (!p.set && p.key.find("running_") == std::string::npos && p.key.find("num_batches") == std::string::npos)
-            return set_error(INNFER_ERR_INVALID, "unet: parameter '%s' was never set", p.key.c_str());
+    for (auto& vv : u->f32_up) vv.clear();
+    DeviceBufs& dev = u->weights;
     std::vector<f16> panel;
     for (auto* v : {&u->down, &u->up})
         for (auto& l : *v) {
+            static_cast<LayerDev&>(l) = LayerDev{};
             const std::vector<float>& w = u->params[l.w].host;
             if (l.patch) {
                 gg::pack_panels(panel, l.cout, 16 * l.cin, 64, 1,
                             [&](int co, int j, int) { const int t = j / l.cin, ci = j - t * l.cin;
                                                       return w[(((size_t)co * l.cin + ci) * 4 + (t >> 2)) * 4 + (t & 3)]; });
-                int rc = upload_f16(&l.d_w[0], panel); if (rc) return rc;
+                rc = dev.put(&l.d_w[0], panel); if (rc) return rc;
                 if (l.cout % 64 == 0) {        // ... and as a one-tap panel for the halo-tile kernel, whose epilogue writes the fp16 slabs directly
                     std::vector<float> w1((size_t)l.cout * 64, 0.f), b3((size_t)l.cout, 0.f);
                     if (l.bias >= 0) b3 = u->params[l.bias].host;          // instance-norm nets: the outermost down conv has a bias and no norm
@@ -815,14 +731,13 @@ static int upload_all(innfer_unet* u) {
                         }
                     std::vector<char> packed(conv_packed_bytes_taps(l.cout, 64, TAPS_1X1));
                     conv_pack_1x1(w1.data(), l.cout, 64, packed.data());
-                    if (!l.d_w3) INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-                    INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
-                    rc = upload_f32(&l.d_b3, b3); if (rc) return rc;
+                    rc = dev.put(&l.d_w3, packed); if (rc) return rc;
+                    rc = dev.put(&l.d_b3, b3); if (rc) return rc;
                 }
                 if (l.cout == 64) {            // unet_first_mfma's panel: k = c * 16 + ky * 4 + kx
                     std::vector<f16> wf(UNET_FIRST_PANEL);
                     pack_unet_first(w.data(), l.cin, wf.data());
-                    rc = upload_f16(&l.d_wf, wf); if (rc) return rc;
+                    rc = dev.put(&l.d_wf, wf); if (rc) return rc;
                 }
             } else if (l.phases) {
                 // The four output phases of ConvTranspose2d(k4, s2, p1) as ONE 3x3 convolution with 4*cout output channels over the
@@ -843,23 +758,21 @@ static int upload_all(innfer_unet* u) {
                 }
                 std::vector<char> packed(conv_packed_bytes(K3, l.cin_pad));
                 conv_pack(w3.data(), K3, l.cin_pad, packed.data());
-                if (!l.d_w3) INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-                INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
-                int rc = upload_f32(&l.d_b3, b3); if (rc) return rc;
+                rc = dev.put(&l.d_w3, packed); if (rc) return rc;
+                rc = dev.put(&l.d_b3, b3); if (rc) return rc;
             } else if (l.upconv) {
                 // Upsample(nearest 2x) + Conv2d(3x3, zero padding): conv3x3.hip's halo-tile kernel with the upsampled read (`up`);
                 // the bias (outermost / instance-norm nets) rides in the conv epilogue
                 std::vector<char> packed(conv_packed_bytes(l.cout, l.cin));
                 conv_pack(w.data(), l.cout, l.cin, packed.data());
-                if (!l.d_w3) INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-                INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
+                rc = dev.put(&l.d_w3, packed); if (rc) return rc;
                 std::vector<float> b3((size_t)std::max(16, l.cout), 0.f);
                 if (l.bias >= 0) std::copy(u->params[l.bias].host.begin(), u->params[l.bias].host.end(), b3.begin());
-                int rc = upload_f32(&l.d_b3, b3); if (rc) return rc;
+                rc = dev.put(&l.d_b3, b3); if (rc) return rc;
             } else if (!l.transposed) {
                 gg::pack_panels(panel, l.cout, l.cin, l.cin_pad, 16,
                             [&](int co, int ci, int t) { return w[(((size_t)co * l.cin + ci) * 4 + (t >> 2)) * 4 + (t & 3)]; });
-                int rc = upload_f16(&l.d_w[0], panel); if (rc) return rc;
+                rc = dev.put(&l.d_w[0], panel); if (rc) return rc;
                 if (l.tile4) {
                     // Conv2d(4, 2, 1) = the 2x2-tap conv of the space-to-depth source (conv3x3_pc's stride-2 loader): virtual channel (2 pa + pb) * cin + ci,
                     // tap (1 + dy, 1 + dx) of the 3x3 lattice carries w[co][ci][2 dy + pa][2 dx + pb]
@@ -867,9 +780,8 @@ static int upload_all(innfer_unet* u) {
                     if (l.bias >= 0) b3 = u->params[l.bias].host;
                     std::vector<char> packed(conv_packed_bytes_s2k4(l.cout, l.cin));
                     conv_pack_s2k4(w.data(), l.cout, l.cin, packed.data());
-                    if (!l.d_w3) INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-                    INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
-                    rc = upload_f32(&l.d_b3, b3); if (rc) return rc;
+                    rc = dev.put(&l.d_w3, packed); if (rc) return rc;
+                    rc = dev.put(&l.d_b3, b3); if (rc) return rc;
                 }
             } else {
                 if (l.tile4) {
@@ -879,9 +791,8 @@ static int upload_all(innfer_unet* u) {
                     if (l.bias >= 0) for (int co = 0; co < 4 * l.cout; ++co) b3[co] = u->params[l.bias].host[co % l.cout];
                     std::vector<char> packed(conv_packed_bytes_deconv2x(l.cout, l.cin));
                     conv_pack_deconv2x(w.data(), l.cout, l.cin, 4, packed.data());
-                    if (!l.d_w3) INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-                    INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
-                    int rc = upload_f32(&l.d_b3, b3); if (rc) return rc;
+                    rc = dev.put(&l.d_w3, packed); if (rc) return rc;
+                    rc = dev.put(&l.d_b3, b3); if (rc) return rc;
                 }
                 std::vector<f16> all;                               // the four phase panels back to back: one grouped launch reads them
                 for (int ph = 0; ph < 4; ++ph) {
@@ -891,17 +802,17 @@ static int upload_all(innfer_unet* u) {
                                 [&](int co, int ci, int t) { return w[(((size_t)ci * l.cout + co) * 4 + ky[t]) * 4 + kx[t]]; });
                     all.insert(all.end(), panel.begin(), panel.end());
                 }
-                int rc = upload_f16(&l.d_w[0], all); if (rc) return rc;
+                rc = dev.put(&l.d_w[0], all); if (rc) return rc;
                 l.phase_elems = (long)panel.size();
-                for (int ph = 1; ph < 4; ++ph) l.d_w[ph] = l.d_w[0] + ph * l.phase_elems;      // aliases, never freed
+                for (int ph = 1; ph < 4; ++ph) l.d_w[ph] = l.d_w[0] + ph * l.phase_elems;      // views into [0]'s block
             }
-            if (l.bias >= 0) { int rc = upload_f32(&l.d_bias, u->params[l.bias].host); if (rc) return rc; }
-            if (l.gamma >= 0) { int rc = upload_f32(&l.d_gamma, u->params[l.gamma].host); if (rc) return rc; }
-            if (l.beta >= 0) { int rc = upload_f32(&l.d_beta, u->params[l.beta].host); if (rc) return rc; }
+            if (l.bias >= 0) { rc = dev.put(&l.d_bias, u->params[l.bias].host); if (rc) return rc; }
+            if (l.gamma >= 0) { rc = dev.put(&l.d_gamma, u->params[l.gamma].host); if (rc) return rc; }
+            if (l.beta >= 0) { rc = dev.put(&l.d_beta, u->params[l.beta].host); if (rc) return rc; }
             if (u->instance_norm) {            // InstanceNorm2d(affine=False): unit scale, zero shift on the statistics of the image
                 const std::vector<float> ones((size_t)l.cout, 1.f), zeros((size_t)l.cout, 0.f);
-                int rc = upload_f32(&l.d_ones, ones); if (rc) return rc;
-                if (l.normed) { rc = upload_f32(&l.d_gamma, ones); if (rc) return rc; rc = upload_f32(&l.d_beta, zeros); if (rc) return rc; }
+                rc = dev.put(&l.d_ones, ones); if (rc) return rc;
+                if (l.normed) { rc = dev.put(&l.d_gamma, ones); if (rc) return rc; rc = dev.put(&l.d_beta, zeros); if (rc) return rc; }
             }
             if (l.gamma >= 0) {
                 // eval-mode transform as ATen forms it (batch_norm_cpu_transform_input: alpha = weight / sqrt(running_var + eps),
@@ -915,8 +826,8 @@ static int upload_all(innfer_unet* u) {
                     al[c] = g[c] * (1.0f / std::sqrt(var + 1e-5f));
                     sh[c] = b[c] - mean * al[c];
                 }
-                int rc = upload_f32(&l.d_ev_alpha, al); if (rc) return rc;
-                rc = upload_f32(&l.d_ev_shift, sh); if (rc) return rc;
+                rc = dev.put(&l.d_ev_alpha, al); if (rc) return rc;
+                rc = dev.put(&l.d_ev_shift, sh); if (rc) return rc;
             }
         }
     u->uploaded = true;
@@ -1018,9 +929,7 @@ extern "C" int innfer_unet_set_precision(innfer_unet* u, int fp32) {
     auto put = [&](float** dst, int K, int C, int ntap, const std::function<float(int, int, int)>& w) -> int {
         host.resize(f32conv_packed_floats(K, C, ntap));
         f32conv_pack(K, C, ntap, w, host.data());
-        INNFER_HIP(hipMalloc((void**)dst, host.size() * sizeof(float)));
-        INNFER_HIP(hipMemcpy(*dst, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-        return INNFER_OK;
+        return u->f32.put(dst, host);
     };
     for (int k = 0; k < L; ++k) {
         const Layer &d = u->down[k], &p = u->up[k];
@@ -1384,7 +1293,7 @@ extern "C" int innfer_unet_forward(innfer_unet* u, const void* d_in, int in_dtyp
             if (rc) return rc;
         } else {
             GtScope gt(s, "unet_final (bias + tanh -> NCHW)", 0.0, (double)N * HW * ((l.cout + 3) / 4 * 4) * 4.0 + (double)N * HW * l.cout * (out_dtype == INNFER_F32 ? 4.0 : 2.0));
-            int rc = launch_unet_final(raw, (l.cout + 3) / 4 * 4, l.cout, HW, N, l.d_bias, d_out, out_dtype == INNFER_F32, s);
+            int rc = launch_tanh_bias_to_nchw(raw, (l.cout + 3) / 4 * 4, l.cout, HW, N, l.d_bias, d_out, out_dtype == INNFER_F32, s);
             if (rc) return rc;
         }
         h = hf; w = wf;

@@ -9,6 +9,7 @@
 //   bilinear 2x (align_corners=False) + skip addition      wb_upadd (ATen's source index / lambda arithmetic)
 //   guided filter, 3x3 box means, reflect padding          gf_ab (means, covariance, A, b) + gf_out (mean_A * x + mean_b)
 #include "common.h"
+#include "engine_host.h"
 #include "gather_gemm.h"
 
 #include <cmath>
@@ -217,16 +218,17 @@ __global__ void gf_out_fast(const float* A, const float* B, const void* xhr, int
     if (f32) ((float*)out)[i] = v; else ((f16*)out)[i] = (f16)v;
 }
 
-struct Param { std::string key; std::vector<int> shape; std::vector<float> host; bool set = false; };
-struct Layer { int w = -1, b = -1, cin = 0, cout = 0, k = 3; f16* d_w = nullptr; float* d_b = nullptr;
-               void* d_w3 = nullptr; float* d_b3 = nullptr;
-               void* d_ws2 = nullptr; };    // the two stride-2 3x3 convs: panels of the stride-2 gather loader (conv_pack_s2k4 over the kernel embedded in 4x4)     // 3x3 layers: conv3x3.hip panels + bias (the stride-1 ones run there)
+struct LayerDev { f16* d_w = nullptr; float* d_b = nullptr;      // a layer's views of the engine's device blocks (innfer_wbc.weights): value-reset as one before every upload
+                  void* d_w3 = nullptr; float* d_b3 = nullptr;   // 3x3 layers: conv3x3.hip panels + bias (the stride-1 ones run there)
+                  void* d_ws2 = nullptr; };                      // the two stride-2 3x3 convs: panels of the stride-2 gather loader (conv_pack_s2k4 over the kernel embedded in 4x4)
+struct Layer : LayerDev { int w = -1, b = -1, cin = 0, cout = 0, k = 3; };
 
 }  // namespace
 
 struct innfer_wbc {
     int nf = 32; int tf = 0;
-    std::vector<Param> params;
+    ParamTable params;
+    DeviceBufs weights, f32;     // every device block of the network / of its fp32 panels (f32_w)
     std::vector<Layer> layers;   // conv, conv_1..conv_4, block_0..3 (conv1, conv2), conv_5..conv_9
     bool fp32 = false;           // innfer_wbc_set_precision(1): the fp32 forward on NCHW fp32 tensors (f32ops.hip), the reference's -no_fp16 mode
     std::vector<float*> f32_w;   //   one f32conv panel per layer
@@ -235,8 +237,8 @@ struct innfer_wbc {
 
 static void wb_add(innfer_wbc* u, const std::string& key, int cin, int cout, int k) {
     Layer l; l.cin = cin; l.cout = cout; l.k = k;
-    Param pw; pw.key = key + ".weight"; pw.shape = {cout, cin, k, k}; u->params.push_back(pw); l.w = (int)u->params.size() - 1;
-    Param pb; pb.key = key + ".bias"; pb.shape = {cout}; u->params.push_back(pb); l.b = (int)u->params.size() - 1;
+    l.w = u->params.add(key + ".weight", {cout, cin, k, k});
+    l.b = u->params.add(key + ".bias", {cout});
     u->layers.push_back(l);
 }
 
@@ -258,46 +260,31 @@ extern "C" int innfer_wbc_create(innfer_wbc** out, int nf, int tf_mode) {
     return INNFER_OK;
 }
 
-static void wb_free(innfer_wbc* u) {
-    for (auto& l : u->layers) {
-        if (l.d_w) (void)hipFree(l.d_w); if (l.d_b) (void)hipFree(l.d_b); if (l.d_w3) (void)hipFree(l.d_w3); if (l.d_b3) (void)hipFree(l.d_b3);
-        if (l.d_ws2) (void)hipFree(l.d_ws2);
-        l.d_w = nullptr; l.d_b = nullptr; l.d_w3 = nullptr; l.d_b3 = nullptr; l.d_ws2 = nullptr;
-    }
-}
-
-extern "C" void innfer_wbc_destroy(innfer_wbc* u) { if (u) { wb_free(u); for (auto v : u->f32_w) if (v) (void)hipFree(v); delete u; } }
+extern "C" void innfer_wbc_destroy(innfer_wbc* u) { delete u; }
 extern "C" int innfer_wbc_num_params(innfer_wbc* u) { return u ? (int)u->params.size() : INNFER_ERR_INVALID; }
 
 extern "C" int innfer_wbc_param_info(innfer_wbc* u, int idx, char* key, size_t key_cap, int* ndim, int* shape4) {
-    if (!u || idx < 0 || idx >= (int)u->params.size()) return set_error(INNFER_ERR_INVALID, "wbc_param_info: bad index");
-    const Param& q = u->params[idx];
-    if (key && key_cap) { strncpy(key, q.key.c_str(), key_cap - 1); key[key_cap - 1] = 0; }
-    if (ndim) *ndim = (int)q.shape.size();
-    if (shape4) for (size_t i = 0; i < 4; ++i) shape4[i] = i < q.shape.size() ? q.shape[i] : 1;
-    return INNFER_OK;
+    return ParamTable::of(u).info("wbc", idx, key, key_cap, ndim, shape4);
 }
 
 extern "C" int innfer_wbc_set_param(innfer_wbc* u, int idx, const float* h_data) {
-    if (!u || idx < 0 || idx >= (int)u->params.size() || !h_data) return set_error(INNFER_ERR_INVALID, "wbc_set_param: bad arguments");
-    Param& q = u->params[idx];
-    size_t n = 1;
-    for (int s : q.shape) n *= (size_t)s;
-    q.host.assign(h_data, h_data + n);
-    q.set = true;
-    u->uploaded = false;
-    return INNFER_OK;
+    const int rc = ParamTable::of(u).set("wbc", idx, h_data);
+    if (!rc) u->uploaded = false;
+    return rc;
 }
 
 namespace {
 
 int wb_upload(innfer_wbc* u) {
-    for (auto& q : u->params) if (!q.set) return set_error(INNFER_ERR_INVALID, "wbc: parameter '%s' was never set", q.key.c_str());
-    wb_free(u);
-    for (auto v : u->f32_w) if (v) (void)hipFree(v);               // the fp32 panels follow the parameters: rebuilt by innfer_wbc_set_precision
+    int rc = u->params.require_all_set("wbc", false);
+    if (rc) return rc;
+    DeviceBufs& dev = u->weights;
+    dev.clear();
+    u->f32.clear();                                                // the fp32 panels follow the parameters: rebuilt by innfer_wbc_set_precision
     u->f32_w.clear();
     std::vector<f16> panel;
     for (auto& l : u->layers) {
+        static_cast<LayerDev&>(l) = LayerDev{};
         const std::vector<float>& w = u->params[l.w].host;
         const int cin_pad = (l.cin + 31) / 32 * 32, kk = l.k * l.k;
         if (l.k == 7 && 7 * l.cin <= 32)      // first conv on the row-patch slab (wb_pre): tap t = ky, channel kx*cin + c
@@ -306,10 +293,8 @@ int wb_upload(innfer_wbc* u) {
                 return w[((size_t)co * l.cin + c) * 49 + ky * 7 + kx]; });
         else
         gg::pack_panels(panel, l.cout, l.cin, cin_pad, kk, [&](int co, int ci, int t) { return w[((size_t)co * l.cin + ci) * kk + t]; });
-        INNFER_HIP(hipMalloc((void**)&l.d_w, panel.size() * sizeof(f16)));
-        INNFER_HIP(hipMemcpy(l.d_w, panel.data(), panel.size() * sizeof(f16), hipMemcpyHostToDevice));
-        INNFER_HIP(hipMalloc((void**)&l.d_b, l.cout * sizeof(float)));
-        INNFER_HIP(hipMemcpy(l.d_b, u->params[l.b].host.data(), l.cout * sizeof(float), hipMemcpyHostToDevice));
+        rc = dev.put(&l.d_w, panel); if (rc) return rc;
+        rc = dev.put(&l.d_b, u->params[l.b].host); if (rc) return rc;
         if (l.k == 7 && 7 * l.cin <= 32 && l.cout % 32 == 0) {
             // first conv over the row-patch slab as a 7 x 1 column conv on the halo-tile kernel (three vertically displaced 3-tap blocks, conv_pack7v):
             // bias + LeakyReLU + the fp16 slab come out of its epilogue (gather GEMM -> 64-wide fp32 rows -> wb_post took 282 us at 1080p)
@@ -322,20 +307,16 @@ int wb_upload(innfer_wbc* u) {
             conv_pack7v(wv.data(), l.cout, 32, packed.data());
             std::vector<float> b3((size_t)(l.cout + 63) / 64 * 64, 0.f);
             for (int c = 0; c < l.cout; ++c) b3[c] = u->params[l.b].host[c];
-            INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-            INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
-            INNFER_HIP(hipMalloc((void**)&l.d_b3, b3.size() * sizeof(float)));
-            INNFER_HIP(hipMemcpy(l.d_b3, b3.data(), b3.size() * sizeof(float), hipMemcpyHostToDevice));
+            rc = dev.put(&l.d_w3, packed); if (rc) return rc;
+            rc = dev.put(&l.d_b3, b3); if (rc) return rc;
         }
         if (l.k == 7 && l.cin % 32 == 0 && l.cout <= 16) {          // last conv (32 -> 3): nine displaced 3x3 convs on the halo-tile kernel
             std::vector<char> packed(conv_packed_bytes7x7(l.cout, l.cin));
             conv_pack7x7(w.data(), l.cout, l.cin, packed.data());
             std::vector<float> b3(64, 0.f);
             for (int c = 0; c < l.cout; ++c) b3[c] = u->params[l.b].host[c];
-            INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-            INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
-            INNFER_HIP(hipMalloc((void**)&l.d_b3, b3.size() * sizeof(float)));
-            INNFER_HIP(hipMemcpy(l.d_b3, b3.data(), b3.size() * sizeof(float), hipMemcpyHostToDevice));
+            rc = dev.put(&l.d_w3, packed); if (rc) return rc;
+            rc = dev.put(&l.d_b3, b3); if (rc) return rc;
         }
         const size_t li_ = (size_t)(&l - &u->layers[0]);
         if ((li_ == 1 || li_ == 3) && l.k == 3 && l.cin % 32 == 0 && l.cout % 32 == 0) {
@@ -350,18 +331,15 @@ int wb_upload(innfer_wbc* u) {
                             w4[(((size_t)co * l.cin + ci) * 4 + ky + o) * 4 + kx + o] = w[((size_t)co * l.cin + ci) * 9 + ky * 3 + kx];
             std::vector<char> packed(conv_packed_bytes_s2k4(l.cout, l.cin));
             conv_pack_s2k4(w4.data(), l.cout, l.cin, packed.data());
-            INNFER_HIP(hipMalloc(&l.d_ws2, packed.size()));
-            INNFER_HIP(hipMemcpy(l.d_ws2, packed.data(), packed.size(), hipMemcpyHostToDevice));
+            rc = dev.put(&l.d_ws2, packed); if (rc) return rc;
         }
         if (l.k == 3 && l.cin % 32 == 0 && l.cout % 32 == 0) {       // halo-tile form for the stride-1 launches
             std::vector<char> packed(conv_packed_bytes(l.cout, l.cin));
             conv_pack(w.data(), l.cout, l.cin, packed.data());
             std::vector<float> b3((size_t)(l.cout + 63) / 64 * 64, 0.f);
             for (int c = 0; c < l.cout; ++c) b3[c] = u->params[l.b].host[c];
-            INNFER_HIP(hipMalloc(&l.d_w3, packed.size()));
-            INNFER_HIP(hipMemcpy(l.d_w3, packed.data(), packed.size(), hipMemcpyHostToDevice));
-            INNFER_HIP(hipMalloc((void**)&l.d_b3, b3.size() * sizeof(float)));
-            INNFER_HIP(hipMemcpy(l.d_b3, b3.data(), b3.size() * sizeof(float), hipMemcpyHostToDevice));
+            rc = dev.put(&l.d_w3, packed); if (rc) return rc;
+            rc = dev.put(&l.d_b3, b3); if (rc) return rc;
         }
     }
     u->uploaded = true;
@@ -463,9 +441,9 @@ extern "C" int innfer_wbc_set_precision(innfer_wbc* u, int fp32) {
         host.resize(f32conv_packed_floats(l.cout, C, T));
         f32conv_pack(l.cout, C, T, [&w, C, T](int k, int c, int t) { return w[((size_t)k * C + c) * T + t]; }, host.data());
         float* d = nullptr;
-        INNFER_HIP(hipMalloc((void**)&d, host.size() * sizeof(float)));
+        const int rc = u->f32.put(&d, host);
+        if (rc) return rc;
         u->f32_w.push_back(d);
-        INNFER_HIP(hipMemcpy(d, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     return INNFER_OK;
 }

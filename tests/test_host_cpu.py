@@ -609,3 +609,51 @@ def test_up2x_phase_packer_sums_taps_in_float32_and_rounds_once():
         L.check(L.lib.innfer_pack_up2x_phases(w.ctypes.data, K, Cc, rows, p1.ctypes.data))
         L.check(L.lib.innfer_pack_convt2x_rows(np.ascontiguousarray(wt).ctypes.data, K, Cc, 4, rows, p2.ctypes.data))
         assert np.array_equal(p1, p2)
+
+
+# the five generator engines share one parameter table (csrc/engine_host.h): smallest constructor arguments each accepts
+_ENGINE_CREATE = {
+    "unet": ("create", (3, 3, 5, 32)),
+    "pan": ("create", (3, 3, 40, 24, 1, 2)),
+    "ppon": ("create", (3, 3, 64, 1, 2, C.c_float(1.0))),
+    "resnet": ("create", (3, 3, 32, 1)),
+    "wbc": ("create", (32, 0)),
+}
+
+
+@pytest.mark.parametrize("eng", sorted(_ENGINE_CREATE))
+def test_engine_param_accessors_refuse_and_truncate(eng):
+    """innfer_<eng>_num_params / _param_info / _set_param through the loaded library, no GPU call: a null handle and indices -1 and n are
+    ERR_INVALID, a 4-byte key buffer gets a NUL-terminated 3-character prefix and nothing behind it is written, shape4 is padded with 1,
+    a NULL data pointer is refused."""
+    fn = lambda name: getattr(L.lib, f"innfer_{eng}_{name}")
+    create, args = _ENGINE_CREATE[eng]
+    h = C.c_void_p()
+    assert fn(create)(C.byref(h), *args) == 0, L.last_error()
+    try:
+        assert fn("num_params")(None) == L.ERR_INVALID
+        n = fn("num_params")(h)
+        assert n > 0
+        nd, shp = C.c_int(-7), (C.c_int * 4)(-7, -7, -7, -7)
+        for bad in (-1, n):
+            assert fn("param_info")(h, bad, None, 0, C.byref(nd), shp) == L.ERR_INVALID
+            assert L.last_error() == f"{eng}_param_info: bad index"
+            assert nd.value == -7 and list(shp) == [-7] * 4
+        assert fn("param_info")(None, 0, None, 0, None, None) == L.ERR_INVALID
+        full, guarded = C.create_string_buffer(256), C.create_string_buffer(b"\xaa" * 16, 16)
+        for i in range(n):
+            assert fn("param_info")(h, i, full, 256, C.byref(nd), shp) == 0
+            assert 0 <= nd.value <= 4 and all(s >= 1 for s in shp) and list(shp)[nd.value:] == [1] * (4 - nd.value), (full.value, list(shp))
+        assert nd.value == 1                                        # every engine's last entry is a bias vector: [n] -> (n, 1, 1, 1)
+        assert fn("param_info")(h, 0, guarded, 4, None, None) == 0
+        assert fn("param_info")(h, 0, full, 256, None, None) == 0
+        assert len(full.value) > 3
+        assert guarded.raw[:4] == full.value[:3] + b"\0" and guarded.raw[4:] == b"\xaa" * 12
+        assert fn("set_param")(h, 0, None) == L.ERR_INVALID
+        assert L.last_error() == f"{eng}_set_param: bad arguments"
+        one = np.zeros(1 << 20, dtype=np.float32)
+        for bad in (-1, n):
+            assert fn("set_param")(h, bad, one.ctypes.data) == L.ERR_INVALID
+        assert fn("set_param")(None, 0, one.ctypes.data) == L.ERR_INVALID
+    finally:
+        fn("destroy")(h)
