@@ -312,6 +312,10 @@ SIGNATURES = {
     "innfer_extract_tiles_u8_rect": (C.c_int, [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_stitch_tiles": (C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
     "innfer_stitch_tiles_u8": (C.c_int, [C.c_void_p] + [C.c_int] * 10 + [C.c_void_p, C.c_void_p]),
+    # (123, additive) many images as one tile stream: `sizes` is a host int array H_0, W_0, H_1, W_1, ...; the tables are innfer_multi_tile / innfer_multi_image
+    "innfer_chop_multi_plan": (C.c_int, [C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_double, C.c_int] + [C.c_void_p] * 7),
+    "innfer_extract_tiles_u8_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 3 + [C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_recompose_u8_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double] + [C.c_int] * 4 + [C.c_void_p] * 3),
 }
 
 # INNFER_ABI_ANY=1 (measurement only: scripts/evidence_r5.sh A/Bs an OLDER build of the library against the current one on one box): bind the entry points that
@@ -371,6 +375,29 @@ def chop_plan(H, W, patch=200, step=0.5):
     ys, xs = (C.c_int * nh.value)(), (C.c_int * nw.value)()
     check(_lib.innfer_chop_plan(H, W, patch, step, C.byref(ps), C.byref(nh), C.byref(nw), ys, xs))
     return ps.value, list(ys), list(xs)
+
+
+MULTI_TILE = [("img_off", "<i8"), ("H", "<i4"), ("W", "<i4"), ("oy", "<i4"), ("ox", "<i4")]                         # innfer_multi_tile
+MULTI_IMAGE = [("out_off", "<i8"), ("first", "<i8"), ("FH", "<i4"), ("FW", "<i4"), ("nh", "<i4"), ("nw", "<i4")]     # innfer_multi_image
+
+
+def chop_multi_plan(sizes, channels, pad=0, patch=200, step=0.5, scale=1):
+    """innfer_chop_multi_plan (host only): the geometry of the images [(H, W), ...] of `channels` channels as ONE tile stream -- a dict of ps, sizes (int32 [n, 2],
+    what the kernels' entry points take), counts [n], first [n + 1], in_off / out_off (int64 [n + 1], bytes; the last entry is the packed buffer's size) and
+    the two tables the caller uploads: tiles (MULTI_TILE records, one per tile, for the gather) and images (MULTI_IMAGE records, for the blend at `scale`)."""
+    import numpy as np
+    hw = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(-1, 2))
+    n = hw.shape[0]
+    ps = C.c_int()
+    counts, first = np.zeros(n, np.int32), np.zeros(n + 1, np.int32)
+    in_off, out_off = np.zeros(n + 1, np.int64), np.zeros(n + 1, np.int64)
+    images = np.zeros(n, np.dtype(MULTI_IMAGE))
+    args = (n, hw.ctypes.data, int(channels), int(pad), int(patch), float(step), int(scale), C.byref(ps), counts.ctypes.data, first.ctypes.data,
+            in_off.ctypes.data, out_off.ctypes.data)
+    check(_lib.innfer_chop_multi_plan(*args, None, images.ctypes.data))
+    tiles = np.zeros(int(first[n]), np.dtype(MULTI_TILE))
+    check(_lib.innfer_chop_multi_plan(*args, tiles.ctypes.data, images.ctypes.data))
+    return dict(ps=ps.value, sizes=hw, counts=counts, first=first, in_off=in_off, out_off=out_off, tiles=tiles, images=images)
 
 
 def tile_plan(H, W, tile, halo=16):
