@@ -234,6 +234,9 @@ SIGNATURES = {
     "innfer_color_fix_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "innfer_color_fix": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "innfer_color_fix_mode_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "innfer_color_fix_mode": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_void_p]),
     "innfer_nchw_to_u8hwc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "innfer_linear_resize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
     "innfer_extract_tiles_u8": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
@@ -448,6 +451,16 @@ def resample_filter(filter):
     if code not in RESAMPLE_FILTERS.values():
         raise ValueError(f"resample: filter must be one of {', '.join(RESAMPLE_FILTERS)}, got {filter!r}")
     return int(code)
+
+
+COLOR_FIX_MODES = {"lowfreq": 0, "wavelet": 1, "adain": 2}                    # INNFER_COLOR_FIX_*: the colour fixes (-cf_mode)
+
+
+def color_fix_mode(mode):
+    """The INNFER_COLOR_FIX_* code of a mode name; ValueError for anything else."""
+    if not isinstance(mode, str) or mode not in COLOR_FIX_MODES:
+        raise ValueError(f"color_fix: mode must be one of {', '.join(COLOR_FIX_MODES)}, got {mode!r}")
+    return COLOR_FIX_MODES[mode]
 
 
 def resample_taps(n_in, n_out, filter="lanczos"):

@@ -17,11 +17,13 @@ class FramePipeline:
     """`for out in FramePipeline(model, scale)(frames)`: frames are uint8 HWC BGR numpy arrays of ONE
     shape; yields uint8 HWC BGR numpy arrays.  A yielded array is a view of a pinned buffer that stays untouched until the
     NEXT frame has been yielded (the pipeline owns depth + 1 output buffers: `depth` in flight and the one lent out) -- copy it if
-    it must live longer than that."""
+    it must live longer than that.  color_fix: True (the reference's -cf, 'lowfreq') or a mode name of utils.color_fix ('lowfreq', 'wavelet', 'adain'):
+    every result is fixed against its frame on the device, before the download."""
 
     def __init__(self, model, scale, device='cuda', half=True, normalize=False, depth=3, color_fix=False):
         self.model, self.scale, self.dev = model, scale, torch.device(device)
-        self.half, self.normalize, self.depth, self.cf = half, normalize, max(2, depth), color_fix
+        self.half, self.normalize, self.depth = half, normalize, max(2, depth)
+        self.cf = L.color_fix_mode(color_fix if isinstance(color_fix, str) else 'lowfreq') if color_fix else None     # the mode's code; None: no fix
         self.s_in, self.s_out = torch.cuda.Stream(self.dev), torch.cuda.Stream(self.dev)
         self._slots = None
         self._free_out, self._lent = [], None
@@ -52,13 +54,13 @@ class FramePipeline:
             L.check(L.lib.innfer_u8hwc_to_nchw(sl['d_in'].data_ptr(), H, W, C, int(self.normalize), x.data_ptr(), _dt(x), cur.cuda_stream))
             y = self.model(x)
             L.check(L.lib.innfer_nchw_to_u8hwc(y.data_ptr(), _dt(y), H * s, W * s, C, int(self.normalize), sl['d_out'].data_ptr(), cur.cuda_stream))
-        if self.cf:
-            need = L.lib.innfer_color_fix_workspace_bytes(H, W, H * s, W * s, C)
+        if self.cf is not None:
+            need = max(1, L.lib.innfer_color_fix_mode_workspace_bytes(self.cf, H, W, H * s, W * s, C))
             if self._ws_cf is None or self._ws_cf.numel() < need:
                 self._ws_cf = torch.empty(need, dtype=torch.uint8, device=self.dev)
             fixed = torch.empty_like(sl['d_out'])
-            L.check(L.lib.innfer_color_fix(sl['d_in'].data_ptr(), H, W, sl['d_out'].data_ptr(), H * s, W * s, C, fixed.data_ptr(),
-                                           self._ws_cf.data_ptr(), self._ws_cf.numel(), cur.cuda_stream))
+            L.check(L.lib.innfer_color_fix_mode(self.cf, sl['d_in'].data_ptr(), H, W, sl['d_out'].data_ptr(), H * s, W * s, C, fixed.data_ptr(),
+                                                self._ws_cf.data_ptr(), self._ws_cf.numel(), cur.cuda_stream))
             sl['d_out'].copy_(fixed)
         sl['done'].record(cur)
 

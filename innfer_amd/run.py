@@ -171,6 +171,29 @@ def _into_out(r, out):
     return r if out is None else out.copy_(r)
 
 
+def _accepts_color_fix(fixed):
+    """Decorator of Model.run_u8 / Model.run_u8_batch: the keyword color_fix=None on top of the function's own parameters.  The colour fix is a step
+    BEHIND the plain call -- utils.color_fix(img, run_u8(img, ...)) -- so it is a layer around it: without the keyword the call goes straight through,
+    with it the arguments are bound to the plain call's names and handed to the method `fixed` together with color_fix.  (The plain functions keep their
+    parameter lists, which the tests of earlier features pin; introspection follows __wrapped__ and shows those.)"""
+    import functools
+    import inspect
+
+    def layer(plain):
+        sig = inspect.signature(plain)
+
+        @functools.wraps(plain)
+        def call(self, *args, color_fix=None, **kw):
+            if color_fix is None:
+                return plain(self, *args, **kw)
+            bound = sig.bind(self, *args, **kw)
+            named = dict(bound.arguments)
+            del named['self']
+            return getattr(self, fixed)(color_fix=color_fix, **named)
+        return call
+    return layer
+
+
 TILE_MIN = 32            # the smallest -tile: below it the halo outweighs the core
 TILE_PAD = 16            # the default -tile_pad (Real-ESRGAN's is 10; 16 = utils.SEAMLESS_PAD)
 
@@ -354,6 +377,7 @@ class Model:
             acc = y if acc is None else acc + y
         return (acc * 0.125).to(data.dtype)
 
+    @_accepts_color_fix('_run_u8_color_fix')
     def run_u8(self, img, normalize=False, fp16=True, out=None, fit_channels=False, seamless=None, outscale=None, outfilter='lanczos', tta=False):
         """Image in, image out: tensor2np(self(np2tensor(img, normalize)[.half()]), denormalize=normalize) (run.py:421-431) with the two
         conversions fused into the neighbouring kernels -- the tile gather / the blend on the chop path (_chop_u8: innfer_extract_tiles_u8_seamless,
@@ -374,7 +398,12 @@ class Model:
         (_tta_fits), forward_tta runs on the device tensor between the existing conversions -- the same bits.
         Model(tile=N): self(...) above is tile_forward, and every definition holds with it inside.  Plain and seamless= images go through the uint8 gather
         and stitch (_tile_u8: innfer_extract_tiles_u8_rect, innfer_stitch_tiles_u8 -- neither the float image nor the padded image exists); fit_channels
-        and tta run the tensor path with the tiled __call__ as the forward.  Model(tile=0) runs as chop=False does."""
+        and tta run the tensor path with the tiled __call__ as the forward.  Model(tile=0) runs as chop=False does.
+        color_fix (keyword only, added by _accepts_color_fix: a layer around this function, whose own parameters are those of the plain call):
+        'lowfreq' (the reference's -cf), 'wavelet' or 'adain' -- by definition utils.color_fix(img, run_u8(img, <the same options without
+        color_fix and outscale>), mode=color_fix), then the outscale resample.  img is the image as given: under seamless= the unpadded image against the
+        cropped result, under fit_channels the image in its own layout (H x W as H x W x 1).  One upload, the network, the fix and the resample on the
+        device, one download of the final image (_run_u8_color_fix)."""
         import numpy as np
         if outscale is not None:
             return self._run_u8_outscale(img, outscale, outfilter, normalize, fp16, out, fit_channels, seamless, tta)
@@ -429,6 +458,32 @@ class Model:
         _check_out(out, (oh, ow) + tuple(r.shape[2:]))
         with torch.cuda.device(r.device):
             r = U.resample(r, size=(oh, ow), filter=outfilter, wrap=seamless == 'tile', out=out)
+        return r.cpu().numpy() if host else r
+
+    def _run_u8_color_fix(self, img, color_fix, normalize=False, fp16=True, out=None, fit_channels=False, seamless=None, outscale=None, outfilter='lanczos', tta=False):
+        """run_u8(color_fix=): the plain call on the device, utils.color_fix of the device image and the device result [, utils.resample] before the download."""
+        from . import lib as L
+        from .utils import utils as U
+        mode = color_fix
+        L.color_fix_mode(mode)
+        final = None
+        if outscale is not None:
+            final = U.resample_size(img.shape[0], img.shape[1], outscale)
+            L.resample_filter(outfilter)
+        d, host = self._as_device_u8(img)
+        r = self.run_u8(d, normalize=normalize, fp16=fp16, fit_channels=fit_channels, seamless=seamless, tta=tta)
+        flat = r.dim() == 2                                     # fit_channels of an H x W image: fixed as H x W x 1
+        lr, sr = (d[:, :, None] if d.dim() == 2 else d), (r[:, :, None] if flat else r)
+        if final is None:
+            _check_out(out, r.shape)
+        else:
+            _check_out(out, final + tuple(r.shape[2:]))
+        with torch.cuda.device(r.device):
+            r = U.color_fix(lr, sr, mode=mode, out=None if out is None or final is not None else (out[:, :, None] if flat else out))
+            if flat:
+                r = r[:, :, 0]
+            if final is not None:
+                r = U.resample(r, size=final, filter=outfilter, wrap=seamless == 'tile', out=out)
         return r.cpu().numpy() if host else r
 
     def _tta_fits(self, nbytes, device):
@@ -555,6 +610,7 @@ class Model:
         return out
 
     # ------------------------------------------------------------- many images as one tile stream
+    @_accepts_color_fix('_run_u8_batch')
     def run_u8_batch(self, imgs, normalize=False, fp16=True, seamless=None, outscale=None, outfilter='lanczos', fit_channels=False, tta=False):
         """[run_u8(img, same options) for img in imgs], bit for bit -- that is the definition.  imgs: uint8 HWC images of any sizes, all numpy arrays
         (numpy results) or all cuda tensors (cuda results).  The results of a group are views of ONE buffer -- page-locked host memory for numpy results, which
@@ -563,19 +619,25 @@ class Model:
         ONE tile stream: a chop tile is ps x ps whatever its image's size, so the images are grouped by (channels, ps), result order kept; per group the
         images are packed into one buffer (numpy: one pinned staging buffer, one upload; cuda: packed on the device), ONE gather cuts all their tiles
         (innfer_extract_tiles_u8_multi), run_tile_batches runs the stream exactly as _chop_u8 runs one image's, ONE blend writes every result into one
-        packed buffer (innfer_recompose_u8_multi), outscale= resamples each result on the device, and one copy into pinned memory brings a group's results
+        packed buffer (innfer_recompose_u8_multi), color_fix= fixes each result against its image in the packed upload, outscale= resamples each result on the device, and one copy into pinned memory brings a group's results
         back.  Small images then share a network launch instead of running one launch each on a fraction of the chip.  A group whose tile buffers
         (low-resolution tiles and results) exceed half of the free memory (_batch_fits: the _tta_fits rule) runs as consecutive sub-groups, and an
         allocator out-of-memory on the buffers halves the group: the same bits.  An image that is left alone in its group goes through run_u8 itself.
         Everything else -- Model(tile=N), Model(tile=0), chop=False, fit_channels, tta, a train-mode model (meval=False: BatchNorm depends on the batch) --
-        loops run_u8 over the images: correct by definition, not faster."""
+        loops run_u8 over the images: correct by definition, not faster.
+        color_fix (keyword only, added by _accepts_color_fix as for run_u8): run_u8's; the fast path fixes every packed device result against its image
+        in the packed upload before the resample."""
+        return self._run_u8_batch(imgs, normalize, fp16, seamless, outscale, outfilter, fit_channels, tta)
+
+    def _run_u8_batch(self, imgs, normalize=False, fp16=True, seamless=None, outscale=None, outfilter='lanczos', fit_channels=False, tta=False, color_fix=None):
+        """run_u8_batch [with color_fix=]."""
         import numpy as np
         from .utils import utils as U
         imgs = list(imgs)
         host = [isinstance(im, np.ndarray) for im in imgs]
         if imgs and any(host) != all(host):
             raise TypeError('run_u8_batch: the images must be all numpy arrays or all cuda tensors')
-        opts = dict(normalize=normalize, fp16=fp16, seamless=seamless, outscale=outscale, outfilter=outfilter, fit_channels=fit_channels, tta=tta)
+        opts = dict(normalize=normalize, fp16=fp16, seamless=seamless, outscale=outscale, outfilter=outfilter, fit_channels=fit_channels, tta=tta, color_fix=color_fix)
 
         def plain(im):                                          # what the gather and the blend are built for; anything else is run_u8's to run or refuse
             if isinstance(im, np.ndarray):
@@ -583,6 +645,9 @@ class Model:
             return torch.is_tensor(im) and im.is_cuda and im.dim() == 3 and 1 <= im.shape[2] <= 4 and im.dtype == torch.uint8
         if not (self.chop and self.tile is None and self.eval and not fit_channels and not tta and all(plain(im) for im in imgs)):
             return [self.run_u8(im, **opts) for im in imgs]
+        if color_fix is not None:
+            from . import lib as L
+            L.color_fix_mode(color_fix)
         mode = None
         for im in imgs:                                         # run_u8's refusals, before anything runs
             if seamless is not None:
@@ -646,6 +711,7 @@ class Model:
         from .utils import utils as U
         s, Cc = int(self.scale or 1), imgs[idx[0]].shape[2]
         normalize, fp16, seamless, outscale, outfilter = (opts[k] for k in ('normalize', 'fp16', 'seamless', 'outscale', 'outfilter'))
+        color_fix = opts.get('color_fix')
         dt, code = (torch.float16, L.F16) if fp16 else (torch.float32, L.F32)
         pad, border = (0, L.BORDER_MODES['replicate']) if mode is None else (U.SEAMLESS_PAD, mode)
         plan = L.chop_multi_plan([imgs[i].shape[:2] for i in idx], Cc, pad, 200, 0.5, s)
@@ -674,7 +740,9 @@ class Model:
             L.check(L.lib.innfer_extract_tiles_u8_multi(d.data_ptr(), n, sizes.ctypes.data, Cc, int(bool(normalize)), 200, 0.5, pad, border, table.data_ptr(),
                                                         tiles.data_ptr(), code, stream))
             hr = run_tile_batches(self.model, tiles, self.tile_batch, pick=self._pick if self.arch == 'ppon' else None, out=buf)
-            del tiles, d, table
+            del tiles, table
+            if color_fix is None:
+                del d
             hr = hr.contiguous()
             Co, P = hr.shape[1], hr.shape[2]
             if Co != Cc:                                        # the packed results hold the network's channel count
@@ -687,6 +755,12 @@ class Model:
             del hr, frames
             shapes = [(int(h) * s, int(w) * s, Co) for h, w in sizes]
             res = [out[out_off[j]:out_off[j] + int(np.prod(shapes[j]))].view(shapes[j]) for j in range(n)]
+            if color_fix is not None:                           # run_u8's definition: utils.color_fix of each image in the packed upload and its device result
+                lrs = [d[in_off[j]:in_off[j] + int(h) * int(w) * Cc].view(int(h), int(w), Cc) for j, (h, w) in enumerate(sizes)]
+                out = torch.empty_like(out)
+                res = [U.color_fix(lr, r, mode=color_fix, out=out[out_off[j]:out_off[j] + int(np.prod(shapes[j]))].view(shapes[j]))
+                       for j, (lr, r) in enumerate(zip(lrs, res))]
+                del d, lrs
             if outscale is not None:                            # run_u8's definition: utils.resample of each device result, here into one packed buffer
                 finals = [U.resample_size(int(h), int(w), outscale) + (Co,) for h, w in sizes]
                 off = np.concatenate(([0], np.cumsum([-(-int(np.prod(f)) // 16) * 16 for f in finals])))
@@ -782,6 +856,7 @@ def get_scale_name(model_path, scale=None):
 
 SEAMLESS_CHOICES = ('tile', 'mirror', 'replicate', 'alpha_pad')           # utils.SEAMLESS_MODES
 OUTFILTER_CHOICES = ('lanczos', 'bicubic', 'bilinear', 'box')             # utils.RESAMPLE_FILTERS
+CF_MODE_CHOICES = ('lowfreq', 'wavelet', 'adain')                         # utils.COLOR_FIX_MODES
 
 pix2pix_extras = {'meval': False, 'strict': True, 'normalize': True}       # run.py:299-303
 cyglegan_extras = {'meval': True, 'strict': False, 'normalize': True}      # run.py:305-309
@@ -812,6 +887,10 @@ def build_parser():
                         help='Final size relative to the input, e.g. 2 or 2.5 with a 4x model: the result is resampled on the GPU before it is downloaded.')
     parser.add_argument('-outfilter', required=False, choices=OUTFILTER_CHOICES, default=argparse.SUPPRESS,
                         help='Filter of -outscale (default lanczos); antialiased when it reduces.')
+    parser.add_argument('-cf_mode', required=False, choices=CF_MODE_CHOICES, default=argparse.SUPPRESS,
+                        help='The colour correction (given alone it turns the correction on; -cf alone is lowfreq).  lowfreq: the low-frequency LR - SR difference '
+                             'in linear light; wavelet: the result keeps its own detail and takes the input\'s colours below about 63 px (five a-trous levels, '
+                             'StableSR\'s wavelet fix); adain: every channel is moved to the input\'s mean and standard deviation.')
     parser.add_argument('-tta', required=False, action='store_true', default=argparse.SUPPRESS,
                         help='Self-ensemble ("x8"): run the image in its eight flipped / rotated orientations and average the results before quantisation; '
                              'eight times the network cost.')
@@ -875,6 +954,7 @@ def main(argv=None):
             raise ValueError(f"-batch {batch} with '{args.arch}': the preset runs every image whole, there are no tiles to share a launch")
     tta = getattr(args, 'tta', False)
     outscale, outfilter = getattr(args, 'outscale', None), getattr(args, 'outfilter', 'lanczos')
+    cf_mode = getattr(args, 'cf_mode', 'lowfreq' if args.cf else None)      # None: no colour correction
     if outscale is not None:
         U.resample_size(1, 1, outscale)                     # ValueError unless 0 < F < inf
     meval, strict = defaults['meval'], defaults['strict']
@@ -946,10 +1026,13 @@ def main(argv=None):
         if tta:
             sm['tta'] = True
         final = U.resample_size(img.shape[0], img.shape[1], outscale) if outscale is not None else None      # relative to the image fed to the chain
-        if final and not args.cf:                                                   # run_u8 resamples before the download
+        in_run_u8 = single and (plan or img.ndim == 3)                              # the network step is run_u8 / run_u8_batch: the fix and the resample go into it
+        if final and (in_run_u8 or not cf_mode):                                    # run_u8 resamples before the download
             sm.update(outscale=outscale, outfilter=outfilter)
+        if cf_mode and in_run_u8:
+            sm['color_fix'] = cf_mode
         src = img
-        if seamless and not (single and (plan or img.ndim == 3)):                   # chains, 16-bit images, the guided filter: pad once in front, crop behind
+        if seamless and not in_run_u8:                   # chains, 16-bit images, the guided filter: pad once in front, crop behind
             img = U.seamless_pad(img, seamless)
         return img, src, plan, flat, single, sm, final
 
@@ -963,14 +1046,14 @@ def main(argv=None):
         t_img = U.np2tensor(img, normalize=normalize, device=device, dtype=torch.float16 if fp16 else torch.float32)
         return U.tensor2np(chain(t_img).detach(), denormalize=normalize)
 
-    def after(image_path, img, src, flat, final, img_out):
+    def after(image_path, img, src, flat, final, img_out, fixed):
         if img is not src:                                                          # padded in front of the chain: PAD x the chain's scale off every side
             total = 1
             for mod in models:
                 total *= int(mod.scale or 1)
             img, img_out = src, U.seamless_crop(img_out, total)
-        if args.cf:
-            img_out = U.color_fix(img, img_out)
+        if cf_mode and not fixed:
+            img_out = U.color_fix(img, img_out, mode=cf_mode)
         if final and img_out.shape[:2] != final:                                    # not done inside run_u8: chains, -cf, 16-bit images, the guided filter
             img_out = U.resample(img_out, size=final, filter=outfilter, wrap=seamless == 'tile')
         if flat:
@@ -1004,7 +1087,7 @@ def main(argv=None):
                 opts = ready[together[0]][6]                                            # the same for every image of a run
                 batched = dict(zip(together, models[0].run_u8_batch([ready[k][1] for k in together], normalize=normalize, fp16=fp16, **opts)))
             for k, (image_path, img, src, plan, flat, single, sm, final) in enumerate(ready):
-                after(image_path, img, src, flat, final, batched.pop(k) if k in batched else network(img, plan, single, sm))
+                after(image_path, img, src, flat, final, batched.pop(k) if k in batched else network(img, plan, single, sm), 'color_fix' in sm)
         while pending:
             pending.popleft().result()
     finally:

@@ -600,27 +600,145 @@ def linear_resize(img, st=256, device='cuda'):
     return out.cpu().numpy()
 
 
-def color_fix(imgA, imgB, device='cuda'):
+COLOR_FIX_MODES = tuple(L.COLOR_FIX_MODES)
+
+
+def _cubic_taps_np(dst_size, src_size):
+    """cubic_taps of csrc/colorfix.hip for every destination index of an axis: the four clamped source indices and the four float32 weights
+    (A = -0.75, src = (dst + 0.5) * (src_size / dst_size) - 0.5)."""
+    f32 = np.float32
+    A, one = f32(-0.75), f32(1)
+    f = (np.arange(dst_size, dtype=np.float32) + f32(0.5)) * (f32(src_size) / f32(dst_size)) - f32(0.5)
+    fl = np.floor(f)
+    t = f - fl
+    w0 = ((A * (t + one) - f32(5) * A) * (t + one) + f32(8) * A) * (t + one) - f32(4) * A
+    w1 = ((A + f32(2)) * t - (A + f32(3))) * t * t + one
+    w2 = ((A + f32(2)) * (one - t) - (A + f32(3))) * (one - t) * (one - t) + one
+    w3 = one - w0 - w1 - w2
+    idx = np.clip(fl.astype(np.int64)[:, None] + np.arange(-1, 3)[None, :], 0, src_size - 1)
+    return idx, np.stack([w0, w1, w2, w3], 1)
+
+
+def _cubic_enlarge_np(x, oh, ow):
+    """cubic_sample of csrc/colorfix.hip for every pixel of the oh x ow result: per source row r = 0 + s0 w0 + s1 w1 + s2 w2 + s3 w3 along x, then
+    acc = acc + r * wy[j] over the four rows; float32 HWC."""
+    ix, wx = _cubic_taps_np(ow, x.shape[1])
+    iy, wy = _cubic_taps_np(oh, x.shape[0])
+    rows = np.zeros((x.shape[0], ow, x.shape[2]), np.float32)
+    for k in range(4):
+        rows = rows + x[:, ix[:, k]] * wx[:, k].reshape(1, ow, 1)
+    acc = np.zeros((oh, ow, x.shape[2]), np.float32)
+    for k in range(4):
+        acc = acc + rows[iy[:, k]] * wy[:, k].reshape(oh, 1, 1)
+    return acc
+
+
+def _atrous_np(x, levels=5):
+    """`levels` a-trous levels of the [0.25, 0.5, 0.25] filter, dilation 2^i: along x, then along y, replicate border, float32."""
+    f32 = np.float32
+    for i in range(levels):
+        r = 1 << i
+        for axis in (1, 0):
+            n = x.shape[axis]
+            p = np.arange(n)
+            lo, hi = np.take(x, np.clip(p - r, 0, n - 1), axis=axis), np.take(x, np.clip(p + r, 0, n - 1), axis=axis)
+            x = x * f32(0.5) + (lo + hi) * f32(0.25)
+    return x
+
+
+def _adain_stats_np(img):
+    """Per channel (mean, unbiased variance) in float64 from the exact integer sums of the uint8 image."""
+    n = img.shape[0] * img.shape[1]
+    x = img.reshape(n, img.shape[2]).astype(np.int64)
+    m = x.sum(0).astype(np.float64) / np.float64(n)
+    q = (x * x).sum(0).astype(np.float64) / np.float64(n)
+    var = np.maximum(q - m * m, 0.0) * (np.float64(n) / np.float64(n - 1)) if n > 1 else np.zeros_like(m)
+    return m, var
+
+
+def color_fix_np(imgA, imgB, mode):
+    """The contract of the colour fixes that are not the reference's (`-cf_mode wavelet | adain`), in numpy; innfer_color_fix_mode computes the same
+    codes.  imgA: the LR image, imgB: the SR image, uint8 HWC with one C in 1 .. 4, of equal sizes or with hA < hB and wA < wB.  Channels are
+    independent; alpha is one more channel.
+    'wavelet' (StableSR's wavelet reconstruction: SR's high band on LR's low band, as one decomposition of the difference), float32, code units:
+    d = up - f32(imgB), up = f32(imgA) or its cubic enlargement to B's size (_cubic_enlarge_np: the arithmetic of csrc/colorfix.hip's cubic_sample);
+    five a-trous levels of d (_atrous_np); clamp(floor(f32(imgB) + B5(d) + 0.5), 0, 255).
+    'adain': per channel, from the exact integer sums, in float64: m = S1 / n, q = S2 / n, var = max(q - m m, 0) n / (n - 1) (0 for n = 1),
+    eps = 1e-5 * 255 * 255, g = sqrt(varA + eps) / sqrt(varB + eps), o = mA - mB g; clamp(floor(f32(imgB) * f32(g) + f32(o) + 0.5), 0, 255) with the
+    product and the sum each rounded to float32.  LR's statistics are those of the LR image itself.
+    'lowfreq' is color_fix itself (the reference's fix) and is not restated here."""
+    for im in (imgA, imgB):
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 3:
+            raise TypeError('color_fix_np: expected uint8 HWC numpy images')
+    if mode not in ('wavelet', 'adain'):
+        raise ValueError(f"color_fix_np: mode must be 'wavelet' or 'adain', got {mode!r}")
+    if imgA.shape[2] != imgB.shape[2] or not 1 <= imgA.shape[2] <= 4:
+        raise ValueError('color_fix_np: both images need the same channel count in 1 .. 4')
+    (hA, wA), (hB, wB) = imgA.shape[:2], imgB.shape[:2]
+    scaling = hA < hB and wA < wB
+    if not scaling and (hA, wA) != (hB, wB) or min(hA, wA, hB, wB) < 1:
+        raise ValueError(f'color_fix_np: images of {hA}x{wA} and {hB}x{wB} cannot be subtracted')
+    f32 = np.float32
+    b = imgB.astype(np.float32)
+    if mode == 'wavelet':
+        up = _cubic_enlarge_np(imgA.astype(np.float32), hB, wB) if scaling else imgA.astype(np.float32)
+        v = b + _atrous_np(up - b)
+    else:
+        (mA, vA), (mB, vB) = _adain_stats_np(imgA), _adain_stats_np(imgB)
+        eps = np.float64(1e-5 * 255 * 255)
+        g = np.sqrt(vA + eps) / np.sqrt(vB + eps)
+        o = mA - mB * g
+        v = b * g.astype(np.float32) + o.astype(np.float32)
+    return np.clip(np.floor(v + f32(0.5)), 0, 255).astype(np.uint8)
+
+
+def color_fix(imgA, imgB, device='cuda', mode='lowfreq', out=None):
     """`-cf` (utils.py:278-315): add the low-frequency LR - SR difference (linear light) back to the SR
     image.  imgA (LR) and imgB (SR) are uint8 HWC numpy images like the reference's; both cross PCIe as
     uint8, everything else runs in libinnfer_amd.so (csrc/colorfix.hip); returns a uint8 HWC numpy image.
     The reference's two OpenCV calls (bicubic resize, 3x3 Gaussian) follow OpenCV's published float32
-    algorithms -- OpenCV itself is not available here to compare with."""
-    for im in (imgA, imgB):
-        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 3:
-            raise TypeError('color_fix: expected uint8 HWC numpy images')
+    algorithms -- OpenCV itself is not available here to compare with.
+    mode: 'lowfreq' is that fix; 'wavelet' and 'adain' are color_fix_np's (`-cf_mode`), to the code.
+    Two cuda uint8 tensors stay on the GPU: the result is a cuda tensor (`out` when given: contiguous, of imgB's shape), launched on the current stream."""
+    code = L.color_fix_mode(mode)
+    dev_in = torch.is_tensor(imgA) and torch.is_tensor(imgB)
+    if dev_in:
+        for im in (imgA, imgB):
+            if im.dtype != torch.uint8 or im.dim() != 3:
+                raise TypeError('color_fix: expected uint8 HWC tensors')
+            _need_cuda(im, 'color_fix')
+        if imgA.device != imgB.device:
+            raise ValueError('color_fix: the two images are on different devices')
+    else:
+        for im in (imgA, imgB):
+            if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 3:
+                raise TypeError('color_fix: expected uint8 HWC numpy images')
     if imgA.shape[2] != imgB.shape[2]:
         raise ValueError('color_fix: channel counts differ')
     hA, wA, Cc = imgA.shape
     hB, wB, _ = imgB.shape
-    d_a = torch.from_numpy(np.ascontiguousarray(imgA)).to(device)
-    d_b = torch.from_numpy(np.ascontiguousarray(imgB)).to(device)
-    out = torch.empty((hB, wB, Cc), dtype=torch.uint8, device=d_a.device)
-    ws = torch.empty(L.lib.innfer_color_fix_workspace_bytes(hA, wA, hB, wB, Cc), dtype=torch.uint8, device=d_a.device)
-    with _on(out):
-        L.check(L.lib.innfer_color_fix(d_a.data_ptr(), hA, wA, d_b.data_ptr(), hB, wB, Cc, out.data_ptr(),
-                                       ws.data_ptr(), ws.numel(), _stream(out)))
-    return out.cpu().numpy()
+    if dev_in:
+        d_a, d_b = imgA.contiguous(), imgB.contiguous()
+    else:
+        d_a = torch.from_numpy(np.ascontiguousarray(imgA)).to(device)
+        d_b = torch.from_numpy(np.ascontiguousarray(imgB)).to(device)
+    if out is None:
+        out = torch.empty((hB, wB, Cc), dtype=torch.uint8, device=d_a.device)
+    elif not torch.is_tensor(out) or tuple(out.shape) != (hB, wB, Cc) or out.dtype != torch.uint8 or out.device != d_a.device or not out.is_contiguous():
+        raise ValueError(f'color_fix: out must be a contiguous uint8 tensor of shape {(hB, wB, Cc)} on {d_a.device}')
+    elif out.data_ptr() == d_b.data_ptr() or out.data_ptr() == d_a.data_ptr():
+        raise ValueError('color_fix: out must not be one of the two images (neighbouring pixels are read after the first are written)')
+    if code == 0:                                               # the reference's fix: the call it has always been
+        ws = torch.empty(L.lib.innfer_color_fix_workspace_bytes(hA, wA, hB, wB, Cc), dtype=torch.uint8, device=d_a.device)
+        with _on(out):
+            L.check(L.lib.innfer_color_fix(d_a.data_ptr(), hA, wA, d_b.data_ptr(), hB, wB, Cc, out.data_ptr(),
+                                           ws.data_ptr(), ws.numel(), _stream(out)))
+    else:
+        ws = torch.empty(max(1, L.lib.innfer_color_fix_mode_workspace_bytes(code, hA, wA, hB, wB, Cc)), dtype=torch.uint8, device=d_a.device)
+        with _on(out):
+            L.check(L.lib.innfer_color_fix_mode(code, d_a.data_ptr(), hA, wA, d_b.data_ptr(), hB, wB, Cc, out.data_ptr(),
+                                                ws.data_ptr(), ws.numel(), _stream(out)))
+    return out if dev_in else out.cpu().numpy()
 
 
 def guided_filter(x, y, x_HR=None, ks=None, r=None, eps=1e-2, box_kernel=None, mode='regular', conv_a=None):
