@@ -1,4 +1,4 @@
-// First convolution of a generator: few input channels (1..4), NCHW planar input
+// First convolution of a generator: few input channels (1..8), NCHW planar input
 // straight from the caller's tensor, fp16 blocked-NHWC slab output.
 // Replaces `fea_conv = conv_block(in_nc, nf, 3)` (RRDBNet_arch.py:25, SRResNet_arch.py:24).
 //

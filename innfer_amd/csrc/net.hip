@@ -83,7 +83,7 @@ extern "C" int innfer_timer_stop(void* stream, int cap, char* names, int name_ca
 struct ConvSlot {
     std::string key;
     int K = 0, C = 0;
-    bool first = false;          // small-Cin VALU conv (fp32 [C*9][K] weights)
+    bool first = false;          // the network's first conv: first_conv_mfma, few input channels (fp32 [C*9][K] weights, first_conv_layout)
     int ksize = 3;               // 1: a 1x1 conv (one-tap panel, ConvLaunch.conv1x1)
     void* d_w = nullptr;         // packed panels (MFMA) or fp32 k-major (first)
     std::vector<float> h_w;      // MFMA convs: the fp32 weights as they were set, kept for the fp32-accurate mode's panels
@@ -334,6 +334,14 @@ static int build_split_panels(ConvSlot& c) {
     return INNFER_OK;
 }
 
+// A first conv's weights as first_conv_mfma reads them (FirstConvLaunch.w): OIHW [K][C][3][3] -> k-major [C * 9][K] fp32.  The one layout code of
+// innfer_net_set_conv and innfer_first_conv.
+static void first_conv_layout(const float* w, int K, int C, float* d) {
+    for (int ci = 0; ci < C; ++ci)
+        for (int t = 0; t < 9; ++t)
+            for (int k = 0; k < K; ++k) d[((size_t)ci * 9 + t) * K + k] = w[((size_t)k * C + ci) * 9 + t];
+}
+
 extern "C" int innfer_net_set_conv(innfer_net_t net, int idx, const float* w, const float* b) {
     if (!net || idx < 0 || idx >= (int)net->convs.size() || !w) return set_error(INNFER_ERR_INVALID, "set_conv: bad arguments");
     ConvSlot& c = net->convs[idx];
@@ -345,10 +353,7 @@ extern "C" int innfer_net_set_conv(innfer_net_t net, int idx, const float* w, co
         bias_n = c.K;
     } else if (c.first) {
         host.resize((size_t)c.C * 9 * c.K * sizeof(float));
-        float* d = (float*)host.data();
-        for (int ci = 0; ci < c.C; ++ci)
-            for (int t = 0; t < 9; ++t)
-                for (int k = 0; k < c.K; ++k) d[((size_t)ci * 9 + t) * c.K + k] = w[((size_t)k * c.C + ci) * 9 + t];
+        first_conv_layout(w, c.K, c.C, (float*)host.data());
         bias_n = c.K;
     } else {
         if (c.ksize == 1) {          // [K,C,1,1]: the one-tap panel of the kernel's 1x1 instantiation
@@ -742,11 +747,36 @@ __global__ void slab_pixel_shuffle(const f16* src, long src_g, f16* dst, long ds
     *(f16x8*)(dst + (long)(c >> 5) * dst_g + m * 32 + (c & 31)) = v;
 }
 
-int do_input_map(const ConvSlot& cs, const f16* src, f16* dst, long G, hipStream_t s, long lo = 0) {
-    const int groups = (cs.C + 31) / 32;
+// The launchers of the slab passes: innfer_net_forward and the single-launch entry points (innfer_slab_*, for tests) both go through them, so grid, block and
+// argument order under test are the network's.
+// map: alpha[C] then shift[C] (device); G: elements of a group, all of them mapped; lo != 0: the (hi, lo) pair form
+int launch_input_map(const f16* src, f16* dst, long G, int C, const float* map, int act, hipStream_t s, long lo = 0) {
+    const int groups = (C + 31) / 32;
     const long n = G / 8 * groups;
-    if (lo) hipLaunchKernelGGL(slab_input_map_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, lo, G, groups, (const float*)cs.d_map, cs.C, cs.map_act);
-    else hipLaunchKernelGGL(slab_input_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, G, groups, (const float*)cs.d_map, cs.C, cs.map_act);
+    if (lo) hipLaunchKernelGGL(slab_input_map_split, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, lo, G, groups, map, C, act);
+    else hipLaunchKernelGGL(slab_input_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, dst, G, groups, map, C, act);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int do_input_map(const ConvSlot& cs, const f16* src, f16* dst, long G, hipStream_t s, long lo = 0) {
+    return launch_input_map(src, dst, G, cs.C, (const float*)cs.d_map, cs.map_act, s, lo);
+}
+
+// PixelShuffle(r) of nf r^2 channels on the h x w grid -> nf channels on r h x r w; lo != 0: once more on the lo twins, `lo` elements behind either slab
+int launch_pixel_shuffle(const f16* src, long src_g, f16* dst, long dst_g, int nf, int N, int h, int w, int r, hipStream_t s, long lo = 0) {
+    const long nthr = (long)N * h * w * r * r * (nf / 8);
+    hipLaunchKernelGGL(slab_pixel_shuffle, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, src, src_g, dst, dst_g, nf, N, h, w, r);
+    if (lo) hipLaunchKernelGGL(slab_pixel_shuffle, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, src + lo, src_g, dst + lo, dst_g, nf, N, h, w, r);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+// nearest-neighbour f x of `groups` 32-channel groups; lo as above
+int launch_upsample_nearest(const f16* src, long src_g, f16* dst, long dst_g, int groups, int N, int h, int w, int f, hipStream_t s, long lo = 0) {
+    const long nthr = (long)N * f * f * h * w * 4 * groups;
+    hipLaunchKernelGGL(slab_upsample_nearest, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, src, src_g, dst, dst_g, groups, N, h, w, f);
+    if (lo) hipLaunchKernelGGL(slab_upsample_nearest, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, src + lo, src_g, dst + lo, dst_g, groups, N, h, w, f);
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
 }
@@ -1024,19 +1054,16 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
             f16* Y = (f16*)(ws + cv.hr);
             rc = do_conv(mk(cs, t, gi, Y, gi, N, h, w, net->trunk_act), s);
             if (rc) return rc;
-            const long gr = gi * r * r, nthr = (long)N * h * w * r * r * (net->nf / 8);
-            hipLaunchKernelGGL(slab_pixel_shuffle, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, (const f16*)Y, gi, dst, gr, net->nf, N, h, w, r);
-            if (LO) hipLaunchKernelGGL(slab_pixel_shuffle, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, (const f16*)Y + LO, gi, dst + LO, gr, net->nf, N, h, w, r);
-            INNFER_HIP(hipGetLastError());
+            rc = launch_pixel_shuffle(Y, gi, dst, gi * r * r, net->nf, N, h, w, r, s, LO);
+            if (rc) return rc;
             t = dst; h *= r; w *= r;
             continue;
         }
         if (net->scale == 3) {      // Upsample(nearest 3x), materialised in the (still unused) HR slab -> conv -> LeakyReLU
             f16* U = (f16*)(ws + cv.hr);
-            const long g3 = gi * 9, nthr = (long)N * 9 * h * w * 4 * (net->nf / 32);
-            hipLaunchKernelGGL(slab_upsample_nearest, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, t, gi, U, g3, net->nf / 32, N, h, w, 3);
-            if (LO) hipLaunchKernelGGL(slab_upsample_nearest, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, t + LO, gi, U + LO, g3, net->nf / 32, N, h, w, 3);
-            INNFER_HIP(hipGetLastError());
+            const long g3 = gi * 9;
+            rc = launch_upsample_nearest(t, gi, U, g3, net->nf / 32, N, h, w, 3, s, LO);
+            if (rc) return rc;
             rc = do_conv(mk(cs, U, g3, dst, g3, N, 3 * h, 3 * w, net->trunk_act), s);
             if (rc) return rc;
             t = dst; h *= 3; w *= 3;
@@ -1424,5 +1451,92 @@ extern "C" int innfer_first_conv_unshuffle(const void* d_in, int in_dtype, int n
         if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "first_conv_unshuffle: the launch failed");
     }
     (void)hipFree(d_w); (void)hipFree(d_b);
+    return rc;
+}
+
+// The first conv of RRDBNet / SRResNet / SRVGGNetCompact (and PPON) alone, for tests: first_conv_layout + first_conv_launch, the code the networks run.  Uploads, launches, waits.
+extern "C" int innfer_first_conv(const void* d_in, int in_dtype, int normalize, int fp16_mode, int N, int in_nc, int H, int W,
+                                 const float* h_weight_oihw, const float* h_bias, int K, int act, const float* h_slope,
+                                 void* d_slab, int64_t group_stride, int64_t lo, void* d_slab2, int64_t group_stride2, int64_t lo2, void* stream) {
+    if (!d_in || !h_weight_oihw || !d_slab) return set_error(INNFER_ERR_INVALID, "first_conv: null argument");
+    if (in_dtype != INNFER_F16 && in_dtype != INNFER_F32 && in_dtype != INNFER_U8) return set_error(INNFER_ERR_INVALID, "first_conv: bad dtype");
+    if ((K != 32 && K != 64) || in_nc < 1 || in_nc > 8 || (act != 0 && act != 1 && act != 2 && act != 8))
+        return set_error(INNFER_ERR_UNSUPPORTED, "first_conv: K %d (32 | 64), in_nc %d (1..8), act %d (0, 1, 2, 8)", K, in_nc, act);
+    if (N <= 0 || H <= 0 || W <= 0) return set_error(INNFER_ERR_INVALID, "first_conv: bad shape %dx%dx%d", N, H, W);
+    const long px = (long)N * H * W, need_lo = (long)(K / 32 - 1);
+    if (group_stride < px * 32 || (d_slab2 && group_stride2 < px * 32))
+        return set_error(INNFER_ERR_INVALID, "first_conv: group stride %ld / %ld < %ld", (long)group_stride, (long)group_stride2, px * 32);
+    if (lo < 0 || lo2 < 0 || (lo && lo < need_lo * group_stride + px * 32) || (d_slab2 && ((lo != 0) != (lo2 != 0) || (lo2 && lo2 < need_lo * group_stride2 + px * 32))) || (!d_slab2 && lo2))
+        return set_error(INNFER_ERR_INVALID, "first_conv: the lo distances (%ld, %ld) must be 0 or clear the hi slab, and be given for both slabs or neither", (long)lo, (long)lo2);
+    if (act == 8 && !h_slope) return set_error(INNFER_ERR_INVALID, "first_conv: act 8 needs the slope vector");
+    if (act == 8 && (lo || lo2)) return set_error(INNFER_ERR_UNSUPPORTED, "first_conv: act 8 is built for fp16 outputs (no split output)");
+    std::vector<float> host((size_t)in_nc * 9 * K), bias(K, 0.f);
+    first_conv_layout(h_weight_oihw, K, in_nc, host.data());
+    if (h_bias) for (int k = 0; k < K; ++k) bias[k] = h_bias[k];
+    float *d_w = nullptr, *d_b = nullptr, *d_s = nullptr;
+    int rc = INNFER_OK;
+    if (hipMalloc((void**)&d_w, host.size() * sizeof(float)) != hipSuccess || hipMalloc((void**)&d_b, K * sizeof(float)) != hipSuccess ||
+        (act == 8 && hipMalloc((void**)&d_s, K * sizeof(float)) != hipSuccess))
+        rc = set_error(INNFER_ERR_NOMEM, "first_conv: out of device memory");
+    if (rc == INNFER_OK && (hipMemcpy(d_w, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+                            hipMemcpy(d_b, bias.data(), K * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+                            (d_s && hipMemcpy(d_s, h_slope, K * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)))
+        rc = set_error(INNFER_ERR_HIP, "first_conv: copying the weights failed");
+    if (rc == INNFER_OK) {
+        FirstConvLaunch F{};
+        F.in = d_in; F.in_f32 = in_dtype == INNFER_F32; F.Cin = in_nc; F.in_u8 = in_dtype == INNFER_U8; F.in_norm = normalize != 0; F.in_round16 = fp16_mode != 0;
+        F.w = d_w; F.bias = d_b; F.out = (f16*)d_slab; F.out_gstride = group_stride; F.out2 = (f16*)d_slab2; F.out2_gstride = group_stride2;
+        F.K = K; F.N = N; F.H = H; F.W = W; F.act = act; F.out_lo = lo; F.out2_lo = lo2; F.slope = d_s;
+        rc = first_conv_launch(F, (hipStream_t)stream);
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "first_conv: the launch failed");
+    }
+    (void)hipFree(d_w); (void)hipFree(d_b); (void)hipFree(d_s);
+    return rc;
+}
+
+// The slab passes of innfer_net_forward as single launches, for tests: each checks its arguments and calls the launcher the network calls.
+static int slab_pass_args(const char* what, const void* a, const void* b, int N, int H, int W, int f, int64_t src_gs, int64_t dst_gs, int64_t lo, long src_need, long dst_need) {
+    if (!a || !b) return set_error(INNFER_ERR_INVALID, "%s: null argument", what);
+    if (N <= 0 || H <= 0 || W <= 0 || f < 1) return set_error(INNFER_ERR_INVALID, "%s: bad shape %dx%dx%d, factor %d", what, N, H, W, f);
+    if ((long)H * f > 32768 || (long)W * f > 32768 || (long)N * H * f * W * f > (1L << 30)) return set_error(INNFER_ERR_UNSUPPORTED, "%s: %d images of %d x %d at factor %d", what, N, H, W, f);
+    const long px = (long)N * H * W;
+    if (src_gs < px * 32 || dst_gs < px * f * f * 32) return set_error(INNFER_ERR_INVALID, "%s: group strides %ld / %ld < %ld / %ld", what, (long)src_gs, (long)dst_gs, px * 32, px * f * f * 32);
+    if (lo < 0 || (lo && (lo < src_need || lo < dst_need))) return set_error(INNFER_ERR_INVALID, "%s: lo %ld must be 0 or clear both hi slabs", what, (long)lo);
+    return INNFER_OK;
+}
+
+extern "C" int innfer_slab_upsample_nearest(const void* d_src, int64_t src_gs, void* d_dst, int64_t dst_gs, int groups, int N, int H, int W, int factor, int64_t lo, void* stream) {
+    if (groups < 1 || groups > 64) return set_error(INNFER_ERR_INVALID, "slab_upsample_nearest: %d groups", groups);
+    const long px = (long)N * H * W;
+    if (int rc = slab_pass_args("slab_upsample_nearest", d_src, d_dst, N, H, W, factor, src_gs, dst_gs, lo, (groups - 1) * src_gs + px * 32, (groups - 1) * dst_gs + px * factor * factor * 32)) return rc;
+    return launch_upsample_nearest((const f16*)d_src, src_gs, (f16*)d_dst, dst_gs, groups, N, H, W, factor, (hipStream_t)stream, lo);
+}
+
+extern "C" int innfer_slab_pixel_shuffle(const void* d_src, int64_t src_gs, void* d_dst, int64_t dst_gs, int nf, int N, int H, int W, int r, int64_t lo, void* stream) {
+    if (nf < 8 || nf % 8 || nf > 2048) return set_error(INNFER_ERR_INVALID, "slab_pixel_shuffle: nf %d must be a positive multiple of 8", nf);
+    if (r < 1 || r > 8) return set_error(INNFER_ERR_INVALID, "slab_pixel_shuffle: factor %d", r);
+    const long px = (long)N * H * W;
+    if (int rc = slab_pass_args("slab_pixel_shuffle", d_src, d_dst, N, H, W, r, src_gs, dst_gs, lo, (long)((nf * r * r + 31) / 32 - 1) * src_gs + px * 32, (long)((nf + 31) / 32 - 1) * dst_gs + px * r * r * 32)) return rc;
+    return launch_pixel_shuffle((const f16*)d_src, src_gs, (f16*)d_dst, dst_gs, nf, N, H, W, r, (hipStream_t)stream, lo);
+}
+
+// dst = act(alpha[c] * src + shift[c]) over every element of ceil(C / 32) groups of gs elements (channels beyond C: zero); lo != 0: on the (hi, lo) pairs.  Uploads the map, launches, waits.
+extern "C" int innfer_slab_input_map(const void* d_src, void* d_dst, int64_t gs, int64_t lo, int C, const float* h_alpha, const float* h_shift, int act, void* stream) {
+    if (!d_src || !d_dst) return set_error(INNFER_ERR_INVALID, "slab_input_map: null argument");
+    if (C < 1 || C > 2048 || act < 0 || act > 2) return set_error(INNFER_ERR_INVALID, "slab_input_map: C %d, act %d (0..2)", C, act);
+    if (gs < 32 || gs % 32 || gs > (1L << 31)) return set_error(INNFER_ERR_INVALID, "slab_input_map: a group of %ld elements (whole pixels of 32 channels)", (long)gs);
+    const long groups = (C + 31) / 32;
+    if (lo < 0 || (lo && lo < groups * gs)) return set_error(INNFER_ERR_INVALID, "slab_input_map: lo %ld must be 0 or clear the %ld groups of the hi slab", (long)lo, groups);
+    std::vector<float> h(2 * (size_t)C);
+    for (int i = 0; i < C; ++i) { h[i] = h_alpha ? h_alpha[i] : 1.f; h[C + i] = h_shift ? h_shift[i] : 0.f; }
+    float* d_map = nullptr;
+    if (hipMalloc((void**)&d_map, h.size() * sizeof(float)) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "slab_input_map: out of device memory");
+    int rc = INNFER_OK;
+    if (hipMemcpy(d_map, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = set_error(INNFER_ERR_HIP, "slab_input_map: copying the map failed");
+    if (rc == INNFER_OK) {
+        rc = launch_input_map((const f16*)d_src, (f16*)d_dst, gs, C, d_map, act, (hipStream_t)stream, lo);
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "slab_input_map: the launch failed");
+    }
+    (void)hipFree(d_map);
     return rc;
 }

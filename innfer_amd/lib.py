@@ -111,6 +111,10 @@ SIGNATURES = {
     "innfer_rrdbnet_create_ex": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 10),
     "innfer_rrdbnet_create_ex2": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 11),
     "innfer_first_conv_unshuffle": (C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "innfer_first_conv": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_void_p, C.c_int64, C.c_int64] * 2 + [C.c_void_p]),
+    "innfer_slab_upsample_nearest": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_int] * 5 + [C.c_int64, C.c_void_p]),
+    "innfer_slab_pixel_shuffle": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_int] * 5 + [C.c_int64, C.c_void_p]),
+    "innfer_slab_input_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_srresnet_create_ex": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 6 + [C.c_float, C.c_int]),
     "innfer_net_set_conv_input_map": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "innfer_net_set_outm": (C.c_int, [C.c_void_p, C.c_int]),
