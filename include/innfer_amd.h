@@ -45,7 +45,7 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  innfer_version() returns the library's; a binding should compare. */
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  innfer_version() returns the library's; a binding should compare. */
 #define INNFER_ABI_VERSION 123
 int innfer_version(void);
 const char* innfer_last_error(void);
@@ -93,6 +93,14 @@ int innfer_first_conv_unshuffle(const void* d_in, int in_dtype, int normalize, i
 int innfer_first_conv(const void* d_in, int in_dtype, int normalize, int fp16_mode, int N, int in_nc, int H, int W,
                       const float* h_weight_oihw, const float* h_bias, int K, int act, const float* h_slope,
                       void* d_slab, int64_t group_stride, int64_t lo, void* d_slab2, int64_t group_stride2, int64_t lo2, void* stream);
+/* The same launch with a per-input-channel affine map on the loaded value (SPAN's `(x - mean) * img_range` as the prologue of conv_1): the conv's operand is
+ * fp16(h_alpha[c] * v + h_shift[c]) -- one fp32 fma, one rounding -- of the value v innfer_first_conv would multiply (the fp16 tensor value; np2tensor of the uint8 image:
+ * with fp16_mode 0 and h_alpha = 255 that is code - 255 mean in one rounding).  The zero padding stays zero AFTER the map (a mean folded into the bias would be wrong on
+ * the border ring).  h_alpha / h_shift: in_nc host floats, NULL = 1 / 0; both NULL: no map, innfer_first_conv's launch and bits.  fp16 or uint8 input, act 0 .. 2, one
+ * fp16 slab; a float32 input with a map is INNFER_ERR_UNSUPPORTED. */
+int innfer_first_conv_map(const void* d_in, int in_dtype, int normalize, int fp16_mode, int N, int in_nc, int H, int W,
+                          const float* h_weight_oihw, const float* h_bias, int K, int act, const float* h_alpha, const float* h_shift,
+                          void* d_slab, int64_t group_stride, void* stream);
 /* (123, additive) The slab passes innfer_net_forward runs between its convs, as single launches (for tests); each checks its arguments and calls the launcher the network
  * calls.  Slabs are blocked-NHWC fp16, 32-channel groups `*_gs` elements apart; lo != 0 repeats the launch on the lo twins `lo` elements behind source and destination
  * (the fp32-accurate mode).  The first two do not wait for the stream.
@@ -131,6 +139,20 @@ int innfer_net_set_conv_input_map(innfer_net_t net, int idx, const float* h_alph
  * Every layer is ONE launch (the activation is the conv's epilogue, act 8); the workspace holds two nf-channel slabs and the last conv's 32- / 64-channel slab.
  * Arithmetic of the tail, per output value: fp16(float(fp16 conv value) + float(fp16 input value)) -- torch's half `out += base` -- then float() or tensor2np. */
 int innfer_compact_create(innfer_net_t* out, int in_nc, int out_nc, int nf, int num_conv, int scale);
+
+/* SPAN, the Swift Parameter-free Attention Network (the community's "fast" 2x / 4x models; the reference has no such architecture).  With Conv3XC collapsed to ONE
+ * 3x3 zero-pad-1 conv (its eval form; the caller folds sk + conv.2 . conv.1 . conv.0 into one weight and bias):
+ *   SPAB(x): out1 = c1_r(x); out2 = c2_r(SiLU(out1)); out3 = c3_r(SiLU(out2)); out = (out3 + x) * (sigmoid(out3) - 0.5); returns (out, out1)
+ *   x = (x - mean) * img_range when norm (per channel; the mean is NOT added back); f0 = conv_1(x); b1 .. b5 = block_1 .. block_5; (b6, b5_2) = block_6(b5);
+ *   out = PixelShuffle(scale)(upsampler.0(conv_cat(cat[f0, conv_2(b6), b1, b5_2])))
+ * on the engine of innfer_net_*: innfer_net_conv_info reports the convs under the keys conv_1, block_<i>.c<j>_r (i = 1 .. 6, j = 1 .. 3), conv_2, conv_cat ([nf, 4 nf, 1, 1])
+ * and upsampler.0 (K = out_nc scale^2); innfer_net_set_conv loads them; innfer_net_forward[_timed] / innfer_net_workspace_bytes / innfer_net_flops / innfer_net_set_u8_io
+ * work as for SRVGGNetCompact.  nf in {32, 64} (fewer features: zero-pad the weights -- exact: SiLU(0) = 0 and the gate of (0, 0) is 0), in_nc == out_nc in 1 .. 4,
+ * scale 1 .. 4; anything else is INNFER_ERR_UNSUPPORTED.  fp16 mode only, as SRVGGNetCompact.  mean: in_nc host floats (read only when norm).
+ * A forward is 24 launches: conv_1 (the input map is its prologue: operand fp16(img_range * v - mean[c] * img_range), zero padding AFTER the map), three per SPAB
+ * (act 9, act 9, act 10 with res1 = the block's input), one SiLU pass (block_6's out1 goes to the concat raw), conv_2, conv_cat (1x1 over the concat slab: f0, b1, b5_2 and
+ * conv_2's result were written into it at their channel offsets), upsampler.0, and the PixelShuffle store (innfer_shuffle_add without a base). */
+int innfer_span_create(innfer_net_t* out, int in_nc, int out_nc, int nf, int scale, int norm, float img_range, const float* h_mean);
 /* The activation behind conv `idx` as K host floats: y = x >= 0 ? x : h_slope[c] * x -- nn.PReLU(num_parameters = K).weight, or the constant 0 (ReLU) / 0.1
  * (LeakyReLU(0.1)).  Load time, synchronous.  Every conv of an SRVGGNetCompact except the last needs one before the first forward; other convs refuse it. */
 int innfer_net_set_conv_slope(innfer_net_t net, int idx, const float* h_slope);
@@ -556,6 +578,11 @@ size_t innfer_conv7x7_packed_bytes(int K, int C);
 int innfer_pack_conv7x7(const float* h_weight_oihw, int K, int C, void* h_packed);
 int innfer_pack_up2x_phases(const float* h_weight_oihw, int K, int C, int plane_rows, void* h_packed);
 int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream);
+/* a->act = 9 (SiLU): f * sigmoid(f); a->act = 10 (the gate that ends a SPAB block of SPAN): (f + res1) * (sigmoid(f) - 0.5) with d_res1 the block's input in the
+ * output's slab layout (res1_scale unused; no d_res2) -- fp32 on the accumulator + bias with the hardware exponential / reciprocal, one fp16 rounding at the store.
+ * Built like act 8: epilogues of the plain 3x3 slab convs with K = 64 (plane_rows 0 / 1) and K = 32, batches, row ranges and out_ch_off included; every other form (split,
+ * d_stats_part, the self gate, conv1x1, out_planar, the stride-2 / phase / column / dilated forms, upsample2x, reflect_pad, d_res2, act 9 with d_res1) answers
+ * INNFER_ERR_UNSUPPORTED and act 10 without d_res1 INNFER_ERR_INVALID; nothing is launched. */
 /* The same launch with the per-channel slope activation: a->act = 8 computes f >= 0 ? f : d_slope[c] * f (nn.PReLU; d_slope: device floats padded like d_bias and
  * indexed by the same channel, whatever plane_rows / out_ch_off).  Built as the epilogue of the plain 3x3 slab convs with K = 64 (plane_rows 0 / 1) and K = 32, row
  * ranges and batches included; every other form (split, d_stats_part, the self gate, conv1x1, out_planar, the stride-2 / phase / column / dilated forms, residuals,
@@ -569,6 +596,7 @@ int innfer_conv3x3_f16_grid(const innfer_conv_args* a, int consumer_grid, void* 
  * pixels whose first C scale^2 channels are the conv result (channel c s^2 + a s + b -> output channel c at (s y + a, s x + b)); d_base: planar fp16 [N][C][H][W]
  * (INNFER_F16) or N uint8 HWC BGR(A) images (INNFER_U8: np2tensor with `normalize`, rounded to fp16); d_out: planar fp16 / fp32 [N][C][sH][sW], or N uint8 HWC BGR(A)
  * images (tensor2np of the fp16 result, denormalize = `normalize`).  r = fp16(float(slab) + float(base)): one fp32 add, one rounding.  C 1 .. 4, scale 1 .. 4. */
+/* d_base == NULL: no base -- d_out = PixelShuffle(scale)(slab) alone, the same three stores (SPAN's tail); base_dtype is then ignored. */
 int innfer_shuffle_add(const void* d_slab, int64_t group_stride, const void* d_base, int base_dtype, int normalize, void* d_out, int out_dtype,
                        int N, int C, int H, int W, int scale, void* stream);
 /* Panels of the split form: 3 * innfer_conv3x3_packed_bytes(K, C) bytes ((w - wh) * 2^11 | wh | wh, in the order the kernel's virtual chunks meet them).  (106) */

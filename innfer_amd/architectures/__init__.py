@@ -29,6 +29,8 @@ def get_network(opt_net):
         from .RRDBNet_arch import RealESRGANNet as net
     elif kind == 'compact_net':
         from .SRVGG_arch import SRVGGNetCompact as net
+    elif kind == 'span_net':
+        from .SPAN_arch import SPAN as net
     else:
         raise NotImplementedError('Model [{:s}] not recognized'.format(kind))
     return net(**opt_net)

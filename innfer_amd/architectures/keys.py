@@ -146,6 +146,35 @@ def compact_shapes(num_in_ch=3, num_out_ch=3, num_feat=64, num_conv=16, upscale=
     return s
 
 
+def span_convs():
+    """Prefixes of SPAN's thirteen Conv3XC units in forward order: conv_1, block_<i>.c<j>_r (i = 1 .. 6, j = 1 .. 3), conv_2."""
+    return ['conv_1'] + [f'block_{i}.c{j}_r' for i in range(1, 7) for j in range(1, 4)] + ['conv_2']
+
+
+def span_shapes(num_in_ch=3, num_out_ch=3, feature_channels=48, upscale=4, norm=True, deploy=False, gain=2):
+    """State-dict key -> shape of SPAN (Swift Parameter-free Attention Network).  Conv3XC(ci, co, gain) carries sk = Conv2d(ci, co, 1), conv.0 = Conv2d(ci, ci gain, 1),
+    conv.1 = Conv2d(ci gain, co gain, 3), conv.2 = Conv2d(co gain, co, 1) and eval_conv = Conv2d(ci, co, 3) -- a `deploy` checkpoint only eval_conv; then
+    conv_cat = Conv2d(4 f, f, 1) and upsampler.0 = Conv2d(f, num_out_ch upscale^2, 3).  norm=False checkpoints carry a one-element buffer `no_norm`."""
+    f = feature_channels
+    s = {}
+
+    def conv(k, co, ci, ks):
+        s[k + '.weight'], s[k + '.bias'] = (co, ci, ks, ks), (co,)
+    for p in span_convs():
+        ci = num_in_ch if p == 'conv_1' else f
+        if not deploy:
+            conv(p + '.sk', f, ci, 1)
+            conv(p + '.conv.0', ci * gain, ci, 1)
+            conv(p + '.conv.1', f * gain, ci * gain, 3)
+            conv(p + '.conv.2', f, f * gain, 1)
+        conv(p + '.eval_conv', f, ci, 3)
+    conv('conv_cat', f, 4 * f, 1)
+    conv('upsampler.0', num_out_ch * upscale * upscale, f, 3)
+    if not norm:
+        s['no_norm'] = (1,)
+    return s
+
+
 def srresnet_layout(nb, norm=False, mode='CNA'):
     """Positions of a ResNetBlock's / LR_conv's layers inside the flattened Sequentials (SRResNet_arch.py:23-27,68-86; block.py:242-254,
     B.sequential flattens nested Sequentials): {engine key -> (conv key, BatchNorm in front of the conv or None, BatchNorm behind it or None)}.

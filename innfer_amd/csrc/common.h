@@ -103,7 +103,7 @@ struct ConvLaunch {
     int out_coff;                                 // channel offset inside that group (0 or 16)
     int K;                                        // valid output channels
     int N, H, W;                                  // conv (output) size
-    int act; int up;                              // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 8 per-channel slope (`slope`) / 3 tanh (OUT_NCHW only) / 4, 5 res1 * sigmoid(conv) with / without LeakyReLU (slab) / 6 sigmoid (OUT_NCHW only) / 7 pair gate: 64 rows -> 32 outputs, row 16 lg + r (r < 8) times sigmoid(row 16 lg + r + 8) (slab, PAN's PAConv); up: input read through nearest 2x
+    int act; int up;                              // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 8 per-channel slope (`slope`) / 3 tanh (OUT_NCHW only) / 4, 5 res1 * sigmoid(conv) with / without LeakyReLU (slab) / 6 sigmoid (OUT_NCHW only) / 7 pair gate: 64 rows -> 32 outputs, row 16 lg + r (r < 8) times sigmoid(row 16 lg + r + 8) (slab, PAN's PAConv) / 9 SiLU, f * sigmoid(f) / 10 SPAN's gate, (f + res1) * (sigmoid(f) - 0.5) (s1 unused, no res2) -- 9 and 10: epilogues of the plain 3x3 slab convs of 64 (rowp 0 / 1) and 32 outputs (conv3x3_pc SPAN), every other form refuses them; up: input read through nearest 2x
     const f16* res1; long res1_gstride; float s1;
     const f16* res2; long res2_gstride; float s2;
     int y0, y1;                                   // output rows [y0,y1)
@@ -194,6 +194,10 @@ struct FirstConvLaunch {
     int K; int N, H, W; int act;                  // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 8 per-channel slope (`slope`)
     long out_lo, out2_lo;                         // != 0: split output (ConvLaunch.split): the lo part of every value goes this many elements behind its hi part
     const float* slope;                           // act 8: K device floats, f >= 0 ? f : slope[c] * f (ConvLaunch.slope); fp16 outputs only (no split output)
+    const float* in_map;                          // != nullptr: alpha[Cin] then shift[Cin] (device) -- the conv's operand is fp16(alpha[c] * v + shift[c]), one fp32 fma and one rounding, of
+                                                  // the value v the unmapped conv multiplies (the planar fp16 value; np2tensor of the uint8 image -- with in_round16 = 0 and alpha = 255 that is
+                                                  // code - 255 mean in ONE rounding); the zero padding stays zero behind the map.  fp16 or uint8 input, act 0..2, fp16 outputs; nullptr: today's
+                                                  // kernels and bits
 };
 int first_conv_launch(const FirstConvLaunch& L, hipStream_t s);
 
@@ -215,7 +219,7 @@ int first_unshuffle_launch(const FirstUnshuffleLaunch& L, hipStream_t s);
 // ---- PixelShuffle(s) of a conv slab + the nearest-upsampled network input: SRVGGNetCompact's tail (shuffle_add.hip) ----
 struct ShuffleAddLaunch {
     const f16* slab; long gstride;                // the last conv's result on the LR grid: C s^2 valid channels (channel c s^2 + a s + b -> output channel c at (s y + a, s x + b))
-    const void* base; int base_u8, base_norm;     // the network's input: planar fp16 [N][C][H][W], or the uint8 HWC BGR(A) image as the first conv reads it in the fp16 mode (FirstConvLaunch.in_u8, in_norm, in_round16 = 1)
+    const void* base; int base_u8, base_norm;     // nullptr: no base, the result is PixelShuffle(s) alone (SPAN's tail); else the network's input: planar fp16 [N][C][H][W], or the uint8 HWC BGR(A) image as the first conv reads it in the fp16 mode (FirstConvLaunch.in_u8, in_norm, in_round16 = 1)
     void* out; int out_mode;                      // 0 fp16 / 1 fp32 planar [N][C][sH][sW]; 2 the uint8 HWC BGR(A) image (tensor2np as the store: out_denorm, as ConvLaunch.out_u8 with out_round16)
     int out_denorm;
     int C, s, N, H, W;                            // C 1..4, s 1..4; H x W: the LR grid

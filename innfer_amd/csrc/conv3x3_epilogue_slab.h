@@ -197,6 +197,10 @@ __device__ __forceinline__ void epilogue_slab(const KP& p, f32x4 (&acc)[NT][2 * 
                 } else if (ACT == 4 || ACT == 5) {           // pixel-attention gate (PAN): res1 * sigmoid(conv), ACT 4: LeakyReLU(0.2) after it
                     f = (float)r1[R1 ? m : 0][t][j] * (fast_sigmoid(f));
                     if (ACT == 4) f = fmaxf(f, 0.2f * f);
+                } else if (ACT == 9) {                       // SiLU (conv3x3_pc SPAN)
+                    f = f * fast_sigmoid(f);
+                } else if (ACT == 10) {                      // SPAN's gate: (f + res1) * (sigmoid(f) - 0.5), the second factor as tanh(f / 2) / 2 -- the same value without the cancellation
+                    f = (f + (float)r1[R1 ? m : 0][t][j]) * (0.5f * fast_tanh(0.5f * f));
                 } else {
                     if (ACT == 1) f = __builtin_amdgcn_fmed3f(f, 0.2f * f, ACT_TOP);
                     else if (ACT == 2) f = __builtin_amdgcn_fmed3f(f, 0.f, ACT_TOP);

@@ -58,6 +58,10 @@
 #pragma unroll
                 for (int t = 0; t < NT; ++t) slope_r[t] = *(const f32x4*)(slope_lds + lane_cbase<NT, ROWP>(lg) + toff_lin<NT, ROWP>(t));
                 epilogue_slab<RPW, NT, 8, false, false, true, false, false, false, false, ROWP, false>(p, acc, n, ty0, tx0, cw, li, cbase, dcur, slope_r);
+            } else if constexpr (SPAN) {
+                // act 10 (the gate that ends a SPAB: res1 = the block's input, loaded hoisted) / act 9 (SiLU): plain slab store
+                if (p.act == 10) epilogue_slab<RPW, NT, 10, true, false, true, false, false, false, false, ROWP, false>(p, acc, n, ty0, tx0, cw, li, cbase, dcur);
+                else epilogue_slab<RPW, NT, 9, false, false, true, false, false, false, false, ROWP, false>(p, acc, n, ty0, tx0, cw, li, cbase, dcur);
             } else if constexpr (OUTMODE == OUT_SLAB) {
             if constexpr (STATS) {
                 const int lid = run_start + (p.rev ? run_len - 1 - (jt - slots) : (jt - slots));         // (jt was advanced above)

@@ -37,6 +37,11 @@ __device__ __forceinline__ float first_conv_input(const FP& p, long n, int ci, i
     return p.in_f32 ? ((const float*)p.in)[o] : (float)((const f16*)p.in)[o];
 }
 
+// One input value behind FirstConvLaunch.in_map: operand = fp16(fma(alpha[ci], v, shift[ci])) of the value v the unmapped conv would multiply (first_conv_input).
+__device__ __forceinline__ float first_conv_input_map(const FP& p, const float* map, long n, int ci, int Y, int X, long hw) {
+    return (float)(f16)__builtin_fmaf(map[ci], first_conv_input(p, n, ci, Y, X, hw), map[p.Cin + ci]);
+}
+
 // The same conv on the matrix cores (K = 32 or 64 outputs): the 9 * Cin taps of a pixel are the k dimension of a 16 x 16 x 32 MFMA
 // (27 of 32 for RGB; ceil(9 Cin / 32) steps), 16 consecutive pixels are its columns, 16 * NT output channels its rows.  A lane gathers
 // the 8 patch values of its (pixel, k-octet) straight from the planar input -- 8 loads per lane and 16 pixels instead of the VALU
@@ -52,7 +57,9 @@ constexpr int FIRST_ROWS = 16;
 template <int NT, int STEPS, bool FAST16>                           // STEPS = ceil(9 Cin / 32): 1 for gray / RGB, 2 for 4..7 channels, 3 for 8; FAST16: planar fp16 input
 __global__ __launch_bounds__(256) void first_conv_mfma(const FP p) {
     constexpr bool PRELU = false;
+    constexpr bool IMAP = false;
     [[maybe_unused]] const float* const slope_p = nullptr;
+    [[maybe_unused]] const float* const map_p = nullptr;
 #include "conv_first_body.inc"
 }
 
@@ -61,8 +68,25 @@ struct FPS { FP f; const float* slope; };
 template <int NT, int STEPS, bool FAST16>
 __global__ __launch_bounds__(256) void first_conv_mfma_prelu(const FPS ps) {
     constexpr bool PRELU = true;
+    constexpr bool IMAP = false;
     const FP& p = ps.f;
     const float* const slope_p = ps.slope;
+    [[maybe_unused]] const float* const map_p = nullptr;
+#include "conv_first_body.inc"
+}
+
+// FirstConvLaunch.in_map: the operand is fp16(alpha[c] * v + shift[c]) of the loaded value v (the planar fp16 value, or np2tensor of the uint8 image) -- SPAN's
+// `(x - mean) * img_range` in front of conv_1 without a pass of its own.  One fp32 fma, one rounding; a tap outside the image multiplies zero, AFTER the map (folding the
+// shift into the bias would be wrong on the border ring).  The same body on its generic-input path; act 0 / 1 / 2 at run time.
+struct FPM { FP f; const float* map; };
+template <int NT, int STEPS, bool FAST16>
+__global__ __launch_bounds__(256) void first_conv_mfma_map(const FPM pm) {
+    static_assert(!FAST16, "the mapped operand is computed per value: the generic-input path");
+    constexpr bool PRELU = false;
+    constexpr bool IMAP = true;
+    const FP& p = pm.f;
+    [[maybe_unused]] const float* const slope_p = nullptr;
+    const float* const map_p = pm.map;
 #include "conv_first_body.inc"
 }
 
@@ -76,14 +100,18 @@ int first_conv_launch(const FirstConvLaunch& L, hipStream_t s) {
          L.K, (long)L.N * L.H * L.W, L.H, L.W, L.act, L.out_lo, L.out2_lo};
     if (L.act == 8 && (!L.slope || L.out_lo || L.out2_lo || (L.K != 32 && L.K != 64)))
         return set_error(L.slope ? INNFER_ERR_UNSUPPORTED : INNFER_ERR_INVALID, "first conv: act 8 (per-channel slope) needs the slope vector; built for 32 / 64 fp16 outputs (no split output)");
+    if (L.in_map && (L.in_f32 || L.act == 8 || L.out_lo || L.out2_lo || (L.K != 32 && L.K != 64)))
+        return set_error(INNFER_ERR_UNSUPPORTED, "first conv: the input map is built for fp16 or uint8 input, act 0..2 and 32 / 64 fp16 outputs (no split output)");
     const FPS ps{p, L.slope};
+    const FPM pm{p, L.in_map};
     if (L.K == 32 || L.K == 64) {
         if (L.N > 65535 || (L.H + FIRST_ROWS - 1) / FIRST_ROWS > 65535) return set_error(INNFER_ERR_UNSUPPORTED, "first conv: %d images of %d rows exceed the launch grid", L.N, L.H);
         const dim3 grid((unsigned)((L.W + 63) / 64), (unsigned)((L.H + FIRST_ROWS - 1) / FIRST_ROWS), (unsigned)L.N);
         const int steps = (L.Cin * 9 + 31) / 32;
         const bool fast16 = !L.in_u8 && !L.in_f32 && (long)L.Cin * L.H * L.W < 0x7fffffffL;
         if (L.W >= (1 << 20) - 1) return set_error(INNFER_ERR_UNSUPPORTED, "first conv: %d columns", L.W);
-#define FC(NT_, ST_) do { if (L.act == 8) { if (fast16) hipLaunchKernelGGL((first_conv_mfma_prelu<NT_, ST_, true>), grid, dim3(256), 0, s, ps); \
+#define FC(NT_, ST_) do { if (L.in_map) hipLaunchKernelGGL((first_conv_mfma_map<NT_, ST_, false>), grid, dim3(256), 0, s, pm); \
+                          else if (L.act == 8) { if (fast16) hipLaunchKernelGGL((first_conv_mfma_prelu<NT_, ST_, true>), grid, dim3(256), 0, s, ps); \
                                               else hipLaunchKernelGGL((first_conv_mfma_prelu<NT_, ST_, false>), grid, dim3(256), 0, s, ps); } \
                           else if (fast16) hipLaunchKernelGGL((first_conv_mfma<NT_, ST_, true>), grid, dim3(256), 0, s, p); \
                           else hipLaunchKernelGGL((first_conv_mfma<NT_, ST_, false>), grid, dim3(256), 0, s, p); } while (0)

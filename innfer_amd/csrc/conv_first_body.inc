@@ -1,6 +1,7 @@
 // first_conv_mfma: the kernel body (csrc/conv_first.hip), included textually by the two kernels that share it -- first_conv_mfma (act 0 / 1 / 2, chosen at run time) and
 // first_conv_mfma_prelu (act 8: per-channel slopes, SRVGGNetCompact's body.0 + body.1) -- so that the first keeps exactly the code it had as the only kernel.  It uses the
-// kernel's template parameters (NT, STEPS, FAST16), its argument block `p` (FP), the flag PRELU and the pointer slope_p; not a stand-alone file.
+// kernel's template parameters (NT, STEPS, FAST16), its argument block `p` (FP), the flags PRELU / IMAP and the pointers slope_p / map_p; not a stand-alone file.
+// first_conv_mfma_map (IMAP: a per-input-channel affine on the loaded value, SPAN's `(x - mean) * img_range`) is the third kernel on this body.
     const int lane = threadIdx.x & 63, li = lane & 15, lg = lane >> 4;
     const int nk = p.Cin * 9;
     const int x = blockIdx.x * 64 + (threadIdx.x >> 6) * 16 + li;    // this lane's column
@@ -51,7 +52,7 @@
             if (r == 0) top |= 1u << (st * 8 + e);
             if (r == 2) bot |= 1u << (st * 8 + e);
         }
-    const bool any_lo = !FAST16 && (p.in_f32 != 0 || (p.in_u8 && !p.in_round16));
+    const bool any_lo = !FAST16 && !IMAP && (p.in_f32 != 0 || (p.in_u8 && !p.in_round16));
     [[maybe_unused]] const f16* in16 = (const f16*)p.in + n * p.Cin * hw;
     // One row of the strip: (FAST16) `raw` holds the row's 8 STEPS patch values as loaded -- requested one row ahead, first touched here.
     auto process = [&](int y, const unsigned (&raw)[STEPS][8]) __attribute__((always_inline)) {
@@ -75,6 +76,9 @@
                     const int kk = st * 32 + lg * 8 + e;
                     const int r = (kk - (kk / 9) * 9) / 3;
                     float v = 0.f;
+                    if constexpr (IMAP) {        // the mapped operand: an fp16 value, no lo part; outside the image the operand stays zero
+                        if ((ok >> (st * 8 + e)) & 1) v = first_conv_input_map(p, map_p, n, eoff[st][e] >> 20, y + r - 1, (eoff[st][e] & 0xfffff) - 1, hw);
+                    } else
                     if ((ok >> (st * 8 + e)) & 1) v = first_conv_input(p, n, eoff[st][e] >> 20, y + r - 1, (eoff[st][e] & 0xfffff) - 1, hw);
                     const f16 h = (f16)v;
                     xh[e] = h;

@@ -110,7 +110,8 @@ struct ConvSlot {
 };
 
 struct innfer_net {
-    int kind = 0;                // 0 rrdbnet, 1 srresnet, 2 BasicSR's SRVGGNetCompact (innfer_compact_create; compact_forward)
+    int kind = 0;                // 0 rrdbnet, 1 srresnet, 2 BasicSR's SRVGGNetCompact (innfer_compact_create; compact_forward), 3 SPAN (innfer_span_create; span_forward)
+    bool span_norm = false;      // SPAN(norm=True): conv_1 reads (x - mean) * img_range through FirstConvLaunch.in_map (convs[0].d_map: alpha[in_nc] then shift[in_nc])
     int in_nc = 3, out_nc = 3, nf = 64, nb = 23, gc = 32, scale = 4, n_up = 2;
     int final_act = 0;           // `finalact` of the reference constructors: activation after the last conv (ConvLaunch.act codes)
     int band_rows = 0;
@@ -263,6 +264,41 @@ extern "C" int innfer_compact_create(innfer_net_t* out, int in_nc, int out_nc, i
     }
     add_conv(net, "body." + std::to_string(2 * num_conv + 2), out_nc * scale * scale, nf);
     net->convs.back().Kp = out_nc * scale * scale <= 32 ? 32 : 64;
+    *out = net;
+    return INNFER_OK;
+}
+
+// SPAN (Swift Parameter-free Attention Network; the reference has no such architecture -- include/innfer_amd.h carries the definition): 3x3 convs on the LR grid with
+// SiLU (act 9) and gate (act 10) epilogues.  The convs are the COLLAPSED Conv3XC (one 3x3 conv each, folded by the caller), conv_cat (1x1 over the 4 nf-channel concat) and
+// upsampler.0 (nf -> out_nc scale^2, PixelShuffle in shuffle_add_launch without a base).  fp16 engine only.
+extern "C" int innfer_span_create(innfer_net_t* out, int in_nc, int out_nc, int nf, int scale, int norm, float img_range, const float* mean) {
+    if (!out) return set_error(INNFER_ERR_INVALID, "span_create: null out");
+    if (nf != 32 && nf != 64) return set_error(INNFER_ERR_UNSUPPORTED, "span_create: nf=%d (built: 32, 64; fewer features are zero-padded by the caller)", nf);
+    if (in_nc < 1 || in_nc > 4 || in_nc != out_nc)
+        return set_error(INNFER_ERR_UNSUPPORTED, "span_create: in_nc=%d out_nc=%d (built: in_nc == out_nc in 1..4)", in_nc, out_nc);
+    if (scale < 1 || scale > 4) return set_error(INNFER_ERR_UNSUPPORTED, "span_create: scale %d (built: 1, 2, 3, 4)", scale);
+    if (norm && !mean) return set_error(INNFER_ERR_INVALID, "span_create: norm needs the %d channel means", in_nc);
+    innfer_net* net = new innfer_net();
+    net->kind = 3; net->in_nc = in_nc; net->out_nc = out_nc; net->nf = nf; net->nb = 6;
+    net->gc = 0; net->scale = scale; net->n_up = 0;
+    net->span_norm = norm != 0;
+    add_conv(net, "conv_1", nf, in_nc, true);
+    for (int b = 1; b <= 6; ++b)
+        for (int j = 1; j <= 3; ++j) add_conv(net, "block_" + std::to_string(b) + ".c" + std::to_string(j) + "_r", nf, nf);
+    add_conv(net, "conv_2", nf, nf);
+    add_conv(net, "conv_cat", nf, 4 * nf, false, 1);
+    add_conv(net, "upsampler.0", out_nc * scale * scale, nf);
+    net->convs.back().Kp = out_nc * scale * scale <= 32 ? 32 : 64;
+    if (norm) {                  // (x - mean[c]) * img_range = img_range * x - mean[c] * img_range, x = the fp16 tensor value / np2tensor of the uint8 image
+        float h[8];
+        for (int c = 0; c < in_nc; ++c) { h[c] = img_range; h[in_nc + c] = -mean[c] * img_range; }
+        ConvSlot& c0 = net->convs[0];
+        if (hipMalloc((void**)&c0.d_map, 2 * in_nc * sizeof(float)) != hipSuccess || hipMemcpy(c0.d_map, h, 2 * in_nc * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            innfer_net_destroy(net);
+            return set_error(INNFER_ERR_NOMEM, "span_create: no device memory for the input map");
+        }
+    }
     *out = net;
     return INNFER_OK;
 }
@@ -443,6 +479,7 @@ extern "C" int innfer_net_set_conv_input_map(innfer_net_t net, int idx, const fl
 extern "C" int innfer_net_set_precision(innfer_net_t net, int fp32) {
     if (!net || (fp32 != 0 && fp32 != 1)) return set_error(INNFER_ERR_INVALID, "set_precision: 0 (fp16 arithmetic) or 1 (fp32-accurate)");
     if (fp32 && net->kind == 2) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SRVGGNetCompact is built for the fp16 mode only (no fp32-accurate engine)");
+    if (fp32 && net->kind == 3) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SPAN is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32) {
         // The (wl | wh | wh) panels of every loaded conv are built HERE -- a load-time call, with its hipMalloc and synchronous copies -- never inside
         // innfer_net_forward (stream capture, concurrent callers).  Idempotent: a conv that already has its panels is skipped; innfer_net_set_conv
@@ -558,6 +595,15 @@ static Carve carve(const innfer_net* net, int N, int H, int W) {
         c.slab_w = net->nf;
         c.slab[0] = off; off += al(px * net->nf * 2);
         c.slab[1] = off; if (net->nb > 0) off += al(px * net->nf * 2);
+        c.hr = off; off += al(px * net->convs.back().Kp * 2);
+        c.total = off;
+        return c;
+    }
+    if (net->kind == 3) {        // SPAN: the concat slab (f0 | conv_2 | b1 | b5_2, nf channels each), three rotating feature slabs, the upsampler's 32- / 64-channel slab
+        size_t off = 0;
+        c.slab_w = net->nf;
+        c.fea = off; off += al(px * 4 * net->nf * 2);
+        for (int i = 0; i < 3; ++i) { c.slab[i] = off; off += al(px * net->nf * 2); }
         c.hr = off; off += al(px * net->convs.back().Kp * 2);
         c.total = off;
         return c;
@@ -871,6 +917,101 @@ int compact_forward(innfer_net* net, const void* d_in, int in_dtype, void* d_out
     return timed_end(s, px * k, px * (k * 2.0 + net->in_nc * (T.base_u8 ? 1.0 : 2.0) + k * (T.out_mode == 2 ? 1.0 : T.out_mode == 1 ? 4.0 : 2.0)), 6000);
 }
 
+// dst = SiLU(src) over n8 runs of eight fp16 values: v * sigmoid(v) in fp32 on the stored value, one rounding (SPAN's block_6 keeps its first conv's result raw for the
+// concat, so that one activation is a pass of its own)
+__global__ void slab_silu(const f16* src, f16* dst, long n8) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n8) return;
+    const f16x8 x = *(const f16x8*)(src + i * 8);
+    f16x8 y;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) { const float v = (float)x[e]; y[e] = (f16)(v * fast_sigmoid(v)); }
+    *(f16x8*)(dst + i * 8) = y;
+}
+
+// SPAN (kind 3).  cat = the concat slab, four ranges of nf channels (whole 32-channel groups: torch.cat is a pointer): [f0 | conv_2(b6) | b1 | b5_2].
+//   conv_1 (input map when norm) -> cat[0]; block_i: c1_r act 9, c2_r act 9, c3_r act 10 with res1 = the block's input, rotating through three slabs (block_1 writes its
+//   result to cat[2]); block_6's c1_r runs without activation into cat[3] and slab_silu makes its activated copy; conv_2 -> cat[1]; conv_cat (1x1, 4 nf -> nf);
+//   upsampler.0 -> tail slab; shuffle_add_launch without a base = PixelShuffle(scale) to d_out.  24 launches.
+int span_forward(innfer_net* net, const void* d_in, int in_dtype, void* d_out, int out_dtype, int N, int H, int W, char* ws, const Carve& cv, hipStream_t s) {
+    if (in_dtype == INNFER_F32 || net->fp32) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SPAN is built for the fp16 mode only: fp16 or uint8 input");
+    if (net->outm || net->final_act) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SPAN has no outm / final activation");
+    if (in_dtype == INNFER_U8 && !net->u8_round16) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SPAN is built for the fp16 mode only (innfer_net_set_u8_io fp16_mode = 1)");
+    const long G = (long)N * H * W * 32;
+    const int g = net->nf / 32;
+    f16* cat = (f16*)(ws + cv.fea);
+    f16* cat_r[4] = {cat, cat + (long)g * G, cat + 2L * g * G, cat + 3L * g * G};
+    f16* rot[3] = {(f16*)(ws + cv.slab[0]), (f16*)(ws + cv.slab[1]), (f16*)(ws + cv.slab[2])};
+    f16* tail = (f16*)(ws + cv.hr);
+    int ci = 0;
+    {
+        const ConvSlot& c0 = net->convs[ci++];
+        FirstConvLaunch F{};
+        F.in = d_in; F.in_f32 = 0; F.Cin = c0.C; F.w = (const float*)c0.d_w; F.bias = c0.d_b;
+        F.in_u8 = in_dtype == INNFER_U8; F.in_norm = net->u8_normalize; F.in_round16 = 1;
+        F.out = cat_r[0]; F.out_gstride = G;
+        F.K = net->nf; F.N = N; F.H = H; F.W = W; F.act = 0;
+        F.in_map = net->span_norm ? c0.d_map : nullptr;
+        if (int rc = do_first(F, s)) return rc;
+    }
+    const f16* x = cat_r[0];             // the current block's input
+    for (int b = 1; b <= 6; ++b) {
+        f16* t1 = rot[0] != x ? rot[0] : rot[1];           // two of the three slabs that do not hold x
+        f16* t2 = rot[2] != x && rot[2] != t1 ? rot[2] : rot[1];
+        f16* dst = b == 1 ? cat_r[2] : t1;                 // (c3_r reads t2 and x: t1 is free again once c2_r has read it)
+        const ConvSlot& c1 = net->convs[ci++];
+        const ConvSlot& c2 = net->convs[ci++];
+        const ConvSlot& c3 = net->convs[ci++];
+        if (b < 6) {
+            ConvLaunch L1 = mk_launch(c1, x, G, t1, G, N, H, W, 9, 0);
+            if (int rc = do_conv(L1, s)) return rc;
+        } else {
+            ConvLaunch L1 = mk_launch(c1, x, G, cat_r[3], G, N, H, W, 0, 0);
+            if (int rc = do_conv(L1, s)) return rc;
+            if (int rc = timed_begin(s)) return rc;
+            const long n8 = (long)g * G / 8;
+            hipLaunchKernelGGL(slab_silu, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, (const f16*)cat_r[3], t1, n8);
+            INNFER_HIP(hipGetLastError());
+            if (int rc = debug_after("slab_silu", s)) return rc;
+            // launch kind 6001: the SiLU pass -- bytes: nf channels in and out
+            if (int rc = timed_end(s, (double)n8 * 8, (double)n8 * 8 * 4.0, 6001)) return rc;
+        }
+        ConvLaunch L2 = mk_launch(c2, t1, G, t2, G, N, H, W, 9, 0);
+        if (int rc = do_conv(L2, s)) return rc;
+        ConvLaunch L3 = mk_launch(c3, t2, G, dst, G, N, H, W, 10, 0);
+        L3.res1 = x; L3.res1_gstride = G;
+        if (int rc = do_conv(L3, s)) return rc;
+        x = dst;
+    }
+    {
+        const ConvSlot& c2 = net->convs[ci++];
+        ConvLaunch L = mk_launch(c2, x, G, cat_r[1], G, N, H, W, 0, 0);
+        if (int rc = do_conv(L, s)) return rc;
+    }
+    f16* fused = rot[0] == x ? rot[1] : rot[0];
+    {
+        const ConvSlot& cc = net->convs[ci++];
+        ConvLaunch L = mk_launch(cc, cat, G, fused, G, N, H, W, 0, 0);
+        if (int rc = do_conv(L, s)) return rc;
+    }
+    const ConvSlot& cl = net->convs[ci++];
+    {
+        ConvLaunch L = mk_launch(cl, fused, G, tail, G, N, H, W, 0, 0);
+        L.K = cl.Kp;
+        if (int rc = do_conv(L, s)) return rc;
+    }
+    ShuffleAddLaunch T{};
+    T.slab = tail; T.gstride = G;
+    T.base = nullptr;
+    T.out = d_out; T.out_mode = out_dtype == INNFER_U8 ? 2 : out_dtype == INNFER_F32 ? 1 : 0; T.out_denorm = net->u8_normalize;
+    T.C = net->out_nc; T.s = net->scale; T.N = N; T.H = H; T.W = W;
+    if (int rc = timed_begin(s)) return rc;
+    if (int rc = shuffle_add_launch(T, s)) return rc;
+    if (int rc = debug_after("shuffle (SPAN tail)", s)) return rc;
+    const double px = (double)N * H * W, k = (double)cl.K;
+    return timed_end(s, 0.0, px * (k * 2.0 + k * (T.out_mode == 2 ? 1.0 : T.out_mode == 1 ? 4.0 : 2.0)), 6000);
+}
+
 // Launch a dependent chain of same-resolution convs.  band_rows == 0: one launch per
 // layer over the whole frame.  band_rows > 0: skewed row bands -- layer l of band b
 // covers rows [b*R - l, (b+1)*R - l), so every row a layer reads from its predecessor
@@ -918,6 +1059,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)d_ws;
     if (net->kind == 2) return compact_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
+    if (net->kind == 3) return span_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     const int nf = net->nf, gc = net->gc;
     const long G = (long)N * H * W * 32;          // group stride of every LR-resolution slab
     const long LO = (long)(cv.lo / 2);            // fp32-accurate mode: elements from a slab to its lo twin (0: fp16 mode)
@@ -1317,7 +1459,7 @@ extern "C" int innfer_conv3x3_f16_slope(const innfer_conv_args* a, const float* 
 // PixelShuffle(scale) of a conv slab + the nearest-upsampled input, as a single launch (for tests; SRVGGNetCompact's tail, csrc/shuffle_add.hip)
 extern "C" int innfer_shuffle_add(const void* d_slab, int64_t group_stride, const void* d_base, int base_dtype, int normalize, void* d_out, int out_dtype,
                                   int N, int C, int H, int W, int scale, void* stream) {
-    if ((base_dtype != INNFER_F16 && base_dtype != INNFER_U8) || (out_dtype != INNFER_F16 && out_dtype != INNFER_F32 && out_dtype != INNFER_U8))
+    if ((d_base && base_dtype != INNFER_F16 && base_dtype != INNFER_U8) || (out_dtype != INNFER_F16 && out_dtype != INNFER_F32 && out_dtype != INNFER_U8))
         return set_error(INNFER_ERR_UNSUPPORTED, "shuffle_add: base fp16 or uint8, result fp16, fp32 or uint8");
     ShuffleAddLaunch T{};
     T.slab = (const f16*)d_slab; T.gstride = group_stride;
@@ -1455,9 +1597,24 @@ extern "C" int innfer_first_conv_unshuffle(const void* d_in, int in_dtype, int n
 }
 
 // The first conv of RRDBNet / SRResNet / SRVGGNetCompact (and PPON) alone, for tests: first_conv_layout + first_conv_launch, the code the networks run.  Uploads, launches, waits.
+static int first_conv_impl(const void* d_in, int in_dtype, int normalize, int fp16_mode, int N, int in_nc, int H, int W,
+                           const float* h_weight_oihw, const float* h_bias, int K, int act, const float* h_slope, const float* h_alpha, const float* h_shift,
+                           void* d_slab, int64_t group_stride, int64_t lo, void* d_slab2, int64_t group_stride2, int64_t lo2, void* stream);
 extern "C" int innfer_first_conv(const void* d_in, int in_dtype, int normalize, int fp16_mode, int N, int in_nc, int H, int W,
                                  const float* h_weight_oihw, const float* h_bias, int K, int act, const float* h_slope,
                                  void* d_slab, int64_t group_stride, int64_t lo, void* d_slab2, int64_t group_stride2, int64_t lo2, void* stream) {
+    return first_conv_impl(d_in, in_dtype, normalize, fp16_mode, N, in_nc, H, W, h_weight_oihw, h_bias, K, act, h_slope, nullptr, nullptr, d_slab, group_stride, lo, d_slab2, group_stride2, lo2, stream);
+}
+// The same launch with the per-input-channel map in front of the conv (FirstConvLaunch.in_map; SPAN's conv_1): operand = fp16(h_alpha[c] * v + h_shift[c]); either
+// vector NULL means 1 / 0, both NULL no map at all (innfer_first_conv's launch).
+extern "C" int innfer_first_conv_map(const void* d_in, int in_dtype, int normalize, int fp16_mode, int N, int in_nc, int H, int W,
+                                     const float* h_weight_oihw, const float* h_bias, int K, int act, const float* h_alpha, const float* h_shift,
+                                     void* d_slab, int64_t group_stride, void* stream) {
+    return first_conv_impl(d_in, in_dtype, normalize, fp16_mode, N, in_nc, H, W, h_weight_oihw, h_bias, K, act, nullptr, h_alpha, h_shift, d_slab, group_stride, 0, nullptr, 0, 0, stream);
+}
+static int first_conv_impl(const void* d_in, int in_dtype, int normalize, int fp16_mode, int N, int in_nc, int H, int W,
+                           const float* h_weight_oihw, const float* h_bias, int K, int act, const float* h_slope, const float* h_alpha, const float* h_shift,
+                           void* d_slab, int64_t group_stride, int64_t lo, void* d_slab2, int64_t group_stride2, int64_t lo2, void* stream) {
     if (!d_in || !h_weight_oihw || !d_slab) return set_error(INNFER_ERR_INVALID, "first_conv: null argument");
     if (in_dtype != INNFER_F16 && in_dtype != INNFER_F32 && in_dtype != INNFER_U8) return set_error(INNFER_ERR_INVALID, "first_conv: bad dtype");
     if ((K != 32 && K != 64) || in_nc < 1 || in_nc > 8 || (act != 0 && act != 1 && act != 2 && act != 8))
@@ -1473,11 +1630,15 @@ extern "C" int innfer_first_conv(const void* d_in, int in_dtype, int normalize, 
     std::vector<float> host((size_t)in_nc * 9 * K), bias(K, 0.f);
     first_conv_layout(h_weight_oihw, K, in_nc, host.data());
     if (h_bias) for (int k = 0; k < K; ++k) bias[k] = h_bias[k];
-    float *d_w = nullptr, *d_b = nullptr, *d_s = nullptr;
+    float *d_w = nullptr, *d_b = nullptr, *d_s = nullptr, *d_m = nullptr;
     int rc = INNFER_OK;
+    const bool mapped = h_alpha || h_shift;
+    float h_map[16];
+    for (int c = 0; c < in_nc; ++c) { h_map[c] = h_alpha ? h_alpha[c] : 1.f; h_map[in_nc + c] = h_shift ? h_shift[c] : 0.f; }
     if (hipMalloc((void**)&d_w, host.size() * sizeof(float)) != hipSuccess || hipMalloc((void**)&d_b, K * sizeof(float)) != hipSuccess ||
-        (act == 8 && hipMalloc((void**)&d_s, K * sizeof(float)) != hipSuccess))
+        (act == 8 && hipMalloc((void**)&d_s, K * sizeof(float)) != hipSuccess) || (mapped && hipMalloc((void**)&d_m, 2 * in_nc * sizeof(float)) != hipSuccess))
         rc = set_error(INNFER_ERR_NOMEM, "first_conv: out of device memory");
+    if (rc == INNFER_OK && d_m && hipMemcpy(d_m, h_map, 2 * in_nc * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) rc = set_error(INNFER_ERR_HIP, "first_conv: copying the input map failed");
     if (rc == INNFER_OK && (hipMemcpy(d_w, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
                             hipMemcpy(d_b, bias.data(), K * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
                             (d_s && hipMemcpy(d_s, h_slope, K * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)))
@@ -1486,11 +1647,11 @@ extern "C" int innfer_first_conv(const void* d_in, int in_dtype, int normalize, 
         FirstConvLaunch F{};
         F.in = d_in; F.in_f32 = in_dtype == INNFER_F32; F.Cin = in_nc; F.in_u8 = in_dtype == INNFER_U8; F.in_norm = normalize != 0; F.in_round16 = fp16_mode != 0;
         F.w = d_w; F.bias = d_b; F.out = (f16*)d_slab; F.out_gstride = group_stride; F.out2 = (f16*)d_slab2; F.out2_gstride = group_stride2;
-        F.K = K; F.N = N; F.H = H; F.W = W; F.act = act; F.out_lo = lo; F.out2_lo = lo2; F.slope = d_s;
+        F.K = K; F.N = N; F.H = H; F.W = W; F.act = act; F.out_lo = lo; F.out2_lo = lo2; F.slope = d_s; F.in_map = d_m;
         rc = first_conv_launch(F, (hipStream_t)stream);
         if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "first_conv: the launch failed");
     }
-    (void)hipFree(d_w); (void)hipFree(d_b); (void)hipFree(d_s);
+    (void)hipFree(d_w); (void)hipFree(d_b); (void)hipFree(d_s); (void)hipFree(d_m);
     return rc;
 }
 

@@ -5,6 +5,8 @@
 // tensor2np as the store.  Per output value: r = fp16(float(slab value) + float(fp16 base value)) -- one fp32 add, one rounding, what torch's half
 // `out += base` does -- then float(r), or the quantisation of the last convs' uint8 epilogue (conv3x3_planar.h) on r.
 //
+// Without a base (ShuffleAddLaunch.base == nullptr) the same pass is PixelShuffle(s) alone with the same three stores: SPAN's tail.
+//
 // Memory bound: 2 C s^2 bytes in and at most 4 C s^2 bytes out per LR pixel.  One thread owns one LR pixel: it reads the pixel's C s^2 <= 64 channels as
 // 16-byte pieces of the pixel's 64-byte run in each slab plane (consecutive lanes = consecutive pixels: a wave's loads cover whole lines) and writes, per
 // output channel and row phase, its s consecutive output values as one vector store where the alignment allows -- consecutive lanes write consecutive
@@ -60,7 +62,7 @@ __global__ __launch_bounds__(256) void shuffle_add_kernel(const SP p) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         b[c] = 0.f;
-        if (c >= p.C) continue;
+        if (c >= p.C || !p.base) continue;                       // (no base: PixelShuffle alone -- fp16(v + 0) is v)
         if (p.base_u8) {
             int sc = c;
             if (p.C % 3 == 0) sc = p.C - 1 - c; else if (p.C == 4 && c < 3) sc = 2 - c;
@@ -140,7 +142,7 @@ int launch_s(const SP& p, int out_mode, bool aligned, hipStream_t s) {
 }  // namespace
 
 int shuffle_add_launch(const ShuffleAddLaunch& L, hipStream_t s) {
-    if (!L.slab || !L.base || !L.out) return set_error(INNFER_ERR_INVALID, "shuffle_add: null argument");
+    if (!L.slab || !L.out) return set_error(INNFER_ERR_INVALID, "shuffle_add: null argument");
     if (L.s < 1 || L.s > 4 || L.C < 1 || L.C > 4 || L.out_mode < 0 || L.out_mode > 2)
         return set_error(INNFER_ERR_UNSUPPORTED, "shuffle_add: scale %d (1..4), %d channels (1..4), out_mode %d (0 fp16, 1 fp32, 2 uint8 image)", L.s, L.C, L.out_mode);
     if (L.N <= 0 || L.H <= 0 || L.W <= 0) return set_error(INNFER_ERR_INVALID, "shuffle_add: bad shape %dx%dx%d", L.N, L.H, L.W);

@@ -197,6 +197,8 @@ SIGNATURES = {
     "innfer_conv3x3_f16_grid": (C.c_int, [C.POINTER(ConvArgs), C.c_int, C.c_void_p]),
     "innfer_shuffle_add": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_int] * 5 + [C.c_void_p]),
     "innfer_compact_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 5),
+    "innfer_span_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "innfer_first_conv_map": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "innfer_net_set_conv_slope": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_conv1x1_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "innfer_pack_conv1x1": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

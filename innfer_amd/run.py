@@ -25,6 +25,8 @@ _SNIFF = (
     ('model.1.sub.0.res.0.weight', 'srgan'),
     ('body.0.rdb1.conv1.weight', 'realesrgan'),      # BasicSR's RRDBNet (with conv_first.weight): ahead of the new-arch probe, which shares conv_first
     ('body.0.weight', 'compact'),                    # BasicSR's SRVGGNetCompact: `body` is a ModuleList whose entry 0 is a conv (no body.0.rdb1.*)
+    ('conv_1.sk.weight', 'span'),                    # SPAN (with conv_cat.weight): a full checkpoint ..
+    ('conv_1.eval_conv.weight', 'span'),             # .. or a `deploy` one, which carries only the collapsed convs
     ('conv_first.weight', 'mesrgan'),
     ('model.0.weight', 'esrgan'),
     ('CFEM.0.weight', 'ppon'),
@@ -41,7 +43,7 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
     if 'n_averaged' in state_dict:
         state_dict = swa2normal(state_dict)
     for probe, arch in _SNIFF:
-        if probe in state_dict and (arch != 'realesrgan' or 'conv_first.weight' in state_dict):
+        if probe in state_dict and (arch != 'realesrgan' or 'conv_first.weight' in state_dict) and (arch != 'span' or 'conv_cat.weight' in state_dict):
             break
     else:
         raise Exception("Could not infer model parameters.")
@@ -52,6 +54,8 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
         return _infer_realesrgan(state_dict, in_nc)
     if arch == 'compact':
         return _infer_compact(state_dict)
+    if arch == 'span':
+        return _infer_span(state_dict)
     if arch == 'pan':
         return _infer_pan(state_dict, scale, in_nc, out_nc)
     if arch == 'ppon':
@@ -133,6 +137,27 @@ def _infer_compact(state_dict):
                                   "build SRVGGNetCompact(act_type=...) and load the state dict instead of arch='infer'")
     cfg = {'type': 'compact', 'in_nc': in_nc, 'out_nc': in_nc, 'nf': nf, 'nb': num_conv, 'scale': up, 'act_type': 'prelu'}
     return dict(arch='compact', scale=up, in_nc=in_nc, out_nc=in_nc, nf=nf, nb=num_conv, plus=False, state_dict=state_dict,
+                net_params=get_network_G_config(cfg, up))
+
+
+def _infer_span(state_dict):
+    """SPAN checkpoints: feature_channels from conv_cat, num_in_ch from conv_1, upscale = sqrt(upsampler.0's channels / num_in_ch); `no_norm` marks the
+    norm=False variant of the community training framework, absent `sk` keys a `deploy` checkpoint (only the collapsed eval_conv per Conv3XC)."""
+    import math
+    deploy = 'conv_1.sk.weight' not in state_dict
+    w1 = state_dict['conv_1.eval_conv.weight' if deploy else 'conv_1.sk.weight']
+    wc = state_dict['conv_cat.weight']
+    if 'upsampler.0.weight' not in state_dict or wc.dim() != 4 or int(wc.shape[1]) != 4 * int(wc.shape[0]):
+        raise Exception("Could not infer model parameters.")
+    f, in_nc = int(wc.shape[0]), int(w1.shape[1])
+    k_up = int(state_dict['upsampler.0.weight'].shape[0])
+    up = math.isqrt(k_up // in_nc) if k_up % in_nc == 0 else 0
+    if up * up * in_nc != k_up:
+        raise NotImplementedError(f'SPAN checkpoint: upsampler.0 has {k_up} channels, not num_in_ch ({in_nc}) times a square '
+                                  '(num_out_ch != num_in_ch is not built on the HIP path)')
+    norm = 'no_norm' not in state_dict
+    cfg = {'type': 'span', 'in_nc': in_nc, 'out_nc': in_nc, 'nf': f, 'scale': up, 'norm': norm, 'deploy': deploy}
+    return dict(arch='span', scale=up, in_nc=in_nc, out_nc=in_nc, nf=f, nb=6, plus=False, state_dict=state_dict,
                 net_params=get_network_G_config(cfg, up))
 
 

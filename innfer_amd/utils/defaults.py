@@ -123,6 +123,14 @@ def get_network_G_config(network_G, scale):
         cfg['num_conv'] = _pick(opts, 'nb', 16)
         cfg['upscale'] = _pick(opts, 'scale', scale)
         cfg['act_type'] = _pick(opts, 'act_type', 'prelu')
+    elif kind in ('span_net', 'span'):                     # SPAN (Swift Parameter-free Attention Network): the published constructor surface
+        cfg['type'] = 'span_net'
+        cfg['num_in_ch'] = _pick(opts, 'in_nc', 3)
+        cfg['num_out_ch'] = _pick(opts, 'out_nc', 3)
+        cfg['feature_channels'] = _pick(opts, 'nf', 48)
+        cfg['upscale'] = _pick(opts, 'scale', scale)
+        cfg['norm'] = _pick(opts, 'norm', True)
+        cfg['deploy'] = _pick(opts, 'deploy', False)
     else:
         raise NotImplementedError(f'Generator model [{kind:s}] not recognized')
 
