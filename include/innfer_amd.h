@@ -45,7 +45,7 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  innfer_version() returns the library's; a binding should compare. */
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): RealPLKSR -- innfer_plksr_create, innfer_net_set_group_norm, innfer_conv_args.act 11 (Mish), innfer_plk_conv (the partial large-kernel conv as a single launch), innfer_group_norm_skip / innfer_group_norm_skip_work_bytes (per-sample GroupNorm + skip over a 64-channel slab).  innfer_version() returns the library's; a binding should compare. */
 #define INNFER_ABI_VERSION 123
 int innfer_version(void);
 const char* innfer_last_error(void);
@@ -153,6 +153,31 @@ int innfer_compact_create(innfer_net_t* out, int in_nc, int out_nc, int nf, int 
  * (act 9, act 9, act 10 with res1 = the block's input), one SiLU pass (block_6's out1 goes to the concat raw), conv_2, conv_cat (1x1 over the concat slab: f0, b1, b5_2 and
  * conv_2's result were written into it at their channel offsets), upsampler.0, and the PixelShuffle store (innfer_shuffle_add without a base). */
 int innfer_span_create(innfer_net_t* out, int in_nc, int out_nc, int nf, int scale, int norm, float img_range, const float* h_mean);
+
+/* RealPLKSR (the community's large-kernel models; the reference has no such architecture):
+ *   DCCM(dim):       Sequential(Conv2d(dim, 2 dim, 3, 1, 1), Mish(), Conv2d(2 dim, dim, 3, 1, 1))
+ *   PLKConv2d(p, k): conv = Conv2d(p, p, k, 1, k // 2);  forward: x[:, :p] = conv(x[:, :p])  (the other channels pass through)
+ *   EA(dim):         f = Sequential(Conv2d(dim, dim, 3, 1, 1), Sigmoid());  forward: x * f(x)
+ *   PLKBlock:        channel_mixer = DCCM(dim); lk = PLKConv2d(int(dim * split_ratio), k); attn = EA(dim) or Identity (use_ea False);
+ *                    refine = Conv2d(dim, dim, 1); norm = GroupNorm(norm_groups, dim)       (eps 1e-5, biased variance, per sample over (dim / groups) x H x W)
+ *                    forward: norm(refine(attn(lk(channel_mixer(x))))) + x
+ *   RealPLKSR(in_ch 3, out_ch 3, dim 64, n_blocks 28, upscaling_factor 4, kernel_size 17, split_ratio 0.25, use_ea True, norm_groups 4):
+ *                    feats = Sequential(Conv2d(in_ch, dim, 3, 1, 1), n_blocks x PLKBlock, Dropout2d (no parameters), Conv2d(dim, out_ch s^2, 3, 1, 1))
+ *                    forward: PixelShuffle(s)(feats(x) + repeat_interleave(x, s^2, dim=1))
+ *   Mish(f) = f * tanh(softplus(f)) = f * (n^2 + 2 n) / (n^2 + 2 n + 2),  n = exp(f)
+ * on the engine of innfer_net_*: innfer_net_conv_info reports the convs under the keys feats.0, then per block i = 1 .. n_blocks feats.<i>.channel_mixer.0a and
+ * .channel_mixer.0b ([64, 64, 3, 3] each: output channels 0 .. 63 and 64 .. 127 of channel_mixer.0, one launch each), .channel_mixer.2 ([64, 128, 3, 3]), .lk.conv
+ * ([16, 16, k, k]), .attn.f.0 (use_ea only), .refine ([64, 64, 1, 1]), and feats.<n_blocks + 2> (K = out_ch s^2); innfer_net_set_conv loads them,
+ * innfer_net_set_group_norm the GroupNorm behind every refine; innfer_net_forward[_timed] / innfer_net_workspace_bytes / innfer_net_flops / innfer_net_set_u8_io work as
+ * for SRVGGNetCompact.  dim 64 (split_ratio 0.25: the large kernel on 16 channels), kernel_size odd 3 .. 17, in_ch == out_ch in 1 .. 4, scale 1 .. 4, norm_groups in
+ * {1, 2, 4, 8}; anything else is INNFER_ERR_UNSUPPORTED.  fp16 mode only.
+ * A forward is 9 n_blocks + 3 launches (8 per block without EA): feats.0; per block two Mish launches (act 11), channel_mixer.2, the large-kernel conv, the EA gate (act 5
+ * with res1 = its own input), refine, the GroupNorm statistics, their merge, and t = fp16(alpha[n, c] u + shift[n, c] + x); the last conv; innfer_shuffle_add with the
+ * input as base (PixelShuffle(s)(y + repeat_interleave(x, s^2)) = PixelShuffle(s)(y) + nearest_upsample(x, s)).
+ * GroupNorm statistics are PER SAMPLE and those of whatever the network is given: a tiling front end (the 200-px chop) normalises per tile. */
+int innfer_plksr_create(innfer_net_t* out, int in_nc, int out_nc, int dim, int n_blocks, int scale, int kernel_size, int use_ea, int norm_groups);
+/* gamma / beta (64 host floats each, NULL = 1 / 0) of the GroupNorm behind conv `idx` (a RealPLKSR's refine convs; other convs refuse).  Load time, synchronous. */
+int innfer_net_set_group_norm(innfer_net_t net, int idx, const float* h_gamma, const float* h_beta);
 /* The activation behind conv `idx` as K host floats: y = x >= 0 ? x : h_slope[c] * x -- nn.PReLU(num_parameters = K).weight, or the constant 0 (ReLU) / 0.1
  * (LeakyReLU(0.1)).  Load time, synchronous.  Every conv of an SRVGGNetCompact except the last needs one before the first forward; other convs refuse it. */
 int innfer_net_set_conv_slope(innfer_net_t net, int idx, const float* h_slope);
@@ -583,6 +608,22 @@ int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream);
  * Built like act 8: epilogues of the plain 3x3 slab convs with K = 64 (plane_rows 0 / 1) and K = 32, batches, row ranges and out_ch_off included; every other form (split,
  * d_stats_part, the self gate, conv1x1, out_planar, the stride-2 / phase / column / dilated forms, upsample2x, reflect_pad, d_res2, act 9 with d_res1) answers
  * INNFER_ERR_UNSUPPORTED and act 10 without d_res1 INNFER_ERR_INVALID; nothing is launched. */
+/* a->act = 11 (Mish): f * tanh(softplus(f)) as f * w / (w + 2), w = n (n + 2), n = e^min(f, 20) -- fp32 on the accumulator + bias, one hardware exponential and one
+ * reciprocal per value, f itself for large f, one fp16 rounding at the store.  An epilogue of the plain 3x3 slab conv with K = 64 (plane_rows 0 / 1), batches, row ranges
+ * and out_ch_off included; every other form (K = 32, split, d_stats_part, the self gate, conv1x1, out_planar, the stride-2 / phase / column / dilated forms, residuals,
+ * upsample2x, reflect_pad) answers INNFER_ERR_UNSUPPORTED; nothing is launched. */
+/* (123, additive) RealPLKSR's partial large-kernel conv as a single launch (for tests; csrc/plk_conv.hip): d_in / d_out point at channel 0 of two DIFFERENT 32-channel
+ * slab groups of N * H * W pixels; out channels 0 .. 15 = the k x k zero-padded conv (h_weight_oihw [16][16][k][k], h_bias 16 floats or NULL; k odd, 3 .. 17) of in channels
+ * 0 .. 15 -- fp16 operands, fp32 accumulation, one rounding --, out channels 16 .. 31 = in channels 16 .. 31 bit for bit.  Overlapping groups are INNFER_ERR_INVALID
+ * (other workgroups still read the halo); nothing is launched then.  Uploads, launches, waits. */
+int innfer_plk_conv(const void* d_in, void* d_out, int N, int H, int W, int k, const float* h_weight_oihw, const float* h_bias, void* stream);
+/* (123, additive) GroupNorm(groups, 64) per sample + skip over 64-channel slabs as the network runs it (for tests; csrc/group_norm.hip: statistics, merge, apply):
+ * d_out = fp16(alpha[n][c] * u + shift[n][c] + skip), alpha = h_gamma[c] / sqrt(var + eps), shift = h_beta[c] - mean alpha, mean / biased variance over the
+ * (64 / groups) x HW values of image n's group.  *_gs: group strides in elements; d_out may be d_skip.  groups in {1, 2, 4, 8}.  d_work: at least
+ * innfer_group_norm_skip_work_bytes(N, HW) bytes.  Uploads gamma / beta, launches, waits. */
+size_t innfer_group_norm_skip_work_bytes(int N, int64_t HW);
+int innfer_group_norm_skip(const void* d_u, int64_t u_gs, const void* d_skip, int64_t skip_gs, void* d_out, int64_t out_gs, int N, int64_t HW, int groups,
+                           const float* h_gamma, const float* h_beta, float eps, void* d_work, size_t work_bytes, void* stream);
 /* The same launch with the per-channel slope activation: a->act = 8 computes f >= 0 ? f : d_slope[c] * f (nn.PReLU; d_slope: device floats padded like d_bias and
  * indexed by the same channel, whatever plane_rows / out_ch_off).  Built as the epilogue of the plain 3x3 slab convs with K = 64 (plane_rows 0 / 1) and K = 32, row
  * ranges and batches included; every other form (split, d_stats_part, the self gate, conv1x1, out_planar, the stride-2 / phase / column / dilated forms, residuals,

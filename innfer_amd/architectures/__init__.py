@@ -31,6 +31,8 @@ def get_network(opt_net):
         from .SRVGG_arch import SRVGGNetCompact as net
     elif kind == 'span_net':
         from .SPAN_arch import SPAN as net
+    elif kind in ('realplksr', 'realplksr_net'):
+        from .PLKSR_arch import RealPLKSR as net
     else:
         raise NotImplementedError('Model [{:s}] not recognized'.format(kind))
     return net(**opt_net)

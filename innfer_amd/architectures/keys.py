@@ -175,6 +175,29 @@ def span_shapes(num_in_ch=3, num_out_ch=3, feature_channels=48, upscale=4, norm=
     return s
 
 
+def realplksr_shapes(in_ch=3, out_ch=3, dim=64, n_blocks=28, upscaling_factor=4, kernel_size=17, split_ratio=0.25, use_ea=True):
+    """State-dict key -> shape of RealPLKSR: feats.0 = Conv2d(in_ch, dim, 3); feats.<i> (i = 1 .. n_blocks) a PLKBlock -- channel_mixer.0 = Conv2d(dim, 2 dim, 3),
+    channel_mixer.2 = Conv2d(2 dim, dim, 3), lk.conv = Conv2d(p, p, k) with p = int(dim split_ratio), attn.f.0 = Conv2d(dim, dim, 3) (only with use_ea),
+    refine = Conv2d(dim, dim, 1), norm = GroupNorm(norm_groups, dim) --; feats.<n_blocks + 1> is a Dropout2d (no keys); feats.<n_blocks + 2> =
+    Conv2d(dim, out_ch upscaling_factor^2, 3).  norm_groups leaves no trace in the keys."""
+    p = int(dim * split_ratio)
+    s = {}
+
+    def conv(k, co, ci, ks):
+        s[k + '.weight'], s[k + '.bias'] = (co, ci, ks, ks), (co,)
+    conv('feats.0', dim, in_ch, 3)
+    for i in range(1, n_blocks + 1):
+        conv(f'feats.{i}.channel_mixer.0', 2 * dim, dim, 3)
+        conv(f'feats.{i}.channel_mixer.2', dim, 2 * dim, 3)
+        conv(f'feats.{i}.lk.conv', p, p, kernel_size)
+        if use_ea:
+            conv(f'feats.{i}.attn.f.0', dim, dim, 3)
+        conv(f'feats.{i}.refine', dim, dim, 1)
+        s[f'feats.{i}.norm.weight'], s[f'feats.{i}.norm.bias'] = (dim,), (dim,)
+    conv(f'feats.{n_blocks + 2}', out_ch * upscaling_factor ** 2, dim, 3)
+    return s
+
+
 def srresnet_layout(nb, norm=False, mode='CNA'):
     """Positions of a ResNetBlock's / LR_conv's layers inside the flattened Sequentials (SRResNet_arch.py:23-27,68-86; block.py:242-254,
     B.sequential flattens nested Sequentials): {engine key -> (conv key, BatchNorm in front of the conv or None, BatchNorm behind it or None)}.

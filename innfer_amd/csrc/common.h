@@ -25,6 +25,9 @@ int set_error(int code, const char* fmt, ...);
 // Activations of the fp16 engines' epilogues on the hardware exponential / reciprocal (v_exp_f32, v_rcp_f32: 1 ulp each): tanhf / expf / the IEEE division are 30 .. 50
 // instructions per value, these 4 .. 6 -- the results are rounded to fp16 (or are a final fp32 image within the engines' 1e-2 bounds).  The fp32 mode (f32ops.hip) keeps libm.
 __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
+// Mish(f) = f * tanh(softplus(f)) = f * w / (w + 2) with w = n (n + 2), n = e^f: no cancellation on either side of zero, one exponential and one reciprocal.  The exponent is
+// capped at 20 (w = e^40 stays finite; w / (w + 2) is already 1 in fp32 from f = 9 on), so a large f returns f itself; a NaN stays a NaN.
+__device__ __forceinline__ float fast_mish(float x) { const float n = __expf(x > 20.0f ? 20.0f : x); const float w = n * (n + 2.0f); return x * (w * __builtin_amdgcn_rcpf(w + 2.0f)); }
 __device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }      // (+-inf -> +-1; absolute error ~1e-7)
 
 // Generic launch timer (innfer_timer_start / innfer_timer_stop, net.hip): while a collection is open on the calling thread every instrumented launch is
@@ -103,7 +106,7 @@ struct ConvLaunch {
     int out_coff;                                 // channel offset inside that group (0 or 16)
     int K;                                        // valid output channels
     int N, H, W;                                  // conv (output) size
-    int act; int up;                              // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 8 per-channel slope (`slope`) / 3 tanh (OUT_NCHW only) / 4, 5 res1 * sigmoid(conv) with / without LeakyReLU (slab) / 6 sigmoid (OUT_NCHW only) / 7 pair gate: 64 rows -> 32 outputs, row 16 lg + r (r < 8) times sigmoid(row 16 lg + r + 8) (slab, PAN's PAConv) / 9 SiLU, f * sigmoid(f) / 10 SPAN's gate, (f + res1) * (sigmoid(f) - 0.5) (s1 unused, no res2) -- 9 and 10: epilogues of the plain 3x3 slab convs of 64 (rowp 0 / 1) and 32 outputs (conv3x3_pc SPAN), every other form refuses them; up: input read through nearest 2x
+    int act; int up;                              // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 8 per-channel slope (`slope`) / 3 tanh (OUT_NCHW only) / 4, 5 res1 * sigmoid(conv) with / without LeakyReLU (slab) / 6 sigmoid (OUT_NCHW only) / 7 pair gate: 64 rows -> 32 outputs, row 16 lg + r (r < 8) times sigmoid(row 16 lg + r + 8) (slab, PAN's PAConv) / 9 SiLU, f * sigmoid(f) / 10 SPAN's gate, (f + res1) * (sigmoid(f) - 0.5) (s1 unused, no res2) / 11 Mish, f * tanh(softplus(f)): epilogue of the plain 3x3 slab conv of 64 outputs (rowp 0 / 1; conv3x3_pc MISH) -- 9 and 10: epilogues of the plain 3x3 slab convs of 64 (rowp 0 / 1) and 32 outputs (conv3x3_pc SPAN), every other form refuses them; up: input read through nearest 2x
     const f16* res1; long res1_gstride; float s1;
     const f16* res2; long res2_gstride; float s2;
     int y0, y1;                                   // output rows [y0,y1)
@@ -225,6 +228,27 @@ struct ShuffleAddLaunch {
     int C, s, N, H, W;                            // C 1..4, s 1..4; H x W: the LR grid
 };
 int shuffle_add_launch(const ShuffleAddLaunch& L, hipStream_t s);
+
+// ---- RealPLKSR's partial large-kernel conv (plk_conv.hip) ----
+struct PlkLaunch {
+    const f16* in; f16* out;                      // channel 0 of the input / output slab GROUP (N * H * W * 32 elements each; they must not overlap): out channels 0 .. 15 =
+                                                  // the k x k zero-padded conv of in channels 0 .. 15 (+ bias, one fp16 rounding), out channels 16 .. 31 = in channels 16 .. 31
+    const f16* wpk; const float* bias;            // plk_pack panel (device); 16 floats
+    int k;                                        // odd, 3 .. 17
+    int N, H, W;
+};
+size_t plk_packed_bytes(int k);
+void plk_pack(const float* w_oihw, int k, void* packed);      // host; w [16][16][k][k]
+int plk_conv_launch(const PlkLaunch& L, hipStream_t s);
+
+// ---- GroupNorm over a 64-channel slab, per sample, + skip (group_norm.hip): RealPLKSR's `norm(refine(..)) + x` ----
+// Three launches: gn_stats (records of (count, mean, M2) per image, 1024-pixel segment and channel octet), gn_finalize (the records of a group merged in a fixed order with
+// Chan's update -> alpha[n][c] = gamma[c] / sqrt(var + eps), shift[n][c] = beta[c] - mean alpha), gn_apply: out = fp16(fma(alpha, u, shift) + skip).
+// Statistics are PER SAMPLE: a batch (the chop path's tiles, -batch) normalises every image by its own mean and variance.  groups in {1, 2, 4, 8} (whole octets).
+size_t gn_work_floats(int N, long HW);            // floats of `work`: the records, then alpha[N][64] and shift[N][64]
+int gn_stats_launch(const f16* u, long u_gs, int N, long HW, float* work, hipStream_t s);
+int gn_finalize_launch(int N, long HW, int groups, const float* gamma, const float* beta, float eps, float* work, hipStream_t s);
+int gn_apply_launch(const f16* u, long u_gs, const f16* skip, long skip_gs, f16* out, long out_gs, int N, long HW, const float* work, hipStream_t s);
 
 // ---- layout / tiles / blend / pre-post (tiles.hip) ---------------------------
 int nchw_to_slab(const void* src, int src_f32, f16* slab, long gstride, int ch_off, int N, int C, int H, int W, hipStream_t s);

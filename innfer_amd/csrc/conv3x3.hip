@@ -478,7 +478,7 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     constexpr bool UP4 = (TMF & PC_UP4) != 0;
     // + PC_ROWP: the plane row order of the 64-channel groups (see toff_slab): plain 3x3 slab convs (canvas, RLDS, FUSE forms included) and the one-pass up-conv
     constexpr bool ROWP = (TMF & PC_ROWP) != 0;
-    static_assert(!ROWP || (((RPW == 2 && NT == 4) || GRID2) && OUTMODE == OUT_SLAB && TM == TAPS_3X3 && (TMF & ~(TAPS_3X3 | PC_FUSE | PC_RLDS | PC_UP4 | PC_ROWP | PC_PSH | PC_PRELU | PC_GRID2 | PC_SPAN)) == 0 && !S9 && !POLY), "plane row order: the 64-channel slab kernels");
+    static_assert(!ROWP || (((RPW == 2 && NT == 4) || GRID2) && OUTMODE == OUT_SLAB && TM == TAPS_3X3 && (TMF & ~(TAPS_3X3 | PC_FUSE | PC_RLDS | PC_UP4 | PC_ROWP | PC_PSH | PC_PRELU | PC_GRID2 | PC_SPAN | PC_MISH)) == 0 && !S9 && !POLY), "plane row order: the 64-channel slab kernels");
     // + PC_PSH: nn.PixelShuffle(2) as the store of a conv nf -> 4 nf (pixelshuffle_block, block.py:333-346; SRResNet's up stages, RRDBNet(upsample_mode=
     // 'pixelshuffle')) on THIS kernel -- until round 4 those launches ran on the two-workgroup kernel of round 1 (0.30 of the MFMA peak, a third of an SRResNet frame).
     // The panels are phase-major (conv_pack_shuffle2) in the plane row order, so a channel group is one output phase of 64 channels and the epilogue is the
@@ -499,6 +499,10 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     // the one-residual epilogue of the plain kernels.  fp32 on the accumulator, one rounding at the store.  Instantiations of their own: the other kernels' code does not change.
     constexpr bool SPAN = (TMF & PC_SPAN) != 0;
     static_assert(!SPAN || (OUTMODE == OUT_SLAB && (NT == 4 || NT == 2) && NSI == 2 && (TMF & ~(TAPS_3X3 | PC_ROWP | PC_SPAN)) == 0 && TM == TAPS_3X3 && !S9 && !POLY && !CV), "SiLU / SPAN gate epilogue: the plain 64- / 32-output slab kernels");
+    // + PC_MISH: ConvLaunch.act 11 (Mish: f * tanh(softplus(f)), the activation inside RealPLKSR's DCCM) as the slab epilogue of the plain nine-tap 64-output kernel in
+    // either row order -- fp32 on the accumulator, one rounding at the store.  Instantiations of their own: the other kernels' code does not change.
+    constexpr bool MISH = (TMF & PC_MISH) != 0;
+    static_assert(!MISH || (OUTMODE == OUT_SLAB && NT == 4 && NSI == 2 && (TMF & ~(TAPS_3X3 | PC_ROWP | PC_MISH)) == 0 && TM == TAPS_3X3 && !S9 && !POLY && !CV), "Mish epilogue: the plain 64-output slab kernel");
     static_assert(!FUSE || (RPW == 2 && (NT == 4 || (NT == 2 && !ROWP)) && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_FUSE) == TAPS_3X3 && !S9 && !POLY && !CV), "the fused last conv: the plain 64-channel instantiation (and the 32-channel one on 16-row tiles)");
     using L = PcLayout<RPW, NT, NSI, TMF>;                  // the LDS layout, shared with launch_pc
     constexpr int TH = L::TH;
@@ -1052,7 +1056,7 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
     if (L.act == 7 && (L.out_mode != OUT_SLAB || conv_nt_for(L.K) != 4 || L.K % 64 || L.res1 || L.res2 || L.conv1x1 || L.dilation > 1 || L.dilation_groups ||
                        L.deconv_phases || L.stride2 || L.conv7v || L.stats_part))
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the pair gate is an epilogue of the plain 64-row slab conv (32 gated outputs per 64 rows)");
-    if (L.act < 0 || L.act > 10 || (L.phase_c > 0 && (L.K % L.phase_c || L.K / L.phase_c != 4)))
+    if (L.act < 0 || L.act > 11 || (L.phase_c > 0 && (L.K % L.phase_c || L.K / L.phase_c != 4)))
         return set_error(INNFER_ERR_INVALID, "conv3x3: act=%d phase_c=%d K=%d", L.act, L.phase_c, L.K);
     k.act = L.act;
     k.res1 = L.res1; k.res1_gstride = L.res1_gstride; k.s1 = L.s1;
@@ -1096,6 +1100,14 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
                                                      "statistics / gate / 1x1 / planar / phase / stride-2 / dilated / fused-last forms, no other residual, upsampling or reflection padding");
         if (nt == 2) return launch_pc<3, 2, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_SPAN>(k, L.N, s);
         return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP | PC_SPAN>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_SPAN>(k, L.N, s);
+    }
+    if (L.act == 11) {        // Mish: conv3x3_pc<.., TMF | PC_MISH>, the plain nine-tap slab kernel of 64 outputs in either row order
+        if (L.out_mode != OUT_SLAB || nt != 4 || L.K != 64 || L.split || L.stats_part || L.gate_w || L.conv1x1 || L.prefix_lrelu || L.deconv_phases || L.stride2 ||
+            L.conv7v || L.conv7 || L.fuse_w || L.dilation > 1 || L.dilation_groups || L.in_relu || L.res1 || L.res2 || L.up || L.reflect || L.phase_c || L.outm || L.out_u8 ||
+            (L.rowp && (L.rowp != 1 || (L.out_coff & 31))))
+            return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: act 11 (Mish) is built as the epilogue of the plain 3x3 slab conv of 64 outputs -- not the 32-output / split / "
+                                                     "statistics / gate / 1x1 / planar / phase / stride-2 / dilated / fused-last forms, no residual, upsampling or reflection padding");
+        return L.rowp ? launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_ROWP | PC_MISH>(k, L.N, s) : launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_MISH>(k, L.N, s);
     }
     if (L.rowp && !(L.rowp == 2 && L.out_mode == OUT_SHUFFLE2) && (nt != 4 || L.out_mode != OUT_SLAB || L.split || L.stats_part || L.stride2 || L.conv1x1 || L.conv7 || L.conv7v || L.prefix_lrelu ||
                    L.gate_w || L.act > 2 || L.dilation > 1 || L.dilation_groups || (L.out_coff & 31)))

@@ -62,6 +62,9 @@
                 // act 10 (the gate that ends a SPAB: res1 = the block's input, loaded hoisted) / act 9 (SiLU): plain slab store
                 if (p.act == 10) epilogue_slab<RPW, NT, 10, true, false, true, false, false, false, false, ROWP, false>(p, acc, n, ty0, tx0, cw, li, cbase, dcur);
                 else epilogue_slab<RPW, NT, 9, false, false, true, false, false, false, false, ROWP, false>(p, acc, n, ty0, tx0, cw, li, cbase, dcur);
+            } else if constexpr (MISH) {
+                // act 11 (Mish, RealPLKSR's DCCM): plain slab store, no residual
+                epilogue_slab<RPW, NT, 11, false, false, true, false, false, false, false, ROWP, false>(p, acc, n, ty0, tx0, cw, li, cbase, dcur);
             } else if constexpr (OUTMODE == OUT_SLAB) {
             if constexpr (STATS) {
                 const int lid = run_start + (p.rev ? run_len - 1 - (jt - slots) : (jt - slots));         // (jt was advanced above)

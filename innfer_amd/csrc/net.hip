@@ -107,10 +107,16 @@ struct ConvSlot {
     bool map_ok = false;         // slot may carry an input map (first conv of an SRResNet block, LR_conv)
     float* d_map = nullptr;      // alpha[C] then shift[C]
     int map_act = 0;
+    // RealPLKSR (kind 4)
+    bool plk = false;            // lk.conv: [16, 16, k, k] on csrc/plk_conv.hip (ksize = k; d_w: plk_pack panel, d_b: 16 floats)
+    bool lane_rows = false;      // attn.f.0: a 64-output conv whose epilogue is the gate act 5 -- a form of the lane-contiguous panels only, so d_w is never packed in the plane row order
+    bool gn_ok = false;          // refine: GroupNorm(groups, 64) follows it -- d_gn: gamma[64] then beta[64] (innfer_net_set_group_norm)
+    float* d_gn = nullptr;
 };
 
 struct innfer_net {
-    int kind = 0;                // 0 rrdbnet, 1 srresnet, 2 BasicSR's SRVGGNetCompact (innfer_compact_create; compact_forward), 3 SPAN (innfer_span_create; span_forward)
+    int kind = 0;                // 0 rrdbnet, 1 srresnet, 2 BasicSR's SRVGGNetCompact (innfer_compact_create; compact_forward), 3 SPAN (innfer_span_create; span_forward), 4 RealPLKSR (innfer_plksr_create; plksr_forward)
+    int plk_k = 17, plk_ea = 1, plk_groups = 4;      // RealPLKSR: kernel_size, use_ea, norm_groups
     bool span_norm = false;      // SPAN(norm=True): conv_1 reads (x - mean) * img_range through FirstConvLaunch.in_map (convs[0].d_map: alpha[in_nc] then shift[in_nc])
     int in_nc = 3, out_nc = 3, nf = 64, nb = 23, gc = 32, scale = 4, n_up = 2;
     int final_act = 0;           // `finalact` of the reference constructors: activation after the last conv (ConvLaunch.act codes)
@@ -303,6 +309,53 @@ extern "C" int innfer_span_create(innfer_net_t* out, int in_nc, int out_nc, int 
     return INNFER_OK;
 }
 
+// RealPLKSR (the reference has no such architecture -- include/innfer_amd.h carries the definition): per block DCCM (3x3 64 -> 128 with Mish as two 64-output launches
+// of act 11, 3x3 128 -> 64), the partial large-kernel conv (plk_conv.hip), the EA gate (3x3 64 -> 64, act 5 on its own input), refine (1x1) and GroupNorm + skip
+// (group_norm.hip); the tail is SRVGGNetCompact's.  fp16 engine only.
+extern "C" int innfer_plksr_create(innfer_net_t* out, int in_nc, int out_nc, int dim, int n_blocks, int scale, int kernel_size, int use_ea, int norm_groups) {
+    if (!out) return set_error(INNFER_ERR_INVALID, "plksr_create: null out");
+    if (dim != 64) return set_error(INNFER_ERR_UNSUPPORTED, "plksr_create: dim=%d (built: 64, with the large kernel on its first 16 channels)", dim);
+    if (in_nc < 1 || in_nc > 4 || in_nc != out_nc)
+        return set_error(INNFER_ERR_UNSUPPORTED, "plksr_create: in_nc=%d out_nc=%d (built: in_nc == out_nc in 1..4 -- the network adds its repeated input to its result)", in_nc, out_nc);
+    if (n_blocks < 1 || n_blocks > 4096) return set_error(INNFER_ERR_UNSUPPORTED, "plksr_create: n_blocks=%d", n_blocks);
+    if (scale < 1 || scale > 4) return set_error(INNFER_ERR_UNSUPPORTED, "plksr_create: scale %d (built: 1, 2, 3, 4)", scale);
+    if (kernel_size < 3 || kernel_size > 17 || !(kernel_size & 1)) return set_error(INNFER_ERR_UNSUPPORTED, "plksr_create: kernel_size %d (built: odd, 3 .. 17)", kernel_size);
+    if (norm_groups != 1 && norm_groups != 2 && norm_groups != 4 && norm_groups != 8)
+        return set_error(INNFER_ERR_UNSUPPORTED, "plksr_create: norm_groups %d (built: 1, 2, 4, 8)", norm_groups);
+    innfer_net* net = new innfer_net();
+    net->kind = 4; net->in_nc = in_nc; net->out_nc = out_nc; net->nf = dim; net->nb = n_blocks;
+    net->gc = 0; net->scale = scale; net->n_up = 0;
+    net->plk_k = kernel_size; net->plk_ea = use_ea != 0; net->plk_groups = norm_groups;
+    add_conv(net, "feats.0", dim, in_nc, true);
+    for (int b = 1; b <= n_blocks; ++b) {
+        const std::string p = "feats." + std::to_string(b) + ".";
+        add_conv(net, p + "channel_mixer.0a", dim, dim);              // output channels 0 .. 63 and 64 .. 127 of channel_mixer.0: one 64-output launch each
+        add_conv(net, p + "channel_mixer.0b", dim, dim);
+        add_conv(net, p + "channel_mixer.2", dim, 2 * dim);
+        add_conv(net, p + "lk.conv", 16, 16, false, kernel_size);
+        net->convs.back().plk = true;
+        if (use_ea) { add_conv(net, p + "attn.f.0", dim, dim); net->convs.back().lane_rows = true; }
+        add_conv(net, p + "refine", dim, dim, false, 1);
+        net->convs.back().gn_ok = true;
+    }
+    add_conv(net, "feats." + std::to_string(n_blocks + 2), out_nc * scale * scale, dim);
+    net->convs.back().Kp = out_nc * scale * scale <= 32 ? 32 : 64;
+    *out = net;
+    return INNFER_OK;
+}
+
+// The affine parameters of the GroupNorm behind conv `idx` (RealPLKSR's refine): 64 host floats each, NULL = 1 / 0.  Load time, synchronous.
+extern "C" int innfer_net_set_group_norm(innfer_net_t net, int idx, const float* h_gamma, const float* h_beta) {
+    if (!net || idx < 0 || idx >= (int)net->convs.size()) return set_error(INNFER_ERR_INVALID, "set_group_norm: bad arguments");
+    ConvSlot& c = net->convs[idx];
+    if (!c.gn_ok) return set_error(INNFER_ERR_UNSUPPORTED, "set_group_norm: no GroupNorm follows '%s' (built: the refine convs of a RealPLKSR)", c.key.c_str());
+    float h[128];
+    for (int i = 0; i < 64; ++i) { h[i] = h_gamma ? h_gamma[i] : 1.f; h[64 + i] = h_beta ? h_beta[i] : 0.f; }
+    if (!c.d_gn) INNFER_HIP(hipMalloc((void**)&c.d_gn, sizeof h));
+    INNFER_HIP(hipMemcpy(c.d_gn, h, sizeof h, hipMemcpyHostToDevice));
+    return INNFER_OK;
+}
+
 // The activation behind conv `idx` of an SRVGGNetCompact as K per-channel slopes (host floats): y = x >= 0 ? x : slope[c] * x -- nn.PReLU's weight, or the
 // constant 0 (ReLU) / 0.1 (LeakyReLU(0.1)).  Load time, synchronous, like innfer_net_set_conv.
 extern "C" int innfer_net_set_conv_slope(innfer_net_t net, int idx, const float* h_slope) {
@@ -338,6 +391,7 @@ extern "C" void innfer_net_destroy(innfer_net_t net) {
         if (c.d_b4) (void)hipFree(c.d_b4);
         if (c.d_map) (void)hipFree(c.d_map);
         if (c.d_slope) (void)hipFree(c.d_slope);
+        if (c.d_gn) (void)hipFree(c.d_gn);
     }
     delete net;
 }
@@ -391,6 +445,10 @@ extern "C" int innfer_net_set_conv(innfer_net_t net, int idx, const float* w, co
         host.resize((size_t)c.C * 9 * c.K * sizeof(float));
         first_conv_layout(w, c.K, c.C, (float*)host.data());
         bias_n = c.K;
+    } else if (c.plk) {              // RealPLKSR's lk.conv [16, 16, k, k]: the streamed [step][lane][8] panel of plk_conv.hip
+        host.resize(plk_packed_bytes(c.ksize));
+        plk_pack(w, c.ksize, host.data());
+        bias_n = 16;
     } else {
         if (c.ksize == 1) {          // [K,C,1,1]: the one-tap panel of the kernel's 1x1 instantiation
             host.resize(conv_packed_bytes_taps(c.K, c.C, TAPS_1X1));
@@ -403,7 +461,7 @@ extern "C" int innfer_net_set_conv(innfer_net_t net, int idx, const float* w, co
             conv_pack(wp.data(), c.Kp, c.C, host.data(), c.rowp);
         } else {
             host.resize(conv_packed_bytes(c.K, c.C));
-            c.rowp = c.K == 64;
+            c.rowp = c.K == 64 && !c.lane_rows;
             conv_pack(w, c.K, c.C, host.data(), c.rowp);
         }
         const int per = 16 * conv_nt_for(c.Kp ? c.Kp : c.K);
@@ -480,6 +538,7 @@ extern "C" int innfer_net_set_precision(innfer_net_t net, int fp32) {
     if (!net || (fp32 != 0 && fp32 != 1)) return set_error(INNFER_ERR_INVALID, "set_precision: 0 (fp16 arithmetic) or 1 (fp32-accurate)");
     if (fp32 && net->kind == 2) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SRVGGNetCompact is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 3) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SPAN is built for the fp16 mode only (no fp32-accurate engine)");
+    if (fp32 && net->kind == 4) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: RealPLKSR is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32) {
         // The (wl | wh | wh) panels of every loaded conv are built HERE -- a load-time call, with its hipMalloc and synchronous copies -- never inside
         // innfer_net_forward (stream capture, concurrent callers).  Idempotent: a conv that already has its panels is skipped; innfer_net_set_conv
@@ -605,6 +664,18 @@ static Carve carve(const innfer_net* net, int N, int H, int W) {
         c.fea = off; off += al(px * 4 * net->nf * 2);
         for (int i = 0; i < 3; ++i) { c.slab[i] = off; off += al(px * net->nf * 2); }
         c.hr = off; off += al(px * net->convs.back().Kp * 2);
+        c.total = off;
+        return c;
+    }
+    if (net->kind == 4) {        // RealPLKSR: x (64 channels; norm + skip rewrites it in place), the Mish slab (128 channels; its first half later holds the gated tensor,
+                                 // its second refine's result), three groups [U0 | T0 | U1] around the large-kernel conv, the last conv's slab, the GroupNorm records and affine
+        size_t off = 0;
+        c.slab_w = net->nf;
+        c.fea = off; off += al(px * 64 * 2);
+        c.slab[0] = off; off += al(px * 128 * 2);
+        c.slab[1] = off; off += al(px * 96 * 2);
+        c.hr = off; off += al(px * net->convs.back().Kp * 2);
+        c.tmp = off; off += al(gn_work_floats(N, (long)H * W) * sizeof(float));
         c.total = off;
         return c;
     }
@@ -1012,6 +1083,86 @@ int span_forward(innfer_net* net, const void* d_in, int in_dtype, void* d_out, i
     return timed_end(s, 0.0, px * (k * 2.0 + k * (T.out_mode == 2 ? 1.0 : T.out_mode == 1 ? 4.0 : 2.0)), 6000);
 }
 
+// RealPLKSR (kind 4).  Per block, on x (two groups): channel_mixer.0 as two act-11 launches -> M (four groups); channel_mixer.2 -> groups 0 and 2 of the three-group
+// buffer [U0 | T0 | U1] (output group stride 2 G); plk_conv U0 -> T0 (its channels 16 .. 31 copied), so [T0 | U1] at stride G is lk's result; the EA gate (act 5 with
+// res1 = its own input) -> M[0, 1]; refine (1x1) -> M[2, 3]; GroupNorm statistics, finalize, and x = fp16(alpha u + shift + x) in place.  9 launches (8 without EA);
+// the tail is SRVGGNetCompact's: the last conv, then shuffle_add with the input as base.  9 n_blocks + 3 launches at most.
+static int plksr_pass(hipStream_t s, const char* what, double flops, double bytes, int kind, const std::function<int()>& launch) {
+    if (int rc = timed_begin(s)) return rc;
+    if (int rc = launch()) return rc;
+    if (int rc = debug_after(what, s)) return rc;
+    return timed_end(s, flops, bytes, kind);
+}
+
+int plksr_forward(innfer_net* net, const void* d_in, int in_dtype, void* d_out, int out_dtype, int N, int H, int W, char* ws, const Carve& cv, hipStream_t s) {
+    if (in_dtype == INNFER_F32 || net->fp32) return set_error(INNFER_ERR_UNSUPPORTED, "forward: RealPLKSR is built for the fp16 mode only: fp16 or uint8 input");
+    if (net->outm || net->final_act) return set_error(INNFER_ERR_UNSUPPORTED, "forward: RealPLKSR has no outm / final activation");
+    if (in_dtype == INNFER_U8 && !net->u8_round16) return set_error(INNFER_ERR_UNSUPPORTED, "forward: RealPLKSR is built for the fp16 mode only (innfer_net_set_u8_io fp16_mode = 1)");
+    for (auto& c : net->convs)
+        if (c.gn_ok && !c.d_gn) return set_error(INNFER_ERR_INVALID, "forward: the GroupNorm parameters behind '%s' were never set (innfer_net_set_group_norm)", c.key.c_str());
+    const long HW = (long)H * W, G = (long)N * HW * 32;
+    const double px = (double)N * HW;
+    f16* x = (f16*)(ws + cv.fea);
+    f16* M = (f16*)(ws + cv.slab[0]);
+    f16* U = (f16*)(ws + cv.slab[1]);
+    f16* tail = (f16*)(ws + cv.hr);
+    float* work = (float*)(ws + cv.tmp);
+    int ci = 0;
+    {
+        const ConvSlot& c0 = net->convs[ci++];
+        FirstConvLaunch F{};
+        F.in = d_in; F.in_f32 = 0; F.Cin = c0.C; F.w = (const float*)c0.d_w; F.bias = c0.d_b;
+        F.in_u8 = in_dtype == INNFER_U8; F.in_norm = net->u8_normalize; F.in_round16 = 1;
+        F.out = x; F.out_gstride = G;
+        F.K = net->nf; F.N = N; F.H = H; F.W = W; F.act = 0;
+        if (int rc = do_first(F, s)) return rc;
+    }
+    for (int b = 0; b < net->nb; ++b) {
+        const ConvSlot& ca = net->convs[ci++];
+        const ConvSlot& cb = net->convs[ci++];
+        const ConvSlot& c2 = net->convs[ci++];
+        const ConvSlot& lk = net->convs[ci++];
+        const ConvSlot* ea = net->plk_ea ? &net->convs[ci++] : nullptr;
+        const ConvSlot& rf = net->convs[ci++];
+        ConvLaunch La = mk_launch(ca, x, G, M, G, N, H, W, 11, 0);
+        if (int rc = do_conv(La, s)) return rc;
+        ConvLaunch Lb = mk_launch(cb, x, G, M + 2 * G, G, N, H, W, 11, 0);
+        if (int rc = do_conv(Lb, s)) return rc;
+        ConvLaunch L2 = mk_launch(c2, M, G, U, 2 * G, N, H, W, 0, 0);
+        if (int rc = do_conv(L2, s)) return rc;
+        PlkLaunch P{U, U + G, (const f16*)lk.d_w, lk.d_b, lk.ksize, N, H, W};
+        // launch kind 7000: the partial large-kernel conv -- bytes: one group in, one out, the panel
+        if (int rc = plksr_pass(s, "plk_conv", 2.0 * lk.ksize * lk.ksize * 256.0 * px, px * 128.0 + lk.ksize * lk.ksize * 512.0, 7000, [&] { return plk_conv_launch(P, s); })) return rc;
+        const f16* v = U + G;
+        if (ea) {
+            ConvLaunch Le = mk_launch(*ea, U + G, G, M, G, N, H, W, 5, 0);
+            Le.res1 = U + G; Le.res1_gstride = G;
+            if (int rc = do_conv(Le, s)) return rc;
+            v = M;
+        }
+        f16* u = M + 2 * G;
+        ConvLaunch Lr = mk_launch(rf, v, G, u, G, N, H, W, 0, 0);
+        if (int rc = do_conv(Lr, s)) return rc;
+        // launch kinds 7001 .. 7003: the GroupNorm statistics, their merge, and norm + skip
+        if (int rc = plksr_pass(s, "gn_stats", 3.0 * 64 * px, px * 128.0, 7001, [&] { return gn_stats_launch(u, G, N, HW, work, s); })) return rc;
+        if (int rc = plksr_pass(s, "gn_finalize", 0.0, 0.0, 7002, [&] { return gn_finalize_launch(N, HW, net->plk_groups, rf.d_gn, rf.d_gn + 64, 1e-5f, work, s); })) return rc;
+        if (int rc = plksr_pass(s, "gn_apply", 2.0 * 64 * px, px * 384.0, 7003, [&] { return gn_apply_launch(u, G, x, G, x, G, N, HW, work, s); })) return rc;
+    }
+    const ConvSlot& cl = net->convs[ci++];
+    {
+        ConvLaunch L = mk_launch(cl, x, G, tail, G, N, H, W, 0, 0);
+        L.K = cl.Kp;
+        if (int rc = do_conv(L, s)) return rc;
+    }
+    ShuffleAddLaunch T{};
+    T.slab = tail; T.gstride = G;
+    T.base = d_in; T.base_u8 = in_dtype == INNFER_U8; T.base_norm = net->u8_normalize;
+    T.out = d_out; T.out_mode = out_dtype == INNFER_U8 ? 2 : out_dtype == INNFER_F32 ? 1 : 0; T.out_denorm = net->u8_normalize;
+    T.C = net->out_nc; T.s = net->scale; T.N = N; T.H = H; T.W = W;
+    const double k = (double)cl.K;
+    return plksr_pass(s, "shuffle_add", px * k, px * (k * 2.0 + net->in_nc * (T.base_u8 ? 1.0 : 2.0) + k * (T.out_mode == 2 ? 1.0 : T.out_mode == 1 ? 4.0 : 2.0)), 6000, [&] { return shuffle_add_launch(T, s); });
+}
+
 // Launch a dependent chain of same-resolution convs.  band_rows == 0: one launch per
 // layer over the whole frame.  band_rows > 0: skewed row bands -- layer l of band b
 // covers rows [b*R - l, (b+1)*R - l), so every row a layer reads from its predecessor
@@ -1060,6 +1211,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     char* ws = (char*)d_ws;
     if (net->kind == 2) return compact_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 3) return span_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
+    if (net->kind == 4) return plksr_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     const int nf = net->nf, gc = net->gc;
     const long G = (long)N * H * W * 32;          // group stride of every LR-resolution slab
     const long LO = (long)(cv.lo / 2);            // fp32-accurate mode: elements from a slab to its lo twin (0: fp16 mode)
@@ -1455,6 +1607,57 @@ extern "C" int innfer_conv3x3_f16_grid(const innfer_conv_args* a, int consumer_g
 }
 // The same launch with act = 8: f >= 0 ? f : d_slope[c] * f, d_slope padded like d_bias (for tests; the SRVGGNetCompact engine's layers)
 extern "C" int innfer_conv3x3_f16_slope(const innfer_conv_args* a, const float* d_slope, void* stream) { return conv3x3_f16_impl(a, d_slope, stream); }
+
+// RealPLKSR's partial large-kernel conv alone, for tests: plk_pack + plk_conv_launch, the code the network runs.  Uploads, launches, waits.
+extern "C" int innfer_plk_conv(const void* d_in, void* d_out, int N, int H, int W, int k, const float* h_weight_oihw, const float* h_bias, void* stream) {
+    if (!d_in || !d_out || !h_weight_oihw) return set_error(INNFER_ERR_INVALID, "plk_conv: null argument");
+    if (k < 3 || k > 17 || !(k & 1)) return set_error(INNFER_ERR_UNSUPPORTED, "plk_conv: kernel size %d (built: odd, 3 .. 17)", k);
+    if (N <= 0 || H <= 0 || W <= 0) return set_error(INNFER_ERR_INVALID, "plk_conv: bad shape %dx%dx%d", N, H, W);
+    {
+        const long G = (long)N * H * W * 32;
+        const f16 *a = (const f16*)d_in, *b = (const f16*)d_out;
+        if (a < b + G && b < a + G) return set_error(INNFER_ERR_INVALID, "plk_conv: the output group overlaps the input group");
+    }
+    std::vector<char> host(plk_packed_bytes(k));
+    plk_pack(h_weight_oihw, k, host.data());
+    float bias[16];
+    for (int i = 0; i < 16; ++i) bias[i] = h_bias ? h_bias[i] : 0.f;
+    void* d_w = nullptr; float* d_b = nullptr;
+    int rc = INNFER_OK;
+    if (hipMalloc(&d_w, host.size()) != hipSuccess || hipMalloc((void**)&d_b, sizeof bias) != hipSuccess) rc = set_error(INNFER_ERR_NOMEM, "plk_conv: out of device memory");
+    if (rc == INNFER_OK && (hipMemcpy(d_w, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_b, bias, sizeof bias, hipMemcpyHostToDevice) != hipSuccess))
+        rc = set_error(INNFER_ERR_HIP, "plk_conv: copying the weights failed");
+    if (rc == INNFER_OK) {
+        const PlkLaunch P{(const f16*)d_in, (f16*)d_out, (const f16*)d_w, d_b, k, N, H, W};
+        rc = plk_conv_launch(P, (hipStream_t)stream);
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "plk_conv: the launch failed");
+    }
+    (void)hipFree(d_w); (void)hipFree(d_b);
+    return rc;
+}
+
+// GroupNorm(groups, 64) per sample + skip alone, for tests: the three launches of group_norm.hip in the network's order.  Uploads gamma / beta, launches, waits.
+extern "C" size_t innfer_group_norm_skip_work_bytes(int N, int64_t HW) { return (N > 0 && HW > 0) ? gn_work_floats(N, (long)HW) * sizeof(float) : 0; }
+extern "C" int innfer_group_norm_skip(const void* d_u, int64_t u_gs, const void* d_skip, int64_t skip_gs, void* d_out, int64_t out_gs, int N, int64_t HW, int groups,
+                                      const float* h_gamma, const float* h_beta, float eps, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_u || !d_skip || !d_out || !d_work || N <= 0 || N > 65535 || HW <= 0) return set_error(INNFER_ERR_INVALID, "group_norm_skip: null argument or N=%d HW=%lld", N, (long long)HW);
+    if (groups != 1 && groups != 2 && groups != 4 && groups != 8) return set_error(INNFER_ERR_UNSUPPORTED, "group_norm_skip: %d groups of 64 channels (built: 1, 2, 4, 8)", groups);
+    const int64_t G = (int64_t)N * HW * 32;
+    if (u_gs < G || skip_gs < G || out_gs < G) return set_error(INNFER_ERR_INVALID, "group_norm_skip: a group stride below N * HW * 32");
+    if (work_bytes < gn_work_floats(N, (long)HW) * sizeof(float)) return set_error(INNFER_ERR_WORKSPACE, "group_norm_skip: work_bytes %zu < %zu", work_bytes, gn_work_floats(N, (long)HW) * sizeof(float));
+    float h[128];
+    for (int i = 0; i < 64; ++i) { h[i] = h_gamma ? h_gamma[i] : 1.f; h[64 + i] = h_beta ? h_beta[i] : 0.f; }
+    float* d_gn = nullptr;
+    if (hipMalloc((void**)&d_gn, sizeof h) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "group_norm_skip: out of device memory");
+    int rc = hipMemcpy(d_gn, h, sizeof h, hipMemcpyHostToDevice) == hipSuccess ? INNFER_OK : set_error(INNFER_ERR_HIP, "group_norm_skip: copying the parameters failed");
+    hipStream_t s = (hipStream_t)stream;
+    if (rc == INNFER_OK) rc = gn_stats_launch((const f16*)d_u, (long)u_gs, N, (long)HW, (float*)d_work, s);
+    if (rc == INNFER_OK) rc = gn_finalize_launch(N, (long)HW, groups, d_gn, d_gn + 64, eps, (float*)d_work, s);
+    if (rc == INNFER_OK) rc = gn_apply_launch((const f16*)d_u, (long)u_gs, (const f16*)d_skip, (long)skip_gs, (f16*)d_out, (long)out_gs, N, (long)HW, (const float*)d_work, s);
+    if (hipStreamSynchronize(s) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "group_norm_skip: a launch failed");
+    (void)hipFree(d_gn);
+    return rc;
+}
 
 // PixelShuffle(scale) of a conv slab + the nearest-upsampled input, as a single launch (for tests; SRVGGNetCompact's tail, csrc/shuffle_add.hip)
 extern "C" int innfer_shuffle_add(const void* d_slab, int64_t group_stride, const void* d_base, int base_dtype, int normalize, void* d_out, int out_dtype,

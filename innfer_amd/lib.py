@@ -200,6 +200,12 @@ SIGNATURES = {
     "innfer_span_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
     "innfer_first_conv_map": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "innfer_net_set_conv_slope": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_plksr_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 8),
+    "innfer_net_set_group_norm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "innfer_plk_conv": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "innfer_group_norm_skip_work_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
+    "innfer_group_norm_skip": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "innfer_conv1x1_packed_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "innfer_pack_conv1x1": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "innfer_pack_conv1x1_split": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),

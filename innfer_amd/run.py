@@ -27,6 +27,7 @@ _SNIFF = (
     ('body.0.weight', 'compact'),                    # BasicSR's SRVGGNetCompact: `body` is a ModuleList whose entry 0 is a conv (no body.0.rdb1.*)
     ('conv_1.sk.weight', 'span'),                    # SPAN (with conv_cat.weight): a full checkpoint ..
     ('conv_1.eval_conv.weight', 'span'),             # .. or a `deploy` one, which carries only the collapsed convs
+    ('feats.0.weight', 'realplksr'),                 # RealPLKSR (with feats.1.channel_mixer.0.weight)
     ('conv_first.weight', 'mesrgan'),
     ('model.0.weight', 'esrgan'),
     ('CFEM.0.weight', 'ppon'),
@@ -43,7 +44,8 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
     if 'n_averaged' in state_dict:
         state_dict = swa2normal(state_dict)
     for probe, arch in _SNIFF:
-        if probe in state_dict and (arch != 'realesrgan' or 'conv_first.weight' in state_dict) and (arch != 'span' or 'conv_cat.weight' in state_dict):
+        if probe in state_dict and (arch != 'realesrgan' or 'conv_first.weight' in state_dict) and (arch != 'span' or 'conv_cat.weight' in state_dict) and \
+                (arch != 'realplksr' or 'feats.1.channel_mixer.0.weight' in state_dict):
             break
     else:
         raise Exception("Could not infer model parameters.")
@@ -56,6 +58,8 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
         return _infer_compact(state_dict)
     if arch == 'span':
         return _infer_span(state_dict)
+    if arch == 'realplksr':
+        return _infer_realplksr(state_dict)
     if arch == 'pan':
         return _infer_pan(state_dict, scale, in_nc, out_nc)
     if arch == 'ppon':
@@ -158,6 +162,36 @@ def _infer_span(state_dict):
     norm = 'no_norm' not in state_dict
     cfg = {'type': 'span', 'in_nc': in_nc, 'out_nc': in_nc, 'nf': f, 'scale': up, 'norm': norm, 'deploy': deploy}
     return dict(arch='span', scale=up, in_nc=in_nc, out_nc=in_nc, nf=f, nb=6, plus=False, state_dict=state_dict,
+                net_params=get_network_G_config(cfg, up))
+
+
+def _infer_realplksr(state_dict):
+    """RealPLKSR checkpoints: dim and in_ch from feats.0, n_blocks from the highest feats.<i>.channel_mixer.0, kernel_size and split_ratio from feats.1.lk.conv, use_ea
+    from feats.1.attn.f.0, the scale = sqrt(last conv's channels / in_ch).  norm_groups is not in the keys: the published default, 4.  DySample checkpoints (to_img.*) and
+    the original PLKSR (no GroupNorm: feats.1.norm.weight missing) are refused."""
+    import math
+    if any(k.startswith('to_img.') for k in state_dict):
+        raise NotImplementedError('RealPLKSR checkpoint with a DySample upsampler (to_img.* keys): not built on the HIP path')
+    if 'feats.1.norm.weight' not in state_dict:
+        raise NotImplementedError('PLKSR checkpoint without feats.1.norm.weight (the original PLKSR, no GroupNorm): only RealPLKSR is built on the HIP path')
+    w0 = state_dict['feats.0.weight']
+    dim, in_nc = int(w0.shape[0]), int(w0.shape[1])
+    n_blocks = 0
+    while f'feats.{n_blocks + 1}.channel_mixer.0.weight' in state_dict:
+        n_blocks += 1
+    last = f'feats.{n_blocks + 2}.weight'
+    if last not in state_dict or 'feats.1.lk.conv.weight' not in state_dict:
+        raise Exception("Could not infer model parameters.")
+    lk = state_dict['feats.1.lk.conv.weight']
+    p, ks = int(lk.shape[0]), int(lk.shape[-1])
+    k_last = int(state_dict[last].shape[0])
+    up = math.isqrt(k_last // in_nc) if k_last % in_nc == 0 else 0
+    if up * up * in_nc != k_last:
+        raise NotImplementedError(f'RealPLKSR checkpoint: the last conv has {k_last} channels, not in_ch ({in_nc}) times a square '
+                                  '(out_ch != in_ch is not built on the HIP path)')
+    cfg = {'type': 'realplksr', 'in_nc': in_nc, 'out_nc': in_nc, 'nf': dim, 'nb': n_blocks, 'scale': up, 'kernel_size': ks, 'split_ratio': p / dim,
+           'use_ea': 'feats.1.attn.f.0.weight' in state_dict}
+    return dict(arch='realplksr', scale=up, in_nc=in_nc, out_nc=in_nc, nf=dim, nb=n_blocks, plus=False, state_dict=state_dict,
                 net_params=get_network_G_config(cfg, up))
 
 

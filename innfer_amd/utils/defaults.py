@@ -131,6 +131,17 @@ def get_network_G_config(network_G, scale):
         cfg['upscale'] = _pick(opts, 'scale', scale)
         cfg['norm'] = _pick(opts, 'norm', True)
         cfg['deploy'] = _pick(opts, 'deploy', False)
+    elif kind in ('realplksr', 'realplksr_net'):           # RealPLKSR (partial large-kernel conv, Mish, GroupNorm): the published constructor surface
+        cfg['type'] = 'realplksr'
+        cfg['in_ch'] = _pick(opts, 'in_nc', 3)
+        cfg['out_ch'] = _pick(opts, 'out_nc', 3)
+        cfg['dim'] = _pick(opts, 'nf', 64)
+        cfg['n_blocks'] = _pick(opts, 'nb', 28)
+        cfg['upscaling_factor'] = _pick(opts, 'scale', scale)
+        cfg['kernel_size'] = _pick(opts, 'kernel_size', 17)
+        cfg['split_ratio'] = _pick(opts, 'split_ratio', 0.25)
+        cfg['use_ea'] = _pick(opts, 'use_ea', True)
+        cfg['norm_groups'] = _pick(opts, 'norm_groups', 4)
     else:
         raise NotImplementedError(f'Generator model [{kind:s}] not recognized')
 
