@@ -33,6 +33,8 @@ def get_network(opt_net):
         from .SPAN_arch import SPAN as net
     elif kind in ('realplksr', 'realplksr_net'):
         from .PLKSR_arch import RealPLKSR as net
+    elif kind in ('swinir', 'swinir_net'):
+        from .SwinIR_arch import SwinIR as net
     else:
         raise NotImplementedError('Model [{:s}] not recognized'.format(kind))
     return net(**opt_net)

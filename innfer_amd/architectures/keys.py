@@ -198,6 +198,59 @@ def realplksr_shapes(in_ch=3, out_ch=3, dim=64, n_blocks=28, upscaling_factor=4,
     return s
 
 
+def swinir_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=6, mlp_ratio=2.0, upscale=4, upsampler='pixelshuffle', resi_connection='1conv', window_size=8):
+    """State-dict key -> shape of the PARAMETERS of SwinIR (KAIR / BasicSR swinir_arch.py; patch_size 1, qkv_bias, patch_norm, no absolute position embedding).  The buffers
+    (attn.relative_position_index on every block, attn_mask on the odd ones) are not parameters: the index is a formula and the mask depends on img_size."""
+    C, hid, s = embed_dim, int(embed_dim * mlp_ratio + 1e-6), {}
+
+    def lin(k, co, ci):
+        s[k + '.weight'], s[k + '.bias'] = (co, ci), (co,)
+
+    def conv(k, co, ci, ks=3):
+        s[k + '.weight'], s[k + '.bias'] = (co, ci, ks, ks), (co,)
+
+    def norm(k):
+        s[k + '.weight'], s[k + '.bias'] = (C,), (C,)
+
+    def resi(k):
+        if resi_connection == '3conv':
+            conv(k + '.0', C // 4, C); conv(k + '.2', C // 4, C // 4, 1); conv(k + '.4', C, C // 4)
+        else:
+            conv(k, C, C)
+    conv('conv_first', C, in_chans)
+    norm('patch_embed.norm')
+    for i, depth in enumerate(depths):
+        for j in range(depth):
+            b = f'layers.{i}.residual_group.blocks.{j}.'
+            norm(b + 'norm1')
+            s[b + 'attn.relative_position_bias_table'] = ((2 * window_size - 1) ** 2, num_heads)
+            lin(b + 'attn.qkv', 3 * C, C)
+            lin(b + 'attn.proj', C, C)
+            norm(b + 'norm2')
+            lin(b + 'mlp.fc1', hid, C)
+            lin(b + 'mlp.fc2', C, hid)
+        resi(f'layers.{i}.conv')
+    norm('norm')
+    resi('conv_after_body')
+    if upsampler == 'pixelshuffledirect':
+        conv('upsample.0', upscale * upscale * in_chans, C)
+        return s
+    conv('conv_before_upsample.0', 64, C)
+    if upsampler == 'pixelshuffle':
+        if upscale == 3:
+            conv('upsample.0', 576, 64)
+        else:
+            for st in range(max(1, upscale.bit_length() - 1)):
+                conv(f'upsample.{2 * st}', 256, 64)
+    else:                                    # nearest+conv
+        conv('conv_up1', 64, 64)
+        if upscale == 4:
+            conv('conv_up2', 64, 64)
+        conv('conv_hr', 64, 64)
+    conv('conv_last', in_chans, 64)
+    return s
+
+
 def srresnet_layout(nb, norm=False, mode='CNA'):
     """Positions of a ResNetBlock's / LR_conv's layers inside the flattened Sequentials (SRResNet_arch.py:23-27,68-86; block.py:242-254,
     B.sequential flattens nested Sequentials): {engine key -> (conv key, BatchNorm in front of the conv or None, BatchNorm behind it or None)}.

@@ -28,6 +28,17 @@ __device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn
 // Mish(f) = f * tanh(softplus(f)) = f * w / (w + 2) with w = n (n + 2), n = e^f: no cancellation on either side of zero, one exponential and one reciprocal.  The exponent is
 // capped at 20 (w = e^40 stays finite; w / (w + 2) is already 1 in fp32 from f = 9 on), so a large f returns f itself; a NaN stays a NaN.
 __device__ __forceinline__ float fast_mish(float x) { const float n = __expf(x > 20.0f ? 20.0f : x); const float w = n * (n + 2.0f); return x * (w * __builtin_amdgcn_rcpf(w + 2.0f)); }
+// GELU(f) = f Phi(f) = f (1 + erf(f / sqrt 2)) / 2, the exact (erf) form.  erfc(x) = t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) e^(-x^2), t = 1 / (1 + p x), x >= 0, is Abramowitz &
+// Stegun 7.1.26: |error| <= 1.5e-7 absolute.  With h = |f| erfc(|f| / sqrt 2) / 2 the result is f - h above zero and -h below: no cancellation on the negative side, where
+// 1 + erf would lose every digit.  |f| is capped at 100 inside h (e^(-5000) = 0: h = 0), so a large f returns f itself or -0; a NaN stays a NaN.
+__device__ __forceinline__ float fast_gelu(float f) {
+    const float a0 = fabsf(f), a = a0 > 100.0f ? 100.0f : a0, x = a * 0.70710678118654752440f;
+    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(0.3275911f, x, 1.0f));
+    float q = __builtin_fmaf(1.061405429f, t, -1.453152027f);
+    q = __builtin_fmaf(q, t, 1.421413741f); q = __builtin_fmaf(q, t, -0.284496736f); q = __builtin_fmaf(q, t, 0.254829592f);
+    const float h = (0.5f * a) * ((q * t) * __expf(-(x * x)));
+    return f >= 0.f ? f - h : -h;
+}
 __device__ __forceinline__ float fast_tanh(float x) { return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)); }      // (+-inf -> +-1; absolute error ~1e-7)
 
 // Generic launch timer (innfer_timer_start / innfer_timer_stop, net.hip): while a collection is open on the calling thread every instrumented launch is
@@ -106,7 +117,7 @@ struct ConvLaunch {
     int out_coff;                                 // channel offset inside that group (0 or 16)
     int K;                                        // valid output channels
     int N, H, W;                                  // conv (output) size
-    int act; int up;                              // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 8 per-channel slope (`slope`) / 3 tanh (OUT_NCHW only) / 4, 5 res1 * sigmoid(conv) with / without LeakyReLU (slab) / 6 sigmoid (OUT_NCHW only) / 7 pair gate: 64 rows -> 32 outputs, row 16 lg + r (r < 8) times sigmoid(row 16 lg + r + 8) (slab, PAN's PAConv) / 9 SiLU, f * sigmoid(f) / 10 SPAN's gate, (f + res1) * (sigmoid(f) - 0.5) (s1 unused, no res2) / 11 Mish, f * tanh(softplus(f)): epilogue of the plain 3x3 slab conv of 64 outputs (rowp 0 / 1; conv3x3_pc MISH) -- 9 and 10: epilogues of the plain 3x3 slab convs of 64 (rowp 0 / 1) and 32 outputs (conv3x3_pc SPAN), every other form refuses them; up: input read through nearest 2x
+    int act; int up;                              // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 8 per-channel slope (`slope`) / 3 tanh (OUT_NCHW only) / 4, 5 res1 * sigmoid(conv) with / without LeakyReLU (slab) / 6 sigmoid (OUT_NCHW only) / 7 pair gate: 64 rows -> 32 outputs, row 16 lg + r (r < 8) times sigmoid(row 16 lg + r + 8) (slab, PAN's PAConv) / 9 SiLU, f * sigmoid(f) / 10 SPAN's gate, (f + res1) * (sigmoid(f) - 0.5) (s1 unused, no res2) / 11 Mish, f * tanh(softplus(f)): epilogue of the plain 3x3 slab conv of 64 outputs (rowp 0 / 1; conv3x3_pc MISH) / 12 exact GELU, f (1 + erf(f / sqrt 2)) / 2: epilogue of the 1x1 slab conv of 64 outputs (conv3x3_pc GELU), every other form refuses it -- 9 and 10: epilogues of the plain 3x3 slab convs of 64 (rowp 0 / 1) and 32 outputs (conv3x3_pc SPAN), every other form refuses them; up: input read through nearest 2x
     const f16* res1; long res1_gstride; float s1;
     const f16* res2; long res2_gstride; float s2;
     int y0, y1;                                   // output rows [y0,y1)
@@ -249,6 +260,13 @@ size_t gn_work_floats(int N, long HW);            // floats of `work`: the recor
 int gn_stats_launch(const f16* u, long u_gs, int N, long HW, float* work, hipStream_t s);
 int gn_finalize_launch(int N, long HW, int groups, const float* gamma, const float* beta, float eps, float* work, hipStream_t s);
 int gn_apply_launch(const f16* u, long u_gs, const f16* skip, long skip_gs, f16* out, long out_gs, int N, long HW, const float* work, hipStream_t s);
+
+// ---- SwinIR's window attention (win_attn.hip) and per-pixel LayerNorm (layer_norm.hip) ----
+// qkv: the head-padded slab of 3 nH groups (q | k | v; head h of each in its own 32-channel group: d real channels, then zeros; q already scaled); out: nH groups, channels
+// d .. 31 written as zeros; relb: dense fp32 [nH][64 query][64 key] relative position bias; Hp, Wp multiples of 8; shift 0 or 4 (the cyclic shift with its -100 mask)
+int win_attn_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, int N, int Hp, int Wp, int nH, int d, int shift, hipStream_t s);
+// out = fp16(LayerNorm(C)(in)) per pixel over the C real channels of two c_pad-channel slabs (pad channels written as zeros); in == out allowed
+int layer_norm_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s);
 
 // ---- layout / tiles / blend / pre-post (tiles.hip) ---------------------------
 int nchw_to_slab(const void* src, int src_f32, f16* slab, long gstride, int ch_off, int N, int C, int H, int W, hipStream_t s);

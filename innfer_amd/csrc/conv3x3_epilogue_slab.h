@@ -201,6 +201,8 @@ __device__ __forceinline__ void epilogue_slab(const KP& p, f32x4 (&acc)[NT][2 * 
                     f = f * fast_sigmoid(f);
                 } else if (ACT == 11) {                      // Mish (conv3x3_pc MISH)
                     f = fast_mish(f);
+                } else if (ACT == 12) {                      // exact GELU (conv3x3_pc GELU)
+                    f = fast_gelu(f);
                 } else if (ACT == 10) {                      // SPAN's gate: (f + res1) * (sigmoid(f) - 0.5), the second factor as tanh(f / 2) / 2 -- the same value without the cancellation
                     f = (f + (float)r1[R1 ? m : 0][t][j]) * (0.5f * fast_tanh(0.5f * f));
                 } else {

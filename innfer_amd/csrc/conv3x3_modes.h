@@ -25,6 +25,7 @@ constexpr int PC_PSH   = 0x800000;    // nn.PixelShuffle(2) as the store: phase-
 constexpr int PC_PRELU = 0x1000000;   // act 8: per-channel slopes in the slab epilogue (LDS tail: 256 B of slopes per consumer wave)
 constexpr int PC_GRID2 = 0x2000000;   // the eight consumer waves as a 2 x 4 grid (32-channel half x 4-row group; RPW 4, NT 2) over the same 16 x 32 tile and 64-row panels
 constexpr int PC_MISH  = 0x8000000;   // act 11 in the slab epilogue: Mish, f * tanh(softplus(f)) (one hardware exponential + reciprocal per value; RealPLKSR's DCCM)
+constexpr int PC_GELU  = 0x10000000;  // act 12 in the slab epilogue of the 64-output 1x1 conv: the exact (erf) GELU (SwinIR's mlp.fc1)
 constexpr int PC_SPAN  = 0x4000000;   // act 9 / 10 in the slab epilogue: SiLU, and SPAN's gate (f + res1) * (sigmoid(f) - 0.5) (one hardware exponential + reciprocal per value)
 
 // "tap mask + every flag below X": what an instantiation of mode X is compared against when the lower flags must all be clear

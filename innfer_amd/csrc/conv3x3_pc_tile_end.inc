@@ -65,6 +65,9 @@
             } else if constexpr (MISH) {
                 // act 11 (Mish, RealPLKSR's DCCM): plain slab store, no residual
                 epilogue_slab<RPW, NT, 11, false, false, true, false, false, false, false, ROWP, false>(p, acc, n, ty0, tx0, cw, li, cbase, dcur);
+            } else if constexpr (GELU) {
+                // act 12 (exact GELU, SwinIR's mlp.fc1): plain slab store, no residual
+                epilogue_slab<RPW, NT, 12, false, false, true, false, false, false, false, false, false>(p, acc, n, ty0, tx0, cw, li, cbase, dcur);
             } else if constexpr (OUTMODE == OUT_SLAB) {
             if constexpr (STATS) {
                 const int lid = run_start + (p.rev ? run_len - 1 - (jt - slots) : (jt - slots));         // (jt was advanced above)

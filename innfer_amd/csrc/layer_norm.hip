@@ -1,0 +1,84 @@
+// nn.LayerNorm(C) per pixel over a channel-padded fp16 slab (SwinIR: tokens = pixels): mean and biased variance over the C REAL channels of the slab's c_pad / 32 groups, eps inside
+// the square root, per-channel affine.  Four lanes own a pixel: lane q holds channels 8 q .. 8 q + 7 of every group (one 16-byte load per group, at most 64 values), so both
+// passes run on registers -- the sum, then the squared deviations from the mean (fp32, fixed order: the lane's groups in order, then the quad's butterfly) -- and
+//   out = fp16(fma((x - mean) * rstd, gamma[c], beta[c])),  rstd = 1 / sqrtf(var + eps):  one fp16 rounding.
+// Channels >= C are left out of the statistics whatever they hold and are WRITTEN as zeros.  in == out is allowed (a thread reads all it writes before it writes).
+// Memory bound: 64 bytes per group in, 64 out.
+#include "common.h"
+
+namespace innfer {
+
+namespace {
+
+struct LnArgs {
+    const f16* in; long in_gs;
+    f16* out; long out_gs;
+    const float* gamma; const float* beta;
+    long npix; int C; float eps;
+};
+
+template <int NG>
+__global__ __launch_bounds__(256) void layer_norm_kernel(const LnArgs p) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    const int q = (int)(i & 3);
+    const bool live = (i >> 2) < p.npix;
+    const long px = live ? (i >> 2) : p.npix - 1;          // (a quad beyond the last pixel repeats it and stores nothing: the exchanges below stay inside whole quads)
+    const f16* ib = p.in + px * 32 + q * 8;
+    f16x8 v[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) v[g] = *(const f16x8*)(ib + g * p.in_gs);
+    auto quad = [](float s) { s += __shfl_xor(s, 1); return s + __shfl_xor(s, 2); };
+    float s = 0.f;
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            if (g * 32 + q * 8 + e < p.C) s += (float)v[g][e];
+    const float rc = 1.0f / (float)p.C;
+    const float mu = quad(s) * rc;
+    s = 0.f;
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float d = (float)v[g][e] - mu;
+            if (g * 32 + q * 8 + e < p.C) s += d * d;
+        }
+    const float rstd = 1.0f / sqrtf(quad(s) * rc + p.eps);
+    if (!live) return;
+    f16* ob = p.out + px * 32 + q * 8;
+#pragma unroll
+    for (int g = 0; g < NG; ++g) {
+        const int c0 = g * 32 + q * 8;
+        f16x8 y;
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            y[e] = c0 + e < p.C ? (f16)__builtin_fmaf(((float)v[g][e] - mu) * rstd, p.gamma[c0 + e], p.beta[c0 + e]) : (f16)0.f;
+        *(f16x8*)(ob + g * p.out_gs) = y;
+    }
+}
+
+}  // namespace
+
+// c_pad: channels of both slabs (a multiple of 64, >= C, <= 256): every group is read and written.  gamma / beta: device floats, at least C each (the values behind C are never read)
+int layer_norm_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s) {
+    if (!in || !out || !gamma || !beta || npix <= 0) return set_error(INNFER_ERR_INVALID, "layer norm: null argument or %ld pixels", npix);
+    if (C < 1 || c_pad < C || c_pad > 256 || c_pad % 64) return set_error(INNFER_ERR_UNSUPPORTED, "layer norm: C=%d in a slab of %d channels (built: slabs of 64, 128, 192 or 256 channels -- at most eight groups in a quad's registers)", C, c_pad);
+    if (in_gs < npix * 32 || out_gs < npix * 32) return set_error(INNFER_ERR_INVALID, "layer norm: a group stride below %ld pixels x 32", npix);
+    const long nblk = (npix * 4 + 255) / 256;
+    if (nblk > 0x7fffffffL) return set_error(INNFER_ERR_UNSUPPORTED, "layer norm: %ld pixels exceed the launch grid", npix);
+    const int ng = c_pad / 32;
+    GtScope gt(s, "layer norm (per pixel, padded slab)", 8.0 * C * (double)npix, 128.0 * ng * (double)npix);
+    const LnArgs p{in, in_gs, out, out_gs, gamma, beta, npix, C, eps};
+    const dim3 grid((unsigned)nblk), block(256);
+    switch (ng) {
+        case 2: hipLaunchKernelGGL(layer_norm_kernel<2>, grid, block, 0, s, p); break;
+        case 4: hipLaunchKernelGGL(layer_norm_kernel<4>, grid, block, 0, s, p); break;
+        case 6: hipLaunchKernelGGL(layer_norm_kernel<6>, grid, block, 0, s, p); break;
+        default: hipLaunchKernelGGL(layer_norm_kernel<8>, grid, block, 0, s, p); break;
+    }
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+}  // namespace innfer

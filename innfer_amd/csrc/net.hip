@@ -112,11 +112,19 @@ struct ConvSlot {
     bool lane_rows = false;      // attn.f.0: a 64-output conv whose epilogue is the gate act 5 -- a form of the lane-contiguous panels only, so d_w is never packed in the plane row order
     bool gn_ok = false;          // refine: GroupNorm(groups, 64) follows it -- d_gn: gamma[64] then beta[64] (innfer_net_set_group_norm)
     float* d_gn = nullptr;
+    // SwinIR (kind 5)
+    float mult = 1.f;            // pixels this conv runs on per pixel of the padded LR grid (the tail's convs behind an upsampling stage): innfer_net_flops
 };
 
 struct innfer_net {
     int kind = 0;                // 0 rrdbnet, 1 srresnet, 2 BasicSR's SRVGGNetCompact (innfer_compact_create; compact_forward), 3 SPAN (innfer_span_create; span_forward), 4 RealPLKSR (innfer_plksr_create; plksr_forward)
     int plk_k = 17, plk_ea = 1, plk_groups = 4;      // RealPLKSR: kernel_size, use_ea, norm_groups
+    // SwinIR (kind 5; innfer_swinir_create): C = embed_dim padded to sw_cp, sw_nh heads of sw_d channels, the MLP's hidden size padded to sw_hp, RSTB depths, the tail
+    // (0 pixelshuffle, 1 pixelshuffledirect, 2 nearest+conv), resi_connection '3conv' (C / 4 padded to sw_c4p); the LayerNorm parameters (gamma[C] then beta[C] per norm, in
+    // the order patch_embed.norm, (norm1, norm2) per block, norm) and the dense relative position bias of every block ([nH][64][64])
+    int sw_c = 0, sw_cp = 0, sw_nh = 0, sw_d = 0, sw_hid = 0, sw_hp = 0, sw_tail = 0, sw_conv3 = 0, sw_c4p = 0;
+    std::vector<int> sw_depths;
+    std::vector<float*> sw_ln, sw_relb;
     bool span_norm = false;      // SPAN(norm=True): conv_1 reads (x - mean) * img_range through FirstConvLaunch.in_map (convs[0].d_map: alpha[in_nc] then shift[in_nc])
     int in_nc = 3, out_nc = 3, nf = 64, nb = 23, gc = 32, scale = 4, n_up = 2;
     int final_act = 0;           // `finalact` of the reference constructors: activation after the last conv (ConvLaunch.act codes)
@@ -344,6 +352,119 @@ extern "C" int innfer_plksr_create(innfer_net_t* out, int in_nc, int out_nc, int
     return INNFER_OK;
 }
 
+// SwinIR (Liang et al. 2021; the reference has no such architecture -- include/innfer_amd.h carries the definition) on 8 x 8 windows.  Every Linear and every conv from or
+// to the C_pad-channel token slab is a chain of 64-output launches, one ConvSlot each (key `<state-dict key>#<p>`: output channels 64 p .. 64 p + 63 of the RE-LAID-OUT
+// weight the caller passes: input channels padded with zeros, qkv rows in the head-padded order, proj columns likewise).  fp16 engine only.
+static void swin_add_sliced(innfer_net* net, const std::string& key, int Kp, int C, int ksize, float mult = 1.f) {
+    for (int p = 0; p < Kp / 64; ++p) {
+        add_conv(net, key + "#" + std::to_string(p), 64, C, false, ksize);
+        net->convs.back().mult = mult;
+    }
+}
+static void swin_add_resi(innfer_net* net, const std::string& key) {          // resi_connection: '1conv' a 3x3 conv, '3conv' 3x3 C -> C / 4, 1x1, 3x3 C / 4 -> C with LeakyReLU(0.2) between
+    if (!net->sw_conv3) { swin_add_sliced(net, key, net->sw_cp, net->sw_cp, 3); return; }
+    swin_add_sliced(net, key + ".0", net->sw_c4p, net->sw_cp, 3);
+    swin_add_sliced(net, key + ".2", net->sw_c4p, net->sw_c4p, 1);
+    swin_add_sliced(net, key + ".4", net->sw_cp, net->sw_c4p, 3);
+}
+extern "C" int innfer_swinir_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int upsampler,
+                                    int scale, int conv3, const float* h_mean) {
+    if (!out || !depths) return set_error(INNFER_ERR_INVALID, "swinir_create: null argument");
+    if (embed_dim < 1 || embed_dim > 256 || num_heads < 1 || num_heads > 8 || embed_dim % num_heads || embed_dim / num_heads > 32)
+        return set_error(INNFER_ERR_UNSUPPORTED, "swinir_create: embed_dim=%d num_heads=%d (built: embed_dim <= 256, <= 8 heads of <= 32 channels, embed_dim %% num_heads == 0)", embed_dim, num_heads);
+    if (mlp_hidden < 1 || mlp_hidden > 1024) return set_error(INNFER_ERR_UNSUPPORTED, "swinir_create: an MLP of %d hidden channels (built: <= 1024)", mlp_hidden);
+    if (in_nc < 1 || in_nc > 4 || in_nc != out_nc)
+        return set_error(INNFER_ERR_UNSUPPORTED, "swinir_create: in_chans=%d, %d output channels (built: equal, 1..4)", in_nc, out_nc);
+    if (n_layers < 1 || n_layers > 64) return set_error(INNFER_ERR_UNSUPPORTED, "swinir_create: %d residual groups", n_layers);
+    for (int i = 0; i < n_layers; ++i)
+        if (depths[i] < 1 || depths[i] > 64) return set_error(INNFER_ERR_UNSUPPORTED, "swinir_create: depth %d of residual group %d", depths[i], i);
+    if (upsampler < 0 || upsampler > 2) return set_error(INNFER_ERR_UNSUPPORTED, "swinir_create: upsampler %d (0 pixelshuffle, 1 pixelshuffledirect, 2 nearest+conv)", upsampler);
+    if ((upsampler == 2 && scale != 2 && scale != 4) || (upsampler != 2 && (scale < 2 || scale > 4)))
+        return set_error(INNFER_ERR_UNSUPPORTED, "swinir_create: scale %d (built: 2, 3, 4 with pixelshuffle / pixelshuffledirect, 2 and 4 with nearest+conv)", scale);
+    innfer_net* net = new innfer_net();
+    net->kind = 5; net->in_nc = in_nc; net->out_nc = out_nc; net->nf = 64; net->nb = 0; net->gc = 0; net->scale = scale; net->n_up = 0;
+    net->sw_c = embed_dim; net->sw_cp = (embed_dim + 63) / 64 * 64; net->sw_nh = num_heads; net->sw_d = embed_dim / num_heads;
+    net->sw_hid = mlp_hidden; net->sw_hp = (mlp_hidden + 63) / 64 * 64; net->sw_tail = upsampler; net->sw_conv3 = conv3 != 0;
+    net->sw_c4p = (embed_dim / 4 + 63) / 64 * 64;
+    net->sw_depths.assign(depths, depths + n_layers);
+    const int cp = net->sw_cp;
+    for (int p = 0; p < cp / 64; ++p) add_conv(net, "conv_first#" + std::to_string(p), 64, in_nc, true);
+    for (int i = 0; i < n_layers; ++i) {
+        for (int j = 0; j < depths[i]; ++j) {
+            const std::string b = "layers." + std::to_string(i) + ".residual_group.blocks." + std::to_string(j) + ".";
+            swin_add_sliced(net, b + "attn.qkv", (3 * num_heads + 1) / 2 * 64, cp, 1);
+            swin_add_sliced(net, b + "attn.proj", cp, 32 * num_heads, 1);
+            swin_add_sliced(net, b + "mlp.fc1", net->sw_hp, cp, 1);
+            swin_add_sliced(net, b + "mlp.fc2", cp, net->sw_hp, 1);
+            net->nb++;
+        }
+        swin_add_resi(net, "layers." + std::to_string(i) + ".conv");
+    }
+    swin_add_resi(net, "conv_after_body");
+    const float s2 = (float)(scale * scale);
+    if (upsampler == 1) {
+        add_conv(net, "upsample.0", out_nc * scale * scale, cp);
+        net->convs.back().Kp = out_nc * scale * scale <= 32 ? 32 : 64;
+    } else {
+        add_conv(net, "conv_before_upsample.0", 64, cp);
+        net->convs.back().slope_ok = true;
+        if (upsampler == 0) {
+            if (scale == 3) add_conv(net, "upsample.0", 576, 64);
+            else {
+                add_conv(net, "upsample.0", 256, 64); net->convs.back().ps2 = true;
+                if (scale == 4) { add_conv(net, "upsample.2", 256, 64); net->convs.back().ps2 = true; net->convs.back().mult = 4.f; }
+            }
+        } else {
+            add_conv(net, "conv_up1", 64, 64); net->convs.back().mult = 4.f;
+            if (scale == 4) { add_conv(net, "conv_up2", 64, 64); net->convs.back().mult = 16.f; }
+            add_conv(net, "conv_hr", 64, 64); net->convs.back().mult = s2;
+        }
+        add_conv(net, "conv_last", out_nc, 64); net->convs.back().mult = s2;
+    }
+    net->sw_ln.assign(2 + 2 * (size_t)net->nb, nullptr);
+    net->sw_relb.assign((size_t)net->nb, nullptr);
+    int rc = INNFER_OK;
+    {   // x - mean in front of conv_first (img_range 1): the input map of every slice of the first conv, held by slice 0; nn.LeakyReLU() (slope 0.01) behind conv_before_upsample
+        float h[8];
+        for (int c = 0; c < in_nc; ++c) { h[c] = 1.f; h[in_nc + c] = h_mean ? -h_mean[c] : 0.f; }
+        ConvSlot& c0 = net->convs[0];
+        if (hipMalloc((void**)&c0.d_map, 2 * in_nc * sizeof(float)) != hipSuccess || hipMemcpy(c0.d_map, h, 2 * in_nc * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            rc = set_error(INNFER_ERR_NOMEM, "swinir_create: no device memory for the input map");
+        for (size_t i = 0; i < net->convs.size() && rc == INNFER_OK; ++i)
+            if (net->convs[i].slope_ok) {
+                const std::vector<float> sl(64, 0.01f);
+                rc = innfer_net_set_conv_slope(net, (int)i, sl.data());
+            }
+    }
+    if (rc != INNFER_OK) { (void)hipGetLastError(); innfer_net_destroy(net); return rc; }
+    *out = net;
+    return INNFER_OK;
+}
+
+// gamma / beta (C host floats each) of LayerNorm `idx` of a SwinIR: 0 patch_embed.norm, 1 + 2 b / 2 + 2 b norm1 / norm2 of block b (blocks counted through the residual
+// groups), the last one norm.  Load time, synchronous.
+extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float* h_gamma, const float* h_beta) {
+    if (!net || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "set_layer_norm: null argument");
+    if (net->kind != 5) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR)");
+    if (idx < 0 || idx >= (int)net->sw_ln.size()) return set_error(INNFER_ERR_INVALID, "set_layer_norm: index %d of %zu", idx, net->sw_ln.size());
+    std::vector<float> h(2 * (size_t)net->sw_cp, 0.f);
+    for (int c = 0; c < net->sw_c; ++c) { h[c] = h_gamma[c]; h[net->sw_cp + c] = h_beta[c]; }
+    if (!net->sw_ln[idx]) INNFER_HIP(hipMalloc((void**)&net->sw_ln[idx], h.size() * sizeof(float)));
+    INNFER_HIP(hipMemcpy(net->sw_ln[idx], h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return INNFER_OK;
+}
+
+// The relative position bias of block `blk` of a SwinIR as the dense table the attention reads: [num_heads][64 query][64 key] host floats.  Load time, synchronous.
+extern "C" int innfer_net_set_attn_bias(innfer_net_t net, int blk, const float* h_bias) {
+    if (!net || !h_bias) return set_error(INNFER_ERR_INVALID, "set_attn_bias: null argument");
+    if (net->kind != 5) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_bias: the network has no window attention (built: SwinIR)");
+    if (blk < 0 || blk >= (int)net->sw_relb.size()) return set_error(INNFER_ERR_INVALID, "set_attn_bias: block %d of %zu", blk, net->sw_relb.size());
+    const size_t nb = (size_t)net->sw_nh * 4096 * sizeof(float);
+    if (!net->sw_relb[blk]) INNFER_HIP(hipMalloc((void**)&net->sw_relb[blk], nb));
+    INNFER_HIP(hipMemcpy(net->sw_relb[blk], h_bias, nb, hipMemcpyHostToDevice));
+    return INNFER_OK;
+}
+
 // The affine parameters of the GroupNorm behind conv `idx` (RealPLKSR's refine): 64 host floats each, NULL = 1 / 0.  Load time, synchronous.
 extern "C" int innfer_net_set_group_norm(innfer_net_t net, int idx, const float* h_gamma, const float* h_beta) {
     if (!net || idx < 0 || idx >= (int)net->convs.size()) return set_error(INNFER_ERR_INVALID, "set_group_norm: bad arguments");
@@ -379,6 +500,8 @@ extern "C" int innfer_net_set_outm(innfer_net_t net, int outm) {
 
 extern "C" void innfer_net_destroy(innfer_net_t net) {
     if (!net) return;
+    for (float* q : net->sw_ln) if (q) (void)hipFree(q);
+    for (float* q : net->sw_relb) if (q) (void)hipFree(q);
     for (auto& c : net->convs) {
         if (c.d_w) (void)hipFree(c.d_w);
         if (c.d_b) (void)hipFree(c.d_b);
@@ -539,6 +662,7 @@ extern "C" int innfer_net_set_precision(innfer_net_t net, int fp32) {
     if (fp32 && net->kind == 2) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SRVGGNetCompact is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 3) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SPAN is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 4) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: RealPLKSR is built for the fp16 mode only (no fp32-accurate engine)");
+    if (fp32 && net->kind == 5) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SwinIR is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32) {
         // The (wl | wh | wh) panels of every loaded conv are built HERE -- a load-time call, with its hipMalloc and synchronous copies -- never inside
         // innfer_net_forward (stream capture, concurrent callers).  Idempotent: a conv that already has its panels is skipped; innfer_net_set_conv
@@ -613,6 +737,12 @@ extern "C" int innfer_net_set_final_act(innfer_net_t net, int act) {
 
 extern "C" double innfer_net_flops(innfer_net_t net, int N, int H, int W) {
     if (!net) return 0.0;
+    if (net->kind == 5) {        // SwinIR: every conv on the padded grid (its tail's at their own resolution) + the two products of every window and head
+        const double px = (double)N * ((H + 7) / 8 * 8) * ((W + 7) / 8 * 8);
+        double f = (double)net->nb * net->sw_nh * (px / 64) * 4.0 * 64 * 64 * 32;
+        for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
+        return f;
+    }
     H = (H + net->unshuffle - 1) / net->unshuffle; W = (W + net->unshuffle - 1) / net->unshuffle;      // the LR grid
     double px = (double)N * H * W, f = 0.0;
     const int nconv = (int)net->convs.size();
@@ -645,8 +775,41 @@ struct Carve {
     int slab_w;
 };
 
+// SwinIR's workspace (kind 5) on the padded grid Hp x Wp: the padded input, the first conv's result (the last shortcut), two buffers the residual groups alternate between,
+// the token stream, the normalised tokens, the qkv slab (head-padded), the attention's result (head-padded), the MLP's hidden slab, the two C / 4 buffers of '3conv',
+// the tail's slabs, and the full-size result in front of the crop.
+struct SwinCarve { size_t xin, f0, r[2], t, u, qkv, att, hid, c4[2], b64, up[2], hr, outp, total; int Hp, Wp; };
+static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
+    SwinCarve c{};
+    c.Hp = (H + 7) / 8 * 8; c.Wp = (W + 7) / 8 * 8;
+    const size_t px = (size_t)N * c.Hp * c.Wp, s2 = (size_t)net->scale * net->scale;
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
+    c.xin = take(px * net->in_nc * 2);
+    c.f0 = take(px * net->sw_cp * 2);
+    c.r[0] = take(px * net->sw_cp * 2); c.r[1] = take(px * net->sw_cp * 2);
+    c.t = take(px * net->sw_cp * 2);
+    c.u = take(px * net->sw_cp * 2);
+    c.qkv = take(px * ((3 * net->sw_nh + 1) / 2 * 64) * 2);
+    c.att = take(px * 32 * net->sw_nh * 2);
+    c.hid = take(px * net->sw_hp * 2);
+    if (net->sw_conv3) { c.c4[0] = take(px * net->sw_c4p * 2); c.c4[1] = take(px * net->sw_c4p * 2); }
+    if (net->sw_tail == 1) c.hr = take(px * net->convs.back().Kp * 2);
+    else {
+        c.b64 = take(px * 64 * 2);
+        if (net->sw_tail == 0 && net->scale == 3) { c.up[0] = take(px * 576 * 2); c.up[1] = take(px * 9 * 64 * 2); }
+        else { c.up[0] = take(px * 4 * 64 * 2); if (net->scale == 4) c.up[1] = take(px * 16 * 64 * 2); }
+        if (net->sw_tail == 2) c.hr = take(px * s2 * 64 * 2);
+    }
+    c.outp = take(px * s2 * net->out_nc * 4);
+    c.total = off;
+    return c;
+}
+
 static Carve carve(const innfer_net* net, int N, int H, int W) {
     Carve c{};
+    if (net->kind == 5) { c.total = swin_carve(net, N, H, W).total; return c; }
     const size_t px = (size_t)N * H * W;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     if (net->kind == 2) {        // SRVGGNetCompact: the two ping-pong feature slabs (one when there is no nf -> nf conv) and the last conv's 32- / 64-channel slab
@@ -1163,6 +1326,186 @@ int plksr_forward(innfer_net* net, const void* d_in, int in_dtype, void* d_out, 
     return plksr_pass(s, "shuffle_add", px * k, px * (k * 2.0 + net->in_nc * (T.base_u8 ? 1.0 : 2.0) + k * (T.out_mode == 2 ? 1.0 : T.out_mode == 1 ? 4.0 : 2.0)), 6000, [&] { return shuffle_add_launch(T, s); });
 }
 
+// dst[o][y][x] = src[o][ry][rx] over `outer` planes of `inner`-byte pixels: a window copy between two sizes.  dst larger: F.pad(.., (0, pw, 0, ph), 'reflect') -- row y >= sh
+// reads row 2 (sh - 1) - y; dst smaller: the crop to its top-left dh x dw.  Planar tensors: outer = N C, inner = the element; uint8 HWC images: outer = N, inner = C.
+__global__ void rect_copy(const uint8_t* src, uint8_t* dst, long outer, int sh, int sw, int dh, int dw, int inner) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= outer * dh * dw) return;
+    const int x = (int)(i % dw), y = (int)((i / dw) % dh);
+    const long o = i / ((long)dw * dh);
+    const int ry = y < sh ? y : 2 * (sh - 1) - y, rx = x < sw ? x : 2 * (sw - 1) - x;
+    const uint8_t* q = src + ((o * sh + ry) * sw + rx) * inner;
+    for (int b = 0; b < inner; ++b) dst[i * inner + b] = q[b];
+}
+
+// SwinIR (kind 5) on the padded grid Hp x Wp (multiples of 8).  [pad]; conv_first (the input map x - mean its prologue) in C_pad / 64 launches -> f0; r = LN(f0);
+// per residual group: per block  u = LN(t); qkv (ceil(3 nH / 2) launches of two head groups); the window attention; proj + shortcut (C_pad / 64 launches, res1 = the
+// block's input: the group's input r for its first block, else t in place); u = LN(t); fc1 with GELU (act 12; hidden_pad / 64 launches); fc2 + shortcut (in place);
+// then r' = conv(t) + r into the other r buffer.  t = LN(r); F = conv_after_body(t) + f0; the tail; [crop].
+static int swinir_forward(innfer_net* net, const void* d_in, int in_dtype, void* d_out, int out_dtype, int N, int H, int W, char* ws, hipStream_t s) {
+    if (in_dtype == INNFER_F32 || net->fp32) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SwinIR is built for the fp16 mode only: fp16 or uint8 input");
+    if (net->outm || net->final_act) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SwinIR has no outm / final activation");
+    if (in_dtype == INNFER_U8 && !net->u8_round16) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SwinIR is built for the fp16 mode only (innfer_net_set_u8_io fp16_mode = 1)");
+    for (size_t i = 0; i < net->sw_ln.size(); ++i)
+        if (!net->sw_ln[i]) return set_error(INNFER_ERR_INVALID, "forward: the parameters of LayerNorm %zu were never set (innfer_net_set_layer_norm)", i);
+    for (size_t i = 0; i < net->sw_relb.size(); ++i)
+        if (!net->sw_relb[i]) return set_error(INNFER_ERR_INVALID, "forward: the relative position bias of block %zu was never set (innfer_net_set_attn_bias)", i);
+    const SwinCarve cv = swin_carve(net, N, H, W);
+    const int Hp = cv.Hp, Wp = cv.Wp, sc = net->scale, cp = net->sw_cp, nh = net->sw_nh;
+    if (Hp - H >= H || Wp - W >= W) return set_error(INNFER_ERR_INVALID, "forward: %d x %d cannot be reflect-padded to %d x %d (the pad must be smaller than the side)", H, W, Hp, Wp);
+    const bool padded = Hp != H || Wp != W;
+    const long npx = (long)N * Hp * Wp, G = npx * 32;
+    const double px = (double)npx;
+    const int omode = out_dtype == INNFER_U8 ? 2 : out_dtype == INNFER_F32 ? 1 : 0;
+    auto window = [&](const char* what, const void* src, void* dst, long outer, int sh, int sw, int dh, int dw, int inner, int kind) {
+        const long n = outer * dh * dw;
+        return plksr_pass(s, what, 0.0, 2.0 * n * inner, kind, [&] {
+            hipLaunchKernelGGL(rect_copy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const uint8_t*)src, (uint8_t*)dst, outer, sh, sw, dh, dw, inner);
+            INNFER_HIP(hipGetLastError());
+            return (int)INNFER_OK;
+        });
+    };
+    auto norm = [&](int idx, const f16* in, f16* out) {
+        // launch kind 8000: LayerNorm -- bytes: C_pad channels in and out
+        return plksr_pass(s, "layer_norm", 8.0 * net->sw_c * px, px * cp * 4.0, 8000,
+                          [&] { return layer_norm_launch(in, G, out, G, npx, net->sw_c, cp, net->sw_ln[idx], net->sw_ln[idx] + cp, 1e-5f, s); });
+    };
+    // a conv cut into 64-output launches: slice p writes channel groups 2 p, 2 p + 1 of `out` (and adds the same groups of `res`)
+    int ci = 0;
+    auto sliced = [&](int nslices, const f16* in, f16* out, int act, const f16* res) {
+        for (int p = 0; p < nslices; ++p) {
+            const ConvSlot& cs = net->convs[ci++];
+            ConvLaunch L = mk_launch(cs, in, G, out + 2L * p * G, G, N, Hp, Wp, act, 0);
+            if (res) { L.res1 = res + 2L * p * G; L.res1_gstride = G; L.s1 = 1.f; }
+            if (int rc = do_conv(L, s)) return rc;
+        }
+        return (int)INNFER_OK;
+    };
+    auto resi = [&](const f16* in, f16* out, const f16* res) {
+        if (!net->sw_conv3) return sliced(cp / 64, in, out, 0, res);
+        f16 *a = (f16*)(ws + cv.c4[0]), *b = (f16*)(ws + cv.c4[1]);
+        if (int rc = sliced(net->sw_c4p / 64, in, a, 1, nullptr)) return rc;
+        if (int rc = sliced(net->sw_c4p / 64, a, b, 1, nullptr)) return rc;
+        return sliced(cp / 64, b, out, 0, res);
+    };
+    const void* xin = d_in;
+    if (padded) {
+        xin = ws + cv.xin;
+        // launch kind 8002: the reflect pad of the input (8003: the crop of the result)
+        if (int rc = in_dtype == INNFER_U8 ? window("reflect pad", d_in, ws + cv.xin, N, H, W, Hp, Wp, net->in_nc, 8002)
+                                           : window("reflect pad", d_in, ws + cv.xin, (long)N * net->in_nc, H, W, Hp, Wp, 2, 8002)) return rc;
+    }
+    f16* f0 = (f16*)(ws + cv.f0);
+    f16* r[2] = {(f16*)(ws + cv.r[0]), (f16*)(ws + cv.r[1])};
+    f16* t = (f16*)(ws + cv.t);
+    f16* u = (f16*)(ws + cv.u);
+    f16* qkv = (f16*)(ws + cv.qkv);
+    f16* att = (f16*)(ws + cv.att);
+    f16* hid = (f16*)(ws + cv.hid);
+    const float* in_map = net->convs[0].d_map;
+    for (int p = 0; p < cp / 64; ++p) {
+        const ConvSlot& c0 = net->convs[ci++];
+        FirstConvLaunch F{};
+        F.in = xin; F.in_f32 = 0; F.Cin = c0.C; F.w = (const float*)c0.d_w; F.bias = c0.d_b;
+        F.in_u8 = in_dtype == INNFER_U8; F.in_norm = net->u8_normalize; F.in_round16 = 1;
+        F.out = f0 + 2L * p * G; F.out_gstride = G;
+        F.K = 64; F.N = N; F.H = Hp; F.W = Wp; F.act = 0;
+        F.in_map = in_map;
+        if (int rc = do_first(F, s)) return rc;
+    }
+    int cur = 0, blk = 0;
+    if (int rc = norm(0, f0, r[0])) return rc;
+    for (size_t i = 0; i < net->sw_depths.size(); ++i) {
+        for (int j = 0; j < net->sw_depths[i]; ++j, ++blk) {
+            const f16* x = j == 0 ? r[cur] : t;
+            if (int rc = norm(1 + 2 * blk, x, u)) return rc;
+            if (int rc = sliced((3 * nh + 1) / 2, u, qkv, 0, nullptr)) return rc;
+            // launch kind 8001: the window attention -- bytes: q, k, v in, o out (32-channel head groups), the bias table
+            if (int rc = plksr_pass(s, "window_attention", 4.0 * 64 * 32 * nh * px, px * nh * 256.0 + nh * 16384.0, 8001,
+                                    [&] { return win_attn_launch(qkv, G, att, G, net->sw_relb[blk], N, Hp, Wp, nh, net->sw_d, (j & 1) ? 4 : 0, s); })) return rc;
+            if (int rc = sliced(cp / 64, att, t, 0, x)) return rc;
+            if (int rc = norm(2 + 2 * blk, t, u)) return rc;
+            if (int rc = sliced(net->sw_hp / 64, u, hid, 12, nullptr)) return rc;
+            if (int rc = sliced(cp / 64, hid, t, 0, t)) return rc;
+        }
+        if (int rc = resi(t, r[cur ^ 1], r[cur])) return rc;
+        cur ^= 1;
+    }
+    if (int rc = norm((int)net->sw_ln.size() - 1, r[cur], t)) return rc;
+    f16* F = r[cur ^ 1];
+    if (int rc = resi(t, F, f0)) return rc;
+
+    const int hs = Hp * sc, wsz = Wp * sc;
+    void* dst = padded ? (void*)(ws + cv.outp) : d_out;
+    if (net->sw_tail == 1) {     // pixelshuffledirect: one conv C -> s^2 out, PixelShuffle(s) as the store (SRVGGNetCompact's tail without a base image)
+        const ConvSlot& cl = net->convs[ci++];
+        f16* tail = (f16*)(ws + cv.hr);
+        ConvLaunch L = mk_launch(cl, F, G, tail, G, N, Hp, Wp, 0, 0);
+        L.K = cl.Kp;
+        if (int rc = do_conv(L, s)) return rc;
+        ShuffleAddLaunch T{};
+        T.slab = tail; T.gstride = G; T.base = nullptr;
+        T.out = dst; T.out_mode = omode; T.out_denorm = net->u8_normalize;
+        T.C = net->out_nc; T.s = sc; T.N = N; T.H = Hp; T.W = Wp;
+        const double k = (double)cl.K;
+        if (int rc = plksr_pass(s, "shuffle (SwinIR tail)", 0.0, px * (k * 2.0 + k * (omode == 2 ? 1.0 : omode == 1 ? 4.0 : 2.0)), 6000, [&] { return shuffle_add_launch(T, s); })) return rc;
+    } else {
+        f16* b64 = (f16*)(ws + cv.b64);
+        {   // conv_before_upsample + nn.LeakyReLU() (slope 0.01: act 8 with a constant slope vector)
+            const ConvSlot& cb = net->convs[ci++];
+            ConvLaunch L = mk_launch(cb, F, G, b64, G, N, Hp, Wp, 8, 0);
+            L.slope = cb.d_slope;
+            if (int rc = do_conv(L, s)) return rc;
+        }
+        const f16* hr = b64;
+        int h = Hp, w = Wp;
+        if (net->sw_tail == 0 && sc == 3) {          // conv 64 -> 576, PixelShuffle(3) as a gather pass
+            const ConvSlot& cs = net->convs[ci++];
+            f16 *Y = (f16*)(ws + cv.up[0]), *D = (f16*)(ws + cv.up[1]);
+            if (int rc = do_conv(mk_launch(cs, hr, G, Y, G, N, h, w, 0, 0), s)) return rc;
+            // launch kind 8004: the PixelShuffle(3) gather -- bytes: 576 channels in, 64 x 9 pixels out
+            if (int rc = plksr_pass(s, "pixel_shuffle3", 0.0, px * 576 * 4.0, 8004, [&] { return launch_pixel_shuffle(Y, G, D, G * 9, 64, N, h, w, 3, s); })) return rc;
+            hr = D; h *= 3; w *= 3;
+        } else if (net->sw_tail == 0) {              // per factor of 2: conv 64 -> 256 with PixelShuffle(2) as its store
+            for (int st = 0; (2 << st) <= sc; ++st) {
+                const ConvSlot& cs = net->convs[ci++];
+                f16* D = (f16*)(ws + cv.up[st]);
+                const long gi = (long)N * h * w * 32;
+                ConvLaunch L = mk_launch(cs, hr, gi, D, gi * 4, N, h, w, 0, 0);
+                L.out_mode = OUT_SHUFFLE2;
+                if (cs.d_ps && (long)N * h * w * 256 < 0x7fffffffL) { L.wpk = (const f16*)cs.d_ps; L.bias = cs.d_bps; L.rowp = 2; }
+                if (int rc = do_conv(L, s)) return rc;
+                hr = D; h *= 2; w *= 2;
+            }
+        } else {                                     // nearest+conv: lrelu(conv_up1(nearest2x)), [lrelu(conv_up2(nearest2x)),] lrelu(conv_hr)
+            for (int st = 0; (2 << st) <= sc; ++st) {
+                const ConvSlot& cs = net->convs[ci++];
+                f16* D = (f16*)(ws + cv.up[st]);
+                const long gi = (long)N * h * w * 32;
+                ConvLaunch L = mk_launch(cs, hr, gi, D, gi * 4, N, 2 * h, 2 * w, 1, 0);
+                L.up = 1;
+                if (int rc = do_conv(L, s)) return rc;
+                hr = D; h *= 2; w *= 2;
+            }
+            const ConvSlot& ch = net->convs[ci++];
+            const long gh = (long)N * h * w * 32;
+            f16* D = (f16*)(ws + cv.hr);
+            if (int rc = do_conv(mk_launch(ch, hr, gh, D, gh, N, h, w, 1, 0), s)) return rc;
+            hr = D;
+        }
+        const ConvSlot& cl = net->convs[ci++];
+        ConvLaunch L = mk_launch(cl, hr, (long)N * h * w * 32, dst, 0, N, h, w, 0, 0);
+        L.out_mode = OUT_NCHW; L.out_f32 = out_dtype == INNFER_F32;
+        L.out_u8 = out_dtype == INNFER_U8; L.out_denorm = net->u8_normalize; L.out_round16 = 1;
+        if (int rc = do_conv(L, s)) return rc;
+    }
+    if (padded) {
+        if (omode == 2) return window("crop", dst, d_out, N, hs, wsz, H * sc, W * sc, net->out_nc, 8003);
+        return window("crop", dst, d_out, (long)N * net->out_nc, hs, wsz, H * sc, W * sc, omode == 1 ? 4 : 2, 8003);
+    }
+    return INNFER_OK;
+}
+
 // Launch a dependent chain of same-resolution convs.  band_rows == 0: one launch per
 // layer over the whole frame.  band_rows > 0: skewed row bands -- layer l of band b
 // covers rows [b*R - l, (b+1)*R - l), so every row a layer reads from its predecessor
@@ -1209,6 +1552,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     if (ws_bytes < cv.total) return set_error(INNFER_ERR_WORKSPACE, "forward: workspace %zu < %zu bytes", ws_bytes, cv.total);
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)d_ws;
+    if (net->kind == 5) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);
     if (net->kind == 2) return compact_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 3) return span_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 4) return plksr_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
@@ -1607,6 +1951,36 @@ extern "C" int innfer_conv3x3_f16_grid(const innfer_conv_args* a, int consumer_g
 }
 // The same launch with act = 8: f >= 0 ? f : d_slope[c] * f, d_slope padded like d_bias (for tests; the SRVGGNetCompact engine's layers)
 extern "C" int innfer_conv3x3_f16_slope(const innfer_conv_args* a, const float* d_slope, void* stream) { return conv3x3_f16_impl(a, d_slope, stream); }
+
+// SwinIR's window attention alone, for tests: win_attn_launch, the code the network runs.  Uploads the bias table, launches, waits.
+extern "C" int innfer_window_attention(const void* d_qkv, int64_t qkv_gs, void* d_out, int64_t out_gs, const float* h_bias, int N, int Hp, int Wp, int num_heads, int head_dim,
+                                       int shift, void* stream) {
+    if (!d_qkv || !d_out || !h_bias) return set_error(INNFER_ERR_INVALID, "window_attention: null argument");
+    if (num_heads < 1 || num_heads > 8) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention: %d heads (built: 1 .. 8)", num_heads);
+    float* d_b = nullptr;
+    const size_t nb = (size_t)num_heads * 4096 * sizeof(float);
+    if (hipMalloc((void**)&d_b, nb) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "window_attention: out of device memory");
+    int rc = hipMemcpy(d_b, h_bias, nb, hipMemcpyHostToDevice) == hipSuccess ? INNFER_OK : set_error(INNFER_ERR_HIP, "window_attention: copying the bias table failed");
+    if (rc == INNFER_OK) rc = win_attn_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, d_b, N, Hp, Wp, num_heads, head_dim, shift, (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "window_attention: the launch failed");
+    (void)hipFree(d_b);
+    return rc;
+}
+
+// SwinIR's per-pixel LayerNorm alone, for tests: layer_norm_launch, the code the network runs.  Uploads gamma / beta, launches, waits.
+extern "C" int innfer_layer_norm(const void* d_in, int64_t in_gs, void* d_out, int64_t out_gs, int64_t npix, int C, int c_pad, const float* h_gamma, const float* h_beta,
+                                 float eps, void* stream) {
+    if (!d_in || !d_out || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "layer_norm: null argument");
+    if (C < 1 || C > 256) return set_error(INNFER_ERR_UNSUPPORTED, "layer_norm: C=%d (built: 1 .. 256)", C);
+    float* d_p = nullptr;
+    if (hipMalloc((void**)&d_p, 2 * (size_t)C * sizeof(float)) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "layer_norm: out of device memory");
+    int rc = (hipMemcpy(d_p, h_gamma, C * sizeof(float), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_p + C, h_beta, C * sizeof(float), hipMemcpyHostToDevice) == hipSuccess)
+                 ? INNFER_OK : set_error(INNFER_ERR_HIP, "layer_norm: copying the parameters failed");
+    if (rc == INNFER_OK) rc = layer_norm_launch((const f16*)d_in, (long)in_gs, (f16*)d_out, (long)out_gs, (long)npix, C, c_pad, d_p, d_p + C, eps, (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "layer_norm: the launch failed");
+    (void)hipFree(d_p);
+    return rc;
+}
 
 // RealPLKSR's partial large-kernel conv alone, for tests: plk_pack + plk_conv_launch, the code the network runs.  Uploads, launches, waits.
 extern "C" int innfer_plk_conv(const void* d_in, void* d_out, int N, int H, int W, int k, const float* h_weight_oihw, const float* h_bias, void* stream) {

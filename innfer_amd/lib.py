@@ -202,6 +202,11 @@ SIGNATURES = {
     "innfer_net_set_conv_slope": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_plksr_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 8),
     "innfer_net_set_group_norm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "innfer_swinir_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "innfer_net_set_layer_norm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "innfer_net_set_attn_bias": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_window_attention": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "innfer_layer_norm": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "innfer_plk_conv": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p]),
     "innfer_group_norm_skip_work_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "innfer_group_norm_skip": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,

@@ -28,6 +28,7 @@ _SNIFF = (
     ('conv_1.sk.weight', 'span'),                    # SPAN (with conv_cat.weight): a full checkpoint ..
     ('conv_1.eval_conv.weight', 'span'),             # .. or a `deploy` one, which carries only the collapsed convs
     ('feats.0.weight', 'realplksr'),                 # RealPLKSR (with feats.1.channel_mixer.0.weight)
+    ('layers.0.residual_group.blocks.0.norm1.weight', 'swinir'),      # SwinIR and what builds on its skeleton (with conv_first.weight): ahead of the new-arch probe
     ('conv_first.weight', 'mesrgan'),
     ('model.0.weight', 'esrgan'),
     ('CFEM.0.weight', 'ppon'),
@@ -45,7 +46,7 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
         state_dict = swa2normal(state_dict)
     for probe, arch in _SNIFF:
         if probe in state_dict and (arch != 'realesrgan' or 'conv_first.weight' in state_dict) and (arch != 'span' or 'conv_cat.weight' in state_dict) and \
-                (arch != 'realplksr' or 'feats.1.channel_mixer.0.weight' in state_dict):
+                (arch != 'realplksr' or 'feats.1.channel_mixer.0.weight' in state_dict) and (arch != 'swinir' or 'conv_first.weight' in state_dict):
             break
     else:
         raise Exception("Could not infer model parameters.")
@@ -60,6 +61,8 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
         return _infer_span(state_dict)
     if arch == 'realplksr':
         return _infer_realplksr(state_dict)
+    if arch == 'swinir':
+        return _infer_swinir(state_dict)
     if arch == 'pan':
         return _infer_pan(state_dict, scale, in_nc, out_nc)
     if arch == 'ppon':
@@ -192,6 +195,78 @@ def _infer_realplksr(state_dict):
     cfg = {'type': 'realplksr', 'in_nc': in_nc, 'out_nc': in_nc, 'nf': dim, 'nb': n_blocks, 'scale': up, 'kernel_size': ks, 'split_ratio': p / dim,
            'use_ea': 'feats.1.attn.f.0.weight' in state_dict}
     return dict(arch='realplksr', scale=up, in_nc=in_nc, out_nc=in_nc, nf=dim, nb=n_blocks, plus=False, state_dict=state_dict,
+                net_params=get_network_G_config(cfg, up))
+
+
+def _infer_swinir(state_dict):
+    """SwinIR checkpoints (the three super-resolution forms): embed_dim and in_chans from conv_first, depths by counting layers.<i>.residual_group.blocks.<j>, num_heads and
+    the window from the relative position bias table ([(2 ws - 1)^2, nH]), mlp_ratio from mlp.fc1, '3conv' from layers.0.conv.0, the tail and the scale from the tail's keys.
+    The buffers (attn.relative_position_index, attn_mask) are dropped from the state dict handed back: the engine rebuilds the index from its formula -- a stored index that
+    differs is refused -- and computes the mask from the coordinates (the stored one is sized for img_size).  Swin2SR, HAT / DRCT, an absolute position embedding, a window
+    other than 8, the denoising / JPEG forms (no upsampler) and checkpoints without patch_embed.norm or qkv biases are refused."""
+    import math
+    b0 = 'layers.0.residual_group.blocks.0.'
+    if any(k.endswith('attn.logit_scale') for k in state_dict):
+        raise NotImplementedError('Swin2SR checkpoint (attn.logit_scale: cosine attention, continuous position bias): not built on the HIP path')
+    if any('overlap_attn' in k or 'conv_block' in k for k in state_dict):
+        raise NotImplementedError('HAT / DRCT checkpoint (overlap_attn / conv_block keys): not built on the HIP path')
+    if 'absolute_pos_embed' in state_dict:
+        raise NotImplementedError('SwinIR checkpoint with absolute_pos_embed (ape=True): not built on the HIP path')
+    if b0 + 'attn.relative_position_bias_table' not in state_dict or b0 + 'attn.qkv.weight' not in state_dict or b0 + 'mlp.fc1.weight' not in state_dict:
+        raise Exception("Could not infer model parameters.")
+    if 'patch_embed.norm.weight' not in state_dict:
+        raise NotImplementedError('SwinIR checkpoint without patch_embed.norm (patch_norm=False): not built on the HIP path')
+    if b0 + 'attn.qkv.bias' not in state_dict:
+        raise NotImplementedError('SwinIR checkpoint without attn.qkv.bias (qkv_bias=False): not built on the HIP path')
+    w0 = state_dict['conv_first.weight']
+    C, in_nc = int(w0.shape[0]), int(w0.shape[1])
+    depths = []
+    while f'layers.{len(depths)}.residual_group.blocks.0.norm1.weight' in state_dict:
+        i, j = len(depths), 0
+        while f'layers.{i}.residual_group.blocks.{j}.norm1.weight' in state_dict:
+            j += 1
+        depths.append(j)
+    table = state_dict[b0 + 'attn.relative_position_bias_table']
+    nh, side = int(table.shape[1]), math.isqrt(int(table.shape[0]))
+    ws = (side + 1) // 2
+    if side * side != int(table.shape[0]) or 2 * ws - 1 != side:
+        raise Exception("Could not infer model parameters.")
+    if ws != 8:
+        raise NotImplementedError(f'SwinIR checkpoint with window_size {ws}: only 8 x 8 windows are built on the HIP path')
+    hidden = int(state_dict[b0 + 'mlp.fc1.weight'].shape[0])
+    if 'conv_up1.weight' in state_dict:
+        upsampler, up = 'nearest+conv', 4 if 'conv_up2.weight' in state_dict else 2
+        out_nc = int(state_dict['conv_last.weight'].shape[0])
+    elif 'conv_before_upsample.0.weight' in state_dict:
+        upsampler, up = 'pixelshuffle', 1
+        for k, v in state_dict.items():
+            if k.startswith('upsample.') and k.endswith('.weight'):
+                f = math.isqrt(int(v.shape[0]) // 64)
+                if f * f * 64 != int(v.shape[0]):
+                    raise Exception("Could not infer model parameters.")
+                up *= f
+        out_nc = int(state_dict['conv_last.weight'].shape[0])
+    elif 'upsample.0.weight' in state_dict:
+        upsampler = 'pixelshuffledirect'
+        k_up = int(state_dict['upsample.0.weight'].shape[0])
+        up = math.isqrt(k_up // in_nc) if k_up % in_nc == 0 else 0
+        if up * up * in_nc != k_up:
+            raise NotImplementedError(f'SwinIR checkpoint: upsample.0 has {k_up} channels, not in_chans ({in_nc}) times a square (more output than input channels is not built on the HIP path)')
+        out_nc = in_nc
+    else:
+        raise NotImplementedError("SwinIR checkpoint without an upsampler (upsampler '': the denoising / JPEG models): only the super-resolution forms are built on the HIP path")
+    if out_nc != in_nc:
+        raise NotImplementedError(f'SwinIR checkpoint: conv_last has {out_nc} channels, conv_first takes {in_nc} (unequal channel counts are not built on the HIP path)')
+    from .architectures.SwinIR_arch import relative_position_index
+    want = relative_position_index(ws)
+    for k in [k for k in state_dict if k.endswith('attn.relative_position_index')]:
+        v = state_dict[k]
+        if tuple(v.shape) != tuple(want.shape) or not bool((v.cpu().long() == want).all()):
+            raise NotImplementedError(f'SwinIR checkpoint: {k} differs from (ri - rj + 7) * 15 + (ci - cj + 7), the index the engine builds its bias table with')
+    state_dict = {k: v for k, v in state_dict.items() if not (k.endswith('attn.relative_position_index') or k.endswith('.attn_mask'))}
+    cfg = {'type': 'swinir', 'in_nc': in_nc, 'nf': C, 'depths': depths, 'num_heads': [nh] * len(depths), 'window_size': ws, 'mlp_ratio': hidden / C, 'scale': up,
+           'upsampler': upsampler, 'resi_connection': '3conv' if 'layers.0.conv.0.weight' in state_dict else '1conv'}
+    return dict(arch='swinir', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=sum(depths), plus=False, state_dict=state_dict,
                 net_params=get_network_G_config(cfg, up))
 
 

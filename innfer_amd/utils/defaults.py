@@ -142,6 +142,19 @@ def get_network_G_config(network_G, scale):
         cfg['split_ratio'] = _pick(opts, 'split_ratio', 0.25)
         cfg['use_ea'] = _pick(opts, 'use_ea', True)
         cfg['norm_groups'] = _pick(opts, 'norm_groups', 4)
+    elif kind in ('swinir', 'swinir_net'):                 # SwinIR (window-attention transformer, the super-resolution forms): the published constructor surface
+        cfg['type'] = 'swinir'
+        cfg['in_chans'] = _pick(opts, 'in_nc', 3)
+        cfg['embed_dim'] = _pick(opts, 'nf', 180)
+        cfg['depths'] = list(_pick(opts, 'depths', [6] * 6))
+        cfg['num_heads'] = list(_pick(opts, 'num_heads', [6] * len(cfg['depths'])))
+        cfg['window_size'] = _pick(opts, 'window_size', 8)
+        cfg['mlp_ratio'] = _pick(opts, 'mlp_ratio', 2.0)
+        cfg['upscale'] = _pick(opts, 'scale', scale)
+        cfg['img_range'] = _pick(opts, 'img_range', 1.0)
+        cfg['upsampler'] = _pick(opts, 'upsampler', 'pixelshuffle')
+        cfg['resi_connection'] = _pick(opts, 'resi_connection', '1conv')
+        opts.pop('out_nc', None)
     else:
         raise NotImplementedError(f'Generator model [{kind:s}] not recognized')
 
