@@ -45,7 +45,7 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): RealPLKSR -- innfer_plksr_create, innfer_net_set_group_norm, innfer_conv_args.act 11 (Mish), innfer_plk_conv (the partial large-kernel conv as a single launch), innfer_group_norm_skip / innfer_group_norm_skip_work_bytes (per-sample GroupNorm + skip over a 64-channel slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): SwinIR -- innfer_swinir_create, innfer_net_set_layer_norm, innfer_net_set_attn_bias, innfer_conv_args.act 12 (exact GELU on the 1x1 form), innfer_window_attention (the 8 x 8 window attention as a single launch), innfer_layer_norm (per-pixel LayerNorm over a padded slab).  innfer_version() returns the library's; a binding should compare. */
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): RealPLKSR -- innfer_plksr_create, innfer_net_set_group_norm, innfer_conv_args.act 11 (Mish), innfer_plk_conv (the partial large-kernel conv as a single launch), innfer_group_norm_skip / innfer_group_norm_skip_work_bytes (per-sample GroupNorm + skip over a 64-channel slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): SwinIR -- innfer_swinir_create, innfer_net_set_layer_norm, innfer_net_set_attn_bias, innfer_conv_args.act 12 (exact GELU on the 1x1 form), innfer_window_attention (the 8 x 8 window attention as a single launch), innfer_layer_norm (per-pixel LayerNorm over a padded slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a HAT): HAT -- innfer_hat_create, innfer_net_set_chan_attn, innfer_net_set_conv_scale, innfer_conv_args.act 13 (exact GELU on the plain 3x3 form), innfer_window_attention16 (the 16 x 16 window attention over a 16 x 16 or an overlapping 24 x 24 key window as a single launch), innfer_chan_attn_work_bytes / innfer_chan_attn_excite / innfer_chan_attn_scale_add (the channel attention's launches).  innfer_version() returns the library's; a binding should compare. */
 #define INNFER_ABI_VERSION 123
 int innfer_version(void);
 const char* innfer_last_error(void);
@@ -216,6 +216,47 @@ int innfer_window_attention(const void* d_qkv, int64_t qkv_gs, void* d_out, int6
  * Uploads gamma / beta (C host floats each), launches, waits. */
 int innfer_layer_norm(const void* d_in, int64_t in_gs, void* d_out, int64_t out_gs, int64_t npix, int C, int c_pad, const float* h_gamma, const float* h_beta, float eps,
                       void* stream);
+/* (123, additive) HAT (Chen et al. 2023, "Activating More Pixels in Image Super-Resolution Transformer"; the reference has no such architecture) on SwinIR's skeleton, with
+ * C = embed_dim, nH heads of d = C / nH, window ws = 16, overlapping window ows = 24, patch_size 1, qkv_bias, patch_norm, no absolute position embedding, img_range 1, '1conv':
+ *   forward(x):  reflect-pad right / bottom to multiples of 16; f = conv_first(x - mean); f = conv_after_body(norm(RHAGs(patch_embed.norm(f)))) + f;
+ *                conv_before_upsample + LeakyReLU(0.01); upsample (pixelshuffle); conv_last; + mean; crop
+ *   RHAG i:      t = conv(OCAB(HAB_{n-1}(... HAB_0(t)))) + t
+ *   HAB j:       u = norm1(t);  t = t + proj(attn(u)) + conv_scale * CAB(u);  t = t + fc2(GELU(fc1(norm2(t))))
+ *                attn: SwinIR's window attention with ws 16, shift 8 for odd j; -100 between region labels of the rolled frame (rows / columns split at Hp - 16 and Hp - 8)
+ *   CAB(u):      z = conv3x3(C -> C / compress_ratio) -> exact GELU -> conv3x3(C / compress_ratio -> C);  y = sigmoid(W2 relu(W1 mean_pixels(z) + b1) + b2);  CAB = z * y[channel]
+ *                -- the mean runs over the whole padded Hp x Wp grid of ONE sample
+ *   OCAB:        u = norm1(t); q, k, v = qkv(u); queries: the 16 x 16 windows; keys / values of window (wy, wx): the 24 x 24 pixels from (16 wy - 4, 16 wx - 4), a position
+ *                outside the padded grid has k = v = 0 (its score is the bias alone and it takes part in the softmax); softmax(q d^-0.5 k^T + B) v; no shift, no mask;
+ *                t = t + proj(.);  t = t + fc2(GELU(fc1(norm2(t))))
+ * on the engine of innfer_net_*, laid out as innfer_swinir_create's: conv slots `<state-dict key>#<p>` in forward order -- conv_first; per HAB conv_block.cab.0 (ONE slice:
+ * [64, C_pad, 3, 3], C / compress_ratio real rows), conv_block.cab.2 ([64, 64, 3, 3] slices), attn.qkv, attn.proj, mlp.fc1, mlp.fc2; per group overlap_attn.qkv, .proj,
+ * .mlp.fc1, .mlp.fc2 and the group's conv; conv_after_body; the pixelshuffle tail.  LayerNorms (innfer_net_set_layer_norm) and bias tables (innfer_net_set_attn_bias) are
+ * numbered in forward order: 0 patch_embed.norm; per group (norm1, norm2) of every HAB, then (norm1, norm2) of the OCAB; the last one norm -- tables: per group every HAB's
+ * [nH][256][256], then the OCAB's [nH][256][576].  compress_ch = C / compress_ratio and squeeze_ch = C / squeeze_factor, 1 .. 64 each; scale 2, 3, 4; the other limits as SwinIR's.
+ * innfer_net_forward takes H x W (each side larger than its pad to 16) and writes scale H x scale W.  Launches of a forward, with B HABs, R groups, S1 = C_pad / 64,
+ * SQ = ceil(3 nH / 2), SH = hidden_pad / 64, T = 2 + log2(scale) (4 for scale 3):
+ *   S1 + 2 + B (7 + SQ + 3 S1 + SH) + R (3 + SQ + 2 S1 + SH) + (R + 1) S1 + T + 2 [H x W is not Hp x Wp]. */
+int innfer_hat_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int compress_ch, int squeeze_ch,
+                      int scale, const float* h_mean);
+/* (123, additive) The channel attention of HAB `blk` of a HAT (counted through the groups): conv_block.cab.3.attention.1 as W1 [squeeze_ch][C], b1 [squeeze_ch] and
+ * conv_block.cab.3.attention.3 as W2 [C][squeeze_ch], b2 [C], host floats, kept and applied in fp32.  Load time, synchronous. */
+int innfer_net_set_chan_attn(innfer_net_t net, int blk, const float* h_w1, const float* h_b1, const float* h_w2, const float* h_b2);
+/* (123, additive) conv_scale of a HAT: a constructor argument of the published code that no state dict carries; 0.01 until set. */
+int innfer_net_set_conv_scale(innfer_net_t net, float conv_scale);
+/* (123, additive) The 16 x 16 window attention as a single launch (for tests; csrc/win_attn16.hip).  Slabs as innfer_window_attention's; Hp, Wp multiples of 16.
+ * key_window 16: the window's own 256 tokens, shift 0 or 8 (the windows of the rolled frame, -100 between regions), h_bias [num_heads][256][256].  key_window 24: the
+ * 24 x 24 pixels from (16 wy - 4, 16 wx - 4), zeros in k and v outside the grid (such a key still takes part in the softmax), shift 0, h_bias [num_heads][256][576].
+ * fp32 scores, running maximum and sum over blocks of 64 keys; P rounded to fp16 in front of P v; fp32 accumulation; one rounding of o / sum.  Uploads the table, launches, waits. */
+int innfer_window_attention16(const void* d_qkv, int64_t qkv_gs, void* d_out, int64_t out_gs, const float* h_bias, int N, int Hp, int Wp, int num_heads, int head_dim,
+                              int shift, int key_window, void* stream);
+/* (123, additive) HAT's channel attention as single launches (for tests; csrc/chan_attn.hip), per sample over slabs of c_pad channels (64, 128, 192, 256) of N x HW pixels.
+ * innfer_chan_attn_excite: the per-(sample, channel) sums of d_z (fp32, a fixed merge order: bit-identical on a repeat) and d_y[n][c] = sigmoid(W2 relu(W1 sums / HW + b1) + b2)
+ * in fp32 (N x c_pad floats; 0 for c >= C); d_sums (may be NULL) receives the sums, N x c_pad floats; d_work: innfer_chan_attn_work_bytes(N, HW, c_pad) bytes.
+ * innfer_chan_attn_scale_add: d_t = fp16(float(d_t) + conv_scale * d_y[n][c] * float(d_z)), one fp16 rounding, in place.  Nothing crosses samples.  Launch, wait. */
+size_t innfer_chan_attn_work_bytes(int N, int64_t HW, int c_pad);
+int innfer_chan_attn_excite(const void* d_z, int64_t z_gs, int N, int64_t HW, int C, int c_pad, int hidden, const float* h_w1, const float* h_b1, const float* h_w2,
+                            const float* h_b2, void* d_y, void* d_sums, void* d_work, size_t work_bytes, void* stream);
+int innfer_chan_attn_scale_add(void* d_t, int64_t t_gs, const void* d_z, int64_t z_gs, const void* d_y, float conv_scale, int N, int64_t HW, int c_pad, void* stream);
 /* The activation behind conv `idx` as K host floats: y = x >= 0 ? x : h_slope[c] * x -- nn.PReLU(num_parameters = K).weight, or the constant 0 (ReLU) / 0.1
  * (LeakyReLU(0.1)).  Load time, synchronous.  Every conv of an SRVGGNetCompact except the last needs one before the first forward; other convs refuse it. */
 int innfer_net_set_conv_slope(innfer_net_t net, int idx, const float* h_slope);
@@ -655,6 +696,9 @@ int innfer_conv3x3_f16(const innfer_conv_args* a, void* stream);
  * fp16 rounding at the store.  An epilogue of the conv1x1 slab conv with K = 64, batches, row ranges and whole-group out_ch_off included; every other form (3x3, K = 32,
  * split, d_stats_part, prefix_lrelu, out_planar, the stride-2 / phase / column / dilated forms, residuals, upsample2x, reflect_pad) answers INNFER_ERR_UNSUPPORTED;
  * nothing is launched. */
+/* (123, additive) a->act = 13: the same GELU as the epilogue of the plain 3x3 slab conv with K = 64 (plane_rows 0), batches, row ranges and whole-group out_ch_off included
+ * (HAT's conv block); every other form (conv1x1 -- that is act 12 --, K = 32, plane_rows, split, d_stats_part, the self gate, out_planar, the stride-2 / phase / column /
+ * dilated forms, residuals, upsample2x, reflect_pad) answers INNFER_ERR_UNSUPPORTED; nothing is launched. */
 /* (123, additive) RealPLKSR's partial large-kernel conv as a single launch (for tests; csrc/plk_conv.hip): d_in / d_out point at channel 0 of two DIFFERENT 32-channel
  * slab groups of N * H * W pixels; out channels 0 .. 15 = the k x k zero-padded conv (h_weight_oihw [16][16][k][k], h_bias 16 floats or NULL; k odd, 3 .. 17) of in channels
  * 0 .. 15 -- fp16 operands, fp32 accumulation, one rounding --, out channels 16 .. 31 = in channels 16 .. 31 bit for bit.  Overlapping groups are INNFER_ERR_INVALID

@@ -35,6 +35,8 @@ def get_network(opt_net):
         from .PLKSR_arch import RealPLKSR as net
     elif kind in ('swinir', 'swinir_net'):
         from .SwinIR_arch import SwinIR as net
+    elif kind in ('hat', 'hat_net'):
+        from .HAT_arch import HAT as net
     else:
         raise NotImplementedError('Model [{:s}] not recognized'.format(kind))
     return net(**opt_net)

@@ -251,6 +251,58 @@ def swinir_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_head
     return s
 
 
+def hat_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=6, mlp_ratio=2.0, upscale=4, compress_ratio=3, squeeze_factor=30, window_size=16,
+               overlap_win_size=24):
+    """State-dict key -> shape of the PARAMETERS of HAT (the published hat_arch.py; patch_size 1, qkv_bias, patch_norm, no absolute position embedding, the pixelshuffle
+    tail, '1conv').  The two top-level buffers (relative_position_index_SA / _OCA) are not parameters."""
+    C, hid, s = embed_dim, int(embed_dim * mlp_ratio + 1e-6), {}
+
+    def lin(k, co, ci):
+        s[k + '.weight'], s[k + '.bias'] = (co, ci), (co,)
+
+    def conv(k, co, ci, ks=3):
+        s[k + '.weight'], s[k + '.bias'] = (co, ci, ks, ks), (co,)
+
+    def norm(k):
+        s[k + '.weight'], s[k + '.bias'] = (C,), (C,)
+    conv('conv_first', C, in_chans)
+    norm('patch_embed.norm')
+    for i, depth in enumerate(depths):
+        g = f'layers.{i}.residual_group.'
+        for j in range(depth):
+            b = g + f'blocks.{j}.'
+            norm(b + 'norm1')
+            s[b + 'attn.relative_position_bias_table'] = ((2 * window_size - 1) ** 2, num_heads)
+            lin(b + 'attn.qkv', 3 * C, C)
+            lin(b + 'attn.proj', C, C)
+            conv(b + 'conv_block.cab.0', C // compress_ratio, C)
+            conv(b + 'conv_block.cab.2', C, C // compress_ratio)
+            conv(b + 'conv_block.cab.3.attention.1', C // squeeze_factor, C, 1)
+            conv(b + 'conv_block.cab.3.attention.3', C, C // squeeze_factor, 1)
+            norm(b + 'norm2')
+            lin(b + 'mlp.fc1', hid, C)
+            lin(b + 'mlp.fc2', C, hid)
+        o = g + 'overlap_attn.'
+        norm(o + 'norm1')
+        s[o + 'relative_position_bias_table'] = ((window_size + overlap_win_size - 1) ** 2, num_heads)
+        lin(o + 'qkv', 3 * C, C)
+        lin(o + 'proj', C, C)
+        norm(o + 'norm2')
+        lin(o + 'mlp.fc1', hid, C)
+        lin(o + 'mlp.fc2', C, hid)
+        conv(f'layers.{i}.conv', C, C)
+    norm('norm')
+    conv('conv_after_body', C, C)
+    conv('conv_before_upsample.0', 64, C)
+    if upscale == 3:
+        conv('upsample.0', 576, 64)
+    else:
+        for st in range(max(1, upscale.bit_length() - 1)):
+            conv(f'upsample.{2 * st}', 256, 64)
+    conv('conv_last', in_chans, 64)
+    return s
+
+
 def srresnet_layout(nb, norm=False, mode='CNA'):
     """Positions of a ResNetBlock's / LR_conv's layers inside the flattened Sequentials (SRResNet_arch.py:23-27,68-86; block.py:242-254,
     B.sequential flattens nested Sequentials): {engine key -> (conv key, BatchNorm in front of the conv or None, BatchNorm behind it or None)}.

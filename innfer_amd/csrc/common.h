@@ -117,7 +117,7 @@ struct ConvLaunch {
     int out_coff;                                 // channel offset inside that group (0 or 16)
     int K;                                        // valid output channels
     int N, H, W;                                  // conv (output) size
-    int act; int up;                              // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 8 per-channel slope (`slope`) / 3 tanh (OUT_NCHW only) / 4, 5 res1 * sigmoid(conv) with / without LeakyReLU (slab) / 6 sigmoid (OUT_NCHW only) / 7 pair gate: 64 rows -> 32 outputs, row 16 lg + r (r < 8) times sigmoid(row 16 lg + r + 8) (slab, PAN's PAConv) / 9 SiLU, f * sigmoid(f) / 10 SPAN's gate, (f + res1) * (sigmoid(f) - 0.5) (s1 unused, no res2) / 11 Mish, f * tanh(softplus(f)): epilogue of the plain 3x3 slab conv of 64 outputs (rowp 0 / 1; conv3x3_pc MISH) / 12 exact GELU, f (1 + erf(f / sqrt 2)) / 2: epilogue of the 1x1 slab conv of 64 outputs (conv3x3_pc GELU), every other form refuses it -- 9 and 10: epilogues of the plain 3x3 slab convs of 64 (rowp 0 / 1) and 32 outputs (conv3x3_pc SPAN), every other form refuses them; up: input read through nearest 2x
+    int act; int up;                              // act: 0 none / 1 LeakyReLU(0.2) / 2 ReLU / 8 per-channel slope (`slope`) / 3 tanh (OUT_NCHW only) / 4, 5 res1 * sigmoid(conv) with / without LeakyReLU (slab) / 6 sigmoid (OUT_NCHW only) / 7 pair gate: 64 rows -> 32 outputs, row 16 lg + r (r < 8) times sigmoid(row 16 lg + r + 8) (slab, PAN's PAConv) / 9 SiLU, f * sigmoid(f) / 10 SPAN's gate, (f + res1) * (sigmoid(f) - 0.5) (s1 unused, no res2) / 11 Mish, f * tanh(softplus(f)): epilogue of the plain 3x3 slab conv of 64 outputs (rowp 0 / 1; conv3x3_pc MISH) / 12 exact GELU, f (1 + erf(f / sqrt 2)) / 2: epilogue of the 1x1 slab conv of 64 outputs (conv3x3_pc GELU), every other form refuses it / 13 the same GELU as the epilogue of the plain 3x3 slab conv of 64 outputs (rowp 0; HAT's conv block), every other form refuses it -- 9 and 10: epilogues of the plain 3x3 slab convs of 64 (rowp 0 / 1) and 32 outputs (conv3x3_pc SPAN), every other form refuses them; up: input read through nearest 2x
     const f16* res1; long res1_gstride; float s1;
     const f16* res2; long res2_gstride; float s2;
     int y0, y1;                                   // output rows [y0,y1)
@@ -267,6 +267,16 @@ int gn_apply_launch(const f16* u, long u_gs, const f16* skip, long skip_gs, f16*
 int win_attn_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, int N, int Hp, int Wp, int nH, int d, int shift, hipStream_t s);
 // out = fp16(LayerNorm(C)(in)) per pixel over the C real channels of two c_pad-channel slabs (pad channels written as zeros); in == out allowed
 int layer_norm_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s);
+
+// ---- HAT's 16 x 16 window attention over a 16 x 16 (self, shift 0 | 8, mask) or 24 x 24 (overlapping, zero-filled at the border) key window (win_attn16.hip) ----
+// slabs as win_attn_launch's; relb: dense fp32 [nH][256 query][kw^2 key]; Hp, Wp multiples of 16; kw 16 | 24; shift 0, or 8 with kw 16
+int win_attn16_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, int N, int Hp, int Wp, int nH, int d, int shift, int kw, hipStream_t s);
+// ---- HAT's channel attention, per sample (chan_attn.hip): segment sums of a c_pad-channel slab, the squeeze / excite vector, t += conv_scale * y[n][c] * z ----
+size_t ca_work_floats(int N, long HW, int c_pad);
+int ca_pool_launch(const f16* z, long z_gs, int N, long HW, int c_pad, float* work, hipStream_t s);
+int ca_excite_launch(const float* work, int N, long HW, int C, int c_pad, int hid, const float* w1, const float* b1, const float* w2, const float* b2, float* y, float* sums,
+                     hipStream_t s);
+int ca_scale_add_launch(f16* t, long t_gs, const f16* z, long z_gs, const float* y, float scale, int N, long HW, int c_pad, hipStream_t s);
 
 // ---- layout / tiles / blend / pre-post (tiles.hip) ---------------------------
 int nchw_to_slab(const void* src, int src_f32, f16* slab, long gstride, int ch_off, int N, int C, int H, int W, hipStream_t s);

@@ -505,8 +505,9 @@ __global__ __launch_bounds__(64 * (NCW + NLW), 1) void conv3x3_pc(const KP p) {
     static_assert(!MISH || (OUTMODE == OUT_SLAB && NT == 4 && NSI == 2 && (TMF & ~(TAPS_3X3 | PC_ROWP | PC_MISH)) == 0 && TM == TAPS_3X3 && !S9 && !POLY && !CV), "Mish epilogue: the plain 64-output slab kernel");
     // + PC_GELU: ConvLaunch.act 12 (the exact GELU between SwinIR's mlp.fc1 and mlp.fc2) as the slab epilogue of the 64-output 1x1 kernel on three input slots -- fp32 on the
     // accumulator, one rounding at the store.  An instantiation of its own: the other kernels' code does not change.
+    // ConvLaunch.act 13 is the same epilogue behind the plain nine-tap 64-output kernel (the conv -> GELU -> conv of HAT's conv block): TAPS_3X3 | PC_GELU on two input slots.
     constexpr bool GELU = (TMF & PC_GELU) != 0;
-    static_assert(!GELU || (OUTMODE == OUT_SLAB && RPW == 2 && NT == 4 && NSI == 3 && TMF == (TAPS_1X1 | PC_GELU) && !S9 && !POLY && !CV), "GELU epilogue: the 64-output 1x1 slab kernel");
+    static_assert(!GELU || (OUTMODE == OUT_SLAB && RPW == 2 && NT == 4 && ((NSI == 3 && TMF == (TAPS_1X1 | PC_GELU)) || (NSI == 2 && TMF == (TAPS_3X3 | PC_GELU))) && !S9 && !POLY && !CV), "GELU epilogue: the 64-output 1x1 slab kernel, the plain 64-output 3x3 slab kernel");
     static_assert(!FUSE || (RPW == 2 && (NT == 4 || (NT == 2 && !ROWP)) && NSI == 2 && OUTMODE == OUT_SLAB && (TMF & PC_BELOW_FUSE) == TAPS_3X3 && !S9 && !POLY && !CV), "the fused last conv: the plain 64-channel instantiation (and the 32-channel one on 16-row tiles)");
     using L = PcLayout<RPW, NT, NSI, TMF>;                  // the LDS layout, shared with launch_pc
     constexpr int TH = L::TH;
@@ -1060,7 +1061,7 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
     if (L.act == 7 && (L.out_mode != OUT_SLAB || conv_nt_for(L.K) != 4 || L.K % 64 || L.res1 || L.res2 || L.conv1x1 || L.dilation > 1 || L.dilation_groups ||
                        L.deconv_phases || L.stride2 || L.conv7v || L.stats_part))
         return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: the pair gate is an epilogue of the plain 64-row slab conv (32 gated outputs per 64 rows)");
-    if (L.act < 0 || L.act > 12 || (L.phase_c > 0 && (L.K % L.phase_c || L.K / L.phase_c != 4)))
+    if (L.act < 0 || L.act > 13 || (L.phase_c > 0 && (L.K % L.phase_c || L.K / L.phase_c != 4)))
         return set_error(INNFER_ERR_INVALID, "conv3x3: act=%d phase_c=%d K=%d", L.act, L.phase_c, L.K);
     k.act = L.act;
     k.res1 = L.res1; k.res1_gstride = L.res1_gstride; k.s1 = L.s1;
@@ -1120,6 +1121,14 @@ int conv_launch(const ConvLaunch& L, hipStream_t s) {
             return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: act 12 (GELU) is built as the epilogue of the 1x1 slab conv of 64 outputs -- not the 3x3 / 32-output / split / "
                                                      "statistics / gate / running-sum / planar / phase / stride-2 / dilated forms, no residual, upsampling or reflection padding");
         return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_1X1 | PC_GELU, false, 3>(k, L.N, s);
+    }
+    if (L.act == 13) {        // exact GELU behind a 3x3 conv: conv3x3_pc<.., TAPS_3X3 | PC_GELU>, the plain nine-tap slab kernel of 64 outputs
+        if (L.out_mode != OUT_SLAB || nt != 4 || L.K != 64 || L.conv1x1 || L.split || L.stats_part || L.gate_w || L.prefix_lrelu || L.deconv_phases || L.stride2 ||
+            L.conv7v || L.conv7 || L.fuse_w || L.dilation > 1 || L.dilation_groups || L.in_relu || L.res1 || L.res2 || L.up || L.reflect || L.phase_c || L.outm || L.out_u8 || L.rowp ||
+            (L.out_coff & 31))
+            return set_error(INNFER_ERR_UNSUPPORTED, "conv3x3: act 13 (GELU) is built as the epilogue of the plain 3x3 slab conv of 64 outputs -- not the 1x1 (act 12) / 32-output / split / "
+                                                     "statistics / gate / plane-order / planar / phase / stride-2 / dilated / fused-last forms, no residual, upsampling or reflection padding");
+        return launch_pc<2, 4, 4, OUT_SLAB, false, false, TAPS_3X3 | PC_GELU>(k, L.N, s);
     }
     if (L.rowp && !(L.rowp == 2 && L.out_mode == OUT_SHUFFLE2) && (nt != 4 || L.out_mode != OUT_SLAB || L.split || L.stats_part || L.stride2 || L.conv1x1 || L.conv7 || L.conv7v || L.prefix_lrelu ||
                    L.gate_w || L.act > 2 || L.dilation > 1 || L.dilation_groups || (L.out_coff & 31)))

@@ -125,6 +125,14 @@ struct innfer_net {
     int sw_c = 0, sw_cp = 0, sw_nh = 0, sw_d = 0, sw_hid = 0, sw_hp = 0, sw_tail = 0, sw_conv3 = 0, sw_c4p = 0;
     std::vector<int> sw_depths;
     std::vector<float*> sw_ln, sw_relb;
+    // HAT (kind 6; innfer_hat_create) on SwinIR's fields: 16 x 16 windows; per HAB the conv block's two 3x3 convs (C -> hat_cc <= 64 -> C) and its channel attention
+    // (hat_ca[blk]: W1 [hat_sq][C], b1 [hat_sq], W2 [C][hat_sq], b2 [C]; innfer_net_set_chan_attn), weighted by hat_scale (conv_scale; innfer_net_set_conv_scale); per
+    // residual group one OCAB behind its HABs.  sw_ln and sw_relb hold their entries in forward order: per group (norm1, norm2) / the [nH][256][256] table of every HAB, then
+    // (norm1, norm2) / the [nH][256][576] table of the OCAB; sw_relb_kw: the key window of each table (16 | 24).
+    int hat_cc = 0, hat_sq = 0;
+    float hat_scale = 0.01f;
+    std::vector<float*> hat_ca;
+    std::vector<int> sw_relb_kw;
     bool span_norm = false;      // SPAN(norm=True): conv_1 reads (x - mean) * img_range through FirstConvLaunch.in_map (convs[0].d_map: alpha[in_nc] then shift[in_nc])
     int in_nc = 3, out_nc = 3, nf = 64, nb = 23, gc = 32, scale = 4, n_up = 2;
     int final_act = 0;           // `finalact` of the reference constructors: activation after the last conv (ConvLaunch.act codes)
@@ -445,7 +453,7 @@ extern "C" int innfer_swinir_create(innfer_net_t* out, int in_nc, int out_nc, in
 // groups), the last one norm.  Load time, synchronous.
 extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float* h_gamma, const float* h_beta) {
     if (!net || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "set_layer_norm: null argument");
-    if (net->kind != 5) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR)");
+    if (net->kind != 5 && net->kind != 6) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR, HAT)");
     if (idx < 0 || idx >= (int)net->sw_ln.size()) return set_error(INNFER_ERR_INVALID, "set_layer_norm: index %d of %zu", idx, net->sw_ln.size());
     std::vector<float> h(2 * (size_t)net->sw_cp, 0.f);
     for (int c = 0; c < net->sw_c; ++c) { h[c] = h_gamma[c]; h[net->sw_cp + c] = h_beta[c]; }
@@ -457,11 +465,110 @@ extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float*
 // The relative position bias of block `blk` of a SwinIR as the dense table the attention reads: [num_heads][64 query][64 key] host floats.  Load time, synchronous.
 extern "C" int innfer_net_set_attn_bias(innfer_net_t net, int blk, const float* h_bias) {
     if (!net || !h_bias) return set_error(INNFER_ERR_INVALID, "set_attn_bias: null argument");
-    if (net->kind != 5) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_bias: the network has no window attention (built: SwinIR)");
+    if (net->kind != 5 && net->kind != 6) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_bias: the network has no window attention (built: SwinIR, HAT)");
     if (blk < 0 || blk >= (int)net->sw_relb.size()) return set_error(INNFER_ERR_INVALID, "set_attn_bias: block %d of %zu", blk, net->sw_relb.size());
-    const size_t nb = (size_t)net->sw_nh * 4096 * sizeof(float);
+    // (HAT: table `blk` in forward order -- [num_heads][256][256] of a HAB, [num_heads][256][576] of a residual group's OCAB)
+    const size_t nb = (size_t)net->sw_nh * (net->kind == 6 ? 256 * (size_t)net->sw_relb_kw[blk] * net->sw_relb_kw[blk] : 4096) * sizeof(float);
     if (!net->sw_relb[blk]) INNFER_HIP(hipMalloc((void**)&net->sw_relb[blk], nb));
     INNFER_HIP(hipMemcpy(net->sw_relb[blk], h_bias, nb, hipMemcpyHostToDevice));
+    return INNFER_OK;
+}
+
+// HAT (Chen et al. 2023; include/innfer_amd.h carries the definition) on SwinIR's skeleton with 16 x 16 windows: per HAB the conv block (two 3x3 convs around a GELU, channel
+// attention) beside the window attention, per residual group one overlapping cross-attention block behind its HABs.  Conv slots in forward order; keys as SwinIR's.
+extern "C" int innfer_hat_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int compress_ch,
+                                 int squeeze_ch, int scale, const float* h_mean) {
+    if (!out || !depths) return set_error(INNFER_ERR_INVALID, "hat_create: null argument");
+    if (embed_dim < 1 || embed_dim > 256 || num_heads < 1 || num_heads > 8 || embed_dim % num_heads || embed_dim / num_heads > 32)
+        return set_error(INNFER_ERR_UNSUPPORTED, "hat_create: embed_dim=%d num_heads=%d (built: embed_dim <= 256, <= 8 heads of <= 32 channels, embed_dim %% num_heads == 0)", embed_dim, num_heads);
+    if (mlp_hidden < 1 || mlp_hidden > 1024) return set_error(INNFER_ERR_UNSUPPORTED, "hat_create: an MLP of %d hidden channels (built: <= 1024)", mlp_hidden);
+    if (compress_ch < 1 || compress_ch > 64 || squeeze_ch < 1 || squeeze_ch > 64)
+        return set_error(INNFER_ERR_UNSUPPORTED, "hat_create: a conv block of %d channels, a channel attention of %d (built: 1 .. 64 each)", compress_ch, squeeze_ch);
+    if (in_nc < 1 || in_nc > 4 || in_nc != out_nc) return set_error(INNFER_ERR_UNSUPPORTED, "hat_create: in_chans=%d, %d output channels (built: equal, 1..4)", in_nc, out_nc);
+    if (n_layers < 1 || n_layers > 64) return set_error(INNFER_ERR_UNSUPPORTED, "hat_create: %d residual groups", n_layers);
+    for (int i = 0; i < n_layers; ++i)
+        if (depths[i] < 1 || depths[i] > 64) return set_error(INNFER_ERR_UNSUPPORTED, "hat_create: depth %d of residual group %d", depths[i], i);
+    if (scale < 2 || scale > 4) return set_error(INNFER_ERR_UNSUPPORTED, "hat_create: scale %d (built: 2, 3, 4 -- the pixelshuffle tail)", scale);
+    innfer_net* net = new innfer_net();
+    net->kind = 6; net->in_nc = in_nc; net->out_nc = out_nc; net->nf = 64; net->nb = 0; net->gc = 0; net->scale = scale; net->n_up = 0;
+    net->sw_c = embed_dim; net->sw_cp = (embed_dim + 63) / 64 * 64; net->sw_nh = num_heads; net->sw_d = embed_dim / num_heads;
+    net->sw_hid = mlp_hidden; net->sw_hp = (mlp_hidden + 63) / 64 * 64; net->sw_tail = 0; net->sw_conv3 = 0;
+    net->hat_cc = compress_ch; net->hat_sq = squeeze_ch;
+    net->sw_depths.assign(depths, depths + n_layers);
+    const int cp = net->sw_cp;
+    for (int p = 0; p < cp / 64; ++p) add_conv(net, "conv_first#" + std::to_string(p), 64, in_nc, true);
+    auto attn_mlp = [&](const std::string& b, const std::string& a) {
+        swin_add_sliced(net, b + a + "qkv", (3 * num_heads + 1) / 2 * 64, cp, 1);
+        swin_add_sliced(net, b + a + "proj", cp, 32 * num_heads, 1);
+        swin_add_sliced(net, b + "mlp.fc1", net->sw_hp, cp, 1);
+        swin_add_sliced(net, b + "mlp.fc2", cp, net->sw_hp, 1);
+    };
+    for (int i = 0; i < n_layers; ++i) {
+        const std::string g = "layers." + std::to_string(i) + ".residual_group.";
+        for (int j = 0; j < depths[i]; ++j) {
+            const std::string b = g + "blocks." + std::to_string(j) + ".";
+            swin_add_sliced(net, b + "conv_block.cab.0", 64, cp, 3);
+            net->convs.back().lane_rows = true;          // (act 13 is an epilogue of the lane-contiguous panels only)
+            swin_add_sliced(net, b + "conv_block.cab.2", cp, 64, 3);
+            attn_mlp(b, "attn.");
+            net->sw_relb_kw.push_back(16);
+            net->nb++;
+        }
+        attn_mlp(g + "overlap_attn.", "");              // (overlap_attn.qkv / .proj / .mlp.fc1 / .mlp.fc2)
+        net->sw_relb_kw.push_back(24);
+        swin_add_sliced(net, "layers." + std::to_string(i) + ".conv", cp, cp, 3);
+    }
+    swin_add_sliced(net, "conv_after_body", cp, cp, 3);
+    add_conv(net, "conv_before_upsample.0", 64, cp);
+    net->convs.back().slope_ok = true;
+    if (scale == 3) add_conv(net, "upsample.0", 576, 64);
+    else {
+        add_conv(net, "upsample.0", 256, 64); net->convs.back().ps2 = true;
+        if (scale == 4) { add_conv(net, "upsample.2", 256, 64); net->convs.back().ps2 = true; net->convs.back().mult = 4.f; }
+    }
+    add_conv(net, "conv_last", out_nc, 64); net->convs.back().mult = (float)(scale * scale);
+    net->sw_ln.assign(2 + 2 * ((size_t)net->nb + n_layers), nullptr);
+    net->sw_relb.assign(net->sw_relb_kw.size(), nullptr);
+    net->hat_ca.assign((size_t)net->nb, nullptr);
+    int rc = INNFER_OK;
+    {   // x - mean in front of conv_first and nn.LeakyReLU() (slope 0.01) behind conv_before_upsample, as innfer_swinir_create
+        float h[8];
+        for (int c = 0; c < in_nc; ++c) { h[c] = 1.f; h[in_nc + c] = h_mean ? -h_mean[c] : 0.f; }
+        ConvSlot& c0 = net->convs[0];
+        if (hipMalloc((void**)&c0.d_map, 2 * in_nc * sizeof(float)) != hipSuccess || hipMemcpy(c0.d_map, h, 2 * in_nc * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            rc = set_error(INNFER_ERR_NOMEM, "hat_create: no device memory for the input map");
+        for (size_t i = 0; i < net->convs.size() && rc == INNFER_OK; ++i)
+            if (net->convs[i].slope_ok) {
+                const std::vector<float> sl(64, 0.01f);
+                rc = innfer_net_set_conv_slope(net, (int)i, sl.data());
+            }
+    }
+    if (rc != INNFER_OK) { (void)hipGetLastError(); innfer_net_destroy(net); return rc; }
+    *out = net;
+    return INNFER_OK;
+}
+
+// The channel attention of HAB `blk` of a HAT (blocks counted through the residual groups): the two 1x1 convs behind the pool as host floats, W1 [squeeze_ch][C], b1
+// [squeeze_ch], W2 [C][squeeze_ch], b2 [C].  Load time, synchronous.
+extern "C" int innfer_net_set_chan_attn(innfer_net_t net, int blk, const float* h_w1, const float* h_b1, const float* h_w2, const float* h_b2) {
+    if (!net || !h_w1 || !h_b1 || !h_w2 || !h_b2) return set_error(INNFER_ERR_INVALID, "set_chan_attn: null argument");
+    if (net->kind != 6) return set_error(INNFER_ERR_UNSUPPORTED, "set_chan_attn: the network has no channel attention (built: HAT)");
+    if (blk < 0 || blk >= (int)net->hat_ca.size()) return set_error(INNFER_ERR_INVALID, "set_chan_attn: block %d of %zu", blk, net->hat_ca.size());
+    const size_t C = (size_t)net->sw_c, q = (size_t)net->hat_sq;
+    std::vector<float> h;
+    h.insert(h.end(), h_w1, h_w1 + q * C); h.insert(h.end(), h_b1, h_b1 + q);
+    h.insert(h.end(), h_w2, h_w2 + C * q); h.insert(h.end(), h_b2, h_b2 + C);
+    if (!net->hat_ca[blk]) INNFER_HIP(hipMalloc((void**)&net->hat_ca[blk], h.size() * sizeof(float)));
+    INNFER_HIP(hipMemcpy(net->hat_ca[blk], h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+    return INNFER_OK;
+}
+
+// conv_scale of a HAT: the weight of the conv block beside the attention (a constructor argument of the published code, not in the state dict; 0.01 by default)
+extern "C" int innfer_net_set_conv_scale(innfer_net_t net, float conv_scale) {
+    if (!net) return set_error(INNFER_ERR_INVALID, "set_conv_scale: null argument");
+    if (net->kind != 6) return set_error(INNFER_ERR_UNSUPPORTED, "set_conv_scale: the network has no conv block (built: HAT)");
+    if (!(conv_scale == conv_scale) || std::fabs(conv_scale) > 65504.f) return set_error(INNFER_ERR_INVALID, "set_conv_scale: %g", (double)conv_scale);
+    net->hat_scale = conv_scale;
     return INNFER_OK;
 }
 
@@ -502,6 +609,7 @@ extern "C" void innfer_net_destroy(innfer_net_t net) {
     if (!net) return;
     for (float* q : net->sw_ln) if (q) (void)hipFree(q);
     for (float* q : net->sw_relb) if (q) (void)hipFree(q);
+    for (float* q : net->hat_ca) if (q) (void)hipFree(q);
     for (auto& c : net->convs) {
         if (c.d_w) (void)hipFree(c.d_w);
         if (c.d_b) (void)hipFree(c.d_b);
@@ -663,6 +771,7 @@ extern "C" int innfer_net_set_precision(innfer_net_t net, int fp32) {
     if (fp32 && net->kind == 3) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SPAN is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 4) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: RealPLKSR is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 5) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SwinIR is built for the fp16 mode only (no fp32-accurate engine)");
+    if (fp32 && net->kind == 6) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: HAT is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32) {
         // The (wl | wh | wh) panels of every loaded conv are built HERE -- a load-time call, with its hipMalloc and synchronous copies -- never inside
         // innfer_net_forward (stream capture, concurrent callers).  Idempotent: a conv that already has its panels is skipped; innfer_net_set_conv
@@ -743,6 +852,12 @@ extern "C" double innfer_net_flops(innfer_net_t net, int N, int H, int W) {
         for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
         return f;
     }
+    if (net->kind == 6) {        // HAT: as SwinIR on the grid padded to 16; 256 x 256 scores per window and head in a HAB, 256 x 576 in an OCAB
+        const double px = (double)N * ((H + 15) / 16 * 16) * ((W + 15) / 16 * 16);
+        double f = net->sw_nh * (px / 256) * 4.0 * 256 * 32 * (256.0 * net->nb + 576.0 * net->sw_depths.size());
+        for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
+        return f;
+    }
     H = (H + net->unshuffle - 1) / net->unshuffle; W = (W + net->unshuffle - 1) / net->unshuffle;      // the LR grid
     double px = (double)N * H * W, f = 0.0;
     const int nconv = (int)net->convs.size();
@@ -778,10 +893,12 @@ struct Carve {
 // SwinIR's workspace (kind 5) on the padded grid Hp x Wp: the padded input, the first conv's result (the last shortcut), two buffers the residual groups alternate between,
 // the token stream, the normalised tokens, the qkv slab (head-padded), the attention's result (head-padded), the MLP's hidden slab, the two C / 4 buffers of '3conv',
 // the tail's slabs, and the full-size result in front of the crop.
-struct SwinCarve { size_t xin, f0, r[2], t, u, qkv, att, hid, c4[2], b64, up[2], hr, outp, total; int Hp, Wp; };
+// HAT (kind 6) pads to multiples of 16 and adds the conv block's 64-channel slab, its C_pad-channel result z, the channel attention's vector and the segment sums.
+struct SwinCarve { size_t xin, f0, r[2], t, u, qkv, att, hid, c4[2], b64, up[2], hr, outp, zc, z, y, pool, total; int Hp, Wp; };
 static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
     SwinCarve c{};
-    c.Hp = (H + 7) / 8 * 8; c.Wp = (W + 7) / 8 * 8;
+    const int wsz = net->kind == 6 ? 16 : 8;
+    c.Hp = (H + wsz - 1) / wsz * wsz; c.Wp = (W + wsz - 1) / wsz * wsz;
     const size_t px = (size_t)N * c.Hp * c.Wp, s2 = (size_t)net->scale * net->scale;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     size_t off = 0;
@@ -803,13 +920,19 @@ static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
         if (net->sw_tail == 2) c.hr = take(px * s2 * 64 * 2);
     }
     c.outp = take(px * s2 * net->out_nc * 4);
+    if (net->kind == 6) {
+        c.zc = take(px * 64 * 2);
+        c.z = take(px * net->sw_cp * 2);
+        c.y = take((size_t)N * net->sw_cp * 4);
+        c.pool = take(ca_work_floats(N, (long)c.Hp * c.Wp, net->sw_cp) * 4);
+    }
     c.total = off;
     return c;
 }
 
 static Carve carve(const innfer_net* net, int N, int H, int W) {
     Carve c{};
-    if (net->kind == 5) { c.total = swin_carve(net, N, H, W).total; return c; }
+    if (net->kind == 5 || net->kind == 6) { c.total = swin_carve(net, N, H, W).total; return c; }
     const size_t px = (size_t)N * H * W;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     if (net->kind == 2) {        // SRVGGNetCompact: the two ping-pong feature slabs (one when there is no nf -> nf conv) and the last conv's 32- / 64-channel slab
@@ -1415,6 +1538,56 @@ static int swinir_forward(innfer_net* net, const void* d_in, int in_dtype, void*
     }
     int cur = 0, blk = 0;
     if (int rc = norm(0, f0, r[0])) return rc;
+    if (net->kind == 6) {
+        // HAT: per HAB  u = LN(t); z = cab.2(GELU(cab.0(u))) (act 13: one launch, then C_pad / 64); the channel sums of z and the squeeze / excite vector y; qkv; the 16 x 16
+        // window attention (shift 8 for odd j); proj + shortcut -> t; t += conv_scale y z; u = LN(t); fc1 with GELU; fc2 + shortcut.  Per residual group, behind its HABs,
+        // the OCAB: u = LN(t); qkv; the overlapping attention (24 x 24 keys); proj + shortcut; u = LN(t); fc1; fc2 + shortcut.  Then r' = conv(t) + r.
+        for (size_t i = 0; i < net->hat_ca.size(); ++i)
+            if (!net->hat_ca[i]) return set_error(INNFER_ERR_INVALID, "forward: the channel attention of block %zu was never set (innfer_net_set_chan_attn)", i);
+        f16* zc = (f16*)(ws + cv.zc);
+        f16* z = (f16*)(ws + cv.z);
+        float* y = (float*)(ws + cv.y);
+        float* pool = (float*)(ws + cv.pool);
+        const long HWp = (long)Hp * Wp;
+        const int C = net->sw_c, sq = net->hat_sq;
+        int ln = 1, tb = 0;
+        auto attn = [&](int kw, int shift) {
+            // launch kind 8001: the window attention -- bytes: q, k, v in, o out (32-channel head groups), the bias table
+            const double nk = (double)kw * kw;
+            return plksr_pass(s, kw == 16 ? "window_attention16" : "overlap_attention", 4.0 * nk * 32 * nh * px, px * nh * 256.0 + nh * 1024.0 * nk, 8001,
+                              [&] { return win_attn16_launch(qkv, G, att, G, net->sw_relb[tb], N, Hp, Wp, nh, net->sw_d, shift, kw, s); });
+        };
+        for (size_t i = 0; i < net->sw_depths.size(); ++i) {
+            for (int j = 0; j < net->sw_depths[i]; ++j, ++blk, ++tb) {
+                const f16* x = j == 0 ? r[cur] : t;
+                if (int rc = norm(ln++, x, u)) return rc;
+                if (int rc = sliced(1, u, zc, 13, nullptr)) return rc;
+                if (int rc = sliced(cp / 64, zc, z, 0, nullptr)) return rc;
+                const float* ca = net->hat_ca[blk];
+                // launch kinds 8005 / 8006 / 8007: the channel sums, the squeeze / excite vector, the scale-add pass
+                if (int rc = plksr_pass(s, "chan_attn_pool", px * cp, px * cp * 2.0, 8005, [&] { return ca_pool_launch(z, G, N, HWp, cp, pool, s); })) return rc;
+                if (int rc = plksr_pass(s, "chan_attn_excite", 4.0 * C * sq * N, 4.0 * (double)ca_work_floats(N, HWp, cp), 8006, [&] {
+                        return ca_excite_launch(pool, N, HWp, C, cp, sq, ca, ca + (long)sq * C, ca + (long)sq * C + sq, ca + 2L * sq * C + sq, y, nullptr, s); })) return rc;
+                if (int rc = sliced((3 * nh + 1) / 2, u, qkv, 0, nullptr)) return rc;
+                if (int rc = attn(16, (j & 1) ? 8 : 0)) return rc;
+                if (int rc = sliced(cp / 64, att, t, 0, x)) return rc;
+                if (int rc = plksr_pass(s, "chan_attn_scale_add", 2.0 * px * cp, px * cp * 6.0, 8007, [&] { return ca_scale_add_launch(t, G, z, G, y, net->hat_scale, N, HWp, cp, s); })) return rc;
+                if (int rc = norm(ln++, t, u)) return rc;
+                if (int rc = sliced(net->sw_hp / 64, u, hid, 12, nullptr)) return rc;
+                if (int rc = sliced(cp / 64, hid, t, 0, t)) return rc;
+            }
+            if (int rc = norm(ln++, t, u)) return rc;
+            if (int rc = sliced((3 * nh + 1) / 2, u, qkv, 0, nullptr)) return rc;
+            if (int rc = attn(24, 0)) return rc;
+            ++tb;
+            if (int rc = sliced(cp / 64, att, t, 0, t)) return rc;
+            if (int rc = norm(ln++, t, u)) return rc;
+            if (int rc = sliced(net->sw_hp / 64, u, hid, 12, nullptr)) return rc;
+            if (int rc = sliced(cp / 64, hid, t, 0, t)) return rc;
+            if (int rc = resi(t, r[cur ^ 1], r[cur])) return rc;
+            cur ^= 1;
+        }
+    } else
     for (size_t i = 0; i < net->sw_depths.size(); ++i) {
         for (int j = 0; j < net->sw_depths[i]; ++j, ++blk) {
             const f16* x = j == 0 ? r[cur] : t;
@@ -1552,7 +1725,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     if (ws_bytes < cv.total) return set_error(INNFER_ERR_WORKSPACE, "forward: workspace %zu < %zu bytes", ws_bytes, cv.total);
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)d_ws;
-    if (net->kind == 5) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);
+    if (net->kind == 5 || net->kind == 6) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);
     if (net->kind == 2) return compact_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 3) return span_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 4) return plksr_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
@@ -1964,6 +2137,51 @@ extern "C" int innfer_window_attention(const void* d_qkv, int64_t qkv_gs, void* 
     if (rc == INNFER_OK) rc = win_attn_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, d_b, N, Hp, Wp, num_heads, head_dim, shift, (hipStream_t)stream);
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "window_attention: the launch failed");
     (void)hipFree(d_b);
+    return rc;
+}
+
+// HAT's 16 x 16 window attention alone (key window 16: self, shift 0 | 8; 24: overlapping), for tests: win_attn16_launch, the code the network runs.  Uploads, launches, waits.
+extern "C" int innfer_window_attention16(const void* d_qkv, int64_t qkv_gs, void* d_out, int64_t out_gs, const float* h_bias, int N, int Hp, int Wp, int num_heads, int head_dim,
+                                         int shift, int key_window, void* stream) {
+    if (!d_qkv || !d_out || !h_bias) return set_error(INNFER_ERR_INVALID, "window_attention16: null argument");
+    if (num_heads < 1 || num_heads > 8) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention16: %d heads (built: 1 .. 8)", num_heads);
+    if (key_window != 16 && key_window != 24) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention16: a key window of %d (built: 16, 24)", key_window);
+    float* d_b = nullptr;
+    const size_t nb = (size_t)num_heads * 256 * key_window * key_window * sizeof(float);
+    if (hipMalloc((void**)&d_b, nb) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "window_attention16: out of device memory");
+    int rc = hipMemcpy(d_b, h_bias, nb, hipMemcpyHostToDevice) == hipSuccess ? INNFER_OK : set_error(INNFER_ERR_HIP, "window_attention16: copying the bias table failed");
+    if (rc == INNFER_OK) rc = win_attn16_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, d_b, N, Hp, Wp, num_heads, head_dim, shift, key_window, (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "window_attention16: the launch failed");
+    (void)hipFree(d_b);
+    return rc;
+}
+
+// HAT's channel attention alone, for tests (chan_attn.hip, the code the network runs): the channel sums + the squeeze / excite vector, and the scale-add pass.
+extern "C" size_t innfer_chan_attn_work_bytes(int N, int64_t HW, int c_pad) { return (N > 0 && HW > 0 && c_pad > 0) ? ca_work_floats(N, (long)HW, c_pad) * sizeof(float) : 0; }
+extern "C" int innfer_chan_attn_excite(const void* d_z, int64_t z_gs, int N, int64_t HW, int C, int c_pad, int hidden, const float* h_w1, const float* h_b1, const float* h_w2,
+                                       const float* h_b2, void* d_y, void* d_sums, void* d_work, size_t work_bytes, void* stream) {
+    if (!d_z || !h_w1 || !h_b1 || !h_w2 || !h_b2 || !d_y || !d_work) return set_error(INNFER_ERR_INVALID, "chan_attn_excite: null argument");
+    if (N <= 0 || HW <= 0 || C < 1 || C > 256 || c_pad < C || c_pad > 256 || c_pad % 64 || hidden < 1 || hidden > 64)
+        return set_error(INNFER_ERR_UNSUPPORTED, "chan_attn_excite: N=%d HW=%ld C=%d c_pad=%d hidden=%d (built: C <= c_pad in 64, 128, 192, 256; hidden <= 64)", N, (long)HW, C, c_pad, hidden);
+    if (work_bytes < innfer_chan_attn_work_bytes(N, HW, c_pad)) return set_error(INNFER_ERR_WORKSPACE, "chan_attn_excite: work buffer %zu < %zu bytes", work_bytes, innfer_chan_attn_work_bytes(N, HW, c_pad));
+    std::vector<float> h;
+    h.insert(h.end(), h_w1, h_w1 + (size_t)hidden * C); h.insert(h.end(), h_b1, h_b1 + hidden);
+    h.insert(h.end(), h_w2, h_w2 + (size_t)C * hidden); h.insert(h.end(), h_b2, h_b2 + C);
+    float* d_p = nullptr;
+    if (hipMalloc((void**)&d_p, h.size() * sizeof(float)) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "chan_attn_excite: out of device memory");
+    int rc = hipMemcpy(d_p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? INNFER_OK : set_error(INNFER_ERR_HIP, "chan_attn_excite: copying the weights failed");
+    hipStream_t s = (hipStream_t)stream;
+    if (rc == INNFER_OK) rc = ca_pool_launch((const f16*)d_z, (long)z_gs, N, (long)HW, c_pad, (float*)d_work, s);
+    if (rc == INNFER_OK) rc = ca_excite_launch((const float*)d_work, N, (long)HW, C, c_pad, hidden, d_p, d_p + (size_t)hidden * C, d_p + (size_t)hidden * C + hidden,
+                                               d_p + 2 * (size_t)hidden * C + hidden, (float*)d_y, (float*)d_sums, s);
+    if (hipStreamSynchronize(s) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "chan_attn_excite: the launch failed");
+    (void)hipFree(d_p);
+    return rc;
+}
+extern "C" int innfer_chan_attn_scale_add(void* d_t, int64_t t_gs, const void* d_z, int64_t z_gs, const void* d_y, float conv_scale, int N, int64_t HW, int c_pad, void* stream) {
+    if (!d_t || !d_z || !d_y) return set_error(INNFER_ERR_INVALID, "chan_attn_scale_add: null argument");
+    int rc = ca_scale_add_launch((f16*)d_t, (long)t_gs, (const f16*)d_z, (long)z_gs, (const float*)d_y, conv_scale, N, (long)HW, c_pad, (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "chan_attn_scale_add: the launch failed");
     return rc;
 }
 

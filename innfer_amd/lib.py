@@ -207,6 +207,13 @@ SIGNATURES = {
     "innfer_net_set_attn_bias": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_window_attention": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     "innfer_layer_norm": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "innfer_hat_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "innfer_net_set_chan_attn": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    "innfer_net_set_conv_scale": (C.c_int, [C.c_void_p, C.c_float]),
+    "innfer_window_attention16": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]),
+    "innfer_chan_attn_work_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+    "innfer_chan_attn_excite": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "innfer_chan_attn_scale_add": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
     "innfer_plk_conv": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p]),
     "innfer_group_norm_skip_work_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "innfer_group_norm_skip": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,

@@ -62,7 +62,8 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
     if arch == 'realplksr':
         return _infer_realplksr(state_dict)
     if arch == 'swinir':
-        return _infer_swinir(state_dict)
+        hat = _infer_hat(state_dict)         # (a complete HAT key set; anything less goes on to SwinIR's sniffing and its refusals)
+        return hat if hat is not None else _infer_swinir(state_dict)
     if arch == 'pan':
         return _infer_pan(state_dict, scale, in_nc, out_nc)
     if arch == 'ppon':
@@ -267,6 +268,87 @@ def _infer_swinir(state_dict):
     cfg = {'type': 'swinir', 'in_nc': in_nc, 'nf': C, 'depths': depths, 'num_heads': [nh] * len(depths), 'window_size': ws, 'mlp_ratio': hidden / C, 'scale': up,
            'upsampler': upsampler, 'resi_connection': '3conv' if 'layers.0.conv.0.weight' in state_dict else '1conv'}
     return dict(arch='swinir', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=sum(depths), plus=False, state_dict=state_dict,
+                net_params=get_network_G_config(cfg, up))
+
+
+_HAT_KEYS = ('layers.0.residual_group.blocks.0.conv_block.cab.0.weight', 'layers.0.residual_group.blocks.0.conv_block.cab.2.weight',
+             'layers.0.residual_group.blocks.0.conv_block.cab.3.attention.1.weight', 'layers.0.residual_group.blocks.0.conv_block.cab.3.attention.3.weight',
+             'layers.0.residual_group.overlap_attn.qkv.weight', 'layers.0.residual_group.overlap_attn.norm1.weight',
+             'layers.0.residual_group.overlap_attn.relative_position_bias_table', 'layers.0.residual_group.blocks.0.attn.relative_position_bias_table')
+
+
+def _infer_hat(state_dict):
+    """HAT checkpoints (HAT-S, HAT, HAT-L, Real_HAT_GAN_SRx4 and fine-tunes), or None when the complete HAT key set (_HAT_KEYS) is not there -- the caller then sniffs as
+    before.  embed_dim and in_chans from conv_first, depths by counting blocks, num_heads and the window from the self-attention's bias table, the overlapping window from
+    the OCAB's (side = ws + ows - 1), compress_ratio / squeeze_factor from the conv block's shapes, mlp_ratio from mlp.fc1, the scale from upsample.*.  conv_scale is not in
+    a state dict: 0.01, as in every published model (net_params takes another).  The two index buffers (relative_position_index_SA / _OCA) are taken out of the state dict
+    handed back and passed on as rpi_sa / rpi_oca: when present they are what the dense bias tables are built from.  DRCT, an absolute position embedding, a window other
+    than 16 / 24, a checkpoint without patch_embed.norm or qkv biases and unbuilt sizes are refused."""
+    import math
+    if any(k not in state_dict for k in _HAT_KEYS):
+        return None
+    b0, o0 = 'layers.0.residual_group.blocks.0.', 'layers.0.residual_group.overlap_attn.'
+    if any(k.endswith('attn.logit_scale') for k in state_dict):
+        raise NotImplementedError('HAT-like checkpoint with attn.logit_scale (cosine attention): not built on the HIP path')
+    if any('.swin_DRCT' in k or '.adjust' in k or '.swin1.' in k for k in state_dict):
+        raise NotImplementedError('DRCT checkpoint (dense-residual Swin blocks): not built on the HIP path')
+    if 'absolute_pos_embed' in state_dict:
+        raise NotImplementedError('HAT checkpoint with absolute_pos_embed (ape=True): not built on the HIP path')
+    if 'patch_embed.norm.weight' not in state_dict:
+        raise NotImplementedError('HAT checkpoint without patch_embed.norm (patch_norm=False): not built on the HIP path')
+    if b0 + 'attn.qkv.bias' not in state_dict or o0 + 'qkv.bias' not in state_dict:
+        raise NotImplementedError('HAT checkpoint without qkv biases (qkv_bias=False): not built on the HIP path')
+    for k in ('conv_first.weight', b0 + 'attn.qkv.weight', b0 + 'mlp.fc1.weight', 'conv_before_upsample.0.weight', 'conv_last.weight'):
+        if k not in state_dict:
+            if k.startswith('conv_before') or k == 'conv_last.weight':
+                raise NotImplementedError('HAT checkpoint without the pixelshuffle tail (conv_before_upsample / conv_last): not built on the HIP path')
+            raise Exception("Could not infer model parameters.")
+    w0 = state_dict['conv_first.weight']
+    C, in_nc = int(w0.shape[0]), int(w0.shape[1])
+    depths = []
+    while f'layers.{len(depths)}.residual_group.blocks.0.norm1.weight' in state_dict:
+        i, j = len(depths), 0
+        while f'layers.{i}.residual_group.blocks.{j}.norm1.weight' in state_dict:
+            j += 1
+        depths.append(j)
+    table, otable = state_dict[b0 + 'attn.relative_position_bias_table'], state_dict[o0 + 'relative_position_bias_table']
+    nh, side, oside = int(table.shape[1]), math.isqrt(int(table.shape[0])), math.isqrt(int(otable.shape[0]))
+    ws = (side + 1) // 2
+    ows = oside + 1 - ws
+    if side * side != int(table.shape[0]) or 2 * ws - 1 != side or oside * oside != int(otable.shape[0]) or not depths:
+        raise Exception("Could not infer model parameters.")
+    if ws != 16 or ows != 24:
+        raise NotImplementedError(f'HAT checkpoint with window_size {ws} and an overlapping window of {ows}: only 16 / 24 are built on the HIP path')
+    if 'layers.0.conv.0.weight' in state_dict or 'layers.0.conv.weight' not in state_dict:
+        raise NotImplementedError("HAT checkpoint with a resi_connection other than '1conv': not built on the HIP path")
+    cc, sq = int(state_dict[_HAT_KEYS[0]].shape[0]), int(state_dict[_HAT_KEYS[2]].shape[0])
+    hidden = int(state_dict[b0 + 'mlp.fc1.weight'].shape[0])
+    if not (1 <= cc <= 64 and 1 <= sq <= 64):
+        raise NotImplementedError(f'HAT checkpoint: a conv block of {cc} channels and a channel attention of {sq} (built on the HIP path: 1 .. 64 each)')
+    up = 1
+    for k, v in state_dict.items():
+        if k.startswith('upsample.') and k.endswith('.weight'):
+            f = math.isqrt(int(v.shape[0]) // 64)
+            if f * f * 64 != int(v.shape[0]):
+                raise Exception("Could not infer model parameters.")
+            up *= f
+    out_nc = int(state_dict['conv_last.weight'].shape[0])
+    if out_nc != in_nc:
+        raise NotImplementedError(f'HAT checkpoint: conv_last has {out_nc} channels, conv_first takes {in_nc} (unequal channel counts are not built on the HIP path)')
+    rpi = {}
+    for name, shape in (('relative_position_index_SA', (ws * ws, ws * ws)), ('relative_position_index_OCA', (ws * ws, ows * ows))):
+        if name in state_dict:
+            v = state_dict[name]
+            if tuple(v.shape) != shape:
+                raise NotImplementedError(f'HAT checkpoint: {name} has shape {tuple(v.shape)}, not {shape}')
+            rpi[name] = v.cpu().long().numpy()
+    state_dict = {k: v for k, v in state_dict.items() if k not in rpi and not k.endswith('.attn_mask')}
+    # compress_ratio / squeeze_factor: C / n where it divides, else the smallest ratio that gives the stored channel count (C // ratio)
+    ratio = lambda n: C // n if C % n == 0 else next(r for r in range(1, C + 1) if C // r == n)
+    cfg = {'type': 'hat', 'in_nc': in_nc, 'nf': C, 'depths': depths, 'num_heads': [nh] * len(depths), 'window_size': ws, 'compress_ratio': ratio(cc), 'squeeze_factor': ratio(sq),
+           'conv_scale': 0.01, 'overlap_ratio': (ows - ws) / ws, 'mlp_ratio': hidden / C, 'scale': up, 'upsampler': 'pixelshuffle', 'resi_connection': '1conv',
+           'rpi_sa': rpi.get('relative_position_index_SA'), 'rpi_oca': rpi.get('relative_position_index_OCA')}
+    return dict(arch='hat', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=sum(depths), plus=False, state_dict=state_dict,
                 net_params=get_network_G_config(cfg, up))
 
 

@@ -155,6 +155,25 @@ def get_network_G_config(network_G, scale):
         cfg['upsampler'] = _pick(opts, 'upsampler', 'pixelshuffle')
         cfg['resi_connection'] = _pick(opts, 'resi_connection', '1conv')
         opts.pop('out_nc', None)
+    elif kind in ('hat', 'hat_net'):                       # HAT (hybrid attention transformer on SwinIR's skeleton): the published constructor surface
+        cfg['type'] = 'hat'
+        cfg['in_chans'] = _pick(opts, 'in_nc', 3)
+        cfg['embed_dim'] = _pick(opts, 'nf', 180)
+        cfg['depths'] = list(_pick(opts, 'depths', [6] * 6))
+        cfg['num_heads'] = list(_pick(opts, 'num_heads', [6] * len(cfg['depths'])))
+        cfg['window_size'] = _pick(opts, 'window_size', 16)
+        cfg['compress_ratio'] = _pick(opts, 'compress_ratio', 3)
+        cfg['squeeze_factor'] = _pick(opts, 'squeeze_factor', 30)
+        cfg['conv_scale'] = _pick(opts, 'conv_scale', 0.01)          # (a constructor float no state dict carries: 0.01 in every published model)
+        cfg['overlap_ratio'] = _pick(opts, 'overlap_ratio', 0.5)
+        cfg['mlp_ratio'] = _pick(opts, 'mlp_ratio', 2.0)
+        cfg['upscale'] = _pick(opts, 'scale', scale)
+        cfg['img_range'] = _pick(opts, 'img_range', 1.0)
+        cfg['upsampler'] = _pick(opts, 'upsampler', 'pixelshuffle')
+        cfg['resi_connection'] = _pick(opts, 'resi_connection', '1conv')
+        cfg['rpi_sa'] = _pick(opts, 'rpi_sa', None)                  # the index buffers of the checkpoint, when it carries them
+        cfg['rpi_oca'] = _pick(opts, 'rpi_oca', None)
+        opts.pop('out_nc', None)
     else:
         raise NotImplementedError(f'Generator model [{kind:s}] not recognized')
 
