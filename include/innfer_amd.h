@@ -216,6 +216,35 @@ int innfer_window_attention(const void* d_qkv, int64_t qkv_gs, void* d_out, int6
  * Uploads gamma / beta (C host floats each), launches, waits. */
 int innfer_layer_norm(const void* d_in, int64_t in_gs, void* d_out, int64_t out_gs, int64_t npix, int C, int c_pad, const float* h_gamma, const float* h_beta, float eps,
                       void* stream);
+/* (123, additive) Swin2SR (Conde et al. 2022, "Swin2SR: SwinV2 Transformer for Compressed Image Super-Resolution and Restoration"; the reference has no such
+ * architecture), the published network_swin2sr.py with window_size 8, patch_size 1, qkv_bias, patch_norm, no absolute position embedding, img_range 1.  SwinIR's skeleton
+ * (innfer_swinir_create: pad, x - mean, conv_first, patch_embed.norm, RSTB = conv(blocks(t)) + t, norm, conv_after_body + f, the tails, + mean, crop, shift 4 for odd j,
+ * the -100 mask between the region labels of the rolled frame) around another block:
+ *   block j:   t = t + norm1(proj(attn(t)));  t = t + norm2(fc2(GELU(fc1(t))))      (the LayerNorm BEHIND each branch; attn reads t itself; exact GELU; eps 1e-5)
+ *   attn(t):   8 x 8 windows of roll(t, (-shift, -shift)); qkv = Linear(C, 3 C, no bias)(t') + cat(q_bias, zeros(C), v_bias) -- k has no bias; per head h
+ *              S = (q^ k^^T) tau_h + B_h + M,  q^ = q / max(||q||_2, 1e-12) over the d channels of the head, k^ likewise;  tau_h = exp(min(logit_scale[h], ln 100));
+ *              P = softmax(S); o = P v; heads concatenated, proj, windows back, roll back.  There is no d^-0.5.
+ *   B_h:       T[225][nH] = cpb_mlp(coords), cpb_mlp = Linear(2, hidden, bias) -> ReLU -> Linear(hidden, nH, no bias);
+ *              coords[15 a + b] = (g(a - 7), g(b - 7)), g(c) = sign(c) log2(|8 c / 7| + 1) / 3  (a checkpoint's relative_coords_table [1, 15, 15, 2], when stored, is used
+ *              in its place);  B_h[i][j] = 16 sigmoid(T[(ri - rj + 7) 15 + (ci - cj + 7)][h]) for tokens i = 8 ri + ci, j = 8 rj + cj
+ * on the engine of innfer_net_*, laid out as innfer_swinir_create's (same arguments, limits, conv slots `<state-dict key>#<p>`, LayerNorm numbering, workspace, fp16 mode
+ * only).  The caller re-lays-out as for SwinIR EXCEPT that attn.qkv's q rows carry no scale and its bias is cat(q_bias, 0, v_bias) under the same permutation; it builds
+ * B_h (innfer_net_set_attn_bias) and tau (innfer_net_set_attn_scale) at load.  Per block: qkv from t (SQ launches), the cosine attention (1), proj -> u (S1),
+ * t = t + LN(u) (1), fc1 with GELU from t (SH), fc2 -> u (S1), t = t + LN(u) (1): 3 + SQ + 2 S1 + SH, so a forward has SwinIR's launch count:
+ *   S1 + 2 + B (3 + SQ + 2 S1 + SH) + (R + 1) SR + T + 2 [H x W is not Hp x Wp]. */
+int innfer_swin2sr_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int upsampler,
+                          int scale, int conv3, const float* h_mean);
+/* (123, additive) tau of block `blk` of a Swin2SR: exp(min(logit_scale, ln 100)) per head, num_heads host floats (finite, > 0).  Load time, synchronous. */
+int innfer_net_set_attn_scale(innfer_net_t net, int blk, const float* h_tau);
+/* (123, additive) The cosine window attention as a single launch (for tests; csrc/win_attn.hip, the COS form).  Slabs, sizes and shift as innfer_window_attention's, q and k
+ * unscaled; h_tau: num_heads host floats.  The raw product runs on the fp16 operands as stored; then in fp32 S = raw (rq_i tau_h) rk_j + B_h[i][j] with
+ * r = 1 / max(sqrtf(sum of squares), 1e-12) (an all-zero row: scores = the bias); mask, softmax, P v as innfer_window_attention.  Uploads, launches, waits. */
+int innfer_window_attention_cos(const void* d_qkv, int64_t qkv_gs, void* d_out, int64_t out_gs, const float* h_bias, const float* h_tau, int N, int Hp, int Wp,
+                                int num_heads, int head_dim, int shift, void* stream);
+/* (123, additive) LayerNorm + residual per pixel (for tests; csrc/layer_norm.hip, the ADD form): d_out = fp16(res + fma((x - mean) rstd, gamma[c], beta[c])), statistics as
+ * innfer_layer_norm's, ONE fp16 rounding; channels C .. c_pad - 1 written as zeros.  d_out may be d_res or d_in.  Uploads gamma / beta, launches, waits. */
+int innfer_layer_norm_add(const void* d_in, int64_t in_gs, const void* d_res, int64_t res_gs, void* d_out, int64_t out_gs, int64_t npix, int C, int c_pad,
+                          const float* h_gamma, const float* h_beta, float eps, void* stream);
 /* (123, additive) HAT (Chen et al. 2023, "Activating More Pixels in Image Super-Resolution Transformer"; the reference has no such architecture) on SwinIR's skeleton, with
  * C = embed_dim, nH heads of d = C / nH, window ws = 16, overlapping window ows = 24, patch_size 1, qkv_bias, patch_norm, no absolute position embedding, img_range 1, '1conv':
  *   forward(x):  reflect-pad right / bottom to multiples of 16; f = conv_first(x - mean); f = conv_after_body(norm(RHAGs(patch_embed.norm(f)))) + f;

@@ -35,6 +35,8 @@ def get_network(opt_net):
         from .PLKSR_arch import RealPLKSR as net
     elif kind in ('swinir', 'swinir_net'):
         from .SwinIR_arch import SwinIR as net
+    elif kind in ('swin2sr', 'swin2sr_net'):
+        from .Swin2SR_arch import Swin2SR as net
     elif kind in ('hat', 'hat_net'):
         from .HAT_arch import HAT as net
     else:

@@ -251,6 +251,23 @@ def swinir_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_head
     return s
 
 
+def swin2sr_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=6, mlp_ratio=2.0, upscale=4, upsampler='pixelshuffle', resi_connection='1conv', window_size=8,
+                   cpb_hidden=512):
+    """State-dict key -> shape of the PARAMETERS of Swin2SR (the published network_swin2sr.py; patch_size 1, qkv_bias, patch_norm, no absolute position embedding): SwinIR's
+    keys with another attention -- no relative_position_bias_table and no qkv.bias; logit_scale, the continuous-position-bias MLP, q_bias and v_bias instead.  The buffers
+    (attn.relative_coords_table and attn.relative_position_index on every block, attn_mask on the odd ones) are not parameters."""
+    s = {}
+    for k, shp in swinir_shapes(in_chans, embed_dim, depths, num_heads, mlp_ratio, upscale, upsampler, resi_connection, window_size).items():
+        if k.endswith('attn.relative_position_bias_table'):
+            a = k[:-len('relative_position_bias_table')]
+            s[a + 'logit_scale'] = (num_heads, 1, 1)
+            s[a + 'cpb_mlp.0.weight'], s[a + 'cpb_mlp.0.bias'], s[a + 'cpb_mlp.2.weight'] = (cpb_hidden, 2), (cpb_hidden,), (num_heads, cpb_hidden)
+            s[a + 'q_bias'], s[a + 'v_bias'] = (embed_dim,), (embed_dim,)
+        elif not k.endswith('attn.qkv.bias'):
+            s[k] = shp
+    return s
+
+
 def hat_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=6, mlp_ratio=2.0, upscale=4, compress_ratio=3, squeeze_factor=30, window_size=16,
                overlap_win_size=24):
     """State-dict key -> shape of the PARAMETERS of HAT (the published hat_arch.py; patch_size 1, qkv_bias, patch_norm, no absolute position embedding, the pixelshuffle

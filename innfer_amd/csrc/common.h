@@ -267,6 +267,11 @@ int gn_apply_launch(const f16* u, long u_gs, const f16* skip, long skip_gs, f16*
 int win_attn_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, int N, int Hp, int Wp, int nH, int d, int shift, hipStream_t s);
 // out = fp16(LayerNorm(C)(in)) per pixel over the C real channels of two c_pad-channel slabs (pad channels written as zeros); in == out allowed
 int layer_norm_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s);
+// Swin2SR on the same two files.  The cosine form of the window attention: q and k as the qkv Linear left them (NO scale inside the weights), tau: nH device floats,
+// S = (q k^T) / (max(||q||, 1e-12) max(||k||, 1e-12)) * tau[h] + B_h + M with the norms and the scaling in fp32 behind the fp16 product; everything else as win_attn_launch
+int win_attn_cos_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, const float* tau, int N, int Hp, int Wp, int nH, int d, int shift, hipStream_t s);
+// out = fp16(res + LayerNorm(C)(in)) (res-post-norm): one rounding; out == res and out == in allowed
+int layer_norm_add_launch(const f16* in, long in_gs, const f16* res, long res_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s);
 
 // ---- HAT's 16 x 16 window attention over a 16 x 16 (self, shift 0 | 8, mask) or 24 x 24 (overlapping, zero-filled at the border) key window (win_attn16.hip) ----
 // slabs as win_attn_launch's; relb: dense fp32 [nH][256 query][kw^2 key]; Hp, Wp multiples of 16; kw 16 | 24; shift 0, or 8 with kw 16

@@ -4,6 +4,8 @@
 //   out = fp16(fma((x - mean) * rstd, gamma[c], beta[c])),  rstd = 1 / sqrtf(var + eps):  one fp16 rounding.
 // Channels >= C are left out of the statistics whatever they hold and are WRITTEN as zeros.  in == out is allowed (a thread reads all it writes before it writes).
 // Memory bound: 64 bytes per group in, 64 out.
+// ADD (Swin2SR's res-post-norm, t = t + norm(branch)): out = fp16(res + fma((x - mean) * rstd, gamma[c], beta[c])) -- the same statistics in the same order, the sum in fp32,
+// still ONE fp16 rounding; pad channels are written as zeros.  out may be res or in: a lane reads the eight channels of every group of both before it writes them.
 #include "common.h"
 
 namespace innfer {
@@ -13,11 +15,12 @@ namespace {
 struct LnArgs {
     const f16* in; long in_gs;
     f16* out; long out_gs;
+    const f16* res; long res_gs;     // ADD only
     const float* gamma; const float* beta;
     long npix; int C; float eps;
 };
 
-template <int NG>
+template <int NG, bool ADD>
 __global__ __launch_bounds__(256) void layer_norm_kernel(const LnArgs p) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     const int q = (int)(i & 3);
@@ -27,6 +30,12 @@ __global__ __launch_bounds__(256) void layer_norm_kernel(const LnArgs p) {
     f16x8 v[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) v[g] = *(const f16x8*)(ib + g * p.in_gs);
+    f16x8 r[ADD ? NG : 1];
+    if constexpr (ADD) {
+        const f16* rb = p.res + px * 32 + q * 8;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) r[g] = *(const f16x8*)(rb + g * p.res_gs);
+    }
     auto quad = [](float s) { s += __shfl_xor(s, 1); return s + __shfl_xor(s, 2); };
     float s = 0.f;
 #pragma unroll
@@ -52,8 +61,10 @@ __global__ __launch_bounds__(256) void layer_norm_kernel(const LnArgs p) {
         const int c0 = g * 32 + q * 8;
         f16x8 y;
 #pragma unroll
-        for (int e = 0; e < 8; ++e)
-            y[e] = c0 + e < p.C ? (f16)__builtin_fmaf(((float)v[g][e] - mu) * rstd, p.gamma[c0 + e], p.beta[c0 + e]) : (f16)0.f;
+        for (int e = 0; e < 8; ++e) {
+            if constexpr (ADD) y[e] = c0 + e < p.C ? (f16)((float)r[g][e] + __builtin_fmaf(((float)v[g][e] - mu) * rstd, p.gamma[c0 + e], p.beta[c0 + e])) : (f16)0.f;
+            else y[e] = c0 + e < p.C ? (f16)__builtin_fmaf(((float)v[g][e] - mu) * rstd, p.gamma[c0 + e], p.beta[c0 + e]) : (f16)0.f;
+        }
         *(f16x8*)(ob + g * p.out_gs) = y;
     }
 }
@@ -61,24 +72,35 @@ __global__ __launch_bounds__(256) void layer_norm_kernel(const LnArgs p) {
 }  // namespace
 
 // c_pad: channels of both slabs (a multiple of 64, >= C, <= 256): every group is read and written.  gamma / beta: device floats, at least C each (the values behind C are never read)
-int layer_norm_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s) {
+template <bool ADD>
+static int layer_norm_any(const f16* in, long in_gs, const f16* res, long res_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s) {
+    if (ADD && (!res || res_gs < npix * 32)) return set_error(INNFER_ERR_INVALID, "layer norm: the residual is null or its group stride below %ld pixels x 32", npix);
     if (!in || !out || !gamma || !beta || npix <= 0) return set_error(INNFER_ERR_INVALID, "layer norm: null argument or %ld pixels", npix);
     if (C < 1 || c_pad < C || c_pad > 256 || c_pad % 64) return set_error(INNFER_ERR_UNSUPPORTED, "layer norm: C=%d in a slab of %d channels (built: slabs of 64, 128, 192 or 256 channels -- at most eight groups in a quad's registers)", C, c_pad);
     if (in_gs < npix * 32 || out_gs < npix * 32) return set_error(INNFER_ERR_INVALID, "layer norm: a group stride below %ld pixels x 32", npix);
     const long nblk = (npix * 4 + 255) / 256;
     if (nblk > 0x7fffffffL) return set_error(INNFER_ERR_UNSUPPORTED, "layer norm: %ld pixels exceed the launch grid", npix);
     const int ng = c_pad / 32;
-    GtScope gt(s, "layer norm (per pixel, padded slab)", 8.0 * C * (double)npix, 128.0 * ng * (double)npix);
-    const LnArgs p{in, in_gs, out, out_gs, gamma, beta, npix, C, eps};
+    GtScope gt(s, ADD ? "layer norm + residual (per pixel, padded slab)" : "layer norm (per pixel, padded slab)", (ADD ? 9.0 : 8.0) * C * (double)npix, (ADD ? 192.0 : 128.0) * ng * (double)npix);
+    const LnArgs p{in, in_gs, out, out_gs, res, res_gs, gamma, beta, npix, C, eps};
     const dim3 grid((unsigned)nblk), block(256);
     switch (ng) {
-        case 2: hipLaunchKernelGGL(layer_norm_kernel<2>, grid, block, 0, s, p); break;
-        case 4: hipLaunchKernelGGL(layer_norm_kernel<4>, grid, block, 0, s, p); break;
-        case 6: hipLaunchKernelGGL(layer_norm_kernel<6>, grid, block, 0, s, p); break;
-        default: hipLaunchKernelGGL(layer_norm_kernel<8>, grid, block, 0, s, p); break;
+        case 2: hipLaunchKernelGGL((layer_norm_kernel<2, ADD>), grid, block, 0, s, p); break;
+        case 4: hipLaunchKernelGGL((layer_norm_kernel<4, ADD>), grid, block, 0, s, p); break;
+        case 6: hipLaunchKernelGGL((layer_norm_kernel<6, ADD>), grid, block, 0, s, p); break;
+        default: hipLaunchKernelGGL((layer_norm_kernel<8, ADD>), grid, block, 0, s, p); break;
     }
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
+}
+
+int layer_norm_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s) {
+    return layer_norm_any<false>(in, in_gs, nullptr, 0, out, out_gs, npix, C, c_pad, gamma, beta, eps, s);
+}
+
+// out = fp16(res + LayerNorm(C)(in)): `res` a third slab of c_pad channels; out may be res or in
+int layer_norm_add_launch(const f16* in, long in_gs, const f16* res, long res_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s) {
+    return layer_norm_any<true>(in, in_gs, res, res_gs, out, out_gs, npix, C, c_pad, gamma, beta, eps, s);
 }
 
 }  // namespace innfer

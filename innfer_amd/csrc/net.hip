@@ -133,6 +133,9 @@ struct innfer_net {
     float hat_scale = 0.01f;
     std::vector<float*> hat_ca;
     std::vector<int> sw_relb_kw;
+    // Swin2SR (kind 7; innfer_swin2sr_create) on SwinIR's fields, slots and workspace: cosine attention (sw_tau[blk]: nH floats, innfer_net_set_attn_scale) and the
+    // LayerNorm BEHIND each branch (t = t + norm(branch)); sw_relb holds 16 sigmoid(cpb_mlp(coords)) gathered into the same dense [nH][64][64] table
+    std::vector<float*> sw_tau;
     bool span_norm = false;      // SPAN(norm=True): conv_1 reads (x - mean) * img_range through FirstConvLaunch.in_map (convs[0].d_map: alpha[in_nc] then shift[in_nc])
     int in_nc = 3, out_nc = 3, nf = 64, nb = 23, gc = 32, scale = 4, n_up = 2;
     int final_act = 0;           // `finalact` of the reference constructors: activation after the last conv (ConvLaunch.act codes)
@@ -375,8 +378,8 @@ static void swin_add_resi(innfer_net* net, const std::string& key) {          //
     swin_add_sliced(net, key + ".2", net->sw_c4p, net->sw_c4p, 1);
     swin_add_sliced(net, key + ".4", net->sw_cp, net->sw_c4p, 3);
 }
-extern "C" int innfer_swinir_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int upsampler,
-                                    int scale, int conv3, const float* h_mean) {
+static int swin_create(int kind, innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int upsampler,
+                       int scale, int conv3, const float* h_mean) {
     if (!out || !depths) return set_error(INNFER_ERR_INVALID, "swinir_create: null argument");
     if (embed_dim < 1 || embed_dim > 256 || num_heads < 1 || num_heads > 8 || embed_dim % num_heads || embed_dim / num_heads > 32)
         return set_error(INNFER_ERR_UNSUPPORTED, "swinir_create: embed_dim=%d num_heads=%d (built: embed_dim <= 256, <= 8 heads of <= 32 channels, embed_dim %% num_heads == 0)", embed_dim, num_heads);
@@ -390,7 +393,7 @@ extern "C" int innfer_swinir_create(innfer_net_t* out, int in_nc, int out_nc, in
     if ((upsampler == 2 && scale != 2 && scale != 4) || (upsampler != 2 && (scale < 2 || scale > 4)))
         return set_error(INNFER_ERR_UNSUPPORTED, "swinir_create: scale %d (built: 2, 3, 4 with pixelshuffle / pixelshuffledirect, 2 and 4 with nearest+conv)", scale);
     innfer_net* net = new innfer_net();
-    net->kind = 5; net->in_nc = in_nc; net->out_nc = out_nc; net->nf = 64; net->nb = 0; net->gc = 0; net->scale = scale; net->n_up = 0;
+    net->kind = kind; net->in_nc = in_nc; net->out_nc = out_nc; net->nf = 64; net->nb = 0; net->gc = 0; net->scale = scale; net->n_up = 0;
     net->sw_c = embed_dim; net->sw_cp = (embed_dim + 63) / 64 * 64; net->sw_nh = num_heads; net->sw_d = embed_dim / num_heads;
     net->sw_hid = mlp_hidden; net->sw_hp = (mlp_hidden + 63) / 64 * 64; net->sw_tail = upsampler; net->sw_conv3 = conv3 != 0;
     net->sw_c4p = (embed_dim / 4 + 63) / 64 * 64;
@@ -431,6 +434,7 @@ extern "C" int innfer_swinir_create(innfer_net_t* out, int in_nc, int out_nc, in
     }
     net->sw_ln.assign(2 + 2 * (size_t)net->nb, nullptr);
     net->sw_relb.assign((size_t)net->nb, nullptr);
+    if (kind == 7) net->sw_tau.assign((size_t)net->nb, nullptr);
     int rc = INNFER_OK;
     {   // x - mean in front of conv_first (img_range 1): the input map of every slice of the first conv, held by slice 0; nn.LeakyReLU() (slope 0.01) behind conv_before_upsample
         float h[8];
@@ -449,11 +453,22 @@ extern "C" int innfer_swinir_create(innfer_net_t* out, int in_nc, int out_nc, in
     return INNFER_OK;
 }
 
+extern "C" int innfer_swinir_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int upsampler,
+                                    int scale, int conv3, const float* h_mean) {
+    return swin_create(5, out, in_nc, out_nc, embed_dim, depths, n_layers, num_heads, mlp_hidden, upsampler, scale, conv3, h_mean);
+}
+// Swin2SR (Conde et al. 2022; include/innfer_amd.h carries the definition): SwinIR's skeleton, conv slots, LayerNorm numbering, tails and workspace; the block is
+// t = t + norm1(proj(attn(t))), t = t + norm2(fc2(GELU(fc1(t)))) with the cosine attention.  Arguments, limits and refusals are innfer_swinir_create's.
+extern "C" int innfer_swin2sr_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int upsampler,
+                                     int scale, int conv3, const float* h_mean) {
+    return swin_create(7, out, in_nc, out_nc, embed_dim, depths, n_layers, num_heads, mlp_hidden, upsampler, scale, conv3, h_mean);
+}
+
 // gamma / beta (C host floats each) of LayerNorm `idx` of a SwinIR: 0 patch_embed.norm, 1 + 2 b / 2 + 2 b norm1 / norm2 of block b (blocks counted through the residual
 // groups), the last one norm.  Load time, synchronous.
 extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float* h_gamma, const float* h_beta) {
     if (!net || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "set_layer_norm: null argument");
-    if (net->kind != 5 && net->kind != 6) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR, HAT)");
+    if (net->kind != 5 && net->kind != 6 && net->kind != 7) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR, HAT, Swin2SR)");
     if (idx < 0 || idx >= (int)net->sw_ln.size()) return set_error(INNFER_ERR_INVALID, "set_layer_norm: index %d of %zu", idx, net->sw_ln.size());
     std::vector<float> h(2 * (size_t)net->sw_cp, 0.f);
     for (int c = 0; c < net->sw_c; ++c) { h[c] = h_gamma[c]; h[net->sw_cp + c] = h_beta[c]; }
@@ -465,12 +480,24 @@ extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float*
 // The relative position bias of block `blk` of a SwinIR as the dense table the attention reads: [num_heads][64 query][64 key] host floats.  Load time, synchronous.
 extern "C" int innfer_net_set_attn_bias(innfer_net_t net, int blk, const float* h_bias) {
     if (!net || !h_bias) return set_error(INNFER_ERR_INVALID, "set_attn_bias: null argument");
-    if (net->kind != 5 && net->kind != 6) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_bias: the network has no window attention (built: SwinIR, HAT)");
+    if (net->kind != 5 && net->kind != 6 && net->kind != 7) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_bias: the network has no window attention (built: SwinIR, HAT, Swin2SR)");
     if (blk < 0 || blk >= (int)net->sw_relb.size()) return set_error(INNFER_ERR_INVALID, "set_attn_bias: block %d of %zu", blk, net->sw_relb.size());
     // (HAT: table `blk` in forward order -- [num_heads][256][256] of a HAB, [num_heads][256][576] of a residual group's OCAB)
     const size_t nb = (size_t)net->sw_nh * (net->kind == 6 ? 256 * (size_t)net->sw_relb_kw[blk] * net->sw_relb_kw[blk] : 4096) * sizeof(float);
     if (!net->sw_relb[blk]) INNFER_HIP(hipMalloc((void**)&net->sw_relb[blk], nb));
     INNFER_HIP(hipMemcpy(net->sw_relb[blk], h_bias, nb, hipMemcpyHostToDevice));
+    return INNFER_OK;
+}
+
+// tau of block `blk` of a Swin2SR: exp(min(logit_scale, ln 100)) of every head, num_heads host floats (finite, > 0).  Load time, synchronous.
+extern "C" int innfer_net_set_attn_scale(innfer_net_t net, int blk, const float* h_tau) {
+    if (!net || !h_tau) return set_error(INNFER_ERR_INVALID, "set_attn_scale: null argument");
+    if (net->kind != 7) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_scale: the network has no cosine attention (built: Swin2SR)");
+    if (blk < 0 || blk >= (int)net->sw_tau.size()) return set_error(INNFER_ERR_INVALID, "set_attn_scale: block %d of %zu", blk, net->sw_tau.size());
+    for (int h = 0; h < net->sw_nh; ++h)
+        if (!(h_tau[h] > 0.f) || !std::isfinite(h_tau[h])) return set_error(INNFER_ERR_INVALID, "set_attn_scale: tau[%d] = %g of block %d (finite, > 0)", h, (double)h_tau[h], blk);
+    if (!net->sw_tau[blk]) INNFER_HIP(hipMalloc((void**)&net->sw_tau[blk], (size_t)net->sw_nh * sizeof(float)));
+    INNFER_HIP(hipMemcpy(net->sw_tau[blk], h_tau, (size_t)net->sw_nh * sizeof(float), hipMemcpyHostToDevice));
     return INNFER_OK;
 }
 
@@ -609,6 +636,7 @@ extern "C" void innfer_net_destroy(innfer_net_t net) {
     if (!net) return;
     for (float* q : net->sw_ln) if (q) (void)hipFree(q);
     for (float* q : net->sw_relb) if (q) (void)hipFree(q);
+    for (float* q : net->sw_tau) if (q) (void)hipFree(q);
     for (float* q : net->hat_ca) if (q) (void)hipFree(q);
     for (auto& c : net->convs) {
         if (c.d_w) (void)hipFree(c.d_w);
@@ -772,6 +800,7 @@ extern "C" int innfer_net_set_precision(innfer_net_t net, int fp32) {
     if (fp32 && net->kind == 4) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: RealPLKSR is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 5) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SwinIR is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 6) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: HAT is built for the fp16 mode only (no fp32-accurate engine)");
+    if (fp32 && net->kind == 7) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: Swin2SR is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32) {
         // The (wl | wh | wh) panels of every loaded conv are built HERE -- a load-time call, with its hipMalloc and synchronous copies -- never inside
         // innfer_net_forward (stream capture, concurrent callers).  Idempotent: a conv that already has its panels is skipped; innfer_net_set_conv
@@ -846,7 +875,7 @@ extern "C" int innfer_net_set_final_act(innfer_net_t net, int act) {
 
 extern "C" double innfer_net_flops(innfer_net_t net, int N, int H, int W) {
     if (!net) return 0.0;
-    if (net->kind == 5) {        // SwinIR: every conv on the padded grid (its tail's at their own resolution) + the two products of every window and head
+    if (net->kind == 5 || net->kind == 7) {        // SwinIR, Swin2SR: every conv on the padded grid (its tail's at their own resolution) + the two products of every window and head
         const double px = (double)N * ((H + 7) / 8 * 8) * ((W + 7) / 8 * 8);
         double f = (double)net->nb * net->sw_nh * (px / 64) * 4.0 * 64 * 64 * 32;
         for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
@@ -932,7 +961,7 @@ static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
 
 static Carve carve(const innfer_net* net, int N, int H, int W) {
     Carve c{};
-    if (net->kind == 5 || net->kind == 6) { c.total = swin_carve(net, N, H, W).total; return c; }
+    if (net->kind == 5 || net->kind == 6 || net->kind == 7) { c.total = swin_carve(net, N, H, W).total; return c; }
     const size_t px = (size_t)N * H * W;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     if (net->kind == 2) {        // SRVGGNetCompact: the two ping-pong feature slabs (one when there is no nf -> nf conv) and the last conv's 32- / 64-channel slab
@@ -1473,6 +1502,8 @@ static int swinir_forward(innfer_net* net, const void* d_in, int in_dtype, void*
         if (!net->sw_ln[i]) return set_error(INNFER_ERR_INVALID, "forward: the parameters of LayerNorm %zu were never set (innfer_net_set_layer_norm)", i);
     for (size_t i = 0; i < net->sw_relb.size(); ++i)
         if (!net->sw_relb[i]) return set_error(INNFER_ERR_INVALID, "forward: the relative position bias of block %zu was never set (innfer_net_set_attn_bias)", i);
+    for (size_t i = 0; i < net->sw_tau.size(); ++i)
+        if (!net->sw_tau[i]) return set_error(INNFER_ERR_INVALID, "forward: the attention scale of block %zu was never set (innfer_net_set_attn_scale)", i);
     const SwinCarve cv = swin_carve(net, N, H, W);
     const int Hp = cv.Hp, Wp = cv.Wp, sc = net->scale, cp = net->sw_cp, nh = net->sw_nh;
     if (Hp - H >= H || Wp - W >= W) return set_error(INNFER_ERR_INVALID, "forward: %d x %d cannot be reflect-padded to %d x %d (the pad must be smaller than the side)", H, W, Hp, Wp);
@@ -1584,6 +1615,29 @@ static int swinir_forward(innfer_net* net, const void* d_in, int in_dtype, void*
             if (int rc = norm(ln++, t, u)) return rc;
             if (int rc = sliced(net->sw_hp / 64, u, hid, 12, nullptr)) return rc;
             if (int rc = sliced(cp / 64, hid, t, 0, t)) return rc;
+            if (int rc = resi(t, r[cur ^ 1], r[cur])) return rc;
+            cur ^= 1;
+        }
+    } else if (net->kind == 7) {
+        // Swin2SR: per block  qkv from the token stream itself; the cosine window attention; u = proj (no shortcut); t = x + LN(u) (one launch; x the group's input r for
+        // its first block, else t in place); fc1 with GELU from t; u = fc2; t = t + LN(u).  The same launch count as SwinIR's block: 3 + SQ + 2 S1 + SH.
+        auto norm_add = [&](int idx, const f16* in, const f16* res, f16* out) {
+            // launch kind 8008: LayerNorm + residual -- bytes: C_pad channels of the branch and of the stream in, the stream out
+            return plksr_pass(s, "layer_norm_add", 9.0 * net->sw_c * px, px * cp * 6.0, 8008,
+                              [&] { return layer_norm_add_launch(in, G, res, G, out, G, npx, net->sw_c, cp, net->sw_ln[idx], net->sw_ln[idx] + cp, 1e-5f, s); });
+        };
+        for (size_t i = 0; i < net->sw_depths.size(); ++i) {
+            for (int j = 0; j < net->sw_depths[i]; ++j, ++blk) {
+                const f16* x = j == 0 ? r[cur] : t;
+                if (int rc = sliced((3 * nh + 1) / 2, x, qkv, 0, nullptr)) return rc;
+                if (int rc = plksr_pass(s, "window_attention_cos", 4.0 * 64 * 32 * nh * px, px * nh * 256.0 + nh * 16384.0, 8001, [&] {
+                        return win_attn_cos_launch(qkv, G, att, G, net->sw_relb[blk], net->sw_tau[blk], N, Hp, Wp, nh, net->sw_d, (j & 1) ? 4 : 0, s); })) return rc;
+                if (int rc = sliced(cp / 64, att, u, 0, nullptr)) return rc;
+                if (int rc = norm_add(1 + 2 * blk, u, x, t)) return rc;
+                if (int rc = sliced(net->sw_hp / 64, t, hid, 12, nullptr)) return rc;
+                if (int rc = sliced(cp / 64, hid, u, 0, nullptr)) return rc;
+                if (int rc = norm_add(2 + 2 * blk, u, t, t)) return rc;
+            }
             if (int rc = resi(t, r[cur ^ 1], r[cur])) return rc;
             cur ^= 1;
         }
@@ -1725,7 +1779,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     if (ws_bytes < cv.total) return set_error(INNFER_ERR_WORKSPACE, "forward: workspace %zu < %zu bytes", ws_bytes, cv.total);
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)d_ws;
-    if (net->kind == 5 || net->kind == 6) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);
+    if (net->kind == 5 || net->kind == 6 || net->kind == 7) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);
     if (net->kind == 2) return compact_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 3) return span_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 4) return plksr_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
@@ -2196,6 +2250,39 @@ extern "C" int innfer_layer_norm(const void* d_in, int64_t in_gs, void* d_out, i
                  ? INNFER_OK : set_error(INNFER_ERR_HIP, "layer_norm: copying the parameters failed");
     if (rc == INNFER_OK) rc = layer_norm_launch((const f16*)d_in, (long)in_gs, (f16*)d_out, (long)out_gs, (long)npix, C, c_pad, d_p, d_p + C, eps, (hipStream_t)stream);
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "layer_norm: the launch failed");
+    (void)hipFree(d_p);
+    return rc;
+}
+
+// Swin2SR's cosine window attention alone, for tests: win_attn_cos_launch, the code the network runs.  Uploads the bias table and the per-head scales, launches, waits.
+extern "C" int innfer_window_attention_cos(const void* d_qkv, int64_t qkv_gs, void* d_out, int64_t out_gs, const float* h_bias, const float* h_tau, int N, int Hp, int Wp,
+                                           int num_heads, int head_dim, int shift, void* stream) {
+    if (!d_qkv || !d_out || !h_bias || !h_tau) return set_error(INNFER_ERR_INVALID, "window_attention_cos: null argument");
+    if (num_heads < 1 || num_heads > 8) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention_cos: %d heads (built: 1 .. 8)", num_heads);
+    float* d_b = nullptr;
+    const size_t nb = (size_t)num_heads * 4096 * sizeof(float), nt = (size_t)num_heads * sizeof(float);
+    if (hipMalloc((void**)&d_b, nb + nt) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "window_attention_cos: out of device memory");
+    float* d_t = d_b + (size_t)num_heads * 4096;
+    int rc = (hipMemcpy(d_b, h_bias, nb, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_t, h_tau, nt, hipMemcpyHostToDevice) == hipSuccess)
+                 ? INNFER_OK : set_error(INNFER_ERR_HIP, "window_attention_cos: copying the bias table and the scales failed");
+    if (rc == INNFER_OK) rc = win_attn_cos_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, d_b, d_t, N, Hp, Wp, num_heads, head_dim, shift, (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "window_attention_cos: the launch failed");
+    (void)hipFree(d_b);
+    return rc;
+}
+
+// Swin2SR's LayerNorm + residual alone, for tests: layer_norm_add_launch, the code the network runs.  Uploads gamma / beta, launches, waits.
+extern "C" int innfer_layer_norm_add(const void* d_in, int64_t in_gs, const void* d_res, int64_t res_gs, void* d_out, int64_t out_gs, int64_t npix, int C, int c_pad,
+                                     const float* h_gamma, const float* h_beta, float eps, void* stream) {
+    if (!d_in || !d_res || !d_out || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "layer_norm_add: null argument");
+    if (C < 1 || C > 256) return set_error(INNFER_ERR_UNSUPPORTED, "layer_norm_add: C=%d (built: 1 .. 256)", C);
+    float* d_p = nullptr;
+    if (hipMalloc((void**)&d_p, 2 * (size_t)C * sizeof(float)) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "layer_norm_add: out of device memory");
+    int rc = (hipMemcpy(d_p, h_gamma, C * sizeof(float), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_p + C, h_beta, C * sizeof(float), hipMemcpyHostToDevice) == hipSuccess)
+                 ? INNFER_OK : set_error(INNFER_ERR_HIP, "layer_norm_add: copying the parameters failed");
+    if (rc == INNFER_OK) rc = layer_norm_add_launch((const f16*)d_in, (long)in_gs, (const f16*)d_res, (long)res_gs, (f16*)d_out, (long)out_gs, (long)npix, C, c_pad, d_p, d_p + C, eps,
+                                                    (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "layer_norm_add: the launch failed");
     (void)hipFree(d_p);
     return rc;
 }

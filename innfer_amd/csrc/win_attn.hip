@@ -14,6 +14,13 @@
 //                       its keys in that order ([32 channels][64 slots], 144-byte rows): an A fragment is one ds_read_b128.  A lane ends with four consecutive channels of
 //                       its query: o / sum in fp32, one rounding, one 8-byte store; channels >= d are written as zeros.
 // A window of image n reads only image n.  Bound by the gather and the exponentials, not by the 32 MFMAs: 12 KB in and 4 KB out per wave.
+//
+// COS (Swin2SR: the SwinV2 cosine attention) is the same kernel with another score: S = (q^ k^T^) tau_h + B_h + M, q^ = q / max(||q||_2, 1e-12), k^ likewise.  The raw
+// product K Q^T runs on the fp16 operands AS STORED (C operand zero); the scaling follows in fp32, s = fma(raw (rq_i tau_h), rk_j, B_h[i][j]) -- normalising q or k into fp16
+// in front of the MFMA would cost one more rounding of every operand.  r = 1 / max(sqrtf(sum of squares), 1e-12) in fp32: a lane holds eight channels of its four tokens,
+// the four lane groups of a token are two exchanges apart (__shfl_xor 16, 32), so rq of query 16 tq + li is on every lane that needs it; the 64 rk go through 256 bytes of
+// LDS per wave in front of the barrier V^T needs anyway (lane l writes key l, a lane reads its four consecutive keys of a 16-key tile as one 16-byte load).  An all-zero q
+// or k row has raw = 0: its scores are the bias alone.  Mask, maximum, exponentials, sum, P and the second product are the code above.
 #include "common.h"
 
 namespace innfer {
@@ -26,13 +33,16 @@ struct WinAttn {
     const f16* qkv; long gs;
     f16* out; long out_gs;
     const float* relb;
+    const float* tau;                // COS: exp(min(logit_scale, ln 100)) of every head
     int N, Hp, Wp, nH, d, shift, total;
 };
 
 __device__ __forceinline__ int wa_band(int r, int n) { return r < n - 8 ? 0 : (r < n - 4 ? 1 : 2); }
 
+template <bool COS>
 __global__ __launch_bounds__(256) void win_attn_kernel(const WinAttn p) {
     __shared__ __attribute__((aligned(16))) f16 vts[4][32 * WA_VROW];
+    __shared__ __attribute__((aligned(16))) float rks[COS ? 4 : 1][64];      // COS: 1 / max(||k||, 1e-12) of the wave's 64 keys
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, li = lane & 15, lg = lane >> 4;
     int item = blockIdx.x * 4 + wave;
     const bool live = item < p.total;
@@ -66,6 +76,27 @@ __global__ __launch_bounds__(256) void win_attn_kernel(const WinAttn p) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) vt[(8 * oct + e) * WA_VROW + slot] = v[e];
     }
+    float rq[4] = {0.f, 0.f, 0.f, 0.f};                  // COS: tau_h / max(||q||, 1e-12) of query 16 tq + li
+    if constexpr (COS) {
+        const float tau = p.tau[h];
+        float mine = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            float sq = 0.f, sk = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float a = (float)qf[t][e], b = (float)kf[t][e];
+                sq = __builtin_fmaf(a, a, sq);
+                sk = __builtin_fmaf(b, b, sk);
+            }
+            sq += __shfl_xor(sq, 16); sq += __shfl_xor(sq, 32);
+            sk += __shfl_xor(sk, 16); sk += __shfl_xor(sk, 32);
+            rq[t] = tau / fmaxf(sqrtf(sq), 1e-12f);
+            const float rk = 1.0f / fmaxf(sqrtf(sk), 1e-12f);
+            if (lg == t) mine = rk;                      // (all four lane groups hold token 16 t + li's value: group t keeps it, so lane l writes key l)
+        }
+        rks[wave][lane] = mine;
+    }
     __syncthreads();
 
     // s[tk][tq][j]: key 16 tk + 4 lg + j, query 16 tq + li
@@ -76,7 +107,14 @@ __global__ __launch_bounds__(256) void win_attn_kernel(const WinAttn p) {
 #pragma unroll
         for (int tk = 0; tk < 4; ++tk) {
             const f32x4 b = *(const f32x4*)(rb + (16 * tq + li) * 64 + 16 * tk + 4 * lg);
-            s[tk][tq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[tk], qf[tq], b, 0, 0, 0);
+            if constexpr (COS) {
+                const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+                const f32x4 raw = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[tk], qf[tq], z, 0, 0, 0);
+                const f32x4 rk = *(const f32x4*)(&rks[wave][16 * tk + 4 * lg]);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s[tk][tq][j] = __builtin_fmaf(raw[j] * rq[tq], rk[j], b[j]);
+            } else
+                s[tk][tq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[tk], qf[tq], b, 0, 0, 0);
         }
     if (p.shift && (wy == (p.Hp >> 3) - 1 || wx == nwx - 1)) {       // (wave-uniform) the windows that wrap
         int lq[4], lk[4][4];
@@ -141,7 +179,8 @@ __global__ __launch_bounds__(256) void win_attn_kernel(const WinAttn p) {
 
 }  // namespace
 
-int win_attn_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, int N, int Hp, int Wp, int nH, int d, int shift, hipStream_t s) {
+static int win_attn_any(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, const float* tau, bool cos, int N, int Hp, int Wp, int nH, int d, int shift, hipStream_t s) {
+    if (cos && !tau) return set_error(INNFER_ERR_INVALID, "window attention: the cosine form without its per-head scales");
     if (!qkv || !out || !relb || N <= 0 || Hp <= 0 || Wp <= 0) return set_error(INNFER_ERR_INVALID, "window attention: null argument or N=%d Hp=%d Wp=%d", N, Hp, Wp);
     if ((Hp & 7) || (Wp & 7)) return set_error(INNFER_ERR_INVALID, "window attention: %d x %d is not a whole number of 8 x 8 windows (the caller pads)", Hp, Wp);
     if (nH < 1 || nH > 8 || d < 1 || d > 32) return set_error(INNFER_ERR_UNSUPPORTED, "window attention: %d heads of %d channels (built: <= 8 heads, <= 32 channels)", nH, d);
@@ -150,11 +189,20 @@ int win_attn_launch(const f16* qkv, long gs, f16* out, long out_gs, const float*
     if (gs < G || out_gs < G) return set_error(INNFER_ERR_INVALID, "window attention: a group stride below N * Hp * Wp * 32");
     const long total = (long)N * nH * (Hp >> 3) * (Wp >> 3);
     if (total > 0x7ffffff0L) return set_error(INNFER_ERR_UNSUPPORTED, "window attention: %ld windows x heads exceed the launch grid", total);
-    GtScope gt(s, "window attention (8 x 8, all heads)", 4.0 * 64 * 64 * 32 * (double)total, (double)total * 64 * 32 * 2 * 4 + nH * 16384.0);
-    const WinAttn p{qkv, gs, out, out_gs, relb, N, Hp, Wp, nH, d, shift, (int)total};
-    hipLaunchKernelGGL(win_attn_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, s, p);
+    GtScope gt(s, cos ? "cosine window attention (8 x 8, all heads)" : "window attention (8 x 8, all heads)", 4.0 * 64 * 64 * 32 * (double)total, (double)total * 64 * 32 * 2 * 4 + nH * 16384.0);
+    const WinAttn p{qkv, gs, out, out_gs, relb, tau, N, Hp, Wp, nH, d, shift, (int)total};
+    if (cos) hipLaunchKernelGGL(win_attn_kernel<true>, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(win_attn_kernel<false>, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, s, p);
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
+}
+
+int win_attn_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, int N, int Hp, int Wp, int nH, int d, int shift, hipStream_t s) {
+    return win_attn_any(qkv, gs, out, out_gs, relb, nullptr, false, N, Hp, Wp, nH, d, shift, s);
+}
+
+int win_attn_cos_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, const float* tau, int N, int Hp, int Wp, int nH, int d, int shift, hipStream_t s) {
+    return win_attn_any(qkv, gs, out, out_gs, relb, tau, true, N, Hp, Wp, nH, d, shift, s);
 }
 
 }  // namespace innfer

@@ -207,6 +207,10 @@ SIGNATURES = {
     "innfer_net_set_attn_bias": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "innfer_window_attention": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     "innfer_layer_norm": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "innfer_swin2sr_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "innfer_net_set_attn_scale": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_window_attention_cos": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
+    "innfer_layer_norm_add": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "innfer_hat_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]),
     "innfer_net_set_chan_attn": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     "innfer_net_set_conv_scale": (C.c_int, [C.c_void_p, C.c_float]),

@@ -63,7 +63,10 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
         return _infer_realplksr(state_dict)
     if arch == 'swinir':
         hat = _infer_hat(state_dict)         # (a complete HAT key set; anything less goes on to SwinIR's sniffing and its refusals)
-        return hat if hat is not None else _infer_swinir(state_dict)
+        if hat is not None:
+            return hat
+        s2 = _infer_swin2sr(state_dict)      # (likewise: block 0's complete Swin2SR key set)
+        return s2 if s2 is not None else _infer_swinir(state_dict)
     if arch == 'pan':
         return _infer_pan(state_dict, scale, in_nc, out_nc)
     if arch == 'ppon':
@@ -268,6 +271,106 @@ def _infer_swinir(state_dict):
     cfg = {'type': 'swinir', 'in_nc': in_nc, 'nf': C, 'depths': depths, 'num_heads': [nh] * len(depths), 'window_size': ws, 'mlp_ratio': hidden / C, 'scale': up,
            'upsampler': upsampler, 'resi_connection': '3conv' if 'layers.0.conv.0.weight' in state_dict else '1conv'}
     return dict(arch='swinir', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=sum(depths), plus=False, state_dict=state_dict,
+                net_params=get_network_G_config(cfg, up))
+
+
+_SWIN2SR_KEYS = ('attn.logit_scale', 'attn.cpb_mlp.0.weight', 'attn.cpb_mlp.0.bias', 'attn.cpb_mlp.2.weight', 'attn.q_bias', 'attn.v_bias', 'attn.qkv.weight', 'norm1.weight',
+                 'mlp.fc1.weight')
+
+
+def _infer_swin2sr(state_dict):
+    """Swin2SR checkpoints (classical, lightweight and real-world super-resolution, and fine-tunes), or None unless block 0 carries the complete key set (_SWIN2SR_KEYS) and
+    neither attn.relative_position_bias_table nor attn.qkv.bias -- the caller then sniffs as before.  embed_dim and in_chans from conv_first, depths by counting blocks,
+    num_heads from attn.logit_scale, the width of cpb_mlp from its first Linear, mlp_ratio from mlp.fc1, '3conv' from layers.0.conv.0, the tail and the scale as
+    _infer_swinir.  There is no bias table to read the window from: it comes from attn.relative_coords_table ([1, 2 ws - 1, 2 ws - 1, 2]) or from
+    attn.relative_position_index ([ws^2, ws^2]) when the checkpoint carries one, and is ASSUMED to be 8 otherwise.  A stored relative_coords_table is authoritative: it is
+    handed on (coords_table) and feeds cpb_mlp in place of the formula; relative_position_index is rebuilt from its formula and a stored one that differs is refused;
+    attn_mask is never read.  All three buffers are dropped from the state dict handed back.  The compressed-SR (pixelshuffle_aux), pixelshuffle_hf and JPEG / denoising
+    forms, an absolute position embedding, another window, a checkpoint without patch_embed.norm or without q_bias / v_bias are refused."""
+    import math
+    import numpy as np
+    b0 = 'layers.0.residual_group.blocks.0.'
+    if b0 + 'attn.logit_scale' in state_dict and b0 + 'attn.cpb_mlp.0.weight' in state_dict and b0 + 'attn.qkv.weight' in state_dict and \
+            b0 + 'attn.relative_position_bias_table' not in state_dict and b0 + 'attn.qkv.bias' not in state_dict and \
+            (b0 + 'attn.q_bias' not in state_dict or b0 + 'attn.v_bias' not in state_dict):
+        raise NotImplementedError('Swin2SR checkpoint without attn.q_bias / attn.v_bias (qkv_bias=False): not built on the HIP path')
+    if any(b0 + k not in state_dict for k in _SWIN2SR_KEYS) or b0 + 'attn.relative_position_bias_table' in state_dict or b0 + 'attn.qkv.bias' in state_dict:
+        return None
+    if any(k.startswith(('conv_bicubic', 'conv_aux', 'conv_after_aux')) for k in state_dict):
+        raise NotImplementedError('Swin2SR checkpoint with the pixelshuffle_aux tail (conv_bicubic / conv_aux / conv_after_aux: the compressed-SR release): not built on the HIP path')
+    if any(k.startswith(('conv_first_hf', 'layers_hf', 'conv_after_body_hf', 'conv_before_upsample_hf', 'upsample_hf', 'conv_last_hf')) for k in state_dict):
+        raise NotImplementedError('Swin2SR checkpoint with the pixelshuffle_hf tail (conv_first_hf / layers_hf): not built on the HIP path')
+    if 'absolute_pos_embed' in state_dict:
+        raise NotImplementedError('Swin2SR checkpoint with absolute_pos_embed (ape=True): not built on the HIP path')
+    if 'patch_embed.norm.weight' not in state_dict:
+        raise NotImplementedError('Swin2SR checkpoint without patch_embed.norm (patch_norm=False): not built on the HIP path')
+    w0 = state_dict['conv_first.weight']
+    C, in_nc = int(w0.shape[0]), int(w0.shape[1])
+    depths = []
+    while f'layers.{len(depths)}.residual_group.blocks.0.norm1.weight' in state_dict:
+        i, j = len(depths), 0
+        while f'layers.{i}.residual_group.blocks.{j}.norm1.weight' in state_dict:
+            j += 1
+        depths.append(j)
+    nh = int(state_dict[b0 + 'attn.logit_scale'].shape[0])
+    cpb = int(state_dict[b0 + 'attn.cpb_mlp.0.weight'].shape[0])
+    hidden = int(state_dict[b0 + 'mlp.fc1.weight'].shape[0])
+    ws, coords = 8, None                     # (no buffer to read the window from: the published models' 8)
+    tables = [k for k in state_dict if k.endswith('attn.relative_coords_table')]
+    indices = [k for k in state_dict if k.endswith('attn.relative_position_index')]
+    if tables:
+        shp = tuple(state_dict[tables[0]].shape)
+        if len(shp) != 4 or shp[0] != 1 or shp[1] != shp[2] or shp[3] != 2 or shp[1] % 2 == 0:
+            raise NotImplementedError(f'Swin2SR checkpoint: {tables[0]} has shape {shp}, not [1, 2 ws - 1, 2 ws - 1, 2]')
+        ws = (shp[1] + 1) // 2
+    elif indices:
+        shp = tuple(state_dict[indices[0]].shape)
+        ws = math.isqrt(int(shp[0])) if len(shp) == 2 else 0
+        if len(shp) != 2 or shp[0] != shp[1] or ws * ws != shp[0]:
+            raise NotImplementedError(f'Swin2SR checkpoint: {indices[0]} has shape {shp}, not [ws^2, ws^2]')
+    if ws != 8:
+        raise NotImplementedError(f'Swin2SR checkpoint with window_size {ws}: only 8 x 8 windows are built on the HIP path')
+    if tables:
+        coords = state_dict[tables[0]].detach().cpu().double().numpy()
+        for k in tables:
+            v = state_dict[k]
+            if tuple(v.shape) != (1, 15, 15, 2):
+                raise NotImplementedError(f'Swin2SR checkpoint: {k} has shape {tuple(v.shape)}, not (1, 15, 15, 2)')
+            if not np.array_equal(v.detach().cpu().double().numpy(), coords):
+                raise NotImplementedError(f'Swin2SR checkpoint: {k} differs from {tables[0]} (one relative_coords_table for every block is built on the HIP path)')
+    if 'conv_up1.weight' in state_dict:
+        upsampler, up = 'nearest+conv', 4 if 'conv_up2.weight' in state_dict else 2
+        out_nc = int(state_dict['conv_last.weight'].shape[0])
+    elif 'conv_before_upsample.0.weight' in state_dict:
+        upsampler, up = 'pixelshuffle', 1
+        for k, v in state_dict.items():
+            if k.startswith('upsample.') and k.endswith('.weight'):
+                f = math.isqrt(int(v.shape[0]) // 64)
+                if f * f * 64 != int(v.shape[0]):
+                    raise Exception("Could not infer model parameters.")
+                up *= f
+        out_nc = int(state_dict['conv_last.weight'].shape[0])
+    elif 'upsample.0.weight' in state_dict:
+        upsampler = 'pixelshuffledirect'
+        k_up = int(state_dict['upsample.0.weight'].shape[0])
+        up = math.isqrt(k_up // in_nc) if k_up % in_nc == 0 else 0
+        if up * up * in_nc != k_up:
+            raise NotImplementedError(f'Swin2SR checkpoint: upsample.0 has {k_up} channels, not in_chans ({in_nc}) times a square (more output than input channels is not built on the HIP path)')
+        out_nc = in_nc
+    else:
+        raise NotImplementedError("Swin2SR checkpoint without an upsampler (upsampler '': the JPEG / denoising models): only the super-resolution forms are built on the HIP path")
+    if out_nc != in_nc:
+        raise NotImplementedError(f'Swin2SR checkpoint: conv_last has {out_nc} channels, conv_first takes {in_nc} (unequal channel counts are not built on the HIP path)')
+    from .architectures.SwinIR_arch import relative_position_index
+    want = relative_position_index(ws)
+    for k in indices:
+        v = state_dict[k]
+        if tuple(v.shape) != tuple(want.shape) or not bool((v.cpu().long() == want).all()):
+            raise NotImplementedError(f'Swin2SR checkpoint: {k} differs from (ri - rj + 7) * 15 + (ci - cj + 7), the index the engine builds its bias table with')
+    state_dict = {k: v for k, v in state_dict.items() if not (k.endswith('attn.relative_position_index') or k.endswith('attn.relative_coords_table') or k.endswith('.attn_mask'))}
+    cfg = {'type': 'swin2sr', 'in_nc': in_nc, 'nf': C, 'depths': depths, 'num_heads': [nh] * len(depths), 'window_size': ws, 'mlp_ratio': hidden / C, 'scale': up,
+           'upsampler': upsampler, 'resi_connection': '3conv' if 'layers.0.conv.0.weight' in state_dict else '1conv', 'cpb_hidden': cpb, 'coords_table': coords}
+    return dict(arch='swin2sr', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=sum(depths), plus=False, state_dict=state_dict,
                 net_params=get_network_G_config(cfg, up))
 
 

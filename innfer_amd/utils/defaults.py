@@ -155,6 +155,21 @@ def get_network_G_config(network_G, scale):
         cfg['upsampler'] = _pick(opts, 'upsampler', 'pixelshuffle')
         cfg['resi_connection'] = _pick(opts, 'resi_connection', '1conv')
         opts.pop('out_nc', None)
+    elif kind in ('swin2sr', 'swin2sr_net'):               # Swin2SR (SwinV2 blocks on SwinIR's skeleton): the published constructor surface
+        cfg['type'] = 'swin2sr'
+        cfg['in_chans'] = _pick(opts, 'in_nc', 3)
+        cfg['embed_dim'] = _pick(opts, 'nf', 180)
+        cfg['depths'] = list(_pick(opts, 'depths', [6] * 6))
+        cfg['num_heads'] = list(_pick(opts, 'num_heads', [6] * len(cfg['depths'])))
+        cfg['window_size'] = _pick(opts, 'window_size', 8)
+        cfg['mlp_ratio'] = _pick(opts, 'mlp_ratio', 2.0)
+        cfg['upscale'] = _pick(opts, 'scale', scale)
+        cfg['img_range'] = _pick(opts, 'img_range', 1.0)
+        cfg['upsampler'] = _pick(opts, 'upsampler', 'pixelshuffle')
+        cfg['resi_connection'] = _pick(opts, 'resi_connection', '1conv')
+        cfg['cpb_hidden'] = _pick(opts, 'cpb_hidden', 512)           # (the width of cpb_mlp: 512 in the published code, read off the checkpoint)
+        cfg['coords_table'] = _pick(opts, 'coords_table', None)      # the checkpoint's relative_coords_table, when it carries one
+        opts.pop('out_nc', None)
     elif kind in ('hat', 'hat_net'):                       # HAT (hybrid attention transformer on SwinIR's skeleton): the published constructor surface
         cfg['type'] = 'hat'
         cfg['in_chans'] = _pick(opts, 'in_nc', 3)
