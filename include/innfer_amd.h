@@ -45,7 +45,7 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): RealPLKSR -- innfer_plksr_create, innfer_net_set_group_norm, innfer_conv_args.act 11 (Mish), innfer_plk_conv (the partial large-kernel conv as a single launch), innfer_group_norm_skip / innfer_group_norm_skip_work_bytes (per-sample GroupNorm + skip over a 64-channel slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): SwinIR -- innfer_swinir_create, innfer_net_set_layer_norm, innfer_net_set_attn_bias, innfer_conv_args.act 12 (exact GELU on the 1x1 form), innfer_window_attention (the 8 x 8 window attention as a single launch), innfer_layer_norm (per-pixel LayerNorm over a padded slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a HAT): HAT -- innfer_hat_create, innfer_net_set_chan_attn, innfer_net_set_conv_scale, innfer_conv_args.act 13 (exact GELU on the plain 3x3 form), innfer_window_attention16 (the 16 x 16 window attention over a 16 x 16 or an overlapping 24 x 24 key window as a single launch), innfer_chan_attn_work_bytes / innfer_chan_attn_excite / innfer_chan_attn_scale_add (the channel attention's launches).  innfer_version() returns the library's; a binding should compare. */
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): RealPLKSR -- innfer_plksr_create, innfer_net_set_group_norm, innfer_conv_args.act 11 (Mish), innfer_plk_conv (the partial large-kernel conv as a single launch), innfer_group_norm_skip / innfer_group_norm_skip_work_bytes (per-sample GroupNorm + skip over a 64-channel slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): SwinIR -- innfer_swinir_create, innfer_net_set_layer_norm, innfer_net_set_attn_bias, innfer_conv_args.act 12 (exact GELU on the 1x1 form), innfer_window_attention (the 8 x 8 window attention as a single launch), innfer_layer_norm (per-pixel LayerNorm over a padded slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a HAT): HAT -- innfer_hat_create, innfer_net_set_chan_attn, innfer_net_set_conv_scale, innfer_conv_args.act 13 (exact GELU on the plain 3x3 form), innfer_window_attention16 (the 16 x 16 window attention over a 16 x 16 or an overlapping 24 x 24 key window as a single launch), innfer_chan_attn_work_bytes / innfer_chan_attn_excite / innfer_chan_attn_scale_add (the channel attention's launches).  Also added under 123 (additive: new entry points only, no struct or signature changed): the kernels of DAT's blocks as single launches -- innfer_window_attention_rect (rectangular windows in two transposed head branches), innfer_channel_attention_work_bytes / innfer_channel_attention_scores / innfer_channel_attention_apply (attention across channels over a whole sample), innfer_dwconv3x3 (depthwise 3 x 3 with its three epilogues), innfer_chan_attn_excite_gelu, innfer_aim_mix (the two gates that blend the attention and conv branches), innfer_layer_norm_wide (LayerNorm over up to 512 channels) -- and the network on them: innfer_dat_create, innfer_dat_block_floats, innfer_net_set_dat_block (innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a DAT).  innfer_version() returns the library's; a binding should compare. */
 #define INNFER_ABI_VERSION 123
 int innfer_version(void);
 const char* innfer_last_error(void);
@@ -286,6 +286,78 @@ size_t innfer_chan_attn_work_bytes(int N, int64_t HW, int c_pad);
 int innfer_chan_attn_excite(const void* d_z, int64_t z_gs, int N, int64_t HW, int C, int c_pad, int hidden, const float* h_w1, const float* h_b1, const float* h_w2,
                             const float* h_b2, void* d_y, void* d_sums, void* d_work, size_t work_bytes, void* stream);
 int innfer_chan_attn_scale_add(void* d_t, int64_t t_gs, const void* d_z, int64_t z_gs, const void* d_y, float conv_scale, int N, int64_t HW, int c_pad, void* stream);
+/* (123, additive) The kernels of a DAT block (Chen et al. 2023, "Dual Aggregation Transformer for Image Super-Resolution"; the reference has no such architecture) as single
+ * launches, for tests.  All slabs hold N x H x W (or N x HW) pixels WITHOUT padding; *_gs are group strides in elements; every entry uploads its host parameters, launches, waits.
+ *
+ * innfer_window_attention_rect (csrc/win_attn_rect.hip): attention over rectangular windows in two head branches of transposed shape.  d_qkv / d_out as
+ * innfer_window_attention's (3 num_heads / num_heads groups of 32 channels; q already scaled).  split [s0, s1] is [8, 32] or [8, 16], T = s0 s1; heads 0 .. nH / 2 - 1 use
+ * windows of s0 rows x s1 columns and shift (s0 / 2, s1 / 2), heads nH / 2 .. nH - 1 windows of s1 x s0 and shift (s1 / 2, s0 / 2) (num_heads even).  The windows tile the
+ * frame Hp x Wp = H, W rounded up to multiples of s1 -- rolled by minus the shift when shifted != 0; a token whose stored pixel lies outside H x W has q = k = v = 0: it is
+ * never read and never stored, as a key its score is bias + mask and it takes part in the softmax.  Shifted: -100 between tokens whose labels 3 a(r) + b(c) in the rolled
+ * frame differ (a = 0 below Hp - wh, 1 below Hp - shy, else 2; b likewise with Wp, ww, shx, for the head's own window wh x ww and shift).  h_bias: [num_heads][T][T] host
+ * floats, query-major, tokens row-major inside the head's own window shape.  Arithmetic as innfer_window_attention16's: fp32 scores, running maximum and sum over blocks of 64
+ * keys; P rounded to fp16 in front of P v; fp32 accumulation; one rounding of o / sum; channels >= head_dim written as zeros. */
+int innfer_window_attention_rect(const void* d_qkv, int64_t qkv_gs, void* d_out, int64_t out_gs, const float* h_bias, int N, int H, int W, int num_heads, int head_dim,
+                                 int s0, int s1, int shifted, void* stream);
+/* innfer_channel_attention_scores / _apply (csrc/chan_self_attn.hip): attention across the head_dim channels of a head over all HW pixels of one sample, on the same qkv slab
+ * (q and k unscaled; whatever their channels >= head_dim hold is ignored).  scores: G[x][y] = sum_n q[n][x] k[n][y], sq[x] = sum_n q[n][x]^2, sk[y] likewise -- fp32 fma
+ * chains over segments of 1024 pixels in order, the segments merged in index order (bit-identical on a repeat) -- then
+ * A[x][y] = softmax_y((G[x][y] (rq[x] rk[y])) temperature[h]), r = 1 / max(sqrtf(s), 1e-12), in fp32.  d_A: [N][num_heads][32][32] floats, rows and columns >= head_dim zeros;
+ * d_gram (may be NULL): [N][num_heads][1088] floats, the merged G [32][32], sq [32], sk [32]; d_work: innfer_channel_attention_work_bytes bytes; d_A and d_work 16-byte
+ * aligned; h_temperature: num_heads host floats.  apply: d_out[n][x] = fp16(sum_{y < head_dim} A[x][y] v[n][y]), an fp32 fma chain over y in order, one rounding, into
+ * num_heads groups whose channels >= head_dim are written as zeros.  Nothing crosses samples. */
+size_t innfer_channel_attention_work_bytes(int N, int64_t HW, int num_heads);
+int innfer_channel_attention_scores(const void* d_qkv, int64_t qkv_gs, int N, int64_t HW, int num_heads, int head_dim, const float* h_temperature, void* d_A, void* d_gram,
+                                    void* d_work, size_t work_bytes, void* stream);
+int innfer_channel_attention_apply(const void* d_qkv, int64_t qkv_gs, void* d_out, int64_t out_gs, const void* d_A, int N, int64_t HW, int num_heads, int head_dim, void* stream);
+/* innfer_dwconv3x3 (csrc/dwconv.hip): depthwise 3 x 3 conv, zero padding, over slabs of c_pad channels (a multiple of 32, <= 512).  h_taps [C][3][3], h_bias [C] host floats
+ * (a BatchNorm behind the conv is folded into both by the caller).  Per value f = bias, then f = fma(tap, x, f) over the nine taps row-major in fp32; epilogue 0: f; 1: the
+ * exact GELU of the conv kernels' act 12; 2: f * d_mul (a second slab of the same shape; NULL otherwise); ONE fp16 rounding.  Channels C .. c_pad - 1 are written as zeros.
+ * d_out must not be d_in. */
+int innfer_dwconv3x3(const void* d_in, int64_t in_gs, const void* d_mul, int64_t mul_gs, void* d_out, int64_t out_gs, int N, int H, int W, int C, int c_pad,
+                     const float* h_taps, const float* h_bias, int epilogue, void* stream);
+/* innfer_chan_attn_excite_gelu: innfer_chan_attn_excite with the exact GELU, f (1 + erff(f / sqrt 2)) / 2, on the hidden units in place of the ReLU (DAT's
+ * channel_interaction with its BatchNorm folded into W1 / b1).  Arguments, sums, merge order and limits as innfer_chan_attn_excite's. */
+int innfer_chan_attn_excite_gelu(const void* d_z, int64_t z_gs, int N, int64_t HW, int C, int c_pad, int hidden, const float* h_w1, const float* h_b1, const float* h_w2,
+                                 const float* h_b2, void* d_y, void* d_sums, void* d_work, size_t work_bytes, void* stream);
+/* innfer_aim_mix (csrc/aim_mix.hip): d_out = fp16(fma(X, gate[n][c], Y * s[pixel])), s = sigmoid(w2 . GELU(W1 X[pixel] + b1) + b2) -- DAT's spatial_interaction (1x1 conv
+ * C -> hidden with its BatchNorm folded in, exact GELU, 1x1 conv hidden -> 1) and the blend of the two branches in ONE launch.  d_x, d_y, d_out: slabs of c_pad channels (64,
+ * 128, 192, 256); d_gate: N x c_pad device floats (innfer_chan_attn_excite_gelu's d_y); h_w1 [hidden][C], h_b1 [hidden], h_w2 [hidden] host floats; hidden <= 16.  fp32: per
+ * hidden unit an fma chain over a lane's 8-channel pieces and a 4-lane butterfly, erff, expf, the division; one fma and one fp16 rounding per output.  X's channels >= C are
+ * ignored; out's are written as zeros.  d_out may be d_x or d_y. */
+int innfer_aim_mix(const void* d_x, int64_t x_gs, const void* d_y, int64_t y_gs, void* d_out, int64_t out_gs, const void* d_gate, int N, int64_t HW, int C, int c_pad,
+                   int hidden, const float* h_w1, const float* h_b1, const float* h_w2, float b2, void* stream);
+/* innfer_layer_norm_wide: innfer_layer_norm over slabs of up to 512 channels (c_pad % 64 == 0; DAT's ffn.sg.norm on half the hidden channels).  Same arithmetic and order. */
+int innfer_layer_norm_wide(const void* d_in, int64_t in_gs, void* d_out, int64_t out_gs, int64_t npix, int C, int c_pad, const float* h_gamma, const float* h_beta, float eps,
+                           void* stream);
+/* (123, additive) DAT (Chen et al. 2023, "Dual Aggregation Transformer for Image Super-Resolution"; the reference has no such architecture), the published dat_arch.py, on
+ * SwinIR's skeleton WITHOUT padding (the engine works on H x W).  C = embed_dim, nH heads of d = C / nH, split = [s0, s1], hid = hidden, tokens = pixels:
+ *   forward(x):  f = conv_first(x - mean); f = conv_after_body(norm(RGs(before_RG.1(f)))) + f; tail (pixelshuffle | pixelshuffledirect); + mean
+ *   RG i:        t = conv(blocks(t)) + t                      ('1conv' | '3conv' as SwinIR's)
+ *   block b:     t = t + attn(norm1(t));  t = t + ffn(norm2(t));   attn: even b (inside its group) the windows (ASA), odd b the channels (ACA)
+ *   ASA:         the attention of innfer_window_attention_rect over qkv = Linear(C, 3 C)(u); shifted when (i even and b > 0 and (b - 2) % 4 == 0) or (i odd and b % 4 == 0),
+ *                or where h_shift (one int per block, counted through the groups; may be NULL) says so
+ *   ACA:         the attention of innfer_channel_attention_scores / _apply with temperature[h]
+ *   both:        c = GELU(BN(dwconv3x3(v)));  out = proj(X sigmoid(cm(mean_pixels(Y))) + Y sigmoid(sm(X))), (X, Y) = (a, c) for ASA, (c, a) for ACA (innfer_aim_mix);
+ *                the mean runs over the H x W grid of ONE sample of whatever the forward is given
+ *   ffn:         h = GELU(fc1(u)); x1, x2 = halves; fc2(x1 * dwconv3x3(LayerNorm(hid / 2)(x2)))
+ * on the engine of innfer_net_*, laid out as innfer_swinir_create's.  Conv slots `<state-dict key>#<p>` in forward order: conv_first; per block attn.qkv (rows as SwinIR's
+ * re-layout, the q rows of an ODD block WITHOUT d^-0.5), attn.proj (columns head x 32), ffn.fc1 (rows: x1's hid / 2 padded to h1p = 64 ceil(hid / 128) with zero rows,
+ * then x2's likewise), ffn.fc2 (h1p input columns); per group its conv; conv_after_body; the tail.  LayerNorms (innfer_net_set_layer_norm): 0 before_RG.1; 1 + 2 k and
+ * 2 + 2 k norm1 / norm2 of block k (counted through the groups); the last one norm.  innfer_net_set_attn_bias(net, k, .) takes the dense [nH][T][T] table of an EVEN block
+ * (T = s0 s1; heads nH / 2 .. nH - 1 in their own s1 x s0 token order); innfer_net_set_dat_block everything else of block k, in the head-padded channel order
+ * (channel 32 h + e = channel d h + e of the model for e < d, zeros for e >= d; Chp = 32 nH), as ONE array of innfer_dat_block_floats(net) host floats:
+ *   dwconv taps [Chp][9], bias [Chp] (BatchNorm folded) | channel_interaction W1 [C / 8][Chp], b1 [C / 8] (BatchNorm folded), W2 [Chp][C / 8], b2 [Chp] |
+ *   spatial_interaction W1 [C / 16][Chp], b1 [C / 16] (BatchNorm folded), w2 [C / 16], b2 [1] | ffn.sg.norm gamma [hid / 2], beta [hid / 2] |
+ *   ffn.sg.conv taps [hid / 2][9], bias [hid / 2] | temperature [nH] (zeros for an even block)
+ * Limits: C in 16 .. 256, nH 2, 4, 6 or 8, d <= 32, hid even and <= 1024, split [8, 32] or [8, 16], in_nc == out_nc in 1 .. 4, upsampler 0 pixelshuffle | 1
+ * pixelshuffledirect, scale 2, 3, 4; fp16 mode only.  Launches of a forward, with B0 / B1 the blocks of even / odd index in their group, R the groups, S1 = C_pad / 64,
+ * SQ = 3 nH / 2, SF = 2 h1p / 64, SR = S1 ('1conv') or 2 ceil(C / 256) + S1 ('3conv'), T = 2 (pixelshuffledirect), 2 + log2(scale) (pixelshuffle 2 / 4), 4 (pixelshuffle 3):
+ *   S1 + 2 + B0 (9 + SQ + 2 S1 + SF) + B1 (11 + SQ + 2 S1 + SF) + (R + 1) SR + T. */
+int innfer_dat_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int hidden, int s0, int s1, int upsampler,
+                      int scale, int conv3, const float* h_mean, const int* h_shift);
+size_t innfer_dat_block_floats(innfer_net_t net);
+int innfer_net_set_dat_block(innfer_net_t net, int blk, const float* h_params, size_t n_floats);
 /* The activation behind conv `idx` as K host floats: y = x >= 0 ? x : h_slope[c] * x -- nn.PReLU(num_parameters = K).weight, or the constant 0 (ReLU) / 0.1
  * (LeakyReLU(0.1)).  Load time, synchronous.  Every conv of an SRVGGNetCompact except the last needs one before the first forward; other convs refuse it. */
 int innfer_net_set_conv_slope(innfer_net_t net, int idx, const float* h_slope);

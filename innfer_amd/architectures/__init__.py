@@ -39,6 +39,8 @@ def get_network(opt_net):
         from .Swin2SR_arch import Swin2SR as net
     elif kind in ('hat', 'hat_net'):
         from .HAT_arch import HAT as net
+    elif kind in ('dat', 'dat_net'):
+        from .DAT_arch import DAT as net
     else:
         raise NotImplementedError('Model [{:s}] not recognized'.format(kind))
     return net(**opt_net)

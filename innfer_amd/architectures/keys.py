@@ -320,6 +320,80 @@ def hat_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=6
     return s
 
 
+def dat_pos_dim(embed_dim):
+    """Width of the DynamicPosBias MLP of a DAT branch as recalled from the published code (the branch's dim // 4, again // 4); a checkpoint's pos_proj.weight decides."""
+    return ((embed_dim // 2) // 4) // 4
+
+
+def dat_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=6, expansion_factor=4.0, upscale=4, upsampler='pixelshuffle', resi_connection='1conv',
+               pos_dim=None):
+    """State-dict key -> shape of the PARAMETERS (and BatchNorm statistics) of DAT (the published dat_arch.py, written down without the source at hand).  THE ONE PLACE a
+    correction of a key name or a shape goes: the shell, the loader, the synthetic checkpoints and the tests' reference are all built from this table.  Not in it, because
+    they are buffers: attn.attns.<0|1>.rpe_biases, attn.attns.<0|1>.relative_position_index and, on shifted blocks, attn.attn_mask_0 / _1."""
+    C, nH, s = embed_dim, num_heads, {}
+    hid = int(C * expansion_factor)
+    p = dat_pos_dim(C) if pos_dim is None else pos_dim
+
+    def lin(k, co, ci):
+        s[k + '.weight'], s[k + '.bias'] = (co, ci), (co,)
+
+    def conv(k, co, ci, ks=3):
+        s[k + '.weight'], s[k + '.bias'] = (co, ci, ks, ks), (co,)
+
+    def norm(k, c=C):
+        s[k + '.weight'], s[k + '.bias'] = (c,), (c,)
+
+    def resi(k):
+        if resi_connection == '3conv':
+            conv(k + '.0', C // 4, C); conv(k + '.2', C // 4, C // 4, 1); conv(k + '.4', C, C // 4)
+        else:
+            conv(k, C, C)
+    conv('conv_first', C, in_chans)
+    norm('before_RG.1')
+    for i, depth in enumerate(depths):
+        for j in range(depth):
+            b = f'layers.{i}.blocks.{j}.'
+            norm(b + 'norm1')
+            lin(b + 'attn.qkv', 3 * C, C)
+            lin(b + 'attn.proj', C, C)
+            conv(b + 'attn.dwconv.0', C, 1)                          # depthwise: groups = C
+            _bn(s, b + 'attn.dwconv.1', C)
+            conv(b + 'attn.channel_interaction.1', C // 8, C, 1)
+            _bn(s, b + 'attn.channel_interaction.2', C // 8)
+            conv(b + 'attn.channel_interaction.4', C, C // 8, 1)
+            conv(b + 'attn.spatial_interaction.0', C // 16, C, 1)
+            _bn(s, b + 'attn.spatial_interaction.1', C // 16)
+            conv(b + 'attn.spatial_interaction.3', 1, C // 16, 1)
+            if j % 2 == 0:
+                for br in (0, 1):
+                    a = b + f'attn.attns.{br}.pos.'
+                    lin(a + 'pos_proj', p, 2)
+                    for m in ('pos1', 'pos2'):
+                        norm(a + m + '.0', p); lin(a + m + '.2', p, p)
+                    norm(a + 'pos3.0', p); lin(a + 'pos3.2', nH // 2, p)
+            else:
+                s[b + 'attn.temperature'] = (nH, 1, 1)
+            norm(b + 'norm2')
+            lin(b + 'ffn.fc1', hid, C)
+            norm(b + 'ffn.sg.norm', hid // 2)
+            conv(b + 'ffn.sg.conv', hid // 2, 1)                     # depthwise: groups = hid / 2
+            lin(b + 'ffn.fc2', C, hid // 2)
+        resi(f'layers.{i}.conv')
+    norm('norm')
+    resi('conv_after_body')
+    if upsampler == 'pixelshuffledirect':
+        conv('upsample.0', upscale * upscale * in_chans, C)
+        return s
+    conv('conv_before_upsample.0', 64, C)
+    if upscale == 3:
+        conv('upsample.0', 576, 64)
+    else:
+        for st in range(max(1, upscale.bit_length() - 1)):
+            conv(f'upsample.{2 * st}', 256, 64)
+    conv('conv_last', in_chans, 64)
+    return s
+
+
 def srresnet_layout(nb, norm=False, mode='CNA'):
     """Positions of a ResNetBlock's / LR_conv's layers inside the flattened Sequentials (SRResNet_arch.py:23-27,68-86; block.py:242-254,
     B.sequential flattens nested Sequentials): {engine key -> (conv key, BatchNorm in front of the conv or None, BatchNorm behind it or None)}.

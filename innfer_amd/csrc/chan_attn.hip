@@ -5,7 +5,7 @@
 //   ca_pool       a workgroup reads a segment of CA_SEG pixels x 32 channels ONCE (16-byte loads, 16 pixels x 8 channels per thread) and writes the segment's 32 channel sums.
 //                 fp32, a fixed order (the thread's pixels in order, the xor butterfly over the wave's 16 pixel lanes, the four waves in index order): deterministic, no atomics.
 //   ca_excite     one workgroup per sample: thread c merges channel c's segment sums in index order, the mean is the total times 1 / HW; thread j < hid the hidden unit j
-//                 (fp32 fma over the channels in order, ReLU); thread c the output (fma over the hidden units in order, 1 / (1 + exp(-x))).  y of a pad channel is 0.
+//                 (fp32 fma over the channels in order, ReLU -- or, in the GELU form of DAT's channel_interaction, f (1 + erff(f / sqrt 2)) / 2); thread c the output (fma over the hidden units in order, 1 / (1 + exp(-x))).  y of a pad channel is 0.
 //   ca_scale_add  per value fmaf(conv_scale * y[n][c], z, t) in fp32 and one fp16 rounding; in place on t.  Memory bound: 2 x 64 bytes in, 64 out per pixel and group.
 // Nothing crosses samples: a batch's sample equals its own forward bit for bit.
 #include "common.h"
@@ -45,6 +45,7 @@ __global__ __launch_bounds__(256) void ca_pool_kernel(const f16* z, long gs, lon
     if (t < 32) part[((long)n * nseg + sg) * c_pad + grp * 32 + t] = ((red[0][t] + red[1][t]) + red[2][t]) + red[3][t];
 }
 
+template <bool GELU>
 __global__ __launch_bounds__(256) void ca_excite_kernel(const float* part, int nseg, long HW, int C, int c_pad, int hid, const float* w1, const float* b1, const float* w2,
                                                         const float* b2, float* y, float* sums) {
     __shared__ float mean[256], hv[64];
@@ -59,7 +60,8 @@ __global__ __launch_bounds__(256) void ca_excite_kernel(const float* part, int n
     if (t < hid) {
         float s = b1[t];
         for (int c = 0; c < C; ++c) s = __builtin_fmaf(w1[t * C + c], mean[c], s);
-        hv[t] = fmaxf(s, 0.f);
+        if constexpr (GELU) hv[t] = (0.5f * s) * (1.0f + erff(s * 0.70710678118654752440f));
+        else hv[t] = fmaxf(s, 0.f);
     }
     __syncthreads();
     if (t < c_pad) {
@@ -114,15 +116,27 @@ int ca_pool_launch(const f16* z, long z_gs, int N, long HW, int c_pad, float* wo
 }
 
 // w1 [hid][C], b1 [hid], w2 [C][hid], b2 [C]: device floats; y: N x c_pad floats; sums (may be null): the merged channel sums, N x c_pad floats
-int ca_excite_launch(const float* work, int N, long HW, int C, int c_pad, int hid, const float* w1, const float* b1, const float* w2, const float* b2, float* y, float* sums,
-                     hipStream_t s) {
+template <bool GELU>
+static int ca_excite_any(const float* work, int N, long HW, int C, int c_pad, int hid, const float* w1, const float* b1, const float* w2, const float* b2, float* y, float* sums,
+                         hipStream_t s) {
     if (!work || !w1 || !b1 || !w2 || !b2 || !y) return set_error(INNFER_ERR_INVALID, "channel attention (excite): null argument");
     if (int rc = ca_check("excite", N, HW, c_pad)) return rc;
     if (C < 1 || C > c_pad || hid < 1 || hid > 64) return set_error(INNFER_ERR_UNSUPPORTED, "channel attention (excite): C=%d of %d, %d hidden channels (built: <= 64)", C, c_pad, hid);
     GtScope gt(s, "channel attention: squeeze / excite", 4.0 * C * hid * N, 4.0 * N * ((double)ca_nseg(HW) * c_pad + c_pad) + 8.0 * C * hid);
-    hipLaunchKernelGGL(ca_excite_kernel, dim3((unsigned)N), dim3(256), 0, s, work, ca_nseg(HW), HW, C, c_pad, hid, w1, b1, w2, b2, y, sums);
+    hipLaunchKernelGGL(ca_excite_kernel<GELU>, dim3((unsigned)N), dim3(256), 0, s, work, ca_nseg(HW), HW, C, c_pad, hid, w1, b1, w2, b2, y, sums);
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
+}
+
+int ca_excite_launch(const float* work, int N, long HW, int C, int c_pad, int hid, const float* w1, const float* b1, const float* w2, const float* b2, float* y, float* sums,
+                     hipStream_t s) {
+    return ca_excite_any<false>(work, N, HW, C, c_pad, hid, w1, b1, w2, b2, y, sums, s);
+}
+
+// The same with the exact GELU, f (1 + erff(f / sqrt 2)) / 2, in place of the ReLU on the hidden units (DAT's channel_interaction, its BatchNorm folded into w1 / b1 at load)
+int ca_excite_gelu_launch(const float* work, int N, long HW, int C, int c_pad, int hid, const float* w1, const float* b1, const float* w2, const float* b2, float* y,
+                          float* sums, hipStream_t s) {
+    return ca_excite_any<true>(work, N, HW, C, c_pad, hid, w1, b1, w2, b2, y, sums, s);
 }
 
 int ca_scale_add_launch(f16* t, long t_gs, const f16* z, long z_gs, const float* y, float scale, int N, long HW, int c_pad, hipStream_t s) {

@@ -283,6 +283,28 @@ int ca_excite_launch(const float* work, int N, long HW, int C, int c_pad, int hi
                      hipStream_t s);
 int ca_scale_add_launch(f16* t, long t_gs, const f16* z, long z_gs, const float* y, float scale, int N, long HW, int c_pad, hipStream_t s);
 
+// ---- DAT's own kernels ----
+// attention over rectangular windows in two head branches of transposed shape (win_attn_rect.hip): slabs of N x H x W pixels (NO pad: a token outside H x W is a zero
+// operand), split [s0, s1] = [8, 32] | [8, 16], relb: dense fp32 [nH][s0 s1][s0 s1], shifted 0 | 1
+int win_attn_rect_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, int N, int H, int W, int nH, int d, int s0, int s1, int shifted, hipStream_t s);
+// attention across channels over all pixels of a sample (chan_self_attn.hip): the Gram matrix and the norms -> A [N][nH][32][32] fp32 (two launches), a = A v (one)
+size_t csa_work_floats(int N, long HW, int nH);
+int csa_scores_launch(const f16* qkv, long gs, int N, long HW, int nH, int d, const float* temp, float* work, float* A, float* gram, hipStream_t s);
+int csa_gram_launch(const f16* qkv, long gs, int N, long HW, int nH, int d, float* work, hipStream_t s);
+int csa_softmax_launch(const float* work, int N, long HW, int nH, int d, const float* temp, float* A, float* gram, hipStream_t s);
+int csa_apply_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* A, int N, long HW, int nH, int d, hipStream_t s);
+// depthwise 3 x 3 over a slab of c_pad <= 512 channels (dwconv.hip): epilogue 0 none | 1 GELU | 2 times the slab `mul`; taps [C][9], bias [C] device floats
+int dwconv3x3_launch(const f16* in, long in_gs, const f16* mul, long mul_gs, f16* out, long out_gs, int N, int H, int W, int C, int c_pad, const float* taps, const float* bias,
+                     int epilogue, hipStream_t s);
+// chan_attn.hip's squeeze / excite with the exact GELU on the hidden units
+int ca_excite_gelu_launch(const float* work, int N, long HW, int C, int c_pad, int hid, const float* w1, const float* b1, const float* w2, const float* b2, float* y,
+                          float* sums, hipStream_t s);
+// out = fp16(x * gate[n][c] + y * sigmoid(w2 . GELU(W1 x + b1) + b2)[pixel]) (aim_mix.hip): gate N x c_pad, w1 [hid][C], b1 [hid], w2 [hid] device floats; hid <= 16
+int aim_mix_launch(const f16* x, long x_gs, const f16* y, long y_gs, f16* out, long out_gs, const float* gate, int N, long HW, int C, int c_pad, int hid, const float* w1,
+                   const float* b1, const float* w2, float b2, hipStream_t s);
+// layer_norm_launch over slabs of up to 512 channels (layer_norm.hip)
+int layer_norm_wide_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s);
+
 // ---- layout / tiles / blend / pre-post (tiles.hip) ---------------------------
 int nchw_to_slab(const void* src, int src_f32, f16* slab, long gstride, int ch_off, int N, int C, int H, int W, hipStream_t s);
 int slab_to_nchw(const f16* slab, long gstride, int ch_off, void* dst, int dst_f32, int N, int C, int H, int W, hipStream_t s);

@@ -71,12 +71,14 @@ __global__ __launch_bounds__(256) void layer_norm_kernel(const LnArgs p) {
 
 }  // namespace
 
-// c_pad: channels of both slabs (a multiple of 64, >= C, <= 256): every group is read and written.  gamma / beta: device floats, at least C each (the values behind C are never read)
-template <bool ADD>
+// c_pad: channels of both slabs (a multiple of 64, >= C, <= MAXC: 256, or 512 in the wide form without residual): every group is read and written.  gamma / beta: device floats, at least C each (the values behind C are never read)
+template <bool ADD, int MAXC = 256>
 static int layer_norm_any(const f16* in, long in_gs, const f16* res, long res_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s) {
     if (ADD && (!res || res_gs < npix * 32)) return set_error(INNFER_ERR_INVALID, "layer norm: the residual is null or its group stride below %ld pixels x 32", npix);
     if (!in || !out || !gamma || !beta || npix <= 0) return set_error(INNFER_ERR_INVALID, "layer norm: null argument or %ld pixels", npix);
-    if (C < 1 || c_pad < C || c_pad > 256 || c_pad % 64) return set_error(INNFER_ERR_UNSUPPORTED, "layer norm: C=%d in a slab of %d channels (built: slabs of 64, 128, 192 or 256 channels -- at most eight groups in a quad's registers)", C, c_pad);
+    if (C < 1 || c_pad < C || c_pad > MAXC || c_pad % 64)
+        return set_error(INNFER_ERR_UNSUPPORTED, MAXC == 256 ? "layer norm: C=%d in a slab of %d channels (built: slabs of 64, 128, 192 or 256 channels -- at most eight groups in a quad's registers)"
+                                                             : "layer norm (wide): C=%d in a slab of %d channels (built: slabs of 64 .. 512 channels in steps of 64 -- at most sixteen groups in a quad's registers)", C, c_pad);
     if (in_gs < npix * 32 || out_gs < npix * 32) return set_error(INNFER_ERR_INVALID, "layer norm: a group stride below %ld pixels x 32", npix);
     const long nblk = (npix * 4 + 255) / 256;
     if (nblk > 0x7fffffffL) return set_error(INNFER_ERR_UNSUPPORTED, "layer norm: %ld pixels exceed the launch grid", npix);
@@ -88,7 +90,17 @@ static int layer_norm_any(const f16* in, long in_gs, const f16* res, long res_gs
         case 2: hipLaunchKernelGGL((layer_norm_kernel<2, ADD>), grid, block, 0, s, p); break;
         case 4: hipLaunchKernelGGL((layer_norm_kernel<4, ADD>), grid, block, 0, s, p); break;
         case 6: hipLaunchKernelGGL((layer_norm_kernel<6, ADD>), grid, block, 0, s, p); break;
-        default: hipLaunchKernelGGL((layer_norm_kernel<8, ADD>), grid, block, 0, s, p); break;
+        case 8: hipLaunchKernelGGL((layer_norm_kernel<8, ADD>), grid, block, 0, s, p); break;
+        default:
+            if constexpr (MAXC > 256 && !ADD) {
+                switch (ng) {
+                    case 10: hipLaunchKernelGGL((layer_norm_kernel<10, false>), grid, block, 0, s, p); break;
+                    case 12: hipLaunchKernelGGL((layer_norm_kernel<12, false>), grid, block, 0, s, p); break;
+                    case 14: hipLaunchKernelGGL((layer_norm_kernel<14, false>), grid, block, 0, s, p); break;
+                    default: hipLaunchKernelGGL((layer_norm_kernel<16, false>), grid, block, 0, s, p); break;
+                }
+            }
+            break;
     }
     INNFER_HIP(hipGetLastError());
     return INNFER_OK;
@@ -96,6 +108,11 @@ static int layer_norm_any(const f16* in, long in_gs, const f16* res, long res_gs
 
 int layer_norm_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s) {
     return layer_norm_any<false>(in, in_gs, nullptr, 0, out, out_gs, npix, C, c_pad, gamma, beta, eps, s);
+}
+
+// The same over slabs of up to 512 channels (DAT's ffn.sg.norm on half the hidden channels): up to sixteen groups, 128 values, in a quad's registers; in == out allowed
+int layer_norm_wide_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s) {
+    return layer_norm_any<false, 512>(in, in_gs, nullptr, 0, out, out_gs, npix, C, c_pad, gamma, beta, eps, s);
 }
 
 // out = fp16(res + LayerNorm(C)(in)): `res` a third slab of c_pad channels; out may be res or in

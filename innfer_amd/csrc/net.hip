@@ -136,7 +136,14 @@ struct innfer_net {
     // Swin2SR (kind 7; innfer_swin2sr_create) on SwinIR's fields, slots and workspace: cosine attention (sw_tau[blk]: nH floats, innfer_net_set_attn_scale) and the
     // LayerNorm BEHIND each branch (t = t + norm(branch)); sw_relb holds 16 sigmoid(cpb_mlp(coords)) gathered into the same dense [nH][64][64] table
     std::vector<float*> sw_tau;
-    bool span_norm = false;      // SPAN(norm=True): conv_1 reads (x - mean) * img_range through FirstConvLaunch.in_map (convs[0].d_map: alpha[in_nc] then shift[in_nc])
+    // DAT (kind 8; innfer_dat_create) on SwinIR's fields on the UNPADDED grid: split [dat_s0, dat_s1], per block whether its windows are those of the rolled frame
+    // (dat_shift), the feed-forward's half padded to dat_h1p (sw_hp = 2 dat_h1p: x1's block, then x2's), and per block one device array (innfer_net_set_dat_block, the
+    // order documented in the header) with the offsets below; sw_relb holds the [nH][T][T] table of the even blocks only
+    int dat_s0 = 8, dat_s1 = 32, dat_h1p = 0;
+    std::vector<int> dat_shift, dat_aca;         // per block (counted through the groups): shifted windows; 1 = the channel form (odd index INSIDE its group)
+    std::vector<float*> dat_blk;
+    std::vector<float> dat_sib2;                 // the last bias of spatial_interaction per block (a kernel argument)
+    bool span_norm = false;     // SPAN(norm=True): conv_1 reads (x - mean) * img_range through FirstConvLaunch.in_map (convs[0].d_map: alpha[in_nc] then shift[in_nc])
     int in_nc = 3, out_nc = 3, nf = 64, nb = 23, gc = 32, scale = 4, n_up = 2;
     int final_act = 0;           // `finalact` of the reference constructors: activation after the last conv (ConvLaunch.act codes)
     int band_rows = 0;
@@ -468,7 +475,7 @@ extern "C" int innfer_swin2sr_create(innfer_net_t* out, int in_nc, int out_nc, i
 // groups), the last one norm.  Load time, synchronous.
 extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float* h_gamma, const float* h_beta) {
     if (!net || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "set_layer_norm: null argument");
-    if (net->kind != 5 && net->kind != 6 && net->kind != 7) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR, HAT, Swin2SR)");
+    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR, HAT, Swin2SR, DAT)");
     if (idx < 0 || idx >= (int)net->sw_ln.size()) return set_error(INNFER_ERR_INVALID, "set_layer_norm: index %d of %zu", idx, net->sw_ln.size());
     std::vector<float> h(2 * (size_t)net->sw_cp, 0.f);
     for (int c = 0; c < net->sw_c; ++c) { h[c] = h_gamma[c]; h[net->sw_cp + c] = h_beta[c]; }
@@ -480,10 +487,12 @@ extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float*
 // The relative position bias of block `blk` of a SwinIR as the dense table the attention reads: [num_heads][64 query][64 key] host floats.  Load time, synchronous.
 extern "C" int innfer_net_set_attn_bias(innfer_net_t net, int blk, const float* h_bias) {
     if (!net || !h_bias) return set_error(INNFER_ERR_INVALID, "set_attn_bias: null argument");
-    if (net->kind != 5 && net->kind != 6 && net->kind != 7) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_bias: the network has no window attention (built: SwinIR, HAT, Swin2SR)");
+    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_bias: the network has no window attention (built: SwinIR, HAT, Swin2SR, DAT)");
     if (blk < 0 || blk >= (int)net->sw_relb.size()) return set_error(INNFER_ERR_INVALID, "set_attn_bias: block %d of %zu", blk, net->sw_relb.size());
     // (HAT: table `blk` in forward order -- [num_heads][256][256] of a HAB, [num_heads][256][576] of a residual group's OCAB)
-    const size_t nb = (size_t)net->sw_nh * (net->kind == 6 ? 256 * (size_t)net->sw_relb_kw[blk] * net->sw_relb_kw[blk] : 4096) * sizeof(float);
+    // (DAT: [num_heads][T][T], T = s0 s1, of an even block; the odd blocks take none)
+    const size_t dat_t = (size_t)net->dat_s0 * net->dat_s1;
+    const size_t nb = (size_t)net->sw_nh * (net->kind == 6 ? 256 * (size_t)net->sw_relb_kw[blk] * net->sw_relb_kw[blk] : net->kind == 8 ? dat_t * dat_t : 4096) * sizeof(float);
     if (!net->sw_relb[blk]) INNFER_HIP(hipMalloc((void**)&net->sw_relb[blk], nb));
     INNFER_HIP(hipMemcpy(net->sw_relb[blk], h_bias, nb, hipMemcpyHostToDevice));
     return INNFER_OK;
@@ -599,6 +608,116 @@ extern "C" int innfer_net_set_conv_scale(innfer_net_t net, float conv_scale) {
     return INNFER_OK;
 }
 
+// DAT (Chen et al. 2023; include/innfer_amd.h carries the definition) on SwinIR's skeleton WITHOUT padding: blocks alternate between attention over rectangular windows
+// (even b) and attention across channels (odd b); both end in the interaction mix with a depthwise conv of v; the feed-forward is gated by a depthwise conv of its
+// second half.  Conv slots in forward order: conv_first; per block attn.qkv, attn.proj (input: the head-padded 32 nH channels), ffn.fc1 (rows: x1's block padded to
+// dat_h1p, then x2's), ffn.fc2 (input: dat_h1p channels); per group its conv; conv_after_body; the tail.
+struct DatOff { size_t dw_t, dw_b, ci_w1, ci_b1, ci_w2, ci_b2, si_w1, si_b1, si_w2, si_b2, sg_g, sg_b, sg_t, sg_cb, temp, total; };
+static DatOff dat_offsets(const innfer_net* net) {
+    const size_t ch = 32 * (size_t)net->sw_nh, hc = (size_t)net->sw_c / 8, hs = (size_t)net->sw_c / 16, half = (size_t)net->sw_hid / 2;
+    DatOff o{};
+    size_t at = 0;
+    auto take = [&](size_t n) { const size_t a = at; at += n; return a; };
+    o.dw_t = take(ch * 9); o.dw_b = take(ch);
+    o.ci_w1 = take(hc * ch); o.ci_b1 = take(hc); o.ci_w2 = take(ch * hc); o.ci_b2 = take(ch);
+    o.si_w1 = take(hs * ch); o.si_b1 = take(hs); o.si_w2 = take(hs); o.si_b2 = take(1);
+    o.sg_g = take(half); o.sg_b = take(half); o.sg_t = take(half * 9); o.sg_cb = take(half);
+    o.temp = take((size_t)net->sw_nh);
+    o.total = at;
+    return o;
+}
+
+extern "C" size_t innfer_dat_block_floats(innfer_net_t net) { return net && net->kind == 8 ? dat_offsets(net).total : 0; }
+
+extern "C" int innfer_dat_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int hidden, int s0, int s1,
+                                 int upsampler, int scale, int conv3, const float* h_mean, const int* h_shift) {
+    if (!out || !depths) return set_error(INNFER_ERR_INVALID, "dat_create: null argument");
+    if (embed_dim < 1 || embed_dim > 256 || num_heads < 2 || num_heads > 8 || (num_heads & 1) || embed_dim % num_heads || embed_dim / num_heads > 32)
+        return set_error(INNFER_ERR_UNSUPPORTED, "dat_create: embed_dim=%d num_heads=%d (built: embed_dim <= 256, 2, 4, 6 or 8 heads of <= 32 channels, embed_dim %% num_heads == 0)", embed_dim, num_heads);
+    if (embed_dim / 16 < 1) return set_error(INNFER_ERR_UNSUPPORTED, "dat_create: embed_dim=%d (built: embed_dim / 8 and embed_dim / 16 in 1 .. 64)", embed_dim);
+    if (hidden < 2 || hidden > 1024 || (hidden & 1)) return set_error(INNFER_ERR_UNSUPPORTED, "dat_create: a feed-forward of %d hidden channels (built: even, <= 1024)", hidden);
+    if (s0 != 8 || (s1 != 32 && s1 != 16)) return set_error(INNFER_ERR_UNSUPPORTED, "dat_create: split_size [%d, %d] (built: [8, 32] and [8, 16])", s0, s1);
+    if (in_nc < 1 || in_nc > 4 || in_nc != out_nc) return set_error(INNFER_ERR_UNSUPPORTED, "dat_create: in_chans=%d, %d output channels (built: equal, 1..4)", in_nc, out_nc);
+    if (n_layers < 1 || n_layers > 64) return set_error(INNFER_ERR_UNSUPPORTED, "dat_create: %d residual groups", n_layers);
+    for (int i = 0; i < n_layers; ++i)
+        if (depths[i] < 1 || depths[i] > 64) return set_error(INNFER_ERR_UNSUPPORTED, "dat_create: depth %d of residual group %d", depths[i], i);
+    if (upsampler < 0 || upsampler > 1) return set_error(INNFER_ERR_UNSUPPORTED, "dat_create: upsampler %d (0 pixelshuffle, 1 pixelshuffledirect)", upsampler);
+    if (scale < 2 || scale > 4) return set_error(INNFER_ERR_UNSUPPORTED, "dat_create: scale %d (built: 2, 3, 4)", scale);
+    innfer_net* net = new innfer_net();
+    net->kind = 8; net->in_nc = in_nc; net->out_nc = out_nc; net->nf = 64; net->nb = 0; net->gc = 0; net->scale = scale; net->n_up = 0;
+    net->sw_c = embed_dim; net->sw_cp = (embed_dim + 63) / 64 * 64; net->sw_nh = num_heads; net->sw_d = embed_dim / num_heads;
+    net->dat_s0 = s0; net->dat_s1 = s1; net->dat_h1p = (hidden / 2 + 63) / 64 * 64;
+    net->sw_hid = hidden; net->sw_hp = 2 * net->dat_h1p; net->sw_tail = upsampler; net->sw_conv3 = conv3 != 0;
+    net->sw_c4p = (embed_dim / 4 + 63) / 64 * 64;
+    net->sw_depths.assign(depths, depths + n_layers);
+    const int cp = net->sw_cp;
+    for (int p = 0; p < cp / 64; ++p) add_conv(net, "conv_first#" + std::to_string(p), 64, in_nc, true);
+    for (int i = 0; i < n_layers; ++i) {
+        for (int j = 0; j < depths[i]; ++j) {
+            const std::string b = "layers." + std::to_string(i) + ".blocks." + std::to_string(j) + ".";
+            swin_add_sliced(net, b + "attn.qkv", (3 * num_heads + 1) / 2 * 64, cp, 1);
+            swin_add_sliced(net, b + "attn.proj", cp, 32 * num_heads, 1);
+            swin_add_sliced(net, b + "ffn.fc1", net->sw_hp, cp, 1);
+            swin_add_sliced(net, b + "ffn.fc2", cp, net->dat_h1p, 1);
+            // shifted: the issue's rule, unless the caller names the blocks (a checkpoint's stored masks decide)
+            const bool formula = (i % 2 == 0 && j > 0 && (j - 2) % 4 == 0) || (i % 2 != 0 && j % 4 == 0);
+            net->dat_shift.push_back(h_shift ? (h_shift[net->nb] != 0) : formula);
+            net->dat_aca.push_back(j & 1);
+            net->nb++;
+        }
+        swin_add_resi(net, "layers." + std::to_string(i) + ".conv");
+    }
+    swin_add_resi(net, "conv_after_body");
+    if (upsampler == 1) {
+        add_conv(net, "upsample.0", out_nc * scale * scale, cp);
+        net->convs.back().Kp = out_nc * scale * scale <= 32 ? 32 : 64;
+    } else {
+        add_conv(net, "conv_before_upsample.0", 64, cp);
+        net->convs.back().slope_ok = true;
+        if (scale == 3) add_conv(net, "upsample.0", 576, 64);
+        else {
+            add_conv(net, "upsample.0", 256, 64); net->convs.back().ps2 = true;
+            if (scale == 4) { add_conv(net, "upsample.2", 256, 64); net->convs.back().ps2 = true; net->convs.back().mult = 4.f; }
+        }
+        add_conv(net, "conv_last", out_nc, 64); net->convs.back().mult = (float)(scale * scale);
+    }
+    net->sw_ln.assign(2 + 2 * (size_t)net->nb, nullptr);
+    net->sw_relb.assign((size_t)net->nb, nullptr);
+    net->dat_blk.assign((size_t)net->nb, nullptr);
+    net->dat_sib2.assign((size_t)net->nb, 0.f);
+    int rc = INNFER_OK;
+    {   // x - mean in front of conv_first and nn.LeakyReLU() (slope 0.01) behind conv_before_upsample, as innfer_swinir_create
+        float h[8];
+        for (int c = 0; c < in_nc; ++c) { h[c] = 1.f; h[in_nc + c] = h_mean ? -h_mean[c] : 0.f; }
+        ConvSlot& c0 = net->convs[0];
+        if (hipMalloc((void**)&c0.d_map, 2 * in_nc * sizeof(float)) != hipSuccess || hipMemcpy(c0.d_map, h, 2 * in_nc * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            rc = set_error(INNFER_ERR_NOMEM, "dat_create: no device memory for the input map");
+        for (size_t i = 0; i < net->convs.size() && rc == INNFER_OK; ++i)
+            if (net->convs[i].slope_ok) {
+                const std::vector<float> sl(64, 0.01f);
+                rc = innfer_net_set_conv_slope(net, (int)i, sl.data());
+            }
+    }
+    if (rc != INNFER_OK) { (void)hipGetLastError(); innfer_net_destroy(net); return rc; }
+    *out = net;
+    return INNFER_OK;
+}
+
+// The per-block parameters of a DAT beside its convs, LayerNorms and bias table: innfer_dat_block_floats(net) host floats in the header's order.  Load time, synchronous.
+extern "C" int innfer_net_set_dat_block(innfer_net_t net, int blk, const float* h_params, size_t n_floats) {
+    if (!net || !h_params) return set_error(INNFER_ERR_INVALID, "set_dat_block: null argument");
+    if (net->kind != 8) return set_error(INNFER_ERR_UNSUPPORTED, "set_dat_block: the network is not a DAT");
+    if (blk < 0 || blk >= (int)net->dat_blk.size()) return set_error(INNFER_ERR_INVALID, "set_dat_block: block %d of %zu", blk, net->dat_blk.size());
+    const DatOff o = dat_offsets(net);
+    if (n_floats != o.total) return set_error(INNFER_ERR_INVALID, "set_dat_block: %zu floats, the block takes %zu (innfer_dat_block_floats)", n_floats, o.total);
+    for (size_t i = 0; i < n_floats; ++i)
+        if (!std::isfinite(h_params[i])) return set_error(INNFER_ERR_INVALID, "set_dat_block: parameter %zu of block %d is not finite", i, blk);
+    if (!net->dat_blk[blk]) INNFER_HIP(hipMalloc((void**)&net->dat_blk[blk], (o.total + 4) * sizeof(float)));
+    INNFER_HIP(hipMemcpy(net->dat_blk[blk], h_params, o.total * sizeof(float), hipMemcpyHostToDevice));
+    net->dat_sib2[blk] = h_params[o.si_b2];
+    return INNFER_OK;
+}
+
 // The affine parameters of the GroupNorm behind conv `idx` (RealPLKSR's refine): 64 host floats each, NULL = 1 / 0.  Load time, synchronous.
 extern "C" int innfer_net_set_group_norm(innfer_net_t net, int idx, const float* h_gamma, const float* h_beta) {
     if (!net || idx < 0 || idx >= (int)net->convs.size()) return set_error(INNFER_ERR_INVALID, "set_group_norm: bad arguments");
@@ -638,6 +757,7 @@ extern "C" void innfer_net_destroy(innfer_net_t net) {
     for (float* q : net->sw_relb) if (q) (void)hipFree(q);
     for (float* q : net->sw_tau) if (q) (void)hipFree(q);
     for (float* q : net->hat_ca) if (q) (void)hipFree(q);
+    for (float* q : net->dat_blk) if (q) (void)hipFree(q);
     for (auto& c : net->convs) {
         if (c.d_w) (void)hipFree(c.d_w);
         if (c.d_b) (void)hipFree(c.d_b);
@@ -801,6 +921,7 @@ extern "C" int innfer_net_set_precision(innfer_net_t net, int fp32) {
     if (fp32 && net->kind == 5) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SwinIR is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 6) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: HAT is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 7) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: Swin2SR is built for the fp16 mode only (no fp32-accurate engine)");
+    if (fp32 && net->kind == 8) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: DAT is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32) {
         // The (wl | wh | wh) panels of every loaded conv are built HERE -- a load-time call, with its hipMalloc and synchronous copies -- never inside
         // innfer_net_forward (stream capture, concurrent callers).  Idempotent: a conv that already has its panels is skipped; innfer_net_set_conv
@@ -887,6 +1008,14 @@ extern "C" double innfer_net_flops(innfer_net_t net, int N, int H, int W) {
         for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
         return f;
     }
+    if (net->kind == 8) {        // DAT: every conv on the grid itself; per even block the two products of every window and head on the frame padded to s1, per odd block the Gram and the apply
+        const double px = (double)N * H * W, s1 = net->dat_s1, T = (double)net->dat_s0 * s1;
+        const double pxp = (double)N * std::ceil(H / s1) * s1 * std::ceil(W / s1) * s1;
+        double f = 0.0;
+        for (size_t b = 0; b < net->dat_blk.size(); ++b) f += net->sw_nh * (net->dat_aca[b] ? px * 4.0 * 32 * 32 : (pxp / T) * 4.0 * T * T * 32);
+        for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
+        return f;
+    }
     H = (H + net->unshuffle - 1) / net->unshuffle; W = (W + net->unshuffle - 1) / net->unshuffle;      // the LR grid
     double px = (double)N * H * W, f = 0.0;
     const int nconv = (int)net->convs.size();
@@ -923,10 +1052,10 @@ struct Carve {
 // the token stream, the normalised tokens, the qkv slab (head-padded), the attention's result (head-padded), the MLP's hidden slab, the two C / 4 buffers of '3conv',
 // the tail's slabs, and the full-size result in front of the crop.
 // HAT (kind 6) pads to multiples of 16 and adds the conv block's 64-channel slab, its C_pad-channel result z, the channel attention's vector and the segment sums.
-struct SwinCarve { size_t xin, f0, r[2], t, u, qkv, att, hid, c4[2], b64, up[2], hr, outp, zc, z, y, pool, total; int Hp, Wp; };
+struct SwinCarve { size_t xin, f0, r[2], t, u, qkv, att, hid, c4[2], b64, up[2], hr, outp, zc, z, y, pool, gram, amat, total; int Hp, Wp; };
 static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
     SwinCarve c{};
-    const int wsz = net->kind == 6 ? 16 : 8;
+    const int wsz = net->kind == 6 ? 16 : net->kind == 8 ? 1 : 8;          // (DAT works on H x W itself)
     c.Hp = (H + wsz - 1) / wsz * wsz; c.Wp = (W + wsz - 1) / wsz * wsz;
     const size_t px = (size_t)N * c.Hp * c.Wp, s2 = (size_t)net->scale * net->scale;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -955,13 +1084,21 @@ static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
         c.y = take((size_t)N * net->sw_cp * 4);
         c.pool = take(ca_work_floats(N, (long)c.Hp * c.Wp, net->sw_cp) * 4);
     }
+    if (net->kind == 8) {        // DAT: c = GELU(dwconv(v)) (head-padded), the normalised second half of the feed-forward, the per-channel gate, the pool's and the Gram's segment records, A
+        c.z = take(px * 32 * net->sw_nh * 2);
+        c.zc = take(px * net->dat_h1p * 2);
+        c.y = take((size_t)N * 32 * net->sw_nh * 4);
+        c.pool = take(ca_work_floats(N, (long)H * W, 32 * net->sw_nh) * 4);
+        c.gram = take(csa_work_floats(N, (long)H * W, net->sw_nh) * 4);
+        c.amat = take((size_t)N * net->sw_nh * 1024 * 4);
+    }
     c.total = off;
     return c;
 }
 
 static Carve carve(const innfer_net* net, int N, int H, int W) {
     Carve c{};
-    if (net->kind == 5 || net->kind == 6 || net->kind == 7) { c.total = swin_carve(net, N, H, W).total; return c; }
+    if (net->kind == 5 || net->kind == 6 || net->kind == 7 || net->kind == 8) { c.total = swin_carve(net, N, H, W).total; return c; }
     const size_t px = (size_t)N * H * W;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     if (net->kind == 2) {        // SRVGGNetCompact: the two ping-pong feature slabs (one when there is no nf -> nf conv) and the last conv's 32- / 64-channel slab
@@ -1501,7 +1638,7 @@ static int swinir_forward(innfer_net* net, const void* d_in, int in_dtype, void*
     for (size_t i = 0; i < net->sw_ln.size(); ++i)
         if (!net->sw_ln[i]) return set_error(INNFER_ERR_INVALID, "forward: the parameters of LayerNorm %zu were never set (innfer_net_set_layer_norm)", i);
     for (size_t i = 0; i < net->sw_relb.size(); ++i)
-        if (!net->sw_relb[i]) return set_error(INNFER_ERR_INVALID, "forward: the relative position bias of block %zu was never set (innfer_net_set_attn_bias)", i);
+        if (!net->sw_relb[i] && !(net->kind == 8 && net->dat_aca[i])) return set_error(INNFER_ERR_INVALID, "forward: the relative position bias of block %zu was never set (innfer_net_set_attn_bias)", i);
     for (size_t i = 0; i < net->sw_tau.size(); ++i)
         if (!net->sw_tau[i]) return set_error(INNFER_ERR_INVALID, "forward: the attention scale of block %zu was never set (innfer_net_set_attn_scale)", i);
     const SwinCarve cv = swin_carve(net, N, H, W);
@@ -1615,6 +1752,64 @@ static int swinir_forward(innfer_net* net, const void* d_in, int in_dtype, void*
             if (int rc = norm(ln++, t, u)) return rc;
             if (int rc = sliced(net->sw_hp / 64, u, hid, 12, nullptr)) return rc;
             if (int rc = sliced(cp / 64, hid, t, 0, t)) return rc;
+            if (int rc = resi(t, r[cur ^ 1], r[cur])) return rc;
+            cur ^= 1;
+        }
+    } else if (net->kind == 8) {
+        // DAT on H x W itself (Hp = H, Wp = W: no pad, no crop).  Per block  u = LN(t); qkv; the attention into `att` -- even index in its group: rectangular windows (one
+        // launch); odd: across channels (Gram, merge + softmax, apply) --; c = GELU(dwconv(v)) on the v groups of the qkv slab (BatchNorm folded); the pool over Y and the
+        // GELU excite; the interaction mix in place on `att` ((X, Y) = (att, c) | (c, att)); proj + shortcut; u = LN(t); fc1 with GELU into [x1 | x2]; LN(x2); x2 = x1 *
+        // dwconv(LN(x2)); fc2 from x2 + shortcut.  9 + SQ + 2 S1 + SF launches (11 + ... for the channel form), SF = 2 h1p / 64.  Then r' = conv(t) + r.
+        for (size_t i = 0; i < net->dat_blk.size(); ++i)
+            if (!net->dat_blk[i]) return set_error(INNFER_ERR_INVALID, "forward: the parameters of block %zu were never set (innfer_net_set_dat_block)", i);
+        const DatOff o = dat_offsets(net);
+        const long HW = (long)H * W;
+        const int chp = 32 * nh, hc = net->sw_c / 8, hs = net->sw_c / 16, half = net->sw_hid / 2, h1p = net->dat_h1p, T = net->dat_s0 * net->dat_s1;
+        f16* cb = (f16*)(ws + cv.z);
+        f16* sg = (f16*)(ws + cv.zc);
+        float* y = (float*)(ws + cv.y);
+        float* pool = (float*)(ws + cv.pool);
+        float* gram = (float*)(ws + cv.gram);
+        float* amat = (float*)(ws + cv.amat);
+        f16* x1 = hid;
+        f16* x2 = hid + (long)(h1p / 32) * G;
+        const f16* vg = qkv + 2L * nh * G;
+        for (size_t i = 0; i < net->sw_depths.size(); ++i) {
+            for (int j = 0; j < net->sw_depths[i]; ++j, ++blk) {
+                const float* P = net->dat_blk[blk];
+                const bool aca = net->dat_aca[blk] != 0;
+                const f16* x = j == 0 ? r[cur] : t;
+                if (int rc = norm(1 + 2 * blk, x, u)) return rc;
+                if (int rc = sliced((3 * nh + 1) / 2, u, qkv, 0, nullptr)) return rc;
+                // launch kinds 8001 the window attention; 8010 / 8011 / 8012 the channel attention's Gram, merge + softmax, apply; 8013 the depthwise conv; 8005 / 8006 the
+                // pool and the excite; 8014 the interaction mix; 8000 LayerNorm
+                if (!aca) {
+                    if (int rc = plksr_pass(s, "window_attention_rect", 4.0 * T * 32 * nh * px, px * nh * 256.0 + nh * 4.0 * T * T, 8001, [&] {
+                            return win_attn_rect_launch(qkv, G, att, G, net->sw_relb[blk], N, H, W, nh, net->sw_d, net->dat_s0, net->dat_s1, net->dat_shift[blk], s); })) return rc;
+                } else {
+                    if (int rc = plksr_pass(s, "channel_attention_gram", 2.0 * 1088 * nh * px, 128.0 * nh * px, 8010, [&] { return csa_gram_launch(qkv, G, N, HW, nh, net->sw_d, gram, s); })) return rc;
+                    if (int rc = plksr_pass(s, "channel_attention_softmax", 0.0, 4.0 * (double)csa_work_floats(N, HW, nh), 8011, [&] {
+                            return csa_softmax_launch(gram, N, HW, nh, net->sw_d, P + o.temp, amat, nullptr, s); })) return rc;
+                    if (int rc = plksr_pass(s, "channel_attention_apply", 2.0 * 1024 * nh * px, 128.0 * nh * px, 8012, [&] { return csa_apply_launch(qkv, G, att, G, amat, N, HW, nh, net->sw_d, s); })) return rc;
+                }
+                if (int rc = plksr_pass(s, "dwconv_gelu", 18.0 * chp * px, 4.0 * chp * px, 8013, [&] {
+                        return dwconv3x3_launch(vg, G, nullptr, 0, cb, G, N, H, W, chp, chp, P + o.dw_t, P + o.dw_b, 1, s); })) return rc;
+                const f16* X = aca ? cb : att;
+                const f16* Y = aca ? att : cb;
+                if (int rc = plksr_pass(s, "chan_attn_pool", px * chp, px * chp * 2.0, 8005, [&] { return ca_pool_launch(Y, G, N, HW, chp, pool, s); })) return rc;
+                if (int rc = plksr_pass(s, "chan_attn_excite_gelu", 4.0 * chp * hc * N, 4.0 * (double)ca_work_floats(N, HW, chp), 8006, [&] {
+                        return ca_excite_gelu_launch(pool, N, HW, chp, chp, hc, P + o.ci_w1, P + o.ci_b1, P + o.ci_w2, P + o.ci_b2, y, nullptr, s); })) return rc;
+                if (int rc = plksr_pass(s, "aim_mix", (2.0 * chp * hs + 3.0 * chp) * px, 6.0 * chp * px, 8014, [&] {
+                        return aim_mix_launch(X, G, Y, G, att, G, y, N, HW, chp, chp, hs, P + o.si_w1, P + o.si_b1, P + o.si_w2, net->dat_sib2[blk], s); })) return rc;
+                if (int rc = sliced(cp / 64, att, t, 0, x)) return rc;
+                if (int rc = norm(2 + 2 * blk, t, u)) return rc;
+                if (int rc = sliced(2 * h1p / 64, u, hid, 12, nullptr)) return rc;
+                if (int rc = plksr_pass(s, "layer_norm_wide", 8.0 * half * px, px * h1p * 4.0, 8000, [&] {
+                        return layer_norm_wide_launch(x2, G, sg, G, npx, half, h1p, P + o.sg_g, P + o.sg_b, 1e-5f, s); })) return rc;
+                if (int rc = plksr_pass(s, "dwconv_gate", 18.0 * half * px, 6.0 * h1p * px, 8013, [&] {
+                        return dwconv3x3_launch(sg, G, x1, G, x2, G, N, H, W, half, h1p, P + o.sg_t, P + o.sg_cb, 2, s); })) return rc;
+                if (int rc = sliced(cp / 64, x2, t, 0, t)) return rc;
+            }
             if (int rc = resi(t, r[cur ^ 1], r[cur])) return rc;
             cur ^= 1;
         }
@@ -1779,7 +1974,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     if (ws_bytes < cv.total) return set_error(INNFER_ERR_WORKSPACE, "forward: workspace %zu < %zu bytes", ws_bytes, cv.total);
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)d_ws;
-    if (net->kind == 5 || net->kind == 6 || net->kind == 7) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);
+    if (net->kind == 5 || net->kind == 6 || net->kind == 7 || net->kind == 8) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);
     if (net->kind == 2) return compact_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 3) return span_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 4) return plksr_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);

@@ -218,6 +218,19 @@ SIGNATURES = {
     "innfer_chan_attn_work_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
     "innfer_chan_attn_excite": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
     "innfer_chan_attn_scale_add": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_float, C.c_int, C.c_int64, C.c_int, C.c_void_p]),
+    # (123, additive) the kernels of a DAT block as single launches
+    "innfer_window_attention_rect": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p]),
+    "innfer_channel_attention_work_bytes": (C.c_size_t, [C.c_int, C.c_int64, C.c_int]),
+    "innfer_channel_attention_scores": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "innfer_channel_attention_apply": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "innfer_dwconv3x3": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "innfer_chan_attn_excite_gelu": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "innfer_aim_mix": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "innfer_layer_norm_wide": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
+    "innfer_dat_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
+    "innfer_dat_block_floats": (C.c_size_t, [C.c_void_p]),
+    "innfer_net_set_dat_block": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "innfer_plk_conv": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_void_p]),
     "innfer_group_norm_skip_work_bytes": (C.c_size_t, [C.c_int, C.c_int64]),
     "innfer_group_norm_skip": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p,

@@ -29,6 +29,7 @@ _SNIFF = (
     ('conv_1.eval_conv.weight', 'span'),             # .. or a `deploy` one, which carries only the collapsed convs
     ('feats.0.weight', 'realplksr'),                 # RealPLKSR (with feats.1.channel_mixer.0.weight)
     ('layers.0.residual_group.blocks.0.norm1.weight', 'swinir'),      # SwinIR and what builds on its skeleton (with conv_first.weight): ahead of the new-arch probe
+    ('before_RG.1.weight', 'dat'),                   # DAT (with conv_first.weight and block 0's complete key set, _DAT_KEYS): ahead of the new-arch probe
     ('conv_first.weight', 'mesrgan'),
     ('model.0.weight', 'esrgan'),
     ('CFEM.0.weight', 'ppon'),
@@ -46,7 +47,8 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
         state_dict = swa2normal(state_dict)
     for probe, arch in _SNIFF:
         if probe in state_dict and (arch != 'realesrgan' or 'conv_first.weight' in state_dict) and (arch != 'span' or 'conv_cat.weight' in state_dict) and \
-                (arch != 'realplksr' or 'feats.1.channel_mixer.0.weight' in state_dict) and (arch != 'swinir' or 'conv_first.weight' in state_dict):
+                (arch != 'realplksr' or 'feats.1.channel_mixer.0.weight' in state_dict) and (arch != 'swinir' or 'conv_first.weight' in state_dict) and \
+                (arch != 'dat' or all(k in state_dict for k in _DAT_KEYS)):
             break
     else:
         raise Exception("Could not infer model parameters.")
@@ -67,6 +69,8 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
             return hat
         s2 = _infer_swin2sr(state_dict)      # (likewise: block 0's complete Swin2SR key set)
         return s2 if s2 is not None else _infer_swinir(state_dict)
+    if arch == 'dat':
+        return _infer_dat(state_dict)
     if arch == 'pan':
         return _infer_pan(state_dict, scale, in_nc, out_nc)
     if arch == 'ppon':
@@ -452,6 +456,97 @@ def _infer_hat(state_dict):
            'conv_scale': 0.01, 'overlap_ratio': (ows - ws) / ws, 'mlp_ratio': hidden / C, 'scale': up, 'upsampler': 'pixelshuffle', 'resi_connection': '1conv',
            'rpi_sa': rpi.get('relative_position_index_SA'), 'rpi_oca': rpi.get('relative_position_index_OCA')}
     return dict(arch='hat', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=sum(depths), plus=False, state_dict=state_dict,
+                net_params=get_network_G_config(cfg, up))
+
+
+# block 0's complete key set of a DAT (a window block): with before_RG.1.weight, what recognises one
+_DAT_B0 = 'layers.0.blocks.0.'
+_DAT_KEYS = ('conv_first.weight', 'norm.weight') + tuple(_DAT_B0 + k for k in (
+    'norm1.weight', 'norm2.weight', 'attn.qkv.weight', 'attn.proj.weight', 'attn.dwconv.0.weight', 'attn.dwconv.1.running_var', 'attn.channel_interaction.1.weight',
+    'attn.channel_interaction.2.running_var', 'attn.channel_interaction.4.weight', 'attn.spatial_interaction.0.weight', 'attn.spatial_interaction.1.running_var',
+    'attn.spatial_interaction.3.weight', 'attn.attns.0.pos.pos_proj.weight', 'attn.attns.0.pos.pos1.0.weight', 'attn.attns.0.pos.pos1.2.weight',
+    'attn.attns.0.pos.pos2.0.weight', 'attn.attns.0.pos.pos2.2.weight', 'attn.attns.0.pos.pos3.0.weight', 'attn.attns.0.pos.pos3.2.weight',
+    'attn.attns.1.pos.pos_proj.weight', 'attn.attns.1.pos.pos3.2.weight', 'ffn.fc1.weight', 'ffn.sg.norm.weight', 'ffn.sg.conv.weight', 'ffn.fc2.weight'))
+
+
+def _infer_dat(state_dict):
+    """DAT checkpoints (DAT, DAT-S, DAT-2, DAT-light and fine-tunes).  embed_dim and in_chans from conv_first, depths by counting blocks, num_heads = 2 x the rows of
+    attns.0.pos.pos3.2 (cross-checked against temperature when there is an odd block), the width of the position MLP from pos_proj, expansion_factor from ffn.fc1, '3conv',
+    the tail and the scale as _infer_swinir reads them.  split_size from attns.0.rpe_biases (its last row + 1); without the buffer [8, 32] is ASSUMED and net_params says
+    so (split_assumed).  If any block stores attn.attn_mask_0, the blocks that store it are the shifted ones (shift_blocks), else the published rule.  A stored rpe_biases
+    feeds the position MLP; a stored relative_position_index that differs from the formula is refused; attn_mask_* values are never read.  Every buffer is dropped from
+    the state dict handed back."""
+    import math
+    from .architectures.DAT_arch import SPLITS, relative_position_index
+    b0 = _DAT_B0
+    if b0 + 'attn.qkv.bias' not in state_dict:
+        raise NotImplementedError('DAT checkpoint without qkv biases (qkv_bias=False): not built on the HIP path')
+    w0 = state_dict['conv_first.weight']
+    C, in_nc = int(w0.shape[0]), int(w0.shape[1])
+    depths = []
+    while f'layers.{len(depths)}.blocks.0.norm1.weight' in state_dict:
+        i, j = len(depths), 0
+        while f'layers.{i}.blocks.{j}.norm1.weight' in state_dict:
+            j += 1
+        depths.append(j)
+    nh = 2 * int(state_dict[b0 + 'attn.attns.0.pos.pos3.2.weight'].shape[0])
+    temp = state_dict.get('layers.0.blocks.1.attn.temperature')
+    if temp is not None and int(temp.shape[0]) != nh:
+        raise Exception("Could not infer model parameters.")
+    pos_dim = int(state_dict[b0 + 'attn.attns.0.pos.pos_proj.weight'].shape[0])
+    hidden = int(state_dict[b0 + 'ffn.fc1.weight'].shape[0])
+    if not depths or C % max(nh, 1) or hidden % 2:
+        raise Exception("Could not infer model parameters.")
+    rpe, split_assumed = [None, None], False
+    for br in (0, 1):
+        v = state_dict.get(b0 + f'attn.attns.{br}.rpe_biases')
+        if v is not None:
+            if v.dim() != 2 or int(v.shape[1]) != 2:
+                raise NotImplementedError(f'DAT checkpoint: attns.{br}.rpe_biases has shape {tuple(v.shape)}, not [rows, 2]')
+            rpe[br] = v.detach().cpu().double().numpy()
+    if rpe[0] is not None:
+        split = (int(round(float(rpe[0][-1][0]))) + 1, int(round(float(rpe[0][-1][1]))) + 1)
+    else:
+        split, split_assumed = (8, 32), True
+    if split not in SPLITS:
+        raise NotImplementedError(f'DAT checkpoint with split_size {list(split)}: only [8, 32] and [8, 16] are built on the HIP path')
+    for br, (wh, ww) in enumerate(((split[0], split[1]), (split[1], split[0]))):
+        if rpe[br] is not None and rpe[br].shape != ((2 * wh - 1) * (2 * ww - 1), 2):
+            raise NotImplementedError(f'DAT checkpoint: attns.{br}.rpe_biases has shape {rpe[br].shape} for a {wh} x {ww} window')
+        idx = relative_position_index(wh, ww)
+        for k, v in state_dict.items():
+            if k.endswith(f'attn.attns.{br}.relative_position_index') and (tuple(v.shape) != tuple(idx.shape) or not bool((v.cpu().long() == idx).all())):
+                raise NotImplementedError(f'DAT checkpoint: {k} differs from the published formula for a {wh} x {ww} window')
+    masks = sorted((int(k.split('.')[1]), int(k.split('.')[3])) for k in state_dict if k.startswith('layers.') and k.endswith('.attn.attn_mask_0'))
+    conv3 = 'layers.0.conv.0.weight' in state_dict
+    if not conv3 and 'layers.0.conv.weight' not in state_dict:
+        raise Exception("Could not infer model parameters.")
+    if 'conv_last.weight' in state_dict and 'conv_before_upsample.0.weight' in state_dict:
+        upsampler, up = 'pixelshuffle', 1
+        for k, v in state_dict.items():
+            if k.startswith('upsample.') and k.endswith('.weight'):
+                f = math.isqrt(int(v.shape[0]) // 64)
+                if f * f * 64 != int(v.shape[0]):
+                    raise Exception("Could not infer model parameters.")
+                up *= f
+        out_nc = int(state_dict['conv_last.weight'].shape[0])
+    elif 'upsample.0.weight' in state_dict:
+        upsampler = 'pixelshuffledirect'
+        n = int(state_dict['upsample.0.weight'].shape[0])
+        up = math.isqrt(n // in_nc)
+        if up * up * in_nc != n:
+            raise Exception("Could not infer model parameters.")
+        out_nc = in_nc
+    else:
+        raise NotImplementedError('DAT checkpoint without a pixelshuffle / pixelshuffledirect tail: not built on the HIP path')
+    if out_nc != in_nc:
+        raise NotImplementedError(f'DAT checkpoint: conv_last has {out_nc} channels, conv_first takes {in_nc} (unequal channel counts are not built on the HIP path)')
+    buffers = ('.rpe_biases', '.relative_position_index', '.attn_mask_0', '.attn_mask_1')
+    state_dict = {k: v for k, v in state_dict.items() if not k.endswith(buffers)}
+    cfg = {'type': 'dat', 'in_nc': in_nc, 'nf': C, 'depths': depths, 'num_heads': [nh] * len(depths), 'split_size': list(split), 'expansion_factor': hidden / C, 'scale': up,
+           'upsampler': upsampler, 'resi_connection': '3conv' if conv3 else '1conv', 'pos_dim': pos_dim, 'shift_blocks': masks if masks else None,
+           'rpe_biases': rpe if rpe[0] is not None or rpe[1] is not None else None, 'split_assumed': split_assumed}
+    return dict(arch='dat', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=sum(depths), plus=False, state_dict=state_dict,
                 net_params=get_network_G_config(cfg, up))
 
 

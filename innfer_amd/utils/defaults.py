@@ -189,6 +189,23 @@ def get_network_G_config(network_G, scale):
         cfg['rpi_sa'] = _pick(opts, 'rpi_sa', None)                  # the index buffers of the checkpoint, when it carries them
         cfg['rpi_oca'] = _pick(opts, 'rpi_oca', None)
         opts.pop('out_nc', None)
+    elif kind in ('dat', 'dat_net'):                       # DAT (dual aggregation transformer on SwinIR's skeleton): the published constructor surface
+        cfg['type'] = 'dat'
+        cfg['in_chans'] = _pick(opts, 'in_nc', 3)
+        cfg['embed_dim'] = _pick(opts, 'nf', 180)
+        cfg['depth'] = list(_pick(opts, 'depths', [6] * 6))
+        cfg['num_heads'] = list(_pick(opts, 'num_heads', [6] * len(cfg['depth'])))
+        cfg['split_size'] = list(_pick(opts, 'split_size', [8, 32]))
+        cfg['expansion_factor'] = _pick(opts, 'expansion_factor', 4.0)
+        cfg['upscale'] = _pick(opts, 'scale', scale)
+        cfg['img_range'] = _pick(opts, 'img_range', 1.0)
+        cfg['upsampler'] = _pick(opts, 'upsampler', 'pixelshuffle')
+        cfg['resi_connection'] = _pick(opts, 'resi_connection', '1conv')
+        cfg['pos_dim'] = _pick(opts, 'pos_dim', None)                # the width of the DynamicPosBias MLP, read off the checkpoint's pos_proj
+        cfg['shift_blocks'] = _pick(opts, 'shift_blocks', None)      # [(group, block)] of the blocks that store attn_mask_0, when any does; else the published rule
+        cfg['rpe_biases'] = _pick(opts, 'rpe_biases', None)          # the checkpoint's rpe_biases per branch, when it carries them
+        cfg['split_assumed'] = _pick(opts, 'split_assumed', False)   # True: the checkpoint had no rpe_biases and [8, 32] was assumed
+        opts.pop('out_nc', None)
     else:
         raise NotImplementedError(f'Generator model [{kind:s}] not recognized')
 
