@@ -45,8 +45,8 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): RealPLKSR -- innfer_plksr_create, innfer_net_set_group_norm, innfer_conv_args.act 11 (Mish), innfer_plk_conv (the partial large-kernel conv as a single launch), innfer_group_norm_skip / innfer_group_norm_skip_work_bytes (per-sample GroupNorm + skip over a 64-channel slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): SwinIR -- innfer_swinir_create, innfer_net_set_layer_norm, innfer_net_set_attn_bias, innfer_conv_args.act 12 (exact GELU on the 1x1 form), innfer_window_attention (the 8 x 8 window attention as a single launch), innfer_layer_norm (per-pixel LayerNorm over a padded slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a HAT): HAT -- innfer_hat_create, innfer_net_set_chan_attn, innfer_net_set_conv_scale, innfer_conv_args.act 13 (exact GELU on the plain 3x3 form), innfer_window_attention16 (the 16 x 16 window attention over a 16 x 16 or an overlapping 24 x 24 key window as a single launch), innfer_chan_attn_work_bytes / innfer_chan_attn_excite / innfer_chan_attn_scale_add (the channel attention's launches).  Also added under 123 (additive: new entry points only, no struct or signature changed): the kernels of DAT's blocks as single launches -- innfer_window_attention_rect (rectangular windows in two transposed head branches), innfer_channel_attention_work_bytes / innfer_channel_attention_scores / innfer_channel_attention_apply (attention across channels over a whole sample), innfer_dwconv3x3 (depthwise 3 x 3 with its three epilogues), innfer_chan_attn_excite_gelu, innfer_aim_mix (the two gates that blend the attention and conv branches), innfer_layer_norm_wide (LayerNorm over up to 512 channels) -- and the network on them: innfer_dat_create, innfer_dat_block_floats, innfer_net_set_dat_block (innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a DAT).  innfer_version() returns the library's; a binding should compare. */
-#define INNFER_ABI_VERSION 123
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): RealPLKSR -- innfer_plksr_create, innfer_net_set_group_norm, innfer_conv_args.act 11 (Mish), innfer_plk_conv (the partial large-kernel conv as a single launch), innfer_group_norm_skip / innfer_group_norm_skip_work_bytes (per-sample GroupNorm + skip over a 64-channel slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): SwinIR -- innfer_swinir_create, innfer_net_set_layer_norm, innfer_net_set_attn_bias, innfer_conv_args.act 12 (exact GELU on the 1x1 form), innfer_window_attention (the 8 x 8 window attention as a single launch), innfer_layer_norm (per-pixel LayerNorm over a padded slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a HAT): HAT -- innfer_hat_create, innfer_net_set_chan_attn, innfer_net_set_conv_scale, innfer_conv_args.act 13 (exact GELU on the plain 3x3 form), innfer_window_attention16 (the 16 x 16 window attention over a 16 x 16 or an overlapping 24 x 24 key window as a single launch), innfer_chan_attn_work_bytes / innfer_chan_attn_excite / innfer_chan_attn_scale_add (the channel attention's launches).  Also added under 123 (additive: new entry points only, no struct or signature changed): the kernels of DAT's blocks as single launches -- innfer_window_attention_rect (rectangular windows in two transposed head branches), innfer_channel_attention_work_bytes / innfer_channel_attention_scores / innfer_channel_attention_apply (attention across channels over a whole sample), innfer_dwconv3x3 (depthwise 3 x 3 with its three epilogues), innfer_chan_attn_excite_gelu, innfer_aim_mix (the two gates that blend the attention and conv branches), innfer_layer_norm_wide (LayerNorm over up to 512 channels) -- and the network on them: innfer_dat_create, innfer_dat_block_floats, innfer_net_set_dat_block (innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a DAT).  124: the remaining pass kernels of PAN, PPON and the WBC UNet and two passes of the fp32 mode one launch at a time, for tests (additive) -- innfer_pan_pre, innfer_pan_upsample, innfer_pan_final, innfer_pan_slab_pair, innfer_ppon_upsample3, innfer_ppon_axpy, innfer_wbc_pre, innfer_wbc_upadd, innfer_f32_prefix_lrelu, innfer_f32_act_copy.  innfer_version() returns the library's; a binding should compare. */
+#define INNFER_ABI_VERSION 124
 int innfer_version(void);
 const char* innfer_last_error(void);
 
@@ -584,6 +584,23 @@ int innfer_pack_pan_scpa(const float* h_conv1_a, const float* h_conv1_b, const f
 int innfer_pan_scpa_block(const void* d_in, void* d_out, int64_t group_stride, const void* d_blob, int N, int H, int W, int form, int in_c8, int out_c8, void* stream);
 int innfer_pan_split_from_nchw(const float* d_x, void* d_planes, int N, int H, int W, void* stream);
 int innfer_pan_split_to_nchw(const void* d_planes, float* d_x, int N, int H, int W, void* stream);
+/* (124, additive) The kernels at the two ends of the forwards one launch at a time, for tests: the launch functions both forwards call (csrc/pan.hip pan_pre_launch /
+ * pan_upsample_launch / pan_final_launch / pan_slab_pair_launch, csrc/f32ops.hip f32_upsample_launch).  Device pointers; no network object is needed.
+ * innfer_pan_pre: NCHW [N][C][H][W] (fp16 | fp32, rounded to nearest even) -> one fp16 group [N * H * W][32], channels C .. 31 written as zeros.  C > 32: INNFER_ERR_UNSUPPORTED.
+ * innfer_pan_upsample: F.interpolate(scale_factor = f, f = 2 | 3; bilinear 0: 'nearest', 1: 'bilinear' with align_corners=False).  INNFER_F16: blocked slabs of C / 32 groups
+ *   (C = 32 | 64; [N * h * w][32] -> [N * f h * f w][32], the groups in_group_stride / out_group_stride elements apart; pan_upsample); INNFER_F32: NCHW fp32, any C
+ *   (f32_upsample_launch; the strides are ignored).  Refused: another f, a slab C other than 32 | 64, a group stride below N H W 32 of its side.
+ * innfer_pan_final: out = raw + bilinear(x, size = (scale H, scale W), align_corners=True) (scale 1: raw + x); d_raw fp32 NCHW [N][C][scale H][scale W], 16-byte aligned;
+ *   d_x [N][C][H][W] and d_out fp16 | fp32 NCHW.  form 0: pan_final (one pixel per thread); 1: pan_final_x4 (four pixels of a row per thread), refused unless
+ *   (W * scale) % 4 == 0; -1: the fp16 forward's choice -- form 1 where it is accepted.  The two forms give the same bits.  scale outside 1 .. 4 is refused.
+ * innfer_pan_slab_pair: fp32 NCHW [N][C][H][W] -> a (hi, lo) pair of fp16 slabs of ceil(C / 32) groups [N * H * W][32]: hi = fp16(x), lo = fp16((x - hi) * 2^11), lo_offset
+ *   elements behind hi; the pad channels up to the next multiple of 32 are written as zeros in both.  Refused: lo_offset below ceil(C / 32) N H W 32 or no multiple of 8.
+ * All four refuse, with nothing launched, a null pointer, a size below 1 and an unknown dtype or form (INNFER_ERR_INVALID). */
+int innfer_pan_pre(const void* d_in, int in_dtype, int N, int C, int H, int W, void* d_slab, void* stream);
+int innfer_pan_upsample(const void* d_in, int dtype, int N, int C, int h, int w, int f, int bilinear, int64_t in_group_stride, void* d_out, int64_t out_group_stride,
+                        void* stream);
+int innfer_pan_final(const float* d_raw, int C, const void* d_x, int x_dtype, int N, int H, int W, int scale, void* d_out, int out_dtype, int form, void* stream);
+int innfer_pan_slab_pair(const float* d_x, int N, int C, int H, int W, void* d_slab, int64_t lo_offset, void* stream);
 
 /* -------------------------------------------------------------------- PPON
  * Replaces PPON.forward with RRBlock_32 / _ResBlock_32 (architectures/PPON_arch.py:12-129): first conv,
@@ -605,6 +622,15 @@ int innfer_ppon_set_precision(innfer_ppon_t p, int fp32);
 /* d_in [N,in_nc,H,W] -> d_out_{c,s,p} [N,out_nc,scale*H,scale*W], NCHW f16/f32; d_out_c / d_out_s may be NULL. */
 int innfer_ppon_forward(innfer_ppon_t p, const void* d_in, int in_dtype, void* d_out_c, void* d_out_s, void* d_out_p,
                         int out_dtype, int N, int H, int W, void* d_workspace, size_t workspace_bytes, void* stream);
+/* (124, additive) The forwards' two pass kernels one launch at a time, for tests: the launch functions they call (csrc/ppon.hip ppon_upsample3_launch / ppon_axpy_launch,
+ * csrc/f32ops.hip f32_axpy_launch).  Device pointers; no network object is needed.
+ * innfer_ppon_upsample3: nearest 3x of a 64-channel fp16 slab: d_in two groups [N * H * W][32] in_group_stride elements apart -> d_out two groups [N * 3H * 3W][32]
+ *   out_group_stride apart.  Refused: a group stride below N H W 32 (9 N H W 32 for the output).
+ * innfer_ppon_axpy: out[i] = a * x[i] + y[i], i < n; d_x may alias d_out, as the forwards call it.  form 0: ppon_axpy (the fp16 engine's kernel; dtype INNFER_F16, or
+ *   INNFER_F32 as with fp32 outputs); form 1: f32_axpy_launch (the fp32 mode's; INNFER_F32 only).
+ * Refused with nothing launched (INNFER_ERR_INVALID): a null pointer, a size below 1, an unknown dtype or form, form 1 on fp16 values. */
+int innfer_ppon_upsample3(const void* d_in, int64_t in_group_stride, void* d_out, int64_t out_group_stride, int N, int H, int W, void* stream);
+int innfer_ppon_axpy(const void* d_x, const void* d_y, void* d_out, float a, int64_t n, int dtype, int form, void* stream);
 
 /* -------------------------------------------------------- CycleGAN ResNet
  * Replaces ResnetGenerator(norm=instance, padding=reflect, upsample=deconv).forward with ResnetBlock
@@ -652,6 +678,16 @@ size_t innfer_wbc_workspace_bytes(innfer_wbc_t u, int N, int H, int W);
 int innfer_wbc_set_precision(innfer_wbc_t w, int fp32);
 int innfer_wbc_forward(innfer_wbc_t u, const void* d_in, int in_dtype, void* d_out, int out_dtype,
                        int N, int H, int W, void* d_workspace, size_t workspace_bytes, void* stream);
+/* (124, additive) The forward's two pass kernels one launch at a time, for tests: the launch functions it calls (csrc/wbcunet.hip wb_pre_launch / wb_upadd_launch,
+ * csrc/f32ops.hip f32_upadd_launch).  Device pointers; no network object is needed.
+ * innfer_wbc_pre: NCHW [N][C][H][W] (fp16 | fp32, rounded to nearest even) -> the row-patch slab [N * H * W][32] of the first 7x7 conv: channel kx * C + c of pixel (y, x)
+ *   holds in[c][y][x + kx - 3], zero outside the row and in channels 7 C .. 31.  Refused: 7 C > 32 (INNFER_ERR_UNSUPPORTED).
+ * innfer_wbc_upadd: out[2h x 2w] = up2x(in[h x w]) + skip.  tf_mode 0: F.interpolate(scale_factor=2, 'bilinear', align_corners=False); 1: tf_2xupsample_bilinear
+ *   (WBCNet_arch.py:126-137).  INNFER_F16: blocked slabs [C / 32][N * pixels][32], C = 32 | 64 (wb_upadd; the upsampled value is rounded to fp16 before the add);
+ *   INNFER_F32: NCHW fp32 (f32_upadd_launch, any C).
+ * Refused with nothing launched (INNFER_ERR_INVALID): a null pointer, a size below 1, a dtype or tf_mode outside the above, a slab C other than 32 | 64. */
+int innfer_wbc_pre(const void* d_in, int in_dtype, int N, int C, int H, int W, void* d_slab, void* stream);
+int innfer_wbc_upadd(const void* d_in, const void* d_skip, int dtype, int N, int C, int h, int w, int tf_mode, void* d_out, void* stream);
 /* d_x (guidance), d_y (input), d_out: [N,C,H,W] tensors of one dtype (f16/f32); means over 3x3 windows, reflect padding. */
 size_t innfer_guided_filter_workspace_bytes(int N, int C, int H, int W);
 int innfer_guided_filter(const void* d_x, const void* d_y, int dtype, int N, int C, int H, int W, float eps, void* d_out,
@@ -867,6 +903,13 @@ int innfer_f32conv_plan(const innfer_f32conv_args* a, int* plan);
 int innfer_f32_norm(const float* d_in, int64_t in_ns, int64_t in_cs, float* d_out, int64_t out_ns, int64_t out_cs, int N, int C, int64_t HW, int mode, float eps,
                     const float* d_weight, const float* d_bias, const float* d_rmean, const float* d_rvar, int act,
                     const float* d_res, int64_t res_ns, int64_t res_cs, int form, void* stream);
+/* (124, additive) Two more passes of the fp32 mode as single launches, for tests (csrc/f32ops.hip f32_prefix_lrelu_launch / f32_act_copy_launch, as PPON's and the UNet's
+ * fp32 forwards call them).  Device pointers; no network object is needed.
+ * innfer_f32_prefix_lrelu: d_t fp32 [N][groups * gc][hw], IN PLACE: channel c of group k becomes LeakyReLU(0.2)(group 0 + .. + group k), the sums formed in group order.
+ * innfer_f32_act_copy: d_out[n * out_ns + r] = act(d_in[n * in_ns + r]), r < per_image, n < N; act 0 none, 1 LeakyReLU(0.2), 2 ReLU, 3 tanh, 4 sigmoid.
+ * Refused with nothing launched (INNFER_ERR_INVALID): a null pointer, a size below 1, an image stride below per_image, an act outside 0 .. 4. */
+int innfer_f32_prefix_lrelu(float* d_t, int N, int groups, int gc, int64_t hw, void* stream);
+int innfer_f32_act_copy(const float* d_in, int64_t in_ns, float* d_out, int64_t out_ns, int64_t per_image, int N, int act, void* stream);
 
 /* (120) The norm statistics of the fp16 engine (csrc/norm_stats.h; train-mode BatchNorm2d of the pix2pix UNet, InstanceNorm2d of the CycleGAN ResNet) as single
  * launches, for tests.  alpha / shift: [N][C] floats with  norm(x) = x * alpha + shift,  alpha = gamma / sqrt(var + eps), shift = beta - mean * alpha  (biased variance

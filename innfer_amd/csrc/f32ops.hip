@@ -1074,3 +1074,19 @@ extern "C" int innfer_f32_norm(const float* d_in, int64_t in_ns, int64_t in_cs, 
     return f32_norm_launch_form(d_in, in_ns, in_cs, d_out, out_ns, out_cs, N, C, HW, mode, eps, d_weight, d_bias, d_rmean, d_rvar, act, (hipStream_t)stream,
                                 d_res, res_ns, res_cs, form);
 }
+
+// ---- C ABI (124): two more fp32-mode passes as single launches, for tests ----
+extern "C" int innfer_f32_prefix_lrelu(float* d_t, int N, int groups, int gc, int64_t hw, void* stream) {
+    if (!d_t) return set_error(INNFER_ERR_INVALID, "f32_prefix_lrelu: null argument");
+    if (N < 1 || groups < 1 || gc < 1 || hw < 1) return set_error(INNFER_ERR_INVALID, "f32_prefix_lrelu: N = %d, %d groups of %d channels, %lld pixels", N, groups, gc, (long long)hw);
+    return f32_prefix_lrelu_launch(d_t, N, groups, gc, (long)hw, (hipStream_t)stream);
+}
+
+extern "C" int innfer_f32_act_copy(const float* d_in, int64_t in_ns, float* d_out, int64_t out_ns, int64_t per_image, int N, int act, void* stream) {
+    if (!d_in || !d_out) return set_error(INNFER_ERR_INVALID, "f32_act_copy: null argument");
+    if (N < 1 || per_image < 1 || in_ns < per_image || out_ns < per_image)
+        return set_error(INNFER_ERR_INVALID, "f32_act_copy: N = %d, %lld values per image, strides %lld / %lld (at least the values per image)", N, (long long)per_image,
+                         (long long)in_ns, (long long)out_ns);
+    if (act < 0 || act > 4) return set_error(INNFER_ERR_INVALID, "f32_act_copy: act %d (0 none, 1 LeakyReLU(0.2), 2 ReLU, 3 tanh, 4 sigmoid)", act);
+    return f32_act_copy_launch(d_in, (long)in_ns, d_out, (long)out_ns, (long)per_image, N, act, (hipStream_t)stream);
+}

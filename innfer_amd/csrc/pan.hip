@@ -647,8 +647,12 @@ __global__ void pan_upsample(const f16* src, long sg, f16* dst, long dg, int gro
 
 // out = conv_last + bias + bilinear(x, align_corners=True) -> NCHW
 // (rs == 0: raw is the planar fp32 [N][C][FH][FW] output of the halo-tile conv, bias already added)
+// pan_final and pan_final_x4 promise the SAME BITS per output, so their arithmetic is spelled out: `#pragma clang fp contract(off)` in both bodies -- every product and
+// sum of the interpolation rounded on its own, as ATen's CPU kernel rounds them.  Left to the compiler's contraction the two differed in the last bit (4 of 4096 values
+// of a 16 x 32 frame at 2x, 50 of 160 of a 1 x 5 frame at 4x with fp32 stores: tests/test_gpu_glue_kernels.py test_pan_final).
 __global__ void pan_final(const float* raw, int rs, const float* bias, int C, const void* x, int x_f32, int N, int H, int W,
                           int scale, void* out, int out_f32) {
+#pragma clang fp contract(off)
     const int FH = H * scale, FW = W * scale;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)N * FH * FW) return;
@@ -679,6 +683,7 @@ __global__ void pan_final(const float* raw, int rs, const float* bias, int C, co
 // The same for the planar raw buffer (rs == 0) when FW % 4 == 0: four consecutive pixels of one channel per thread -- one 16-byte read of the conv's result, the
 // four bilinear samples of the input in pan_final's own arithmetic, one 8- / 16-byte store (the one-pixel-per-thread form moved 1.3 TB/s)
 __global__ void pan_final_x4(const float* raw, int C, const void* x, int x_f32, int N, int H, int W, int scale, void* out, int out_f32) {
+#pragma clang fp contract(off)
     const int FH = H * scale, FW = W * scale, FW4 = FW >> 2;
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (long)N * C * FH * FW4) return;
@@ -711,6 +716,40 @@ __global__ void pan_final_x4(const float* raw, int C, const void* x, int x_f32, 
     }
     if (out_f32) *(f32x4*)((float*)out + o) = f32x4{v[0], v[1], v[2], v[3]};
     else *(f16x4*)((f16*)out + o) = f16x4{(f16)v[0], (f16)v[1], (f16)v[2], (f16)v[3]};
+}
+
+// ---- the launches of the kernels above: the forwards and the single-launch entry points (innfer_pan_pre .. innfer_pan_slab_pair) share them ----
+int pan_pre_launch(const void* in, int in_f32, int C, long HW, int N, f16* slab, hipStream_t s) {
+    const long px = (long)N * HW;
+    hipLaunchKernelGGL(pan_pre, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, s, in, in_f32, C, HW, N, slab);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int pan_slab_pair_launch(const float* x, int C, long HW, int N, int groups, f16* slab, long lo, hipStream_t s) {
+    const long px = (long)N * HW;
+    hipLaunchKernelGGL(pan_nchw_to_slab_pair, dim3((unsigned)((px * groups * 4 + 255) / 256)), dim3(256), 0, s, x, C, HW, N, groups, slab, lo);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int pan_upsample_launch(const f16* src, long sg, f16* dst, long dg, int groups, int N, int h, int w, int f, int bilinear, hipStream_t s) {
+    const long tot = (long)N * (f * h) * (f * w) * groups * 4;
+    hipLaunchKernelGGL(pan_upsample, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, src, sg, dst, dg, groups, N, h, w, f, bilinear);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+// form -1: the strip kernel where the output width is a multiple of 4, else one pixel per thread; 0: one pixel per thread; 1: the strip kernel (the caller checks the width)
+int pan_final_launch(const float* raw, int C, const void* x, int x_f32, int N, int H, int W, int scale, void* out, int out_f32, int form, hipStream_t s) {
+    const long fpx = (long)N * (H * scale) * (W * scale);
+    if (form == 1 || (form < 0 && (W * scale) % 4 == 0)) {
+        const long nthr = fpx * C / 4;
+        hipLaunchKernelGGL(pan_final_x4, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, raw, C, x, x_f32, N, H, W, scale, out, out_f32);
+    } else
+        hipLaunchKernelGGL(pan_final, dim3((unsigned)((fpx + 255) / 256)), dim3(256), 0, s, raw, 0, (const float*)nullptr, C, x, x_f32, N, H, W, scale, out, out_f32);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
 }
 
 struct Gemm {                       // one packed GEMM
@@ -1119,8 +1158,7 @@ int pan_forward_f32(innfer_pan* p, const float* x, float* y, int N, int H, int W
         const long px = (long)N * H * W;
         f16* TS = (f16*)XA;                                     // (XA | XB are contiguous and free here: 320 B per pixel for the 256 of a two-group pair)
         {   GtScope gt(s, "pan NCHW fp32 -> (hi, lo) slab pair", 0.0, (double)px * (nf * 4.0 + 256.0));
-            hipLaunchKernelGGL(pan_nchw_to_slab_pair, dim3((unsigned)((px * 8 + 255) / 256)), dim3(256), 0, s, cur, nf, hw, N, 2, TS, 2 * px * 32);
-            INNFER_HIP(hipGetLastError()); }
+            CK(pan_slab_pair_launch(cur, nf, hw, N, 2, TS, 2 * px * 32, s)); }
         auto convs = [&](const Gemm& g, const f16* in, long in_g, long in_lo, int Ho, int Wo, int up, int act, const f16* res, f16* dst, float* planar, const Gemm* gate = nullptr) -> int {
             ConvLaunch L{};
             const long og = (long)N * Ho * Wo * 32;
@@ -1175,8 +1213,7 @@ int pan_forward_f32(innfer_pan* p, const float* x, float* y, int N, int H, int W
     {
         const long fpx = (long)N * h * w;
         GtScope gt(s, "pan_final (+ bilinear skip, NCHW)", 0.0, (double)fpx * p->out_nc * 8.0);
-        hipLaunchKernelGGL(pan_final, dim3((unsigned)((fpx + 255) / 256)), dim3(256), 0, s, (const float*)RAW, 0, (const float*)nullptr, p->out_nc, (const void*)x, 1, N, H, W, p->scale, (void*)y, 1);
-        INNFER_HIP(hipGetLastError());
+        CK(pan_final_launch(RAW, p->out_nc, x, 1, N, H, W, p->scale, y, 1, 0, s));          // (this forward has always taken the one-pixel form)
     }
 #undef CK
     return INNFER_OK;
@@ -1343,8 +1380,7 @@ extern "C" int innfer_pan_forward(innfer_pan* p, const void* d_in, int in_dtype,
         *T = (f16*)(ws + cv.t), *POOL = (f16*)(ws + cv.pool);
 
     {   GtScope gt(s, "pan_pre (NCHW -> slab)", 0.0, (double)px * (p->in_nc * (in_dtype == INNFER_F32 ? 4.0 : 2.0) + 64.0));
-        hipLaunchKernelGGL(pan_pre, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, s, d_in, in_dtype == INNFER_F32, p->in_nc, (long)H * W, N, X0);
-        INNFER_HIP(hipGetLastError()); }
+        CK(pan_pre_launch(d_in, in_dtype == INNFER_F32, p->in_nc, (long)H * W, N, X0, s)); }
     CK(conv3(X0, G, H, W, 0, 0, nullptr, 0, FEA, G));                                  // conv_first
     const f16* x = FEA;
     for (int k = 0; k < (p->double_scpa ? 2 : 1); ++k) {
@@ -1409,9 +1445,7 @@ extern "C" int innfer_pan_forward(innfer_pan* p, const void* d_in, int in_dtype,
         if (p->bilinear_up || uf == 3) {                                               // conv(upsampled(t)): the upsampling as its own pass
             f16* UPS = (f16*)(ws + cv.ups);
             const int groups = u == 0 ? 2 : 1;                                         // nf = 40 / unf = 24 channels (pad channels stay zero: 0 interpolates to 0)
-            const long tot = hpx * groups * 4;
-            hipLaunchKernelGGL(pan_upsample, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, cur, cur_g, UPS, HG, groups, N, h, w, uf, p->bilinear_up ? 1 : 0);
-            INNFER_HIP(hipGetLastError());
+            CK(pan_upsample_launch(cur, cur_g, UPS, HG, groups, N, h, w, uf, p->bilinear_up ? 1 : 0, s));
             CK(conv3(UPS, HG, hh, ww, 0, va, nullptr, 0, Vd, HG, nullptr, gate));
         } else
         CK(conv3(cur, cur_g, hh, ww, 1, va, nullptr, 0, Vd, HG, nullptr, gate));       // conv(nearest2x(t)) [+ PA]
@@ -1437,14 +1471,7 @@ extern "C" int innfer_pan_forward(innfer_pan* p, const void* d_in, int in_dtype,
     {
         const long fpx = (long)N * h * w;
         GtScope gt(s, "pan_final (+ bilinear skip, NCHW)", 0.0, (double)fpx * p->out_nc * (4.0 + (out_dtype == INNFER_F32 ? 4.0 : 2.0)));
-        if (w % 4 == 0) {
-            const long nthr = fpx * p->out_nc / 4;
-            hipLaunchKernelGGL(pan_final_x4, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, (const float*)raw, p->out_nc, d_in, in_dtype == INNFER_F32, N, H, W, p->scale,
-                               d_out, out_dtype == INNFER_F32);
-        } else
-        hipLaunchKernelGGL(pan_final, dim3((unsigned)((fpx + 255) / 256)), dim3(256), 0, s, raw, 0, vec("conv_last.bias"), p->out_nc,
-                           d_in, in_dtype == INNFER_F32, N, H, W, p->scale, d_out, out_dtype == INNFER_F32);
-        INNFER_HIP(hipGetLastError());
+        CK(pan_final_launch(raw, p->out_nc, d_in, in_dtype == INNFER_F32, N, H, W, p->scale, d_out, out_dtype == INNFER_F32, -1, s));
     }
 #undef CK
     return INNFER_OK;
@@ -1523,4 +1550,45 @@ extern "C" int innfer_pan_split_to_nchw(const void* d_planes, float* d_x, int N,
     if (N < 1 || H < 1 || W < 1) return set_error(INNFER_ERR_INVALID, "pan_split_to_nchw: N = %d, %d x %d", N, H, W);
     if (!pan_scpa_split_ok(N, H, W)) return set_error(INNFER_ERR_UNSUPPORTED, "pan_split_to_nchw: tensor too large for 32-bit offsets");
     return pan_split_to_nchw(d_planes, d_x, N, H, W, (hipStream_t)stream);
+}
+
+// ---- the tail kernels one launch at a time, for tests (include/innfer_amd.h, ABI 124): the launch functions the two forwards call ----
+extern "C" int innfer_pan_pre(const void* d_in, int in_dtype, int N, int C, int H, int W, void* d_slab, void* stream) {
+    if (!d_in || !d_slab) return set_error(INNFER_ERR_INVALID, "pan_pre: null argument");
+    if (in_dtype != INNFER_F16 && in_dtype != INNFER_F32) return set_error(INNFER_ERR_INVALID, "pan_pre: input dtype %d (fp16 or fp32 NCHW)", in_dtype);
+    if (N < 1 || C < 1 || H < 1 || W < 1) return set_error(INNFER_ERR_INVALID, "pan_pre: N = %d, C = %d, %d x %d", N, C, H, W);
+    if (C > 32) return set_error(INNFER_ERR_UNSUPPORTED, "pan_pre: %d channels do not fit one 32-channel group", C);
+    return pan_pre_launch(d_in, in_dtype == INNFER_F32, C, (long)H * W, N, (f16*)d_slab, (hipStream_t)stream);
+}
+
+extern "C" int innfer_pan_upsample(const void* d_in, int dtype, int N, int C, int h, int w, int f, int bilinear, int64_t in_group_stride, void* d_out,
+                                   int64_t out_group_stride, void* stream) {
+    if (!d_in || !d_out) return set_error(INNFER_ERR_INVALID, "pan_upsample: null argument");
+    if (N < 1 || C < 1 || h < 1 || w < 1) return set_error(INNFER_ERR_INVALID, "pan_upsample: N = %d, C = %d, %d x %d", N, C, h, w);
+    if ((f != 2 && f != 3) || (bilinear != 0 && bilinear != 1)) return set_error(INNFER_ERR_INVALID, "pan_upsample: factor %d (2 | 3), bilinear %d (0 nearest | 1)", f, bilinear);
+    if (dtype == INNFER_F32) return f32_upsample_launch((const float*)d_in, (float*)d_out, (long)N * C, h, w, f, bilinear, (hipStream_t)stream);
+    if (dtype != INNFER_F16) return set_error(INNFER_ERR_INVALID, "pan_upsample: dtype %d (fp16 slabs or fp32 NCHW)", dtype);
+    if (C % 32 || C > 64) return set_error(INNFER_ERR_INVALID, "pan_upsample: the slab form moves whole 32-channel groups, one or two (C = 32 | 64), not %d", C);
+    if (in_group_stride < (int64_t)N * h * w * 32 || out_group_stride < (int64_t)N * f * h * f * w * 32)
+        return set_error(INNFER_ERR_INVALID, "pan_upsample: group strides %lld / %lld < N H W 32", (long long)in_group_stride, (long long)out_group_stride);
+    return pan_upsample_launch((const f16*)d_in, (long)in_group_stride, (f16*)d_out, (long)out_group_stride, C / 32, N, h, w, f, bilinear, (hipStream_t)stream);
+}
+
+extern "C" int innfer_pan_final(const float* d_raw, int C, const void* d_x, int x_dtype, int N, int H, int W, int scale, void* d_out, int out_dtype, int form, void* stream) {
+    if (!d_raw || !d_x || !d_out) return set_error(INNFER_ERR_INVALID, "pan_final: null argument");
+    if ((x_dtype != INNFER_F16 && x_dtype != INNFER_F32) || (out_dtype != INNFER_F16 && out_dtype != INNFER_F32))
+        return set_error(INNFER_ERR_INVALID, "pan_final: dtypes %d / %d (fp16 or fp32 NCHW)", x_dtype, out_dtype);
+    if (N < 1 || C < 1 || H < 1 || W < 1 || scale < 1 || scale > 4) return set_error(INNFER_ERR_INVALID, "pan_final: N = %d, C = %d, %d x %d, scale %d (1 .. 4)", N, C, H, W, scale);
+    if (form < -1 || form > 1) return set_error(INNFER_ERR_INVALID, "pan_final: form %d (-1 the forward's choice, 0 one pixel per thread, 1 strips of four)", form);
+    if (form == 1 && (W * scale) % 4) return set_error(INNFER_ERR_INVALID, "pan_final: the strip form takes an output width that is a multiple of 4, not %d", W * scale);
+    return pan_final_launch(d_raw, C, d_x, x_dtype == INNFER_F32, N, H, W, scale, d_out, out_dtype == INNFER_F32, form, (hipStream_t)stream);
+}
+
+extern "C" int innfer_pan_slab_pair(const float* d_x, int N, int C, int H, int W, void* d_slab, int64_t lo_offset, void* stream) {
+    if (!d_x || !d_slab) return set_error(INNFER_ERR_INVALID, "pan_slab_pair: null argument");
+    if (N < 1 || C < 1 || H < 1 || W < 1) return set_error(INNFER_ERR_INVALID, "pan_slab_pair: N = %d, C = %d, %d x %d", N, C, H, W);
+    const int groups = (C + 31) / 32;
+    if (lo_offset < (int64_t)groups * N * H * W * 32 || lo_offset % 8)
+        return set_error(INNFER_ERR_INVALID, "pan_slab_pair: lo offset %lld (at least the hi half's %d groups x N H W 32 elements, a multiple of 8)", (long long)lo_offset, groups);
+    return pan_slab_pair_launch(d_x, C, (long)H * W, N, groups, (f16*)d_slab, (long)lo_offset, (hipStream_t)stream);
 }

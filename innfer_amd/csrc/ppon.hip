@@ -106,6 +106,12 @@ __global__ void ppon_axpy(const void* x, const void* y, void* dst, float a, long
     else ((f16*)dst)[i] = (f16)(a * (float)((const f16*)x)[i] + (float)((const f16*)y)[i]);
 }
 
+int ppon_axpy_launch(const void* x, const void* y, void* dst, float a, long n, int f32, hipStream_t s) {
+    hipLaunchKernelGGL(ppon_axpy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, y, dst, a, n, f32);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
 // A record's views of the engine's device blocks (innfer_ppon.weights) sit in a base of their own: value-reset as one before every upload
 struct Conv3Dev { void* d_w = nullptr; float* d_b = nullptr;      // conv3x3.hip panels
                   void* d_up4 = nullptr; float* d_b4 = nullptr;   // the conv of an upconv_block also as four 2x2-tap phases (conv_pack_up2x_phases, bias once per phase)
@@ -306,6 +312,13 @@ __global__ void ppon_upsample3(const f16* src, long src_g, f16* dst, long dst_g,
     const long n = m / ((long)WO * HO);
     const long sp = (n * H + Y / 3) * W + X / 3;
     *(f16x8*)(dst + g * dst_g + m * 32 + q * 8) = *(const f16x8*)(src + g * src_g + sp * 32 + q * 8);
+}
+
+int ppon_upsample3_launch(const f16* src, long src_g, f16* dst, long dst_g, int N, int H, int W, hipStream_t s) {
+    const long nthr = (long)N * 9 * H * W * 4 * 2;
+    hipLaunchKernelGGL(ppon_upsample3, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, src, src_g, dst, dst_g, N, H, W);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
 }
 
 struct QCarve { size_t fea, t[4], o1, comb, raw, raw2, cfem, sfem, up[3], hr, tmp_c, tmp_s, total; };
@@ -610,9 +623,8 @@ extern "C" int innfer_ppon_forward(innfer_ppon* p, const void* d_in, int in_dtyp
             f16* dst = (f16*)(ws + cv.up[u]);
             if (p->scale == 3) {          // Upsample(nearest 3x) materialised in the (still unused) HR slab, then conv -> LeakyReLU
                 f16* U = (f16*)(ws + cv.hr);
-                const long g3 = tg * 9, nthr = (long)N * 9 * h * w * 4 * 2;
-                hipLaunchKernelGGL(ppon_upsample3, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, t, tg, U, g3, N, h, w);
-                INNFER_HIP(hipGetLastError());
+                const long g3 = tg * 9;
+                CK(ppon_upsample3_launch(t, tg, U, g3, N, h, w, s));
                 CK(conv(Hd.up[u], U, g3, dst, g3, 3 * h, 3 * w, 1, 0, nullptr, 0, OUT_SLAB));
                 t = dst; tg = g3; h *= 3; w *= 3;
                 continue;
@@ -651,12 +663,32 @@ extern "C" int innfer_ppon_forward(innfer_ppon* p, const void* d_in, int in_dtyp
     CK(rrblock(CFEM, T[0], T[1], T[2]));                                             // SFEM
     CK(rrblock(T[0], SFEM, T[1], T[2]));
     CK(recon(p->heads[1], SFEM, d_out_s));                                           // out_s = SRM(sfem) + out_c
-    hipLaunchKernelGGL(ppon_axpy, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, (const void*)d_out_s, (const void*)d_out_c, d_out_s, 1.0f, nout, f32o);
+    CK(ppon_axpy_launch(d_out_s, d_out_c, d_out_s, 1.0f, nout, f32o, s));
     CK(rrblock(SFEM, T[0], T[1], T[2]));                                             // PFEM
     CK(rrblock(T[0], CFEM, T[1], T[2]));                                             // (CFEM's slab is free now)
     CK(recon(p->heads[2], CFEM, d_out_p));                                           // out_p = alpha * PRM(pfem) + out_s
-    hipLaunchKernelGGL(ppon_axpy, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, s, (const void*)d_out_p, (const void*)d_out_s, d_out_p, p->alpha, nout, f32o);
-    INNFER_HIP(hipGetLastError());
+    CK(ppon_axpy_launch(d_out_p, d_out_s, d_out_p, p->alpha, nout, f32o, s));
 #undef CK
     return INNFER_OK;
+}
+
+// ---- the two pass kernels one launch at a time, for tests (include/innfer_amd.h, ABI 124): the launch functions the forwards call ----
+extern "C" int innfer_ppon_upsample3(const void* d_in, int64_t in_group_stride, void* d_out, int64_t out_group_stride, int N, int H, int W, void* stream) {
+    if (!d_in || !d_out) return set_error(INNFER_ERR_INVALID, "ppon_upsample3: null argument");
+    if (N < 1 || H < 1 || W < 1) return set_error(INNFER_ERR_INVALID, "ppon_upsample3: N = %d, %d x %d", N, H, W);
+    if (in_group_stride < (int64_t)N * H * W * 32 || out_group_stride < (int64_t)N * H * W * 9 * 32)
+        return set_error(INNFER_ERR_INVALID, "ppon_upsample3: group strides %lld / %lld < N H W 32", (long long)in_group_stride, (long long)out_group_stride);
+    return ppon_upsample3_launch((const f16*)d_in, (long)in_group_stride, (f16*)d_out, (long)out_group_stride, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int innfer_ppon_axpy(const void* d_x, const void* d_y, void* d_out, float a, int64_t n, int dtype, int form, void* stream) {
+    if (!d_x || !d_y || !d_out) return set_error(INNFER_ERR_INVALID, "ppon_axpy: null argument");
+    if (n < 1) return set_error(INNFER_ERR_INVALID, "ppon_axpy: n = %lld", (long long)n);
+    if (dtype != INNFER_F16 && dtype != INNFER_F32) return set_error(INNFER_ERR_INVALID, "ppon_axpy: dtype %d (fp16 or fp32)", dtype);
+    if (form == 1) {
+        if (dtype != INNFER_F32) return set_error(INNFER_ERR_INVALID, "ppon_axpy: form 1 (the fp32 mode's launch) takes fp32 values");
+        return f32_axpy_launch((const float*)d_x, (const float*)d_y, (float*)d_out, a, (long)n, (hipStream_t)stream);
+    }
+    if (form != 0) return set_error(INNFER_ERR_INVALID, "ppon_axpy: form %d (0 ppon_axpy, 1 f32_axpy_launch)", form);
+    return ppon_axpy_launch(d_x, d_y, d_out, a, (long)n, dtype == INNFER_F32, (hipStream_t)stream);
 }

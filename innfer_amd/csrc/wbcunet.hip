@@ -123,6 +123,20 @@ __global__ void wb_pre(const void* in, int in_f32, int C, int H, int W, int N, f
     for (int q = 0; q < 4; ++q) *(f16x8*)(slab + i * 32 + 8 * q) = *(const f16x8*)(v + 8 * q);
 }
 
+// the launches of the two kernels above: the forward and the single-launch entry points (innfer_wbc_pre, innfer_wbc_upadd) share them
+int wb_pre_launch(const void* in, int in_f32, int C, int H, int W, int N, f16* slab, hipStream_t s) {
+    hipLaunchKernelGGL(wb_pre, dim3((unsigned)(((long)N * H * W + 255) / 256)), dim3(256), 0, s, in, in_f32, C, H, W, N, slab);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
+int wb_upadd_launch(const f16* src, const f16* skip, f16* dst, int C, int N, int h, int w, int tf, hipStream_t s) {
+    const long nthr = (long)N * 4 * h * w * (C / 8);
+    hipLaunchKernelGGL(wb_upadd, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, src, (long)N * h * w * 32, skip, dst, (long)N * 4 * h * w * 32, C, N, h, w, tf);
+    INNFER_HIP(hipGetLastError());
+    return INNFER_OK;
+}
+
 // ---- guided filter (r = 1) on NCHW planes --------------------------------------------------------
 __device__ __forceinline__ int refl(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 __device__ __forceinline__ float ld(const void* p, long o, int f32) { return f32 ? ((const float*)p)[o] : (float)((const f16*)p)[o]; }
@@ -534,18 +548,11 @@ extern "C" int innfer_wbc_forward(innfer_wbc* u, const void* d_in, int in_dtype,
         INNFER_HIP(hipGetLastError());
         return INNFER_OK;
     };
-    auto upadd = [&](const f16* src, const f16* skip, f16* dst, int C, int h, int w) -> int {
-        const long nthr = (long)N * 4 * h * w * (C / 8);
-        hipLaunchKernelGGL(wb_upadd, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, src, (long)N * h * w * 32, skip, dst,
-                           (long)N * 4 * h * w * 32, C, N, h, w, u->tf);
-        INNFER_HIP(hipGetLastError());
-        return INNFER_OK;
-    };
+    auto upadd = [&](const f16* src, const f16* skip, f16* dst, int C, int h, int w) -> int { return wb_upadd_launch(src, skip, dst, C, N, h, w, u->tf, s); };
     f16 *XIN = (f16*)(ws + cv.xin), *X0 = (f16*)(ws + cv.x0), *T1 = (f16*)(ws + cv.t1), *X1 = (f16*)(ws + cv.x1), *T2 = (f16*)(ws + cv.t2),
         *A = (f16*)(ws + cv.a), *B = (f16*)(ws + cv.b), *Cc = (f16*)(ws + cv.c), *U1 = (f16*)(ws + cv.u1), *V1 = (f16*)(ws + cv.v1), *U0 = (f16*)(ws + cv.u0);
     const int H2 = H / 2, W2 = W / 2, H4 = H / 4, W4 = W / 4;
-    hipLaunchKernelGGL(wb_pre, dim3((unsigned)(((long)N * H * W + 255) / 256)), dim3(256), 0, s, d_in, in_dtype == INNFER_F32, 3, H, W, N, XIN);
-    INNFER_HIP(hipGetLastError());
+    CK(wb_pre_launch(d_in, in_dtype == INNFER_F32, 3, H, W, N, XIN, s));
     CK(layer(XIN, H, W, 1, 1, nullptr, X0, nullptr));                      // conv
     CK(layer(X0, H, W, 2, 1, nullptr, T1, nullptr));                       // conv_1 (stride 2)
     CK(layer(T1, H2, W2, 1, 1, nullptr, X1, nullptr));                     // conv_2
@@ -567,6 +574,24 @@ extern "C" int innfer_wbc_forward(innfer_wbc* u, const void* d_in, int in_dtype,
     CK(layer(XIN, H, W, 1, 0, nullptr, nullptr, d_out));                   // conv_9 -> NCHW
 #undef CK
     return INNFER_OK;
+}
+
+// ---- the two pass kernels one launch at a time, for tests (include/innfer_amd.h, ABI 124): the launch functions the forwards call ----
+extern "C" int innfer_wbc_pre(const void* d_in, int in_dtype, int N, int C, int H, int W, void* d_slab, void* stream) {
+    if (!d_in || !d_slab) return set_error(INNFER_ERR_INVALID, "wbc_pre: null argument");
+    if (in_dtype != INNFER_F16 && in_dtype != INNFER_F32) return set_error(INNFER_ERR_INVALID, "wbc_pre: input dtype %d (fp16 or fp32 NCHW)", in_dtype);
+    if (N < 1 || C < 1 || H < 1 || W < 1) return set_error(INNFER_ERR_INVALID, "wbc_pre: N = %d, C = %d, %d x %d", N, C, H, W);
+    if (7 * C > 32) return set_error(INNFER_ERR_UNSUPPORTED, "wbc_pre: the seven column taps of %d channels do not fit one 32-channel group", C);
+    return wb_pre_launch(d_in, in_dtype == INNFER_F32, C, H, W, N, (f16*)d_slab, (hipStream_t)stream);
+}
+
+extern "C" int innfer_wbc_upadd(const void* d_in, const void* d_skip, int dtype, int N, int C, int h, int w, int tf_mode, void* d_out, void* stream) {
+    if (!d_in || !d_skip || !d_out) return set_error(INNFER_ERR_INVALID, "wbc_upadd: null argument");
+    if (N < 1 || C < 1 || h < 1 || w < 1 || (tf_mode != 0 && tf_mode != 1)) return set_error(INNFER_ERR_INVALID, "wbc_upadd: N = %d, C = %d, %d x %d, tf_mode %d (0 | 1)", N, C, h, w, tf_mode);
+    if (dtype == INNFER_F32) return f32_upadd_launch((const float*)d_in, (const float*)d_skip, (float*)d_out, (long)N * C, h, w, tf_mode, (hipStream_t)stream);
+    if (dtype != INNFER_F16) return set_error(INNFER_ERR_INVALID, "wbc_upadd: dtype %d (fp16 slabs or fp32 NCHW)", dtype);
+    if (C != 32 && C != 64) return set_error(INNFER_ERR_INVALID, "wbc_upadd: the slab form takes C = 32 or 64, not %d", C);
+    return wb_upadd_launch((const f16*)d_in, (const f16*)d_skip, (f16*)d_out, C, N, h, w, tf_mode, (hipStream_t)stream);
 }
 
 extern "C" size_t innfer_guided_filter_workspace_bytes(int N, int C, int H, int W) {

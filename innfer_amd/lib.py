@@ -350,6 +350,17 @@ SIGNATURES = {
     "innfer_resnet_post_slab_pad": (C.c_int, [C.c_void_p, C.c_int64] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]),
     "innfer_resnet_sum9_tanh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "innfer_resnet_final": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    # (124) the remaining pass kernels of PAN, PPON, the WBC UNet and the fp32 mode, one launch at a time
+    "innfer_pan_pre": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "innfer_pan_upsample": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "innfer_pan_final": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "innfer_pan_slab_pair": (C.c_int, [C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_int64, C.c_void_p]),
+    "innfer_ppon_upsample3": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_int] * 3 + [C.c_void_p]),
+    "innfer_ppon_axpy": (C.c_int, [C.c_void_p] * 3 + [C.c_float, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "innfer_wbc_pre": (C.c_int, [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "innfer_wbc_upadd": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]),
+    "innfer_f32_prefix_lrelu": (C.c_int, [C.c_void_p] + [C.c_int] * 3 + [C.c_int64, C.c_void_p]),
+    "innfer_f32_act_copy": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "innfer_tile_plan": (C.c_int, [C.c_int] * 4 + [C.POINTER(C.c_int)] * 6),
     "innfer_tile_owner": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_int)] * 2),
     "innfer_extract_tiles_rect": (C.c_int, [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
@@ -379,7 +390,7 @@ for _name, (_res, _args) in SIGNATURES.items():
 
 lib = _lib
 
-ABI_VERSION = 123         # the header revision this binding was written against (INNFER_ABI_VERSION)
+ABI_VERSION = 124       # the header revision this binding was written against (INNFER_ABI_VERSION)
 if _lib.innfer_version() != ABI_VERSION and not _ABI_ANY:
     raise ImportError(f"{LIB_PATH} speaks ABI {_lib.innfer_version()}, this binding {ABI_VERSION}: rebuild with `make`")
 

@@ -119,6 +119,6 @@ def test_public_surface():
     assert [sig.parameters[k].default for k in list(sig.parameters)[2:]] == [False, True, None, None, "lanczos", False, False]
     assert list(inspect.signature(R.Model.run_u8).parameters) == ["self", "img", "normalize", "fp16", "out", "fit_channels", "seamless", "outscale", "outfilter",
                                                                   "tta"]                  # untouched
-    assert L.ABI_VERSION == 123 and L.lib.innfer_version() == 123
+    assert L.ABI_VERSION == 124 and L.lib.innfer_version() == 124
     for f in ("innfer_chop_multi_plan", "innfer_extract_tiles_u8_multi", "innfer_recompose_u8_multi"):
         assert hasattr(L.lib, f) and f in L.SIGNATURES

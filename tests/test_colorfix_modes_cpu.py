@@ -146,7 +146,7 @@ def test_binding():
     assert L.COLOR_FIX_MODES == {"lowfreq": 0, "wavelet": 1, "adain": 2}
     for name in ("innfer_color_fix_mode_workspace_bytes", "innfer_color_fix_mode"):
         assert name in L.SIGNATURES and getattr(L.lib, name).argtypes is not None
-    assert L.lib.innfer_version() == 123
+    assert L.lib.innfer_version() == 124
     # the workspace of the new modes does not grow with the images; mode 0 is innfer_color_fix's
     for mode in (1, 2):
         assert L.lib.innfer_color_fix_mode_workspace_bytes(mode, 8, 8, 32, 32, 3) == L.lib.innfer_color_fix_mode_workspace_bytes(mode, 1080, 1920, 4320, 7680, 3) < 1024

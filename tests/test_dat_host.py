@@ -24,7 +24,7 @@ def test_new_symbols_are_declared_bound_and_built():
     for sym in NEW:
         assert re.search(r"^(?:int|size_t) %s\(" % sym, hdr, re.M), sym
         assert sym in L.SIGNATURES and hasattr(L.lib, sym), sym
-    assert re.search(r"^#define INNFER_ABI_VERSION 123$", hdr, re.M) and L.lib.innfer_version() == 123
+    assert re.search(r"^#define INNFER_ABI_VERSION 124$", hdr, re.M) and L.lib.innfer_version() == 124
     assert "innfer_window_attention_rect" in hdr.split("#define INNFER_ABI_VERSION")[0], "the revision note does not name the new entry points"
     mk = open(os.path.join(ROOT, "Makefile")).read()
     for src in ("win_attn_rect", "chan_self_attn", "dwconv", "aim_mix", "dat_launches"):

@@ -226,7 +226,7 @@ def test_input_map_comparators_reject_a_neighbouring_channel():
 
 # ------------------------------------------------------------------------------------------------ refusals (nothing launches: no pointer is dereferenced)
 def test_entry_points_refuse():
-    assert L.ABI_VERSION == 123 == L.lib.innfer_version()
+    assert L.ABI_VERSION == 124 == L.lib.innfer_version()
     n = 0
     for what, rc, want in R.refusals(L):
         assert rc == want, (what, rc, L.last_error())

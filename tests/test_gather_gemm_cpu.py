@@ -48,7 +48,7 @@ def test_packer_writes_the_documented_lds_image(cout, cin, ntaps):
 # ------------------------------------------------------------------------------------------------ plan
 def test_abi_revision():
     import innfer_amd.lib as L
-    assert L.ABI_VERSION == 123 == L.lib.innfer_version()
+    assert L.ABI_VERSION == 124 == L.lib.innfer_version()
     assert C.sizeof(L.GatherGemmArgs) % 8 == 0 and L.GatherGemmArgs.keep_partials.offset + 8 == C.sizeof(L.GatherGemmArgs)
 
 

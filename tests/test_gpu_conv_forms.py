@@ -331,6 +331,48 @@ def test_conv1x1_running_sum_operand(dev, Cc):
             _check(dev, c, "1x1, running-sum operand", act=act)
 
 
+def test_conv1x1_running_sum_operand_with_ppon_residuals(dev):
+    """c2 exactly as PPON issues it: 1x1, 256 -> 64 on the running-sum operand, no activation, then its two residual stages (out * 0.2 + x, * 0.2 + the block's input)."""
+    for (N, H, W) in S16:
+        c = Case("1x1", N, 256, 64, H, W, seed=336, prefix=1)
+        _check(dev, c, "1x1, running-sum operand, two residuals", act=0, nres=2, s1=0.2, s2=0.2)
+
+
+@pytest.mark.parametrize("N,H,W", [(1, 1, 1), (1, 5, 3), (1, 25, 33), (2, 37, 45)])
+def test_dilation_groups_one_launch(dev, N, H, W):
+    """PPON's eight dilated convs (64 -> 32 each, rates 1 .. 8) as the ONE launch the network issues (dilation_groups = 8: one panel and one bias column per rate),
+    each rate against its own float64 dilated conv under ulp16 / 2 + 8 e32 of that rate; 5 x 3 lies below most rates (every tap but the centre's falls outside)."""
+    import innfer_amd.lib as L
+    from innfer_amd import synth
+    G = 8
+    x = torch.from_numpy(synth.uniform((N, 64, H, W), 810 + H, -1, 1)).half()
+    ws = [torch.from_numpy(synth.uniform((32, 64, 3, 3), 820 + g, -1, 1) / np.float32(24.0)) for g in range(G)]
+    b = torch.from_numpy(synth.uniform((32 * G,), 830, -1, 1))
+    pb = L.lib.innfer_conv3x3_packed_bytes(32, 64)
+    packed = np.zeros(G * pb, dtype=np.uint8)
+    for g in range(G):
+        L.check(L.lib.innfer_pack_conv3x3(np.ascontiguousarray(ws[g].numpy()).ctypes.data, 32, 64, packed[g * pb:].ctypes.data))
+    xin, d_packed, d_bias = R.to_slab(x, 3).to(dev), torch.from_numpy(packed).to(dev), b.to(dev)
+    gs, numel = N * H * W * 32, G * N * H * W * 32
+    buf = torch.full((numel + 2 * GUARD,), FILL, dtype=torch.float16, device=dev)
+    a = L.ConvArgs()
+    a.d_in, a.in_group_stride, a.C = xin.data_ptr(), gs, 64
+    a.d_packed, a.d_bias = d_packed.data_ptr(), d_bias.data_ptr()
+    a.d_out, a.out_group_stride, a.out_ch_off, a.K = buf.data_ptr() + 2 * GUARD, gs, 0, 32 * G
+    a.N, a.H, a.W, a.act, a.dilation_groups = N, H, W, 0, G
+    rc = L.lib.innfer_conv3x3_f16(C.byref(a), None)
+    torch.cuda.synchronize()
+    assert rc == 0, L.last_error()
+    raw = buf.cpu()
+    assert bool((raw[:GUARD] == FILL).all()) and bool((raw[GUARD + numel:] == FILL).all()), "wrote outside the output"
+    got = R.from_slab(raw[GUARD:GUARD + numel].reshape(G, N, H, W, 32))
+    for g in range(G):
+        conv = lambda dt: F.conv2d(x.to(dt), ws[g].half().to(dt), b[32 * g:32 * g + 32].to(dt), padding=g + 1, dilation=g + 1)
+        y64 = conv(torch.float64)
+        e32 = (conv(torch.float32).double() - y64).abs().max().item()
+        R.assert_within_fp16_rounding(got[:, 32 * g:32 * g + 32], y64, e32, what=f"dilation_groups rate {g + 1} {N}x{H}x{W}", family="dilation groups, one launch")
+
+
 # ------------------------------------------------------------------------------------------------ the self gate
 @pytest.mark.parametrize("Cc", [32, 64])
 @pytest.mark.parametrize("up", [0, 1])

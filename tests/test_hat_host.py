@@ -159,7 +159,7 @@ def test_refusals():
 
 
 def test_new_symbols_are_declared_and_bound():
-    """The new entry points: declared in the header as additive under 123, bound in lib.py's SIGNATURES; the ABI revision is still 123; the sources are part of the build;
+    """The new entry points: declared in the header as additive under 123, bound in lib.py's SIGNATURES; the ABI revision (now 124); the sources are part of the build;
     win_attn.hip is the SwinIR commit's, untouched."""
     hdr = open(os.path.join(ROOT, "include", "innfer_amd.h")).read()
     lib_py = open(os.path.join(ROOT, "innfer_amd", "lib.py")).read()
@@ -168,7 +168,7 @@ def test_new_symbols_are_declared_and_bound():
         assert '"%s"' % sym in lib_py, sym
     for sym in ("innfer_chan_attn_work_bytes", "innfer_chan_attn_excite", "innfer_chan_attn_scale_add"):
         assert re.search(r"^(int|size_t) %s\(" % sym, hdr, re.M) and '"%s"' % sym in lib_py, sym
-    assert re.search(r"^#define INNFER_ABI_VERSION 123$", hdr, re.M)
+    assert re.search(r"^#define INNFER_ABI_VERSION 124$", hdr, re.M)
     assert "act = 13" in hdr
     net = open(os.path.join(ROOT, "innfer_amd", "csrc", "net.hip")).read()
     assert "net->kind == 6" in net and "win_attn16_launch" in net and "ca_scale_add_launch" in net

@@ -95,7 +95,7 @@ def test_conv_stats_records_formula():
 def test_short_statistics_buffers_are_refused_on_the_host():
     """ABI 120: a d_stats_part of fewer than N * records * channels * 3 floats is INNFER_ERR_WORKSPACE on every branch of innfer_conv3x3_f16 that takes
     statistics, before anything is launched (the pointers here are never dereferenced); likewise innfer_norm_stats' segment scratch."""
-    assert L.ABI_VERSION == 123 == L.lib.innfer_version()
+    assert L.ABI_VERSION == 124 == L.lib.innfer_version()
     fake = 0x1000
     for kw, ph in ((dict(K=64), 1), (dict(K=128), 1), (dict(K=64, stride2_k4=1), 1), (dict(K=64, transposed2x=4), 4), (dict(K=128, transposed2x=3), 4),
                    (dict(K=64, column7=1), 1)):

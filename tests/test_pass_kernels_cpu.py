@@ -121,7 +121,7 @@ def _refused(rc, *codes):
 
 
 def test_unet_entry_points_refuse():
-    assert L.ABI_VERSION == 123 == L.lib.innfer_version()
+    assert L.ABI_VERSION == 124 == L.lib.innfer_version()
     f, no = FAKE, [None, 0, 0, 0]
     lib = L.lib
     # innfer_unet_pre

@@ -105,14 +105,14 @@ def test_refusals():
 
 
 def test_new_symbols_are_declared_and_bound():
-    """The new entry points: declared in the header, bound in lib.py's SIGNATURES; the ABI revision is still 123; the sources are part of the build."""
+    """The new entry points: declared in the header, bound in lib.py's SIGNATURES; the ABI revision (now 124); the sources are part of the build."""
     hdr = open(os.path.join(ROOT, "include", "innfer_amd.h")).read()
     lib_py = open(os.path.join(ROOT, "innfer_amd", "lib.py")).read()
     for sym in ("innfer_plksr_create", "innfer_net_set_group_norm", "innfer_plk_conv", "innfer_group_norm_skip"):
         assert re.search(r"^int %s\(" % sym, hdr, re.M), sym
         assert '"%s"' % sym in lib_py, sym
     assert re.search(r"^size_t innfer_group_norm_skip_work_bytes\(", hdr, re.M) and '"innfer_group_norm_skip_work_bytes"' in lib_py
-    assert re.search(r"^#define INNFER_ABI_VERSION 123$", hdr, re.M)
+    assert re.search(r"^#define INNFER_ABI_VERSION 124$", hdr, re.M)
     assert "plksr_forward" in open(os.path.join(ROOT, "innfer_amd", "csrc", "net.hip")).read()
     mk = open(os.path.join(ROOT, "Makefile")).read()
     assert "csrc/plk_conv.hip" in mk and "csrc/group_norm.hip" in mk

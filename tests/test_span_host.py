@@ -104,13 +104,13 @@ def test_refusals():
 
 
 def test_new_symbols_are_declared_and_bound():
-    """innfer_span_create / innfer_first_conv_map: declared in the header, bound in lib.py's SIGNATURES; the ABI revision is still 123."""
+    """innfer_span_create / innfer_first_conv_map: declared in the header, bound in lib.py's SIGNATURES; the ABI revision (now 124)."""
     hdr = open(os.path.join(ROOT, "include", "innfer_amd.h")).read()
     lib_py = open(os.path.join(ROOT, "innfer_amd", "lib.py")).read()
     for sym in ("innfer_span_create", "innfer_first_conv_map"):
         assert re.search(r"^int %s\(" % sym, hdr, re.M), sym
         assert '"%s"' % sym in lib_py, sym
-    assert re.search(r"^#define INNFER_ABI_VERSION 123$", hdr, re.M)
+    assert re.search(r"^#define INNFER_ABI_VERSION 124$", hdr, re.M)
     assert "span_forward" in open(os.path.join(ROOT, "innfer_amd", "csrc", "net.hip")).read()
 
 

@@ -132,13 +132,13 @@ def test_refusals():
 
 
 def test_new_symbols_are_declared_and_bound():
-    """The new entry points: declared in the header as additive under 123, bound in lib.py's SIGNATURES; the ABI revision is still 123; the sources are part of the build."""
+    """The new entry points: declared in the header as additive under 123, bound in lib.py's SIGNATURES; the ABI revision (now 124); the sources are part of the build."""
     hdr = open(os.path.join(ROOT, "include", "innfer_amd.h")).read()
     lib_py = open(os.path.join(ROOT, "innfer_amd", "lib.py")).read()
     for sym in ("innfer_swinir_create", "innfer_net_set_layer_norm", "innfer_net_set_attn_bias", "innfer_window_attention", "innfer_layer_norm"):
         assert re.search(r"/\* \(123, additive\)(?:(?!\*/).)*\*/\nint %s\(" % sym, hdr, re.S), sym
         assert '"%s"' % sym in lib_py, sym
-    assert re.search(r"^#define INNFER_ABI_VERSION 123$", hdr, re.M)
+    assert re.search(r"^#define INNFER_ABI_VERSION 124$", hdr, re.M)
     assert "act = 12 (GELU" in hdr
     net = open(os.path.join(ROOT, "innfer_amd", "csrc", "net.hip")).read()
     assert "swinir_forward" in net and "net->kind == 5" in net

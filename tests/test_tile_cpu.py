@@ -80,7 +80,7 @@ def test_spot_values_and_refusals():
             L.tile_plan(*bad)
     with pytest.raises(ValueError):
         L.tile_owner(50, 32, 8, 50)
-    assert L.ABI_VERSION == 123 and all(hasattr(L.lib, f) for f in ("innfer_tile_plan", "innfer_tile_owner", "innfer_extract_tiles_rect",
+    assert L.ABI_VERSION == 124 and all(hasattr(L.lib, f) for f in ("innfer_tile_plan", "innfer_tile_owner", "innfer_extract_tiles_rect",
                                                                     "innfer_extract_tiles_u8_rect", "innfer_stitch_tiles", "innfer_stitch_tiles_u8"))
 
 
