@@ -45,7 +45,7 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): RealPLKSR -- innfer_plksr_create, innfer_net_set_group_norm, innfer_conv_args.act 11 (Mish), innfer_plk_conv (the partial large-kernel conv as a single launch), innfer_group_norm_skip / innfer_group_norm_skip_work_bytes (per-sample GroupNorm + skip over a 64-channel slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): SwinIR -- innfer_swinir_create, innfer_net_set_layer_norm, innfer_net_set_attn_bias, innfer_conv_args.act 12 (exact GELU on the 1x1 form), innfer_window_attention (the 8 x 8 window attention as a single launch), innfer_layer_norm (per-pixel LayerNorm over a padded slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a HAT): HAT -- innfer_hat_create, innfer_net_set_chan_attn, innfer_net_set_conv_scale, innfer_conv_args.act 13 (exact GELU on the plain 3x3 form), innfer_window_attention16 (the 16 x 16 window attention over a 16 x 16 or an overlapping 24 x 24 key window as a single launch), innfer_chan_attn_work_bytes / innfer_chan_attn_excite / innfer_chan_attn_scale_add (the channel attention's launches).  Also added under 123 (additive: new entry points only, no struct or signature changed): the kernels of DAT's blocks as single launches -- innfer_window_attention_rect (rectangular windows in two transposed head branches), innfer_channel_attention_work_bytes / innfer_channel_attention_scores / innfer_channel_attention_apply (attention across channels over a whole sample), innfer_dwconv3x3 (depthwise 3 x 3 with its three epilogues), innfer_chan_attn_excite_gelu, innfer_aim_mix (the two gates that blend the attention and conv branches), innfer_layer_norm_wide (LayerNorm over up to 512 channels) -- and the network on them: innfer_dat_create, innfer_dat_block_floats, innfer_net_set_dat_block (innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a DAT).  124: the remaining pass kernels of PAN, PPON and the WBC UNet and two passes of the fp32 mode one launch at a time, for tests (additive) -- innfer_pan_pre, innfer_pan_upsample, innfer_pan_final, innfer_pan_slab_pair, innfer_ppon_upsample3, innfer_ppon_axpy, innfer_wbc_pre, innfer_wbc_upadd, innfer_f32_prefix_lrelu, innfer_f32_act_copy.  innfer_version() returns the library's; a binding should compare. */
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): RealPLKSR -- innfer_plksr_create, innfer_net_set_group_norm, innfer_conv_args.act 11 (Mish), innfer_plk_conv (the partial large-kernel conv as a single launch), innfer_group_norm_skip / innfer_group_norm_skip_work_bytes (per-sample GroupNorm + skip over a 64-channel slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): SwinIR -- innfer_swinir_create, innfer_net_set_layer_norm, innfer_net_set_attn_bias, innfer_conv_args.act 12 (exact GELU on the 1x1 form), innfer_window_attention (the 8 x 8 window attention as a single launch), innfer_layer_norm (per-pixel LayerNorm over a padded slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a HAT): HAT -- innfer_hat_create, innfer_net_set_chan_attn, innfer_net_set_conv_scale, innfer_conv_args.act 13 (exact GELU on the plain 3x3 form), innfer_window_attention16 (the 16 x 16 window attention over a 16 x 16 or an overlapping 24 x 24 key window as a single launch), innfer_chan_attn_work_bytes / innfer_chan_attn_excite / innfer_chan_attn_scale_add (the channel attention's launches).  Also added under 123 (additive: new entry points only, no struct or signature changed): the kernels of DAT's blocks as single launches -- innfer_window_attention_rect (rectangular windows in two transposed head branches), innfer_channel_attention_work_bytes / innfer_channel_attention_scores / innfer_channel_attention_apply (attention across channels over a whole sample), innfer_dwconv3x3 (depthwise 3 x 3 with its three epilogues), innfer_chan_attn_excite_gelu, innfer_aim_mix (the two gates that blend the attention and conv branches), innfer_layer_norm_wide (LayerNorm over up to 512 channels) -- and the network on them: innfer_dat_create, innfer_dat_block_floats, innfer_net_set_dat_block (innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a DAT).  124: the remaining pass kernels of PAN, PPON and the WBC UNet and two passes of the fp32 mode one launch at a time, for tests (additive) -- innfer_pan_pre, innfer_pan_upsample, innfer_pan_final, innfer_pan_slab_pair, innfer_ppon_upsample3, innfer_ppon_axpy, innfer_wbc_pre, innfer_wbc_upadd, innfer_f32_prefix_lrelu, innfer_f32_act_copy.  Added under 124 without a new revision (additive: new entry points only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a DRCT): DRCT -- innfer_drct_create, innfer_window_attention16_wide (the 16 x 16 window attention for heads of 33 .. 128 channels as a single launch), innfer_layer_norm_holed (LayerNorm over a dense slab whose real channels have a hole).  innfer_version() returns the library's; a binding should compare. */
 #define INNFER_ABI_VERSION 124
 int innfer_version(void);
 const char* innfer_last_error(void);
@@ -330,6 +330,39 @@ int innfer_aim_mix(const void* d_x, int64_t x_gs, const void* d_y, int64_t y_gs,
 /* innfer_layer_norm_wide: innfer_layer_norm over slabs of up to 512 channels (c_pad % 64 == 0; DAT's ffn.sg.norm on half the hidden channels).  Same arithmetic and order. */
 int innfer_layer_norm_wide(const void* d_in, int64_t in_gs, void* d_out, int64_t out_gs, int64_t npix, int C, int c_pad, const float* h_gamma, const float* h_beta, float eps,
                            void* stream);
+/* (124, additive) The 16 x 16 window self-attention for heads WIDER than one 32-channel group, as a single launch (for tests; csrc/win_attn16_wide.hip).  32 < head_dim <= 128;
+ * a head owns G = ceil(head_dim / 32) consecutive groups: d_qkv holds 3 num_heads G groups (q of head h in groups h G .. h G + G - 1 -- head_dim real channels, then zeros,
+ * q already scaled -- then the num_heads G groups of k, then those of v), d_out num_heads G groups whose channels >= head_dim of every head are written as zeros.  Hp, Wp
+ * multiples of 16; shift 0 or 8 (the windows of the rolled frame, -100 between regions); h_bias [num_heads][256][256].  Arithmetic as innfer_window_attention16's: fp32 scores
+ * (the G channel steps chained in one accumulator), running maximum and sum over blocks of 64 keys; P rounded to fp16 in front of P v; fp32 accumulation; one rounding of
+ * o / sum.  Refused with a status, before anything is uploaded or written: head_dim <= 32 (innfer_window_attention16 takes those) or > 128, sizes that are no multiples of 16,
+ * a shift other than 0 or 8.  Uploads the table, launches, waits. */
+int innfer_window_attention16_wide(const void* d_qkv, int64_t qkv_gs, void* d_out, int64_t out_gs, const float* h_bias, int N, int Hp, int Wp, int num_heads, int head_dim,
+                                   int shift, void* stream);
+/* (124, additive) innfer_layer_norm over a slab whose real channels are [0, C) and [32 ceil(C / 32), c_end) (csrc/layer_norm.hip; DRCT's dense slab: x in its own groups,
+ * every 32-channel x_k in one group behind them).  The hole [C, 32 ceil(C / 32)) and the channels from c_end on stay out of the statistics whatever they hold -- NaN
+ * included -- and are written as zeros.  c_pad % 64 == 0, <= 512; h_gamma / h_beta: c_pad host floats in SLAB order.  Same arithmetic and order; d_in == d_out allowed. */
+int innfer_layer_norm_holed(const void* d_in, int64_t in_gs, void* d_out, int64_t out_gs, int64_t npix, int C, int c_end, int c_pad, const float* h_gamma,
+                            const float* h_beta, float eps, void* stream);
+/* (124, additive) DRCT (Hsu et al. 2024, "DRCT: Saving Image Super-Resolution away from Information Bottleneck"; the reference has no such architecture).  Written down
+ * without the published drct_arch.py at hand: that file is the definition, and a checkpoint's shapes are authoritative over the formulas here.  C = embed_dim, gc = 32,
+ * 16 x 16 windows, tokens = pixels:
+ *   forward(x):  reflect-pad right / bottom to multiples of 16; f = conv_first(x - mean); f = conv_after_body(norm(RDG_{R-1}(.. RDG_0(patch_embed.norm(f))))) + f;
+ *                conv_before_upsample + LeakyReLU(0.01); upsample (pixelshuffle); conv_last; + mean; crop
+ *   RDG(x):      x_k = lrelu_0.2(adjust_k(swin_k(cat(x, x_1 .. x_{k-1})))) for k = 1 .. 4 (dim_k = C + 32 (k - 1) -> 32);  x_5 = adjust_5(swin_5(cat(x, x_1 .. x_4))) (-> C);
+ *                return 0.2 x_5 + x          (adjust_k: a 1x1 conv with bias)
+ *   swin_k(t):   t = t + proj(attn(norm1(t)));  t = t + fc2(GELU(fc1(norm2(t))));  attn: shift 8 for k = 2, 4; softmax(q d^-0.5 k^T + B_h + M) v, nH_k heads of d = dim_k / nH_k
+ * on the engine of innfer_net_*.  h_heads / h_hidden: 5 n_groups ints, block k of group g at 5 g + k -- read off the checkpoint (relative_position_bias_table.shape[1],
+ * fc1.weight.shape[0]).  torch.cat is never materialised: one dense slab holds x in its own ceil(C / 32) groups (pad channels zero) and every x_k in one group behind them;
+ * the caller permutes the input columns of every norm, qkv, fc1 and adjust to that order, zero columns at the hole and the pads; qkv rows and proj columns are head-padded as
+ * innfer_window_attention16_wide's slab (G = 1: innfer_window_attention16's).  Conv slots `<state-dict key>#<p>` in forward order: conv_first; per block attn.qkv, attn.proj,
+ * mlp.fc1, mlp.fc2, then layers.<g>.adjust<k> (ONE slice for k < 5: 32 real rows and 32 zero rows, which clear the next group of the dense slab; C_pad / 64 slices for k = 5);
+ * conv_after_body; the pixelshuffle tail.  LayerNorms in forward order: 0 patch_embed.norm (C_pad floats), per block norm1, norm2 (lp_k floats each, slab order), the last one
+ * norm.  Bias tables: block b's [nH_b][256][256].  Limits (INNFER_ERR_UNSUPPORTED): embed_dim <= 256; <= 8 heads of <= 128 channels, dim_k % nH_k == 0; hidden <= 1024;
+ * in_nc == out_nc in 1 .. 4; scale 2, 3, 4; the fp16 mode only.  Launches of a forward, with S1 = C_pad / 64, per block lp_k = 32 (ceil(C / 32) + k - 1) rounded up to 64,
+ * S = lp_k / 64, SQ = ceil(3 nH G / 2), SH = hidden_pad / 64, A = 1 (k < 5) | S1 (k = 5), T = 2 + log2(scale) (4 for scale 3):
+ *   2 S1 + 2 + sum over blocks (3 + SQ + 2 S + SH + A) + T + 2 [H x W is not Hp x Wp]. */
+int innfer_drct_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, int n_groups, const int* h_heads, const int* h_hidden, int scale, const float* h_mean);
 /* (123, additive) DAT (Chen et al. 2023, "Dual Aggregation Transformer for Image Super-Resolution"; the reference has no such architecture), the published dat_arch.py, on
  * SwinIR's skeleton WITHOUT padding (the engine works on H x W).  C = embed_dim, nH heads of d = C / nH, split = [s0, s1], hid = hidden, tokens = pixels:
  *   forward(x):  f = conv_first(x - mean); f = conv_after_body(norm(RGs(before_RG.1(f)))) + f; tail (pixelshuffle | pixelshuffledirect); + mean

@@ -41,6 +41,8 @@ def get_network(opt_net):
         from .HAT_arch import HAT as net
     elif kind in ('dat', 'dat_net'):
         from .DAT_arch import DAT as net
+    elif kind in ('drct', 'drct_net'):
+        from .DRCT_arch import DRCT as net
     else:
         raise NotImplementedError('Model [{:s}] not recognized'.format(kind))
     return net(**opt_net)

@@ -320,6 +320,58 @@ def hat_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=6
     return s
 
 
+DRCT_GC = 32        # the dense group's growth: every adjust conv but the last makes 32 channels
+
+
+def drct_head_rule(dim, num_heads):
+    """Heads of a DRCT Swin block on `dim` channels as the published code is recalled to choose them: num_heads - (dim % num_heads).  Only a cross-check and the default of
+    the shell: a checkpoint's relative_position_bias_table.shape[1] decides."""
+    return num_heads - dim % num_heads
+
+
+def drct_shapes(in_chans=3, embed_dim=180, n_groups=6, num_heads=6, mlp_ratio=2.0, upscale=4, block_heads=None, block_hidden=None):
+    """State-dict key -> shape of the PARAMETERS of DRCT (the published drct_arch.py, written down without the source at hand; patch_size 1, qkv_bias, patch_norm, no absolute
+    position embedding, gc 32, the pixelshuffle tail).  THE ONE PLACE a correction of a key name or a shape goes: the shell, the loader, the synthetic checkpoints and the
+    tests are built from this table.  block_heads / block_hidden: per block, 5 n_groups entries (block k of group g at 5 g + k), as a checkpoint states them; None: the
+    published rule and int(dim mlp_ratio).  Not in it, because they are buffers: attn.relative_position_index of every block, attn_mask of the shifted ones."""
+    C, s = embed_dim, {}
+
+    def lin(k, co, ci):
+        s[k + '.weight'], s[k + '.bias'] = (co, ci), (co,)
+
+    def conv(k, co, ci, ks=3):
+        s[k + '.weight'], s[k + '.bias'] = (co, ci, ks, ks), (co,)
+
+    def norm(k, c=C):
+        s[k + '.weight'], s[k + '.bias'] = (c,), (c,)
+    conv('conv_first', C, in_chans)
+    norm('patch_embed.norm')
+    for i in range(n_groups):
+        for k in range(5):
+            dim = C + DRCT_GC * k
+            nh = drct_head_rule(dim, num_heads) if block_heads is None else block_heads[5 * i + k]
+            hid = int(dim * mlp_ratio + 1e-6) if block_hidden is None else block_hidden[5 * i + k]
+            b = f'layers.{i}.swin{k + 1}.'
+            norm(b + 'norm1', dim)
+            s[b + 'attn.relative_position_bias_table'] = (961, nh)
+            lin(b + 'attn.qkv', 3 * dim, dim)
+            lin(b + 'attn.proj', dim, dim)
+            norm(b + 'norm2', dim)
+            lin(b + 'mlp.fc1', hid, dim)
+            lin(b + 'mlp.fc2', dim, hid)
+            conv(f'layers.{i}.adjust{k + 1}', DRCT_GC if k < 4 else C, dim, 1)
+    norm('norm')
+    conv('conv_after_body', C, C)
+    conv('conv_before_upsample.0', 64, C)
+    if upscale == 3:
+        conv('upsample.0', 576, 64)
+    else:
+        for st in range(max(1, upscale.bit_length() - 1)):
+            conv(f'upsample.{2 * st}', 256, 64)
+    conv('conv_last', in_chans, 64)
+    return s
+
+
 def dat_pos_dim(embed_dim):
     """Width of the DynamicPosBias MLP of a DAT branch as recalled from the published code (the branch's dim // 4, again // 4); a checkpoint's pos_proj.weight decides."""
     return ((embed_dim // 2) // 4) // 4

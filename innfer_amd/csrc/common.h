@@ -305,6 +305,14 @@ int aim_mix_launch(const f16* x, long x_gs, const f16* y, long y_gs, f16* out, l
 // layer_norm_launch over slabs of up to 512 channels (layer_norm.hip)
 int layer_norm_wide_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s);
 
+// ---- DRCT's own kernels ----
+// win_attn16_launch's 16 x 16 self-attention (shift 0 | 8) for heads of 32 < d <= 128 channels (win_attn16_wide.hip): a head owns G = ceil(d / 32) consecutive groups --
+// qkv: 3 nH G groups (q of head h in groups h G .., then k, then v), out: nH G groups, channels >= d of a head written as zeros; relb: dense fp32 [nH][256][256]
+int win_attn16_wide_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, int N, int Hp, int Wp, int nH, int d, int shift, hipStream_t s);
+// layer_norm_launch over the real channels [0, C) and [32 ceil(C / 32), c_end) of slabs of c_pad <= 512 channels (layer_norm.hip): the hole and the channels from c_end on
+// stay out of the statistics and are written as zeros; gamma / beta: c_pad device floats in slab order; in == out allowed
+int layer_norm_holed_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_end, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s);
+
 // ---- layout / tiles / blend / pre-post (tiles.hip) ---------------------------
 int nchw_to_slab(const void* src, int src_f32, f16* slab, long gstride, int ch_off, int N, int C, int H, int W, hipStream_t s);
 int slab_to_nchw(const f16* slab, long gstride, int ch_off, void* dst, int dst_f32, int N, int C, int H, int W, hipStream_t s);

@@ -143,6 +143,10 @@ struct innfer_net {
     std::vector<int> dat_shift, dat_aca;         // per block (counted through the groups): shifted windows; 1 = the channel form (odd index INSIDE its group)
     std::vector<float*> dat_blk;
     std::vector<float> dat_sib2;                 // the last bias of spatial_interaction per block (a kernel argument)
+    // DRCT (kind 9; innfer_drct_create) on SwinIR's fields on the grid padded to 16: dr_r dense groups of five Swin blocks; per block (counted through the groups) its head
+    // count and MLP hidden size; sw_ln_w: the floats of gamma (and of beta) of every LayerNorm, in SLAB order (the dense slab's hole and pads included)
+    int dr_r = 0;
+    std::vector<int> dr_nh, dr_hid, sw_ln_w;
     bool span_norm = false;     // SPAN(norm=True): conv_1 reads (x - mean) * img_range through FirstConvLaunch.in_map (convs[0].d_map: alpha[in_nc] then shift[in_nc])
     int in_nc = 3, out_nc = 3, nf = 64, nb = 23, gc = 32, scale = 4, n_up = 2;
     int final_act = 0;           // `finalact` of the reference constructors: activation after the last conv (ConvLaunch.act codes)
@@ -471,12 +475,111 @@ extern "C" int innfer_swin2sr_create(innfer_net_t* out, int in_nc, int out_nc, i
     return swin_create(7, out, in_nc, out_nc, embed_dim, depths, n_layers, num_heads, mlp_hidden, upsampler, scale, conv3, h_mean);
 }
 
+// DRCT's widths: gx = ceil(C / 32) groups of x; block k = 0 .. 4 of a dense group reads ng[k] = gx + k groups (cpk[k] = 32 ng[k] channels: what a matrix product reads),
+// lp[k] = cpk[k] rounded up to 64 (what a LayerNorm covers and a chain of 64-output launches writes); per block b the head groups G = ceil(d / 32), nH G groups of q
+struct DrctDims { int gx, ng[5], cpk[5], lp[5], dense_groups, max_sq, max_hg, max_hp; };
+static int drct_head_groups(const innfer_net* net, size_t b) { const int d = (net->sw_c + 32 * (int)(b % 5)) / net->dr_nh[b]; return net->dr_nh[b] * ((d + 31) / 32); }
+static DrctDims drct_dims(const innfer_net* net) {
+    DrctDims d{};
+    d.gx = (net->sw_c + 31) / 32;
+    for (int k = 0; k < 5; ++k) { d.ng[k] = d.gx + k; d.cpk[k] = 32 * d.ng[k]; d.lp[k] = (d.cpk[k] + 63) / 64 * 64; }
+    d.dense_groups = (d.gx + 5 + 1) / 2 * 2;
+    for (size_t b = 0; b < net->dr_nh.size(); ++b) {
+        const int hg = drct_head_groups(net, b);
+        d.max_hg = std::max(d.max_hg, hg);
+        d.max_sq = std::max(d.max_sq, (3 * hg + 1) / 2);
+        d.max_hp = std::max(d.max_hp, (net->dr_hid[b] + 63) / 64 * 64);
+    }
+    return d;
+}
+// DRCT (Hsu et al. 2024; include/innfer_amd.h carries the definition): n_groups dense groups of five Swin blocks on 16 x 16 windows.  Block k = 0 .. 4 of a group works on
+// dim_k = C + 32 k channels with h_heads[5 g + k] heads and an MLP of h_hidden[5 g + k] channels.  torch.cat is a slab layout: x in its own ceil(C / 32) groups, x_k in one
+// group each behind them; the caller passes every weight with its input columns in that order (zero columns at the hole [C, 32 ceil(C / 32)) and the pads).  Conv slots
+// `<state-dict key>#<p>` in forward order: conv_first; per block attn.qkv (ceil(3 nH G / 2) slices of [64, 32 ng]), attn.proj (lp / 64 slices of [64, 32 nH G]), mlp.fc1,
+// mlp.fc2, adjust (one slice for k < 4: 32 real rows, 32 zero rows that clear the next group; C_pad / 64 slices for k = 4); conv_after_body; the pixelshuffle tail.
+// Launches of a forward, with S1 = C_pad / 64, per block S = lp_k / 64, SQ = ceil(3 nH G / 2), SH = hidden_pad / 64, A = 1 (k < 4) | S1 (k = 4), T = 2 + log2(scale) (4 for 3):
+//   2 S1 + 2 + sum over blocks (3 + SQ + 2 S + SH + A) + T + 2 [H x W is not Hp x Wp]
+extern "C" int innfer_drct_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, int n_groups, const int* h_heads, const int* h_hidden, int scale, const float* h_mean) {
+    if (!out || !h_heads || !h_hidden) return set_error(INNFER_ERR_INVALID, "drct_create: null argument");
+    if (embed_dim < 1 || embed_dim > 256) return set_error(INNFER_ERR_UNSUPPORTED, "drct_create: embed_dim=%d (built: 1 .. 256)", embed_dim);
+    if (in_nc < 1 || in_nc > 4 || in_nc != out_nc) return set_error(INNFER_ERR_UNSUPPORTED, "drct_create: in_chans=%d, %d output channels (built: equal, 1..4)", in_nc, out_nc);
+    if (n_groups < 1 || n_groups > 64) return set_error(INNFER_ERR_UNSUPPORTED, "drct_create: %d dense groups", n_groups);
+    if (scale < 2 || scale > 4) return set_error(INNFER_ERR_UNSUPPORTED, "drct_create: scale %d (built: 2, 3, 4 -- the pixelshuffle tail)", scale);
+    for (int b = 0; b < 5 * n_groups; ++b) {
+        const int dim = embed_dim + 32 * (b % 5), nh = h_heads[b];
+        if (nh < 1 || nh > 8 || dim % nh || dim / nh > 128)
+            return set_error(INNFER_ERR_UNSUPPORTED, "drct_create: block %d has %d heads on %d channels (built: <= 8 heads of <= 128 channels, dim %% heads == 0)", b, nh, dim);
+        if (h_hidden[b] < 1 || h_hidden[b] > 1024) return set_error(INNFER_ERR_UNSUPPORTED, "drct_create: an MLP of %d hidden channels in block %d (built: <= 1024)", h_hidden[b], b);
+    }
+    innfer_net* net = new innfer_net();
+    net->kind = 9; net->in_nc = in_nc; net->out_nc = out_nc; net->nf = 64; net->nb = 5 * n_groups; net->gc = 0; net->scale = scale; net->n_up = 0;
+    net->sw_c = embed_dim; net->sw_cp = (embed_dim + 63) / 64 * 64; net->sw_tail = 0; net->sw_conv3 = 0;
+    net->dr_r = n_groups;
+    net->dr_nh.assign(h_heads, h_heads + 5 * n_groups);
+    net->dr_hid.assign(h_hidden, h_hidden + 5 * n_groups);
+    const DrctDims dd = drct_dims(net);
+    const int cp = net->sw_cp;
+    net->sw_hp = dd.max_hp;
+    for (int p = 0; p < cp / 64; ++p) add_conv(net, "conv_first#" + std::to_string(p), 64, in_nc, true);
+    net->sw_ln_w.push_back(cp);
+    for (int i = 0; i < n_groups; ++i)
+        for (int k = 0; k < 5; ++k) {
+            const size_t b = (size_t)5 * i + k;
+            const std::string g = "layers." + std::to_string(i) + ".", sw = g + "swin" + std::to_string(k + 1) + ".";
+            const int hg = drct_head_groups(net, b), hp = (net->dr_hid[b] + 63) / 64 * 64;
+            swin_add_sliced(net, sw + "attn.qkv", (3 * hg + 1) / 2 * 64, dd.cpk[k], 1);
+            swin_add_sliced(net, sw + "attn.proj", dd.lp[k], 32 * hg, 1);
+            swin_add_sliced(net, sw + "mlp.fc1", hp, dd.cpk[k], 1);
+            swin_add_sliced(net, sw + "mlp.fc2", dd.lp[k], hp, 1);
+            swin_add_sliced(net, g + "adjust" + std::to_string(k + 1), k < 4 ? 64 : cp, dd.cpk[k], 1);
+            net->sw_ln_w.push_back(dd.lp[k]); net->sw_ln_w.push_back(dd.lp[k]);
+        }
+    net->sw_ln_w.push_back(cp);
+    swin_add_sliced(net, "conv_after_body", cp, cp, 3);
+    add_conv(net, "conv_before_upsample.0", 64, cp);
+    net->convs.back().slope_ok = true;
+    const float s2 = (float)(scale * scale);
+    if (scale == 3) add_conv(net, "upsample.0", 576, 64);
+    else {
+        add_conv(net, "upsample.0", 256, 64); net->convs.back().ps2 = true;
+        if (scale == 4) { add_conv(net, "upsample.2", 256, 64); net->convs.back().ps2 = true; net->convs.back().mult = 4.f; }
+    }
+    add_conv(net, "conv_last", out_nc, 64); net->convs.back().mult = s2;
+    net->sw_ln.assign(net->sw_ln_w.size(), nullptr);
+    net->sw_relb.assign((size_t)net->nb, nullptr);
+    int rc = INNFER_OK;
+    {   // x - mean in front of conv_first and nn.LeakyReLU() behind conv_before_upsample, as swin_create
+        float h[8];
+        for (int c = 0; c < in_nc; ++c) { h[c] = 1.f; h[in_nc + c] = h_mean ? -h_mean[c] : 0.f; }
+        ConvSlot& c0 = net->convs[0];
+        if (hipMalloc((void**)&c0.d_map, 2 * in_nc * sizeof(float)) != hipSuccess || hipMemcpy(c0.d_map, h, 2 * in_nc * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            rc = set_error(INNFER_ERR_NOMEM, "drct_create: no device memory for the input map");
+        for (size_t i = 0; i < net->convs.size() && rc == INNFER_OK; ++i)
+            if (net->convs[i].slope_ok) {
+                const std::vector<float> sl(64, 0.01f);
+                rc = innfer_net_set_conv_slope(net, (int)i, sl.data());
+            }
+    }
+    if (rc != INNFER_OK) { (void)hipGetLastError(); innfer_net_destroy(net); return rc; }
+    *out = net;
+    return INNFER_OK;
+}
+
 // gamma / beta (C host floats each) of LayerNorm `idx` of a SwinIR: 0 patch_embed.norm, 1 + 2 b / 2 + 2 b norm1 / norm2 of block b (blocks counted through the residual
 // groups), the last one norm.  Load time, synchronous.
 extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float* h_gamma, const float* h_beta) {
     if (!net || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "set_layer_norm: null argument");
-    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR, HAT, Swin2SR, DAT)");
+    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8 && net->kind != 9) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR, HAT, Swin2SR, DAT, DRCT)");
     if (idx < 0 || idx >= (int)net->sw_ln.size()) return set_error(INNFER_ERR_INVALID, "set_layer_norm: index %d of %zu", idx, net->sw_ln.size());
+    if (net->kind == 9) {        // DRCT: sw_ln_w[idx] floats each, already in the slab order of the tensor the norm reads (zeros at the hole and the pads)
+        const size_t wdt = (size_t)net->sw_ln_w[idx];
+        std::vector<float> h(2 * wdt);
+        std::copy(h_gamma, h_gamma + wdt, h.begin());
+        std::copy(h_beta, h_beta + wdt, h.begin() + wdt);
+        if (!net->sw_ln[idx]) INNFER_HIP(hipMalloc((void**)&net->sw_ln[idx], h.size() * sizeof(float)));
+        INNFER_HIP(hipMemcpy(net->sw_ln[idx], h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+        return INNFER_OK;
+    }
     std::vector<float> h(2 * (size_t)net->sw_cp, 0.f);
     for (int c = 0; c < net->sw_c; ++c) { h[c] = h_gamma[c]; h[net->sw_cp + c] = h_beta[c]; }
     if (!net->sw_ln[idx]) INNFER_HIP(hipMalloc((void**)&net->sw_ln[idx], h.size() * sizeof(float)));
@@ -487,12 +590,13 @@ extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float*
 // The relative position bias of block `blk` of a SwinIR as the dense table the attention reads: [num_heads][64 query][64 key] host floats.  Load time, synchronous.
 extern "C" int innfer_net_set_attn_bias(innfer_net_t net, int blk, const float* h_bias) {
     if (!net || !h_bias) return set_error(INNFER_ERR_INVALID, "set_attn_bias: null argument");
-    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_bias: the network has no window attention (built: SwinIR, HAT, Swin2SR, DAT)");
+    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8 && net->kind != 9) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_bias: the network has no window attention (built: SwinIR, HAT, Swin2SR, DAT, DRCT)");
     if (blk < 0 || blk >= (int)net->sw_relb.size()) return set_error(INNFER_ERR_INVALID, "set_attn_bias: block %d of %zu", blk, net->sw_relb.size());
     // (HAT: table `blk` in forward order -- [num_heads][256][256] of a HAB, [num_heads][256][576] of a residual group's OCAB)
     // (DAT: [num_heads][T][T], T = s0 s1, of an even block; the odd blocks take none)
     const size_t dat_t = (size_t)net->dat_s0 * net->dat_s1;
-    const size_t nb = (size_t)net->sw_nh * (net->kind == 6 ? 256 * (size_t)net->sw_relb_kw[blk] * net->sw_relb_kw[blk] : net->kind == 8 ? dat_t * dat_t : 4096) * sizeof(float);
+    // (DRCT: [nH_blk][256][256] with the block's own head count)
+    const size_t nb = net->kind == 9 ? (size_t)net->dr_nh[blk] * 65536 * sizeof(float) : (size_t)net->sw_nh * (net->kind == 6 ? 256 * (size_t)net->sw_relb_kw[blk] * net->sw_relb_kw[blk] : net->kind == 8 ? dat_t * dat_t : 4096) * sizeof(float);
     if (!net->sw_relb[blk]) INNFER_HIP(hipMalloc((void**)&net->sw_relb[blk], nb));
     INNFER_HIP(hipMemcpy(net->sw_relb[blk], h_bias, nb, hipMemcpyHostToDevice));
     return INNFER_OK;
@@ -922,6 +1026,7 @@ extern "C" int innfer_net_set_precision(innfer_net_t net, int fp32) {
     if (fp32 && net->kind == 6) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: HAT is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 7) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: Swin2SR is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 8) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: DAT is built for the fp16 mode only (no fp32-accurate engine)");
+    if (fp32 && net->kind == 9) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: DRCT is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32) {
         // The (wl | wh | wh) panels of every loaded conv are built HERE -- a load-time call, with its hipMalloc and synchronous copies -- never inside
         // innfer_net_forward (stream capture, concurrent callers).  Idempotent: a conv that already has its panels is skipped; innfer_net_set_conv
@@ -1008,6 +1113,13 @@ extern "C" double innfer_net_flops(innfer_net_t net, int N, int H, int W) {
         for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
         return f;
     }
+    if (net->kind == 9) {        // DRCT: as HAT's grid; per block the two products of every window and head on its real head width
+        const double px = (double)N * ((H + 15) / 16 * 16) * ((W + 15) / 16 * 16);
+        double f = 0.0;
+        for (size_t b = 0; b < net->dr_nh.size(); ++b) f += (px / 256) * 4.0 * 256 * 256 * (net->sw_c + 32.0 * (b % 5));
+        for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
+        return f;
+    }
     if (net->kind == 8) {        // DAT: every conv on the grid itself; per even block the two products of every window and head on the frame padded to s1, per odd block the Gram and the apply
         const double px = (double)N * H * W, s1 = net->dat_s1, T = (double)net->dat_s0 * s1;
         const double pxp = (double)N * std::ceil(H / s1) * s1 * std::ceil(W / s1) * s1;
@@ -1055,7 +1167,7 @@ struct Carve {
 struct SwinCarve { size_t xin, f0, r[2], t, u, qkv, att, hid, c4[2], b64, up[2], hr, outp, zc, z, y, pool, gram, amat, total; int Hp, Wp; };
 static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
     SwinCarve c{};
-    const int wsz = net->kind == 6 ? 16 : net->kind == 8 ? 1 : 8;          // (DAT works on H x W itself)
+    const int wsz = net->kind == 6 || net->kind == 9 ? 16 : net->kind == 8 ? 1 : 8;          // (DAT works on H x W itself)
     c.Hp = (H + wsz - 1) / wsz * wsz; c.Wp = (W + wsz - 1) / wsz * wsz;
     const size_t px = (size_t)N * c.Hp * c.Wp, s2 = (size_t)net->scale * net->scale;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -1063,12 +1175,22 @@ static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
     auto take = [&](size_t bytes) { const size_t o = off; off += al(bytes); return o; };
     c.xin = take(px * net->in_nc * 2);
     c.f0 = take(px * net->sw_cp * 2);
+    if (net->kind == 9) {        // DRCT: r[] are the two dense slabs (x | x1 .. x4 and one spare group, an even count), t and u the widest block's tokens; qkv / att / hid: the maximum over the blocks
+        const DrctDims dd = drct_dims(net);
+        c.r[0] = take(px * 32 * dd.dense_groups * 2); c.r[1] = take(px * 32 * dd.dense_groups * 2);
+        c.t = take(px * dd.lp[4] * 2);
+        c.u = take(px * dd.lp[4] * 2);
+        c.qkv = take(px * (size_t)dd.max_sq * 64 * 2);
+        c.att = take(px * (size_t)dd.max_hg * 32 * 2);
+        c.hid = take(px * (size_t)dd.max_hp * 2);
+    } else {
     c.r[0] = take(px * net->sw_cp * 2); c.r[1] = take(px * net->sw_cp * 2);
     c.t = take(px * net->sw_cp * 2);
     c.u = take(px * net->sw_cp * 2);
     c.qkv = take(px * ((3 * net->sw_nh + 1) / 2 * 64) * 2);
     c.att = take(px * 32 * net->sw_nh * 2);
     c.hid = take(px * net->sw_hp * 2);
+    }
     if (net->sw_conv3) { c.c4[0] = take(px * net->sw_c4p * 2); c.c4[1] = take(px * net->sw_c4p * 2); }
     if (net->sw_tail == 1) c.hr = take(px * net->convs.back().Kp * 2);
     else {
@@ -1098,7 +1220,7 @@ static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
 
 static Carve carve(const innfer_net* net, int N, int H, int W) {
     Carve c{};
-    if (net->kind == 5 || net->kind == 6 || net->kind == 7 || net->kind == 8) { c.total = swin_carve(net, N, H, W).total; return c; }
+    if (net->kind == 5 || net->kind == 6 || net->kind == 7 || net->kind == 8 || net->kind == 9) { c.total = swin_carve(net, N, H, W).total; return c; }
     const size_t px = (size_t)N * H * W;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     if (net->kind == 2) {        // SRVGGNetCompact: the two ping-pong feature slabs (one when there is no nf -> nf conv) and the last conv's 32- / 64-channel slab
@@ -1755,6 +1877,48 @@ static int swinir_forward(innfer_net* net, const void* d_in, int in_dtype, void*
             if (int rc = resi(t, r[cur ^ 1], r[cur])) return rc;
             cur ^= 1;
         }
+    } else if (net->kind == 9) {
+        // DRCT: r[cur] is the dense slab D = x | x1 | x2 | x3 | x4 of the current group (x in its own gx groups, x_k in group gx + k - 1).  Per block k = 0 .. 4:
+        // u = LN(D[: dim_k]) (the holed form); qkv into the head-padded slab (a head owns G = ceil(d / 32) groups); the 16 x 16 attention (win_attn16 for d <= 32, the wide
+        // kernel above; shift 8 for k = 1, 3); proj + shortcut from D -> t; u = LN(t); fc1 with GELU; fc2 + shortcut in place; then adjust: k < 4 ONE 64-output launch with
+        // LeakyReLU(0.2) that writes x_{k+1} into group gx + k of D and ZEROS into group gx + k + 1 (its rows 32 .. 63 are zero), k = 4 the S1 launches 0.2 * . + x into the
+        // other dense slab -- the next group's x.  No group is read by a matrix product before it is written: a product reads 32 ng_k channels, never the rounded-up width;
+        // the rounded-up groups a LayerNorm or a shortcut touches hold the zeros of the launch before (or the pad group of x), and the LayerNorm selects, never multiplies.
+        const DrctDims dd = drct_dims(net);
+        const int C = net->sw_c;
+        int ln = 1;
+        auto hnorm = [&](int idx, const f16* in, f16* out, int k) {
+            return plksr_pass(s, "layer_norm_holed", 8.0 * (C + 32 * k) * px, px * dd.lp[k] * 4.0, 8000, [&] {
+                return layer_norm_holed_launch(in, G, out, G, npx, C, dd.cpk[k], dd.lp[k], net->sw_ln[idx], net->sw_ln[idx] + dd.lp[k], 1e-5f, s); });
+        };
+        for (int i = 0; i < net->dr_r; ++i) {
+            f16 *D = r[cur], *Dn = r[cur ^ 1];
+            for (int k = 0; k < 5; ++k, ++blk) {
+                const int nhb = net->dr_nh[blk], d = (C + 32 * k) / nhb, hg = drct_head_groups(net, (size_t)blk), S = dd.lp[k] / 64, SH = (net->dr_hid[blk] + 63) / 64;
+                const int shift = (k & 1) ? 8 : 0;
+                if (int rc = hnorm(ln++, D, u, k)) return rc;
+                if (int rc = sliced((3 * hg + 1) / 2, u, qkv, 0, nullptr)) return rc;
+                // launch kind 8001: the window attention -- bytes: q, k, v in, o out (the head groups), the bias table
+                if (int rc = plksr_pass(s, d <= 32 ? "window_attention16" : "window_attention16_wide", 4.0 * 256 * (C + 32 * k) * px, px * hg * 256.0 + nhb * 262144.0, 8001, [&] {
+                        return d <= 32 ? win_attn16_launch(qkv, G, att, G, net->sw_relb[blk], N, Hp, Wp, nhb, d, shift, 16, s)
+                                       : win_attn16_wide_launch(qkv, G, att, G, net->sw_relb[blk], N, Hp, Wp, nhb, d, shift, s); })) return rc;
+                if (int rc = sliced(S, att, t, 0, D)) return rc;
+                if (int rc = hnorm(ln++, t, u, k)) return rc;
+                if (int rc = sliced(SH, u, hid, 12, nullptr)) return rc;
+                if (int rc = sliced(S, hid, t, 0, t)) return rc;
+                if (k < 4) {
+                    if (int rc = sliced(1, t, D + (long)dd.ng[k] * G, 1, nullptr)) return rc;
+                } else {
+                    for (int p = 0; p < cp / 64; ++p) {
+                        const ConvSlot& cs = net->convs[ci++];
+                        ConvLaunch L = mk_launch(cs, t, G, Dn + 2L * p * G, G, N, Hp, Wp, 0, 0);
+                        L.res1 = D + 2L * p * G; L.res1_gstride = G; L.s1 = 0.2f;          // 0.2 * x5 + x
+                        if (int rc = do_conv(L, s)) return rc;
+                    }
+                }
+            }
+            cur ^= 1;
+        }
     } else if (net->kind == 8) {
         // DAT on H x W itself (Hp = H, Wp = W: no pad, no crop).  Per block  u = LN(t); qkv; the attention into `att` -- even index in its group: rectangular windows (one
         // launch); odd: across channels (Gram, merge + softmax, apply) --; c = GELU(dwconv(v)) on the v groups of the qkv slab (BatchNorm folded); the pool over Y and the
@@ -1974,7 +2138,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     if (ws_bytes < cv.total) return set_error(INNFER_ERR_WORKSPACE, "forward: workspace %zu < %zu bytes", ws_bytes, cv.total);
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)d_ws;
-    if (net->kind == 5 || net->kind == 6 || net->kind == 7 || net->kind == 8) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);
+    if (net->kind == 5 || net->kind == 6 || net->kind == 7 || net->kind == 8 || net->kind == 9) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);
     if (net->kind == 2) return compact_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 3) return span_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 4) return plksr_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
@@ -2402,6 +2566,41 @@ extern "C" int innfer_window_attention16(const void* d_qkv, int64_t qkv_gs, void
     if (rc == INNFER_OK) rc = win_attn16_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, d_b, N, Hp, Wp, num_heads, head_dim, shift, key_window, (hipStream_t)stream);
     if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "window_attention16: the launch failed");
     (void)hipFree(d_b);
+    return rc;
+}
+
+// DRCT's 16 x 16 window attention for heads of 33 .. 128 channels alone, for tests: win_attn16_wide_launch, the code the network runs.  Every refusal comes before the upload:
+// a refused call touches no device memory.  Uploads, launches, waits.
+extern "C" int innfer_window_attention16_wide(const void* d_qkv, int64_t qkv_gs, void* d_out, int64_t out_gs, const float* h_bias, int N, int Hp, int Wp, int num_heads,
+                                              int head_dim, int shift, void* stream) {
+    if (!d_qkv || !d_out || !h_bias) return set_error(INNFER_ERR_INVALID, "window_attention16_wide: null argument");
+    if (num_heads < 1 || num_heads > 8) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention16_wide: %d heads (built: 1 .. 8)", num_heads);
+    if (head_dim <= 32) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention16_wide: heads of %d channels (built: 33 .. 128; innfer_window_attention16 takes <= 32)", head_dim);
+    if (head_dim > 128) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention16_wide: heads of %d channels (built: 33 .. 128)", head_dim);
+    if (N <= 0 || Hp <= 0 || Wp <= 0 || (Hp & 15) || (Wp & 15)) return set_error(INNFER_ERR_INVALID, "window_attention16_wide: %d images of %d x %d (whole 16 x 16 windows)", N, Hp, Wp);
+    if (shift != 0 && shift != 8) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention16_wide: shift %d (built: 0, 8)", shift);
+    float* d_b = nullptr;
+    const size_t nb = (size_t)num_heads * 65536 * sizeof(float);
+    if (hipMalloc((void**)&d_b, nb) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "window_attention16_wide: out of device memory");
+    int rc = hipMemcpy(d_b, h_bias, nb, hipMemcpyHostToDevice) == hipSuccess ? INNFER_OK : set_error(INNFER_ERR_HIP, "window_attention16_wide: copying the bias table failed");
+    if (rc == INNFER_OK) rc = win_attn16_wide_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, d_b, N, Hp, Wp, num_heads, head_dim, shift, (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "window_attention16_wide: the launch failed");
+    (void)hipFree(d_b);
+    return rc;
+}
+
+// The holed LayerNorm of DRCT's dense slab alone, for tests: layer_norm_holed_launch, the code the network runs.  h_gamma / h_beta: c_pad host floats in slab order.
+extern "C" int innfer_layer_norm_holed(const void* d_in, int64_t in_gs, void* d_out, int64_t out_gs, int64_t npix, int C, int c_end, int c_pad, const float* h_gamma,
+                                       const float* h_beta, float eps, void* stream) {
+    if (!d_in || !d_out || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "layer_norm_holed: null argument");
+    if (c_pad < 64 || c_pad > 512) return set_error(INNFER_ERR_UNSUPPORTED, "layer_norm_holed: a slab of %d channels (built: 64 .. 512)", c_pad);
+    float* d_p = nullptr;
+    if (hipMalloc((void**)&d_p, 2 * (size_t)c_pad * sizeof(float)) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "layer_norm_holed: out of device memory");
+    int rc = (hipMemcpy(d_p, h_gamma, c_pad * sizeof(float), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_p + c_pad, h_beta, c_pad * sizeof(float), hipMemcpyHostToDevice) == hipSuccess)
+                 ? INNFER_OK : set_error(INNFER_ERR_HIP, "layer_norm_holed: copying the parameters failed");
+    if (rc == INNFER_OK) rc = layer_norm_holed_launch((const f16*)d_in, (long)in_gs, (f16*)d_out, (long)out_gs, (long)npix, C, c_end, c_pad, d_p, d_p + c_pad, eps, (hipStream_t)stream);
+    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "layer_norm_holed: the launch failed");
+    (void)hipFree(d_p);
     return rc;
 }
 

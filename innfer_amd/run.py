@@ -30,6 +30,7 @@ _SNIFF = (
     ('feats.0.weight', 'realplksr'),                 # RealPLKSR (with feats.1.channel_mixer.0.weight)
     ('layers.0.residual_group.blocks.0.norm1.weight', 'swinir'),      # SwinIR and what builds on its skeleton (with conv_first.weight): ahead of the new-arch probe
     ('before_RG.1.weight', 'dat'),                   # DAT (with conv_first.weight and block 0's complete key set, _DAT_KEYS): ahead of the new-arch probe
+    ('layers.0.swin1.norm1.weight', 'drct'),         # DRCT (with conv_first.weight and dense group 0's complete key set, _DRCT_KEYS): ahead of the new-arch probe
     ('conv_first.weight', 'mesrgan'),
     ('model.0.weight', 'esrgan'),
     ('CFEM.0.weight', 'ppon'),
@@ -48,7 +49,7 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
     for probe, arch in _SNIFF:
         if probe in state_dict and (arch != 'realesrgan' or 'conv_first.weight' in state_dict) and (arch != 'span' or 'conv_cat.weight' in state_dict) and \
                 (arch != 'realplksr' or 'feats.1.channel_mixer.0.weight' in state_dict) and (arch != 'swinir' or 'conv_first.weight' in state_dict) and \
-                (arch != 'dat' or all(k in state_dict for k in _DAT_KEYS)):
+                (arch != 'dat' or all(k in state_dict for k in _DAT_KEYS)) and (arch != 'drct' or all(k in state_dict for k in _DRCT_KEYS)):
             break
     else:
         raise Exception("Could not infer model parameters.")
@@ -71,6 +72,8 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
         return s2 if s2 is not None else _infer_swinir(state_dict)
     if arch == 'dat':
         return _infer_dat(state_dict)
+    if arch == 'drct':
+        return _infer_drct(state_dict)
     if arch == 'pan':
         return _infer_pan(state_dict, scale, in_nc, out_nc)
     if arch == 'ppon':
@@ -398,7 +401,7 @@ def _infer_hat(state_dict):
     if any(k.endswith('attn.logit_scale') for k in state_dict):
         raise NotImplementedError('HAT-like checkpoint with attn.logit_scale (cosine attention): not built on the HIP path')
     if any('.swin_DRCT' in k or '.adjust' in k or '.swin1.' in k for k in state_dict):
-        raise NotImplementedError('DRCT checkpoint (dense-residual Swin blocks): not built on the HIP path')
+        raise NotImplementedError('HAT checkpoint with DRCT keys (.swin_DRCT / .adjust / .swin1.): neither a HAT nor a complete DRCT key set')
     if 'absolute_pos_embed' in state_dict:
         raise NotImplementedError('HAT checkpoint with absolute_pos_embed (ape=True): not built on the HIP path')
     if 'patch_embed.norm.weight' not in state_dict:
@@ -548,6 +551,86 @@ def _infer_dat(state_dict):
            'rpe_biases': rpe if rpe[0] is not None or rpe[1] is not None else None, 'split_assumed': split_assumed}
     return dict(arch='dat', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=sum(depths), plus=False, state_dict=state_dict,
                 net_params=get_network_G_config(cfg, up))
+
+
+# dense group 0's complete key set of a DRCT: with conv_first.weight, what recognises one (anything less is sniffed as before)
+_DRCT_KEYS = ('conv_first.weight', 'patch_embed.norm.weight', 'norm.weight', 'conv_after_body.weight') + tuple(
+    f'layers.0.swin{k}.{n}' for k in range(1, 6) for n in ('norm1.weight', 'norm1.bias', 'norm2.weight', 'norm2.bias', 'attn.relative_position_bias_table', 'attn.qkv.weight',
+                                                          'attn.qkv.bias', 'attn.proj.weight', 'attn.proj.bias', 'mlp.fc1.weight', 'mlp.fc1.bias', 'mlp.fc2.weight',
+                                                          'mlp.fc2.bias')) + tuple(f'layers.0.adjust{k}.{n}' for k in range(1, 6) for n in ('weight', 'bias'))
+
+
+def _infer_drct(state_dict):
+    """DRCT checkpoints (DRCT, DRCT-L, Real-DRCT-GAN and fine-tunes).  Everything is read off the shapes, which are authoritative over the published formulas: embed_dim and
+    in_chans from conv_first, the dense groups by counting layers.<i>.swin1, per block the heads from relative_position_bias_table.shape[1] and the MLP's hidden size from
+    mlp.fc1.weight.shape[0] (the published head rule is only cross-checked and recorded: heads_follow_rule in the dict handed back, and on the shell), gc from adjust1, the window from the table's rows, the scale
+    from upsample.*.  The buffers (attn.relative_position_index, attn_mask) are dropped from the state dict handed back and never trusted for values: the engine builds the
+    index from its formula -- a stored one that differs is refused -- and computes the mask from the coordinates.  What the HIP path does not build is refused here, before
+    anything touches the GPU."""
+    import math
+    from .architectures.keys import DRCT_GC, drct_head_rule
+    from .architectures.SwinIR_arch import relative_position_index
+    w0 = state_dict['conv_first.weight']
+    C, in_nc = int(w0.shape[0]), int(w0.shape[1])
+    if 'absolute_pos_embed' in state_dict:
+        raise NotImplementedError('DRCT checkpoint with absolute_pos_embed (ape=True): not built on the HIP path')
+    R = 0
+    while f'layers.{R}.swin1.norm1.weight' in state_dict:
+        R += 1
+    gc = int(state_dict['layers.0.adjust1.weight'].shape[0])
+    if gc != DRCT_GC:
+        raise NotImplementedError(f'DRCT checkpoint with gc {gc}: only gc 32 is built on the HIP path')
+    if not 1 <= C <= 256:
+        raise NotImplementedError(f'DRCT checkpoint with embed_dim {C}: up to 256 channels are built on the HIP path')
+    heads, hidden = [], []
+    for i in range(R):
+        for k in range(5):
+            b, dim = f'layers.{i}.swin{k + 1}.', C + gc * k
+            for n in ('attn.relative_position_bias_table', 'attn.qkv.weight', 'mlp.fc1.weight', 'norm1.weight'):
+                if b + n not in state_dict:
+                    raise Exception("Could not infer model parameters.")
+            table = state_dict[b + 'attn.relative_position_bias_table']
+            if int(table.shape[0]) != 961:
+                side = math.isqrt(int(table.shape[0]))
+                raise NotImplementedError(f'DRCT checkpoint with window_size {(side + 1) // 2} ({b}attn.relative_position_bias_table has {int(table.shape[0])} rows): '
+                                          'only 16 x 16 windows (961 rows) are built on the HIP path')
+            if int(state_dict[b + 'norm1.weight'].shape[0]) != dim or tuple(state_dict[b + 'attn.qkv.weight'].shape) != (3 * dim, dim):
+                raise NotImplementedError(f'DRCT checkpoint: {b[:-1]} does not work on C + {gc} k = {dim} channels (norm1 {tuple(state_dict[b + "norm1.weight"].shape)}, '
+                                          f'qkv {tuple(state_dict[b + "attn.qkv.weight"].shape)})')
+            nh, hid = int(table.shape[1]), int(state_dict[b + 'mlp.fc1.weight'].shape[0])
+            if nh < 1 or nh > 8 or dim % nh or dim // nh > 128:
+                raise NotImplementedError(f'DRCT checkpoint: {b[:-1]} has {nh} heads on {dim} channels (built on the HIP path: <= 8 heads of <= 128 channels, dim % heads == 0)')
+            if not 1 <= hid <= 1024:
+                raise NotImplementedError(f'DRCT checkpoint: {b[:-1]} has an MLP of {hid} hidden channels (built on the HIP path: <= 1024)')
+            heads.append(nh); hidden.append(hid)
+    if 'conv_before_upsample.0.weight' not in state_dict or 'conv_last.weight' not in state_dict or 'upsample.0.weight' not in state_dict:
+        raise NotImplementedError('DRCT checkpoint without the pixelshuffle tail (conv_before_upsample / upsample / conv_last): not built on the HIP path')
+    up = 1
+    for k, v in state_dict.items():
+        if k.startswith('upsample.') and k.endswith('.weight'):
+            f = math.isqrt(int(v.shape[0]) // 64)
+            if f * f * 64 != int(v.shape[0]) or int(v.shape[1]) != 64:
+                raise Exception("Could not infer model parameters.")
+            up *= f
+    if up not in (2, 3, 4):
+        raise NotImplementedError(f'DRCT checkpoint with a pixelshuffle tail of scale {up}: 2, 3 and 4 are built on the HIP path')
+    out_nc = int(state_dict['conv_last.weight'].shape[0])
+    if out_nc != in_nc or not 1 <= in_nc <= 4:
+        raise NotImplementedError(f'DRCT checkpoint: conv_last has {out_nc} channels, conv_first takes {in_nc} (built on the HIP path: equal counts, 1 .. 4)')
+    want = relative_position_index(16)
+    for k in [k for k in state_dict if k.endswith('attn.relative_position_index')]:
+        v = state_dict[k]
+        if tuple(v.shape) != tuple(want.shape) or not bool((v.cpu().long() == want).all()):
+            raise NotImplementedError(f'DRCT checkpoint: {k} differs from (ri - rj + 15) * 31 + (ci - cj + 15), the index the engine builds its bias table with')
+    state_dict = {k: v for k, v in state_dict.items() if not (k.endswith('attn.relative_position_index') or k.endswith('.attn_mask'))}
+    # the head count the published rule starts from: block 0 works on C channels and the rule gives num_heads - C % num_heads there (num_heads itself when it divides C)
+    nh0 = heads[0]
+    rule = [drct_head_rule(C + gc * k, nh0) for _ in range(R) for k in range(5)]
+    cfg = {'type': 'drct', 'in_nc': in_nc, 'nf': C, 'depths': [6] * R, 'num_heads': [nh0] * R, 'window_size': 16, 'mlp_ratio': hidden[0] / C, 'scale': up,
+           'upsampler': 'pixelshuffle', 'resi_connection': '1conv', 'gc': gc, 'block_heads': heads, 'block_hidden': hidden}
+    info = dict(arch='drct', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=5 * R, plus=False, state_dict=state_dict, net_params=get_network_G_config(cfg, up))
+    info['heads_follow_rule'] = heads == rule
+    return info
 
 
 def _infer_pan(state_dict, scale, in_nc, out_nc):

@@ -92,4 +92,4 @@ def fill_running_stats(sd, seed=0):
     return out
 
 
-from .architectures.keys import compact_shapes, dat_shapes, hat_shapes, mrrdbnet_shapes, realesrgan_shapes, realplksr_shapes, rrdbnet_shapes, span_shapes, srresnet_shapes, swin2sr_shapes, swinir_shapes  # noqa: E402,F401
+from .architectures.keys import compact_shapes, dat_shapes, drct_shapes, hat_shapes, mrrdbnet_shapes, realesrgan_shapes, realplksr_shapes, rrdbnet_shapes, span_shapes, srresnet_shapes, swin2sr_shapes, swinir_shapes  # noqa: E402,F401

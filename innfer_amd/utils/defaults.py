@@ -206,6 +206,22 @@ def get_network_G_config(network_G, scale):
         cfg['rpe_biases'] = _pick(opts, 'rpe_biases', None)          # the checkpoint's rpe_biases per branch, when it carries them
         cfg['split_assumed'] = _pick(opts, 'split_assumed', False)   # True: the checkpoint had no rpe_biases and [8, 32] was assumed
         opts.pop('out_nc', None)
+    elif kind in ('drct', 'drct_net'):                     # DRCT (dense-residual Swin groups on SwinIR's skeleton): the published constructor surface
+        cfg['type'] = 'drct'
+        cfg['in_chans'] = _pick(opts, 'in_nc', 3)
+        cfg['embed_dim'] = _pick(opts, 'nf', 180)
+        cfg['depths'] = list(_pick(opts, 'depths', [6] * 6))
+        cfg['num_heads'] = list(_pick(opts, 'num_heads', [6] * len(cfg['depths'])))
+        cfg['window_size'] = _pick(opts, 'window_size', 16)
+        cfg['mlp_ratio'] = _pick(opts, 'mlp_ratio', 2.0)
+        cfg['upscale'] = _pick(opts, 'scale', scale)
+        cfg['img_range'] = _pick(opts, 'img_range', 1.0)
+        cfg['upsampler'] = _pick(opts, 'upsampler', 'pixelshuffle')
+        cfg['resi_connection'] = _pick(opts, 'resi_connection', '1conv')
+        cfg['gc'] = _pick(opts, 'gc', 32)
+        cfg['block_heads'] = _pick(opts, 'block_heads', None)        # per block, read off the checkpoint's bias tables (None: the published rule)
+        cfg['block_hidden'] = _pick(opts, 'block_hidden', None)      # per block, read off mlp.fc1 (None: int(dim mlp_ratio))
+        opts.pop('out_nc', None)
     else:
         raise NotImplementedError(f'Generator model [{kind:s}] not recognized')
 
