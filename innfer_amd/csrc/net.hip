@@ -9,6 +9,7 @@
 //   PixelShuffle(2)      -> folded into the conv's store
 #include "common.h"
 #include "norm_stats.h"
+#include "test_entry.h"
 
 #include <cmath>
 #include <cstring>
@@ -2543,14 +2544,10 @@ extern "C" int innfer_window_attention(const void* d_qkv, int64_t qkv_gs, void* 
                                        int shift, void* stream) {
     if (!d_qkv || !d_out || !h_bias) return set_error(INNFER_ERR_INVALID, "window_attention: null argument");
     if (num_heads < 1 || num_heads > 8) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention: %d heads (built: 1 .. 8)", num_heads);
-    float* d_b = nullptr;
-    const size_t nb = (size_t)num_heads * 4096 * sizeof(float);
-    if (hipMalloc((void**)&d_b, nb) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "window_attention: out of device memory");
-    int rc = hipMemcpy(d_b, h_bias, nb, hipMemcpyHostToDevice) == hipSuccess ? INNFER_OK : set_error(INNFER_ERR_HIP, "window_attention: copying the bias table failed");
-    if (rc == INNFER_OK) rc = win_attn_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, d_b, N, Hp, Wp, num_heads, head_dim, shift, (hipStream_t)stream);
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "window_attention: the launch failed");
-    (void)hipFree(d_b);
-    return rc;
+    Upload b("window_attention", {{h_bias, (size_t)num_heads * 4096}}, "bias table");
+    int rc = b.rc;
+    if (rc == INNFER_OK) rc = win_attn_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, b.d, N, Hp, Wp, num_heads, head_dim, shift, (hipStream_t)stream);
+    return finish("window_attention", rc, stream);
 }
 
 // HAT's 16 x 16 window attention alone (key window 16: self, shift 0 | 8; 24: overlapping), for tests: win_attn16_launch, the code the network runs.  Uploads, launches, waits.
@@ -2559,14 +2556,10 @@ extern "C" int innfer_window_attention16(const void* d_qkv, int64_t qkv_gs, void
     if (!d_qkv || !d_out || !h_bias) return set_error(INNFER_ERR_INVALID, "window_attention16: null argument");
     if (num_heads < 1 || num_heads > 8) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention16: %d heads (built: 1 .. 8)", num_heads);
     if (key_window != 16 && key_window != 24) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention16: a key window of %d (built: 16, 24)", key_window);
-    float* d_b = nullptr;
-    const size_t nb = (size_t)num_heads * 256 * key_window * key_window * sizeof(float);
-    if (hipMalloc((void**)&d_b, nb) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "window_attention16: out of device memory");
-    int rc = hipMemcpy(d_b, h_bias, nb, hipMemcpyHostToDevice) == hipSuccess ? INNFER_OK : set_error(INNFER_ERR_HIP, "window_attention16: copying the bias table failed");
-    if (rc == INNFER_OK) rc = win_attn16_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, d_b, N, Hp, Wp, num_heads, head_dim, shift, key_window, (hipStream_t)stream);
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "window_attention16: the launch failed");
-    (void)hipFree(d_b);
-    return rc;
+    Upload b("window_attention16", {{h_bias, (size_t)num_heads * 256 * key_window * key_window}}, "bias table");
+    int rc = b.rc;
+    if (rc == INNFER_OK) rc = win_attn16_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, b.d, N, Hp, Wp, num_heads, head_dim, shift, key_window, (hipStream_t)stream);
+    return finish("window_attention16", rc, stream);
 }
 
 // DRCT's 16 x 16 window attention for heads of 33 .. 128 channels alone, for tests: win_attn16_wide_launch, the code the network runs.  Every refusal comes before the upload:
@@ -2579,14 +2572,10 @@ extern "C" int innfer_window_attention16_wide(const void* d_qkv, int64_t qkv_gs,
     if (head_dim > 128) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention16_wide: heads of %d channels (built: 33 .. 128)", head_dim);
     if (N <= 0 || Hp <= 0 || Wp <= 0 || (Hp & 15) || (Wp & 15)) return set_error(INNFER_ERR_INVALID, "window_attention16_wide: %d images of %d x %d (whole 16 x 16 windows)", N, Hp, Wp);
     if (shift != 0 && shift != 8) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention16_wide: shift %d (built: 0, 8)", shift);
-    float* d_b = nullptr;
-    const size_t nb = (size_t)num_heads * 65536 * sizeof(float);
-    if (hipMalloc((void**)&d_b, nb) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "window_attention16_wide: out of device memory");
-    int rc = hipMemcpy(d_b, h_bias, nb, hipMemcpyHostToDevice) == hipSuccess ? INNFER_OK : set_error(INNFER_ERR_HIP, "window_attention16_wide: copying the bias table failed");
-    if (rc == INNFER_OK) rc = win_attn16_wide_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, d_b, N, Hp, Wp, num_heads, head_dim, shift, (hipStream_t)stream);
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "window_attention16_wide: the launch failed");
-    (void)hipFree(d_b);
-    return rc;
+    Upload b("window_attention16_wide", {{h_bias, (size_t)num_heads * 65536}}, "bias table");
+    int rc = b.rc;
+    if (rc == INNFER_OK) rc = win_attn16_wide_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, b.d, N, Hp, Wp, num_heads, head_dim, shift, (hipStream_t)stream);
+    return finish("window_attention16_wide", rc, stream);
 }
 
 // The holed LayerNorm of DRCT's dense slab alone, for tests: layer_norm_holed_launch, the code the network runs.  h_gamma / h_beta: c_pad host floats in slab order.
@@ -2594,14 +2583,10 @@ extern "C" int innfer_layer_norm_holed(const void* d_in, int64_t in_gs, void* d_
                                        const float* h_beta, float eps, void* stream) {
     if (!d_in || !d_out || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "layer_norm_holed: null argument");
     if (c_pad < 64 || c_pad > 512) return set_error(INNFER_ERR_UNSUPPORTED, "layer_norm_holed: a slab of %d channels (built: 64 .. 512)", c_pad);
-    float* d_p = nullptr;
-    if (hipMalloc((void**)&d_p, 2 * (size_t)c_pad * sizeof(float)) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "layer_norm_holed: out of device memory");
-    int rc = (hipMemcpy(d_p, h_gamma, c_pad * sizeof(float), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_p + c_pad, h_beta, c_pad * sizeof(float), hipMemcpyHostToDevice) == hipSuccess)
-                 ? INNFER_OK : set_error(INNFER_ERR_HIP, "layer_norm_holed: copying the parameters failed");
-    if (rc == INNFER_OK) rc = layer_norm_holed_launch((const f16*)d_in, (long)in_gs, (f16*)d_out, (long)out_gs, (long)npix, C, c_end, c_pad, d_p, d_p + c_pad, eps, (hipStream_t)stream);
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "layer_norm_holed: the launch failed");
-    (void)hipFree(d_p);
-    return rc;
+    Upload p("layer_norm_holed", {{h_gamma, (size_t)c_pad}, {h_beta, (size_t)c_pad}});
+    int rc = p.rc;
+    if (rc == INNFER_OK) rc = layer_norm_holed_launch((const f16*)d_in, (long)in_gs, (f16*)d_out, (long)out_gs, (long)npix, C, c_end, c_pad, p.d, p.d + c_pad, eps, (hipStream_t)stream);
+    return finish("layer_norm_holed", rc, stream);
 }
 
 // HAT's channel attention alone, for tests (chan_attn.hip, the code the network runs): the channel sums + the squeeze / excite vector, and the scale-add pass.
@@ -2612,19 +2597,13 @@ extern "C" int innfer_chan_attn_excite(const void* d_z, int64_t z_gs, int N, int
     if (N <= 0 || HW <= 0 || C < 1 || C > 256 || c_pad < C || c_pad > 256 || c_pad % 64 || hidden < 1 || hidden > 64)
         return set_error(INNFER_ERR_UNSUPPORTED, "chan_attn_excite: N=%d HW=%ld C=%d c_pad=%d hidden=%d (built: C <= c_pad in 64, 128, 192, 256; hidden <= 64)", N, (long)HW, C, c_pad, hidden);
     if (work_bytes < innfer_chan_attn_work_bytes(N, HW, c_pad)) return set_error(INNFER_ERR_WORKSPACE, "chan_attn_excite: work buffer %zu < %zu bytes", work_bytes, innfer_chan_attn_work_bytes(N, HW, c_pad));
-    std::vector<float> h;
-    h.insert(h.end(), h_w1, h_w1 + (size_t)hidden * C); h.insert(h.end(), h_b1, h_b1 + hidden);
-    h.insert(h.end(), h_w2, h_w2 + (size_t)C * hidden); h.insert(h.end(), h_b2, h_b2 + C);
-    float* d_p = nullptr;
-    if (hipMalloc((void**)&d_p, h.size() * sizeof(float)) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "chan_attn_excite: out of device memory");
-    int rc = hipMemcpy(d_p, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess ? INNFER_OK : set_error(INNFER_ERR_HIP, "chan_attn_excite: copying the weights failed");
+    Upload p("chan_attn_excite", {{h_w1, (size_t)hidden * C}, {h_b1, (size_t)hidden}, {h_w2, (size_t)C * hidden}, {h_b2, (size_t)C}}, "weights");
+    int rc = p.rc;
     hipStream_t s = (hipStream_t)stream;
     if (rc == INNFER_OK) rc = ca_pool_launch((const f16*)d_z, (long)z_gs, N, (long)HW, c_pad, (float*)d_work, s);
-    if (rc == INNFER_OK) rc = ca_excite_launch((const float*)d_work, N, (long)HW, C, c_pad, hidden, d_p, d_p + (size_t)hidden * C, d_p + (size_t)hidden * C + hidden,
-                                               d_p + 2 * (size_t)hidden * C + hidden, (float*)d_y, (float*)d_sums, s);
-    if (hipStreamSynchronize(s) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "chan_attn_excite: the launch failed");
-    (void)hipFree(d_p);
-    return rc;
+    if (rc == INNFER_OK) rc = ca_excite_launch((const float*)d_work, N, (long)HW, C, c_pad, hidden, p.d, p.d + (size_t)hidden * C, p.d + (size_t)hidden * C + hidden,
+                                               p.d + 2 * (size_t)hidden * C + hidden, (float*)d_y, (float*)d_sums, s);
+    return finish("chan_attn_excite", rc, stream);
 }
 extern "C" int innfer_chan_attn_scale_add(void* d_t, int64_t t_gs, const void* d_z, int64_t z_gs, const void* d_y, float conv_scale, int N, int64_t HW, int c_pad, void* stream) {
     if (!d_t || !d_z || !d_y) return set_error(INNFER_ERR_INVALID, "chan_attn_scale_add: null argument");
@@ -2638,14 +2617,10 @@ extern "C" int innfer_layer_norm(const void* d_in, int64_t in_gs, void* d_out, i
                                  float eps, void* stream) {
     if (!d_in || !d_out || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "layer_norm: null argument");
     if (C < 1 || C > 256) return set_error(INNFER_ERR_UNSUPPORTED, "layer_norm: C=%d (built: 1 .. 256)", C);
-    float* d_p = nullptr;
-    if (hipMalloc((void**)&d_p, 2 * (size_t)C * sizeof(float)) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "layer_norm: out of device memory");
-    int rc = (hipMemcpy(d_p, h_gamma, C * sizeof(float), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_p + C, h_beta, C * sizeof(float), hipMemcpyHostToDevice) == hipSuccess)
-                 ? INNFER_OK : set_error(INNFER_ERR_HIP, "layer_norm: copying the parameters failed");
-    if (rc == INNFER_OK) rc = layer_norm_launch((const f16*)d_in, (long)in_gs, (f16*)d_out, (long)out_gs, (long)npix, C, c_pad, d_p, d_p + C, eps, (hipStream_t)stream);
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "layer_norm: the launch failed");
-    (void)hipFree(d_p);
-    return rc;
+    Upload p("layer_norm", {{h_gamma, (size_t)C}, {h_beta, (size_t)C}});
+    int rc = p.rc;
+    if (rc == INNFER_OK) rc = layer_norm_launch((const f16*)d_in, (long)in_gs, (f16*)d_out, (long)out_gs, (long)npix, C, c_pad, p.d, p.d + C, eps, (hipStream_t)stream);
+    return finish("layer_norm", rc, stream);
 }
 
 // Swin2SR's cosine window attention alone, for tests: win_attn_cos_launch, the code the network runs.  Uploads the bias table and the per-head scales, launches, waits.
@@ -2653,16 +2628,11 @@ extern "C" int innfer_window_attention_cos(const void* d_qkv, int64_t qkv_gs, vo
                                            int num_heads, int head_dim, int shift, void* stream) {
     if (!d_qkv || !d_out || !h_bias || !h_tau) return set_error(INNFER_ERR_INVALID, "window_attention_cos: null argument");
     if (num_heads < 1 || num_heads > 8) return set_error(INNFER_ERR_UNSUPPORTED, "window_attention_cos: %d heads (built: 1 .. 8)", num_heads);
-    float* d_b = nullptr;
-    const size_t nb = (size_t)num_heads * 4096 * sizeof(float), nt = (size_t)num_heads * sizeof(float);
-    if (hipMalloc((void**)&d_b, nb + nt) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "window_attention_cos: out of device memory");
-    float* d_t = d_b + (size_t)num_heads * 4096;
-    int rc = (hipMemcpy(d_b, h_bias, nb, hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_t, h_tau, nt, hipMemcpyHostToDevice) == hipSuccess)
-                 ? INNFER_OK : set_error(INNFER_ERR_HIP, "window_attention_cos: copying the bias table and the scales failed");
-    if (rc == INNFER_OK) rc = win_attn_cos_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, d_b, d_t, N, Hp, Wp, num_heads, head_dim, shift, (hipStream_t)stream);
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "window_attention_cos: the launch failed");
-    (void)hipFree(d_b);
-    return rc;
+    Upload b("window_attention_cos", {{h_bias, (size_t)num_heads * 4096}, {h_tau, (size_t)num_heads}}, "bias table and the scales");
+    int rc = b.rc;
+    if (rc == INNFER_OK) rc = win_attn_cos_launch((const f16*)d_qkv, (long)qkv_gs, (f16*)d_out, (long)out_gs, b.d, b.d + (size_t)num_heads * 4096, N, Hp, Wp, num_heads, head_dim, shift,
+                                                  (hipStream_t)stream);
+    return finish("window_attention_cos", rc, stream);
 }
 
 // Swin2SR's LayerNorm + residual alone, for tests: layer_norm_add_launch, the code the network runs.  Uploads gamma / beta, launches, waits.
@@ -2670,15 +2640,11 @@ extern "C" int innfer_layer_norm_add(const void* d_in, int64_t in_gs, const void
                                      const float* h_gamma, const float* h_beta, float eps, void* stream) {
     if (!d_in || !d_res || !d_out || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "layer_norm_add: null argument");
     if (C < 1 || C > 256) return set_error(INNFER_ERR_UNSUPPORTED, "layer_norm_add: C=%d (built: 1 .. 256)", C);
-    float* d_p = nullptr;
-    if (hipMalloc((void**)&d_p, 2 * (size_t)C * sizeof(float)) != hipSuccess) return set_error(INNFER_ERR_NOMEM, "layer_norm_add: out of device memory");
-    int rc = (hipMemcpy(d_p, h_gamma, C * sizeof(float), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d_p + C, h_beta, C * sizeof(float), hipMemcpyHostToDevice) == hipSuccess)
-                 ? INNFER_OK : set_error(INNFER_ERR_HIP, "layer_norm_add: copying the parameters failed");
-    if (rc == INNFER_OK) rc = layer_norm_add_launch((const f16*)d_in, (long)in_gs, (const f16*)d_res, (long)res_gs, (f16*)d_out, (long)out_gs, (long)npix, C, c_pad, d_p, d_p + C, eps,
+    Upload p("layer_norm_add", {{h_gamma, (size_t)C}, {h_beta, (size_t)C}});
+    int rc = p.rc;
+    if (rc == INNFER_OK) rc = layer_norm_add_launch((const f16*)d_in, (long)in_gs, (const f16*)d_res, (long)res_gs, (f16*)d_out, (long)out_gs, (long)npix, C, c_pad, p.d, p.d + C, eps,
                                                     (hipStream_t)stream);
-    if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess && rc == INNFER_OK) rc = set_error(INNFER_ERR_HIP, "layer_norm_add: the launch failed");
-    (void)hipFree(d_p);
-    return rc;
+    return finish("layer_norm_add", rc, stream);
 }
 
 // RealPLKSR's partial large-kernel conv alone, for tests: plk_pack + plk_conv_launch, the code the network runs.  Uploads, launches, waits.

@@ -1,26 +1,14 @@
 // Attention of 16 x 16 query windows over the head-padded qkv slab (HAT: the window self-attention of a HAB, and the overlapping cross-attention of an OCAB), templated on
-// the side KW of the KEY window: ONE launch for all windows and heads of a batch.  The slab forms are win_attn.hip's:
-//   qkv slab   3 nH channel groups of 32: group h = q of head h (d real channels, then zeros; the d^-0.5 already inside the weights), nH + h = k, 2 nH + h = v
-//   out slab   nH groups: head h's result at the query pixels, channels d .. 31 written as zeros
+// the side KW of the KEY window: ONE launch for all windows and heads of a batch.  The arithmetic is win_attn_core.h's; this file's own:
 //   KW 16      keys = the window's own 256 tokens.  Token i of window (wy, wx) is pixel (16 wy + i / 16, 16 wx + i % 16) of the SHIFTED frame, pixel ((r + shift) mod Hp,
-//              (c + shift) mod Wp) of the stored one (shift 0 | 8): the roll is the address of the gather, the roll back the address of the store.  With a shift, the windows
-//              of the last window row / column get -100 (not -inf) between tokens of different regions: label 3 a(r) + b(c) of the shifted-frame pixel, a = 0 below Hp - 16,
-//              1 below Hp - 8, else 2.  Computed from the coordinates.
+//              (c + shift) mod Wp) of the stored one (shift 0 | 8): the roll is the address of the gather, the roll back the address of the store.  Masked with a shift.
 //   KW 24      keys = the 24 x 24 pixels from (16 wy - 4, 16 wx - 4) of the stored frame (nn.Unfold(24, stride 16, padding 4) behind the Linear): a position outside the grid
 //              is a key with k = v = 0 -- its score is the bias alone and it TAKES PART in the softmax.  No shift, no mask.
-// A workgroup owns one (image, head, window); wave w its queries 64 w .. 64 w + 63, a query on a lane as in win_attn.hip.  256 x KW^2 fp32 scores do not fit registers, so a
-// wave walks the keys in blocks of 64 (4 blocks for KW 16, 9 for KW 24) with a running maximum and a running sum:
-//   S^T = K Q^T + B^T   per block sixteen v_mfma_f32_16x16x32_f16: A = 16 keys x 32 channels and B = 32 channels x 16 queries are 16-byte loads straight from the slab (lane
-//                       (li, lg): token 16 t + li, channels 8 lg .. 8 lg + 7; zeros for a key outside the grid); the C operand is the relative position bias, a dense
-//                       [nH][256 query][KW^2 key] fp32 table (four consecutive keys of a query per lane: one 16-byte load).
-//   softmax             m' = max(m, block maximum); the sum and the accumulator are multiplied by exp(m - m') -- a per-LANE factor, since the transposed second product
-//                       leaves a query on a lane; P = exp(s - m') in fp32, summed unrounded; P rounded to fp16 is the B operand of the second product.
-//   O^T += V^T P^T      per block sixteen MFMAs.  V^T of the whole key window is staged ONCE per workgroup in LDS ([32 channels][KW^2 slots + 8]: 16.5 KB / 36.5 KB), every
-//                       64-key block in win_attn.hip's slot order, so an A fragment is one ds_read_b128; the four waves share it.  K is not staged: its fragments are read
-//                       once per wave from the slab (L2 serves the three re-reads).  A lane ends with four consecutive channels of its query: o / sum in fp32, one rounding,
-//                       one 8-byte store; channels >= d are written as zeros.
-// A window of image n reads only image n.
-#include "common.h"
+//   geometry   a workgroup owns one (image, head, window); wave w its queries 64 w .. 64 w + 63.  256 x KW^2 fp32 scores do not fit registers, so a wave walks the keys in
+//              blocks of 64 (4 for KW 16, 9 for KW 24) with the running softmax.  The bias is a dense [nH][256 query][KW^2 key] fp32 table.
+//   V^T        of the whole key window, staged ONCE per workgroup in LDS ([32 channels][KW^2 slots + 8]: 16.5 KB / 36.5 KB); the four waves share it.  K is not staged: its
+//              fragments are read once per wave from the slab (L2 serves the three re-reads).
+#include "win_attn_core.h"
 
 namespace innfer {
 
@@ -32,8 +20,6 @@ struct WinAttn16 {
     const float* relb;
     int N, Hp, Wp, nH, d, shift;
 };
-
-__device__ __forceinline__ int wa16_band(int r, int n) { return r < n - 16 ? 0 : (r < n - 8 ? 1 : 2); }
 
 template <int KW>
 __global__ __launch_bounds__(256) void win_attn16_kernel(const WinAttn16 p) {
@@ -72,12 +58,9 @@ __global__ __launch_bounds__(256) void win_attn16_kernel(const WinAttn16 p) {
     const f16* kb = qb + (long)p.nH * p.gs;
     const f16* vb = p.qkv + (long)(2 * p.nH + h) * p.gs;
     for (int pc = tid; pc < NK * 4; pc += 256) {         // V^T into LDS: piece (key, channel octet) -> eight rows, the key's slot inside its 64-key block
-        const int tok = pc >> 2, oct = pc & 3, t = tok & 63;
+        const int tok = pc >> 2, oct = pc & 3;
         const long o = kpix(tok);
-        const f16x8 v = o >= 0 ? *(const f16x8*)(vb + o + 8 * oct) : zero8;
-        const int slot = (tok & ~63) + (t & 32) + 8 * ((t >> 2) & 3) + 4 * ((t >> 4) & 1) + (t & 3);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) vt[(8 * oct + e) * VROW + slot] = v[e];
+        wa::scatter_vt<VROW>(vt, tok, oct, o >= 0 ? *(const f16x8*)(vb + o + 8 * oct) : zero8);
     }
     long px[4];
     f16x8 qf[4];
@@ -91,10 +74,7 @@ __global__ __launch_bounds__(256) void win_attn16_kernel(const WinAttn16 p) {
     const bool masked = KW == 16 && p.shift && (wy == (p.Hp >> 4) - 1 || wx == nwx - 1);      // (workgroup-uniform) the windows that wrap
     int lq[4];
 #pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int tq = 64 * wave + 16 * t + li;
-        lq[t] = 3 * wa16_band(wy * 16 + (tq >> 4), p.Hp) + wa16_band(wx * 16 + (tq & 15), p.Wp);
-    }
+    for (int t = 0; t < 4; ++t) lq[t] = wa::label_sq<16>(wy, wx, 64 * wave + 16 * t + li, p.Hp, p.Wp);
     const float* rb = p.relb + (long)h * 256 * NK + (long)(64 * wave + li) * NK + 4 * lg;
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     float m[4], l[4];
@@ -118,84 +98,24 @@ __global__ __launch_bounds__(256) void win_attn16_kernel(const WinAttn16 p) {
                 const f32x4 bias = *(const f32x4*)(rb + 16 * tq * NK + 64 * b + 16 * tk);
                 s[tk][tq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[tk], qf[tq], bias, 0, 0, 0);
             }
-        if (masked) {
-#pragma unroll
-            for (int tk = 0; tk < 4; ++tk)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int key = 64 * b + 16 * tk + 4 * lg + j;
-                    const int lk = 3 * wa16_band(wy * 16 + (key >> 4), p.Hp) + wa16_band(wx * 16 + (key & 15), p.Wp);
-#pragma unroll
-                    for (int tq = 0; tq < 4; ++tq)
-                        if (lq[tq] != lk) s[tk][tq][j] += -100.0f;
-                }
-        }
+        if (masked) wa::mask_block(s, lq, 64 * b + 4 * lg, [&](int key) { return wa::label_sq<16>(wy, wx, key, p.Hp, p.Wp); });
         f16x8 pf[4][2];                                  // pf[tq][ks]: the B fragment of key step ks of this block
-#pragma unroll
-        for (int tq = 0; tq < 4; ++tq) {
-            float mb = s[0][tq][0];
-#pragma unroll
-            for (int tk = 0; tk < 4; ++tk)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mb = fmaxf(mb, s[tk][tq][j]);
-            mb = fmaxf(mb, __shfl_xor(mb, 16));
-            mb = fmaxf(mb, __shfl_xor(mb, 32));
-            const float mn = fmaxf(m[tq], mb);
-            const float alpha = __expf(m[tq] - mn);      // (first block: exp(-3e38 - mn) = 0 on a zero sum and a zero accumulator)
-            float sum = 0.f;
-#pragma unroll
-            for (int tk = 0; tk < 4; ++tk)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float e = __expf(s[tk][tq][j] - mn);
-                    sum += e;
-                    pf[tq][tk >> 1][4 * (tk & 1) + j] = (f16)e;
-                }
-            sum += __shfl_xor(sum, 16);
-            sum += __shfl_xor(sum, 32);
-            l[tq] = l[tq] * alpha + sum;
-            m[tq] = mn;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { o[0][tq][j] *= alpha; o[1][tq][j] *= alpha; }
-        }
-#pragma unroll
-        for (int td = 0; td < 2; ++td) {
-            const f16* vr = vt + (16 * td + li) * VROW + 64 * b + 8 * lg;
-            const f16x8 a0 = *(const f16x8*)vr, a1 = *(const f16x8*)(vr + 32);
-#pragma unroll
-            for (int tq = 0; tq < 4; ++tq) {
-                o[td][tq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, pf[tq][0], o[td][tq], 0, 0, 0);
-                o[td][tq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, pf[tq][1], o[td][tq], 0, 0, 0);
-            }
-        }
+        wa::softmax_block(s, m, l, o, pf);
+        wa::pv_block<4, 2, VROW>(vt + 64 * b, li, lg, pf, o);
     }
-    f16* ob = p.out + (long)h * p.out_gs + 4 * lg;
-#pragma unroll
-    for (int tq = 0; tq < 4; ++tq) {
-        const float inv = 1.0f / l[tq];
-#pragma unroll
-        for (int td = 0; td < 2; ++td) {
-            f16x4 r;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) r[j] = 16 * td + 4 * lg + j < p.d ? (f16)(o[td][tq][j] * inv) : (f16)0.f;
-            *(f16x4*)(ob + px[tq] + 16 * td) = r;
-        }
-    }
+    wa::store_out(p.out + (long)h * p.out_gs, p.out_gs, px, o, l, p.d, lg, [](int) { return false; });
 }
 
 }  // namespace
 
 // kw 16: the window self-attention (shift 0 | 8); kw 24: the overlapping cross-attention (shift 0).  relb: dense fp32 [nH][256 query][kw^2 key]
 int win_attn16_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, int N, int Hp, int Wp, int nH, int d, int shift, int kw, hipStream_t s) {
-    if (!qkv || !out || !relb || N <= 0 || Hp <= 0 || Wp <= 0) return set_error(INNFER_ERR_INVALID, "window attention 16: null argument or N=%d Hp=%d Wp=%d", N, Hp, Wp);
-    if ((Hp & 15) || (Wp & 15)) return set_error(INNFER_ERR_INVALID, "window attention 16: %d x %d is not a whole number of 16 x 16 windows (the caller pads)", Hp, Wp);
+    if (int rc = wa::refuse_frame("window attention 16", qkv, out, relb, N, Hp, Wp, 16)) return rc;
     if (kw != 16 && kw != 24) return set_error(INNFER_ERR_UNSUPPORTED, "window attention 16: a key window of %d (built: 16, the window itself; 24, the overlapping one)", kw);
     if (nH < 1 || nH > 8 || d < 1 || d > 32) return set_error(INNFER_ERR_UNSUPPORTED, "window attention 16: %d heads of %d channels (built: <= 8 heads, <= 32 channels)", nH, d);
     if (shift != 0 && (shift != 8 || kw != 16)) return set_error(INNFER_ERR_UNSUPPORTED, "window attention 16: shift %d with a key window of %d (built: 0; 8 with 16)", shift, kw);
-    const long G = (long)N * Hp * Wp * 32;
-    if (gs < G || out_gs < G) return set_error(INNFER_ERR_INVALID, "window attention 16: a group stride below N * Hp * Wp * 32");
     const long total = (long)N * nH * (Hp >> 4) * (Wp >> 4);
-    if (total > 0x7fffffffL) return set_error(INNFER_ERR_UNSUPPORTED, "window attention 16: %ld windows x heads exceed the launch grid", total);
+    if (int rc = wa::refuse_strides_grid("window attention 16", gs, out_gs, N, Hp, Wp, total, 0x7fffffffL)) return rc;
     const double nk = (double)kw * kw;
     GtScope gt(s, kw == 16 ? "window attention (16 x 16, all heads)" : "overlapping window attention (16 x 16 on 24 x 24, all heads)", 4.0 * 256 * nk * 32 * (double)total,
                (double)total * (256 * 32 * 2 * 2 + nk * 32 * 2 * 2 + 256 * nk * 4));

@@ -3,16 +3,15 @@
 //   qkv slab   3 nH G channel groups of 32: groups h G .. h G + G - 1 = q of head h (d real channels, then zeros; the d^-0.5 already inside the weights), then the nH G
 //              groups of k, then those of v
 //   out slab   nH G groups: head h's result at the query pixels in groups h G .. h G + G - 1, channels >= d of the head written as zeros
-// Window geometry, the roll as addresses (shift 0 | 8), the -100 mask from the coordinates and the dense [nH][256 query][256 key] fp32 bias as the C operand are those of
-// win_attn16_kernel<16> (win_attn16.hip, which this file does not touch), and so is the declared arithmetic: fp32 scores, blocks of 64 keys with a running maximum and sum,
-// P rounded to fp16 as the operand of the second product, fp32 accumulation, one rounding of o / sum.  Per block a wave issues 8 G v_mfma_f32_16x16x32_f16 for S (chained over
-// the G channel steps in the same accumulator) and 8 G for O.
+// Window geometry, the roll as addresses (shift 0 | 8), the mask and the dense [nH][256 query][256 key] fp32 bias as the C operand are those of win_attn16_kernel<16>
+// (win_attn16.hip); the arithmetic is win_attn_core.h's.  Per block a wave issues 8 G v_mfma_f32_16x16x32_f16 for S (chained over the G channel steps in the same
+// accumulator) and 8 G for O.
 // Resources: 64 queries a wave would need 16 G VGPRs of Q fragments, 32 G of O accumulators and 64 of scores (352 at G = 4: one wave per SIMD).  So a workgroup is EIGHT waves
 // and a wave owns 32 queries: 8 G + 16 G + 32 registers of state, which leaves every instantiation under 256 registers (two waves per SIMD from ONE workgroup) with no scratch:
-// 134 / 164 / 190 VGPRs, no AGPRs, for G = 2 / 3 / 4 as the compiler reports them (tests/test_drct_host.py asserts the scratch condition at compile time).
-// V^T of the window is staged once per workgroup in LDS ([32 G channels][256 slots + 8] fp16: 33.8 / 50.7 / 67.6 KB), in win_attn16's slot order; K fragments come from the
-// slab (L2 serves the seven re-reads of a window's K by the other waves).
-#include "common.h"
+// 127 / 159 / 186 VGPRs, no AGPRs, for G = 2 / 3 / 4 as the compiler reports them (tests/test_drct_host.py asserts the scratch condition at compile time).
+// V^T of the window is staged once per workgroup in LDS ([32 G channels][256 slots + 8] fp16: 33.8 / 50.7 / 67.6 KB); K fragments come from the slab (L2 serves the seven
+// re-reads of a window's K by the other waves).
+#include "win_attn_core.h"
 
 namespace innfer {
 
@@ -24,8 +23,6 @@ struct WinAttn16W {
     const float* relb;
     int N, Hp, Wp, nH, d, shift;
 };
-
-__device__ __forceinline__ int wa16w_band(int r, int n) { return r < n - 16 ? 0 : (r < n - 8 ? 1 : 2); }
 
 template <int G>
 __global__ __launch_bounds__(512) void win_attn16_wide_kernel(const WinAttn16W p) {
@@ -49,11 +46,8 @@ __global__ __launch_bounds__(512) void win_attn16_wide_kernel(const WinAttn16W p
     const f16* kb = qb + sec;
     const f16* vb = p.qkv + 2 * sec + (long)h * G * p.gs;
     for (int pc = tid; pc < 256 * 4 * G; pc += 512) {            // V^T into LDS: piece (key, channel octet) -> eight rows, the key's slot inside its 64-key block
-        const int tok = pc / (4 * G), oct = pc - tok * (4 * G), t = tok & 63;
-        const f16x8 v = *(const f16x8*)(vb + (long)(oct >> 2) * p.gs + pix(tok) + 8 * (oct & 3));
-        const int slot = (tok & ~63) + (t & 32) + 8 * ((t >> 2) & 3) + 4 * ((t >> 4) & 1) + (t & 3);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) vt[(8 * oct + e) * VROW + slot] = v[e];
+        const int tok = pc / (4 * G), oct = pc - tok * (4 * G);
+        wa::scatter_vt<VROW>(vt, tok, oct, *(const f16x8*)(vb + (long)(oct >> 2) * p.gs + pix(tok) + 8 * (oct & 3)));
     }
     long px[2];
     f16x8 qf[2][G];
@@ -68,10 +62,7 @@ __global__ __launch_bounds__(512) void win_attn16_wide_kernel(const WinAttn16W p
     const bool masked = p.shift && (wy == (p.Hp >> 4) - 1 || wx == nwx - 1);      // (workgroup-uniform) the windows that wrap
     int lq[2];
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int tq = 32 * wave + 16 * t + li;
-        lq[t] = 3 * wa16w_band(wy * 16 + (tq >> 4), p.Hp) + wa16w_band(wx * 16 + (tq & 15), p.Wp);
-    }
+    for (int t = 0; t < 2; ++t) lq[t] = wa::label_sq<16>(wy, wx, 32 * wave + 16 * t + li, p.Hp, p.Wp);
     const float* rb = p.relb + (long)h * 65536 + (long)(32 * wave + li) * 256 + 4 * lg;
     const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
     float m[2], l[2];
@@ -103,71 +94,12 @@ __global__ __launch_bounds__(512) void win_attn16_wide_kernel(const WinAttn16W p
 #pragma unroll
                 for (int tk = 0; tk < 4; ++tk) s[tk][tq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[tk], qf[tq][g], s[tk][tq], 0, 0, 0);
         }
-        if (masked) {
-#pragma unroll
-            for (int tk = 0; tk < 4; ++tk)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int key = 64 * b + 16 * tk + 4 * lg + j;
-                    const int lk = 3 * wa16w_band(wy * 16 + (key >> 4), p.Hp) + wa16w_band(wx * 16 + (key & 15), p.Wp);
-#pragma unroll
-                    for (int tq = 0; tq < 2; ++tq)
-                        if (lq[tq] != lk) s[tk][tq][j] += -100.0f;
-                }
-        }
+        if (masked) wa::mask_block(s, lq, 64 * b + 4 * lg, [&](int key) { return wa::label_sq<16>(wy, wx, key, p.Hp, p.Wp); });
         f16x8 pf[2][2];                                  // pf[tq][ks]: the B fragment of key step ks of this block
-#pragma unroll
-        for (int tq = 0; tq < 2; ++tq) {
-            float mb = s[0][tq][0];
-#pragma unroll
-            for (int tk = 0; tk < 4; ++tk)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mb = fmaxf(mb, s[tk][tq][j]);
-            mb = fmaxf(mb, __shfl_xor(mb, 16));
-            mb = fmaxf(mb, __shfl_xor(mb, 32));
-            const float mn = fmaxf(m[tq], mb);
-            const float alpha = __expf(m[tq] - mn);      // (first block: exp(-3e38 - mn) = 0 on a zero sum and a zero accumulator)
-            float sum = 0.f;
-#pragma unroll
-            for (int tk = 0; tk < 4; ++tk)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float e = __expf(s[tk][tq][j] - mn);
-                    sum += e;
-                    pf[tq][tk >> 1][4 * (tk & 1) + j] = (f16)e;
-                }
-            sum += __shfl_xor(sum, 16);
-            sum += __shfl_xor(sum, 32);
-            l[tq] = l[tq] * alpha + sum;
-            m[tq] = mn;
-#pragma unroll
-            for (int td = 0; td < 2 * G; ++td)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) o[td][tq][j] *= alpha;
-        }
-#pragma unroll
-        for (int td = 0; td < 2 * G; ++td) {
-            const f16* vr = vt + (16 * td + li) * VROW + 64 * b + 8 * lg;
-            const f16x8 a0 = *(const f16x8*)vr, a1 = *(const f16x8*)(vr + 32);
-#pragma unroll
-            for (int tq = 0; tq < 2; ++tq) {
-                o[td][tq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, pf[tq][0], o[td][tq], 0, 0, 0);
-                o[td][tq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, pf[tq][1], o[td][tq], 0, 0, 0);
-            }
-        }
+        wa::softmax_block(s, m, l, o, pf);
+        wa::pv_block<2, 2 * G, VROW>(vt + 64 * b, li, lg, pf, o);
     }
-    f16* ob = p.out + (long)h * G * p.out_gs + 4 * lg;
-#pragma unroll
-    for (int tq = 0; tq < 2; ++tq) {
-        const float inv = 1.0f / l[tq];
-#pragma unroll
-        for (int td = 0; td < 2 * G; ++td) {
-            f16x4 r;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) r[j] = 16 * td + 4 * lg + j < p.d ? (f16)(o[td][tq][j] * inv) : (f16)0.f;
-            *(f16x4*)(ob + (long)(td >> 1) * p.out_gs + px[tq] + 16 * (td & 1)) = r;
-        }
-    }
+    wa::store_out(p.out + (long)h * G * p.out_gs, p.out_gs, px, o, l, p.d, lg, [](int) { return false; });
 }
 
 template <int G>
@@ -184,15 +116,12 @@ int wa16w_go(const WinAttn16W& p, unsigned total, hipStream_t s) {
 
 // relb: dense fp32 [nH][256 query][256 key]; Hp, Wp multiples of 16; 32 < d <= 128; shift 0 | 8.  A refusal launches nothing.
 int win_attn16_wide_launch(const f16* qkv, long gs, f16* out, long out_gs, const float* relb, int N, int Hp, int Wp, int nH, int d, int shift, hipStream_t s) {
-    if (!qkv || !out || !relb || N <= 0 || Hp <= 0 || Wp <= 0) return set_error(INNFER_ERR_INVALID, "wide window attention 16: null argument or N=%d Hp=%d Wp=%d", N, Hp, Wp);
-    if ((Hp & 15) || (Wp & 15)) return set_error(INNFER_ERR_INVALID, "wide window attention 16: %d x %d is not a whole number of 16 x 16 windows (the caller pads)", Hp, Wp);
+    if (int rc = wa::refuse_frame("wide window attention 16", qkv, out, relb, N, Hp, Wp, 16)) return rc;
     if (nH < 1 || nH > 8 || d <= 32 || d > 128)
         return set_error(INNFER_ERR_UNSUPPORTED, "wide window attention 16: %d heads of %d channels (built: <= 8 heads of 33 .. 128 channels; win_attn16_launch takes d <= 32)", nH, d);
     if (shift != 0 && shift != 8) return set_error(INNFER_ERR_UNSUPPORTED, "wide window attention 16: shift %d (built: 0, 8)", shift);
-    const long Gs = (long)N * Hp * Wp * 32;
-    if (gs < Gs || out_gs < Gs) return set_error(INNFER_ERR_INVALID, "wide window attention 16: a group stride below N * Hp * Wp * 32");
     const long total = (long)N * nH * (Hp >> 4) * (Wp >> 4);
-    if (total > 0x7fffffffL) return set_error(INNFER_ERR_UNSUPPORTED, "wide window attention 16: %ld windows x heads exceed the launch grid", total);
+    if (int rc = wa::refuse_strides_grid("wide window attention 16", gs, out_gs, N, Hp, Wp, total, 0x7fffffffL)) return rc;
     const int g = (d + 31) / 32;
     GtScope gt(s, "window attention (16 x 16, heads of 2 .. 4 groups)", 4.0 * 256 * 256 * d * (double)total, (double)total * (256.0 * 32 * g * 2 * 4 + 65536.0 * 4));
     const WinAttn16W p{qkv, gs, out, out_gs, relb, N, Hp, Wp, nH, d, shift};

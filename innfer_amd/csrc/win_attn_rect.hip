@@ -1,5 +1,6 @@
-// Attention over RECTANGULAR windows in two head branches of transposed shape (DAT's adaptive spatial attention), over the head-padded qkv slab of win_attn.hip on the
-// UNPADDED H x W grid: ONE launch for all windows, both branches and all heads of a batch.  split = [s0, s1] ([8, 32] | [8, 16]), T = s0 s1 tokens per window (256 | 128):
+// Attention over RECTANGULAR windows in two head branches of transposed shape (DAT's adaptive spatial attention), over the head-padded qkv slab on the UNPADDED H x W grid:
+// ONE launch for all windows, both branches and all heads of a batch.  The arithmetic is win_attn_core.h's (the running softmax over blocks of 64 keys); this file's own is
+// the geometry.  split = [s0, s1] ([8, 32] | [8, 16]), T = s0 s1 tokens per window (256 | 128):
 //   branch 0   heads 0 .. nH / 2 - 1: windows of s0 rows x s1 columns, shift (s0 / 2, s1 / 2)
 //   branch 1   heads nH / 2 .. nH - 1: windows of s1 rows x s0 columns, shift (s1 / 2, s0 / 2)
 // The frame the windows tile is Hp x Wp, H and W rounded up to multiples of s1 = max(s0, s1); it exists only as coordinates.  Token i of window (wy, wx) of a head whose
@@ -9,13 +10,8 @@
 // Shifted: -100 (not -inf) between tokens whose labels 3 a(r) + b(c) differ, a = 0 below Hp - wh, 1 below Hp - shy, else 2 on the rolled-frame row, b likewise with Wp, ww,
 // shx: anisotropic per branch, computed from the coordinates, only in the last window row / column (elsewhere every label is 0).
 // The bias is a dense [nH][T][T] fp32 table (query-major), tokens row-major inside the head's OWN window shape.
-// A workgroup of T threads owns one (image, head, window); wave w its queries 64 w .. 64 w + 63.  The arithmetic is win_attn16.hip's: the keys are walked in blocks of 64
-// with a running maximum and a running sum,
-//   S^T = K Q^T + B^T   sixteen v_mfma_f32_16x16x32_f16 per block, the fragments 16-byte loads from the slab (zeros for a pad token), the C operand the bias;
-//   softmax             m' = max(m, block maximum); sum and accumulator times exp(m - m'); P = exp(s - m') in fp32, summed unrounded, rounded to fp16 for the second product;
-//   O^T += V^T P^T      sixteen MFMAs per block, V^T of the window staged once per workgroup in LDS ([32][T + 8] fp16) in win_attn.hip's slot order;
-// o / sum in fp32, one rounding, one 8-byte store per lane and channel quad; channels >= d are written as zeros.  A window of image n reads only image n.
-#include "common.h"
+// A workgroup of T threads owns one (image, head, window); wave w its queries 64 w .. 64 w + 63; V^T of the window is staged once per workgroup in LDS ([32][T + 8] fp16).
+#include "win_attn_core.h"
 
 namespace innfer {
 
@@ -27,8 +23,6 @@ struct WinAttnRect {
     const float* relb;
     int N, H, W, Hp, Wp, nH, d, s0, s1, shifted;
 };
-
-__device__ __forceinline__ int war_band(int r, int n, int win, int sh) { return r < n - win ? 0 : (r < n - sh ? 1 : 2); }
 
 template <int T>
 __global__ __launch_bounds__(T) void win_attn_rect_kernel(const WinAttnRect p) {
@@ -60,12 +54,9 @@ __global__ __launch_bounds__(T) void win_attn_rect_kernel(const WinAttnRect p) {
     const f16* kb = qb + (long)p.nH * p.gs;
     const f16* vb = p.qkv + (long)(2 * p.nH + h) * p.gs;
     for (int pc = tid; pc < T * 4; pc += T) {                  // V^T into LDS: piece (key, channel octet) -> eight rows, the key's slot inside its 64-key block
-        const int tok = pc >> 2, oct = pc & 3, t = tok & 63;
+        const int tok = pc >> 2, oct = pc & 3;
         const long o = tpix(tok);
-        const f16x8 v = o >= 0 ? *(const f16x8*)(vb + o + 8 * oct) : zero8;
-        const int slot = (tok & ~63) + (t & 32) + 8 * ((t >> 2) & 3) + 4 * ((t >> 4) & 1) + (t & 3);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) vt[(8 * oct + e) * VROW + slot] = v[e];
+        wa::scatter_vt<VROW>(vt, tok, oct, o >= 0 ? *(const f16x8*)(vb + o + 8 * oct) : zero8);
     }
     long px[4];
     f16x8 qf[4];
@@ -79,7 +70,7 @@ __global__ __launch_bounds__(T) void win_attn_rect_kernel(const WinAttnRect p) {
     const bool masked = p.shifted && (wy == nwy - 1 || wx == nwx - 1);      // (workgroup-uniform) the windows that wrap
     auto label = [&](int j) -> int {
         const int jr = j / ww;
-        return 3 * war_band(wy * wh + jr, p.Hp, wh, shy) + war_band(wx * ww + (j - jr * ww), p.Wp, ww, shx);
+        return 3 * wa::band(wy * wh + jr, p.Hp, wh, shy) + wa::band(wx * ww + (j - jr * ww), p.Wp, ww, shx);
     };
     int lq[4];
 #pragma unroll
@@ -107,69 +98,12 @@ __global__ __launch_bounds__(T) void win_attn_rect_kernel(const WinAttnRect p) {
                 const f32x4 bias = *(const f32x4*)(rb + 16 * tq * T + 64 * b + 16 * tk);
                 s[tk][tq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf[tk], qf[tq], bias, 0, 0, 0);
             }
-        if (masked) {
-#pragma unroll
-            for (int tk = 0; tk < 4; ++tk)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int lk = label(64 * b + 16 * tk + 4 * lg + j);
-#pragma unroll
-                    for (int tq = 0; tq < 4; ++tq)
-                        if (lq[tq] != lk) s[tk][tq][j] += -100.0f;
-                }
-        }
+        if (masked) wa::mask_block(s, lq, 64 * b + 4 * lg, label);
         f16x8 pf[4][2];                                  // pf[tq][ks]: the B fragment of key step ks of this block
-#pragma unroll
-        for (int tq = 0; tq < 4; ++tq) {
-            float mb = s[0][tq][0];
-#pragma unroll
-            for (int tk = 0; tk < 4; ++tk)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) mb = fmaxf(mb, s[tk][tq][j]);
-            mb = fmaxf(mb, __shfl_xor(mb, 16));
-            mb = fmaxf(mb, __shfl_xor(mb, 32));
-            const float mn = fmaxf(m[tq], mb);
-            const float alpha = __expf(m[tq] - mn);      // (first block: exp(-3e38 - mn) = 0 on a zero sum and a zero accumulator)
-            float sum = 0.f;
-#pragma unroll
-            for (int tk = 0; tk < 4; ++tk)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float e = __expf(s[tk][tq][j] - mn);
-                    sum += e;
-                    pf[tq][tk >> 1][4 * (tk & 1) + j] = (f16)e;
-                }
-            sum += __shfl_xor(sum, 16);
-            sum += __shfl_xor(sum, 32);
-            l[tq] = l[tq] * alpha + sum;
-            m[tq] = mn;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { o[0][tq][j] *= alpha; o[1][tq][j] *= alpha; }
-        }
-#pragma unroll
-        for (int td = 0; td < 2; ++td) {
-            const f16* vr = vt + (16 * td + li) * VROW + 64 * b + 8 * lg;
-            const f16x8 a0 = *(const f16x8*)vr, a1 = *(const f16x8*)(vr + 32);
-#pragma unroll
-            for (int tq = 0; tq < 4; ++tq) {
-                o[td][tq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a0, pf[tq][0], o[td][tq], 0, 0, 0);
-                o[td][tq] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a1, pf[tq][1], o[td][tq], 0, 0, 0);
-            }
-        }
+        wa::softmax_block(s, m, l, o, pf);
+        wa::pv_block<4, 2, VROW>(vt + 64 * b, li, lg, pf, o);
     }
-    f16* ob = p.out + (long)h * p.out_gs + 4 * lg;
-#pragma unroll
-    for (int tq = 0; tq < 4; ++tq) {
-        if (px[tq] < 0) continue;                        // a pad token as a query: its result is dropped
-        const float inv = 1.0f / l[tq];
-#pragma unroll
-        for (int td = 0; td < 2; ++td) {
-            f16x4 r;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) r[j] = 16 * td + 4 * lg + j < p.d ? (f16)(o[td][tq][j] * inv) : (f16)0.f;
-            *(f16x4*)(ob + px[tq] + 16 * td) = r;
-        }
-    }
+    wa::store_out(p.out + (long)h * p.out_gs, p.out_gs, px, o, l, p.d, lg, [&](int tq) { return px[tq] < 0; });      // a pad token as a query: its result is dropped
 }
 
 }  // namespace

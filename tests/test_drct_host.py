@@ -324,15 +324,19 @@ def test_new_symbols_are_declared_and_bound():
     assert "template <int KW>" in open(os.path.join(ROOT, "innfer_amd", "csrc", "win_attn16.hip")).read()
 
 
-def test_wide_attention_uses_no_scratch_and_fits_two_waves_a_simd():
-    """The scratch condition, at compile time: hipcc's kernel resource-usage remarks for csrc/win_attn16_wide.hip state ScratchSize 0 for all three instantiations, and
-    VGPRs + AGPRs <= 256, so that the two waves a SIMD that an 8-wave workgroup needs fit (DESIGN.md 3.4p records the figures)."""
+_USAGE = {}
+
+
+def _resource_usage(name):
+    """hipcc's kernel resource-usage remarks for csrc/<name>.hip: {mangled kernel name: {field: value}} (compiled once per file)."""
     import shutil
     import subprocess
+    if name in _USAGE:
+        return _USAGE[name]
     hipcc = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc on this machine")
-    src = os.path.join(ROOT, "innfer_amd", "csrc", "win_attn16_wide.hip")
+    src = os.path.join(ROOT, "innfer_amd", "csrc", name + ".hip")
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -343,12 +347,48 @@ def test_wide_attention_uses_no_scratch_and_fits_two_waves_a_simd():
             cur = kernels.setdefault(m.group(1), {})
         elif m:
             cur[m.group(2).strip()] = int(m.group(3))
+    _USAGE[name] = kernels
+    return kernels
+
+
+def test_wide_attention_uses_no_scratch_and_fits_two_waves_a_simd():
+    """The scratch condition, at compile time: hipcc's kernel resource-usage remarks for csrc/win_attn16_wide.hip state ScratchSize 0 for all three instantiations, and
+    VGPRs + AGPRs <= 256, so that the two waves a SIMD that an 8-wave workgroup needs fit (DESIGN.md 3.4p records the figures)."""
+    kernels = _resource_usage("win_attn16_wide")
     wide = {k: v for k, v in kernels.items() if "win_attn16_wide_kernel" in k}
     print({k: (v.get("VGPRs"), v.get("AGPRs"), v.get("ScratchSize")) for k, v in wide.items()})
     assert len(wide) == 3, list(kernels)
     for k, v in wide.items():
         assert v["ScratchSize"] == 0, (k, v)
         assert v["VGPRs"] + v["AGPRs"] <= 256, (k, v)
+
+
+# (file, the instantiation inside the mangled name): (static LDS bytes, waves a SIMD as the compiler reports them) of the build BEFORE the four kernels shared
+# csrc/win_attn_core.h -- the copies the core replaced.  The wide kernel's LDS is dynamic (0 here).
+WINDOW_KERNELS = {
+    ("win_attn", "win_attn_kernelILb1E"): (19456, 4), ("win_attn", "win_attn_kernelILb0E"): (18432, 2),
+    ("win_attn16", "win_attn16_kernelILi16E"): (16896, 2), ("win_attn16", "win_attn16_kernelILi24E"): (37376, 2),
+    ("win_attn16_wide", "win_attn16_wide_kernelILi2E"): (0, 3), ("win_attn16_wide", "win_attn16_wide_kernelILi3E"): (0, 3),
+    ("win_attn16_wide", "win_attn16_wide_kernelILi4E"): (0, 2),
+    ("win_attn_rect", "win_attn_rect_kernelILi256E"): (16896, 2), ("win_attn_rect", "win_attn_rect_kernelILi128E"): (8704, 2),
+}
+
+
+@pytest.mark.parametrize("src", sorted({f for f, _ in WINDOW_KERNELS}))
+def test_window_attention_kernels_keep_their_resources(src):
+    """Every instantiation of the four window-attention kernels, built on the shared core: no scratch, the static LDS of the separate copies byte for byte, and no
+    fewer waves a SIMD than they had (DESIGN.md 3.4p records the register counts of both)."""
+    kernels = _resource_usage(src)
+    for (f, inst), (lds, waves) in WINDOW_KERNELS.items():
+        if f != src:
+            continue
+        hit = [v for k, v in kernels.items() if inst in k]
+        assert len(hit) == 1, (inst, list(kernels))
+        v = hit[0]
+        print(inst, {q: v.get(q) for q in ("VGPRs", "AGPRs", "ScratchSize", "LDS Size", "Occupancy")})
+        assert v["ScratchSize"] == 0, (inst, v)
+        assert v["LDS Size"] == lds, (inst, v)
+        assert v["Occupancy"] >= waves, (inst, v)
 
 
 # ------------------------------------------------------------------------------------------------ the folds, taken apart and put together again
