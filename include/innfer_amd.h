@@ -423,7 +423,9 @@ int innfer_net_scale(innfer_net_t net);
 size_t innfer_net_workspace_bytes(innfer_net_t net, int N, int H, int W);
 
 /* nn.Module.forward(x): d_in [N,in_nc,H,W] -> d_out [N,out_nc,s*H,s*W], NCHW,
- * dtypes per innfer_dtype.  Replaces `self.model(data)` (run.py:187-189,217-219). */
+ * dtypes per innfer_dtype.  Replaces `self.model(data)` (run.py:187-189,217-219).
+ * d_workspace: at least innfer_net_workspace_bytes(net, N, H, W) bytes; it need not be cleared.  A short or
+ * missing workspace is INNFER_ERR_WORKSPACE, with nothing launched. */
 int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dtype, void* d_out, int out_dtype,
                        int N, int H, int W, void* d_workspace, size_t workspace_bytes, void* stream);
 

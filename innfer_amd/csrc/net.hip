@@ -2126,7 +2126,7 @@ int run_chain(std::vector<ConvLaunch>& chain, int band_rows, hipStream_t s) {
 
 extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dtype, void* d_out, int out_dtype,
                                   int N, int H, int W, void* d_ws, size_t ws_bytes, void* stream) {
-    if (!net || !d_in || !d_out || !d_ws) return set_error(INNFER_ERR_INVALID, "forward: null argument");
+    if (!net || !d_in || !d_out) return set_error(INNFER_ERR_INVALID, "forward: null argument");
     if (N <= 0 || H <= 0 || W <= 0) return set_error(INNFER_ERR_INVALID, "forward: bad shape %dx%dx%d", N, H, W);
     auto dtype_ok = [](int d) { return d == INNFER_F16 || d == INNFER_F32 || d == INNFER_U8; };
     if (!dtype_ok(in_dtype) || !dtype_ok(out_dtype)) return set_error(INNFER_ERR_INVALID, "forward: bad dtype");
@@ -2136,7 +2136,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     const int img_h = H, img_w = W;               // (unshuffle > 1: the image; H x W below is the LR grid every layer runs on)
     H = (H + net->unshuffle - 1) / net->unshuffle; W = (W + net->unshuffle - 1) / net->unshuffle;
     const Carve cv = carve(net, N, H, W);
-    if (ws_bytes < cv.total) return set_error(INNFER_ERR_WORKSPACE, "forward: workspace %zu < %zu bytes", ws_bytes, cv.total);
+    if (!d_ws || ws_bytes < cv.total) return set_error(INNFER_ERR_WORKSPACE, "forward: workspace %zu < %zu bytes", d_ws ? ws_bytes : (size_t)0, cv.total);          // (short or missing, as innfer_pan_attention's)
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)d_ws;
     if (net->kind == 5 || net->kind == 6 || net->kind == 7 || net->kind == 8 || net->kind == 9) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);

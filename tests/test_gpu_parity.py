@@ -2349,7 +2349,8 @@ def test_4k_input_untiled_addresses_beyond_2gib(dev):
 def test_every_family_ignores_workspace_contents(dev, kind, scale, shape):
     """Every byte a forward reads from its workspace was written by an earlier launch of the SAME forward: filling the
     workspace with NaN patterns between two forwards must not change a single output bit (pad channels, halo rows, split-K
-    partials, statistics scratch ...)."""
+    partials, statistics scratch ...).  Nor must 0x7B bytes (fp16 0x7B7B = 6.1e4, fp32 1.3e36: finite and huge) -- a running
+    maximum or a select drops a NaN it read and shows a huge finite value; NaN x 0 shows where a finite value x 0 does not."""
     from innfer_amd import synth
     from innfer_amd.architectures import get_network
     from innfer_amd.utils.defaults import get_network_G_config
@@ -2365,7 +2366,9 @@ def test_every_family_ignores_workspace_contents(dev, kind, scale, shape):
     y = out(net(x)).clone()
     assert torch.isfinite(y).all()
     net._ws.fill_(0xFF)
-    assert torch.equal(out(net(x)), y)
+    assert torch.equal(out(net(x)), y), "0xFF (NaN) in the workspace changes the result"
+    net._ws.fill_(0x7B)
+    assert torch.equal(out(net(x)), y), "0x7B (huge, finite) in the workspace changes the result"
 
 
 @pytest.mark.parametrize("kind", ["wbcunet", "resnet_9blocks"])
