@@ -45,7 +45,7 @@ typedef struct innfer_net* innfer_net_t;
 
 /* ABI revision of this header (major*100 + minor).  101/102: innfer_conv_args grew reflect_pad / dilation / dilation_groups (zero-initialise the struct),
  * innfer_wbc_create takes tf_mode, innfer_net_set_final_act.  103: innfer_net_forward_timed reports algorithmic bytes, innfer_conv_args.pixel_shuffle2, innfer_unet_set_eval,
- * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): RealPLKSR -- innfer_plksr_create, innfer_net_set_group_norm, innfer_conv_args.act 11 (Mish), innfer_plk_conv (the partial large-kernel conv as a single launch), innfer_group_norm_skip / innfer_group_norm_skip_work_bytes (per-sample GroupNorm + skip over a 64-channel slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): SwinIR -- innfer_swinir_create, innfer_net_set_layer_norm, innfer_net_set_attn_bias, innfer_conv_args.act 12 (exact GELU on the 1x1 form), innfer_window_attention (the 8 x 8 window attention as a single launch), innfer_layer_norm (per-pixel LayerNorm over a padded slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a HAT): HAT -- innfer_hat_create, innfer_net_set_chan_attn, innfer_net_set_conv_scale, innfer_conv_args.act 13 (exact GELU on the plain 3x3 form), innfer_window_attention16 (the 16 x 16 window attention over a 16 x 16 or an overlapping 24 x 24 key window as a single launch), innfer_chan_attn_work_bytes / innfer_chan_attn_excite / innfer_chan_attn_scale_add (the channel attention's launches).  Also added under 123 (additive: new entry points only, no struct or signature changed): the kernels of DAT's blocks as single launches -- innfer_window_attention_rect (rectangular windows in two transposed head branches), innfer_channel_attention_work_bytes / innfer_channel_attention_scores / innfer_channel_attention_apply (attention across channels over a whole sample), innfer_dwconv3x3 (depthwise 3 x 3 with its three epilogues), innfer_chan_attn_excite_gelu, innfer_aim_mix (the two gates that blend the attention and conv branches), innfer_layer_norm_wide (LayerNorm over up to 512 channels) -- and the network on them: innfer_dat_create, innfer_dat_block_floats, innfer_net_set_dat_block (innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a DAT).  124: the remaining pass kernels of PAN, PPON and the WBC UNet and two passes of the fp32 mode one launch at a time, for tests (additive) -- innfer_pan_pre, innfer_pan_upsample, innfer_pan_final, innfer_pan_slab_pair, innfer_ppon_upsample3, innfer_ppon_axpy, innfer_wbc_pre, innfer_wbc_upadd, innfer_f32_prefix_lrelu, innfer_f32_act_copy.  Added under 124 without a new revision (additive: new entry points only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a DRCT): DRCT -- innfer_drct_create, innfer_window_attention16_wide (the 16 x 16 window attention for heads of 33 .. 128 channels as a single launch), innfer_layer_norm_holed (LayerNorm over a dense slab whose real channels have a hole).  innfer_version() returns the library's; a binding should compare. */
+ * innfer_comm_* / innfer_gather_tiles / innfer_shard_tiles.  104: innfer_rrdbnet_create_ex, innfer_pan_create_ex, innfer_srresnet_create_ex, innfer_resnet_create_ex, innfer_unet_create_ex, innfer_net_set_outm, innfer_guided_filter_ex, innfer_filter2d, innfer_net_set_pair_convs, innfer_inthwc_to_nchw / innfer_nchw_to_inthwc, innfer_linear_resize, INNFER_U8 at the network boundary (innfer_net_set_u8_io), innfer_extract_tiles_u8 / innfer_recompose_u8, innfer_conv_args.stride2_k4 / transposed2x / column7 with innfer_pack_conv4x4s2 / innfer_pack_convt2x / innfer_pack_conv7x1.  105: innfer_net_set_conv_input_map, SRResNet scale 3, PixelShuffle(3) stages (nf 64) and PixelShuffle(2) on nf 32.  106: the fp32-accurate mode -- innfer_net_set_precision, innfer_conv_args.split / *_lo, innfer_pack_conv3x3_split, innfer_nchw_to_slab_split / innfer_slab_split_to_nchw.  107: innfer_net_set_fused_tail, innfer_net_set_upconv_phases.  108: innfer_net_set_residual_lds, innfer_conv_args.res1_from_input, innfer_pan_set_fused_scpa, innfer_unet_set_precision, innfer_pan_set_precision, innfer_ppon_set_precision, innfer_resnet_set_precision, innfer_wbc_set_precision.  109: innfer_conv_args.plane_rows, innfer_pack_conv3x3_rows, innfer_pack_convt2x_rows; innfer_net_set_upconv_phases takes 0 / 1 / 2.  110: innfer_net_set_conv on a network in the fp32 mode builds that conv's split panels (either call order of set_precision / set_conv works); innfer_pack_conv3x3_shuffle2 + innfer_conv_args.plane_rows = 2.  111: innfer_net_set_hr_chain.  112: REMOVED -- innfer_net_set_pair_convs (csrc/conv_pair.hip: the fused conv pairs of a dense block, measured 3 % slower per frame in round 2 and off ever since), innfer_pack_conv3x3_wino / innfer_conv3x3_wino_packed_bytes and the meaning of innfer_conv_args.winograd (now reserved0, must be 0): the row-Winograd experiment of round 3.  113: no new symbol -- innfer_pan_set_precision(p, 1) now selects the split-operand forms for PAN's SCPA trunk / up-stages / attention (innfer_pan_set_fused_scpa(p, 0) keeps the 112 form; 5: A/B of the PA epilogue).  114: innfer_f32conv_args, innfer_f32conv_packed_floats, innfer_pack_f32conv, innfer_f32conv, innfer_f32conv_plan, innfer_f32_norm (the fp32-mode building blocks as single launches, for tests).  115: fit_channels -- innfer_channel_minmax, innfer_extract_tiles_u8_fit, innfer_recompose_u8_fit, innfer_inthwc_to_nchw_fit, innfer_nchw_to_inthwc_fit (gray, gray + alpha and BGRA images through an RGB network).  116: innfer_rrdbnet_create_ex2 (pixel_unshuffle(2 | 4) folded into the first conv: BasicSR / Real-ESRGAN RRDBNet scale 2 and 1), innfer_first_conv_unshuffle (that conv as a single launch, for tests).  117: seamless modes -- innfer_border_index, innfer_pad_inthwc, innfer_extract_tiles_u8_seamless, innfer_extract_tiles_u8_fit_seamless, innfer_recompose_u8_seamless, innfer_recompose_u8_fit_seamless (tileable textures: the chop path reads the image through a border index map and blends only the crop window).  118: -outscale -- innfer_resample_taps, innfer_resample_plan, innfer_resample_workspace_bytes, innfer_resample_inthwc (the result resampled to any final size on the device: an antialiased separable resampler in the Pillow / ATen antialias=True convention).  119: -tta -- innfer_dihedral_index, innfer_extract_tiles_u8_tta, innfer_recompose_u8_tta (the 8-way flip / rotate self-ensemble fused into the uint8 chop path: one gather of the eight orientations' tiles, one blend that averages the eight results before quantisation).  120: the fp16 engine's norm statistics as single launches, for tests -- innfer_conv_args.d_stats_part / stats_part_floats, innfer_conv_stats_records, innfer_norm_combine_parts, innfer_norm_stats, innfer_resnet_post_slab_parts, innfer_unet_post_slab_parts.  121: every remaining form of the conv kernel as a single launch, for tests -- innfer_conv_args.conv1x1 / prefix_lrelu / d_gate_packed / d_gate_bias / in_relu / conv7x7 / out_planar / out_denorm / out_round16 / planar_phases / outm and act 3 / 6, innfer_conv1x1_packed_bytes, innfer_pack_conv1x1, innfer_pack_conv1x1_split, innfer_pack_selfgate, innfer_conv7x7_packed_bytes, innfer_pack_conv7x7, innfer_pack_up2x_phases.  Added under 121 without a new revision (new entry points only, no struct or signature changed): BasicSR's SRVGGNetCompact -- innfer_compact_create, innfer_net_set_conv_slope, innfer_conv3x3_f16_slope (act 8: per-channel slopes), innfer_shuffle_add.  122: the gather GEMM (csrc/gather_gemm.h) as a single launch, for tests -- innfer_gather_gemm_args, innfer_gather_gemm_packed_bytes, innfer_pack_gather_gemm, innfer_gather_gemm, innfer_gather_gemm_plan.  Added under 122 without a new revision (122, additive: new entry points only, no struct or signature changed): the stitched tile path, `-tile N -tile_pad P` -- innfer_tile_plan, innfer_tile_owner, innfer_extract_tiles_rect, innfer_extract_tiles_u8_rect, innfer_stitch_tiles, innfer_stitch_tiles_u8 (csrc/tiles_stitch.hip).  Also added under 122 (additive: new entry points only, no struct or signature changed): innfer_net_set_consumer_grid, innfer_conv3x3_f16_grid (the 64-output trunk convs on a 2 x 4 consumer-wave grid with the residual prefetched; bit-identical results).  Also added under 122 (additive): the launches of PAN's self-attention block one at a time, for tests -- innfer_pan_attention, innfer_pan_attention_workspace_bytes, innfer_pan_maxpool, innfer_pan_fsa_combine.  Also added under 122 (additive): one SCPA block of PAN as a single launch, for tests -- innfer_pan_scpa_blob_bytes, innfer_pack_pan_scpa, innfer_pan_scpa_block, innfer_pan_split_from_nchw, innfer_pan_split_to_nchw.  123: the pass kernels of the pix2pix UNet and the CycleGAN ResNet one launch at a time, for tests (additive) -- innfer_unet_pre / _post / _post_slab / _deep_post / _final, innfer_unet_first_packed_bytes, innfer_pack_unet_first, innfer_unet_first_conv, innfer_resnet_pre / _post / _post_slab / _post_slab_pad / _sum9_tanh / _final.  Added under 123 without a new revision (additive: new entry points only, no struct or signature changed): many images as one tile stream, `-batch B` -- innfer_chop_multi_plan, innfer_extract_tiles_u8_multi, innfer_recompose_u8_multi (csrc/tiles_u8_multi.hip).  Also added under 123 (additive): the colour-fix modes, `-cf_mode wavelet | adain` -- innfer_color_fix_mode_workspace_bytes, innfer_color_fix_mode (csrc/colorfix.hip).  Also added under 123 (additive: new entry points only, no struct or signature changed): the launches every RRDBNet / SRResNet / SRVGGNetCompact forward starts with and the slab passes between its convs one at a time, for tests -- innfer_first_conv, innfer_slab_upsample_nearest, innfer_slab_pixel_shuffle, innfer_slab_input_map.  Also added under 123 (additive: new entry points and new values of existing fields only, no struct or signature changed): SPAN -- innfer_span_create, innfer_first_conv_map (a per-input-channel affine map in front of the first conv), innfer_conv_args.act 9 (SiLU) / 10 (SPAN's gate), innfer_shuffle_add with a NULL base (PixelShuffle alone).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): RealPLKSR -- innfer_plksr_create, innfer_net_set_group_norm, innfer_conv_args.act 11 (Mish), innfer_plk_conv (the partial large-kernel conv as a single launch), innfer_group_norm_skip / innfer_group_norm_skip_work_bytes (per-sample GroupNorm + skip over a 64-channel slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed): SwinIR -- innfer_swinir_create, innfer_net_set_layer_norm, innfer_net_set_attn_bias, innfer_conv_args.act 12 (exact GELU on the 1x1 form), innfer_window_attention (the 8 x 8 window attention as a single launch), innfer_layer_norm (per-pixel LayerNorm over a padded slab).  Also added under 123 (additive: new entry points and a new value of an existing field only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a HAT): HAT -- innfer_hat_create, innfer_net_set_chan_attn, innfer_net_set_conv_scale, innfer_conv_args.act 13 (exact GELU on the plain 3x3 form), innfer_window_attention16 (the 16 x 16 window attention over a 16 x 16 or an overlapping 24 x 24 key window as a single launch), innfer_chan_attn_work_bytes / innfer_chan_attn_excite / innfer_chan_attn_scale_add (the channel attention's launches).  Also added under 123 (additive: new entry points only, no struct or signature changed): the kernels of DAT's blocks as single launches -- innfer_window_attention_rect (rectangular windows in two transposed head branches), innfer_channel_attention_work_bytes / innfer_channel_attention_scores / innfer_channel_attention_apply (attention across channels over a whole sample), innfer_dwconv3x3 (depthwise 3 x 3 with its three epilogues), innfer_chan_attn_excite_gelu, innfer_aim_mix (the two gates that blend the attention and conv branches), innfer_layer_norm_wide (LayerNorm over up to 512 channels) -- and the network on them: innfer_dat_create, innfer_dat_block_floats, innfer_net_set_dat_block (innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a DAT).  124: the remaining pass kernels of PAN, PPON and the WBC UNet and two passes of the fp32 mode one launch at a time, for tests (additive) -- innfer_pan_pre, innfer_pan_upsample, innfer_pan_final, innfer_pan_slab_pair, innfer_ppon_upsample3, innfer_ppon_axpy, innfer_wbc_pre, innfer_wbc_upadd, innfer_f32_prefix_lrelu, innfer_f32_act_copy.  Added under 124 without a new revision (additive: new entry points only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept a DRCT): DRCT -- innfer_drct_create, innfer_window_attention16_wide (the 16 x 16 window attention for heads of 33 .. 128 channels as a single launch), innfer_layer_norm_holed (LayerNorm over a dense slab whose real channels have a hole).  Also added under 124 (additive: new entry points only, no struct or signature changed; innfer_net_set_layer_norm / innfer_net_set_attn_bias also accept an SRFormer, the latter with the COMPACT table): SRFormer -- innfer_srformer_create, innfer_net_set_dwconv5, innfer_window_attention_perm (the permuted window attention over 16 / 22 / 24 windows as a single launch), innfer_dwconv5x5_gelu_add (the feed-forward's depthwise 5 x 5 conv with GELU and its input added back).  innfer_version() returns the library's; a binding should compare. */
 #define INNFER_ABI_VERSION 124
 int innfer_version(void);
 const char* innfer_last_error(void);
@@ -363,6 +363,38 @@ int innfer_layer_norm_holed(const void* d_in, int64_t in_gs, void* d_out, int64_
  * S = lp_k / 64, SQ = ceil(3 nH G / 2), SH = hidden_pad / 64, A = 1 (k < 5) | S1 (k = 5), T = 2 + log2(scale) (4 for scale 3):
  *   2 S1 + 2 + sum over blocks (3 + SQ + 2 S + SH + A) + T + 2 [H x W is not Hp x Wp]. */
 int innfer_drct_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, int n_groups, const int* h_heads, const int* h_hidden, int scale, const float* h_mean);
+/* (124, additive) SRFormer (Zhou et al. 2023, "SRFormer: Permuted Self-Attention for Single Image Super-Resolution"; the reference has no such architecture).  Written down
+ * without the published source at hand: these formulas are the definition, and a checkpoint's shapes are authoritative for sizes.  SwinIR's skeleton (pad, mean,
+ * conv_first, patch_embed.norm, RSTB = conv(blocks(t)) + t, norm, conv_after_body + f, SwinIR's three tails, crop) on windows of ws = 16 | 22 | 24, pw = ws / 2, around
+ *   block j:   t = t + proj(PSA(norm1(t)));  t = t + fc2(h + GELU(dw5x5(h))),  h = GELU(fc1(norm2(t)))        (dw5x5: depthwise, zero padding 2; exact GELU; shift ws / 2 for odd j)
+ *   PSA:       per ws x ws window of the rolled frame, n = ws^2 queries and pw^2 keys; q = q(u) d^-0.5, head h = channels [h d, (h + 1) d), d = C / nH; kv(u) gives C / 2
+ *              channels per pixel, k the first C / 4, v the next; key token (py, px) has C channels: channel f = s (C / 4) + cc is channel cc of pixel (2 py + s / 2,
+ *              2 px + s % 2), s = 0 .. 3, head h is f in [h d, (h + 1) d), v likewise; S = q k^T + B + M, softmax over the keys, o = P v, proj
+ *   B:         B[h][query (r, c)][key (py, px)] = table[(r / 2 - py + pw - 1)(2 pw - 1) + (c / 2 - px + pw - 1)][h]
+ *   M:         (shift only) -100 where labels differ; a query's label is SwinIR's on the rolled frame (slices (0, -ws), (-ws, -ws / 2), (-ws / 2, end) per axis), a key's
+ *              comes from the same construction on the half-resolution grid (slices (0, -pw), (-pw, -(pw / 2)), (-(pw / 2), end), integer division)
+ * on the engine of innfer_net_*.  Conv slots `<state-dict key>#<p>` in forward order: conv_first; per block attn.q (ceil(nH / 2) slices: head h's d rows at 32 h, zero
+ * pads, times d^-0.5), attn.kv (ceil(C / 128) slices: k's C / 4 rows, zero-padded to 32 ceil(C / 128), then v's likewise), attn.proj (head-padded input columns), mlp.fc1,
+ * mlp.fc2; per group its conv; conv_after_body; the tail.  LayerNorms as SwinIR's.  innfer_net_set_attn_bias takes the COMPACT table of block b: [nH][(2 pw - 1)^2] floats.
+ * innfer_net_set_dwconv5: mlp.dwconv.depthwise_conv.0 of block b, taps [hidden][25] and bias [hidden].  Limits (INNFER_ERR_UNSUPPORTED): SwinIR's, window 16 | 22 | 24,
+ * embed_dim % 4 == 0; the fp16 mode only.  Launches of a forward, with S1 = C_pad / 64, SQ = ceil(nH / 2), SK = ceil(C / 128), SH = hidden_pad / 64, SR = S1 ('1conv') or
+ * 2 ceil(C / 256) + S1 ('3conv'), B blocks in R groups, T the tail's (2 pixelshuffledirect; 2 + log2(scale), 4 for scale 3, pixelshuffle; 3 + log2(scale) nearest+conv):
+ *   S1 + 2 + B (4 + SQ + SK + 2 S1 + SH) + (R + 1) SR + T + 2 [H x W is not Hp x Wp]. */
+int innfer_srformer_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int window,
+                           int upsampler, int scale, int conv3, const float* h_mean);
+int innfer_net_set_dwconv5(innfer_net_t net, int blk, const float* h_taps, const float* h_bias);
+/* (124, additive) SRFormer's permuted window attention as a single launch (for tests; csrc/win_attn_perm.hip).  d_q: num_heads head-padded groups (head h = group h: d = C /
+ * num_heads real channels, then zeros; d^-0.5 already inside); d_kv: 2 ceil(C / 128) groups -- k's C / 4 channels in natural order (zero pads), then v's; d_out: num_heads
+ * groups, channels >= d written as zeros; h_table: the compact [num_heads][(window - 1)^2] host floats.  Declared arithmetic: fp32 scores, ONE pass over the window's keys
+ * (maximum, exp, sum over the unrounded values), P rounded to fp16, fp32 accumulation, one division, one rounding.  Refused with nothing written: window not 16 | 22 | 24;
+ * Hp or Wp no multiple of it; C % 4, C % num_heads; C > 256, num_heads > 8, d > 32; a shift other than 0 or window / 2; a group stride below N Hp Wp 32. */
+int innfer_window_attention_perm(const void* d_q, int64_t q_gs, const void* d_kv, int64_t kv_gs, void* d_out, int64_t out_gs, const float* h_table, int N, int Hp, int Wp,
+                                 int C, int num_heads, int window, int shift, void* stream);
+/* (124, additive) out = fp16(x + GELU(dw5x5(x) + bias)) as a single launch (for tests; csrc/dwconv5.hip): depthwise, zero padding 2, over slabs of c_pad channels (a multiple
+ * of 32, <= 1024); fp32 accumulation from the bias with the taps row-major, the sum in fp32, one rounding.  h_taps [C][5][5], h_bias [C] host floats.  Channels >= C are
+ * written as zeros whatever d_in holds.  d_out must not overlap d_in. */
+int innfer_dwconv5x5_gelu_add(const void* d_in, int64_t in_gs, void* d_out, int64_t out_gs, int N, int H, int W, int C, int c_pad, const float* h_taps, const float* h_bias,
+                              void* stream);
 /* (123, additive) DAT (Chen et al. 2023, "Dual Aggregation Transformer for Image Super-Resolution"; the reference has no such architecture), the published dat_arch.py, on
  * SwinIR's skeleton WITHOUT padding (the engine works on H x W).  C = embed_dim, nH heads of d = C / nH, split = [s0, s1], hid = hidden, tokens = pixels:
  *   forward(x):  f = conv_first(x - mean); f = conv_after_body(norm(RGs(before_RG.1(f)))) + f; tail (pixelshuffle | pixelshuffledirect); + mean

@@ -43,6 +43,8 @@ def get_network(opt_net):
         from .DAT_arch import DAT as net
     elif kind in ('drct', 'drct_net'):
         from .DRCT_arch import DRCT as net
+    elif kind in ('srformer', 'srformer_net'):
+        from .SRFormer_arch import SRFormer as net
     else:
         raise NotImplementedError('Model [{:s}] not recognized'.format(kind))
     return net(**opt_net)

@@ -251,6 +251,25 @@ def swinir_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_head
     return s
 
 
+def srformer_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=6, mlp_ratio=2.0, upscale=4, upsampler='pixelshuffle', resi_connection='1conv', window_size=22):
+    """State-dict key -> shape of the PARAMETERS of SRFormer (Zhou et al. 2023; written down without the published source at hand -- a checkpoint's shapes are authoritative):
+    SwinIR's keys, except that a block has attn.q [C, C] and attn.kv [C / 2, C] in place of attn.qkv, a bias table of (2 pw - 1)^2 rows with pw = window_size / 2, and
+    mlp.dwconv.depthwise_conv.0 [hidden, 1, 5, 5] between mlp.fc1 and mlp.fc2.  The buffers (attn.aligned_relative_position_index, attn.relative_position_index, attn_mask)
+    are not parameters."""
+    C, hid, s = embed_dim, int(embed_dim * mlp_ratio + 1e-6), {}
+    for k, shp in swinir_shapes(in_chans, embed_dim, depths, num_heads, mlp_ratio, upscale, upsampler, resi_connection, window_size // 2).items():
+        if '.attn.qkv.' in k:
+            b, leaf = k.split('attn.qkv.')
+            s[b + 'attn.q.' + leaf] = (C, C) if leaf == 'weight' else (C,)
+            s[b + 'attn.kv.' + leaf] = (C // 2, C) if leaf == 'weight' else (C // 2,)
+            continue
+        s[k] = shp
+        if k.endswith('mlp.fc1.bias'):
+            b = k[:-len('fc1.bias')]
+            s[b + 'dwconv.depthwise_conv.0.weight'], s[b + 'dwconv.depthwise_conv.0.bias'] = (hid, 1, 5, 5), (hid,)
+    return s
+
+
 def swin2sr_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=6, mlp_ratio=2.0, upscale=4, upsampler='pixelshuffle', resi_connection='1conv', window_size=8,
                    cpb_hidden=512):
     """State-dict key -> shape of the PARAMETERS of Swin2SR (the published network_swin2sr.py; patch_size 1, qkv_bias, patch_norm, no absolute position embedding): SwinIR's

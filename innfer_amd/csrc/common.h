@@ -313,6 +313,14 @@ int win_attn16_wide_launch(const f16* qkv, long gs, f16* out, long out_gs, const
 // stay out of the statistics and are written as zeros; gamma / beta: c_pad device floats in slab order; in == out allowed
 int layer_norm_holed_launch(const f16* in, long in_gs, f16* out, long out_gs, long npix, int C, int c_end, int c_pad, const float* gamma, const float* beta, float eps, hipStream_t s);
 
+// ---- SRFormer's own kernels ----
+// permuted self-attention over ws x ws windows, ws 16 | 22 | 24 (win_attn_perm.hip): q: nH head-padded groups (scaled); kv: k's C / 4 channels in ceil(C / 128) groups in
+// natural order, then v's; out: nH head-padded groups, channels >= d written as zeros; table: the COMPACT fp32 [nH][(ws - 1)^2] relative position bias; shift 0 | ws / 2
+int win_attn_perm_launch(const f16* q, long q_gs, const f16* kv, long kv_gs, f16* out, long out_gs, const float* table, int N, int Hp, int Wp, int C, int nH, int ws, int shift,
+                         hipStream_t s);
+// out = fp16(x + GELU(dw5x5(x) + bias)) over a slab of c_pad <= 1024 channels (dwconv5.hip): taps [C][25], bias [C] device floats; out must not overlap in
+int dwconv5x5_gelu_add_launch(const f16* in, long in_gs, f16* out, long out_gs, int N, int H, int W, int C, int c_pad, const float* taps, const float* bias, hipStream_t s);
+
 // ---- layout / tiles / blend / pre-post (tiles.hip) ---------------------------
 int nchw_to_slab(const void* src, int src_f32, f16* slab, long gstride, int ch_off, int N, int C, int H, int W, hipStream_t s);
 int slab_to_nchw(const f16* slab, long gstride, int ch_off, void* dst, int dst_f32, int N, int C, int H, int W, hipStream_t s);

@@ -148,6 +148,11 @@ struct innfer_net {
     // count and MLP hidden size; sw_ln_w: the floats of gamma (and of beta) of every LayerNorm, in SLAB order (the dense slab's hole and pads included)
     int dr_r = 0;
     std::vector<int> dr_nh, dr_hid, sw_ln_w;
+    // SRFormer (kind 10; innfer_srformer_create) on SwinIR's fields on the grid padded to sf_ws (16 | 22 | 24): q and kv in two Linears into two slabs (q head-padded;
+    // k, then v, C / 4 channels each in sf_kg = ceil(C / 128) groups), sw_relb holds the COMPACT [nH][(sf_ws - 1)^2] table, sf_dw[blk] the depthwise 5 x 5 conv of the
+    // feed-forward (taps [hidden][25], then bias [hidden]; innfer_net_set_dwconv5)
+    int sf_ws = 0, sf_kg = 0;
+    std::vector<float*> sf_dw;
     bool span_norm = false;     // SPAN(norm=True): conv_1 reads (x - mean) * img_range through FirstConvLaunch.in_map (convs[0].d_map: alpha[in_nc] then shift[in_nc])
     int in_nc = 3, out_nc = 3, nf = 64, nb = 23, gc = 32, scale = 4, n_up = 2;
     int final_act = 0;           // `finalact` of the reference constructors: activation after the last conv (ConvLaunch.act codes)
@@ -391,8 +396,10 @@ static void swin_add_resi(innfer_net* net, const std::string& key) {          //
     swin_add_sliced(net, key + ".4", net->sw_cp, net->sw_c4p, 3);
 }
 static int swin_create(int kind, innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int upsampler,
-                       int scale, int conv3, const float* h_mean) {
+                       int scale, int conv3, const float* h_mean, int window = 8) {
     if (!out || !depths) return set_error(INNFER_ERR_INVALID, "swinir_create: null argument");
+    if (kind == 10 && window != 16 && window != 22 && window != 24) return set_error(INNFER_ERR_UNSUPPORTED, "srformer_create: window_size %d (built: 16, 22, 24)", window);
+    if (kind == 10 && embed_dim % 4) return set_error(INNFER_ERR_UNSUPPORTED, "srformer_create: embed_dim=%d (built: a multiple of 4 -- a key token takes C / 4 channels of four pixels)", embed_dim);
     if (embed_dim < 1 || embed_dim > 256 || num_heads < 1 || num_heads > 8 || embed_dim % num_heads || embed_dim / num_heads > 32)
         return set_error(INNFER_ERR_UNSUPPORTED, "swinir_create: embed_dim=%d num_heads=%d (built: embed_dim <= 256, <= 8 heads of <= 32 channels, embed_dim %% num_heads == 0)", embed_dim, num_heads);
     if (mlp_hidden < 1 || mlp_hidden > 1024) return set_error(INNFER_ERR_UNSUPPORTED, "swinir_create: an MLP of %d hidden channels (built: <= 1024)", mlp_hidden);
@@ -410,11 +417,16 @@ static int swin_create(int kind, innfer_net_t* out, int in_nc, int out_nc, int e
     net->sw_hid = mlp_hidden; net->sw_hp = (mlp_hidden + 63) / 64 * 64; net->sw_tail = upsampler; net->sw_conv3 = conv3 != 0;
     net->sw_c4p = (embed_dim / 4 + 63) / 64 * 64;
     net->sw_depths.assign(depths, depths + n_layers);
+    if (kind == 10) { net->sf_ws = window; net->sf_kg = (embed_dim / 4 + 31) / 32; }
     const int cp = net->sw_cp;
     for (int p = 0; p < cp / 64; ++p) add_conv(net, "conv_first#" + std::to_string(p), 64, in_nc, true);
     for (int i = 0; i < n_layers; ++i) {
         for (int j = 0; j < depths[i]; ++j) {
             const std::string b = "layers." + std::to_string(i) + ".residual_group.blocks." + std::to_string(j) + ".";
+            if (kind == 10) {      // SRFormer: q into the head-padded slab, kv into k's and v's groups
+                swin_add_sliced(net, b + "attn.q", (num_heads + 1) / 2 * 64, cp, 1);
+                swin_add_sliced(net, b + "attn.kv", net->sf_kg * 64, cp, 1);
+            } else
             swin_add_sliced(net, b + "attn.qkv", (3 * num_heads + 1) / 2 * 64, cp, 1);
             swin_add_sliced(net, b + "attn.proj", cp, 32 * num_heads, 1);
             swin_add_sliced(net, b + "mlp.fc1", net->sw_hp, cp, 1);
@@ -447,6 +459,7 @@ static int swin_create(int kind, innfer_net_t* out, int in_nc, int out_nc, int e
     net->sw_ln.assign(2 + 2 * (size_t)net->nb, nullptr);
     net->sw_relb.assign((size_t)net->nb, nullptr);
     if (kind == 7) net->sw_tau.assign((size_t)net->nb, nullptr);
+    if (kind == 10) net->sf_dw.assign((size_t)net->nb, nullptr);
     int rc = INNFER_OK;
     {   // x - mean in front of conv_first (img_range 1): the input map of every slice of the first conv, held by slice 0; nn.LeakyReLU() (slope 0.01) behind conv_before_upsample
         float h[8];
@@ -474,6 +487,24 @@ extern "C" int innfer_swinir_create(innfer_net_t* out, int in_nc, int out_nc, in
 extern "C" int innfer_swin2sr_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int upsampler,
                                      int scale, int conv3, const float* h_mean) {
     return swin_create(7, out, in_nc, out_nc, embed_dim, depths, n_layers, num_heads, mlp_hidden, upsampler, scale, conv3, h_mean);
+}
+
+// SRFormer (Zhou et al. 2023; include/innfer_amd.h carries the definition): SwinIR's skeleton, LayerNorm numbering, tails and workspace on windows of 16 | 22 | 24; the block
+// is t = t + proj(PSA(norm1(t))), t = t + fc2(h + GELU(dw5x5(h))), h = GELU(fc1(norm2(t))).  Conv slots per block: attn.q, attn.kv, attn.proj, mlp.fc1, mlp.fc2.
+extern "C" int innfer_srformer_create(innfer_net_t* out, int in_nc, int out_nc, int embed_dim, const int* depths, int n_layers, int num_heads, int mlp_hidden, int window,
+                                      int upsampler, int scale, int conv3, const float* h_mean) {
+    return swin_create(10, out, in_nc, out_nc, embed_dim, depths, n_layers, num_heads, mlp_hidden, upsampler, scale, conv3, h_mean, window);
+}
+// mlp.dwconv.depthwise_conv.0 of block `blk` of an SRFormer: taps [hidden][25] and bias [hidden], host floats.  Load time, synchronous.
+extern "C" int innfer_net_set_dwconv5(innfer_net_t net, int blk, const float* h_taps, const float* h_bias) {
+    if (!net || !h_taps || !h_bias) return set_error(INNFER_ERR_INVALID, "set_dwconv5: null argument");
+    if (net->kind != 10) return set_error(INNFER_ERR_UNSUPPORTED, "set_dwconv5: the network has no depthwise 5 x 5 conv (built: SRFormer)");
+    if (blk < 0 || blk >= (int)net->sf_dw.size()) return set_error(INNFER_ERR_INVALID, "set_dwconv5: block %d of %zu", blk, net->sf_dw.size());
+    const size_t hid = (size_t)net->sw_hid;
+    if (!net->sf_dw[blk]) INNFER_HIP(hipMalloc((void**)&net->sf_dw[blk], 26 * hid * sizeof(float)));
+    INNFER_HIP(hipMemcpy(net->sf_dw[blk], h_taps, 25 * hid * sizeof(float), hipMemcpyHostToDevice));
+    INNFER_HIP(hipMemcpy(net->sf_dw[blk] + 25 * hid, h_bias, hid * sizeof(float), hipMemcpyHostToDevice));
+    return INNFER_OK;
 }
 
 // DRCT's widths: gx = ceil(C / 32) groups of x; block k = 0 .. 4 of a dense group reads ng[k] = gx + k groups (cpk[k] = 32 ng[k] channels: what a matrix product reads),
@@ -570,7 +601,7 @@ extern "C" int innfer_drct_create(innfer_net_t* out, int in_nc, int out_nc, int 
 // groups), the last one norm.  Load time, synchronous.
 extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float* h_gamma, const float* h_beta) {
     if (!net || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "set_layer_norm: null argument");
-    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8 && net->kind != 9) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR, HAT, Swin2SR, DAT, DRCT)");
+    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8 && net->kind != 9 && net->kind != 10) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR, HAT, Swin2SR, DAT, DRCT, SRFormer)");
     if (idx < 0 || idx >= (int)net->sw_ln.size()) return set_error(INNFER_ERR_INVALID, "set_layer_norm: index %d of %zu", idx, net->sw_ln.size());
     if (net->kind == 9) {        // DRCT: sw_ln_w[idx] floats each, already in the slab order of the tensor the norm reads (zeros at the hole and the pads)
         const size_t wdt = (size_t)net->sw_ln_w[idx];
@@ -591,13 +622,22 @@ extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float*
 // The relative position bias of block `blk` of a SwinIR as the dense table the attention reads: [num_heads][64 query][64 key] host floats.  Load time, synchronous.
 extern "C" int innfer_net_set_attn_bias(innfer_net_t net, int blk, const float* h_bias) {
     if (!net || !h_bias) return set_error(INNFER_ERR_INVALID, "set_attn_bias: null argument");
-    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8 && net->kind != 9) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_bias: the network has no window attention (built: SwinIR, HAT, Swin2SR, DAT, DRCT)");
+    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8 && net->kind != 9 && net->kind != 10) return set_error(INNFER_ERR_UNSUPPORTED, "set_attn_bias: the network has no window attention (built: SwinIR, HAT, Swin2SR, DAT, DRCT, SRFormer)");
     if (blk < 0 || blk >= (int)net->sw_relb.size()) return set_error(INNFER_ERR_INVALID, "set_attn_bias: block %d of %zu", blk, net->sw_relb.size());
     // (HAT: table `blk` in forward order -- [num_heads][256][256] of a HAB, [num_heads][256][576] of a residual group's OCAB)
     // (DAT: [num_heads][T][T], T = s0 s1, of an even block; the odd blocks take none)
     const size_t dat_t = (size_t)net->dat_s0 * net->dat_s1;
     // (DRCT: [nH_blk][256][256] with the block's own head count)
-    const size_t nb = net->kind == 9 ? (size_t)net->dr_nh[blk] * 65536 * sizeof(float) : (size_t)net->sw_nh * (net->kind == 6 ? 256 * (size_t)net->sw_relb_kw[blk] * net->sw_relb_kw[blk] : net->kind == 8 ? dat_t * dat_t : 4096) * sizeof(float);
+    // (SRFormer: the COMPACT table [num_heads][(ws - 1)^2] -- the attention gathers from it)
+    size_t per_head = 4096;          // floats of one head's table: SwinIR, Swin2SR [64][64]
+    int heads = net->sw_nh;
+    switch (net->kind) {
+        case 6: per_head = 256 * (size_t)net->sw_relb_kw[blk] * net->sw_relb_kw[blk]; break;
+        case 8: per_head = dat_t * dat_t; break;
+        case 9: per_head = 65536; heads = net->dr_nh[blk]; break;
+        case 10: per_head = (size_t)(net->sf_ws - 1) * (net->sf_ws - 1); break;
+    }
+    const size_t nb = (size_t)heads * per_head * sizeof(float);
     if (!net->sw_relb[blk]) INNFER_HIP(hipMalloc((void**)&net->sw_relb[blk], nb));
     INNFER_HIP(hipMemcpy(net->sw_relb[blk], h_bias, nb, hipMemcpyHostToDevice));
     return INNFER_OK;
@@ -863,6 +903,7 @@ extern "C" void innfer_net_destroy(innfer_net_t net) {
     for (float* q : net->sw_tau) if (q) (void)hipFree(q);
     for (float* q : net->hat_ca) if (q) (void)hipFree(q);
     for (float* q : net->dat_blk) if (q) (void)hipFree(q);
+    for (float* q : net->sf_dw) if (q) (void)hipFree(q);
     for (auto& c : net->convs) {
         if (c.d_w) (void)hipFree(c.d_w);
         if (c.d_b) (void)hipFree(c.d_b);
@@ -1028,6 +1069,7 @@ extern "C" int innfer_net_set_precision(innfer_net_t net, int fp32) {
     if (fp32 && net->kind == 7) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: Swin2SR is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 8) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: DAT is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 9) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: DRCT is built for the fp16 mode only (no fp32-accurate engine)");
+    if (fp32 && net->kind == 10) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SRFormer is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32) {
         // The (wl | wh | wh) panels of every loaded conv are built HERE -- a load-time call, with its hipMalloc and synchronous copies -- never inside
         // innfer_net_forward (stream capture, concurrent callers).  Idempotent: a conv that already has its panels is skipped; innfer_net_set_conv
@@ -1114,6 +1156,13 @@ extern "C" double innfer_net_flops(innfer_net_t net, int N, int H, int W) {
         for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
         return f;
     }
+    if (net->kind == 10) {       // SRFormer: every conv on the grid padded to the window; ws^2 x ws^2 / 4 scores per window and head; 25 taps per hidden channel
+        const int wsz = net->sf_ws;
+        const double px = (double)N * ((H + wsz - 1) / wsz * wsz) * ((W + wsz - 1) / wsz * wsz);
+        double f = (double)net->nb * (net->sw_nh * px * 4.0 * (wsz * wsz / 4) * 32 + 50.0 * net->sw_hid * px);
+        for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
+        return f;
+    }
     if (net->kind == 9) {        // DRCT: as HAT's grid; per block the two products of every window and head on its real head width
         const double px = (double)N * ((H + 15) / 16 * 16) * ((W + 15) / 16 * 16);
         double f = 0.0;
@@ -1168,7 +1217,7 @@ struct Carve {
 struct SwinCarve { size_t xin, f0, r[2], t, u, qkv, att, hid, c4[2], b64, up[2], hr, outp, zc, z, y, pool, gram, amat, total; int Hp, Wp; };
 static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
     SwinCarve c{};
-    const int wsz = net->kind == 6 || net->kind == 9 ? 16 : net->kind == 8 ? 1 : 8;          // (DAT works on H x W itself)
+    const int wsz = net->kind == 10 ? net->sf_ws : net->kind == 6 || net->kind == 9 ? 16 : net->kind == 8 ? 1 : 8;          // (DAT works on H x W itself)
     c.Hp = (H + wsz - 1) / wsz * wsz; c.Wp = (W + wsz - 1) / wsz * wsz;
     const size_t px = (size_t)N * c.Hp * c.Wp, s2 = (size_t)net->scale * net->scale;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -1188,7 +1237,8 @@ static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
     c.r[0] = take(px * net->sw_cp * 2); c.r[1] = take(px * net->sw_cp * 2);
     c.t = take(px * net->sw_cp * 2);
     c.u = take(px * net->sw_cp * 2);
-    c.qkv = take(px * ((3 * net->sw_nh + 1) / 2 * 64) * 2);
+    // (SRFormer: the q slab -- an even count of groups, a launch writes two --, then the kv slab)
+    c.qkv = take(px * (net->kind == 10 ? (net->sw_nh + 1) / 2 * 64 + net->sf_kg * 64 : (3 * net->sw_nh + 1) / 2 * 64) * 2);
     c.att = take(px * 32 * net->sw_nh * 2);
     c.hid = take(px * net->sw_hp * 2);
     }
@@ -1207,6 +1257,7 @@ static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
         c.y = take((size_t)N * net->sw_cp * 4);
         c.pool = take(ca_work_floats(N, (long)c.Hp * c.Wp, net->sw_cp) * 4);
     }
+    if (net->kind == 10) c.z = take(px * net->sw_hp * 2);        // SRFormer: h + GELU(dw5x5(h)), what fc2 reads
     if (net->kind == 8) {        // DAT: c = GELU(dwconv(v)) (head-padded), the normalised second half of the feed-forward, the per-channel gate, the pool's and the Gram's segment records, A
         c.z = take(px * 32 * net->sw_nh * 2);
         c.zc = take(px * net->dat_h1p * 2);
@@ -1221,7 +1272,7 @@ static SwinCarve swin_carve(const innfer_net* net, int N, int H, int W) {
 
 static Carve carve(const innfer_net* net, int N, int H, int W) {
     Carve c{};
-    if (net->kind == 5 || net->kind == 6 || net->kind == 7 || net->kind == 8 || net->kind == 9) { c.total = swin_carve(net, N, H, W).total; return c; }
+    if (net->kind == 5 || net->kind == 6 || net->kind == 7 || net->kind == 8 || net->kind == 9 || net->kind == 10) { c.total = swin_carve(net, N, H, W).total; return c; }
     const size_t px = (size_t)N * H * W;
     auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     if (net->kind == 2) {        // SRVGGNetCompact: the two ping-pong feature slabs (one when there is no nf -> nf conv) and the last conv's 32- / 64-channel slab
@@ -1764,6 +1815,8 @@ static int swinir_forward(innfer_net* net, const void* d_in, int in_dtype, void*
         if (!net->sw_relb[i] && !(net->kind == 8 && net->dat_aca[i])) return set_error(INNFER_ERR_INVALID, "forward: the relative position bias of block %zu was never set (innfer_net_set_attn_bias)", i);
     for (size_t i = 0; i < net->sw_tau.size(); ++i)
         if (!net->sw_tau[i]) return set_error(INNFER_ERR_INVALID, "forward: the attention scale of block %zu was never set (innfer_net_set_attn_scale)", i);
+    for (size_t i = 0; i < net->sf_dw.size(); ++i)
+        if (!net->sf_dw[i]) return set_error(INNFER_ERR_INVALID, "forward: the depthwise conv of block %zu was never set (innfer_net_set_dwconv5)", i);
     const SwinCarve cv = swin_carve(net, N, H, W);
     const int Hp = cv.Hp, Wp = cv.Wp, sc = net->scale, cp = net->sw_cp, nh = net->sw_nh;
     if (Hp - H >= H || Wp - W >= W) return set_error(INNFER_ERR_INVALID, "forward: %d x %d cannot be reflect-padded to %d x %d (the pad must be smaller than the side)", H, W, Hp, Wp);
@@ -1978,6 +2031,32 @@ static int swinir_forward(innfer_net* net, const void* d_in, int in_dtype, void*
             if (int rc = resi(t, r[cur ^ 1], r[cur])) return rc;
             cur ^= 1;
         }
+    } else if (net->kind == 10) {
+        // SRFormer: per block  u = LN(t); q (SQ = ceil(nH / 2) launches) and kv (SK = ceil(C / 128) launches) from u into their two slabs; the permuted window attention
+        // (shift ws / 2 for odd j); proj + shortcut; u = LN(t); h = fc1 with GELU; z = h + GELU(dw5x5(h)); fc2 from z + shortcut (in place): 4 + SQ + SK + 2 S1 + SH launches.
+        const int wsz = net->sf_ws, sq = (nh + 1) / 2, hd = net->sw_hid;
+        f16* kvs = qkv + 2L * sq * G;
+        f16* z = (f16*)(ws + cv.z);
+        for (size_t i = 0; i < net->sw_depths.size(); ++i) {
+            for (int j = 0; j < net->sw_depths[i]; ++j, ++blk) {
+                const f16* x = j == 0 ? r[cur] : t;
+                if (int rc = norm(1 + 2 * blk, x, u)) return rc;
+                if (int rc = sliced(sq, u, qkv, 0, nullptr)) return rc;
+                if (int rc = sliced(net->sf_kg, u, kvs, 0, nullptr)) return rc;
+                // launch kind 8001: the window attention -- bytes: q in, o out (32-channel head groups), k and v (a quarter of the pixels' channels each), the compact table
+                if (int rc = plksr_pass(s, "window_attention_perm", 1.0 * wsz * wsz * 32 * nh * px, px * nh * 160.0 + nh * 4.0 * (wsz - 1) * (wsz - 1), 8001, [&] {
+                        return win_attn_perm_launch(qkv, G, kvs, G, att, G, net->sw_relb[blk], N, Hp, Wp, net->sw_c, nh, wsz, (j & 1) ? wsz / 2 : 0, s); })) return rc;
+                if (int rc = sliced(cp / 64, att, t, 0, x)) return rc;
+                if (int rc = norm(2 + 2 * blk, t, u)) return rc;
+                if (int rc = sliced(net->sw_hp / 64, u, hid, 12, nullptr)) return rc;
+                // launch kind 8013: the depthwise conv -- bytes: the hidden slab in and out
+                if (int rc = plksr_pass(s, "dwconv5_gelu_add", 50.0 * hd * px, 4.0 * net->sw_hp * px, 8013, [&] {
+                        return dwconv5x5_gelu_add_launch(hid, G, z, G, N, Hp, Wp, hd, net->sw_hp, net->sf_dw[blk], net->sf_dw[blk] + 25L * hd, s); })) return rc;
+                if (int rc = sliced(cp / 64, z, t, 0, t)) return rc;
+            }
+            if (int rc = resi(t, r[cur ^ 1], r[cur])) return rc;
+            cur ^= 1;
+        }
     } else if (net->kind == 7) {
         // Swin2SR: per block  qkv from the token stream itself; the cosine window attention; u = proj (no shortcut); t = x + LN(u) (one launch; x the group's input r for
         // its first block, else t in place); fc1 with GELU from t; u = fc2; t = t + LN(u).  The same launch count as SwinIR's block: 3 + SQ + 2 S1 + SH.
@@ -2139,7 +2218,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     if (!d_ws || ws_bytes < cv.total) return set_error(INNFER_ERR_WORKSPACE, "forward: workspace %zu < %zu bytes", d_ws ? ws_bytes : (size_t)0, cv.total);          // (short or missing, as innfer_pan_attention's)
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)d_ws;
-    if (net->kind == 5 || net->kind == 6 || net->kind == 7 || net->kind == 8 || net->kind == 9) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);
+    if (net->kind == 5 || net->kind == 6 || net->kind == 7 || net->kind == 8 || net->kind == 9 || net->kind == 10) return swinir_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, s);
     if (net->kind == 2) return compact_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 3) return span_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 4) return plksr_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);

@@ -65,7 +65,9 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
     if arch == 'realplksr':
         return _infer_realplksr(state_dict)
     if arch == 'swinir':
-        hat = _infer_hat(state_dict)         # (a complete HAT key set; anything less goes on to SwinIR's sniffing and its refusals)
+        if all(_SRFORMER_B0 + k in state_dict for k in _SRFORMER_KEYS):      # (block 0's complete SRFormer key set; anything less goes on as before)
+            return _infer_srformer(state_dict)
+        hat = _infer_hat(state_dict)        # (a complete HAT key set; anything less goes on to SwinIR's sniffing and its refusals)
         if hat is not None:
             return hat
         s2 = _infer_swin2sr(state_dict)      # (likewise: block 0's complete Swin2SR key set)
@@ -278,6 +280,84 @@ def _infer_swinir(state_dict):
     cfg = {'type': 'swinir', 'in_nc': in_nc, 'nf': C, 'depths': depths, 'num_heads': [nh] * len(depths), 'window_size': ws, 'mlp_ratio': hidden / C, 'scale': up,
            'upsampler': upsampler, 'resi_connection': '3conv' if 'layers.0.conv.0.weight' in state_dict else '1conv'}
     return dict(arch='swinir', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=sum(depths), plus=False, state_dict=state_dict,
+                net_params=get_network_G_config(cfg, up))
+
+
+_SRFORMER_B0 = 'layers.0.residual_group.blocks.0.'
+_SRFORMER_KEYS = ('attn.q.weight', 'attn.kv.weight', 'mlp.dwconv.depthwise_conv.0.weight')
+
+
+def _infer_srformer(state_dict):
+    """SRFormer checkpoints (light, classical, real-world).  Everything is read off the shapes: embed_dim and in_chans from conv_first, depths by counting blocks, num_heads and
+    the window from the bias table ([(2 pw - 1)^2, nH]: 225 / 441 / 529 rows are windows of 16 / 22 / 24), hidden from mlp.fc1, the tail and the scale as _infer_swinir
+    reads them.  The buffers (attn.aligned_relative_position_index, attn.relative_position_index, attn_mask) are dropped; a stored aligned index that differs from the
+    formula the engine's bias gather restates is refused.  Other windows, an absolute position embedding, the '' upsampler, hidden > 1024 and unequal channel counts are
+    refused here, before anything touches the GPU."""
+    import math
+    b0 = _SRFORMER_B0
+    if 'absolute_pos_embed' in state_dict:
+        raise NotImplementedError('SRFormer checkpoint with absolute_pos_embed (ape=True): not built on the HIP path')
+    for k in ('attn.relative_position_bias_table', 'attn.q.bias', 'attn.kv.bias', 'mlp.fc1.weight'):
+        if b0 + k not in state_dict:
+            raise NotImplementedError(f'SRFormer checkpoint without {k}: not built on the HIP path')
+    if 'patch_embed.norm.weight' not in state_dict:
+        raise NotImplementedError('SRFormer checkpoint without patch_embed.norm (patch_norm=False): not built on the HIP path')
+    w0 = state_dict['conv_first.weight']
+    C, in_nc = int(w0.shape[0]), int(w0.shape[1])
+    depths = []
+    while f'layers.{len(depths)}.residual_group.blocks.0.norm1.weight' in state_dict:
+        i, j = len(depths), 0
+        while f'layers.{i}.residual_group.blocks.{j}.norm1.weight' in state_dict:
+            j += 1
+        depths.append(j)
+    table = state_dict[b0 + 'attn.relative_position_bias_table']
+    nh, rows = int(table.shape[1]), int(table.shape[0])
+    ws = {225: 16, 441: 22, 529: 24}.get(rows)
+    if ws is None:
+        side = math.isqrt(rows)
+        raise NotImplementedError(f'SRFormer checkpoint with window_size {side + 1 if side * side == rows else "?"} (a bias table of {rows} rows): windows of 16, 22 and 24 '
+                                  f'(225, 441, 529 rows) are built on the HIP path')
+    if tuple(state_dict[b0 + 'attn.q.weight'].shape) != (C, C) or tuple(state_dict[b0 + 'attn.kv.weight'].shape) != (C // 2, C) or C % 4:
+        raise NotImplementedError(f'SRFormer checkpoint: attn.q {tuple(state_dict[b0 + "attn.q.weight"].shape)} / attn.kv {tuple(state_dict[b0 + "attn.kv.weight"].shape)} on '
+                                  f'{C} channels (built on the HIP path: [C, C] and [C / 2, C], C a multiple of 4)')
+    if not (C <= 256 and 1 <= nh <= 8 and C % nh == 0 and C // nh <= 32):
+        raise NotImplementedError(f'SRFormer checkpoint with {nh} heads on {C} channels (built on the HIP path: embed_dim <= 256, <= 8 heads of <= 32 channels)')
+    hidden = int(state_dict[b0 + 'mlp.fc1.weight'].shape[0])
+    if hidden > 1024:
+        raise NotImplementedError(f'SRFormer checkpoint with an MLP of {hidden} hidden channels (built on the HIP path: hidden <= 1024)')
+    if 'conv_up1.weight' in state_dict:
+        upsampler, up = 'nearest+conv', 4 if 'conv_up2.weight' in state_dict else 2
+        out_nc = int(state_dict['conv_last.weight'].shape[0])
+    elif 'conv_before_upsample.0.weight' in state_dict:
+        upsampler, up = 'pixelshuffle', 1
+        for k, v in state_dict.items():
+            if k.startswith('upsample.') and k.endswith('.weight'):
+                f = math.isqrt(int(v.shape[0]) // 64)
+                if f * f * 64 != int(v.shape[0]):
+                    raise Exception("Could not infer model parameters.")
+                up *= f
+        out_nc = int(state_dict['conv_last.weight'].shape[0])
+    elif 'upsample.0.weight' in state_dict:
+        upsampler = 'pixelshuffledirect'
+        k_up = int(state_dict['upsample.0.weight'].shape[0])
+        up = math.isqrt(k_up // in_nc) if k_up % in_nc == 0 else 0
+        if up * up * in_nc != k_up:
+            raise NotImplementedError(f'SRFormer checkpoint: upsample.0 has {k_up} channels, not in_chans ({in_nc}) times a square (unequal channel counts are not built on the HIP path)')
+        out_nc = in_nc
+    else:
+        raise NotImplementedError("SRFormer checkpoint without an upsampler (upsampler '': the denoising / JPEG form): only the super-resolution forms are built on the HIP path")
+    if out_nc != in_nc:
+        raise NotImplementedError(f'SRFormer checkpoint: conv_last has {out_nc} channels, conv_first takes {in_nc} (unequal channel counts are not built on the HIP path)')
+    from .architectures.SRFormer_arch import aligned_relative_position_index
+    want = aligned_relative_position_index(ws)
+    for k in [k for k in state_dict if k.endswith('attn.aligned_relative_position_index')]:
+        v = state_dict[k]
+        if tuple(v.shape) != tuple(want.shape) or not bool((v.cpu().long() == want).all()):
+            raise NotImplementedError(f'SRFormer checkpoint: {k} differs from (r // 2 - py + pw - 1)(2 pw - 1) + (c // 2 - px + pw - 1), the index the engine gathers its bias with')
+    state_dict = {k: v for k, v in state_dict.items() if not (k.endswith('attn.aligned_relative_position_index') or k.endswith('attn.relative_position_index') or k.endswith('.attn_mask'))}
+    cfg = {'type': 'srformer', 'in_nc': in_nc, 'nf': C, 'depths': depths, 'num_heads': [nh] * len(depths), 'window_size': ws, 'mlp_ratio': hidden / C, 'scale': up,
+           'upsampler': upsampler, 'resi_connection': '3conv' if 'layers.0.conv.0.weight' in state_dict else '1conv'}
+    return dict(arch='srformer', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=sum(depths), plus=False, state_dict=state_dict,
                 net_params=get_network_G_config(cfg, up))
 
 
