@@ -45,6 +45,8 @@ def get_network(opt_net):
         from .DRCT_arch import DRCT as net
     elif kind in ('srformer', 'srformer_net'):
         from .SRFormer_arch import SRFormer as net
+    elif kind in ('safmn', 'safmn_net'):
+        from .SAFMN_arch import SAFMN as net
     else:
         raise NotImplementedError('Model [{:s}] not recognized'.format(kind))
     return net(**opt_net)

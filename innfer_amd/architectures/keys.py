@@ -270,6 +270,24 @@ def srformer_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_he
     return s
 
 
+def safmn_shapes(dim=36, n_blocks=8, ffn_scale=2.0, upscaling_factor=4, in_chans=3):
+    """State-dict key -> shape of SAFMN (Sun et al. 2023; the published safmn_arch.py with BasicSR's key names): to_feat, per AttBlock norm1 / norm2 (LayerNorm over the
+    channels), safm.mfr.0 .. 3 (depthwise 3 x 3 on dim / 4 channels each), safm.aggr (1 x 1), ccm.ccm.0 (3 x 3, dim -> int(dim ffn_scale)) and ccm.ccm.2 (1 x 1), to_img.0."""
+    hid, chunk, s = int(dim * ffn_scale + 1e-6), dim // 4, {}
+    s['to_feat.weight'], s['to_feat.bias'] = (dim, in_chans, 3, 3), (dim,)
+    for b in range(n_blocks):
+        k = f'feats.{b}.'
+        for n in ('norm1', 'norm2'):
+            s[k + n + '.weight'], s[k + n + '.bias'] = (dim,), (dim,)
+        for i in range(4):
+            s[k + f'safm.mfr.{i}.weight'], s[k + f'safm.mfr.{i}.bias'] = (chunk, 1, 3, 3), (chunk,)
+        s[k + 'safm.aggr.weight'], s[k + 'safm.aggr.bias'] = (dim, dim, 1, 1), (dim,)
+        s[k + 'ccm.ccm.0.weight'], s[k + 'ccm.ccm.0.bias'] = (hid, dim, 3, 3), (hid,)
+        s[k + 'ccm.ccm.2.weight'], s[k + 'ccm.ccm.2.bias'] = (dim, hid, 1, 1), (dim,)
+    s['to_img.0.weight'], s['to_img.0.bias'] = (in_chans * upscaling_factor ** 2, dim, 3, 3), (in_chans * upscaling_factor ** 2,)
+    return s
+
+
 def swin2sr_shapes(in_chans=3, embed_dim=180, depths=(6, 6, 6, 6, 6, 6), num_heads=6, mlp_ratio=2.0, upscale=4, upsampler='pixelshuffle', resi_connection='1conv', window_size=8,
                    cpb_hidden=512):
     """State-dict key -> shape of the PARAMETERS of Swin2SR (the published network_swin2sr.py; patch_size 1, qkv_bias, patch_norm, no absolute position embedding): SwinIR's

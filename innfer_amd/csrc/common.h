@@ -321,6 +321,16 @@ int win_attn_perm_launch(const f16* q, long q_gs, const f16* kv, long kv_gs, f16
 // out = fp16(x + GELU(dw5x5(x) + bias)) over a slab of c_pad <= 1024 channels (dwconv5.hip): taps [C][25], bias [C] device floats; out must not overlap in
 int dwconv5x5_gelu_add_launch(const f16* in, long in_gs, f16* out, long out_gs, int N, int H, int W, int C, int c_pad, const float* taps, const float* bias, hipStream_t s);
 
+// ---- SAFMN's own kernel (safm.hip) ----
+// out = fp16(t + GELU(aggr(cat(s_0 .. s_3)) + b) * u) over slabs of c_pad <= 256 channels, dim of them real: the four-level max-pool / depthwise 3 x 3 / nearest pyramid,
+// the 1 x 1 aggregation and the gate as one launch.  wq / ab: safm_pack's fp16 [kp][kp] rows and fp32 [kp] bias for kp = safm_kp(c_pad); mfr: taps [dim][9], then bias
+// [dim]; all on the device.  out may be t, must not overlap u
+int safm_kp(int c_pad);
+void safm_pack(const float* w, const float* b, int dim, int kp, f16* wq, float* ab);
+int safm_launch(const f16* u, long u_gs, const f16* t, long t_gs, f16* out, long out_gs, int N, int H, int W, int dim, int c_pad, const f16* wq, const float* ab,
+                const float* mfr, hipStream_t s);
+int slab_add_launch(const f16* a, const f16* b, f16* out, long n, hipStream_t s);          // out = fp16(a + b) over n halfs (a multiple of 8)
+
 // ---- layout / tiles / blend / pre-post (tiles.hip) ---------------------------
 int nchw_to_slab(const void* src, int src_f32, f16* slab, long gstride, int ch_off, int N, int C, int H, int W, hipStream_t s);
 int slab_to_nchw(const f16* slab, long gstride, int ch_off, void* dst, int dst_f32, int N, int C, int H, int W, hipStream_t s);

@@ -113,6 +113,7 @@ struct ConvSlot {
     bool lane_rows = false;      // attn.f.0: a 64-output conv whose epilogue is the gate act 5 -- a form of the lane-contiguous panels only, so d_w is never packed in the plane row order
     bool gn_ok = false;          // refine: GroupNorm(groups, 64) follows it -- d_gn: gamma[64] then beta[64] (innfer_net_set_group_norm)
     float* d_gn = nullptr;
+    bool safm = false;           // SAFMN's safm.aggr [dim, dim, 1, 1]: d_w is safm_pack's fp16 [KP][KP] rows, d_b its [KP] bias -- read by csrc/safm.hip, never by the conv kernel
     // SwinIR (kind 5)
     float mult = 1.f;            // pixels this conv runs on per pixel of the padded LR grid (the tail's convs behind an upsampling stage): innfer_net_flops
 };
@@ -153,6 +154,9 @@ struct innfer_net {
     // feed-forward (taps [hidden][25], then bias [hidden]; innfer_net_set_dwconv5)
     int sf_ws = 0, sf_kg = 0;
     std::vector<float*> sf_dw;
+    // SAFMN (kind 11; innfer_safmn_create) on SwinIR's fields sw_c / sw_cp / sw_hid / sw_hp / sw_ln on the UNPADDED grid: nb AttBlocks, sm_mfr[blk] the four depthwise
+    // 3 x 3 convs of block blk's SAFM as one array (taps [dim][9], then bias [dim]; innfer_net_set_safm)
+    std::vector<float*> sm_mfr;
     bool span_norm = false;     // SPAN(norm=True): conv_1 reads (x - mean) * img_range through FirstConvLaunch.in_map (convs[0].d_map: alpha[in_nc] then shift[in_nc])
     int in_nc = 3, out_nc = 3, nf = 64, nb = 23, gc = 32, scale = 4, n_up = 2;
     int final_act = 0;           // `finalact` of the reference constructors: activation after the last conv (ConvLaunch.act codes)
@@ -507,6 +511,48 @@ extern "C" int innfer_net_set_dwconv5(innfer_net_t net, int blk, const float* h_
     return INNFER_OK;
 }
 
+// SAFMN (Sun et al. 2023; include/innfer_amd.h carries the definition): to_feat, nb AttBlocks t = t + safm(norm1(t)), t = t + ccm(norm2(t)), the global skip, to_img.0 with
+// PixelShuffle as the tail's store.  Conv slots: to_feat#p; per block safm.aggr (csrc/safm.hip's operand), ccm.ccm.0#p (3 x 3, GELU), ccm.ccm.2#p (1 x 1); to_img.0.
+extern "C" int innfer_safmn_create(innfer_net_t* out, int in_nc, int out_nc, int dim, int n_blocks, int hidden, int scale) {
+    if (!out) return set_error(INNFER_ERR_INVALID, "safmn_create: null argument");
+    if (dim < 8 || dim > 256 || dim % 4) return set_error(INNFER_ERR_UNSUPPORTED, "safmn_create: dim=%d (built: a multiple of 4 in 8 .. 256 -- four levels of dim / 4 channels)", dim);
+    if (hidden < 1 || hidden > 1024) return set_error(INNFER_ERR_UNSUPPORTED, "safmn_create: a feed-forward of %d hidden channels (built: 1 .. 1024)", hidden);
+    if (in_nc < 1 || in_nc > 4 || in_nc != out_nc) return set_error(INNFER_ERR_UNSUPPORTED, "safmn_create: %d input, %d output channels (built: equal, 1..4)", in_nc, out_nc);
+    if (scale < 1 || scale > 4) return set_error(INNFER_ERR_UNSUPPORTED, "safmn_create: scale %d (built: 1 .. 4)", scale);
+    if (n_blocks < 1 || n_blocks > 256) return set_error(INNFER_ERR_UNSUPPORTED, "safmn_create: %d blocks", n_blocks);
+    innfer_net* net = new innfer_net();
+    net->kind = 11; net->in_nc = in_nc; net->out_nc = out_nc; net->nf = 64; net->nb = n_blocks; net->gc = 0; net->scale = scale; net->n_up = 0;
+    net->sw_c = dim; net->sw_cp = (dim + 63) / 64 * 64; net->sw_hid = hidden; net->sw_hp = (hidden + 63) / 64 * 64; net->sw_tail = 1;
+    const int cp = net->sw_cp;
+    for (int p = 0; p < cp / 64; ++p) add_conv(net, "to_feat#" + std::to_string(p), 64, in_nc, true);
+    for (int b = 0; b < n_blocks; ++b) {
+        const std::string k = "feats." + std::to_string(b) + ".";
+        add_conv(net, k + "safm.aggr", dim, dim, false, 1);
+        net->convs.back().safm = true;
+        const size_t first = net->convs.size();
+        swin_add_sliced(net, k + "ccm.ccm.0", net->sw_hp, cp, 3);
+        for (size_t i = first; i < net->convs.size(); ++i) net->convs[i].lane_rows = true;          // (act 13 is an epilogue of the lane-contiguous panels only)
+        swin_add_sliced(net, k + "ccm.ccm.2", cp, net->sw_hp, 1);
+    }
+    add_conv(net, "to_img.0", out_nc * scale * scale, cp);
+    net->convs.back().Kp = out_nc * scale * scale <= 32 ? 32 : 64;
+    net->sw_ln.assign(2 * (size_t)n_blocks, nullptr);
+    net->sm_mfr.assign((size_t)n_blocks, nullptr);
+    *out = net;
+    return INNFER_OK;
+}
+// safm.mfr.0 .. 3 of block `blk` of a SAFMN, concatenated in channel order: taps [dim][9] and bias [dim], host floats.  Load time, synchronous.
+extern "C" int innfer_net_set_safm(innfer_net_t net, int blk, const float* h_taps, const float* h_bias) {
+    if (!net || !h_taps || !h_bias) return set_error(INNFER_ERR_INVALID, "set_safm: null argument");
+    if (net->kind != 11) return set_error(INNFER_ERR_UNSUPPORTED, "set_safm: the network has no feature modulation (built: SAFMN)");
+    if (blk < 0 || blk >= (int)net->sm_mfr.size()) return set_error(INNFER_ERR_INVALID, "set_safm: block %d of %zu", blk, net->sm_mfr.size());
+    const size_t dim = (size_t)net->sw_c;
+    if (!net->sm_mfr[blk]) INNFER_HIP(hipMalloc((void**)&net->sm_mfr[blk], 10 * dim * sizeof(float)));
+    INNFER_HIP(hipMemcpy(net->sm_mfr[blk], h_taps, 9 * dim * sizeof(float), hipMemcpyHostToDevice));
+    INNFER_HIP(hipMemcpy(net->sm_mfr[blk] + 9 * dim, h_bias, dim * sizeof(float), hipMemcpyHostToDevice));
+    return INNFER_OK;
+}
+
 // DRCT's widths: gx = ceil(C / 32) groups of x; block k = 0 .. 4 of a dense group reads ng[k] = gx + k groups (cpk[k] = 32 ng[k] channels: what a matrix product reads),
 // lp[k] = cpk[k] rounded up to 64 (what a LayerNorm covers and a chain of 64-output launches writes); per block b the head groups G = ceil(d / 32), nH G groups of q
 struct DrctDims { int gx, ng[5], cpk[5], lp[5], dense_groups, max_sq, max_hg, max_hp; };
@@ -601,7 +647,7 @@ extern "C" int innfer_drct_create(innfer_net_t* out, int in_nc, int out_nc, int 
 // groups), the last one norm.  Load time, synchronous.
 extern "C" int innfer_net_set_layer_norm(innfer_net_t net, int idx, const float* h_gamma, const float* h_beta) {
     if (!net || !h_gamma || !h_beta) return set_error(INNFER_ERR_INVALID, "set_layer_norm: null argument");
-    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8 && net->kind != 9 && net->kind != 10) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR, HAT, Swin2SR, DAT, DRCT, SRFormer)");
+    if (net->kind != 5 && net->kind != 6 && net->kind != 7 && net->kind != 8 && net->kind != 9 && net->kind != 10 && net->kind != 11) return set_error(INNFER_ERR_UNSUPPORTED, "set_layer_norm: the network has no LayerNorm (built: SwinIR, HAT, Swin2SR, DAT, DRCT, SRFormer, SAFMN)");
     if (idx < 0 || idx >= (int)net->sw_ln.size()) return set_error(INNFER_ERR_INVALID, "set_layer_norm: index %d of %zu", idx, net->sw_ln.size());
     if (net->kind == 9) {        // DRCT: sw_ln_w[idx] floats each, already in the slab order of the tensor the norm reads (zeros at the hole and the pads)
         const size_t wdt = (size_t)net->sw_ln_w[idx];
@@ -904,6 +950,7 @@ extern "C" void innfer_net_destroy(innfer_net_t net) {
     for (float* q : net->hat_ca) if (q) (void)hipFree(q);
     for (float* q : net->dat_blk) if (q) (void)hipFree(q);
     for (float* q : net->sf_dw) if (q) (void)hipFree(q);
+    for (float* q : net->sm_mfr) if (q) (void)hipFree(q);
     for (auto& c : net->convs) {
         if (c.d_w) (void)hipFree(c.d_w);
         if (c.d_b) (void)hipFree(c.d_b);
@@ -970,6 +1017,12 @@ extern "C" int innfer_net_set_conv(innfer_net_t net, int idx, const float* w, co
         host.resize((size_t)c.C * 9 * c.K * sizeof(float));
         first_conv_layout(w, c.K, c.C, (float*)host.data());
         bias_n = c.K;
+    } else if (c.safm) {             // SAFMN's safm.aggr [dim, dim, 1, 1]: plain fp16 rows padded to the kernel's panel width (csrc/safm.hip)
+        const int kp = safm_kp(net->sw_cp);
+        host.resize((size_t)kp * kp * sizeof(f16));
+        std::vector<float> ab(kp);
+        safm_pack(w, b, c.K, kp, (f16*)host.data(), ab.data());
+        bias_n = (size_t)kp;
     } else if (c.plk) {              // RealPLKSR's lk.conv [16, 16, k, k]: the streamed [step][lane][8] panel of plk_conv.hip
         host.resize(plk_packed_bytes(c.ksize));
         plk_pack(w, c.ksize, host.data());
@@ -1070,6 +1123,7 @@ extern "C" int innfer_net_set_precision(innfer_net_t net, int fp32) {
     if (fp32 && net->kind == 8) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: DAT is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 9) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: DRCT is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32 && net->kind == 10) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SRFormer is built for the fp16 mode only (no fp32-accurate engine)");
+    if (fp32 && net->kind == 11) return set_error(INNFER_ERR_UNSUPPORTED, "set_precision: SAFMN is built for the fp16 mode only (no fp32-accurate engine)");
     if (fp32) {
         // The (wl | wh | wh) panels of every loaded conv are built HERE -- a load-time call, with its hipMalloc and synchronous copies -- never inside
         // innfer_net_forward (stream capture, concurrent callers).  Idempotent: a conv that already has its panels is skipped; innfer_net_set_conv
@@ -1153,6 +1207,12 @@ extern "C" double innfer_net_flops(innfer_net_t net, int N, int H, int W) {
     if (net->kind == 6) {        // HAT: as SwinIR on the grid padded to 16; 256 x 256 scores per window and head in a HAB, 256 x 576 in an OCAB
         const double px = (double)N * ((H + 15) / 16 * 16) * ((W + 15) / 16 * 16);
         double f = net->sw_nh * (px / 256) * 4.0 * 256 * 32 * (256.0 * net->nb + 576.0 * net->sw_depths.size());
+        for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
+        return f;
+    }
+    if (net->kind == 11) {       // SAFMN: every conv on H x W (safm.aggr among them), nine taps per channel on the four pooled grids (at most 1 + 1/4 + 1/16 + 1/64 of a grid each)
+        const double px = (double)N * H * W;
+        double f = (double)net->nb * 18.0 * (net->sw_c / 4) * px * (1.0 + 0.25 + 0.0625 + 0.015625);
         for (auto& c : net->convs) f += 2.0 * c.ksize * c.ksize * c.K * c.C * px * c.mult;
         return f;
     }
@@ -1280,6 +1340,17 @@ static Carve carve(const innfer_net* net, int N, int H, int W) {
         c.slab_w = net->nf;
         c.slab[0] = off; off += al(px * net->nf * 2);
         c.slab[1] = off; if (net->nb > 0) off += al(px * net->nf * 2);
+        c.hr = off; off += al(px * net->convs.back().Kp * 2);
+        c.total = off;
+        return c;
+    }
+    if (net->kind == 11) {       // SAFMN: to_feat's result (the global skip), the token stream t, the normalised tokens u, the feed-forward's hidden slab, to_img.0's slab
+        size_t off = 0;
+        c.slab_w = net->sw_cp;
+        c.fea = off; off += al(px * net->sw_cp * 2);
+        c.slab[0] = off; off += al(px * net->sw_cp * 2);
+        c.slab[1] = off; off += al(px * net->sw_cp * 2);
+        c.slab[2] = off; off += al(px * net->sw_hp * 2);
         c.hr = off; off += al(px * net->convs.back().Kp * 2);
         c.total = off;
         return c;
@@ -2172,6 +2243,72 @@ static int swinir_forward(innfer_net* net, const void* d_in, int in_dtype, void*
     return INNFER_OK;
 }
 
+// SAFMN (kind 11) on H x W itself (no pad: the pooled grids are torch's for any size >= 8).  S1 = C_pad / 64, SH = hidden_pad / 64:
+//   to_feat (S1 first-conv launches) -> f0;  per block  u = LN(t) (eps 1e-6);  t = t + GELU(aggr(..) + b) * u (ONE launch, csrc/safm.hip; block 0 reads f0 and writes t);
+//   u = LN(t);  hid = GELU(ccm.0(u)) (SH launches, act 13);  t = ccm.2(hid) + t (S1 launches, in place);  u = t + f0 (one pass);  to_img.0 -> the tail slab;  PixelShuffle
+//   as shuffle_add_launch's store.  S1 + nb (3 + SH + S1) + 3 launches.
+int safmn_forward(innfer_net* net, const void* d_in, int in_dtype, void* d_out, int out_dtype, int N, int H, int W, char* ws, const Carve& cv, hipStream_t s) {
+    if (in_dtype == INNFER_F32 || net->fp32) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SAFMN is built for the fp16 mode only: fp16 or uint8 input");
+    if (net->outm || net->final_act) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SAFMN has no outm / final activation");
+    if (in_dtype == INNFER_U8 && !net->u8_round16) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SAFMN is built for the fp16 mode only (innfer_net_set_u8_io fp16_mode = 1)");
+    if (H < 8 || W < 8) return set_error(INNFER_ERR_UNSUPPORTED, "forward: SAFMN pools down to (H >> 3) x (W >> 3): both sides must be at least 8, got %d x %d", H, W);
+    for (size_t i = 0; i < net->sw_ln.size(); ++i)
+        if (!net->sw_ln[i]) return set_error(INNFER_ERR_INVALID, "forward: the parameters of LayerNorm %zu were never set (innfer_net_set_layer_norm)", i);
+    for (size_t i = 0; i < net->sm_mfr.size(); ++i)
+        if (!net->sm_mfr[i]) return set_error(INNFER_ERR_INVALID, "forward: the depthwise convs of block %zu were never set (innfer_net_set_safm)", i);
+    const int cp = net->sw_cp, dim = net->sw_c;
+    const long npx = (long)N * H * W, G = npx * 32;
+    const double px = (double)npx;
+    f16 *f0 = (f16*)(ws + cv.fea), *t = (f16*)(ws + cv.slab[0]), *u = (f16*)(ws + cv.slab[1]), *hid = (f16*)(ws + cv.slab[2]), *tail = (f16*)(ws + cv.hr);
+    int ci = 0;
+    auto norm = [&](int idx, const f16* in, f16* out) {
+        return plksr_pass(s, "layer_norm", 8.0 * dim * px, px * cp * 4.0, 8000,
+                          [&] { return layer_norm_launch(in, G, out, G, npx, dim, cp, net->sw_ln[idx], net->sw_ln[idx] + cp, 1e-6f, s); });
+    };
+    auto sliced = [&](int nslices, const f16* in, f16* out, int act, const f16* res) {
+        for (int p = 0; p < nslices; ++p) {
+            const ConvSlot& cs = net->convs[ci++];
+            ConvLaunch L = mk_launch(cs, in, G, out + 2L * p * G, G, N, H, W, act, 0);
+            if (res) { L.res1 = res + 2L * p * G; L.res1_gstride = G; L.s1 = 1.f; }
+            if (int rc = do_conv(L, s)) return rc;
+        }
+        return (int)INNFER_OK;
+    };
+    for (int p = 0; p < cp / 64; ++p) {
+        const ConvSlot& c0 = net->convs[ci++];
+        FirstConvLaunch F{};
+        F.in = d_in; F.in_f32 = 0; F.Cin = c0.C; F.w = (const float*)c0.d_w; F.bias = c0.d_b;
+        F.in_u8 = in_dtype == INNFER_U8; F.in_norm = net->u8_normalize; F.in_round16 = 1;
+        F.out = f0 + 2L * p * G; F.out_gstride = G;
+        F.K = 64; F.N = N; F.H = H; F.W = W; F.act = 0;
+        if (int rc = do_first(F, s)) return rc;
+    }
+    for (int b = 0; b < net->nb; ++b) {
+        const f16* x = b == 0 ? f0 : t;
+        if (int rc = norm(2 * b, x, u)) return rc;
+        const ConvSlot& ag = net->convs[ci++];
+        // launch kind 8014: the feature modulation -- bytes: u and t in, t out
+        if (int rc = plksr_pass(s, "safm", (2.0 * dim * dim + 18.0 * dim) * px, 6.0 * cp * px, 8014, [&] {
+                return safm_launch(u, G, x, G, t, G, N, H, W, dim, cp, (const f16*)ag.d_w, ag.d_b, net->sm_mfr[b], s); })) return rc;
+        if (int rc = norm(2 * b + 1, t, u)) return rc;
+        if (int rc = sliced(net->sw_hp / 64, u, hid, 13, nullptr)) return rc;
+        if (int rc = sliced(cp / 64, hid, t, 0, t)) return rc;
+    }
+    // launch kind 8015: the global skip -- bytes: two slabs in, one out
+    if (int rc = plksr_pass(s, "slab_add", px * cp, 6.0 * cp * px, 8015, [&] { return slab_add_launch(t, f0, u, (long)(cp / 32) * G, s); })) return rc;
+    const ConvSlot& cl = net->convs[ci++];
+    ConvLaunch L = mk_launch(cl, u, G, tail, G, N, H, W, 0, 0);
+    L.K = cl.Kp;
+    if (int rc = do_conv(L, s)) return rc;
+    const int omode = out_dtype == INNFER_U8 ? 2 : out_dtype == INNFER_F32 ? 1 : 0;
+    ShuffleAddLaunch T{};
+    T.slab = tail; T.gstride = G; T.base = nullptr;
+    T.out = d_out; T.out_mode = omode; T.out_denorm = net->u8_normalize;
+    T.C = net->out_nc; T.s = net->scale; T.N = N; T.H = H; T.W = W;
+    const double k = (double)cl.K;
+    return plksr_pass(s, "shuffle (SAFMN tail)", 0.0, px * (k * 2.0 + k * (omode == 2 ? 1.0 : omode == 1 ? 4.0 : 2.0)), 6000, [&] { return shuffle_add_launch(T, s); });
+}
+
 // Launch a dependent chain of same-resolution convs.  band_rows == 0: one launch per
 // layer over the whole frame.  band_rows > 0: skewed row bands -- layer l of band b
 // covers rows [b*R - l, (b+1)*R - l), so every row a layer reads from its predecessor
@@ -2222,6 +2359,7 @@ extern "C" int innfer_net_forward(innfer_net_t net, const void* d_in, int in_dty
     if (net->kind == 2) return compact_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 3) return span_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     if (net->kind == 4) return plksr_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
+    if (net->kind == 11) return safmn_forward(net, d_in, in_dtype, d_out, out_dtype, N, H, W, ws, cv, s);
     const int nf = net->nf, gc = net->gc;
     const long G = (long)N * H * W * 32;          // group stride of every LR-resolution slab
     const long LO = (long)(cv.lo / 2);            // fp32-accurate mode: elements from a slab to its lo twin (0: fp16 mode)

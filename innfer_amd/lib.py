@@ -237,6 +237,10 @@ SIGNATURES = {
     "innfer_net_set_dwconv5": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "innfer_window_attention_perm": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p] + [C.c_int] * 7 + [C.c_void_p]),
     "innfer_dwconv5x5_gelu_add": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (124, additive) SAFMN
+    "innfer_safmn_create": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 6),
+    "innfer_net_set_safm": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "innfer_safm": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_int] * 5 + [C.c_void_p] * 5),
     "innfer_dat_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 8 + [C.c_void_p, C.c_void_p]),
     "innfer_dat_block_floats": (C.c_size_t, [C.c_void_p]),
     "innfer_net_set_dat_block": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),

@@ -31,6 +31,7 @@ _SNIFF = (
     ('layers.0.residual_group.blocks.0.norm1.weight', 'swinir'),      # SwinIR and what builds on its skeleton (with conv_first.weight): ahead of the new-arch probe
     ('before_RG.1.weight', 'dat'),                   # DAT (with conv_first.weight and block 0's complete key set, _DAT_KEYS): ahead of the new-arch probe
     ('layers.0.swin1.norm1.weight', 'drct'),         # DRCT (with conv_first.weight and dense group 0's complete key set, _DRCT_KEYS): ahead of the new-arch probe
+    ('to_feat.weight', 'safmn'),                     # SAFMN (with block 0's complete key set, _SAFMN_KEYS)
     ('conv_first.weight', 'mesrgan'),
     ('model.0.weight', 'esrgan'),
     ('CFEM.0.weight', 'ppon'),
@@ -49,7 +50,8 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
     for probe, arch in _SNIFF:
         if probe in state_dict and (arch != 'realesrgan' or 'conv_first.weight' in state_dict) and (arch != 'span' or 'conv_cat.weight' in state_dict) and \
                 (arch != 'realplksr' or 'feats.1.channel_mixer.0.weight' in state_dict) and (arch != 'swinir' or 'conv_first.weight' in state_dict) and \
-                (arch != 'dat' or all(k in state_dict for k in _DAT_KEYS)) and (arch != 'drct' or all(k in state_dict for k in _DRCT_KEYS)):
+                (arch != 'dat' or all(k in state_dict for k in _DAT_KEYS)) and (arch != 'drct' or all(k in state_dict for k in _DRCT_KEYS)) and \
+                (arch != 'safmn' or all(k in state_dict for k in _SAFMN_KEYS)):
             break
     else:
         raise Exception("Could not infer model parameters.")
@@ -74,6 +76,8 @@ def infer_from_state_dict(state_dict, scale=None, in_nc=3, out_nc=3):
         return s2 if s2 is not None else _infer_swinir(state_dict)
     if arch == 'dat':
         return _infer_dat(state_dict)
+    if arch == 'safmn':
+        return _infer_safmn(state_dict)
     if arch == 'drct':
         return _infer_drct(state_dict)
     if arch == 'pan':
@@ -359,6 +363,42 @@ def _infer_srformer(state_dict):
            'upsampler': upsampler, 'resi_connection': '3conv' if 'layers.0.conv.0.weight' in state_dict else '1conv'}
     return dict(arch='srformer', scale=up, in_nc=in_nc, out_nc=in_nc, nf=C, nb=sum(depths), plus=False, state_dict=state_dict,
                 net_params=get_network_G_config(cfg, up))
+
+
+_SAFMN_KEYS = tuple(f'feats.0.{k}.{leaf}' for k in ('norm1', 'norm2', 'safm.mfr.0', 'safm.mfr.1', 'safm.mfr.2', 'safm.mfr.3', 'safm.aggr', 'ccm.ccm.0', 'ccm.ccm.2')
+                    for leaf in ('weight', 'bias')) + ('to_feat.bias', 'to_img.0.weight', 'to_img.0.bias')
+
+
+def _infer_safmn(state_dict):
+    """SAFMN checkpoints (SAFMN, SAFMN-L and fine-tunes).  Everything is read off the shapes: dim and in_chans from to_feat, the blocks by counting, hidden from ccm.ccm.0,
+    the scale as the square root of to_img.0's rows over in_chans; the levels by counting block 0's safm.mfr entries -- anything but four is refused here, before anything
+    touches the GPU."""
+    import math
+    w0 = state_dict['to_feat.weight']
+    dim, in_nc = int(w0.shape[0]), int(w0.shape[1])
+    levels = 0
+    while f'feats.0.safm.mfr.{levels}.weight' in state_dict:
+        levels += 1
+    if levels != 4:
+        raise NotImplementedError(f'SAFMN checkpoint with {levels} feature-modulation levels (safm.mfr.0 .. {levels - 1}): four are built on the HIP path')
+    if dim % 4 or not 8 <= dim <= 256:
+        raise NotImplementedError(f'SAFMN checkpoint with dim {dim} (built on the HIP path: a multiple of 4 in 8 .. 256)')
+    nb = 0
+    while f'feats.{nb}.norm1.weight' in state_dict:
+        nb += 1
+    hidden = int(state_dict['feats.0.ccm.ccm.0.weight'].shape[0])
+    if not 1 <= hidden <= 1024:
+        raise NotImplementedError(f'SAFMN checkpoint with a feed-forward of {hidden} hidden channels (built on the HIP path: <= 1024)')
+    if not 1 <= in_nc <= 4:
+        raise NotImplementedError(f'SAFMN checkpoint with {in_nc} input channels (built on the HIP path: 1 .. 4)')
+    rows = int(state_dict['to_img.0.weight'].shape[0])
+    up = math.isqrt(rows // in_nc) if rows % in_nc == 0 else 0
+    if up * up * in_nc != rows:
+        raise NotImplementedError(f'SAFMN checkpoint: to_img.0 has {rows} channels, not in_chans ({in_nc}) times a square (unequal channel counts are not built on the HIP path)')
+    if not 1 <= up <= 4:
+        raise NotImplementedError(f'SAFMN checkpoint with scale {up} (built on the HIP path: 1 .. 4)')
+    cfg = {'type': 'safmn', 'in_nc': in_nc, 'nf': dim, 'nb': nb, 'ffn_scale': hidden / dim, 'scale': up}
+    return dict(arch='safmn', scale=up, in_nc=in_nc, out_nc=in_nc, nf=dim, nb=nb, plus=False, state_dict=state_dict, net_params=get_network_G_config(cfg, up))
 
 
 _SWIN2SR_KEYS = ('attn.logit_scale', 'attn.cpb_mlp.0.weight', 'attn.cpb_mlp.0.bias', 'attn.cpb_mlp.2.weight', 'attn.q_bias', 'attn.v_bias', 'attn.qkv.weight', 'norm1.weight',

@@ -235,6 +235,14 @@ def get_network_G_config(network_G, scale):
         cfg['upsampler'] = _pick(opts, 'upsampler', 'pixelshuffle')
         cfg['resi_connection'] = _pick(opts, 'resi_connection', '1conv')
         opts.pop('out_nc', None)
+    elif kind in ('safmn', 'safmn_net'):                   # SAFMN (feature modulation blocks, pixelshuffledirect tail): the published constructor names
+        cfg['type'] = 'safmn'
+        cfg['dim'] = _pick(opts, 'nf', 36)
+        cfg['n_blocks'] = _pick(opts, 'nb', 8)
+        cfg['ffn_scale'] = _pick(opts, 'ffn_scale', 2.0)
+        cfg['upscaling_factor'] = _pick(opts, 'scale', scale)
+        cfg['in_chans'] = _pick(opts, 'in_nc', 3)
+        opts.pop('out_nc', None)
     else:
         raise NotImplementedError(f'Generator model [{kind:s}] not recognized')
 
